@@ -17,9 +17,18 @@ no stage completes for GHF_BENCH_STEP_TIMEOUT seconds (default 180) -- a collect
 until the driver's limit.
 
 Rank 0 prints ONE JSON line.  `value` = input GB (1e9 B) pushed through encode+decode per second by the
-whole job.  `roofline` prices the dominant kernel against HBM peak; `cpu_baseline` is the reference's
-own code (oracle/_ref, built from /root/reference in the build container) timed on this host, pinned to one
-core.  `configs` (N=1) holds the other single-GPU BASELINE configs at their full 4 GiB size.
+whole job; `ms_per_step` = wall milliseconds of one timed step.  A plain run does only that: set-up, one pass over
+the buffer sets, the warm-up, the timed steps, the outputs (--dump-outputs) and the line.
+
+--full adds what takes runs of its own or checks the results: the byte-for-byte round trips of every buffer set after
+each phase, `stage_ms_alone` and `roofline` (the dominant kernel priced against HBM peak, one kernel at a time),
+`single_buffer_ms`, `decode_foreign`, `cpu_baseline` (the reference's own code, oracle/_ref, built by `make -C oracle
+ref` where the reference tree exists, timed on this host, pinned to one core), `configs` (N=1: the other single-GPU
+BASELINE configs at their full 4 GiB size), and at N>1 the same shard on one GPU alone and the one-call
+ghf_encode_sharded check.
+
+--dump-outputs DIR writes what the last timed step computed (encoded stream, its length, the code, decoded bytes) as
+DIR/<name>.npy in float32 / float64; the inputs are the same from run to run, so two builds compare output for output.
 """
 import argparse
 import json
@@ -43,10 +52,16 @@ def parse():
     ap.add_argument("--kind", default="uniform", choices=["uniform", "zipf", "sym16"])
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="gloo = rehearsal of the N>1 control flow with several ranks on ONE GPU (collectives staged via host)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-verify", action="store_true")
-    ap.add_argument("--no-configs", action="store_true", help="skip the 4 GiB configs block (N=1)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the checks and the extra measurements (round trips, per-kernel pass, roofline, configs, cpu_baseline, ...)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs to DIR/<name>.npy (float32 / float64, ~33 MB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip cpu_baseline")
+    ap.add_argument("--no-verify", action="store_true", help="(--full) skip the round-trip checks")
+    ap.add_argument("--no-configs", action="store_true", help="(--full) skip the 4 GiB configs block (N=1)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.mib is None:
         args.mib = 256 if int(os.environ.get("WORLD_SIZE", "1")) == 1 else 4096
     return args
@@ -181,6 +196,43 @@ def full_size_config(torch, ghf, synth, ctx, kind, mib, reps=5):
     del d_in, out, dec
     torch.cuda.empty_cache()
     return res
+
+
+DUMP_SAMPLE = 1 << 22  # positions per long byte array (float32: 16 MB), split over the ranks
+DUMP_HEAD = 1 << 16  # leading bytes kept whole (the .crs2 header is 1064 B)
+DUMP_BLOCK = 1 << 20  # block of the per-block sums that cover every byte
+DUMP_SEED = 20240601
+
+
+def dump_outputs(torch, ctx, dirname, b, d_code, d_nbytes, world, rank):
+    """what a caller of the timed path got from its last step -- the encoded stream and its length, the code it was
+    written with, the decoded bytes and their count -- as DIR/<name>.npy.  The two long byte arrays go out as their head,
+    a fixed seeded sample of positions, and per-block plain and position-weighted sums that cover every byte."""
+    import numpy as np
+
+    os.makedirs(dirname, exist_ok=True)
+    sfx = "" if world == 1 else "_rank%d" % rank
+    nb, nd = int(b.end[1].item()), int(d_nbytes.item())
+    code = ctx.code_to_host(d_code)
+    arrays = {"compressed_nbytes": np.array([nb], dtype=np.float64), "decoded_nbytes": np.array([nd], dtype=np.float64),
+              "code_length": np.array(list(code.length), dtype=np.float32),
+              "code_codeword": np.array(list(code.codeword), dtype=np.float64)}
+    w = torch.arange(1, DUMP_BLOCK + 1, dtype=torch.int64, device=b.out.device)
+    for name, t, m in (("compressed", b.out, nb), ("decoded", b.dec, nd)):
+        m = min(m, t.numel())  # (never gather past the buffer, whatever the count says)
+        t = t[:m]
+        arrays[name + "_head"] = t[:DUMP_HEAD].float().cpu().numpy()
+        pos = np.sort(np.random.default_rng(DUMP_SEED + rank).integers(0, max(m, 1), size=min(m, DUMP_SAMPLE // world)))
+        arrays[name + "_sample"] = t[torch.from_numpy(pos).to(t.device)].float().cpu().numpy()
+        sums, wsums = [], []
+        for q in range(0, m, DUMP_BLOCK):  # (weighted sums < 255 * 2^39: exact in float64)
+            blk = t[q : q + DUMP_BLOCK].to(torch.int64)
+            sums.append(blk.sum())
+            wsums.append((blk * w[: blk.numel()]).sum())
+        arrays[name + "_block_sums"] = torch.stack(sums).double().cpu().numpy() if sums else np.zeros(0)
+        arrays[name + "_block_wsums"] = torch.stack(wsums).double().cpu().numpy() if wsums else np.zeros(0)
+    for k, a in arrays.items():
+        np.save(os.path.join(dirname, k + sfx + ".npy"), a)
 
 
 class Watchdog:
@@ -492,15 +544,15 @@ def main():
     def verify_sets(what):
         torch.cuda.synchronize()
         for cx in ctxs:
-            cx.sync()
-        if not args.no_verify:
+            cx.sync()  # raises if any stage latched an error (every run); the byte comparison is --full's
+        if args.full and not args.no_verify:
             for si, b in enumerate(sets):
                 assert bool((b.dec[:n] == b.d_in).all().item()), "round trip mismatch (%s, buffer set %d)" % (what, si)
 
     extra = {}
     # ---- N > 1, before any communicator exists: the SAME shard on this GPU alone, same pipeline, no collectives.  The
     # speed-up of the N-GPU run is quoted against this number (same bytes per GPU), never against the 256 MiB N = 1 line.
-    if world > 1:
+    if world > 1 and args.full:
         solo = Run(False, None)
         solo.run(NSETS, False)
         verify_sets("same shard, this GPU alone")
@@ -547,7 +599,7 @@ def main():
         extra["shard_output_bytes"] = {"per_buffer_set": exact, "static_bound": bound, "sized_by": "ghf_shard_bytes(all-gathered totals) after the first pass"}
         job.run(NSETS, False)
         verify_sets("sharded pipeline, exact outputs")
-    if world > 1 and comms:
+    if world > 1 and comms and args.full:
         # one step through the ONE-CALL entry point (ghf_encode_sharded: K1 -> all-reduce -> K2/K3 -> K4 -> all-gather -> K5 on
         # one stream): its bytes must equal what the staged calls above wrote for the same shard, and decode back
         wd.enter("ghf_encode_sharded (verified step)")
@@ -611,30 +663,20 @@ def main():
         cx.sync()
         return {k: sum(a.elapsed_time(z) for a, z in v) / len(v) for k, v in acc.items()}
 
-    wd.enter("per-kernel pass")
-    stage_alone = alone_ms()
-    verify_sets("per-kernel pass")
+    if args.dump_outputs:
+        wd.enter("dump of the outputs")
+        last = args.steps - 1  # (its buffer set and its code slot: nothing ran behind it)
+        dump_outputs(torch, ctx, args.dump_outputs, sets[last % NSETS], codes[last % DEPTH], t_nbytes, world, rank)
+    if args.full:
+        wd.enter("per-kernel pass")
+        stage_alone = alone_ms()
+        verify_sets("per-kernel pass")
     wd.enter("done")
 
     if rank == 0:
         ms_per_step = elapsed * 1e3 / args.steps
         total_in = n * world
         value = total_in * args.steps / elapsed / 1e9
-        enc_ms = sum(stage_alone.get(k, 0.0) for k in names[:7])  # un-overlapped sum of the encode stages
-        # roofline of the dominant kernel (algorithmic bytes): emit reads N and writes the body,
-        # decode reads C and writes N, histogram reads N
-        cand = {"k_emit": (n + comp_bytes, stage_alone["emit"]), "k_decode": (comp_bytes + n, stage_alone["decode"]),
-                "k_histogram": (n, stage_alone["histogram"])}
-        dom = max(cand, key=lambda k: cand[k][1])
-        ach = cand[dom][0] / (cand[dom][1] * 1e-3) / 1e9
-        traffic = None
-        tf = os.path.join(ROOT, "profiles", "traffic.json")
-        if os.path.exists(tf):
-            try:
-                traffic = json.load(open(tf)).get("%s_%s_%dMiB" % (dom, args.kind, args.mib))
-            except Exception:
-                traffic = None
-        probes = copy_probe(torch, ctx, sets[0].d_in, sets[0].dec)
         cfg4 = world > 1 and args.kind == "uniform" and args.mib == 4096
         res = {
             "metric": "encode+decode GB/s (input bytes)", "value": round(value, 3), "unit": "GB/s", "n_gpus": world,
@@ -649,23 +691,42 @@ def main():
                        "pipeline": "steps software-pipelined, up to %d in flight (one ghf context each, %d side stream(s)), rotating over %d sets of {input, output, decoded, side-car} buffers: main stream = histogram of step i+%d, emit + decode of step i%s; side stream(s), ahead of the main one = histogram all-reduce, one-wave code build, chunk pricing, decode tables, offset all-gather.  stage_ms = events inside the timed region (kernels of different streams share the GPU); stage_ms_alone and roofline = a separate pass behind it, one kernel at a time" % (DEPTH, NSIDE, NSETS, DEPTH - 1, " (even and odd steps on two main streams)" if NMAIN > 1 else "")},
             "main_streams": NMAIN,
             "host_enqueue_ms_per_front": round(job.host_front_s * 1e3 / max(job.host_fronts, 1), 4),
-            "encode_GBps": round(n * world / (enc_ms * 1e-3) / 1e9, 3), "decode_GBps": round(n * world / (stage_alone["decode"] * 1e-3) / 1e9, 3),
             "stage_ms": {k: round(v, 4) for k, v in stage_ms.items()},
-            "stage_ms_alone": {k: round(v, 4) for k, v in stage_alone.items()},
-            "roofline": {"bound": "hbm", "kernel": dom, "achieved": round(ach, 1), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
-                         "frac": round(ach / HBM_PEAK_GBPS, 4), "traffic": traffic,
-                         "traffic_source": "profiles/traffic.json (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this workload, builder-run, corrected as the guide prescribes; not measured in this run)" if traffic is not None else None,
-                         "algorithmic_bytes_per_launch": cand[dom][0], "avg_launch_ms": round(cand[dom][1], 4),
-                         "timed_by": "HIP events on the kernel's stream around each of 20 launches, one kernel on the GPU at a time, right behind the timed region (stage_ms_alone); the same kernel inside the timed region, sharing the GPU with the other stream's kernels: %.4f ms (stage_ms)" % stage_ms[{"k_emit": "emit", "k_decode": "decode", "k_histogram": "histogram"}[dom]],
-                         "all_kernels": {k: {"achieved": round(v[0] / (v[1] * 1e-3) / 1e9, 1), "frac": round(v[0] / (v[1] * 1e-3) / 1e9 / HBM_PEAK_GBPS, 4)}
-                                         for k, v in cand.items() if v[1] > 0}},
+            "full": bool(args.full),
             "library": ghf.lib_identity(),
         }
-        res["roofline"].update(probes)
+        if args.full:
+            enc_ms = sum(stage_alone.get(k, 0.0) for k in names[:7])  # un-overlapped sum of the encode stages
+            # roofline of the dominant kernel (algorithmic bytes): emit reads N and writes the body,
+            # decode reads C and writes N, histogram reads N
+            cand = {"k_emit": (n + comp_bytes, stage_alone["emit"]), "k_decode": (comp_bytes + n, stage_alone["decode"]),
+                    "k_histogram": (n, stage_alone["histogram"])}
+            dom = max(cand, key=lambda k: cand[k][1])
+            ach = cand[dom][0] / (cand[dom][1] * 1e-3) / 1e9
+            traffic = None
+            tf = os.path.join(ROOT, "profiles", "traffic.json")
+            if os.path.exists(tf):
+                try:
+                    traffic = json.load(open(tf)).get("%s_%s_%dMiB" % (dom, args.kind, args.mib))
+                except Exception:
+                    traffic = None
+            probes = copy_probe(torch, ctx, sets[0].d_in, sets[0].dec)
+            res["encode_GBps"] = round(n * world / (enc_ms * 1e-3) / 1e9, 3)
+            res["decode_GBps"] = round(n * world / (stage_alone["decode"] * 1e-3) / 1e9, 3)
+            res["stage_ms_alone"] = {k: round(v, 4) for k, v in stage_alone.items()}
+            res["roofline"] = {
+                "bound": "hbm", "kernel": dom, "achieved": round(ach, 1), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
+                "frac": round(ach / HBM_PEAK_GBPS, 4), "traffic": traffic,
+                "traffic_source": "profiles/traffic.json (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this workload, run separately, corrected as the guide prescribes; not measured in this run)" if traffic is not None else None,
+                "algorithmic_bytes_per_launch": cand[dom][0], "avg_launch_ms": round(cand[dom][1], 4),
+                "timed_by": "HIP events on the kernel's stream around each of 20 launches, one kernel on the GPU at a time, right behind the timed region (stage_ms_alone); the same kernel inside the timed region, sharing the GPU with the other stream's kernels: %.4f ms (stage_ms)" % stage_ms[{"k_emit": "emit", "k_decode": "decode", "k_histogram": "histogram"}[dom]],
+                "all_kernels": {k: {"achieved": round(v[0] / (v[1] * 1e-3) / 1e9, 1), "frac": round(v[0] / (v[1] * 1e-3) / 1e9 / HBM_PEAK_GBPS, 4)}
+                                for k, v in cand.items() if v[1] > 0}}
+            res["roofline"].update(probes)
         res.update(extra)
         if "same_shard_1gpu_ms_per_step" in extra:
             res["speedup_vs_same_shard"] = round(world * extra["same_shard_1gpu_ms_per_step"] / ms_per_step, 3)
-        if world == 1:
+        if world == 1 and args.full:
             # ONE buffer, nothing overlapped: every stage of encode + decode back to back on one stream (the latency a caller
             # with a single buffer sees; `value` above is the throughput of the pipelined job)
             cx, b = ctxs[0], sets[0]
@@ -716,7 +777,7 @@ def main():
                 res["config"]["rccl_version"] = ".".join(str(x) for x in torch.cuda.nccl.version())
             except Exception:
                 pass
-        if world == 1 and not args.no_configs:
+        if world == 1 and args.full and not args.no_configs:
             # the other single-GPU BASELINE configs at full size: 4 GiB uniform (north star: encode read side), configs[2]
             # (4 GiB Zipf encode) and configs[4] (4 GiB 16-symbol decode); every number has its stage times beside it
             host_in = sets[0].d_in.cpu().numpy() if not args.no_cpu_baseline else None
@@ -733,8 +794,8 @@ def main():
                     blk[key] = {"error": repr(e)[:200]}
             res["configs"] = blk
         else:
-            host_in = sets[0].d_in.cpu().numpy() if (world == 1 and not args.no_cpu_baseline) else None
-        if world == 1 and not args.no_cpu_baseline:
+            host_in = sets[0].d_in.cpu().numpy() if (world == 1 and args.full and not args.no_cpu_baseline) else None
+        if world == 1 and args.full and not args.no_cpu_baseline:
             res["cpu_baseline"] = cpu_baseline(host_in, args.kind)
         print(json.dumps(res), flush=True)
     wd.close()

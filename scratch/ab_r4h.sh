@@ -9,9 +9,9 @@ timeout -k 10 400 python3 scratch/k_ab.py --mib 256,4096 --kinds uniform,zipf --
 cat $O/k5pro.txt
 timeout -k 10 900 python3 -m pytest tests -m gpu -x -q > $O/gpu_tests.log 2>&1 || { tail -30 $O/gpu_tests.log; exit 1; }
 tail -2 $O/gpu_tests.log
-timeout -k 10 400 python3 bench.py > $O/bench.json 2> $O/bench.err || exit 1
-timeout -k 10 200 python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-configs > $O/bench20_a.json 2> $O/bench20_a.err || exit 1
-timeout -k 10 200 python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-configs > $O/bench20_b.json 2> $O/bench20_b.err || exit 1
+timeout -k 10 400 python3 bench.py --full > $O/bench.json 2> $O/bench.err || exit 1
+timeout -k 10 200 python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-configs > $O/bench20_a.json 2> $O/bench20_a.err || exit 1
+timeout -k 10 200 python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-configs > $O/bench20_b.json 2> $O/bench20_b.err || exit 1
 python3 - <<'P'
 import json
 for f in ("bench.json","bench20_a.json","bench20_b.json"):

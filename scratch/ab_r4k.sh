@@ -6,15 +6,15 @@ O=$R/gpurun_out/r4k
 mkdir -p $O
 cd $R
 for rep in 1 2 3; do
-  timeout -k 10 200 python3 bench.py --steps 200 --no-cpu-baseline --no-configs > $O/b256_shipped_$rep.json 2> $O/b256_shipped_$rep.err || exit 1
+  timeout -k 10 200 python3 bench.py --full --steps 200 --no-cpu-baseline --no-configs > $O/b256_shipped_$rep.json 2> $O/b256_shipped_$rep.err || exit 1
   timeout -k 10 200 python3 scratch/bench_with_lib2.py scratch/exp/libghf_k5nt.so --steps 200 --no-cpu-baseline --no-configs > $O/b256_k5nt_$rep.json 2> $O/b256_k5nt_$rep.err || exit 1
 done
 for kind in zipf sym16; do
-  timeout -k 10 200 python3 bench.py --steps 200 --kind $kind --no-cpu-baseline --no-configs > $O/b256${kind}_shipped_1.json 2> $O/b256${kind}_shipped_1.err || exit 1
+  timeout -k 10 200 python3 bench.py --full --steps 200 --kind $kind --no-cpu-baseline --no-configs > $O/b256${kind}_shipped_1.json 2> $O/b256${kind}_shipped_1.err || exit 1
   timeout -k 10 200 python3 scratch/bench_with_lib2.py scratch/exp/libghf_k5nt.so --steps 200 --kind $kind --no-cpu-baseline --no-configs > $O/b256${kind}_k5nt_1.json 2> $O/b256${kind}_k5nt_1.err || exit 1
 done
 for rep in 1 2; do
-  timeout -k 10 300 python3 bench.py --mib 4096 --steps 40 --warmup 2 --no-cpu-baseline --no-configs > $O/b4096_shipped_$rep.json 2> $O/b4096_shipped_$rep.err || exit 1
+  timeout -k 10 300 python3 bench.py --full --mib 4096 --steps 40 --warmup 2 --no-cpu-baseline --no-configs > $O/b4096_shipped_$rep.json 2> $O/b4096_shipped_$rep.err || exit 1
   timeout -k 10 300 python3 scratch/bench_with_lib2.py scratch/exp/libghf_k5nt.so --mib 4096 --steps 40 --warmup 2 --no-cpu-baseline --no-configs > $O/b4096_k5nt_$rep.json 2> $O/b4096_k5nt_$rep.err || exit 1
 done
 python3 - <<'P'

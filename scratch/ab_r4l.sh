@@ -7,7 +7,7 @@ mkdir -p $O
 cd $R
 timeout -k 10 400 python3 scratch/k_ab.py --mib 256,4096 --kinds uniform,zipf,sym16 --reps 60 shipped k7pro=scratch/exp/libghf_k7pro.so shipped2 k7pro2=scratch/exp/libghf_k7pro.so > $O/k_ab.txt 2> $O/k_ab.err || { tail -5 $O/k_ab.err; exit 1; }
 for rep in 1 2 3; do
-  timeout -k 10 200 python3 bench.py --steps 200 --no-cpu-baseline --no-configs > $O/b256_shipped_$rep.json 2> $O/b256_shipped_$rep.err || exit 1
+  timeout -k 10 200 python3 bench.py --full --steps 200 --no-cpu-baseline --no-configs > $O/b256_shipped_$rep.json 2> $O/b256_shipped_$rep.err || exit 1
   timeout -k 10 200 python3 scratch/bench_with_lib2.py scratch/exp/libghf_k7pro.so --steps 200 --no-cpu-baseline --no-configs > $O/b256_k7pro_$rep.json 2> $O/b256_k7pro_$rep.err || exit 1
 done
 python3 - <<'P'

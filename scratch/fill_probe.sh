@@ -7,10 +7,10 @@ mkdir -p $O
 cd $R
 for kind in uniform sym16 zipf; do
   for rep in 1 2 3; do
-    timeout -k 10 200 python3 bench.py --kind $kind --steps 20 --warmup 5 --no-cpu-baseline --no-configs > $O/${kind}_20_$rep.json 2> $O/${kind}_20_$rep.err || exit 1
+    timeout -k 10 200 python3 bench.py --full --kind $kind --steps 20 --warmup 5 --no-cpu-baseline --no-configs > $O/${kind}_20_$rep.json 2> $O/${kind}_20_$rep.err || exit 1
   done
-  timeout -k 10 200 python3 bench.py --kind $kind --steps 200 --no-cpu-baseline --no-configs > $O/${kind}_200_1.json 2> $O/${kind}_200_1.err || exit 1
-  timeout -k 10 200 python3 bench.py --kind $kind --steps 60 --warmup 5 --no-cpu-baseline --no-configs > $O/${kind}_60_1.json 2> $O/${kind}_60_1.err || exit 1
+  timeout -k 10 200 python3 bench.py --full --kind $kind --steps 200 --no-cpu-baseline --no-configs > $O/${kind}_200_1.json 2> $O/${kind}_200_1.err || exit 1
+  timeout -k 10 200 python3 bench.py --full --kind $kind --steps 60 --warmup 5 --no-cpu-baseline --no-configs > $O/${kind}_60_1.json 2> $O/${kind}_60_1.err || exit 1
 done
 python3 - <<'P'
 import json, glob

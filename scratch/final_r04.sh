@@ -25,7 +25,7 @@ step 200 $O/smoke.log python3 -c "import __graft_entry__ as g; g.smoke(); print(
 # the driver's command, four ramps of the look-ahead (RAMP0 fronts before the first emit), twice each, alternating
 for rep in 1 2; do
   for r0 in 3 5 7 4; do
-    GHF_BENCH_RAMP0=$r0 step 200 $O/bench20_ramp${r0}_$rep.json python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-configs
+    GHF_BENCH_RAMP0=$r0 step 200 $O/bench20_ramp${r0}_$rep.json python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-configs
   done
 done
 cd /tmp
@@ -35,7 +35,7 @@ for KIND in zipf sym16; do
   i=0
   for PMC in "FETCH_SIZE" "WRITE_SIZE" "$SQ1" "$SQ2"; do
     i=$((i+1))
-    step 300 $O/pmc_${KIND}_p$i.log rocprofv3 --kernel-trace --pmc $PMC --output-format csv -d $O/pmc_${KIND}_p$i -- python3 $R/bench.py --kind $KIND --steps 3 --warmup 1 --no-cpu-baseline --no-verify --no-configs
+    step 300 $O/pmc_${KIND}_p$i.log rocprofv3 --kernel-trace --pmc $PMC --output-format csv -d $O/pmc_${KIND}_p$i -- python3 $R/bench.py --full --kind $KIND --steps 3 --warmup 1 --no-cpu-baseline --no-verify --no-configs
   done
 done
 find $O -name '*kernel_trace.csv' -size +1M -delete

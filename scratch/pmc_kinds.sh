@@ -11,7 +11,7 @@ for KIND in zipf sym16; do
   i=0
   for PMC in "FETCH_SIZE" "WRITE_SIZE" "$SQ1" "$SQ2"; do
     i=$((i+1))
-    timeout -k 10 300 rocprofv3 --kernel-trace --pmc $PMC --output-format csv -d $O/${KIND}_p$i -- python3 $R/bench.py --kind $KIND --steps 3 --warmup 1 --no-cpu-baseline --no-verify --no-configs > $O/${KIND}_p$i.log 2>&1 || echo "pmc $KIND pass $i failed"
+    timeout -k 10 300 rocprofv3 --kernel-trace --pmc $PMC --output-format csv -d $O/${KIND}_p$i -- python3 $R/bench.py --full --kind $KIND --steps 3 --warmup 1 --no-cpu-baseline --no-verify --no-configs > $O/${KIND}_p$i.log 2>&1 || echo "pmc $KIND pass $i failed"
   done
 done
 find $O -name '*kernel_trace.csv' -size +1M -delete

@@ -24,9 +24,9 @@ for KIND in uniform zipf sym16; do
 done
 cd $R
 step 300 $O/foreign_times.txt python3 scratch/foreign_time.py
-GHF_BENCH_MAINS=1 step 200 $O/bench_one_main_stream.json python3 bench.py --steps 200 --no-configs --no-cpu-baseline
-GHF_BENCH_NSIDE=2 step 200 $O/bench_two_side_streams.json python3 bench.py --steps 200 --no-configs --no-cpu-baseline
-GHF_BENCH_NSIDE=1 step 200 $O/bench_one_side_stream.json python3 bench.py --steps 200 --no-configs --no-cpu-baseline
+GHF_BENCH_MAINS=1 step 200 $O/bench_one_main_stream.json python3 bench.py --full --steps 200 --no-configs --no-cpu-baseline
+GHF_BENCH_NSIDE=2 step 200 $O/bench_two_side_streams.json python3 bench.py --full --steps 200 --no-configs --no-cpu-baseline
+GHF_BENCH_NSIDE=1 step 200 $O/bench_one_side_stream.json python3 bench.py --full --steps 200 --no-configs --no-cpu-baseline
 step 300 $O/membench.txt ./scratch/membench
 step 600 $O/file_perf.log python3 scratch/file_perf.py 4 uniform zipf; cp gpurun_out/file_perf.json $O/file_perf.json
 step 300 $O/pipe_trace_reuse_uniform.log python3 scratch/file_trace_reuse.py uniform

@@ -8,12 +8,12 @@ cd $R
 for rep in 1 2 3; do
   for cfg in "0 3" "1 3" "1 7" "0 7" "1 5"; do
     set -- $cfg
-    GHF_BENCH_K1_STREAM=$1 GHF_BENCH_RAMP0=$2 timeout -k 10 200 python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-configs > $O/b20_k1s$1_ramp$2_$rep.json 2> $O/b20_k1s$1_ramp$2_$rep.err || exit 1
+    GHF_BENCH_K1_STREAM=$1 GHF_BENCH_RAMP0=$2 timeout -k 10 200 python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-configs > $O/b20_k1s$1_ramp$2_$rep.json 2> $O/b20_k1s$1_ramp$2_$rep.err || exit 1
   done
 done
 for cfg in "0 3" "1 3" "1 7"; do
   set -- $cfg
-  GHF_BENCH_K1_STREAM=$1 GHF_BENCH_RAMP0=$2 timeout -k 10 200 python3 bench.py --steps 200 --no-cpu-baseline --no-configs > $O/b200_k1s$1_ramp$2.json 2> $O/b200_k1s$1_ramp$2.err || exit 1
+  GHF_BENCH_K1_STREAM=$1 GHF_BENCH_RAMP0=$2 timeout -k 10 200 python3 bench.py --full --steps 200 --no-cpu-baseline --no-configs > $O/b200_k1s$1_ramp$2.json 2> $O/b200_k1s$1_ramp$2.err || exit 1
 done
 python3 - <<'P'
 import json, glob, collections

@@ -82,3 +82,38 @@ def _sparse(a):
 
 # small enough to commit the whole .crs2
 INLINE_CRS2 = {"aaaabbc", "aaaaaaaa", "single_x", "ab", "ff_1", "all256_once", "sym16_n1000", "zipf_n3001"}
+
+
+# ---- the random sweeps behind tests/golden/golden_sweeps.json (generator tests/golden/make_golden_sweeps.py): fresh
+# inputs beyond the named cases, on which the compiled reference's outputs were recorded.  -> list of (label, bytes)
+def sweep_crs2_inputs():
+    """40 inputs of 1..70000 bytes, four kinds; every fifth folded to a few distinct values (many exact ties)"""
+    out = []
+    for i in range(40):
+        kind = ["uniform", "zipf", "sym16", "text"][i % 4]
+        n = int(dg.splitmix64(np.uint64(1234 + i)) % np.uint64(70000)) + 1
+        data = dg.make(kind, n, seed=1000 + i)
+        if i % 5 == 0:
+            data = data % np.uint8(3 + i % 7)
+        out.append(("%d_%s_%d" % (i, kind, n), data))
+    return out
+
+
+def sweep_crs_inputs():
+    """`.crs`: 2..50000 bytes over k = 2..256 values with skewed random weights (inputs of fewer than 2 symbols dropped)"""
+    rng = np.random.default_rng(4242)
+    out = []
+    for case in range(24):
+        n = int(rng.integers(2, 50000))
+        k = int(rng.integers(2, 257))
+        w = rng.random(k) ** int(rng.integers(1, 6))
+        data = rng.choice(k, size=n, p=w / w.sum()).astype(np.uint8)
+        if np.count_nonzero(np.bincount(data, minlength=256)) < 2:
+            continue
+        out.append(("%d_n%d_k%d" % (case, n, k), data))
+    return out
+
+
+def limited_stream_input():
+    """14.9 MB of 33 Fibonacci counts: one bit too deep for the reference's encoder, so the stream is length-limited to 32"""
+    return dg.counts_to_bytes(dg.fib_counts(33), seed=5)

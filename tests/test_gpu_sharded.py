@@ -200,12 +200,12 @@ def test_encode_sharded_c_abi_world1_over_rccl():
         ctx.close()
 
 
-def _bench_two_ranks(extra_env=None, timeout=400):
+def _bench_two_ranks(extra_env=None, timeout=400, extra_args=()):
     import subprocess
 
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(29900 + os.getpid() % 90), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "2",
-           "--backend", "gloo", "--mib", "32"]
+           "--backend", "gloo", "--mib", "32"] + list(extra_args)
     env = dict(os.environ)
     env.update(extra_env or {})
     return subprocess.run(cmd, capture_output=True, text=True, timeout=timeout, env=env)
@@ -217,7 +217,7 @@ def test_bench_two_rank_rehearsal():
     two collectives through the host.  The RCCL run is the driver's."""
     import json
 
-    r = _bench_two_ranks()
+    r = _bench_two_ranks(extra_args=["--full"])  # (the same-shard run and the round-trip checks are --full's)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     line = [l for l in r.stdout.splitlines() if l.startswith("{")][-1]
     d = json.loads(line)

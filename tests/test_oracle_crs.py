@@ -2,19 +2,24 @@
 vectors the compiled reference produced (tests/golden/golden_crs.json, generator tests/golden/make_golden_crs.py)."""
 import base64
 import hashlib
+import json
 import os
-import tempfile
 
 import numpy as np
 import pytest
 
-from cases import CRS_CASES as CASES
+from cases import CRS_CASES as CASES, sweep_crs_inputs
 from oracle import oracle as orc
 import datagen as dg
 
 
 def sha(b):
     return hashlib.sha256(bytes(b)).hexdigest()
+
+
+def _sweeps():
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "golden_sweeps.json")) as f:
+        return json.load(f)
 
 
 @pytest.mark.parametrize("name", list(CASES))
@@ -64,25 +69,15 @@ def test_crs_oracle_rejects_what_the_reference_leaves_undefined():
         orc.crs_decompress(bad)
 
 
-@pytest.mark.ref
-@pytest.mark.skipif(not orc.have_ref(), reason="compiled reference only exists in the build container")
 def test_crs_random_inputs_against_the_compiled_reference():
-    rng = np.random.default_rng(4242)
-    with tempfile.TemporaryDirectory(dir="/tmp") as td:
-        for case in range(24):
-            n = int(rng.integers(2, 50000))
-            k = int(rng.integers(2, 257))
-            w = rng.random(k) ** int(rng.integers(1, 6))
-            data = rng.choice(k, size=n, p=w / w.sum()).astype(np.uint8)
-            if np.count_nonzero(np.bincount(data, minlength=256)) < 2:
-                continue
-            fin, fcrs, fde = (os.path.join(td, "%d.%s" % (case, e)) for e in ("bin", "crs", "de"))
-            data.tofile(fin)
-            orc.ref_run(["nc", fin, fcrs])
-            ref = np.fromfile(fcrs, dtype=np.uint8)
-            mine = orc.crs_compress(data)
-            assert np.array_equal(ref, mine), (case, n, k)
-            mine.tofile(fcrs)
-            orc.ref_run(["nd", fcrs, fde])  # the reference reads what the oracle wrote
-            assert np.array_equal(np.fromfile(fde, dtype=np.uint8), data)
-            assert np.array_equal(orc.crs_decompress(ref), data)
+    """fresh random inputs: the oracle's .crs == what the compiled reference wrote (tests/golden/golden_sweeps.json,
+    generator tests/golden/make_golden_sweeps.py); the reference's decoder read those same bytes back to the input"""
+    recs = _sweeps()["crs"]
+    inputs = sweep_crs_inputs()
+    assert len(recs) == len(inputs) > 20
+    for (label, data), g in zip(inputs, recs):
+        assert g["label"] == label and data.size == g["n"] and sha(data) == g["input_sha256"], "input generator drifted"
+        mine = orc.crs_compress(data)
+        assert mine.size == g["ref_bytes"] and sha(mine) == g["ref_sha256"], label
+        assert g["ref_decoded_sha256"] == sha(data), label  # the reference reads what the oracle wrote
+        assert np.array_equal(orc.crs_decompress(mine), data), label

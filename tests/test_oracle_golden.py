@@ -2,19 +2,24 @@
 (tests/golden/golden.json, generator tests/golden/make_golden.py) -- every stage, bit-exact."""
 import base64
 import hashlib
+import json
 import os
-import tempfile
 
 import numpy as np
 import pytest
 
-from cases import CASES
+from cases import CASES, sweep_crs2_inputs
 from oracle import oracle as orc
 import datagen as dg
 
 
 def sha(b):
     return hashlib.sha256(bytes(b)).hexdigest()
+
+
+def _sweeps():
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "golden_sweeps.json")) as f:
+        return json.load(f)
 
 
 @pytest.mark.parametrize("name", list(CASES))
@@ -66,23 +71,14 @@ def test_oracle_rejects_what_the_reference_leaves_undefined():
         orc.build_code(h)
 
 
-@pytest.mark.ref
-@pytest.mark.skipif(not orc.have_ref(), reason="compiled reference only exists in the build container")
 def test_oracle_vs_compiled_reference_random_sweep():
-    """fresh random inputs (not in the fixtures): restatement == compiled reference, byte for byte."""
-    rng_seed = 1234
-    with tempfile.TemporaryDirectory(dir="/tmp") as td:
-        for i in range(40):
-            kind = ["uniform", "zipf", "sym16", "text"][i % 4]
-            n = int(dg.splitmix64(np.uint64(rng_seed + i)) % np.uint64(70000)) + 1
-            data = dg.make(kind, n, seed=1000 + i)
-            if i % 5 == 0:  # few distinct values -> many exact ties
-                data = data % np.uint8(3 + i % 7)
-            fin, fout, fde = (os.path.join(td, "x." + e) for e in ("bin", "crs2", "de"))
-            data.tofile(fin)
-            orc.ref_run(["c", fin, fout])
-            ref = np.fromfile(fout, dtype=np.uint8)
-            mine = orc.compress(data)
-            assert mine.size == ref.size and np.array_equal(mine, ref), (i, kind, n)
-            orc.ref_run(["d", fout, fde])
-            assert np.array_equal(np.fromfile(fde, dtype=np.uint8), orc.decompress(ref, cap=n + 8))
+    """fresh random inputs (not in the named cases): restatement == what the compiled reference wrote, byte for byte
+    (tests/golden/golden_sweeps.json, generator tests/golden/make_golden_sweeps.py), and both decoders agree."""
+    recs = _sweeps()["crs2"]
+    inputs = sweep_crs2_inputs()
+    assert len(recs) == len(inputs) == 40
+    for (label, data), g in zip(inputs, recs):
+        assert g["label"] == label and data.size == g["n"] and sha(data) == g["input_sha256"], "input generator drifted"
+        mine = orc.compress(data)
+        assert mine.size == g["ref_bytes"] and sha(mine) == g["ref_sha256"], label
+        assert sha(orc.decompress(mine, cap=data.size + 8)) == g["ref_decoded_sha256"] == sha(data), label

@@ -4,15 +4,26 @@ that definition is "unpinned" by construction.  What is checked: the definition'
 code, optimal = never worse than any other 32-bit-limited code we can think of, untouched when nothing exceeds the
 limit), and -- with the compiled reference -- that the reference's DECODER reads limited streams back."""
 import ctypes as C
+import hashlib
+import json
 import os
-import tempfile
 from fractions import Fraction
 
 import numpy as np
 import pytest
 
+from cases import limited_stream_input
 from oracle import oracle as orc
 import datagen as dg
+
+
+def sha(b):
+    return hashlib.sha256(bytes(b)).hexdigest()
+
+
+def _sweeps():
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "golden_sweeps.json")) as f:
+        return json.load(f)
 
 
 def fib_hist(k):
@@ -80,14 +91,13 @@ def test_limit_is_optimal_against_brute_force_on_small_alphabets():
             assert cost == best, (case, limit, w.tolist(), L[:4].tolist(), int(L[256]))
 
 
-@pytest.mark.ref
-@pytest.mark.skipif(not orc.have_ref(), reason="compiled reference only exists where oracle/_ref was built")
 def test_reference_decoder_reads_a_limited_stream():
-    data = dg.counts_to_bytes(dg.fib_counts(33), seed=5)  # 14.9 MB: one bit too deep for the reference's encoder
+    """the compiled reference's bit-serial decoder read this very stream back to the input (tests/golden/golden_sweeps.json,
+    generator tests/golden/make_golden_sweeps.py)"""
+    data = limited_stream_input()  # 14.9 MB: one bit too deep for the reference's encoder
+    g = _sweeps()["limited"]
+    assert data.size == g["n"] and sha(data) == g["input_sha256"], "input generator drifted"
     crs = orc.compress_limited(data, 32)
-    with tempfile.TemporaryDirectory(dir="/tmp") as td:
-        f = os.path.join(td, "lim.crs2")
-        crs.tofile(f)
-        orc.ref_run(["d", f, f + ".de"], timeout=300)
-        assert np.array_equal(np.fromfile(f + ".de", dtype=np.uint8), data)
+    assert crs.size == g["stream_bytes"] and sha(crs) == g["stream_sha256"]
+    assert g["ref_decoded_sha256"] == sha(data)
     assert np.array_equal(orc.decompress(crs, cap=data.size + 8), data)
