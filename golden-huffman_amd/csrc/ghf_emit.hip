@@ -721,9 +721,74 @@ __global__ __launch_bounds__(kEmitThreads) void k_emit_long(EmitParams P) {
   emit_chunk<4>(P, G, c, reinterpret_cast<const uint32_t*>(P.code), stage, stage + wave * kStageWords, lane, pre);
 }
 
+// n == 0: a shard that holds nothing (more ranks than bytes, an uneven cut).  k_emit has no chunk to give a wave, so one
+// wave does what chunk 0 and the last chunk would have done around an empty body: the header (GHF_EMIT_HEADER), the end
+// mark and its padding at the start bit (GHF_EMIT_LAST), the units up to the last defined byte (bits in front of the start
+// bit as k_emit's carry path leaves them, zeros behind the end), and d_end.  At most two units: the end mark is <= 39 bits.
+__global__ __launch_bounds__(64) void k_emit_empty(EmitParams P) {
+  const int lane = threadIdx.x;
+  if (*P.status != 0) return;
+  const int max_len = P.code->max_len;
+  const bool last = (P.flags & GHF_EMIT_LAST) != 0;
+  if (max_len < 1 || max_len > 64 || (max_len > 32 && (last || !(P.flags & GHF_EMIT_LONG_CODES)))) {
+    if (lane == 0) latch_status(P.status, GHF_E_FORMAT);
+    return;
+  }
+  const uint64_t S = P.d_start_bit ? *P.d_start_bit : 8ull * (1040ull + 8ull * (uint64_t)max_len);
+  const uint64_t origin = (P.flags & GHF_EMIT_REBASE) ? ((S >> 7) << 4) : 0ull;
+  const uint32_t el = last ? P.code->length[GHF_NSYM - 1] : 0u;
+  const uint64_t end = last ? ((S + el + 7) & ~7ull) : S;
+  const uint32_t L = (uint32_t)(end - S);  // end mark + padding: <= 39 bits
+  const uint64_t V = last ? (((uint64_t)P.code->codeword[GHF_NSYM - 1] << (L - el)) | ((1ull << (L - el)) - 1ull)) : 0ull;
+  // emit_begin's arithmetic
+  const uint64_t end_byte = ((end + 7) >> 3) - origin;
+  const uint64_t end_unit_bytes = (((end >> 7) + 1) << 4) - origin;
+  const bool fits = end_unit_bytes <= P.cap || (((end & 127u) == 0) && end_byte <= P.cap);
+  if (lane == 0) {
+    if (!fits) latch_status(P.status, GHF_E_CAP);
+    if (P.d_end) {
+      P.d_end[0] = end;
+      P.d_end[1] = end_byte;
+    }
+  }
+  if (!fits) return;
+  uint32_t* const out32 = reinterpret_cast<uint32_t*>(P.out);
+  const uint64_t u_lo = S >> 7;
+  if (P.flags & GHF_EMIT_HEADER) {
+    const int nwords = 1 + GHF_NSYM + 2 + 2 * max_len;
+    for (int w = lane; w < nwords && (uint64_t)w < u_lo * 4; w += 64) out32[w] = bswap32(header_word(P.code, w, max_len));
+  }
+  const uint64_t n_units = (((end + 7) >> 3) + 15) / 16 - u_lo;  // units holding bytes [16 * u_lo, ceil(end / 8))
+  if ((uint64_t)lane >= n_units) return;
+  const uint64_t u = u_lo + (uint64_t)lane;
+  uint32_t ww[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const uint64_t gw = u * 4 + (uint64_t)k;  // stream word
+    uint32_t pre = 0;                          // the bits in front of S: zeros (REBASE), the header's, or what d_out holds
+    if (gw * 32 < S && !(P.flags & GHF_EMIT_REBASE)) {
+      if (!(P.flags & GHF_EMIT_HEADER)) pre = bswap32(out32[gw]);
+      else if (gw < (uint64_t)(1 + GHF_NSYM + 2 + 2 * max_len)) pre = header_word(P.code, (int)gw, max_len);
+    }
+    uint32_t w = 0;
+    for (int i = 0; i < 32; ++i) {
+      const uint64_t b = gw * 32 + (uint64_t)i;
+      uint32_t bit = 0;
+      if (b < S) bit = (pre >> (31 - i)) & 1u;
+      else if (b < end) bit = (uint32_t)(V >> (L - 1u - (uint32_t)(b - S))) & 1u;
+      w |= bit << (31 - i);
+    }
+    ww[k] = bswap32(w);
+  }
+  reinterpret_cast<uint4*>(P.out)[u - (origin >> 4)] = make_uint4(ww[0], ww[1], ww[2], ww[3]);
+}
+
 void launch_emit(const EmitParams& p, hipStream_t s) {
   const uint32_t blocks = (p.nchunks + kEmitWaves - 1) / kEmitWaves;
-  if (blocks == 0) return;
+  if (blocks == 0) {
+    hipLaunchKernelGGL(k_emit_empty, dim3(1), dim3(64), 0, s, p);
+    return;
+  }
   hipLaunchKernelGGL(k_emit, dim3(blocks), dim3(kEmitThreads), 0, s, p);
   if (p.flags & GHF_EMIT_LONG_CODES) hipLaunchKernelGGL(k_emit_long, dim3(blocks), dim3(kEmitThreads), 0, s, p);
 }

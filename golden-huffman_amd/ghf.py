@@ -395,6 +395,19 @@ class Context:
     def index_free(self, idx):
         self.L.ghf_index_free(self.h, C.byref(idx))
 
+    def index_to_host(self, idx):
+        """the side-car's two device arrays as numpy arrays (chunk_bit u64[n_chunks], seg_bit u32[n_segs]); synchronises"""
+        import numpy as np
+
+        chunk_bit = np.zeros(idx.n_chunks, dtype=np.uint64)
+        seg_bit = np.zeros(idx.n_segs, dtype=np.uint32)
+        if chunk_bit.size:
+            self._chk(self.L.ghf_copy_d2h(self.h, chunk_bit.ctypes.data, idx.d_chunk_bit, chunk_bit.nbytes), "ghf_copy_d2h")
+        if seg_bit.size:
+            self._chk(self.L.ghf_copy_d2h(self.h, seg_bit.ctypes.data, idx.d_seg_bit, seg_bit.nbytes), "ghf_copy_d2h")
+        self.sync()
+        return chunk_bit, seg_bit
+
     def compress(self, d_in, d_out=None, d_code=None, index=None, n=None, code_flags=0):
         """whole single-GPU pipeline, no host sync. -> (d_out, d_out_bytes[1] int64 device, d_code)"""
         n = d_in.numel() if n is None else n

@@ -282,7 +282,10 @@ int ghf_shard_bytes(ghf_ctx* ctx, const ghf_code* d_code, const uint64_t* d_tota
  * (n == 0) writes the 1048-byte header of that code followed by the byte 0x7F (the end mark, then 1-bits up to the
  * byte, as flush_bits pads): 1049 bytes that ghf_parse_header accepts and ghf_decode turns back into nothing.
  * This is the builder's own definition -- PARITY UNPINNED: no reference output exists to compare with.  The staged
- * calls (ghf_encode_plan / ghf_encode_emit) keep refusing n == 0. */
+ * calls take n == 0 with any code (that is a rank whose shard is empty in ghf_encode_sharded, which takes it too):
+ * ghf_encode_plan gives 0 body bits, and ghf_encode_emit writes what surrounds an empty body -- the header under
+ * GHF_EMIT_HEADER, the end mark and its padding at the start bit under GHF_EMIT_LAST (zeros in front of it in its unit
+ * under GHF_EMIT_REBASE) -- and always d_end. */
 #define GHF_EMPTY_OK 2u
 int ghf_build_code_ex(ghf_ctx* ctx, const uint64_t* d_hist, ghf_code* d_code, unsigned flags);
 int ghf_compress_ex(ghf_ctx* ctx, const uint8_t* d_in, size_t n, uint8_t* d_out, size_t cap, uint64_t* d_out_bytes,

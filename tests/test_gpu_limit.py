@@ -116,7 +116,7 @@ def test_empty_input_opt_in(env):
     back, n_out = ctx.decode(d_out, nb, ctx.code_to_device(hcode), None, cap=64)
     ctx.sync()
     assert int(n_out.item()) == 0
-    # the staged calls keep refusing, the histogram alone is fine (only the end mark counts)
+    # without the flag the code builder refuses an empty histogram; the histogram alone is fine (only the end mark counts)
     h = ctx.histogram(nothing, n=0)
     ctx.build_code(h)
     with pytest.raises(ghf.GhfError) as e:

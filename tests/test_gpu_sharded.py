@@ -161,6 +161,28 @@ def test_three_ranks_heterogeneous_shards_on_one_gpu():
     assert body_bits > 0 and ghf.shard_bound(n_total // world) >= 4 * (n_total // world)
 
 
+def test_three_ranks_with_an_empty_rank_0_on_one_gpu():
+    """more ranks than bytes: world 3 over 2 bytes, so rank 0's shard is empty.  Its K5 launch still has to write the header
+    and d_end (an empty last shard: the end mark), or the merged stream is not the single-stream .crs2"""
+    import datagen as dg
+    from oracle import oracle as orc
+
+    world, n_total, kind = 3, 2, "zipf"
+    port = 33300 + (os.getpid() % 2000)
+    ctx = mp.get_context("spawn")
+    q = ctx.Queue()
+    procs = [ctx.Process(target=_worker, args=(r, world, port, kind, n_total, q)) for r in range(world)]
+    for p in procs:
+        p.start()
+    got = [q.get(timeout=150) for _ in range(world)]
+    for p in procs:
+        p.join(timeout=60)
+    assert all(g[1] for g in got), "a rank failed to decode its own shard: %s" % [g[3] for g in got]
+    ref = orc.compress(dg.make(kind, n_total, seed=9))
+    got_stream = np.frombuffer(next(g[2] for g in got if g[2] is not None), dtype=np.uint8)
+    assert got_stream.size == ref.size and np.array_equal(got_stream, ref)
+
+
 def test_encode_sharded_c_abi_world1_over_rccl():
     """ghf_encode_sharded with a REAL RCCL communicator of one rank (ncclCommInitRank through the C ABI): the two
     collectives are queued on the context's stream; the result is the single-stream .crs2"""
