@@ -7,111 +7,31 @@
 #include <new>
 #include <string>
 
-#include "ghf_internal.h"
+#include "ghf_ctx.h"
 
 using namespace ghf;
-
-struct ghf_ctx {
-  int device = 0;
-  hipStream_t own_stream = nullptr;
-  hipStream_t stream = nullptr;
-  int* d_status = nullptr;
-  int* h_status = nullptr;  // pinned
-  // workspace
-  uint32_t* d_chunk_hist = nullptr;
-  size_t chunk_hist_cap = 0;  // in chunks
-  uint64_t* d_chunk_off = nullptr;
-  size_t chunk_off_cap = 0;  // in entries
-  const uint8_t* hist_in = nullptr;  // what d_chunk_hist currently describes
-  uint64_t hist_n = 0;
-  uint32_t hist_chunk = 0;
-  const uint8_t* plan_in = nullptr;  // what d_chunk_off currently describes
-  uint64_t plan_n = 0;
-  const ghf_code* plan_code = nullptr;
-  uint64_t* d_hist = nullptr;   // [257]
-  uint64_t* d_hist_acc = nullptr;  // K1's replicated totals + arrival counter, zero between launches
-  ghf_code* d_code = nullptr;   // scratch tables for ghf_compress
-  ghf_tree* d_tree = nullptr;   // scratch tree for ghf_crs_compress
-  DecTables* d_dt = nullptr;
-  const ghf_code* dt_code = nullptr;  // ghf_decode_prepare() built d_dt from these tables; consumed by the next ghf_decode
-  uint64_t* d_totals = nullptr;  // [totals_cap] per-rank body bits (ghf_encode_sharded)
-  int totals_cap = 0;
-  uint64_t* d_u64 = nullptr;    // [16] scratch scalars: 0 total_bits, 1..2 end, 3 n_symbols, 4 eof_sub, 6 start bit (.crs), 8 landing, 9 changed + count, 10 first moved (inverted)
-  uint64_t* h_u64 = nullptr;    // [16] pinned mirror
-  // K6 workspace (foreign streams)
-  void* d_sync = nullptr;
-  size_t sync_cap = 0;  // bytes
-  ghf_index fidx = {};  // side-car rebuilt for the last foreign stream
-  uint64_t* d_seg_abs = nullptr;
-  size_t fidx_cap_segs = 0, fidx_cap_chunks = 0;
-  const uint8_t* fidx_stream = nullptr;  // which stream c->fidx currently describes
-  size_t fidx_bytes = 0;
-  std::string err;
-};
 
 namespace {
 
 thread_local std::string g_create_err;  // ghf_last_error(NULL): why ghf_ctx_create failed
 
-int fail(ghf_ctx* c, int code, const char* what, hipError_t e = hipSuccess) {
-  if (c) {
-    c->err = what;
-    if (e != hipSuccess) {
-      c->err += ": ";
-      c->err += hipGetErrorString(e);
-    }
-  }
-  return code;
-}
-
-#define GHF_HIP(c, call)                                         \
-  do {                                                           \
-    hipError_t e_ = (call);                                      \
-    if (e_ != hipSuccess) return fail((c), GHF_E_HIP, #call, e_); \
-  } while (0)
-
 int ensure_ws(ghf_ctx* c, size_t nchunks) {
-  if (nchunks + 1 > c->chunk_off_cap) {
-    if (c->d_chunk_off) (void)hipFree(c->d_chunk_off);
-    c->d_chunk_off = nullptr;
-    c->chunk_off_cap = 0;
-    size_t cap = std::max<size_t>(nchunks + 1, 1024);
-    GHF_HIP(c, hipMalloc(&c->d_chunk_off, cap * sizeof(uint64_t)));
-    c->chunk_off_cap = cap;
-    c->plan_in = nullptr;
-  }
-  if (nchunks > c->chunk_hist_cap) {
-    if (c->d_chunk_hist) (void)hipFree(c->d_chunk_hist);
-    c->d_chunk_hist = nullptr;
-    c->chunk_hist_cap = 0;
-    size_t cap = std::max<size_t>(nchunks, 1024);
-    GHF_HIP(c, hipMalloc(&c->d_chunk_hist, cap * 256 * sizeof(uint32_t)));
-    c->chunk_hist_cap = cap;
-    c->hist_in = nullptr;
-  }
-  return GHF_OK;
+  bool new_off = false, new_hist = false;
+  int rc = grow(c, c->chunk_off, nchunks + 1, 1024, &new_off);
+  if (!rc) rc = grow(c, c->chunk_hist, nchunks * 256, 1024 * 256, &new_hist);
+  if (new_off) c->plan.forget();
+  if (new_hist) c->hist.forget();
+  return rc;
 }
 
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
-}  // namespace
-
-// accessors for ghf_comm.hip (the struct stays private to this file)
-int ghf_api_fail(ghf_ctx* c, int code, const char* what) { return fail(c, code, what); }
-hipStream_t ghf_api_stream(ghf_ctx* c) { return c->stream; }
-int ghf_api_device(ghf_ctx* c) { return c->device; }
-uint64_t* ghf_api_scratch_u64(ghf_ctx* c) { return c->d_u64; }
-uint64_t* ghf_api_hist(ghf_ctx* c) { return c->d_hist; }
-uint64_t* ghf_api_totals(ghf_ctx* c, int world) {
-  if (world > c->totals_cap) {
-    if (c->d_totals) (void)hipFree(c->d_totals);
-    c->d_totals = nullptr;
-    c->totals_cap = 0;
-    if (hipMalloc(&c->d_totals, (size_t)(world < 8 ? 8 : world) * sizeof(uint64_t)) != hipSuccess) return nullptr;
-    c->totals_cap = world < 8 ? 8 : world;
-  }
-  return c->d_totals;
+// the part of "this side-car is one of ours" that packing and decoding both ask for
+inline bool index_has_arrays(const ghf_index* ix) {
+  return ix->d_chunk_bit && ix->d_seg_bit && ix->chunk_symbols == (uint32_t)kBlockSymbols && ix->seg_symbols == (uint32_t)kSegSymbols;
 }
+
+}  // namespace
 
 extern "C" {
 
@@ -162,8 +82,8 @@ int ghf_ctx_create(int device, ghf_ctx** out) {
   GHF_STEP(hipMalloc(&c->d_code, sizeof(ghf_code)));
   GHF_STEP(hipMalloc(&c->d_tree, sizeof(ghf_tree)));
   GHF_STEP(hipMalloc(&c->d_dt, sizeof(DecTables)));
-  GHF_STEP(hipMalloc(&c->d_u64, 16 * sizeof(uint64_t)));
-  GHF_STEP(hipHostMalloc(&c->h_u64, 16 * sizeof(uint64_t), hipHostMallocDefault));
+  GHF_STEP(hipMalloc(&c->d, sizeof(Scalars)));
+  GHF_STEP(hipHostMalloc(&c->h, sizeof(Scalars), hipHostMallocDefault));
   GHF_STEP(hipMemset(c->d_status, 0, sizeof(int)));
 #undef GHF_STEP
   if (e != hipSuccess) {
@@ -182,20 +102,20 @@ int ghf_ctx_destroy(ghf_ctx* c) {
   if (c->stream) (void)hipStreamSynchronize(c->stream);
   if (c->d_status) (void)hipFree(c->d_status);
   if (c->h_status) (void)hipHostFree(c->h_status);
-  if (c->d_chunk_hist) (void)hipFree(c->d_chunk_hist);
-  if (c->d_chunk_off) (void)hipFree(c->d_chunk_off);
   if (c->d_hist) (void)hipFree(c->d_hist);
   if (c->d_hist_acc) (void)hipFree(c->d_hist_acc);
   if (c->d_code) (void)hipFree(c->d_code);
   if (c->d_tree) (void)hipFree(c->d_tree);
   if (c->d_dt) (void)hipFree(c->d_dt);
-  if (c->d_u64) (void)hipFree(c->d_u64);
-  if (c->d_totals) (void)hipFree(c->d_totals);
-  if (c->h_u64) (void)hipHostFree(c->h_u64);
-  if (c->d_sync) (void)hipFree(c->d_sync);
-  if (c->d_seg_abs) (void)hipFree(c->d_seg_abs);
-  if (c->fidx.d_chunk_bit) (void)hipFree(c->fidx.d_chunk_bit);
-  if (c->fidx.d_seg_bit) (void)hipFree(c->fidx.d_seg_bit);
+  if (c->d) (void)hipFree(c->d);
+  if (c->h) (void)hipHostFree(c->h);
+  release(c->chunk_hist);
+  release(c->chunk_off);
+  release(c->totals);
+  release(c->sync);
+  release(c->seg_bit);
+  release(c->seg_abs);
+  release(c->chunk_bit);
   if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
   delete c;
   return GHF_OK;
@@ -346,11 +266,10 @@ static int histogram(ghf_ctx* c, const uint8_t* d_in, size_t n, uint64_t* d_hist
   const size_t nchunks = (size_t)chunk_count_for(n);
   int rc = ensure_ws(c, nchunks);
   if (rc) return rc;
-  launch_histogram(d_in, n, cl, (uint32_t)nchunks, c->d_chunk_hist, d_hist, c->d_hist_acc, add, c->stream);
+  launch_histogram(d_in, n, cl, (uint32_t)nchunks, c->chunk_hist.p, d_hist, c->d_hist_acc, add, c->stream);
   GHF_HIP(c, hipGetLastError());
-  c->hist_in = add ? nullptr : d_in;  // a piece's buffer is refilled before anything is planned: nothing to keep
-  c->hist_n = n;
-  c->hist_chunk = cl;
+  if (add) c->hist.forget();  // a piece's buffer is refilled before anything is planned: nothing to keep
+  else c->hist = {d_in, n, cl};
   return GHF_OK;
 }
 int ghf_histogram(ghf_ctx* c, const uint8_t* d_in, size_t n, uint64_t* d_hist) { return histogram(c, d_in, n, d_hist, false); }
@@ -361,8 +280,8 @@ int ghf_build_code_ex(ghf_ctx* c, const uint64_t* d_hist, ghf_code* d_code, unsi
   GHF_HIP(c, hipSetDevice(c->device));
   launch_build_code(d_hist, d_code, c->d_status, flags, c->stream);
   GHF_HIP(c, hipGetLastError());
-  if (c->plan_code == d_code) c->plan_in = nullptr;  // tables changed: any cached plan is stale
-  if (c->dt_code == d_code) c->dt_code = nullptr;
+  if (c->plan.code == d_code) c->plan.forget();  // tables changed: any cached plan is stale
+  if (c->prepared.describes(d_code)) c->prepared.forget();
   return GHF_OK;
 }
 
@@ -383,13 +302,11 @@ int ghf_encode_plan(ghf_ctx* c, const uint8_t* d_in, size_t n, const ghf_code* d
   const size_t nchunks = (size_t)chunk_count_for(n);
   int rc = ensure_ws(c, nchunks);
   if (rc) return rc;
-  const bool have_hist = c->hist_in == d_in && c->hist_n == n && c->hist_chunk == cl && n != 0;
-  launch_plan(d_in, n, cl, (uint32_t)nchunks, have_hist ? c->d_chunk_hist : nullptr, d_code, c->d_chunk_off,
-              d_total_bits ? d_total_bits : c->d_u64, c->stream);
+  const bool have_hist = c->hist.describes(d_in, n, cl) && n != 0;
+  launch_plan(d_in, n, cl, (uint32_t)nchunks, have_hist ? c->chunk_hist.p : nullptr, d_code, c->chunk_off.p,
+              d_total_bits ? d_total_bits : &c->d->total_bits, c->stream);
   GHF_HIP(c, hipGetLastError());
-  c->plan_in = d_in;
-  c->plan_n = n;
-  c->plan_code = d_code;
+  c->plan = {d_in, n, d_code};
   return GHF_OK;
 }
 
@@ -399,21 +316,18 @@ int ghf_encode_emit(ghf_ctx* c, const uint8_t* d_in, size_t n, const ghf_code* d
   if (!aligned16(d_out)) return fail(c, GHF_E_INVAL, "d_out must be 16-byte aligned");
   if ((flags & GHF_EMIT_HEADER) && (flags & GHF_EMIT_REBASE))
     return fail(c, GHF_E_INVAL, "GHF_EMIT_HEADER is for the buffer that starts at stream byte 0 (rank 0 / single GPU)");
-  if (c->plan_in != d_in || c->plan_n != n || c->plan_code != d_code)
+  if (!c->plan.describes(d_in, n, d_code))
     return fail(c, GHF_E_INVAL, "ghf_encode_emit: call ghf_encode_plan on the same (d_in, n, d_code) first");
   GHF_HIP(c, hipSetDevice(c->device));
   const uint32_t cl = chunk_symbols_for(n);
   const size_t nchunks = (size_t)chunk_count_for(n);
-  if (index) {
-    if (index->n_symbols != n || index->chunk_symbols != (uint32_t)kBlockSymbols || index->seg_symbols != (uint32_t)kSegSymbols ||
-        !index->d_chunk_bit || !index->d_seg_bit)
-      return fail(c, GHF_E_INVAL, "ghf_encode_emit: index does not match n (use ghf_index_alloc)");
-  }
+  if (index && (index->n_symbols != n || !index_has_arrays(index)))
+    return fail(c, GHF_E_INVAL, "ghf_encode_emit: index does not match n (use ghf_index_alloc)");
   EmitParams p;
   p.in = d_in;
   p.n = n;
   p.code = d_code;
-  p.chunk_off = c->d_chunk_off;
+  p.chunk_off = c->chunk_off.p;
   p.d_start_bit = d_start_bit;
   p.out = d_out;
   p.cap = cap;
@@ -466,11 +380,11 @@ int ghf_compress_ex(ghf_ctx* c, const uint8_t* d_in, size_t n, uint8_t* d_out, s
   }
   if ((rc = ghf_histogram(c, d_in, n, c->d_hist))) return rc;   // compressor.h:63
   if ((rc = ghf_build_code_ex(c, c->d_hist, code, code_flags))) return rc;  // compressor.h:64
-  if ((rc = ghf_encode_plan(c, d_in, n, code, c->d_u64))) return rc;
+  if ((rc = ghf_encode_plan(c, d_in, n, code, &c->d->total_bits))) return rc;
   // compressor.h:70 + :72 -- the header rides along with the emit launches
-  if ((rc = ghf_encode_emit(c, d_in, n, code, nullptr, GHF_EMIT_LAST | GHF_EMIT_HEADER, d_out, cap, index, c->d_u64 + 1))) return rc;
+  if ((rc = ghf_encode_emit(c, d_in, n, code, nullptr, GHF_EMIT_LAST | GHF_EMIT_HEADER, d_out, cap, index, c->d->end))) return rc;
   if (d_out_bytes) {
-    launch_store_u64(d_out_bytes, c->d_u64 + 2, 0, c->stream);
+    launch_store_u64(d_out_bytes, &c->d->end[1], 0, c->stream);
     GHF_HIP(c, hipGetLastError());
   }
   return GHF_OK;
@@ -582,12 +496,183 @@ int ghf_parse_header(const uint8_t* h, size_t n, ghf_code* code, size_t* header_
   return GHF_OK;
 }
 
-// K6: rebuild the side-car of a stream that came without one (e.g. a .crs2 written by the reference).
+// ---- K6: rebuild the side-car of a stream that came without one (e.g. a .crs2 written by the reference) ----------
 // Synchronises with the host a few times (convergence flag, symbol count); fills c->fidx.
-static int rebuild_index_at(ghf_ctx* c, const uint8_t* d_stream, size_t stream_bytes, size_t hdr, uint64_t end_bit, int mode,
-                            size_t cap, uint32_t first_start = 0, uint64_t* landing = nullptr, int* has_end_mark = nullptr,
-                            bool prefer_scan = false, int max_len_hint = 0);
+struct RebuildRequest {
+  const uint8_t* d_stream;
+  size_t stream_bytes;
+  SyncKind kind;
+  uint64_t end_bit;           // one past the last bit that may belong to a code
+  uint32_t first_start = 0;   // kSyncPiece: the first code boundary is assumed this many bits behind hdr
+  size_t hdr = 0;             // bytes in front of the first code
+  int max_len = 0;            // the longest code, for the stride of the scan's function rows
+  bool scan_at_once = false;  // a near-fixed-length code: seed the boundaries with the deterministic scan before any pass
+  size_t cap = (size_t)-1;    // decoded bytes the caller has room for
+};
 
+struct RebuildResult {
+  uint64_t n = 0;             // symbols: codes that start in front of end_bit, up to the end mark
+  uint64_t landing = 0;       // kSyncPiece: bits the last code runs past end_bit
+  bool has_end_mark = false;  // kSyncPiece: the piece holds one
+};
+
+// cuts c->sync into K6's arrays for p.nsub subsequences; *scan_ws: the deterministic scan's share
+static int carve_sync_workspace(ghf_ctx* c, SyncParams& p, uint8_t** scan_ws) {
+  const size_t ntiles = (p.nsub + 255) / 256;
+  size_t off = 0;
+  auto carve = [&](size_t bytes) {
+    const size_t o = off;
+    off += (bytes + 255) & ~(size_t)255;
+    return o;
+  };
+  const size_t o_start = carve((p.nsub + 1) * 2), o_used = carve(p.nsub * 2), o_cnt = carve(p.nsub * 4), o_eof = carve(p.nsub),
+               o_tile = carve((ntiles + 2) * 8), o_scan = carve(sync_scan_workspace(p.nsub));
+  const int rc = grow(c, c->sync, off);
+  if (rc) return rc;
+  uint8_t* ws = c->sync.p;
+  p.start = reinterpret_cast<uint16_t*>(ws + o_start);
+  p.used = reinterpret_cast<uint16_t*>(ws + o_used);
+  p.cnt = reinterpret_cast<uint32_t*>(ws + o_cnt);
+  p.eof = ws + o_eof;
+  p.tile_sum = reinterpret_cast<uint64_t*>(ws + o_tile);
+  *scan_ws = ws + o_scan;
+  return GHF_OK;
+}
+
+// seeds the boundary guesses and queues passes until none moves; the last batch's read-back is left in c->h->k6
+static int settle_boundaries(ghf_ctx* c, SyncParams& p, uint8_t* scan_ws, const RebuildRequest& q) {
+  // the stride of the scan's function rows (launch_sync_scan): a shallow code does not pay for 64-byte rows
+  const uint32_t stride = (q.max_len >= 1 && q.max_len <= 16) ? 16u : (q.max_len > 32 ? 64u : 32u);
+  bool scanned = q.first_start >= stride;  // (the scan follows entry offsets below its stride only: such a piece counts as seeded)
+  const bool scan_first = q.scan_at_once && !scanned;
+  p.first = scan_first ? 0u : 3u;
+  p.first_start = q.first_start;
+  // `start`, `used`, `eof` (11 bytes per KiB of stream: 3 + 3 + 1.5 MB at 256 MiB) are not cleared when the fixed-point passes
+  // come first: the first k_sync_pass of the call finds every subsequence unworked and every guess 0 because its parameters
+  // say so (SyncParams::first), and writes all three arrays whole.  (Round 3 queued three memsets, 60 us at 256 MiB in front
+  // of a 1 ms job.)
+  if (scan_first) {
+    // (the scan's kernels write the guesses they derive -- and, for the subsequences whose class walk already is the whole
+    //  answer, the results too: `used` must say "nothing yet" for all the others)
+    GHF_HIP(c, hipMemsetAsync(p.start, 0, (p.nsub + 1) * 2, c->stream));
+    if (q.first_start) launch_store_u64(reinterpret_cast<uint64_t*>(p.start), nullptr, q.first_start, c->stream);  // start[0]
+    GHF_HIP(c, hipMemsetAsync(p.used, 0xFF, p.nsub * 2, c->stream));
+    GHF_HIP(c, hipMemsetAsync(p.eof, 0, p.nsub, c->stream));
+    launch_sync_scan(p, scan_ws, stride, q.first_start, c->stream);  // (seeds the boundaries; the passes below only verify)
+    scanned = true;
+  } else {
+    launch_store_u64(reinterpret_cast<uint64_t*>(p.start), nullptr, q.first_start, c->stream);  // start[0] (k_sync_pass stores start[1 ..])
+  }
+  // passes until no boundary guess moves (self-synchronisation: a handful of passes in practice).  They are queued in
+  // batches; behind every batch the counts (first end mark, symbols per tile, their scan) and the landing bit are queued as
+  // well, and the host reads {symbols, end-mark subsequence, "something moved", landing} in ONE round trip: a stream that has
+  // settled in its first batch -- the usual case, and the rule behind the deterministic scan -- costs one synchronisation (round 2:
+  // four per call, a quarter of the file decompressor's K6 time at 16 MiB pieces).
+  // Streams that self-synchronise slowly (near-fixed-length codes) would need one pass per subsequence of drift: their
+  // boundaries are seeded by the deterministic scan (launch_sync_scan) -- at once when the caller knows the code is of that
+  // kind, otherwise as soon as a first batch of passes has not settled.  The passes then only verify.
+  constexpr int kBatch = 4;
+  const K6Readback& k = c->h->k6;
+  for (uint64_t passes = 0;;) {
+    if (passes > p.nsub + 2) return fail(c, GHF_E_CORRUPT, "self-synchronisation did not converge");
+    // (behind the deterministic scan the first pass only has to CONFIRM the boundaries: one pass, not a batch)
+    const int nb = (scanned && passes == 0) ? 1 : kBatch;
+    for (int b = 0; b < nb; ++b) {
+      GHF_HIP(c, hipMemsetAsync(&c->d->k6.moved, 0, sizeof(K6Moved), c->stream));  // flag, count, first (inverted)
+      launch_sync_pass(p, c->stream);
+      p.first = 0;
+    }
+    passes += nb;
+    launch_store_u64(p.eof_sub, nullptr, p.nsub, c->stream);  // "none found"; k_sync_eof takes the minimum
+    launch_sync_counts(p, &c->d->k6.n_symbols, c->stream);
+    launch_load_u16(&c->d->k6.landing, p.start + p.nsub, c->stream);
+    GHF_HIP(c, hipMemcpyAsync(&c->h->k6, &c->d->k6, sizeof(K6Readback), hipMemcpyDeviceToHost, c->stream));
+    GHF_HIP(c, hipStreamSynchronize(c->stream));
+    const uint64_t moved = (uint64_t)k.moved.changed[1] * 256;  // boundaries the batch's last pass moved (sampled: every 256th group)
+#ifdef GHF_K6_TRACE  // (scratch/build_variant.sh k6trace -DGHF_K6_TRACE: what every batch of passes left behind)
+    fprintf(stderr, "[k6] nsub %llu passes %llu scanned %d flag %u moved~%llu first %llu eof_sub %llu\n", (unsigned long long)p.nsub,
+            (unsigned long long)passes, (int)scanned, (unsigned)k.moved.changed[0], (unsigned long long)moved,
+            (unsigned long long)~k.moved.first_inv, (unsigned long long)k.eof_sub);
+#endif
+    if (k.moved.changed[0] == 0) break;
+    // .crs2: settled IN FRONT OF THE END MARK is settled.  No landing at or before the first end mark's subsequence moved
+    // in the batch's last pass -> every boundary up to it is a fixed point, the mark is the stream's (the first one, and
+    // real).  What lies behind it (a buffer longer than its stream: stale bytes) may go on moving for ever.
+    if (q.kind == kSyncCrs2 && k.moved.first_inv != 0 && ~k.moved.first_inv >= k.eof_sub && k.eof_sub < p.nsub) break;
+    // Not settled.  A boundary that is still moving travels ONE subsequence to the right per pass, and a pass in which
+    // little moved costs little (a wave whose 64 subsequences are current skips them), so a few more batches are cheaper
+    // than the deterministic scan over the whole stream -- which long streams of a quickly synchronising code otherwise
+    // fall into because SOME stretch among their millions of subsequences needs a fifth pass (4 GiB Zipf: 44 ms with
+    // the scan after the first batch, see profiles/r04/foreign_4GiB.txt).  Codes that do not settle in kScanAfter passes
+    // (long runs of one value, near-fixed-length codes the caller did not announce) get the scan then.
+    // What decides is HOW MUCH still moves: a few stragglers (one stretch in a 4 GiB Zipf stream needs 17..20 passes,
+    // whichever seed) are followed for up to kScanAfterFew passes; a stream in which boundaries still move everywhere
+    // after two batches is not going to settle by itself.
+    constexpr uint64_t kScanAfterMany = 8, kScanAfterFew = 64;
+    const uint64_t few = p.nsub >> 10 > 4096 ? p.nsub >> 10 : 4096;
+    if (!scanned && (passes >= kScanAfterFew || (passes >= kScanAfterMany && moved > few))) {
+      launch_sync_scan(p, scan_ws, stride, q.first_start, c->stream);
+      scanned = true;
+    }
+  }
+  return GHF_OK;
+}
+
+// sizes c->fidx for n symbols and queues the kernel that fills it from the settled boundaries
+static int build_sidecar(ghf_ctx* c, const SyncParams& p, uint64_t n, uint32_t flags) {
+  const uint64_t n_chunks = (n + kBlockSymbols - 1) / kBlockSymbols, n_segs = (n + kSegSymbols - 1) / kSegSymbols;
+  ghf_index& ix = c->fidx;
+  if (n) {  // (d_seg_abs has one entry more than there are segments)
+    int rc = grow(c, c->seg_bit, n_segs);
+    if (!rc) rc = grow(c, c->seg_abs, n_segs + 1);
+    if (!rc) rc = grow(c, c->chunk_bit, n_chunks);
+    ix.d_seg_bit = c->seg_bit.p;
+    ix.d_chunk_bit = c->chunk_bit.p;
+    if (rc) return rc;
+  }
+  ix.n_symbols = n;
+  ix.chunk_symbols = kBlockSymbols;
+  ix.seg_symbols = kSegSymbols;
+  ix.n_chunks = n_chunks;
+  ix.n_segs = n_segs;
+  ix.flags = flags;
+  if (n) launch_sync_index(p, c->seg_abs.p, n, ix.d_chunk_bit, ix.d_seg_bit, c->stream);
+  GHF_HIP(c, hipGetLastError());
+  return GHF_OK;
+}
+
+static int rebuild_index_at(ghf_ctx* c, const RebuildRequest& q, RebuildResult* r /* may be null */) {
+  SyncParams p;
+  p.stream = q.d_stream;
+  p.stream_bytes = q.stream_bytes;
+  p.body_bit0 = (uint64_t)q.hdr * 8;
+  p.end_bit = q.end_bit;
+  p.no_eof = q.kind;
+  p.dt = c->d_dt;
+  p.nsub = (q.end_bit - p.body_bit0 + 511) / 512;
+  p.changed = c->d->k6.moved.changed;
+  p.moved_first_inv = &c->d->k6.moved.first_inv;
+  p.eof_sub = &c->d->k6.eof_sub;
+  uint8_t* scan_ws = nullptr;
+  int rc = carve_sync_workspace(c, p, &scan_ws);
+  if (!rc) rc = settle_boundaries(c, p, scan_ws, q);
+  if (rc) return rc;
+  const uint64_t n = c->h->k6.n_symbols;
+  const uint16_t land16 = (uint16_t)c->h->k6.landing;  // 0xFFFF: the last subsequence ended at an end mark (real, or a fake one of a wrong guess)
+  const bool has_end_mark = c->h->k6.eof_sub < p.nsub;
+  // .crs: every subsequence counts; a flagged one means bits that are no code or a code running past the end
+  // (eof_sub == nsub, "none", makes the counting kernels take every subsequence: n is already the total)
+  if (q.kind == kSyncCrs && has_end_mark) return fail(c, GHF_E_CORRUPT, "the .crs body does not end on a code boundary");
+  if (q.kind == kSyncCrs2 && !has_end_mark) return fail(c, GHF_E_CORRUPT, "no end mark in the stream");
+  if (n > q.cap) return fail(c, GHF_E_CAP, "ghf_decode: output capacity below the decoded size");
+  rc = build_sidecar(c, p, n, (q.kind == kSyncPiece && !has_end_mark) ? (uint32_t)GHF_INDEX_NO_END_MARK : 0u);
+  if (rc) return rc;
+  c->rebuilt = {q.d_stream, q.stream_bytes};
+  if (r) *r = {n, land16 == 0xFFFF ? 0u : land16, has_end_mark};
+  return GHF_OK;
+}
+
+// a whole .crs2: the header's length and the kind of code come from the device-resident tables
 static int rebuild_index(ghf_ctx* c, const uint8_t* d_stream, size_t stream_bytes, const ghf_code* d_code, size_t cap) {
   ghf_code* hc = new (std::nothrow) ghf_code;
   if (!hc) return GHF_E_NOMEM;
@@ -597,211 +682,73 @@ static int rebuild_index(ghf_ctx* c, const uint8_t* d_stream, size_t stream_byte
   delete hc;
   if (e != hipSuccess) return fail(c, GHF_E_HIP, "copy tables to host", e);
   if (max_len < 1 || max_len > 32) return fail(c, GHF_E_FORMAT, "bad max_len in tables");
-  const size_t hdr = ghf_header_bytes(max_len);
-  if (stream_bytes <= hdr) return fail(c, GHF_E_FORMAT, "stream shorter than its header");
-  return rebuild_index_at(c, d_stream, stream_bytes, hdr, (uint64_t)stream_bytes * 8, 0, cap, 0, nullptr, nullptr,
-                          /*prefer_scan=*/max_len - min_len <= 1, max_len);
+  RebuildRequest q{d_stream, stream_bytes, kSyncCrs2, (uint64_t)stream_bytes * 8};
+  q.hdr = ghf_header_bytes(max_len);
+  if (stream_bytes <= q.hdr) return fail(c, GHF_E_FORMAT, "stream shorter than its header");
+  q.max_len = max_len;
+  q.scan_at_once = max_len - min_len <= 1;
+  q.cap = cap;
+  return rebuild_index_at(c, q, nullptr);
 }
 
-// K6 driver.  hdr = bytes in front of the first code; end_bit = one past the last bit that may belong to a code;
-// mode 0: .crs2 (ends with the end mark); 1: .crs (no end mark, must end exactly at end_bit); 2: a piece of a .crs2
-// whose first code boundary is assumed first_start bits behind hdr and whose last code may run past end_bit
-static int rebuild_index_at(ghf_ctx* c, const uint8_t* d_stream, size_t stream_bytes, size_t hdr, uint64_t end_bit, int mode,
-                            size_t cap, uint32_t first_start, uint64_t* landing, int* has_end_mark, bool prefer_scan, int max_len_hint) {
-  const bool no_eof = mode == 1;
-  SyncParams p;
-  p.stream = d_stream;
-  p.stream_bytes = stream_bytes;
-  p.body_bit0 = (uint64_t)hdr * 8;
-  p.end_bit = end_bit;
-  p.no_eof = (uint32_t)mode;
-  p.dt = c->d_dt;
-  p.nsub = (end_bit - p.body_bit0 + 511) / 512;
-  const size_t ntiles = (p.nsub + 255) / 256;
-  // carve the workspace
-  size_t off = 0;
-  auto carve = [&](size_t bytes) {
-    const size_t o = off;
-    off += (bytes + 255) & ~(size_t)255;
-    return o;
-  };
-  const size_t o_start = carve((p.nsub + 1) * 2), o_used = carve(p.nsub * 2), o_cnt = carve(p.nsub * 4), o_eof = carve(p.nsub),
-               o_tile = carve((ntiles + 2) * 8), o_scan = carve(sync_scan_workspace(p.nsub));
-  if (off > c->sync_cap) {
-    if (c->d_sync) (void)hipFree(c->d_sync);
-    c->d_sync = nullptr;
-    c->sync_cap = 0;
-    GHF_HIP(c, hipMalloc(&c->d_sync, off));
-    c->sync_cap = off;
-  }
-  uint8_t* ws = static_cast<uint8_t*>(c->d_sync);
-  p.start = reinterpret_cast<uint16_t*>(ws + o_start);
-  p.used = reinterpret_cast<uint16_t*>(ws + o_used);
-  p.cnt = reinterpret_cast<uint32_t*>(ws + o_cnt);
-  p.eof = ws + o_eof;
-  p.tile_sum = reinterpret_cast<uint64_t*>(ws + o_tile);
-  p.changed = reinterpret_cast<uint32_t*>(c->d_u64 + 9);
-  p.moved_first_inv = reinterpret_cast<unsigned long long*>(c->d_u64 + 10);
-  p.eof_sub = c->d_u64 + 4;
-  // `start`, `used`, `eof` (11 bytes per KiB of stream: 3 + 3 + 1.5 MB at 256 MiB) are not cleared when the fixed-point passes
-  // come first: the first k_sync_pass of the call finds every subsequence unworked and every guess 0 because its parameters
-  // say so (SyncParams::first), and writes all three arrays whole.  (Round 3 queued three memsets, 60 us at 256 MiB in front
-  // of a 1 ms job.)
-  const bool scan_first = prefer_scan && first_start < ((max_len_hint >= 1 && max_len_hint <= 16) ? 16u : (max_len_hint > 32 ? 64u : 32u));
-  if (scan_first) {
-    // (the scan's kernels write the guesses they derive -- and, for the subsequences whose class walk already is the whole
-    //  answer, the results too: `used` must say "nothing yet" for all the others)
-    GHF_HIP(c, hipMemsetAsync(p.start, 0, (p.nsub + 1) * 2, c->stream));
-    if (first_start) launch_store_u64(reinterpret_cast<uint64_t*>(p.start), nullptr, first_start, c->stream);  // start[0]
-    GHF_HIP(c, hipMemsetAsync(p.used, 0xFF, p.nsub * 2, c->stream));
-    GHF_HIP(c, hipMemsetAsync(p.eof, 0, p.nsub, c->stream));
-  } else {
-    launch_store_u64(reinterpret_cast<uint64_t*>(p.start), nullptr, first_start, c->stream);  // start[0] (k_sync_pass stores start[1 ..])
-  }
-  p.first = scan_first ? 0u : 3u;
-  p.first_start = first_start;
-  // passes until no boundary guess moves (self-synchronisation: a handful of passes in practice).  They are queued in
-  // batches; behind every batch the counts (first end mark, symbols per tile, their scan) and the landing bit are queued as
-  // well, and the host reads {symbols, end-mark subsequence, "something moved", landing} in ONE round trip: a stream that has
-  // settled in its first batch -- the usual case, and the rule behind the deterministic scan -- costs one synchronisation (round 2:
-  // four per call, a quarter of the file decompressor's K6 time at 16 MiB pieces).
-  // Streams that self-synchronise slowly (near-fixed-length codes) would need one pass per subsequence of drift: their
-  // boundaries are seeded by the deterministic scan (launch_sync_scan) -- at once when the caller knows the code is of that
-  // kind, otherwise as soon as a first batch of passes has not settled.  The passes then only verify.
-  uint64_t n = 0, eof_sub = 0;
-  uint16_t land16 = 0;
-  {
-    constexpr int kBatch = 4;
-    uint64_t passes = 0;
-    const uint32_t fn_stride = (max_len_hint >= 1 && max_len_hint <= 16) ? 16u : (max_len_hint > 32 ? 64u : 32u);
-    bool scanned = first_start >= fn_stride;  // (the scan follows entry offsets below its stride only)
-    if (prefer_scan && !scanned) {
-      launch_sync_scan(p, ws + o_scan, fn_stride, first_start, c->stream);
-      scanned = true;
-    }
-    for (;;) {
-      if (passes > p.nsub + 2) return fail(c, GHF_E_CORRUPT, "self-synchronisation did not converge");
-      // (behind the deterministic scan the first pass only has to CONFIRM the boundaries: one pass, not a batch)
-      const int nb = (scanned && passes == 0) ? 1 : kBatch;
-      for (int b = 0; b < nb; ++b) {
-        GHF_HIP(c, hipMemsetAsync(p.changed, 0, 16, c->stream));  // flag, count, first (inverted)
-        launch_sync_pass(p, c->stream);
-        p.first = 0;
-      }
-      passes += nb;
-      launch_store_u64(p.eof_sub, nullptr, p.nsub, c->stream);  // "none found"; k_sync_eof takes the minimum
-      launch_sync_counts(p, c->d_u64 + 3, c->stream);
-      launch_load_u16(c->d_u64 + 8, p.start + p.nsub, c->stream);
-      GHF_HIP(c, hipMemcpyAsync(c->h_u64 + 3, c->d_u64 + 3, 8 * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
-      GHF_HIP(c, hipStreamSynchronize(c->stream));
-#ifdef GHF_K6_TRACE  // (scratch/build_variant.sh k6trace -DGHF_K6_TRACE: what every batch of passes left behind)
-      fprintf(stderr, "[k6] nsub %llu passes %llu scanned %d flag %u moved~%llu first %llu eof_sub %llu\n", (unsigned long long)p.nsub,
-              (unsigned long long)passes, (int)scanned, (unsigned)c->h_u64[9], (unsigned long long)((c->h_u64[9] >> 32) * 256),
-              (unsigned long long)~c->h_u64[10], (unsigned long long)c->h_u64[4]);
-#endif
-      if ((uint32_t)c->h_u64[9] == 0) break;
-      // .crs2: settled IN FRONT OF THE END MARK is settled.  No landing at or before the first end mark's subsequence moved
-      // in the batch's last pass -> every boundary up to it is a fixed point, the mark is the stream's (the first one, and
-      // real).  What lies behind it (a buffer longer than its stream: stale bytes) may go on moving for ever.
-      if (!no_eof && mode != 2 && c->h_u64[10] != 0 && ~c->h_u64[10] >= c->h_u64[4] && c->h_u64[4] < p.nsub) break;
-      const uint64_t moved = (c->h_u64[9] >> 32) * 256;  // boundaries the batch's last pass moved (sampled: every 256th group)
-      // Not settled.  A boundary that is still moving travels ONE subsequence to the right per pass, and a pass in which
-      // little moved costs little (a wave whose 64 subsequences are current skips them), so a few more batches are cheaper
-      // than the deterministic scan over the whole stream -- which long streams of a quickly synchronising code otherwise
-      // fall into because SOME stretch among their millions of subsequences needs a fifth pass (4 GiB Zipf: 44 ms with
-      // the scan after the first batch, see profiles/r04/foreign_4GiB.txt).  Codes that do not settle in kScanAfter passes
-      // (long runs of one value, near-fixed-length codes the caller did not announce) get the scan then.
-      // What decides is HOW MUCH still moves: a few stragglers (one stretch in a 4 GiB Zipf stream needs 17..20 passes,
-      // whichever seed) are followed for up to kScanAfterFew passes; a stream in which boundaries still move everywhere
-      // after two batches is not going to settle by itself.
-      constexpr uint64_t kScanAfterMany = 8, kScanAfterFew = 64;
-      const uint64_t few = p.nsub >> 10 > 4096 ? p.nsub >> 10 : 4096;
-      if (!scanned && (passes >= kScanAfterFew || (passes >= kScanAfterMany && moved > few))) {
-        launch_sync_scan(p, ws + o_scan, fn_stride, first_start, c->stream);
-        scanned = true;
-      }
-    }
-    n = c->h_u64[3];
-    eof_sub = c->h_u64[4];
-    land16 = (uint16_t)c->h_u64[8];
-  }
-  if (no_eof) {
-    // every subsequence counts; a flagged one means bits that are no code or a code running past the end
-    // (eof_sub == nsub, "none", makes the counting kernels take every subsequence: n is already the total)
-    if (eof_sub < p.nsub) return fail(c, GHF_E_CORRUPT, "the .crs body does not end on a code boundary");
-  } else if (mode == 2) {
-    if (has_end_mark) *has_end_mark = eof_sub < p.nsub;
-    if (landing) *landing = land16 == 0xFFFF ? 0 : land16;  // 0xFFFF: the last subsequence ended at an end mark (real, or a fake one of a wrong guess)
-  } else if (eof_sub >= p.nsub) {
-    return fail(c, GHF_E_CORRUPT, "no end mark in the stream");
-  }
-  if (n > cap) return fail(c, GHF_E_CAP, "ghf_decode: output capacity below the decoded size");
-  // size the side-car
-  ghf_index& ix = c->fidx;
-  const uint64_t n_chunks = (n + kBlockSymbols - 1) / kBlockSymbols, n_segs = (n + kSegSymbols - 1) / kSegSymbols;
-  if (n_segs > c->fidx_cap_segs) {
-    if (ix.d_seg_bit) (void)hipFree(ix.d_seg_bit);
-    if (c->d_seg_abs) (void)hipFree(c->d_seg_abs);
-    ix.d_seg_bit = nullptr;
-    c->d_seg_abs = nullptr;
-    c->fidx_cap_segs = 0;
-    GHF_HIP(c, hipMalloc(&ix.d_seg_bit, n_segs * sizeof(uint32_t)));
-    GHF_HIP(c, hipMalloc(&c->d_seg_abs, (n_segs + 1) * sizeof(uint64_t)));
-    c->fidx_cap_segs = n_segs;
-  }
-  if (n_chunks > c->fidx_cap_chunks) {
-    if (ix.d_chunk_bit) (void)hipFree(ix.d_chunk_bit);
-    ix.d_chunk_bit = nullptr;
-    c->fidx_cap_chunks = 0;
-    GHF_HIP(c, hipMalloc(&ix.d_chunk_bit, n_chunks * sizeof(uint64_t)));
-    c->fidx_cap_chunks = n_chunks;
-  }
-  ix.n_symbols = n;
-  ix.chunk_symbols = kBlockSymbols;
-  ix.seg_symbols = kSegSymbols;
-  ix.n_chunks = n_chunks;
-  ix.n_segs = n_segs;
-  ix.flags = (mode == 2 && eof_sub >= p.nsub) ? (uint32_t)GHF_INDEX_NO_END_MARK : 0u;
-  if (n) launch_sync_index(p, c->d_seg_abs, n, ix.d_chunk_bit, ix.d_seg_bit, c->stream);
-  GHF_HIP(c, hipGetLastError());
-  c->fidx_stream = d_stream;
-  c->fidx_bytes = stream_bytes;
+// the depth of a device-resident tree (1..64), for the stride of K6's function rows: 16 / 32 / 64 bytes as for .crs2 -- a
+// shallow tree does not pay for 64-byte rows -- and, where the caller asks for it, tree_bytes; one round trip
+static int crs_tree_shape(ghf_ctx* c, const ghf_tree* d_tree, uint32_t* tree_bytes, int* max_len) {
+  hipError_t e = hipSuccess;
+  if (tree_bytes) e = hipMemcpyAsync(&c->h->tree_bytes, &d_tree->tree_bytes, sizeof(d_tree->tree_bytes), hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(&c->h->tree_max_len, &d_tree->max_len, sizeof(d_tree->max_len), hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  if (e != hipSuccess) return fail(c, GHF_E_HIP, tree_bytes ? "copy tree_bytes to host" : "copy the tree's max_len to host", e);
+  if (tree_bytes) *tree_bytes = c->h->tree_bytes;
+  const uint32_t ml = c->h->tree_max_len;
+  *max_len = (ml >= 1 && ml <= 64) ? (int)ml : 64;  // (anything else is refused by k_crs_decode_tables)
   return GHF_OK;
 }
 
-// Multi-GPU decode of a side-car-less stream: one rank's piece.  Rebuilds the piece's side-car and keeps it
-// for the following ghf_decode(index = NULL) of the same (d_piece, piece_bytes).
-int ghf_sync_piece(ghf_ctx* c, const uint8_t* d_piece, size_t piece_bytes, uint32_t first_bit, uint64_t end_bit,
-                   const ghf_code* d_code, uint64_t* landing, uint64_t* n_symbols, int* has_end_mark) {
-  if (!c || !d_piece || !d_code || !landing || !n_symbols || !has_end_mark) return GHF_E_INVAL;
-  if (!aligned16(d_piece)) return fail(c, GHF_E_INVAL, "d_piece must be 16-byte aligned");
-  if (first_bit >= 512 || end_bit > (uint64_t)piece_bytes * 8 || first_bit > end_bit) return fail(c, GHF_E_INVAL, "ghf_sync_piece: bad first_bit / end_bit");
+// Multi-GPU decode of a side-car-less stream and the file pipeline's .crs pieces: one piece.  Rebuilds the
+// piece's side-car and keeps it for the following decode with index = NULL of the same (d_piece, bytes).
+// ghf_sync_piece (canonical tables at d_code) and ghf_crs_sync_piece (d_tree): one of the two is given.
+// q: the piece, its first_start and end_bit as the caller gave them; the code's shape is filled in here.
+static int sync_piece(ghf_ctx* c, const char* who, RebuildRequest q, const ghf_code* d_code, const ghf_tree* d_tree, RebuildResult* r) {
+  if (!aligned16(q.d_stream)) return fail(c, GHF_E_INVAL, "d_piece must be 16-byte aligned");
+  if (q.first_start >= 512 || q.end_bit > (uint64_t)q.stream_bytes * 8 || q.first_start > q.end_bit)
+    return fail(c, GHF_E_INVAL, (std::string(who) + ": bad first_bit / end_bit").c_str());
   GHF_HIP(c, hipSetDevice(c->device));
-  launch_build_decode_tables(d_code, c->d_dt, c->d_status, c->stream);
-  c->dt_code = nullptr;
-  c->fidx_stream = nullptr;
-  *landing = 0;
-  *n_symbols = 0;
-  *has_end_mark = 0;
-  if (end_bit == 0) {  // nothing of this piece is its own
+  if (d_code) launch_build_decode_tables(d_code, c->d_dt, c->d_status, c->stream);
+  else launch_crs_decode_tables(d_tree, c->d_dt, c->d_status, c->stream);
+  c->prepared.forget();
+  c->rebuilt.forget();
+  if (q.end_bit == 0) {  // nothing of this piece is its own
     c->fidx.n_symbols = 0;
     c->fidx.n_segs = 0;
     c->fidx.n_chunks = 0;
-    c->fidx_stream = d_piece;
-    c->fidx_bytes = piece_bytes;
+    c->rebuilt = {q.d_stream, q.stream_bytes};
     return GHF_OK;
   }
-  // near-fixed-length codes re-synchronise slowly: the deterministic scan seeds the boundaries at once (as in rebuild_index)
-  GHF_HIP(c, hipMemcpyAsync(c->h_u64 + 6, &d_code->min_len, 2 * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-  GHF_HIP(c, hipStreamSynchronize(c->stream));
-  int32_t lens[2];
-  std::memcpy(lens, c->h_u64 + 6, sizeof lens);
-  if (lens[1] < 1 || lens[1] > 32 || lens[0] < 1 || lens[0] > lens[1]) return fail(c, GHF_E_FORMAT, "bad min_len / max_len in tables");
-  const int rc = rebuild_index_at(c, d_piece, piece_bytes, 0, end_bit, 2, (size_t)-1, first_bit, landing, has_end_mark,
-                                  /*prefer_scan=*/lens[1] - lens[0] <= 1, lens[1]);
-  if (rc) return rc;
-  *n_symbols = c->fidx.n_symbols;
-  return GHF_OK;
+  if (d_code) {
+    // near-fixed-length codes re-synchronise slowly: the deterministic scan seeds the boundaries at once (as in rebuild_index)
+    GHF_HIP(c, hipMemcpyAsync(c->h->code_lens, &d_code->min_len, sizeof c->h->code_lens, hipMemcpyDeviceToHost, c->stream));
+    GHF_HIP(c, hipStreamSynchronize(c->stream));
+    const int32_t min_len = c->h->code_lens[0], max_len = c->h->code_lens[1];
+    if (max_len < 1 || max_len > 32 || min_len < 1 || min_len > max_len) return fail(c, GHF_E_FORMAT, "bad min_len / max_len in tables");
+    q.max_len = max_len;
+    q.scan_at_once = max_len - min_len <= 1;
+  } else {
+    const int rc = crs_tree_shape(c, d_tree, nullptr, &q.max_len);
+    if (rc) return rc;
+  }
+  return rebuild_index_at(c, q, r);
+}
+
+int ghf_sync_piece(ghf_ctx* c, const uint8_t* d_piece, size_t piece_bytes, uint32_t first_bit, uint64_t end_bit,
+                   const ghf_code* d_code, uint64_t* landing, uint64_t* n_symbols, int* has_end_mark) {
+  if (!c || !d_piece || !d_code || !landing || !n_symbols || !has_end_mark) return GHF_E_INVAL;
+  RebuildResult r;
+  const int rc = sync_piece(c, "ghf_sync_piece", RebuildRequest{d_piece, piece_bytes, kSyncPiece, end_bit, first_bit}, d_code, nullptr, &r);
+  *landing = r.landing;
+  *n_symbols = r.n;
+  *has_end_mark = r.has_end_mark;
+  return rc;
 }
 
 int ghf_decoded_size(ghf_ctx* c, const uint8_t* d_stream, size_t stream_bytes, const ghf_code* d_code, uint64_t* n_out) {
@@ -809,8 +756,8 @@ int ghf_decoded_size(ghf_ctx* c, const uint8_t* d_stream, size_t stream_bytes, c
   if (!aligned16(d_stream)) return fail(c, GHF_E_INVAL, "d_stream must be 16-byte aligned");
   GHF_HIP(c, hipSetDevice(c->device));
   launch_build_decode_tables(d_code, c->d_dt, c->d_status, c->stream);
-  c->dt_code = nullptr;
-  c->fidx_stream = nullptr;
+  c->prepared.forget();
+  c->rebuilt.forget();
   const int rc = rebuild_index(c, d_stream, stream_bytes, d_code, (size_t)-1);
   if (rc) return rc;
   *n_out = c->fidx.n_symbols;
@@ -822,7 +769,35 @@ int ghf_decode_prepare(ghf_ctx* c, const ghf_code* d_code) {
   GHF_HIP(c, hipSetDevice(c->device));
   launch_build_decode_tables(d_code, c->d_dt, c->d_status, c->stream);
   GHF_HIP(c, hipGetLastError());
-  c->dt_code = d_code;
+  c->prepared = {d_code};
+  return GHF_OK;
+}
+
+// nothing to decode (the end mark comes first: GHF_EMPTY_OK's stream, a shard or a piece that holds nothing; an empty .crs body): no K7
+static int nothing_decoded(ghf_ctx* c, uint64_t* d_out_bytes) {
+  if (d_out_bytes) launch_store_u64(d_out_bytes, nullptr, 0, c->stream);
+  GHF_HIP(c, hipGetLastError());
+  return GHF_OK;
+}
+
+// What ghf_decode and ghf_crs_decode (`who`) share once d_dt is queued and the side-car is chosen: K7.
+// p: stream, stream_bytes, out, out_bytes and no_end_mark as the caller has them; the rest is filled here.
+static int decode_with_index(ghf_ctx* c, const char* who, const ghf_index* index, size_t cap, DecParams p) {
+  const std::string f = std::string(who) + ": ";
+  if (!index_has_arrays(index) || index->n_segs != (index->n_symbols + kSegSymbols - 1) / kSegSymbols ||
+      index->n_chunks != (index->n_symbols + kBlockSymbols - 1) / kBlockSymbols)
+    return fail(c, GHF_E_INVAL, (f + "malformed index").c_str());
+  if (cap < index->n_symbols) return fail(c, GHF_E_CAP, (f + "output capacity below n_symbols").c_str());
+  if (index->n_chunks >= kDecMaxGroups) return fail(c, GHF_E_INVAL, (f + "more than 2^44 symbols in one call").c_str());
+  p.dt = c->d_dt;
+  p.chunk_bit = index->d_chunk_bit;
+  p.seg_bit = index->d_seg_bit;
+  p.n_symbols = index->n_symbols;
+  p.n_segs = index->n_segs;
+  p.status = c->d_status;
+  launch_decode(p, c->stream);
+  if (p.out_bytes && index->n_symbols == 0) launch_store_u64(p.out_bytes, nullptr, 0, c->stream);  // no decode launch then
+  GHF_HIP(c, hipGetLastError());
   return GHF_OK;
 }
 
@@ -831,58 +806,35 @@ int ghf_decode(ghf_ctx* c, const uint8_t* d_stream, size_t stream_bytes, const g
   if (!c || !d_stream || !d_code || !d_out) return GHF_E_INVAL;
   if (!aligned16(d_stream)) return fail(c, GHF_E_INVAL, "d_stream must be 16-byte aligned");
   GHF_HIP(c, hipSetDevice(c->device));
-  if (c->dt_code == d_code && index) c->dt_code = nullptr;  // prepared: single use (the tables also hold this decode's work counters)
-  else {
-    c->dt_code = nullptr;
-    launch_build_decode_tables(d_code, c->d_dt, c->d_status, c->stream);
-  }
+  // prepared: single use (the tables also hold this decode's work counters)
+  if (!(c->prepared.describes(d_code) && index)) launch_build_decode_tables(d_code, c->d_dt, c->d_status, c->stream);
+  c->prepared.forget();
   if (!index) {
-    if (c->fidx_stream != d_stream || c->fidx_bytes != stream_bytes) {  // else: ghf_decoded_size already did it
+    if (!c->rebuilt.describes(d_stream, stream_bytes)) {  // else: ghf_decoded_size / ghf_sync_piece already did it
       const int rc = rebuild_index(c, d_stream, stream_bytes, d_code, cap);
       if (rc) return rc;
     }
-    c->fidx_stream = nullptr;  // single use: the buffer may be rewritten afterwards
+    c->rebuilt.forget();  // single use: the buffer may be rewritten afterwards
     index = &c->fidx;
   }
-  if (index->n_symbols == 0) {  // the end mark comes first (GHF_EMPTY_OK's stream, or a shard that holds nothing): no K7
-    if (d_out_bytes) {
-      launch_store_u64(d_out_bytes, nullptr, 0, c->stream);
-      GHF_HIP(c, hipGetLastError());
-    }
-    return GHF_OK;
-  }
-  if (!index->d_chunk_bit || !index->d_seg_bit || index->seg_symbols != (uint32_t)kSegSymbols ||
-      index->chunk_symbols != (uint32_t)kBlockSymbols || index->n_segs != (index->n_symbols + kSegSymbols - 1) / kSegSymbols ||
-      index->n_chunks != (index->n_symbols + kBlockSymbols - 1) / kBlockSymbols)
-    return fail(c, GHF_E_INVAL, "ghf_decode: malformed index");
-  if (cap < index->n_symbols) return fail(c, GHF_E_CAP, "ghf_decode: output capacity below n_symbols");
-  if (index->n_chunks >= kDecMaxGroups) return fail(c, GHF_E_INVAL, "ghf_decode: more than 2^44 symbols in one call");
-  DecParams p;
+  if (index->n_symbols == 0) return nothing_decoded(c, d_out_bytes);
+  DecParams p = {};
   p.stream = d_stream;
   p.stream_bytes = stream_bytes;
-  p.dt = c->d_dt;
-  p.chunk_bit = index->d_chunk_bit;
-  p.seg_bit = index->d_seg_bit;
-  p.n_symbols = index->n_symbols;
-  p.n_segs = index->n_segs;
   p.no_end_mark = (index->flags & GHF_INDEX_NO_END_MARK) ? 1u : 0u;
   p.out = d_out;
-  p.status = c->d_status;
   p.out_bytes = d_out_bytes;
-  launch_decode(p, c->stream);
-  if (d_out_bytes && index->n_symbols == 0) launch_store_u64(d_out_bytes, nullptr, 0, c->stream);  // no decode launch then
-  GHF_HIP(c, hipGetLastError());
-  return GHF_OK;
+  return decode_with_index(c, "ghf_decode", index, cap, p);
 }
 
 // ---------------------------------------------------------------------------------------------- .crs
 int ghf_crs_build_code(ghf_ctx* c, const uint64_t* d_hist, ghf_tree* d_tree, ghf_code* d_code) {
   if (!c || !d_hist || !d_tree || !d_code) return GHF_E_INVAL;
   GHF_HIP(c, hipSetDevice(c->device));
-  launch_crs_build_code(d_hist, d_tree, d_code, c->d_u64 + 6, c->d_status, c->stream);
+  launch_crs_build_code(d_hist, d_tree, d_code, &c->d->start_bit, c->d_status, c->stream);
   GHF_HIP(c, hipGetLastError());
-  c->plan_in = nullptr;  // d_code changed: a cached plan no longer describes it
-  if (c->dt_code == d_code) c->dt_code = nullptr;  // ... and neither do decode tables prepared from it
+  c->plan.forget();  // d_code changed: a cached plan no longer describes it
+  if (c->prepared.describes(d_code)) c->prepared.forget();  // ... and neither do decode tables prepared from it
   return GHF_OK;
 }
 
@@ -896,11 +848,11 @@ int ghf_crs_compress(ghf_ctx* c, const uint8_t* d_in, size_t n, uint8_t* d_out, 
   ghf_tree* tree = d_tree ? d_tree : c->d_tree;
   int rc;
   if ((rc = ghf_histogram(c, d_in, n, c->d_hist))) return rc;            // compressor.h:63
-  if ((rc = ghf_crs_build_code(c, c->d_hist, tree, c->d_code))) return rc;  // compressor.h:64, start bit -> d_u64[6]
-  if ((rc = ghf_encode_plan(c, d_in, n, c->d_code, c->d_u64))) return rc;
+  if ((rc = ghf_crs_build_code(c, c->d_hist, tree, c->d_code))) return rc;  // compressor.h:64, start bit -> d->start_bit
+  if ((rc = ghf_encode_plan(c, d_in, n, c->d_code, &c->d->total_bits))) return rc;
   // compressor.h:72: the body right behind tree + two prefix bytes; no end mark, zero fill (flags = 0)
-  if ((rc = ghf_encode_emit(c, d_in, n, c->d_code, c->d_u64 + 6, GHF_EMIT_LONG_CODES, d_out, cap, index, c->d_u64 + 1))) return rc;
-  launch_crs_finish(tree, c->d_u64, d_out, d_out_bytes, c->d_status, c->stream);  // compressor.h:70 + normal_huff_encoder.h:176-184
+  if ((rc = ghf_encode_emit(c, d_in, n, c->d_code, &c->d->start_bit, GHF_EMIT_LONG_CODES, d_out, cap, index, c->d->end))) return rc;
+  launch_crs_finish(tree, &c->d->total_bits, d_out, d_out_bytes, c->d_status, c->stream);  // compressor.h:70 + normal_huff_encoder.h:176-184
   GHF_HIP(c, hipGetLastError());
   return GHF_OK;
 }
@@ -965,32 +917,16 @@ int ghf_crs_parse_header(const uint8_t* h, size_t n, ghf_tree* tree, size_t* tre
   return GHF_OK;
 }
 
-// the depth of a device-resident tree (1..64), for the stride of K6's function rows: 16 / 32 / 64 bytes as for .crs2 -- a
-// shallow tree does not pay for 64-byte rows
-static int crs_max_len(ghf_ctx* c, const ghf_tree* d_tree, int* max_len) {
-  hipError_t e = hipMemcpyAsync(c->h_u64 + 9, &d_tree->max_len, sizeof(d_tree->max_len), hipMemcpyDeviceToHost, c->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  if (e != hipSuccess) return fail(c, GHF_E_HIP, "copy the tree's max_len to host", e);
-  uint32_t ml = 0;
-  std::memcpy(&ml, c->h_u64 + 9, sizeof ml);
-  *max_len = (ml >= 1 && ml <= 64) ? (int)ml : 64;  // (anything else is refused by k_crs_decode_tables)
-  return GHF_OK;
-}
-
-static int crs_geometry(ghf_ctx* c, const ghf_tree* d_tree, size_t stream_bytes, int left_bits, size_t* hdr, uint64_t* end_bit, int* max_len) {
+// where the body of a whole .crs lies and how deep its tree is: the request for its side-car (cap is the caller's)
+static int crs_request(ghf_ctx* c, const uint8_t* d_stream, size_t stream_bytes, int left_bits, const ghf_tree* d_tree, RebuildRequest* q) {
   if (left_bits < 0 || left_bits > 7) return fail(c, GHF_E_FORMAT, "left_bits must be 0..7");
-  uint32_t tb = 0, ml = 0;
-  hipError_t e = hipMemcpyAsync(c->h_u64 + 7, &d_tree->tree_bytes, 4, hipMemcpyDeviceToHost, c->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(c->h_u64 + 9, &d_tree->max_len, sizeof(d_tree->max_len), hipMemcpyDeviceToHost, c->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  if (e != hipSuccess) return fail(c, GHF_E_HIP, "copy tree_bytes to host", e);
-  std::memcpy(&tb, c->h_u64 + 7, 4);
-  std::memcpy(&ml, c->h_u64 + 9, 4);
-  *max_len = (ml >= 1 && ml <= 64) ? (int)ml : 64;
+  uint32_t tb = 0;
+  *q = RebuildRequest{d_stream, stream_bytes, kSyncCrs, (uint64_t)stream_bytes * 8 - (uint64_t)left_bits};
+  const int rc = crs_tree_shape(c, d_tree, &tb, &q->max_len);  // (codes up to 64 bits)
+  if (rc) return rc;
   if (tb < 6 || tb > 1022 || (tb & 1)) return fail(c, GHF_E_FORMAT, "bad tree_bytes");
-  *hdr = (size_t)tb + 2;
-  if (stream_bytes < *hdr || (left_bits && stream_bytes == *hdr)) return fail(c, GHF_E_FORMAT, "stream shorter than its header");
-  *end_bit = (uint64_t)stream_bytes * 8 - (uint64_t)left_bits;
+  q->hdr = (size_t)tb + 2;
+  if (stream_bytes < q->hdr || (left_bits && stream_bytes == q->hdr)) return fail(c, GHF_E_FORMAT, "stream shorter than its header");
   return GHF_OK;
 }
 
@@ -999,51 +935,30 @@ int ghf_crs_decoded_size(ghf_ctx* c, const uint8_t* d_stream, size_t stream_byte
   if (!c || !d_stream || !d_tree || !n_out) return GHF_E_INVAL;
   if (!aligned16(d_stream)) return fail(c, GHF_E_INVAL, "d_stream must be 16-byte aligned");
   GHF_HIP(c, hipSetDevice(c->device));
-  size_t hdr;
-  uint64_t end_bit;
-  int depth = 64;
-  int rc = crs_geometry(c, d_tree, stream_bytes, left_bits, &hdr, &end_bit, &depth);
+  RebuildRequest q;
+  int rc = crs_request(c, d_stream, stream_bytes, left_bits, d_tree, &q);
   if (rc) return rc;
   launch_crs_decode_tables(d_tree, c->d_dt, c->d_status, c->stream);
-  c->dt_code = nullptr;
-  if (end_bit == (uint64_t)hdr * 8) {  // an empty body decodes to nothing
-    *n_out = 0;
-    return GHF_OK;
+  c->prepared.forget();
+  RebuildResult r;  // an empty body decodes to nothing
+  if (q.end_bit != (uint64_t)q.hdr * 8) {
+    rc = rebuild_index_at(c, q, &r);
+    if (rc) return rc;
   }
-  rc = rebuild_index_at(c, d_stream, stream_bytes, hdr, end_bit, 1, (size_t)-1, 0, nullptr, nullptr, false, depth);  // (codes up to 64 bits)
-  if (rc) return rc;
-  *n_out = c->fidx.n_symbols;
+  *n_out = r.n;
   return GHF_OK;
 }
 
 int ghf_crs_sync_piece(ghf_ctx* c, const uint8_t* d_piece, size_t piece_bytes, uint32_t first_bit, uint64_t end_bit,
                        const ghf_tree* d_tree, uint64_t* landing, uint64_t* n_symbols) {
   if (!c || !d_piece || !d_tree || !landing || !n_symbols) return GHF_E_INVAL;
-  if (!aligned16(d_piece)) return fail(c, GHF_E_INVAL, "d_piece must be 16-byte aligned");
-  if (first_bit >= 512 || end_bit > (uint64_t)piece_bytes * 8 || first_bit > end_bit) return fail(c, GHF_E_INVAL, "ghf_crs_sync_piece: bad first_bit / end_bit");
-  GHF_HIP(c, hipSetDevice(c->device));
-  launch_crs_decode_tables(d_tree, c->d_dt, c->d_status, c->stream);
-  c->dt_code = nullptr;
-  c->fidx_stream = nullptr;
-  *landing = 0;
-  *n_symbols = 0;
-  if (end_bit == 0) {  // nothing of this piece is its own
-    c->fidx.n_symbols = 0;
-    c->fidx.n_segs = 0;
-    c->fidx.n_chunks = 0;
-    c->fidx_stream = d_piece;
-    c->fidx_bytes = piece_bytes;
-    return GHF_OK;
-  }
-  int bad = 0;  // with the tree's tables "end mark" can only mean: bits that are no code
-  int depth = 64;
-  int rc = crs_max_len(c, d_tree, &depth);
-  if (rc) return rc;
-  rc = rebuild_index_at(c, d_piece, piece_bytes, 0, end_bit, 2, (size_t)-1, first_bit, landing, &bad, false, depth);
-  if (rc) return rc;
-  if (bad) return fail(c, GHF_E_CORRUPT, "the .crs body holds bits that are no code");
-  *n_symbols = c->fidx.n_symbols;
-  return GHF_OK;
+  RebuildResult r;
+  int rc = sync_piece(c, "ghf_crs_sync_piece", RebuildRequest{d_piece, piece_bytes, kSyncPiece, end_bit, first_bit}, nullptr, d_tree, &r);
+  // with the tree's tables "end mark" can only mean: bits that are no code
+  if (!rc && r.has_end_mark) rc = fail(c, GHF_E_CORRUPT, "the .crs body holds bits that are no code");
+  *landing = r.landing;
+  *n_symbols = rc ? 0 : r.n;
+  return rc;
 }
 
 int ghf_crs_decode(ghf_ctx* c, const uint8_t* d_stream, size_t stream_bytes, int left_bits, const ghf_tree* d_tree,
@@ -1052,50 +967,28 @@ int ghf_crs_decode(ghf_ctx* c, const uint8_t* d_stream, size_t stream_bytes, int
   if (!aligned16(d_stream)) return fail(c, GHF_E_INVAL, "d_stream must be 16-byte aligned");
   GHF_HIP(c, hipSetDevice(c->device));
   launch_crs_decode_tables(d_tree, c->d_dt, c->d_status, c->stream);
-  c->dt_code = nullptr;
+  c->prepared.forget();
   if (!index) {
-    if (c->fidx_stream != d_stream || c->fidx_bytes != stream_bytes) {  // else: ghf_crs_decoded_size / ghf_crs_sync_piece did it
-      size_t hdr;
-      uint64_t end_bit;
-      int depth = 64;
-      int rc = crs_geometry(c, d_tree, stream_bytes, left_bits, &hdr, &end_bit, &depth);
+    if (!c->rebuilt.describes(d_stream, stream_bytes)) {  // else: ghf_crs_decoded_size / ghf_crs_sync_piece did it
+      RebuildRequest q;
+      int rc = crs_request(c, d_stream, stream_bytes, left_bits, d_tree, &q);
       if (rc) return rc;
-      if (end_bit == (uint64_t)hdr * 8) {
-        if (d_out_bytes) launch_store_u64(d_out_bytes, nullptr, 0, c->stream);
-        return GHF_OK;
-      }
-      rc = rebuild_index_at(c, d_stream, stream_bytes, hdr, end_bit, 1, cap, 0, nullptr, nullptr, false, depth);
+      if (q.end_bit == (uint64_t)q.hdr * 8) return nothing_decoded(c, d_out_bytes);
+      q.cap = cap;
+      rc = rebuild_index_at(c, q, nullptr);
       if (rc) return rc;
     }
-    c->fidx_stream = nullptr;
+    c->rebuilt.forget();
     index = &c->fidx;
-    if (index->n_symbols == 0) {
-      if (d_out_bytes) launch_store_u64(d_out_bytes, nullptr, 0, c->stream);
-      return GHF_OK;
-    }
+    if (index->n_symbols == 0) return nothing_decoded(c, d_out_bytes);
   }
-  if (!index->d_chunk_bit || !index->d_seg_bit || index->seg_symbols != (uint32_t)kSegSymbols ||
-      index->chunk_symbols != (uint32_t)kBlockSymbols || index->n_segs != (index->n_symbols + kSegSymbols - 1) / kSegSymbols ||
-      index->n_chunks != (index->n_symbols + kBlockSymbols - 1) / kBlockSymbols)
-    return fail(c, GHF_E_INVAL, "ghf_crs_decode: malformed index");
-  if (cap < index->n_symbols) return fail(c, GHF_E_CAP, "ghf_crs_decode: output capacity below n_symbols");
-  if (index->n_chunks >= kDecMaxGroups) return fail(c, GHF_E_INVAL, "ghf_crs_decode: more than 2^44 symbols in one call");
-  DecParams p;
+  DecParams p = {};
   p.stream = d_stream;
   p.stream_bytes = stream_bytes;
-  p.dt = c->d_dt;
-  p.chunk_bit = index->d_chunk_bit;
-  p.seg_bit = index->d_seg_bit;
-  p.n_symbols = index->n_symbols;
-  p.n_segs = index->n_segs;
   p.no_end_mark = 1u;  // there is none in this format; the end of every segment but the last is checked against the side-car
   p.out = d_out;
-  p.status = c->d_status;
   p.out_bytes = d_out_bytes;
-  launch_decode(p, c->stream);
-  if (d_out_bytes && index->n_symbols == 0) launch_store_u64(d_out_bytes, nullptr, 0, c->stream);
-  GHF_HIP(c, hipGetLastError());
-  return GHF_OK;
+  return decode_with_index(c, "ghf_crs_decode", index, cap, p);
 }
 
 }  // extern "C"

@@ -13,7 +13,7 @@
 #include <string>
 #include <vector>
 
-#include "ghf_internal.h"
+#include "ghf_ctx.h"
 
 using namespace ghf;
 
@@ -67,18 +67,10 @@ Rccl* rccl() {
 
 }  // namespace
 
-// from ghf_api.hip
-int ghf_api_fail(ghf_ctx* c, int code, const char* what);
-hipStream_t ghf_api_stream(ghf_ctx* c);
-int ghf_api_device(ghf_ctx* c);
-uint64_t* ghf_api_scratch_u64(ghf_ctx* c);  // [8] device scalars
-uint64_t* ghf_api_hist(ghf_ctx* c);         // [257] device
-uint64_t* ghf_api_totals(ghf_ctx* c, int world);  // [world] device, grown on demand
-
 #define GHF_NCCL(c, call)                                                                         \
   do {                                                                                            \
     ncclResult_t r_ = (call);                                                                     \
-    if (r_ != ncclSuccess) return ghf_api_fail((c), GHF_E_HIP, (std::string(#call ": ") + R->GetErrorString(r_)).c_str()); \
+    if (r_ != ncclSuccess) return fail((c), GHF_E_HIP, (std::string(#call ": ") + R->GetErrorString(r_)).c_str()); \
   } while (0)
 
 extern "C" {
@@ -103,8 +95,8 @@ int ghf_comm_init_rank(ghf_ctx* c, const uint8_t id[GHF_COMM_ID_BYTES], int worl
   if (!c || !id || !out || world < 1 || rank < 0 || rank >= world) return GHF_E_INVAL;
   *out = nullptr;
   Rccl* R = rccl();
-  if (!R) return ghf_api_fail(c, GHF_E_HIP, "RCCL is not available in this process");
-  if (hipSetDevice(ghf_api_device(c)) != hipSuccess) return ghf_api_fail(c, GHF_E_HIP, "hipSetDevice");
+  if (!R) return fail(c, GHF_E_HIP, "RCCL is not available in this process");
+  if (hipSetDevice(c->device) != hipSuccess) return fail(c, GHF_E_HIP, "hipSetDevice");
   ghf_comm* m = new (std::nothrow) ghf_comm();
   if (!m) return GHF_E_NOMEM;
   ncclUniqueId u;
@@ -112,7 +104,7 @@ int ghf_comm_init_rank(ghf_ctx* c, const uint8_t id[GHF_COMM_ID_BYTES], int worl
   const ncclResult_t r = R->CommInitRank(&m->comm, world, u, rank);
   if (r != ncclSuccess) {
     delete m;
-    return ghf_api_fail(c, GHF_E_HIP, (std::string("ncclCommInitRank: ") + R->GetErrorString(r)).c_str());
+    return fail(c, GHF_E_HIP, (std::string("ncclCommInitRank: ") + R->GetErrorString(r)).c_str());
   }
   m->world = world;
   m->rank = rank;
@@ -138,21 +130,21 @@ int ghf_comm_allreduce_hist(ghf_ctx* c, ghf_comm* m, uint64_t* d_hist) {
   if (!c || !d_hist) return GHF_E_INVAL;
   if (!m || m->world == 1) return GHF_OK;
   Rccl* R = rccl();
-  if (!R) return ghf_api_fail(c, GHF_E_HIP, "RCCL is not available in this process");
+  if (!R) return fail(c, GHF_E_HIP, "RCCL is not available in this process");
   // 256 counts; the end-mark slot [256] == 1 on every rank must not be summed (include/encoder.h:128)
-  GHF_NCCL(c, R->AllReduce(d_hist, d_hist, 256, ncclUint64, ncclSum, m->comm, ghf_api_stream(c)));
+  GHF_NCCL(c, R->AllReduce(d_hist, d_hist, 256, ncclUint64, ncclSum, m->comm, c->stream));
   return GHF_OK;
 }
 
 int ghf_comm_allgather_total(ghf_ctx* c, ghf_comm* m, const uint64_t* d_total, uint64_t* d_totals) {
   if (!c || !d_total || !d_totals) return GHF_E_INVAL;
   if (!m || m->world == 1) {
-    launch_store_u64(d_totals, d_total, 0, ghf_api_stream(c));
+    launch_store_u64(d_totals, d_total, 0, c->stream);
     return GHF_OK;
   }
   Rccl* R = rccl();
-  if (!R) return ghf_api_fail(c, GHF_E_HIP, "RCCL is not available in this process");
-  GHF_NCCL(c, R->AllGather(d_total, d_totals, 1, ncclUint64, m->comm, ghf_api_stream(c)));
+  if (!R) return fail(c, GHF_E_HIP, "RCCL is not available in this process");
+  GHF_NCCL(c, R->AllGather(d_total, d_totals, 1, ncclUint64, m->comm, c->stream));
   return GHF_OK;
 }
 
@@ -163,17 +155,17 @@ size_t ghf_shard_bound(size_t n) {
 
 int ghf_shard_bytes(ghf_ctx* c, const ghf_code* d_code, const uint64_t* d_totals, int world, int rank, size_t* bytes) {
   if (!c || !d_code || !d_totals || !bytes || world < 1 || world > 4096 || rank < 0 || rank >= world) return GHF_E_INVAL;
-  if (hipSetDevice(ghf_api_device(c)) != hipSuccess) return ghf_api_fail(c, GHF_E_HIP, "hipSetDevice");
+  if (hipSetDevice(c->device) != hipSuccess) return fail(c, GHF_E_HIP, "hipSetDevice");
   std::vector<uint64_t> tot((size_t)world);
   int32_t lens[2] = {0, 0};  // min_len, max_len
   uint32_t eof_len = 0;
-  hipStream_t s = ghf_api_stream(c);
+  hipStream_t s = c->stream;
   hipError_t e = hipMemcpyAsync(tot.data(), d_totals, sizeof(uint64_t) * (size_t)world, hipMemcpyDeviceToHost, s);
   if (e == hipSuccess) e = hipMemcpyAsync(lens, &d_code->min_len, sizeof lens, hipMemcpyDeviceToHost, s);
   if (e == hipSuccess) e = hipMemcpyAsync(&eof_len, &d_code->length[GHF_NSYM - 1], sizeof eof_len, hipMemcpyDeviceToHost, s);
   if (e == hipSuccess) e = hipStreamSynchronize(s);
-  if (e != hipSuccess) return ghf_api_fail(c, GHF_E_HIP, "ghf_shard_bytes: copy totals / code lengths to host");
-  if (lens[1] < 1 || lens[1] > 32 || eof_len > 32) return ghf_api_fail(c, GHF_E_FORMAT, "ghf_shard_bytes: bad max_len in tables");
+  if (e != hipSuccess) return fail(c, GHF_E_HIP, "ghf_shard_bytes: copy totals / code lengths to host");
+  if (lens[1] < 1 || lens[1] > 32 || eof_len > 32) return fail(c, GHF_E_FORMAT, "ghf_shard_bytes: bad max_len in tables");
   // the arithmetic of K5's emit_begin (ghf_emit.hip): the shard's first bit, its last, the 16-byte units between
   uint64_t start = 8ull * (1040ull + 8ull * (uint64_t)lens[1]);
   for (int h = 0; h < rank; ++h) start += tot[(size_t)h];
@@ -189,17 +181,14 @@ int ghf_encode_sharded(ghf_ctx* c, ghf_comm* m, const uint8_t* d_in, size_t n, u
   if (!c || !d_out || !d_code || (n && !d_in)) return GHF_E_INVAL;
   const int world = m ? m->world : 1, rank = m ? m->rank : 0;
   int rc;
-  uint64_t* d_hist = ghf_api_hist(c);
-  uint64_t* d_u64 = ghf_api_scratch_u64(c);
-  uint64_t* d_totals = ghf_api_totals(c, world);
-  if (!d_totals) return GHF_E_NOMEM;
-  if ((rc = ghf_histogram(c, d_in, n, d_hist))) return rc;                  // K1, local
-  if ((rc = ghf_comm_allreduce_hist(c, m, d_hist))) return rc;               // 2 KiB over xGMI
-  if ((rc = ghf_build_code(c, d_hist, d_code))) return rc;                   // K2/K3 redundantly: deterministic, no broadcast
-  if ((rc = ghf_encode_plan(c, d_in, n, d_code, d_u64))) return rc;          // K4, local: body bits of this shard
-  if ((rc = ghf_comm_allgather_total(c, m, d_u64, d_totals))) return rc;     // 8 B per rank
-  uint64_t* start = d_start_bit ? d_start_bit : d_u64 + 6;
-  if ((rc = ghf_shard_start_bit(c, d_code, d_totals, world, rank, start))) return rc;
+  if (grow(c, c->totals, (size_t)world, 8)) return GHF_E_NOMEM;
+  if ((rc = ghf_histogram(c, d_in, n, c->d_hist))) return rc;                          // K1, local
+  if ((rc = ghf_comm_allreduce_hist(c, m, c->d_hist))) return rc;                       // 2 KiB over xGMI
+  if ((rc = ghf_build_code(c, c->d_hist, d_code))) return rc;                           // K2/K3 redundantly: deterministic, no broadcast
+  if ((rc = ghf_encode_plan(c, d_in, n, d_code, &c->d->total_bits))) return rc;         // K4, local: body bits of this shard
+  if ((rc = ghf_comm_allgather_total(c, m, &c->d->total_bits, c->totals.p))) return rc; // 8 B per rank
+  uint64_t* start = d_start_bit ? d_start_bit : &c->d->start_bit;
+  if ((rc = ghf_shard_start_bit(c, d_code, c->totals.p, world, rank, start))) return rc;
   int flags = 0;
   if (rank == world - 1) flags |= GHF_EMIT_LAST;
   if (rank > 0) flags |= GHF_EMIT_REBASE;

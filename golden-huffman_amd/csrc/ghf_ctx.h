@@ -1,0 +1,169 @@
+// golden-huffman_amd/csrc/ghf_ctx.h -- the context behind the C ABI of include/ghf.h.  Host-only and private to
+// ghf_api.hip and ghf_comm.hip: what a ghf_ctx owns on the device, and what its workspace currently describes.
+#ifndef GHF_CTX_H_
+#define GHF_CTX_H_
+#include <algorithm>
+#include <cstddef>
+#include <string>
+
+#include "ghf_internal.h"
+
+namespace ghf {
+
+// ---- scalars the kernels leave for the host or for each other ------------------------------------------------------
+// One copy on the device (ghf_ctx::d) and a pinned mirror of the same type (ghf_ctx::h).  Every member a kernel
+// writes is 8 bytes wide, so every device address handed out is 8-byte aligned.
+
+// what one pass of K6 says about itself.  k_sync_pass raises `changed`, counts and takes the maximum in place, so the
+// host clears all three with ONE memset in front of every pass: they stay adjacent, in this order.
+struct K6Moved {
+  uint32_t changed[2];               // [0] some guess moved during the pass; [1] how many did, roughly
+  unsigned long long first_inv;      // ~(smallest subsequence whose landing moved); 0: none
+};
+static_assert(sizeof(K6Moved) == 16 && offsetof(K6Moved, first_inv) == 8, "one 16-byte memset clears flag, count and first");
+
+// what the host reads behind every batch of K6 passes, in ONE copy of sizeof(K6Readback).  The block keeps the 64 bytes
+// and the place (24 bytes behind a 256-byte boundary) it has always had: the runtime chooses the kernel that copies it
+// by size and alignment, and a block cut to its members, or moved to a 64-byte boundary, is copied by another launch.
+struct K6Readback {
+  uint64_t n_symbols;  // k_sync_counts: codes in front of the end mark (or in the whole body)
+  uint64_t eof_sub;    // first subsequence holding the end mark; nsub: none
+  uint64_t unused[3];
+  uint64_t landing;    // start[nsub]: bits the last code runs past end_bit (0xFFFF: it ended at an end mark)
+  K6Moved moved;       // of the batch's last pass
+};
+static_assert(sizeof(K6Readback) == 64 && offsetof(K6Readback, moved) % 8 == 0, "one 64-byte copy; 64-bit atomics on moved.first_inv");
+
+struct Scalars {
+  uint64_t total_bits;  // K4: body bits of the planned input
+  uint64_t end[2];      // K5's d_end: {absolute end bit, bytes} of what ghf_compress / ghf_crs_compress emitted
+  K6Readback k6;
+  uint64_t start_bit;   // .crs: the body's first bit (k_crs_build_code); ghf_encode_sharded: the shard's, unless the caller keeps it
+  // the pinned mirror only: where small reads from device-resident tables land
+  int32_t code_lens[2];   // ghf_code::{min_len, max_len}
+  uint32_t tree_bytes;    // ghf_tree::tree_bytes
+  uint32_t tree_max_len;  // ghf_tree::max_len
+};
+static_assert(offsetof(Scalars, end) % 8 == 0 && offsetof(Scalars, k6) == 24 && offsetof(Scalars, start_bit) % 8 == 0,
+              "8-byte aligned device scalars; the read-back where it has always been");
+
+// ---- buffers that grow on demand ------------------------------------------------------------------------------------
+template <class T>
+struct DevBuf {
+  T* p = nullptr;
+  size_t cap = 0;  // in elements
+};
+
+template <class T>
+void release(DevBuf<T>& b) {
+  if (b.p) (void)hipFree(b.p);
+  b.p = nullptr;
+  b.cap = 0;
+}
+
+// ---- what the workspace currently describes ---------------------------------------------------------------------------
+// Each cache sits beside the rule that empties it; a forgotten cache describes nothing (`in` / `code` / `stream` null).
+
+// chunk_hist holds K1's per-chunk histograms of (in, n) cut into chunks of `chunk` symbols: K4 need not count again.
+// Forgotten when chunk_hist is replaced, and by ghf_histogram_add (a piece's buffer is refilled before anything is planned).
+struct HistCache {
+  const uint8_t* in = nullptr;
+  uint64_t n = 0;
+  uint32_t chunk = 0;
+  bool describes(const uint8_t* in_, uint64_t n_, uint32_t chunk_) const { return in == in_ && n == n_ && chunk == chunk_; }
+  void forget() { in = nullptr; }
+};
+
+// chunk_off holds K4's plan of (in, n) under the tables at `code`: what ghf_encode_emit requires.
+// Forgotten when chunk_off is replaced and when the tables at `code` are rebuilt.
+struct PlanCache {
+  const uint8_t* in = nullptr;
+  uint64_t n = 0;
+  const ghf_code* code = nullptr;
+  bool describes(const uint8_t* in_, uint64_t n_, const ghf_code* code_) const { return in == in_ && n == n_ && code == code_; }
+  void forget() { in = nullptr; }
+};
+
+// d_dt holds the decode tables ghf_decode_prepare built from `code`, for ONE following indexed ghf_decode (the tables
+// also hold that decode's work counters).  Forgotten by whatever else writes d_dt and when the tables at `code` are rebuilt.
+struct PreparedTables {
+  const ghf_code* code = nullptr;
+  bool describes(const ghf_code* code_) const { return code == code_; }
+  void forget() { code = nullptr; }
+};
+
+// fidx is the side-car K6 rebuilt for (stream, bytes), for ONE following decode with index = NULL (the buffer may be
+// rewritten afterwards).  Forgotten by every call that is about to rebuild it.
+struct RebuiltIndex {
+  const uint8_t* stream = nullptr;
+  size_t bytes = 0;
+  bool describes(const uint8_t* stream_, size_t bytes_) const { return stream == stream_ && bytes == bytes_; }
+  void forget() { stream = nullptr; }
+};
+
+}  // namespace ghf
+
+struct ghf_ctx {
+  int device = 0;
+  hipStream_t own_stream = nullptr;
+  hipStream_t stream = nullptr;
+  int* d_status = nullptr;
+  int* h_status = nullptr;  // pinned
+  ghf::Scalars* d = nullptr;
+  ghf::Scalars* h = nullptr;  // pinned
+  uint64_t* d_hist = nullptr;      // [257]
+  uint64_t* d_hist_acc = nullptr;  // K1's replicated totals + arrival counter, zero between launches
+  ghf_code* d_code = nullptr;      // scratch tables for ghf_compress
+  ghf_tree* d_tree = nullptr;      // scratch tree for ghf_crs_compress
+  ghf::DecTables* d_dt = nullptr;
+  ghf::PreparedTables prepared;
+  // encode workspace
+  ghf::DevBuf<uint32_t> chunk_hist;  // [chunks][256]
+  ghf::HistCache hist;
+  ghf::DevBuf<uint64_t> chunk_off;   // [chunks + 1]
+  ghf::PlanCache plan;
+  ghf::DevBuf<uint64_t> totals;      // per-rank body bits (ghf_encode_sharded)
+  // K6 workspace (foreign streams) and the side-car it rebuilds; fidx.d_seg_bit / d_chunk_bit mirror seg_bit.p / chunk_bit.p
+  ghf::DevBuf<uint8_t> sync;
+  ghf::DevBuf<uint32_t> seg_bit;
+  ghf::DevBuf<uint64_t> seg_abs;     // [segments + 1]
+  ghf::DevBuf<uint64_t> chunk_bit;
+  ghf_index fidx = {};
+  ghf::RebuiltIndex rebuilt;
+  std::string err;
+};
+
+namespace ghf {
+
+inline int fail(ghf_ctx* c, int code, const char* what, hipError_t e = hipSuccess) {
+  if (c) {
+    c->err = what;
+    if (e != hipSuccess) {
+      c->err += ": ";
+      c->err += hipGetErrorString(e);
+    }
+  }
+  return code;
+}
+
+#define GHF_HIP(c, call)                                         \
+  do {                                                           \
+    hipError_t e_ = (call);                                      \
+    if (e_ != hipSuccess) return fail((c), GHF_E_HIP, #call, e_); \
+  } while (0)
+
+// Makes room for `need` elements: a buffer that is too small is freed and replaced by one of max(need, floor).
+// *replaced is set when a new buffer is in place -- whatever described the old one is gone.
+template <class T>
+int grow(ghf_ctx* c, DevBuf<T>& b, size_t need, size_t floor = 0, bool* replaced = nullptr) {
+  if (need <= b.cap) return GHF_OK;
+  release(b);
+  const size_t cap = std::max(need, floor);
+  GHF_HIP(c, hipMalloc(&b.p, cap * sizeof(T)));
+  b.cap = cap;
+  if (replaced) *replaced = true;
+  return GHF_OK;
+}
+
+}  // namespace ghf
+#endif

@@ -115,6 +115,11 @@ struct DecParams {
 };
 
 // K6: side-car reconstruction for foreign streams
+enum SyncKind : uint32_t {  // what SyncParams::no_eof carries
+  kSyncCrs2 = 0,   // a whole .crs2: ends with the end mark
+  kSyncCrs = 1,    // a whole .crs: no end mark, the last code must end exactly at end_bit
+  kSyncPiece = 2,  // a piece of a stream (multi-GPU / file pipeline): see SyncParams::no_eof
+};
 struct SyncParams {
   const uint8_t* stream;
   uint64_t stream_bytes;
