@@ -116,6 +116,8 @@ int ghf_ctx_destroy(ghf_ctx* c) {
   release(c->seg_bit);
   release(c->seg_abs);
   release(c->chunk_bit);
+  release(c->range_seg);
+  release(c->range_chunk);
   if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
   delete c;
   return GHF_OK;
@@ -825,6 +827,191 @@ int ghf_decode(ghf_ctx* c, const uint8_t* d_stream, size_t stream_bytes, const g
   p.out = d_out;
   p.out_bytes = d_out_bytes;
   return decode_with_index(c, "ghf_decode", index, cap, p);
+}
+
+// ---------------------------------------------------------------------------------------------- seek table
+// (no reference counterpart; the format: DESIGN.md "Seekable .crs2")
+size_t ghf_seek_bytes(size_t n_symbols) { return kSeekHeaderBytes + kSeekRecordBytes * (size_t)seek_blocks_for(n_symbols); }
+
+static inline uint32_t le32(const uint8_t* p) {
+  return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
+}
+static inline uint64_t le64(const uint8_t* p) { return (uint64_t)le32(p) | ((uint64_t)le32(p + 4) << 32); }
+
+int ghf_seek_parse(const uint8_t* h, size_t bytes, ghf_seek_info* info) {
+  if (!h || !info) return GHF_E_INVAL;
+  std::memset(info, 0, sizeof *info);
+  if (bytes < kSeekHeaderBytes) return GHF_E_FORMAT;
+  if (le64(h) != kSeekMagic || le32(h + 8) != kSeekVersion) return GHF_E_FORMAT;
+  const uint32_t flags = le32(h + 12);
+  const uint64_t n = le64(h + 16), n_blocks = le64(h + 32);
+  if (flags & ~(uint32_t)GHF_INDEX_NO_END_MARK) return GHF_E_FORMAT;
+  if (le32(h + 24) != (uint32_t)kBlockSymbols || le32(h + 28) != (uint32_t)kRunSymbols) return GHF_E_FORMAT;
+  if (n_blocks != seek_blocks_for(n) || n_blocks >= kDecMaxGroups) return GHF_E_FORMAT;
+  for (size_t i = 40; i < kSeekHeaderBytes; ++i)
+    if (h[i]) return GHF_E_FORMAT;
+  if (bytes != kSeekHeaderBytes + kSeekRecordBytes * (size_t)n_blocks) return GHF_E_FORMAT;  // truncated, or something behind it
+  info->n_symbols = n;
+  info->n_blocks = n_blocks;
+  info->flags = flags;
+  info->version = kSeekVersion;
+  return GHF_OK;
+}
+
+// the part of "this info describes a table of table_bytes" that every consumer of (info, d_table) asks for
+static int seek_table_ok(ghf_ctx* c, const char* who, const ghf_seek_info* info, const uint8_t* d_table, size_t table_bytes) {
+  const std::string f = std::string(who) + ": ";
+  if (!aligned16(d_table)) return fail(c, GHF_E_INVAL, (f + "d_table must be 16-byte aligned").c_str());
+  if (info->version != kSeekVersion || (info->flags & ~(uint32_t)GHF_INDEX_NO_END_MARK) || info->n_blocks != seek_blocks_for(info->n_symbols) ||
+      info->n_blocks >= kDecMaxGroups || table_bytes != ghf_seek_bytes(info->n_symbols))
+    return fail(c, GHF_E_FORMAT, (f + "the seek table does not have the size its header implies").c_str());
+  return GHF_OK;
+}
+
+static bool index_is_whole(const ghf_index* ix) {
+  return index_has_arrays(ix) && ix->n_segs == (ix->n_symbols + kSegSymbols - 1) / kSegSymbols &&
+         ix->n_chunks == (ix->n_symbols + kBlockSymbols - 1) / kBlockSymbols && ix->n_chunks < kDecMaxGroups;
+}
+
+int ghf_seek_pack(ghf_ctx* c, const ghf_index* index, const uint8_t* d_stream, size_t stream_bytes, uint8_t* d_table, size_t cap) {
+  if (!c || !d_table) return GHF_E_INVAL;
+  if (!aligned16(d_table) || !aligned16(d_stream)) return fail(c, GHF_E_INVAL, "ghf_seek_pack: d_stream and d_table must be 16-byte aligned");
+  if (!index) {  // the side-car K6 last rebuilt on this context, while it still describes this buffer
+    if (!d_stream || !c->rebuilt.describes(d_stream, stream_bytes))
+      return fail(c, GHF_E_INVAL, "ghf_seek_pack: no rebuilt side-car for this stream (call ghf_decoded_size first)");
+    index = &c->fidx;
+  }
+  if (index->n_symbols != 0 && !index_is_whole(index)) return fail(c, GHF_E_INVAL, "ghf_seek_pack: malformed index");
+  if (cap < ghf_seek_bytes(index->n_symbols)) return fail(c, GHF_E_CAP, "ghf_seek_pack: table capacity below ghf_seek_bytes(n_symbols)");
+  GHF_HIP(c, hipSetDevice(c->device));
+  SeekPackParams p = {};
+  p.chunk_bit = index->d_chunk_bit;
+  p.seg_bit = index->d_seg_bit;
+  p.n_symbols = index->n_symbols;
+  p.n_blocks = seek_blocks_for(index->n_symbols);
+  p.n_segs = (index->n_symbols + kSegSymbols - 1) / kSegSymbols;
+  p.flags = index->flags & (uint32_t)GHF_INDEX_NO_END_MARK;
+  p.table = d_table;
+  p.status = c->d_status;
+  launch_seek_pack(p, c->stream);
+  GHF_HIP(c, hipGetLastError());
+  return GHF_OK;
+}
+
+// queues k_seek_expand for blocks [g0, g1) of the table; d_dt must already be queued
+static void expand_blocks(ghf_ctx* c, const ghf_seek_info* info, const uint8_t* d_table, const uint8_t* d_stream, size_t stream_bytes,
+                          uint64_t g0, uint64_t g1, uint64_t* d_chunk_bit, uint32_t* d_seg_bit) {
+  SeekExpandParams p = {};
+  p.records = d_table + kSeekHeaderBytes;
+  p.stream = d_stream;
+  p.stream_bytes = stream_bytes;
+  p.dt = c->d_dt;
+  p.n_symbols = info->n_symbols;
+  p.n_blocks = info->n_blocks;
+  p.g0 = g0;
+  p.g1 = g1;
+  p.chunk_bit = d_chunk_bit;
+  p.seg_bit = d_seg_bit;
+  p.status = c->d_status;
+  launch_seek_expand(p, c->stream);
+}
+
+int ghf_seek_expand(ghf_ctx* c, const ghf_seek_info* info, const uint8_t* d_table, size_t table_bytes, const uint8_t* d_stream,
+                    size_t stream_bytes, const ghf_code* d_code, ghf_index* index) {
+  if (!c || !info || !d_table || !d_stream || !d_code || !index) return GHF_E_INVAL;
+  if (!aligned16(d_stream)) return fail(c, GHF_E_INVAL, "ghf_seek_expand: d_stream must be 16-byte aligned");
+  int rc = seek_table_ok(c, "ghf_seek_expand", info, d_table, table_bytes);
+  if (rc) return rc;
+  if (index->n_symbols != info->n_symbols || (info->n_symbols != 0 && !index_is_whole(index)))
+    return fail(c, GHF_E_INVAL, "ghf_seek_expand: the index was not allocated for the table's n_symbols");
+  GHF_HIP(c, hipSetDevice(c->device));
+  index->flags = info->flags;
+  if (info->n_blocks == 0) return GHF_OK;
+  launch_build_decode_tables(d_code, c->d_dt, c->d_status, c->stream);
+  c->prepared.forget();
+  expand_blocks(c, info, d_table, d_stream, stream_bytes, 0, info->n_blocks, index->d_chunk_bit, index->d_seg_bit);
+  GHF_HIP(c, hipGetLastError());
+  return GHF_OK;
+}
+
+int ghf_decode_range(ghf_ctx* c, const uint8_t* d_stream, size_t stream_bytes, const ghf_code* d_code, const ghf_index* index,
+                     const ghf_seek_info* info, const uint8_t* d_table, size_t table_bytes, uint64_t first, uint64_t count,
+                     uint8_t* d_out, size_t cap) {
+  if (!c || !d_stream || !d_code) return GHF_E_INVAL;
+  if (!aligned16(d_stream)) return fail(c, GHF_E_INVAL, "ghf_decode_range: d_stream must be 16-byte aligned");
+  const bool by_table = info || d_table;
+  if ((index != nullptr) == by_table || (by_table && !(info && d_table)))
+    return fail(c, GHF_E_INVAL, "ghf_decode_range: exactly one of index / (info, d_table) must be given");
+  uint64_t n = 0;
+  uint32_t flags = 0;
+  if (by_table) {
+    const int rc = seek_table_ok(c, "ghf_decode_range", info, d_table, table_bytes);
+    if (rc) return rc;
+    n = info->n_symbols;
+    flags = info->flags;
+  } else {
+    if (index->n_symbols != 0 && !index_is_whole(index)) return fail(c, GHF_E_INVAL, "ghf_decode_range: malformed index");
+    n = index->n_symbols;
+    flags = index->flags;
+  }
+  if (first > n || count > n - first) return fail(c, GHF_E_INVAL, "ghf_decode_range: first + count exceeds n_symbols");
+  if (cap < count) return fail(c, GHF_E_CAP, "ghf_decode_range: output capacity below count");
+  if (count == 0) return GHF_OK;
+  if (!d_out) return GHF_E_INVAL;
+  GHF_HIP(c, hipSetDevice(c->device));
+  const uint64_t end = first + count;
+  const uint64_t gA = first / kBlockSymbols, gB = (end + kBlockSymbols - 1) / kBlockSymbols;  // the covered blocks [gA, gB)
+  launch_build_decode_tables(d_code, c->d_dt, c->d_status, c->stream);
+  c->prepared.forget();
+  const uint64_t* chunk_bit;
+  const uint32_t* seg_bit;
+  if (by_table) {  // only the covered blocks are expanded
+    int rc = grow(c, c->range_chunk, gB - gA, 1024);
+    if (!rc) rc = grow(c, c->range_seg, (gB - gA) * (kBlockSymbols / kSegSymbols), 1024 * 64);
+    if (rc) return rc;
+    expand_blocks(c, info, d_table, d_stream, stream_bytes, gA, gB, c->range_chunk.p, c->range_seg.p);
+    chunk_bit = c->range_chunk.p;
+    seg_bit = c->range_seg.p;
+  } else {
+    chunk_bit = index->d_chunk_bit + gA;
+    seg_bit = index->d_seg_bit + gA * (kBlockSymbols / kSegSymbols);
+  }
+  uint64_t gI = gA;  // the first block K7 takes
+  if (first % kBlockSymbols) {
+    DecHeadParams h = {};
+    h.stream = d_stream;
+    h.stream_bytes = stream_bytes;
+    h.dt = c->d_dt;
+    h.chunk_bit = chunk_bit;
+    h.seg_bit = seg_bit;
+    h.blk_sym0 = gA * kBlockSymbols;
+    h.n_symbols = n;
+    h.lo = first;
+    h.hi = std::min<uint64_t>(end, (gA + 1) * kBlockSymbols);
+    h.out = d_out;
+    h.status = c->d_status;
+    launch_decode_head(h, c->stream);
+    gI = gA + 1;
+  }
+  if (end > gI * kBlockSymbols) {
+    // K7 on a view of the side-car that begins at block gI and ends with the range: a segment's start depends on its own
+    // block only.  The view's last segment may be cut short by the range; only the stream's own end is followed by the end mark.
+    DecParams p = {};
+    p.stream = d_stream;
+    p.stream_bytes = stream_bytes;
+    p.dt = c->d_dt;
+    p.chunk_bit = chunk_bit + (gI - gA);
+    p.seg_bit = seg_bit + (gI - gA) * (kBlockSymbols / kSegSymbols);
+    p.n_symbols = end - gI * kBlockSymbols;
+    p.n_segs = (p.n_symbols + kSegSymbols - 1) / kSegSymbols;
+    p.no_end_mark = (end == n && !(flags & GHF_INDEX_NO_END_MARK)) ? 0u : 1u;
+    p.out = d_out + (gI * kBlockSymbols - first);
+    p.out_bytes = nullptr;
+    p.status = c->d_status;
+    launch_decode(p, c->stream);
+  }
+  GHF_HIP(c, hipGetLastError());
+  return GHF_OK;
 }
 
 // ---------------------------------------------------------------------------------------------- .crs

@@ -130,6 +130,9 @@ struct ghf_ctx {
   ghf::DevBuf<uint64_t> chunk_bit;
   ghf_index fidx = {};
   ghf::RebuiltIndex rebuilt;
+  // ghf_decode_range from a seek table: the side-car of the covered blocks only (describes nothing between calls)
+  ghf::DevBuf<uint32_t> range_seg;
+  ghf::DevBuf<uint64_t> range_chunk;
   std::string err;
 };
 

@@ -114,6 +114,52 @@ struct DecParams {
   int* status;
 };
 
+// ---- the seek table: the persistent form of the side-car (DESIGN.md "Seekable .crs2") ---------------------------------
+// 64-byte header, then one 24-byte record per block: u64 start_bit (= chunk_bit), u16 run_bits[8] (bit lengths of the
+// block's eight runs of 512 symbols).  All little-endian.
+constexpr int kRunSymbols = 512;
+constexpr int kRunsPerBlock = kBlockSymbols / kRunSymbols;  // 8
+constexpr int kRunSegs = kRunSymbols / kSegSymbols;         // 8
+constexpr size_t kSeekHeaderBytes = 64;
+constexpr size_t kSeekRecordBytes = 24;
+constexpr uint64_t kSeekMagic = 0x314B454553464847ull;  // "GHFSEEK1"
+constexpr uint32_t kSeekVersion = 1;
+inline uint64_t seek_blocks_for(uint64_t n) { return (n + kBlockSymbols - 1) / kBlockSymbols; }
+
+struct SeekPackParams {
+  const uint64_t* chunk_bit;
+  const uint32_t* seg_bit;
+  uint64_t n_symbols, n_blocks, n_segs;
+  uint32_t flags;
+  uint8_t* table;  // 16-byte aligned, kSeekHeaderBytes + n_blocks * kSeekRecordBytes
+  int* status;
+};
+// blocks [g0, g1) of the table -> chunk_bit[0 .. g1 - g0), seg_bit[0 .. 64 * (g1 - g0)) (only the segments that exist)
+struct SeekExpandParams {
+  const uint8_t* records;  // the table behind its header: 8-byte aligned, n_blocks records
+  const uint8_t* stream;
+  uint64_t stream_bytes;
+  const DecTables* dt;
+  uint64_t n_symbols, n_blocks;  // of the whole stream
+  uint64_t g0, g1;
+  uint64_t* chunk_bit;
+  uint32_t* seg_bit;
+  int* status;
+};
+// the part [lo, hi) of ONE block (hi <= the block's end) -> out[0 .. hi - lo)
+struct DecHeadParams {
+  const uint8_t* stream;
+  uint64_t stream_bytes;
+  const DecTables* dt;
+  const uint64_t* chunk_bit;  // the block's
+  const uint32_t* seg_bit;    // the block's first segment
+  uint64_t blk_sym0;          // stream position of the block's first symbol
+  uint64_t n_symbols;         // of the whole stream
+  uint64_t lo, hi;
+  uint8_t* out;
+  int* status;
+};
+
 // K6: side-car reconstruction for foreign streams
 enum SyncKind : uint32_t {  // what SyncParams::no_eof carries
   kSyncCrs2 = 0,   // a whole .crs2: ends with the end mark
@@ -168,6 +214,9 @@ void launch_emit(const EmitParams& p, hipStream_t s);
 void launch_build_decode_tables(const ghf_code* d_code, DecTables* d_dt, int* d_status, hipStream_t s);
 constexpr uint64_t kDecMaxGroups = 0xFFFF0000ull;  // groups of 4096 symbols one k_decode launch takes (2^44 symbols)
 void launch_decode(const DecParams& p, hipStream_t s);
+void launch_seek_pack(const SeekPackParams& p, hipStream_t s);
+void launch_seek_expand(const SeekExpandParams& p, hipStream_t s);
+void launch_decode_head(const DecHeadParams& p, hipStream_t s);
 void launch_crs_build_code(const uint64_t* d_hist, ghf_tree* d_tree, ghf_code* d_code, uint64_t* d_start_bit, int* d_status,
                            hipStream_t s);
 void launch_crs_finish(const ghf_tree* d_tree, const uint64_t* d_total_bits, uint8_t* d_out, uint64_t* d_out_bytes, int* d_status,

@@ -66,6 +66,12 @@ class Index(C.Structure):
     ]
 
 
+class SeekInfo(C.Structure):
+    """ghf_seek_info: what ghf_seek_parse reads from the 64-byte header of a seek table"""
+
+    _fields_ = [("n_symbols", C.c_uint64), ("n_blocks", C.c_uint64), ("flags", C.c_uint32), ("version", C.c_uint32)]
+
+
 class Tree(C.Structure):
     """ghf_tree == the reference's HuffTree for the .crs format (include/huff_tree.h:98-176): node ids 0..255 are
     leaves (the key), 256 + i is the i-th parent, left[i] / right[i] its children."""
@@ -106,6 +112,7 @@ EXPORTS = [
     "ghf_comm_allreduce_hist", "ghf_comm_allgather_total", "ghf_encode_sharded", "ghf_shard_bound",
     "ghf_event_create", "ghf_event_destroy", "ghf_event_record", "ghf_event_wait", "ghf_event_sync", "ghf_histogram_add",
     "ghf_crs_sync_piece", "ghf_copy_d2d", "ghf_shard_bytes",
+    "ghf_seek_bytes", "ghf_seek_parse", "ghf_seek_pack", "ghf_seek_expand", "ghf_decode_range",
 ]
 COMM_ID_BYTES = 128
 
@@ -193,6 +200,12 @@ def lib():
     L.ghf_shard_bound.argtypes = [sz]
     L.ghf_shard_bound.restype = sz
     L.ghf_shard_bytes.argtypes = [vp, vp, vp, i32, i32, C.POINTER(sz)]
+    L.ghf_seek_bytes.argtypes = [sz]
+    L.ghf_seek_bytes.restype = sz
+    L.ghf_seek_parse.argtypes = [vp, sz, C.POINTER(SeekInfo)]
+    L.ghf_seek_pack.argtypes = [vp, C.POINTER(Index), vp, sz, vp, sz]
+    L.ghf_seek_expand.argtypes = [vp, C.POINTER(SeekInfo), vp, sz, vp, sz, vp, C.POINTER(Index)]
+    L.ghf_decode_range.argtypes = [vp, vp, sz, vp, C.POINTER(Index), C.POINTER(SeekInfo), vp, sz, u64, u64, vp, sz]
     _lib = L
     return L
 
@@ -243,6 +256,23 @@ def parse_header(host_bytes):
     if rc:
         raise GhfError(rc, "ghf_parse_header")
     return code, hs.value
+
+
+def seek_bytes(n):
+    """size of the seek table of a stream of n symbols: 64 + 24 * ceil(n / 4096)"""
+    return int(lib().ghf_seek_bytes(n))
+
+
+def seek_parse(host_bytes):
+    """host-side validation of a seek table's header against the table's size. -> SeekInfo"""
+    import numpy as np
+
+    a = np.ascontiguousarray(host_bytes, dtype=np.uint8)
+    info = SeekInfo()
+    rc = lib().ghf_seek_parse(a.ctypes.data, a.size, C.byref(info))
+    if rc:
+        raise GhfError(rc, "ghf_seek_parse")
+    return info
 
 
 def crs_parse_header(host_bytes):
@@ -447,6 +477,42 @@ class Context:
                               None if index is None else C.byref(index), d_out.data_ptr(), d_out.numel(), nbytes.data_ptr()),
             "ghf_decode")
         return d_out, nbytes
+
+    # ---- seekable streams: the seek table (the persistent form of the side-car) ----------------
+    def seek_pack(self, index, d_stream=None, stream_bytes=0, d_table=None, n=None):
+        """side-car -> table image in device memory (a uint8 tensor of seek_bytes(n_symbols)).  index=None: the side-car
+        decoded_size() last rebuilt for (d_stream, stream_bytes); n = what decoded_size() returned."""
+        if d_table is None:
+            d_table = self.torch.empty(seek_bytes(index.n_symbols if index is not None else n), dtype=self.torch.uint8,
+                                       device=self.device)
+        self._chk(self.L.ghf_seek_pack(self.h, None if index is None else C.byref(index),
+                                       None if d_stream is None else d_stream.data_ptr(), stream_bytes, d_table.data_ptr(),
+                                       d_table.numel()), "ghf_seek_pack")
+        return d_table
+
+    def seek_expand(self, info, d_table, d_stream, stream_bytes, d_code, index=None, table_bytes=None):
+        """table (device) -> full side-car; -> the index (allocated here unless given)"""
+        if index is None:
+            index = self.index_alloc(info.n_symbols)
+        tb = seek_bytes(info.n_symbols) if table_bytes is None else table_bytes
+        self._chk(self.L.ghf_seek_expand(self.h, C.byref(info), d_table.data_ptr(), tb, d_stream.data_ptr(), stream_bytes,
+                                         d_code.data_ptr(), C.byref(index)), "ghf_seek_expand")
+        return index
+
+    def decode_range(self, d_stream, stream_bytes, d_code, first, count, index=None, info=None, d_table=None, d_out=None,
+                     cap=None, table_bytes=None):
+        """d_out[0..count) = decoded bytes [first, first + count); give either index or (info, d_table)"""
+        if d_out is None:
+            d_out = self.empty_u8(count)
+        if table_bytes is None:
+            table_bytes = seek_bytes(info.n_symbols) if info is not None else 0
+        self._chk(
+            self.L.ghf_decode_range(self.h, d_stream.data_ptr(), stream_bytes, d_code.data_ptr(),
+                                    None if index is None else C.byref(index), None if info is None else C.byref(info),
+                                    None if d_table is None else d_table.data_ptr(), table_bytes, first, count,
+                                    d_out.data_ptr(), d_out.numel() if cap is None else cap),
+            "ghf_decode_range")
+        return d_out
 
     def sync_piece(self, d_piece, piece_bytes, first_bit, end_bit, d_code):
         """one rank's piece of a side-car-less stream (multi-GPU decode): -> (landing, n_symbols, has_end_mark)"""

@@ -215,6 +215,53 @@ int ghf_decode_prepare(ghf_ctx* ctx, const ghf_code* d_code);
  * (d_stream, stream_bytes), which then does not repeat the work. */
 int ghf_decoded_size(ghf_ctx* ctx, const uint8_t* d_stream, size_t stream_bytes, const ghf_code* d_code, uint64_t* n_out);
 
+/* ---- seekable streams: the seek table, the persistent form of the side-car -------------------------
+ * No reference counterpart (the .crs2 wire format has no sync points and the reference decodes front to back,
+ * include/canonical_huff_encoder.cc:377-568); the .crs2 bytes do not change.  A table is 64 + 24 * ceil(n / 4096)
+ * bytes, all fields little-endian: a 64-byte header {"GHFSEEK1", u32 version = 1, u32 flags (GHF_INDEX_NO_END_MARK),
+ * u64 n_symbols, u32 block_symbols = 4096, u32 run_symbols = 512, u64 n_blocks, zeros}, then per block of 4096
+ * symbols {u64 start_bit (= d_chunk_bit[g]), u16 run_bits[8]: the bit lengths of the block's eight runs of 512
+ * symbols, 0 for runs behind the last symbol}.  A block's runs add up to the next block's start_bit minus its own.
+ * The caller stores the table where it likes (e.g. <file>.crs2.seek); on open: ghf_seek_parse -> ghf_seek_expand ->
+ * ghf_decode with the expanded index, or ghf_decode_range straight from the table. */
+typedef struct ghf_seek_info {
+  uint64_t n_symbols, n_blocks;
+  uint32_t flags, version;
+} ghf_seek_info;
+size_t ghf_seek_bytes(size_t n_symbols); /* size of the table of a stream of n_symbols (no reference counterpart; host only) */
+/* No reference counterpart.  Host only, no GPU, nothing queued: validates the 64-byte header at h_table against
+ * `bytes`, the size of the whole table (GHF_E_FORMAT: wrong magic / version / geometry, unknown flags, a size other
+ * than the one n_blocks implies -- truncated or with something behind it) and returns its fields. */
+int ghf_seek_parse(const uint8_t* h_table, size_t bytes, ghf_seek_info* info);
+/* No reference counterpart.  Asynchronous on the stream, never synchronises: the side-car `index` (as an emit call or
+ * ghf_seek_expand filled it) -> the table image, header and records, at d_table in DEVICE memory (cap >=
+ * ghf_seek_bytes(index->n_symbols), else GHF_E_CAP); the caller brings it to the host with ghf_copy_d2h.
+ * index == NULL: the side-car this context last rebuilt for (d_stream, stream_bytes) -- ghf_decoded_size, which DOES
+ * synchronise, must have been the last call that rebuilt one; GHF_E_INVAL otherwise: "index a reference-written file
+ * once, seek forever".  d_stream is not read.  A side-car whose segment ends do not grow latches GHF_E_CORRUPT. */
+int ghf_seek_pack(ghf_ctx* ctx, const ghf_index* index, const uint8_t* d_stream, size_t stream_bytes, uint8_t* d_table,
+                  size_t cap);
+/* No reference counterpart.  Asynchronous on the stream, never synchronises: the table at d_table (DEVICE memory,
+ * table_bytes of it, described by `info` from ghf_seek_parse) -> the full side-car of d_stream in `index`
+ * (ghf_index_alloc(info->n_symbols)); index->flags comes from the table.  ghf_decode(..., index, ...) is then the
+ * ordinary indexed decode.  One lane per run decodes code lengths only and must land on the run's recorded end, and
+ * every block must end where the next one starts: a table that does not fit the stream (or names a bit outside it)
+ * latches GHF_E_CORRUPT, a table_bytes other than ghf_seek_bytes(info->n_symbols) is GHF_E_FORMAT at once.  Nothing
+ * outside d_stream[0 .. stream_bytes) is read and nothing outside the index arrays written, whatever the table holds.
+ * Builds the decode tables of d_code on the context (a state prepared by ghf_decode_prepare is dropped). */
+int ghf_seek_expand(ghf_ctx* ctx, const ghf_seek_info* info, const uint8_t* d_table, size_t table_bytes,
+                    const uint8_t* d_stream, size_t stream_bytes, const ghf_code* d_code, ghf_index* index);
+/* No reference counterpart.  Asynchronous on the stream, never synchronises: d_out[0 .. count) = bytes
+ * [first, first + count) of what d_stream decodes to.  Exactly one of `index` (a live side-car) and (info, d_table,
+ * table_bytes) (a seek table in DEVICE memory; only the covered blocks are expanded, into a workspace of the context
+ * that grows on demand) is given, the other NULL: GHF_E_INVAL otherwise, and for first + count > n_symbols or a
+ * misaligned d_stream / d_table.  cap < count: GHF_E_CAP.  count == 0: nothing is launched.  d_out needs no alignment;
+ * the decode is fastest when d_out and `first` are congruent modulo 16 (16-byte stores).  Only d_out[0 .. count) is
+ * written.  Errors on the device (GHF_E_CORRUPT / GHF_E_FORMAT) are latched as for ghf_decode. */
+int ghf_decode_range(ghf_ctx* ctx, const uint8_t* d_stream, size_t stream_bytes, const ghf_code* d_code,
+                     const ghf_index* index, const ghf_seek_info* info, const uint8_t* d_table, size_t table_bytes,
+                     uint64_t first, uint64_t count, uint8_t* d_out, size_t cap);
+
 /* Multi-GPU decode of a stream that has no side-car ("per-rank self-sync + one all-gather of symbol
  * counts"; the reference's decoders, canonical_huff_encoder.cc:377-568, are single-stream).  The caller cuts the body
  * at byte positions; a rank's piece is its own bytes followed by >= 8 bytes of look-ahead from the next piece (zeros
