@@ -118,6 +118,7 @@ int ghf_ctx_destroy(ghf_ctx* c) {
   release(c->chunk_bit);
   release(c->range_seg);
   release(c->range_chunk);
+  release(c->batch_codes);
   if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
   delete c;
   return GHF_OK;
@@ -420,6 +421,122 @@ int ghf_index_free(ghf_ctx* c, ghf_index* idx) {
   if (idx->d_seg_bit) (void)hipFree(idx->d_seg_bit);
   idx->d_chunk_bit = nullptr;
   idx->d_seg_bit = nullptr;
+  return GHF_OK;
+}
+
+// ---------------------------------------------------------------------------------------------- batches
+size_t ghf_compress_batch_bound(size_t max_item_bytes) { return ghf_compress_bound(max_item_bytes); }
+
+int ghf_batch_index_alloc(ghf_ctx* c, uint32_t count, size_t max_item_bytes, ghf_batch_index* out) {
+  if (!c || !out || max_item_bytes == 0 || max_item_bytes > GHF_BATCH_MAX_ITEM) return GHF_E_INVAL;
+  GHF_HIP(c, hipSetDevice(c->device));
+  std::memset(out, 0, sizeof *out);
+  out->count = count;
+  out->max_item_bytes = max_item_bytes;
+  out->blocks_per_item = (max_item_bytes + kBlockSymbols - 1) / kBlockSymbols;
+  out->segs_per_item = (max_item_bytes + kSegSymbols - 1) / kSegSymbols;
+  GHF_HIP(c, hipMalloc(&out->d_chunk_bit, std::max<size_t>((size_t)count * out->blocks_per_item, 1) * sizeof(uint64_t)));
+  hipError_t e = hipMalloc(&out->d_seg_bit, std::max<size_t>((size_t)count * out->segs_per_item, 1) * sizeof(uint32_t));
+  if (e != hipSuccess) {
+    (void)hipFree(out->d_chunk_bit);
+    out->d_chunk_bit = nullptr;
+    return fail(c, GHF_E_HIP, "hipMalloc(batch seg_bit)", e);
+  }
+  return GHF_OK;
+}
+
+int ghf_batch_index_free(ghf_ctx* c, ghf_batch_index* idx) {
+  if (!c || !idx) return GHF_E_INVAL;
+  GHF_HIP(c, hipSetDevice(c->device));
+  GHF_HIP(c, hipStreamSynchronize(c->stream));
+  if (idx->d_chunk_bit) (void)hipFree(idx->d_chunk_bit);
+  if (idx->d_seg_bit) (void)hipFree(idx->d_seg_bit);
+  idx->d_chunk_bit = nullptr;
+  idx->d_seg_bit = nullptr;
+  return GHF_OK;
+}
+
+int ghf_batch_index_item(const ghf_batch_index* idx, uint32_t i, size_t n_i, ghf_index* view) {
+  if (!idx || !view || i >= idx->count || n_i > idx->max_item_bytes) return GHF_E_INVAL;
+  std::memset(view, 0, sizeof *view);
+  view->n_symbols = n_i;
+  view->chunk_symbols = kBlockSymbols;
+  view->seg_symbols = kSegSymbols;
+  view->n_chunks = (n_i + kBlockSymbols - 1) / kBlockSymbols;
+  view->n_segs = (n_i + kSegSymbols - 1) / kSegSymbols;
+  view->d_chunk_bit = idx->d_chunk_bit ? idx->d_chunk_bit + (size_t)i * idx->blocks_per_item : nullptr;
+  view->d_seg_bit = idx->d_seg_bit ? idx->d_seg_bit + (size_t)i * idx->segs_per_item : nullptr;
+  return GHF_OK;
+}
+
+// the index covers `count` items of up to max_item_bytes, at the strides the kernels assume
+static bool batch_index_covers(const ghf_batch_index* ix, uint32_t count, size_t max_item_bytes) {
+  return ix->d_chunk_bit && ix->d_seg_bit && ix->count >= count && ix->max_item_bytes >= max_item_bytes &&
+         ix->max_item_bytes <= GHF_BATCH_MAX_ITEM &&
+         ix->blocks_per_item == (ix->max_item_bytes + kBlockSymbols - 1) / kBlockSymbols &&
+         ix->segs_per_item == (ix->max_item_bytes + kSegSymbols - 1) / kSegSymbols;
+}
+
+int ghf_compress_batch(ghf_ctx* c, const uint8_t* const* d_in_ptrs, const uint64_t* d_in_bytes, size_t max_item_bytes,
+                       uint32_t count, uint8_t* const* d_out_ptrs, const uint64_t* d_out_caps, uint64_t* d_out_bytes,
+                       ghf_code* d_codes, const ghf_batch_index* index, int* d_item_status) {
+  if (!c) return GHF_E_INVAL;
+  if (max_item_bytes == 0 || max_item_bytes > GHF_BATCH_MAX_ITEM)
+    return fail(c, GHF_E_INVAL, "ghf_compress_batch: max_item_bytes must be 1 .. GHF_BATCH_MAX_ITEM");
+  if (index && !batch_index_covers(index, count, max_item_bytes))
+    return fail(c, GHF_E_INVAL, "ghf_compress_batch: index does not cover (count, max_item_bytes) (use ghf_batch_index_alloc)");
+  if (count == 0) return GHF_OK;
+  if (!d_in_ptrs || !d_in_bytes || !d_out_ptrs || !d_out_caps || !d_out_bytes || !d_item_status) return GHF_E_INVAL;
+  GHF_HIP(c, hipSetDevice(c->device));
+  if (!d_codes) {
+    const int rc = grow(c, c->batch_codes, count);
+    if (rc) return rc;
+    d_codes = c->batch_codes.p;
+  }
+  BatchCompressParams p;
+  p.in_ptrs = d_in_ptrs;
+  p.in_bytes = d_in_bytes;
+  p.max_item_bytes = max_item_bytes;
+  p.out_ptrs = d_out_ptrs;
+  p.out_caps = d_out_caps;
+  p.out_bytes = d_out_bytes;
+  p.codes = d_codes;
+  p.chunk_bit = index ? index->d_chunk_bit : nullptr;
+  p.seg_bit = index ? index->d_seg_bit : nullptr;
+  p.blocks_per_item = index ? index->blocks_per_item : 0;
+  p.segs_per_item = index ? index->segs_per_item : 0;
+  p.item_status = d_item_status;
+  launch_compress_batch(p, count, c->stream);
+  GHF_HIP(c, hipGetLastError());
+  return GHF_OK;
+}
+
+int ghf_decode_batch(ghf_ctx* c, const uint8_t* const* d_stream_ptrs, const uint64_t* d_stream_bytes, const ghf_code* d_codes,
+                     const ghf_batch_index* index, const uint64_t* d_n_symbols, uint32_t count, uint8_t* const* d_out_ptrs,
+                     const uint64_t* d_out_caps, uint64_t* d_out_bytes, int* d_item_status) {
+  if (!c || !index) return GHF_E_INVAL;
+  if (!batch_index_covers(index, count, 1))
+    return fail(c, GHF_E_INVAL, "ghf_decode_batch: index does not cover count items (use ghf_batch_index_alloc)");
+  if (count == 0) return GHF_OK;
+  if (!d_stream_ptrs || !d_stream_bytes || !d_codes || !d_n_symbols || !d_out_ptrs || !d_out_caps || !d_out_bytes || !d_item_status)
+    return GHF_E_INVAL;
+  GHF_HIP(c, hipSetDevice(c->device));
+  BatchDecodeParams p;
+  p.stream_ptrs = d_stream_ptrs;
+  p.stream_bytes = d_stream_bytes;
+  p.codes = d_codes;
+  p.chunk_bit = index->d_chunk_bit;
+  p.seg_bit = index->d_seg_bit;
+  p.blocks_per_item = index->blocks_per_item;
+  p.segs_per_item = index->segs_per_item;
+  p.max_item_bytes = index->max_item_bytes;
+  p.n_symbols = d_n_symbols;
+  p.out_ptrs = d_out_ptrs;
+  p.out_caps = d_out_caps;
+  p.out_bytes = d_out_bytes;
+  p.item_status = d_item_status;
+  launch_decode_batch(p, count, c->stream);
+  GHF_HIP(c, hipGetLastError());
   return GHF_OK;
 }
 

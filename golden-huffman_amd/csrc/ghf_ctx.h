@@ -133,6 +133,8 @@ struct ghf_ctx {
   // ghf_decode_range from a seek table: the side-car of the covered blocks only (describes nothing between calls)
   ghf::DevBuf<uint32_t> range_seg;
   ghf::DevBuf<uint64_t> range_chunk;
+  // ghf_compress_batch without d_codes: one table set per item (describes nothing between calls)
+  ghf::DevBuf<ghf_code> batch_codes;
   std::string err;
 };
 

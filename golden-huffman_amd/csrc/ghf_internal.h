@@ -160,6 +160,35 @@ struct DecHeadParams {
   int* status;
 };
 
+// ---- batches of small independent streams (ghf_batch.hip): one workgroup per item; every array is device memory -----
+struct BatchCompressParams {
+  const uint8_t* const* in_ptrs;
+  const uint64_t* in_bytes;
+  uint64_t max_item_bytes;
+  uint8_t* const* out_ptrs;
+  const uint64_t* out_caps;
+  uint64_t* out_bytes;
+  ghf_code* codes;        // [count], never null (the host driver lends its own when the caller keeps none)
+  uint64_t* chunk_bit;    // side-car slices (may both be null): item i at i * blocks_per_item / i * segs_per_item
+  uint32_t* seg_bit;
+  uint64_t blocks_per_item, segs_per_item;
+  int* item_status;
+};
+struct BatchDecodeParams {
+  const uint8_t* const* stream_ptrs;
+  const uint64_t* stream_bytes;
+  const ghf_code* codes;
+  const uint64_t* chunk_bit;
+  const uint32_t* seg_bit;
+  uint64_t blocks_per_item, segs_per_item;
+  uint64_t max_item_bytes;
+  const uint64_t* n_symbols;
+  uint8_t* const* out_ptrs;
+  const uint64_t* out_caps;
+  uint64_t* out_bytes;
+  int* item_status;
+};
+
 // K6: side-car reconstruction for foreign streams
 enum SyncKind : uint32_t {  // what SyncParams::no_eof carries
   kSyncCrs2 = 0,   // a whole .crs2: ends with the end mark
@@ -225,6 +254,8 @@ void launch_crs_decode_tables(const ghf_tree* d_tree, DecTables* d_dt, int* d_st
 void launch_stream_copy(const uint8_t* d_src, uint8_t* d_dst, uint64_t n, bool nt, hipStream_t s);
 void launch_store_u64(uint64_t* d_dst, const uint64_t* d_src_opt, uint64_t add, hipStream_t s);
 void launch_load_u16(uint64_t* d_dst, const uint16_t* d_src, hipStream_t s);
+void launch_compress_batch(const BatchCompressParams& p, uint32_t count, hipStream_t s);  // one launch, grid = count
+void launch_decode_batch(const BatchDecodeParams& p, uint32_t count, hipStream_t s);
 void launch_shard_start(const ghf_code* d_code, const uint64_t* d_totals, int rank, uint64_t* d_start_bit, hipStream_t s);
 
 }  // namespace ghf

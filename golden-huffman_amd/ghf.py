@@ -10,6 +10,7 @@ EMIT_REBASE = 2
 EMIT_HEADER = 4
 INDEX_NO_END_MARK = 1
 CODE_LIMIT = 1
+BATCH_MAX_ITEM = 1 << 20  # GHF_BATCH_MAX_ITEM: the largest item of ghf_compress_batch / ghf_decode_batch
 EMPTY_OK = 2  # opt-in: n == 0 -> header of the one-symbol code + 0x7F (builder's definition, parity unpinned)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -66,6 +67,20 @@ class Index(C.Structure):
     ]
 
 
+class BatchIndex(C.Structure):
+    """ghf_batch_index: the side-cars of a batch, item i's slice at i * blocks_per_item / i * segs_per_item"""
+
+    _fields_ = [
+        ("count", C.c_uint32),
+        ("reserved", C.c_uint32),
+        ("max_item_bytes", C.c_uint64),
+        ("blocks_per_item", C.c_uint64),
+        ("segs_per_item", C.c_uint64),
+        ("d_chunk_bit", C.c_void_p),
+        ("d_seg_bit", C.c_void_p),
+    ]
+
+
 class SeekInfo(C.Structure):
     """ghf_seek_info: what ghf_seek_parse reads from the 64-byte header of a seek table"""
 
@@ -113,6 +128,8 @@ EXPORTS = [
     "ghf_event_create", "ghf_event_destroy", "ghf_event_record", "ghf_event_wait", "ghf_event_sync", "ghf_histogram_add",
     "ghf_crs_sync_piece", "ghf_copy_d2d", "ghf_shard_bytes",
     "ghf_seek_bytes", "ghf_seek_parse", "ghf_seek_pack", "ghf_seek_expand", "ghf_decode_range",
+    "ghf_compress_batch_bound", "ghf_batch_index_alloc", "ghf_batch_index_free", "ghf_batch_index_item",
+    "ghf_compress_batch", "ghf_decode_batch",
 ]
 COMM_ID_BYTES = 128
 
@@ -206,6 +223,13 @@ def lib():
     L.ghf_seek_pack.argtypes = [vp, C.POINTER(Index), vp, sz, vp, sz]
     L.ghf_seek_expand.argtypes = [vp, C.POINTER(SeekInfo), vp, sz, vp, sz, vp, C.POINTER(Index)]
     L.ghf_decode_range.argtypes = [vp, vp, sz, vp, C.POINTER(Index), C.POINTER(SeekInfo), vp, sz, u64, u64, vp, sz]
+    L.ghf_compress_batch_bound.argtypes = [sz]
+    L.ghf_compress_batch_bound.restype = sz
+    L.ghf_batch_index_alloc.argtypes = [vp, C.c_uint32, sz, C.POINTER(BatchIndex)]
+    L.ghf_batch_index_free.argtypes = [vp, C.POINTER(BatchIndex)]
+    L.ghf_batch_index_item.argtypes = [C.POINTER(BatchIndex), C.c_uint32, sz, C.POINTER(Index)]
+    L.ghf_compress_batch.argtypes = [vp, vp, vp, sz, C.c_uint32, vp, vp, vp, vp, C.POINTER(BatchIndex), vp]
+    L.ghf_decode_batch.argtypes = [vp, vp, vp, vp, C.POINTER(BatchIndex), vp, C.c_uint32, vp, vp, vp, vp]
     _lib = L
     return L
 
@@ -220,6 +244,20 @@ def lib_identity():
 
 def compress_bound(n):
     return int(lib().ghf_compress_bound(n))
+
+
+def compress_batch_bound(max_item_bytes):
+    """capacity that suffices for every item of a batch whose items have at most max_item_bytes"""
+    return int(lib().ghf_compress_batch_bound(max_item_bytes))
+
+
+def batch_index_item(bidx, i, n_i):
+    """item i's slice of a BatchIndex as an ordinary Index (a view: it owns nothing); host only"""
+    view = Index()
+    rc = lib().ghf_batch_index_item(C.byref(bidx), i, n_i, C.byref(view))
+    if rc:
+        raise GhfError(rc, "ghf_batch_index_item")
+    return view
 
 
 def shard_bound(n):
@@ -477,6 +515,83 @@ class Context:
                               None if index is None else C.byref(index), d_out.data_ptr(), d_out.numel(), nbytes.data_ptr()),
             "ghf_decode")
         return d_out, nbytes
+
+    # ---- batches of small independent streams (one launch per call, per-item status) ------------
+    def batch_index_alloc(self, count, max_item_bytes):
+        bidx = BatchIndex()
+        self._chk(self.L.ghf_batch_index_alloc(self.h, count, max_item_bytes, C.byref(bidx)), "ghf_batch_index_alloc")
+        return bidx
+
+    def batch_index_free(self, bidx):
+        self.L.ghf_batch_index_free(self.h, C.byref(bidx))
+
+    batch_index_item = staticmethod(batch_index_item)
+
+    def _i64(self, values):
+        return self.torch.tensor([int(v) for v in values], dtype=self.torch.int64).to(self.device)
+
+    def compress_batch(self, items, sizes=None, max_item_bytes=None, d_out=None, out_stride=None, d_codes=None, index=None):
+        """items: a list of CUDA uint8 tensors, or ONE packed CUDA uint8 tensor with `sizes` (item i at the sum of the
+        sizes before it).  The pointer and size arrays are built on the device; no host synchronisation.  d_out: one
+        uint8 tensor holding item i's image at i * out_stride (allocated here unless given).
+        -> dict(out, out_stride, out_bytes int64[count], status int32[count], codes uint8[count, sizeof(Code)], in_ptrs,
+                in_bytes, out_ptrs, count, max_item_bytes)"""
+        t = self.torch
+        if sizes is None:
+            sizes = [int(x.numel()) for x in items]
+            ptrs = [x.data_ptr() if x.numel() else 0 for x in items]
+        else:
+            sizes = [int(v) for v in sizes]
+            base, ptrs, at = items.data_ptr(), [], 0
+            for v in sizes:
+                ptrs.append(base + at)
+                at += v
+        count = len(sizes)
+        if max_item_bytes is None:
+            max_item_bytes = max(max(sizes, default=1), 1)
+        if out_stride is None:
+            out_stride = compress_batch_bound(max_item_bytes)
+        if d_out is None:
+            d_out = t.empty(max(count * out_stride, 16), dtype=t.uint8, device=self.device)
+        if d_codes is None:
+            d_codes = t.zeros((max(count, 1), C.sizeof(Code)), dtype=t.uint8, device=self.device)
+        in_ptrs, in_bytes = self._i64(ptrs), self._i64(sizes)
+        out_ptrs = d_out.data_ptr() + t.arange(count, dtype=t.int64, device=self.device) * out_stride
+        out_caps = t.full((max(count, 1),), out_stride, dtype=t.int64, device=self.device)
+        out_bytes = t.zeros(max(count, 1), dtype=t.int64, device=self.device)
+        status = t.full((max(count, 1),), -1, dtype=t.int32, device=self.device)
+        self._chk(
+            self.L.ghf_compress_batch(self.h, in_ptrs.data_ptr(), in_bytes.data_ptr(), max_item_bytes, count, out_ptrs.data_ptr(),
+                                      out_caps.data_ptr(), out_bytes.data_ptr(), d_codes.data_ptr(),
+                                      None if index is None else C.byref(index), status.data_ptr()),
+            "ghf_compress_batch")
+        return {"out": d_out, "out_stride": out_stride, "out_bytes": out_bytes[:count], "status": status[:count], "codes": d_codes,
+                "in_ptrs": in_ptrs, "in_bytes": in_bytes, "out_ptrs": out_ptrs, "out_caps": out_caps, "count": count,
+                "max_item_bytes": max_item_bytes, "keep": items}
+
+    def decode_batch(self, stream_ptrs, stream_bytes, d_codes, index, n_symbols, d_out=None, out_stride=None, out_ptrs=None,
+                     out_caps=None):
+        """stream_ptrs / stream_bytes / n_symbols: int64 CUDA tensors [count] (e.g. out_ptrs, out_bytes and in_bytes of
+        compress_batch).  Item i is decoded to d_out[i * out_stride ..) unless out_ptrs / out_caps (int64 CUDA tensors) say
+        otherwise.  -> dict(out, out_stride, out_bytes int64[count], status int32[count])"""
+        t = self.torch
+        count = int(n_symbols.numel())
+        if out_ptrs is None:
+            if out_stride is None:
+                out_stride = (int(index.max_item_bytes) + 15) & ~15
+            if d_out is None:
+                d_out = t.empty(max(count * out_stride, 16), dtype=t.uint8, device=self.device)
+            out_ptrs = d_out.data_ptr() + t.arange(count, dtype=t.int64, device=self.device) * out_stride
+            out_caps = t.full((max(count, 1),), out_stride, dtype=t.int64, device=self.device)
+        out_bytes = t.zeros(max(count, 1), dtype=t.int64, device=self.device)
+        status = t.full((max(count, 1),), -1, dtype=t.int32, device=self.device)
+        self._chk(
+            self.L.ghf_decode_batch(self.h, stream_ptrs.data_ptr(), stream_bytes.data_ptr(), d_codes.data_ptr(), C.byref(index),
+                                    n_symbols.data_ptr(), count, out_ptrs.data_ptr(), out_caps.data_ptr(), out_bytes.data_ptr(),
+                                    status.data_ptr()),
+            "ghf_decode_batch")
+        return {"out": d_out, "out_stride": out_stride, "out_bytes": out_bytes[:count], "status": status[:count],
+                "out_ptrs": out_ptrs, "out_caps": out_caps}
 
     # ---- seekable streams: the seek table (the persistent form of the side-car) ----------------
     def seek_pack(self, index, d_stream=None, stream_bytes=0, d_table=None, n=None):

@@ -262,6 +262,75 @@ int ghf_decode_range(ghf_ctx* ctx, const uint8_t* d_stream, size_t stream_bytes,
                      const ghf_index* index, const ghf_seek_info* info, const uint8_t* d_table, size_t table_bytes,
                      uint64_t first, uint64_t count, uint8_t* d_out, size_t cap);
 
+/* ---- batches: many small independent .crs2 streams in one call ---------------------------------------
+ * No reference counterpart (the reference compresses one file per process, include/compressor.h:62-73).  For callers
+ * with thousands of small buffers (pages, records, tensors, log blocks): one call compresses / decodes `count`
+ * independent items with ONE kernel launch, whatever `count` is -- one workgroup per item, which histograms, builds the
+ * exact code (the same K2/K3 body ghf_build_code runs), packs and writes the header.  Asynchronous on the context's
+ * stream, never synchronises, no per-item host work or copy: EVERY array argument, the pointer and size arrays
+ * included, is DEVICE memory; the host knows `count` and `max_item_bytes` only.
+ *
+ * Compress: item i = d_in_ptrs[i][0 .. d_in_bytes[i]) -> a complete standalone .crs2 image at d_out_ptrs[i],
+ * byte-identical to what ghf_compress writes for the same bytes (and so to the reference's file); d_out_bytes[i] <- its
+ * size.  Bytes behind the image are unspecified; nothing at or beyond d_out_caps[i] is written
+ * (ghf_compress_batch_bound(max_item_bytes) always suffices).  Input pointers need no alignment; compress output
+ * pointers and decode stream pointers are 16-byte aligned; decode output pointers need no alignment.  d_codes
+ * (optional): d_codes[i] <- the tables ghf_build_code produces.  index (optional): item i's slice receives exactly the
+ * side-car ghf_compress(..., index) fills for that item; chunk_bit counts from byte 0 of the item's own image.
+ *
+ * Decode: item i = the image at d_stream_ptrs[i] (d_stream_bytes[i] of it), with d_codes[i], item i's slice of `index`
+ * and d_n_symbols[i] (what the compress call was given) -> d_out_ptrs[i][0 .. d_n_symbols[i]), d_out_bytes[i] <- that
+ * size.  The tables pass the checks of ghf_decode (complete prefix code) before anything is decoded; every segment must
+ * land on its recorded end and the end mark must follow the last symbol.  No byte outside d_stream_ptrs[i][0 ..
+ * d_stream_bytes[i]) is read, whatever tables and side-car hold.  A stream without side-car (a file the reference
+ * wrote) goes through ghf_decode(index = NULL).
+ *
+ * Failures are PER ITEM: d_item_status[i] <- a ghf_status_code (GHF_OK is written as well):
+ *   GHF_E_EMPTY   the item has 0 bytes            GHF_E_INVAL  more than max_item_bytes; null / misaligned item pointer
+ *   GHF_E_CAP     the image (the decoded item) is larger than d_out_caps[i]
+ *   GHF_E_FORMAT  decode: d_codes[i] is not a complete prefix code
+ *   GHF_E_CORRUPT decode: a segment does not land on its recorded end, or the end mark is missing / cut off
+ * A failed item leaves d_out_bytes[i] = 0, does not disturb its neighbours and does NOT latch the context's status word:
+ * ghf_sync stays GHF_OK.  Call-level errors (returned at once, nothing queued): null arrays, max_item_bytes == 0 or
+ * > GHF_BATCH_MAX_ITEM, an index whose geometry does not cover (count, max_item_bytes): GHF_E_INVAL.  count == 0 queues
+ * nothing.  The calls leave the context's plan, histogram and prepared-table caches alone.
+ * Not supported here: GHF_CODE_LIMIT and GHF_EMPTY_OK (a code longer than 32 bits needs far more than 1 MiB of input;
+ * an empty item is refused), and the .crs format. */
+#define GHF_BATCH_MAX_ITEM (1u << 20) /* one workgroup owns one item; its bit offsets fit 32 bits */
+
+/* No reference counterpart.  Host only: = ghf_compress_bound(max_item_bytes), a capacity that suffices for every item. */
+size_t ghf_compress_batch_bound(size_t max_item_bytes);
+
+/* The side-cars of a batch: a host struct with two device arrays; item i's slice is the SAME side-car ghf_index
+ * describes, at a fixed stride. */
+typedef struct ghf_batch_index {
+  uint32_t count, reserved;
+  uint64_t max_item_bytes;
+  uint64_t blocks_per_item; /* ceil(max_item_bytes / 4096) */
+  uint64_t segs_per_item;   /* ceil(max_item_bytes / 64) */
+  uint64_t* d_chunk_bit;    /* [count * blocks_per_item], item i at i * blocks_per_item */
+  uint32_t* d_seg_bit;      /* [count * segs_per_item],   item i at i * segs_per_item */
+} ghf_batch_index;
+/* No reference counterpart.  Allocates the two arrays for `count` items of up to max_item_bytes (<= GHF_BATCH_MAX_ITEM). */
+int ghf_batch_index_alloc(ghf_ctx* ctx, uint32_t count, size_t max_item_bytes, ghf_batch_index* out);
+/* No reference counterpart.  Waits for the context's stream, then frees the arrays. */
+int ghf_batch_index_free(ghf_ctx* ctx, ghf_batch_index* idx);
+/* No reference counterpart.  Host only, nothing queued: item i's slice as an ordinary ghf_index (n_symbols = n_i, the
+ * item's size) -- usable with ghf_decode, ghf_seek_pack and ghf_decode_range on the item's image.  The view owns
+ * nothing (do not ghf_index_free it).  GHF_E_INVAL: i >= count, n_i > max_item_bytes. */
+int ghf_batch_index_item(const ghf_batch_index* idx, uint32_t i, size_t n_i, ghf_index* view);
+
+/* No reference counterpart; see above. */
+int ghf_compress_batch(ghf_ctx* ctx, const uint8_t* const* d_in_ptrs, const uint64_t* d_in_bytes, size_t max_item_bytes,
+                       uint32_t count, uint8_t* const* d_out_ptrs, const uint64_t* d_out_caps, uint64_t* d_out_bytes,
+                       ghf_code* d_codes /* [count], optional */, const ghf_batch_index* index /* optional */,
+                       int* d_item_status /* [count] */);
+/* No reference counterpart; see above.  max_item_bytes is index->max_item_bytes. */
+int ghf_decode_batch(ghf_ctx* ctx, const uint8_t* const* d_stream_ptrs, const uint64_t* d_stream_bytes,
+                     const ghf_code* d_codes /* [count] */, const ghf_batch_index* index, const uint64_t* d_n_symbols,
+                     uint32_t count, uint8_t* const* d_out_ptrs, const uint64_t* d_out_caps, uint64_t* d_out_bytes,
+                     int* d_item_status /* [count] */);
+
 /* Multi-GPU decode of a stream that has no side-car ("per-rank self-sync + one all-gather of symbol
  * counts"; the reference's decoders, canonical_huff_encoder.cc:377-568, are single-stream).  The caller cuts the body
  * at byte positions; a rank's piece is its own bytes followed by >= 8 bytes of look-ahead from the next piece (zeros
