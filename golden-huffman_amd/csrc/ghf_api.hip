@@ -540,6 +540,34 @@ int ghf_decode_batch(ghf_ctx* c, const uint8_t* const* d_stream_ptrs, const uint
   return GHF_OK;
 }
 
+int ghf_decode_images_batch(ghf_ctx* c, const uint8_t* const* d_stream_ptrs, const uint64_t* d_stream_bytes, uint32_t count,
+                            uint8_t* const* d_out_ptrs, const uint64_t* d_out_caps, uint64_t* d_out_bytes, ghf_code* d_codes,
+                            int* d_item_status) {
+  if (!c || !d_stream_ptrs || !d_stream_bytes || !d_out_bytes || !d_item_status) return GHF_E_INVAL;
+  if (d_out_ptrs && !d_out_caps) return fail(c, GHF_E_INVAL, "ghf_decode_images_batch: d_out_ptrs without d_out_caps");
+  if (count == 0) return GHF_OK;
+  GHF_HIP(c, hipSetDevice(c->device));
+  BatchImagesParams p;
+  p.stream_ptrs = d_stream_ptrs;
+  p.stream_bytes = d_stream_bytes;
+  p.max_stream_bytes = ghf_compress_bound(GHF_BATCH_MAX_ITEM);
+  p.out_ptrs = d_out_ptrs;
+  p.out_caps = d_out_caps;
+  p.out_bytes = d_out_bytes;
+  p.codes = d_codes;
+  p.item_status = d_item_status;
+  p.stats = c->images_stats;
+  launch_decode_images_batch(p, count, c->stream);
+  GHF_HIP(c, hipGetLastError());
+  return GHF_OK;
+}
+
+int ghf_decode_images_batch_stats(ghf_ctx* c, uint64_t* d_stats) {
+  if (!c || (reinterpret_cast<uintptr_t>(d_stats) & 7u)) return GHF_E_INVAL;
+  c->images_stats = d_stats;
+  return GHF_OK;
+}
+
 // ---------------------------------------------------------------------------------------------- decode
 static inline uint32_t be32(const uint8_t* p) {
   return ((uint32_t)p[0] << 24) | ((uint32_t)p[1] << 16) | ((uint32_t)p[2] << 8) | (uint32_t)p[3];

@@ -264,11 +264,16 @@ __global__ __launch_bounds__(kBatchThreads) void k_compress_batch(BatchCompressP
 constexpr int kBatchDecRoundSegs = kBatchThreads;
 constexpr int kBatchDecRoundBytes = kBatchDecRoundSegs * kSegSymbols;  // 16 KiB
 
-struct BatchDecodeLds {
+// the decode tables of one item in LDS, shared by k_decode_batch and k_decode_images_batch
+struct BatchDecTab {
   uint16_t lut[1 << kDecLutBitsMax];  // sym | len << 9; 0: the code is longer than lut_bits
   uint32_t fcl[36];                   // first_code[len] << (32 - len); 0xFFFFFFFF outside [min_len, max_len]
   uint32_t sp[36];
   uint16_t symbol[GHF_NSYM + 3];
+};
+
+struct BatchDecodeLds {
+  BatchDecTab t;
   alignas(16) uint32_t stage[kBatchDecRoundBytes / 4 + 4];
   unsigned long long kraft;
   int bad;
@@ -285,6 +290,70 @@ __device__ __forceinline__ uint32_t batch_stream_word(const uint8_t* __restrict_
   for (uint32_t j = 0; j < 4; ++j)
     if (b + j < bytes) r |= (uint32_t)s[b + j] << (24 - 8 * j);
   return r;
+}
+
+// the code of `from` .. `to` bits that the window starts with, as sym | len << 9 (0: none): the codes the direct table
+// does not hold (from = its width + 1), and every code while that table is being filled (from = min_len)
+__device__ __forceinline__ uint32_t batch_search_code(const BatchDecTab& T, uint32_t win, int from, int to) {
+  for (int len = from; len <= to; ++len) {
+    const uint32_t f = T.fcl[len];
+    if (win >= f) {
+      const uint32_t k = T.sp[len] + ((win - f) >> (32 - len));
+      return (k < (uint32_t)GHF_NSYM ? (uint32_t)T.symbol[k] : 256u) | ((uint32_t)len << 9);
+    }
+  }
+  return 0;
+}
+
+// the direct table of lb = min(max_len, 12) bits from fcl / sp / symbol (the caller puts a barrier on both sides)
+__device__ __forceinline__ void batch_fill_lut(BatchDecTab& T, int min_len, int lb, int tid) {
+  for (uint32_t idx = tid; idx < (1u << lb); idx += kBatchThreads) T.lut[idx] = (uint16_t)batch_search_code(T, idx << (32 - lb), min_len, lb);
+}
+
+// sym | len << 9 of the code the 32-bit window starts with; len == 0: no code does
+__device__ __forceinline__ uint32_t batch_decode_one(const BatchDecTab& T, uint32_t win, int lb, int long_from, int max_len) {
+  const uint32_t ent = T.lut[win >> (32 - lb)];
+  return ent ? ent : batch_search_code(T, win, long_from, max_len);
+}
+
+// the bit cursor of the batch decoders: 64 stream bits from word `wi` on, `o` (< 32) of them consumed
+struct BatchCursor {
+  uint32_t hi, lo, wi, o;
+  __device__ __forceinline__ void seek(const uint8_t* __restrict__ s, uint64_t bytes, uint32_t bit) {
+    wi = bit >> 5;
+    o = bit & 31u;
+    hi = batch_stream_word(s, bytes, wi);
+    lo = batch_stream_word(s, bytes, wi + 1);
+  }
+  __device__ __forceinline__ uint32_t window() const { return (uint32_t)((((unsigned long long)hi << 32 | lo) << o) >> 32); }
+  __device__ __forceinline__ void skip(const uint8_t* __restrict__ s, uint64_t bytes, uint32_t len) {
+    o += len;
+    if (o >= 32u) {
+      o -= 32u;
+      ++wi;
+      hi = lo;
+      lo = batch_stream_word(s, bytes, wi + 1);
+    }
+  }
+};
+
+// stage[0 .. rbytes) -> dst: byte stores up to the first 16-byte boundary of dst, vectors, byte stores at the end (the
+// stage keeps four spare words behind its last byte)
+__device__ __forceinline__ void batch_store_stage(uint8_t* dst, const uint32_t* stage, uint32_t rbytes, int tid) {
+  uint32_t head = (16u - ((uint32_t)reinterpret_cast<uintptr_t>(dst) & 15u)) & 15u;
+  head = head < rbytes ? head : rbytes;
+  const uint8_t* const sb = reinterpret_cast<const uint8_t*>(stage);
+  if ((uint32_t)tid < head) dst[tid] = sb[tid];
+  const uint32_t nvec = (rbytes - head) >> 4;
+  const uint32_t sh = 8u * (head & 3u);
+  for (uint32_t q = tid; q < nvec; q += kBatchThreads) {
+    const uint32_t at = head + 16u * q;
+    const uint32_t* w = &stage[at >> 2];
+    const uint32_t w0 = w[0], w1 = w[1], w2 = w[2], w3 = w[3], w4 = w[4];
+    *reinterpret_cast<uint4*>(dst + at) = make_uint4(alignbit(w1, w0, sh), alignbit(w2, w1, sh), alignbit(w3, w2, sh), alignbit(w4, w3, sh));
+  }
+  const uint32_t tail0 = head + 16u * nvec;
+  if (tail0 + (uint32_t)tid < rbytes) dst[tail0 + tid] = sb[tail0 + tid];
 }
 
 __global__ __launch_bounds__(kBatchThreads) void k_decode_batch(BatchDecodeParams P) {
@@ -336,10 +405,10 @@ __global__ __launch_bounds__(kBatchThreads) void k_decode_batch(BatchDecodeParam
       f = fc << (32 - tid);
     }
     if (tid < 36) {
-      S.fcl[tid] = f;
-      S.sp[tid] = p;
+      S.t.fcl[tid] = f;
+      S.t.sp[tid] = p;
     }
-    for (int i = tid; i < GHF_NSYM; i += kBatchThreads) S.symbol[i] = (uint16_t)(code->symbol[i] > 256u ? 256u : code->symbol[i]);
+    for (int i = tid; i < GHF_NSYM; i += kBatchThreads) S.t.symbol[i] = (uint16_t)(code->symbol[i] > 256u ? 256u : code->symbol[i]);
     if (k) atomicAdd(&S.kraft, k);
     if (b) atomicOr(&S.bad, 1);
   }
@@ -352,18 +421,7 @@ __global__ __launch_bounds__(kBatchThreads) void k_decode_batch(BatchDecodeParam
     return;
   }
   const int lb = max_len < kDecLutBitsMax ? max_len : kDecLutBitsMax;
-  for (uint32_t idx = tid; idx < (1u << lb); idx += kBatchThreads) {
-    const uint32_t v = idx << (32 - lb);
-    uint32_t ent = 0;
-    for (int len = min_len; len <= lb; ++len) {
-      if (v >= S.fcl[len]) {
-        const uint32_t k = S.sp[len] + ((v - S.fcl[len]) >> (32 - len));
-        ent = (k < (uint32_t)GHF_NSYM ? (uint32_t)S.symbol[k] : 256u) | ((uint32_t)len << 9);
-        break;
-      }
-    }
-    S.lut[idx] = (uint16_t)ent;
-  }
+  batch_fill_lut(S.t, min_len, lb, tid);
   __syncthreads();
 
   const uint64_t* const chunk_bit = P.chunk_bit + (uint64_t)item * P.blocks_per_item;
@@ -386,24 +444,13 @@ __global__ __launch_bounds__(kBatchThreads) void k_decode_batch(BatchDecodeParam
       uint32_t used = 0;
       if (!bad) {
         const uint32_t bit = (uint32_t)B0 + start;
-        uint32_t wi = bit >> 5, o = bit & 31u;
-        uint32_t hi = batch_stream_word(stream, stream_bytes, wi), lo = batch_stream_word(stream, stream_bytes, wi + 1);
+        BatchCursor cur;
+        cur.seek(stream, stream_bytes, bit);
         uint32_t word = 0;
         const uint32_t steps = cnt + (is_last ? 1u : 0u);
 #pragma unroll 1
         for (uint32_t i = 0; i < steps; ++i) {
-          const uint32_t win = (uint32_t)((((unsigned long long)hi << 32 | lo) << o) >> 32);
-          uint32_t ent = S.lut[win >> (32 - lb)];
-          if (ent == 0) {
-            for (int len = long_from; len <= max_len; ++len) {
-              const uint32_t f = S.fcl[len];
-              if (win >= f) {
-                const uint32_t k = S.sp[len] + ((win - f) >> (32 - len));
-                ent = (k < (uint32_t)GHF_NSYM ? (uint32_t)S.symbol[k] : 256u) | ((uint32_t)len << 9);
-                break;
-              }
-            }
-          }
+          const uint32_t ent = batch_decode_one(S.t, cur.window(), lb, long_from, max_len);
           const uint32_t sym = ent & 0x1FFu, len = ent >> 9;
           if (len == 0) {  // no code starts with these bits
             bad = true;
@@ -420,43 +467,295 @@ __global__ __launch_bounds__(kBatchThreads) void k_decode_batch(BatchDecodeParam
           } else if (sym != 256u || (uint64_t)bit + used + len > end_bit) {
             bad = true;  // the end mark is missing behind the last symbol, or the stream ends inside it
           }
-          o += len;
-          if (o >= 32u) {
-            o -= 32u;
-            ++wi;
-            hi = lo;
-            lo = batch_stream_word(stream, stream_bytes, wi + 1);
-          }
+          cur.skip(stream, stream_bytes, len);
         }
         if (used != end - start) bad = true;  // the segment does not land on its recorded end
       }
       if (bad) S.err = 1;
     }
     __syncthreads();
-    // the round's bytes leave: byte stores up to the first 16-byte boundary of out, vectors, byte stores at the end
+    // the round's bytes leave
     const uint32_t rb = s0 * kSegSymbols;
     const uint32_t rbytes = n - rb < (uint32_t)kBatchDecRoundBytes ? n - rb : (uint32_t)kBatchDecRoundBytes;
-    uint8_t* const dst = out + rb;
-    uint32_t head = (16u - ((uint32_t)reinterpret_cast<uintptr_t>(dst) & 15u)) & 15u;
-    head = head < rbytes ? head : rbytes;
-    const uint8_t* const sb = reinterpret_cast<const uint8_t*>(S.stage);
-    if ((uint32_t)tid < head) dst[tid] = sb[tid];
-    const uint32_t nvec = (rbytes - head) >> 4;
-    const uint32_t sh = 8u * (head & 3u);
-    for (uint32_t q = tid; q < nvec; q += kBatchThreads) {
-      const uint32_t at = head + 16u * q;
-      const uint32_t* w = &S.stage[at >> 2];
-      const uint32_t w0 = w[0], w1 = w[1], w2 = w[2], w3 = w[3], w4 = w[4];
-      *reinterpret_cast<uint4*>(dst + at) = make_uint4(alignbit(w1, w0, sh), alignbit(w2, w1, sh), alignbit(w3, w2, sh), alignbit(w4, w3, sh));
-    }
-    const uint32_t tail0 = head + 16u * nvec;
-    if (tail0 + (uint32_t)tid < rbytes) dst[tail0 + tid] = sb[tail0 + tid];
+    batch_store_stage(out + rb, S.stage, rbytes, tid);
     __syncthreads();
   }
   if (tid == 0) {
     const bool ok = S.err == 0;
     P.item_status[item] = ok ? GHF_OK : GHF_E_CORRUPT;
     P.out_bytes[item] = ok ? n : 0;
+  }
+}
+
+// ----------------------------------------------------------------------------------------------------------------------
+// decode of standalone images (ghf_decode_images_batch): the image alone is enough.  The workgroup
+// parses and validates the header with every check ghf_parse_header makes, fills the same tables k_decode_batch uses,
+// then finds the code boundaries itself: rounds of 256 subsequences of 512 bits, one per lane, settled by passes in
+// which lane k restarts from where lane k - 1 landed until nothing moves at or in front of the first end mark (lane 0
+// starts at an exactly known bit, so the fixed point is the true segmentation).  A scan of the lanes' symbol counts gives
+// the output offsets; under kWrite the lanes decode once more into a 16 KiB stage that leaves slice by slice.
+// ----------------------------------------------------------------------------------------------------------------------
+constexpr uint32_t kImgSubBits = 512;
+constexpr uint32_t kImgRoundBits = kBatchThreads * kImgSubBits;
+constexpr uint32_t kImgStageBytes = 16 * 1024;
+constexpr uint32_t kImgNone = 0xFFFFFFFFu;
+constexpr uint32_t kImgEndMark = 1, kImgCutOff = 2;  // why a lane stopped inside its subsequence
+
+struct BatchImagesLds {
+  BatchDecTab t;
+  // header phase: the raw symbol[] words, length / codeword by symbol, seen[], the raw start_pos / first_code words
+  alignas(16) uint32_t stage[kImgStageBytes / 4 + 4];
+  uint16_t over[2][kBatchThreads];  // bits each lane's last code runs past its subsequence; written in pass p, read in p + 1
+  uint32_t mins[3][2];              // [pass % 3]{first lane whose start moved, first lane that met the end (mark) of the stream}
+  uint32_t wave_tot[kBatchWaves];
+  uint32_t stop_kind;
+  unsigned long long kraft;
+  uint32_t used;
+  int bad;
+};
+static_assert(sizeof(BatchImagesLds) <= 40 * 1024, "four workgroups per CU");
+static_assert(4 * (GHF_NSYM + 3) + 2 * 40 <= (int)kImgStageBytes / 4, "the header's scratch fits the stage");
+
+template <bool kWrite>
+__global__ __launch_bounds__(kBatchThreads) void k_decode_images_batch(BatchImagesParams P) {
+  __shared__ BatchImagesLds S;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const uint32_t item = blockIdx.x;
+  const uint64_t stream_bytes = P.stream_bytes[item];
+  const uint8_t* __restrict__ const stream = P.stream_ptrs[item];
+  uint8_t* __restrict__ const out = kWrite ? P.out_ptrs[item] : nullptr;
+  const uint64_t cap = kWrite ? P.out_caps[item] : ~0ull;
+  uint32_t rounds = 0, passes = 0;
+  auto finish = [&](int status, uint64_t n) {  // every lane of the workgroup takes the same exit
+    if (tid == 0) {
+      P.item_status[item] = status;
+      P.out_bytes[item] = status == GHF_OK ? n : 0;
+      if (P.stats && rounds) {
+        atomicAdd(reinterpret_cast<unsigned long long*>(P.stats), (unsigned long long)rounds);
+        atomicAdd(reinterpret_cast<unsigned long long*>(P.stats) + 1, (unsigned long long)passes);
+      }
+    }
+  };
+  if (!stream || (reinterpret_cast<uintptr_t>(stream) & 15u) || (kWrite && !out) || stream_bytes > P.max_stream_bytes)
+    return finish(GHF_E_INVAL, 0);
+
+  // ---- 1. the header: canonical_huff_encoder.cc:349-374 with the checks of ghf_parse_header ----
+  // lengths are bounded before the header's size is trusted, the size against stream_bytes before the tables are read
+  if (stream_bytes < 1040) return finish(GHF_E_FORMAT, 0);
+  const uint32_t* __restrict__ const hw = reinterpret_cast<const uint32_t*>(stream);
+  const uint32_t min_len_u = bswap32(hw[GHF_NSYM + 1]), max_len_u = bswap32(hw[GHF_NSYM + 2]);
+  if (bswap32(hw[0]) != (uint32_t)GHF_NSYM || max_len_u < 1 || max_len_u > 32 || min_len_u < 1 || min_len_u > max_len_u)
+    return finish(GHF_E_FORMAT, 0);
+  const int min_len = (int)min_len_u, max_len = (int)max_len_u;
+  const uint32_t hdr_bytes = 1040u + 8u * max_len_u;
+  if (stream_bytes < hdr_bytes) return finish(GHF_E_FORMAT, 0);
+
+  uint32_t* const raw = S.stage;                     // symbol[] as stored
+  uint32_t* const lenb = raw + (GHF_NSYM + 3);       // length by symbol
+  uint32_t* const cwb = lenb + (GHF_NSYM + 3);       // codeword by symbol
+  uint32_t* const seen = cwb + (GHF_NSYM + 3);
+  uint32_t* const spraw = seen + (GHF_NSYM + 3);     // start_pos[0 .. 40) as stored; 0 outside [1, max_len]
+  uint32_t* const fcraw = spraw + 40;                // first_code, likewise
+  for (int i = tid; i < GHF_NSYM; i += kBatchThreads) {
+    raw[i] = bswap32(hw[1 + i]);
+    lenb[i] = 0;
+    cwb[i] = 0;
+    seen[i] = 0;
+  }
+  if (tid < 40) {
+    const bool in = tid >= 1 && tid <= max_len;
+    spraw[tid] = in ? bswap32(hw[GHF_NSYM + 3 + 2 * (tid - 1)]) : 0u;
+    fcraw[tid] = in ? bswap32(hw[GHF_NSYM + 4 + 2 * (tid - 1)]) : 0u;
+  }
+  if (tid == 0) {
+    S.kraft = 0;
+    S.bad = 0;
+    S.used = GHF_NSYM;
+    for (int b = 0; b < 3; ++b) S.mins[b][0] = S.mins[b][1] = kImgNone;
+  }
+  __syncthreads();
+  for (int i = tid; i < GHF_NSYM; i += kBatchThreads)
+    if (raw[i] == 0xFFFFFFFFu) atomicMin(&S.used, (uint32_t)i);
+  __syncthreads();
+  const uint32_t used = S.used;  // used symbols are a prefix of symbol[], all distinct, the end mark among them
+  {
+    int b = 0;
+    unsigned long long k = 0;
+    for (int i = tid; i < GHF_NSYM; i += kBatchThreads) {
+      const uint32_t s = raw[i];
+      if ((uint32_t)i < used) {
+        if (s >= (uint32_t)GHF_NSYM || atomicExch(&seen[s], 1u)) b = 1;
+      } else if (s != 0xFFFFFFFFu) {
+        b = 1;
+      }
+    }
+    if (used == 1) {  // the empty stream of GHF_EMPTY_OK: the end mark alone, code "0" (not a complete code)
+      if (tid == 0 && (max_len != 1 || fcraw[1] != 0 || spraw[1] != 0)) b = 1;
+    } else {
+      if (tid >= 1 && tid < min_len && fcraw[tid] != 1024u) b = 1;  // canonical_huff_encoder.cc:119-121
+      if (tid >= min_len && tid <= max_len) {
+        const uint32_t a = spraw[tid], e = tid < max_len ? spraw[tid + 1] : used;
+        const unsigned long long fc = fcraw[tid];
+        if (a > e || e > used || (tid == min_len && a != 0) || fc + (e - a) > (1ull << tid)) {
+          b = 1;
+        } else {
+          k = (unsigned long long)(e - a) << (32 - tid);
+          if (tid < max_len) {  // canonical_huff_encoder.cc:109-114: first_code[l] = (first_code[l + 1] + num[l + 1]) / 2
+            const uint32_t nb = (tid + 1 < max_len ? spraw[tid + 2] : used) - spraw[tid + 1];
+            if (fc != ((unsigned long long)fcraw[tid + 1] + nb) / 2) b = 1;
+          } else if (fc != 0) {
+            b = 1;
+          }
+        }
+      }
+    }
+    if (k) atomicAdd(&S.kraft, k);
+    if (b) atomicOr(&S.bad, 1);
+  }
+  __syncthreads();
+  if (S.bad || !seen[GHF_NSYM - 1] || (used != 1 && S.kraft != (1ull << 32))) return finish(GHF_E_FORMAT, 0);
+  // length / codeword by symbol, as ghf_parse_header rebuilds them: position k of symbol[] belongs to one length
+  for (uint32_t k = tid; k < used; k += kBatchThreads) {
+    for (int len = min_len; len <= max_len; ++len) {
+      const uint32_t a = spraw[len], e = len < max_len ? spraw[len + 1] : used;
+      if (k >= a && k < e) {
+        lenb[raw[k]] = (uint32_t)len;
+        cwb[raw[k]] = fcraw[len] + (k - a);
+        break;
+      }
+    }
+  }
+  // the tables k_decode_batch builds from a ghf_code
+  if (tid < 36) {
+    const bool in = tid >= min_len && tid <= max_len;
+    S.t.fcl[tid] = in ? fcraw[tid] << (32 - tid) : 0xFFFFFFFFu;
+    S.t.sp[tid] = in ? spraw[tid] : 0u;
+  }
+  for (int i = tid; i < GHF_NSYM; i += kBatchThreads) S.t.symbol[i] = (uint16_t)(raw[i] > 256u ? 256u : raw[i]);
+  __syncthreads();
+  if (P.codes) {
+    ghf_code* const code = P.codes + item;
+    for (int i = tid; i < GHF_NSYM; i += kBatchThreads) {
+      code->length[i] = lenb[i];
+      code->codeword[i] = cwb[i];
+      code->symbol[i] = raw[i];
+    }
+    if (tid < 64) {
+      code->first_code[tid] = tid < 40 ? fcraw[tid] : 0u;
+      code->start_pos[tid] = tid < 40 ? spraw[tid] : 0u;
+    }
+    if (tid == 0) {
+      code->min_len = min_len;
+      code->max_len = max_len;
+    }
+  }
+  if (used == 1) {  // nothing but the end mark "0" may follow
+    const bool ok = stream_bytes > hdr_bytes && !(stream[hdr_bytes] & 0x80u);
+    return finish(ok ? GHF_OK : GHF_E_CORRUPT, 0);
+  }
+  const int lb = max_len < kDecLutBitsMax ? max_len : kDecLutBitsMax;
+  const int long_from = lb + 1 > min_len ? lb + 1 : min_len;
+  batch_fill_lut(S.t, min_len, lb, tid);
+  __syncthreads();  // (the header's scratch in the stage is dead from here on)
+
+  // ---- 2. + 3. rounds of 256 subsequences ----
+  const uint32_t end_bit = (uint32_t)stream_bytes * 8u;  // stream_bytes <= ghf_compress_bound(1 MiB): below 2^24 bytes
+  uint32_t base = 8u * hdr_bytes;  // first bit of the round's subsequence 0
+  uint32_t carry = 0;              // bits the previous round's last code runs into this one: lane 0's start, exact
+  uint32_t total = 0;              // symbols of the rounds before this one
+  uint32_t pb = 0, po = 0;         // pass % 3, pass % 2
+#pragma unroll 1
+  for (;;) {
+    ++rounds;
+    const uint32_t sub0 = base + (uint32_t)tid * kImgSubBits, sub_end = sub0 + kImgSubBits;
+    uint32_t start = kImgNone, cnt = 0, stop = 0, over = 0;
+    uint32_t round_passes = 0, first_stop;
+#pragma unroll 1
+    for (;;) {
+      const uint32_t in = tid == 0 ? carry : round_passes == 0 ? 0u : (uint32_t)S.over[po][tid - 1];
+      const bool moved = in != start;
+      if (moved) {  // code lengths only, from `in` until the lane leaves its subsequence, the end mark or the stream's end
+        start = in;
+        cnt = 0;
+        stop = 0;
+        uint32_t pos = sub0 + in;
+        BatchCursor cur;
+        cur.seek(stream, stream_bytes, pos);
+#pragma unroll 1
+        while (pos < sub_end) {
+          const uint32_t ent = batch_decode_one(S.t, cur.window(), lb, long_from, max_len);
+          const uint32_t len = ent >> 9;
+          if (len == 0 || pos >= end_bit || len > end_bit - pos) {  // the code (an end mark too) must lie wholly inside the stream
+            stop = kImgCutOff;
+            break;
+          }
+          if ((ent & 0x1FFu) == 256u) {
+            stop = kImgEndMark;
+            break;
+          }
+          ++cnt;
+          pos += len;
+          cur.skip(stream, stream_bytes, len);
+        }
+        over = stop ? 0u : pos - sub_end;
+      }
+      S.over[po ^ 1u][tid] = (uint16_t)over;
+      const unsigned long long m_moved = __ballot(moved), m_stop = __ballot(stop != 0);
+      if (lane == 0) {
+        if (m_moved) atomicMin(&S.mins[pb][0], (uint32_t)(wave * 64 + __builtin_ctzll(m_moved)));
+        if (m_stop) atomicMin(&S.mins[pb][1], (uint32_t)(wave * 64 + __builtin_ctzll(m_stop)));
+      }
+      const uint32_t nb = pb == 2 ? 0u : pb + 1;
+      if (tid == 0) S.mins[nb][0] = S.mins[nb][1] = kImgNone;  // last read two barriers ago, next written behind this one
+      __syncthreads();
+      const uint32_t first_moved = S.mins[pb][0];
+      first_stop = S.mins[pb][1];
+      pb = nb;
+      po ^= 1u;
+      ++round_passes;
+      // settled: nothing moved at or in front of the first stop -- and lanes 0 .. p are exact after pass p in any case
+      if (first_moved == kImgNone || first_moved > first_stop || first_stop < round_passes) break;
+    }
+    passes += round_passes;
+    const uint32_t mine = (uint32_t)tid <= first_stop ? cnt : 0u;  // (first_stop == kImgNone: every lane counts)
+    const uint32_t incl = wave_incl_scan_u32(mine);
+    if (lane == 63) S.wave_tot[wave] = incl;
+    if ((uint32_t)tid == first_stop) S.stop_kind = stop;
+    __syncthreads();
+    uint32_t before = 0, round_total = 0;
+#pragma unroll
+    for (int w = 0; w < kBatchWaves; ++w) {
+      const uint32_t t = S.wave_tot[w];
+      before += w < wave ? t : 0u;
+      round_total += t;
+    }
+    const uint32_t stop_kind = first_stop == kImgNone ? 0u : S.stop_kind;
+    if (stop_kind == kImgCutOff) return finish(GHF_E_CORRUPT, 0);  // the stream ends before a whole end mark
+    if ((uint64_t)total + round_total > cap) return finish(GHF_E_CAP, 0);  // before any store of the round
+    if (kWrite) {
+      const uint32_t rel = before + incl - mine;  // of the lane's first symbol in the round's output
+      uint32_t i = 0;
+      BatchCursor cur;
+      if (mine) cur.seek(stream, stream_bytes, sub0 + start);
+      uint8_t* const sb = reinterpret_cast<uint8_t*>(S.stage);
+#pragma unroll 1
+      for (uint32_t lo = 0; lo < round_total; lo += kImgStageBytes) {  // (min_len 1: a round holds up to 128 Ki symbols)
+        while (i < mine && rel + i < lo + kImgStageBytes) {
+          const uint32_t ent = batch_decode_one(S.t, cur.window(), lb, long_from, max_len);
+          sb[rel + i - lo] = (uint8_t)ent;
+          cur.skip(stream, stream_bytes, ent >> 9);
+          ++i;
+        }
+        __syncthreads();
+        const uint32_t rbytes = round_total - lo < kImgStageBytes ? round_total - lo : kImgStageBytes;
+        batch_store_stage(out + total + lo, S.stage, rbytes, tid);
+        __syncthreads();
+      }
+    }
+    total += round_total;
+    if (stop_kind == kImgEndMark) return finish(GHF_OK, total);
+    carry = S.over[po][kBatchThreads - 1];
+    base += kImgRoundBits;
   }
 }
 
@@ -467,6 +766,11 @@ void launch_compress_batch(const BatchCompressParams& p, uint32_t count, hipStre
 void launch_decode_batch(const BatchDecodeParams& p, uint32_t count, hipStream_t s) {
   if (count == 0) return;
   hipLaunchKernelGGL(k_decode_batch, dim3(count), dim3(kBatchThreads), 0, s, p);
+}
+void launch_decode_images_batch(const BatchImagesParams& p, uint32_t count, hipStream_t s) {
+  if (count == 0) return;
+  if (p.out_ptrs) hipLaunchKernelGGL(k_decode_images_batch<true>, dim3(count), dim3(kBatchThreads), 0, s, p);
+  else hipLaunchKernelGGL(k_decode_images_batch<false>, dim3(count), dim3(kBatchThreads), 0, s, p);
 }
 
 }  // namespace ghf

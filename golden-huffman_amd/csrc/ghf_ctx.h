@@ -135,6 +135,8 @@ struct ghf_ctx {
   ghf::DevBuf<uint64_t> range_chunk;
   // ghf_compress_batch without d_codes: one table set per item (describes nothing between calls)
   ghf::DevBuf<ghf_code> batch_codes;
+  // ghf_decode_images_batch_stats: where the image decoder counts its rounds and passes (the caller's; null = nowhere)
+  uint64_t* images_stats = nullptr;
   std::string err;
 };
 

@@ -188,6 +188,18 @@ struct BatchDecodeParams {
   uint64_t* out_bytes;
   int* item_status;
 };
+// standalone images, nothing else (ghf_decode_images_batch): header, code boundaries and offsets are found by the workgroup
+struct BatchImagesParams {
+  const uint8_t* const* stream_ptrs;
+  const uint64_t* stream_bytes;
+  uint64_t max_stream_bytes;  // ghf_compress_bound(GHF_BATCH_MAX_ITEM): the workgroup's bit offsets fit 32 bits
+  uint8_t* const* out_ptrs;   // null: sizes only (out_caps is ignored)
+  const uint64_t* out_caps;
+  uint64_t* out_bytes;
+  ghf_code* codes;            // [count], may be null
+  int* item_status;
+  uint64_t* stats;            // may be null: [0] += rounds, [1] += passes of every item that reached its body
+};
 
 // K6: side-car reconstruction for foreign streams
 enum SyncKind : uint32_t {  // what SyncParams::no_eof carries
@@ -256,6 +268,7 @@ void launch_store_u64(uint64_t* d_dst, const uint64_t* d_src_opt, uint64_t add, 
 void launch_load_u16(uint64_t* d_dst, const uint16_t* d_src, hipStream_t s);
 void launch_compress_batch(const BatchCompressParams& p, uint32_t count, hipStream_t s);  // one launch, grid = count
 void launch_decode_batch(const BatchDecodeParams& p, uint32_t count, hipStream_t s);
+void launch_decode_images_batch(const BatchImagesParams& p, uint32_t count, hipStream_t s);  // one launch; p.out_ptrs null: sizes only
 void launch_shard_start(const ghf_code* d_code, const uint64_t* d_totals, int rank, uint64_t* d_start_bit, hipStream_t s);
 
 }  // namespace ghf

@@ -129,7 +129,7 @@ EXPORTS = [
     "ghf_crs_sync_piece", "ghf_copy_d2d", "ghf_shard_bytes",
     "ghf_seek_bytes", "ghf_seek_parse", "ghf_seek_pack", "ghf_seek_expand", "ghf_decode_range",
     "ghf_compress_batch_bound", "ghf_batch_index_alloc", "ghf_batch_index_free", "ghf_batch_index_item",
-    "ghf_compress_batch", "ghf_decode_batch",
+    "ghf_compress_batch", "ghf_decode_batch", "ghf_decode_images_batch", "ghf_decode_images_batch_stats",
 ]
 COMM_ID_BYTES = 128
 
@@ -230,6 +230,8 @@ def lib():
     L.ghf_batch_index_item.argtypes = [C.POINTER(BatchIndex), C.c_uint32, sz, C.POINTER(Index)]
     L.ghf_compress_batch.argtypes = [vp, vp, vp, sz, C.c_uint32, vp, vp, vp, vp, C.POINTER(BatchIndex), vp]
     L.ghf_decode_batch.argtypes = [vp, vp, vp, vp, C.POINTER(BatchIndex), vp, C.c_uint32, vp, vp, vp, vp]
+    L.ghf_decode_images_batch.argtypes = [vp, vp, vp, C.c_uint32, vp, vp, vp, vp, vp]
+    L.ghf_decode_images_batch_stats.argtypes = [vp, vp]
     _lib = L
     return L
 
@@ -592,6 +594,47 @@ class Context:
             "ghf_decode_batch")
         return {"out": d_out, "out_stride": out_stride, "out_bytes": out_bytes[:count], "status": status[:count],
                 "out_ptrs": out_ptrs, "out_caps": out_caps}
+
+    def decode_images_batch(self, stream_ptrs, stream_bytes, out=None, caps=None, codes=False):
+        """Standalone .crs2 images and nothing else.  stream_ptrs / stream_bytes: int64 CUDA tensors [count].
+        out=None: the sizes pass -> dict(out_bytes int64[count], status int32[count]).
+        Otherwise the decode pass: `caps` (int64 CUDA tensor [count], e.g. the out_bytes of the sizes pass) says how much
+        room every item gets; out=True allocates one uint8 tensor with item i at i * out_stride, out_stride = the largest
+        cap rounded up to 16 (this reads `caps` back: one host synchronisation); a uint8 CUDA tensor is used as it is, cut
+        into count equal slots.  codes=True: also the items' tables, uint8[count, sizeof(Code)].
+        -> dict(out, out_stride, out_bytes, status[, codes])"""
+        t = self.torch
+        count = int(stream_bytes.numel())
+        out_bytes = t.zeros(max(count, 1), dtype=t.int64, device=self.device)
+        status = t.full((max(count, 1),), -1, dtype=t.int32, device=self.device)
+        d_codes = t.zeros((max(count, 1), C.sizeof(Code)), dtype=t.uint8, device=self.device) if codes else None
+        res = {"out_bytes": out_bytes[:count], "status": status[:count]}
+        out_ptrs = out_caps = None
+        if out is not None:
+            if caps is None:
+                raise ValueError("decode_images_batch: the decode pass needs caps (e.g. the out_bytes of the sizes pass)")
+            if out is True:
+                out_stride = (int(caps.max().item()) + 15) & ~15 if count else 16
+                out = t.empty(max(count * out_stride, 16), dtype=t.uint8, device=self.device)
+            else:
+                out_stride = int(out.numel()) // max(count, 1)
+            out_ptrs = out.data_ptr() + t.arange(count, dtype=t.int64, device=self.device) * out_stride
+            out_caps = t.clamp(caps.to(t.int64), max=out_stride).contiguous()
+            res.update(out=out, out_stride=out_stride, out_ptrs=out_ptrs, out_caps=out_caps)
+        if codes:
+            res["codes"] = d_codes
+        self._chk(
+            self.L.ghf_decode_images_batch(self.h, stream_ptrs.data_ptr(), stream_bytes.data_ptr(), count,
+                                           None if out_ptrs is None else out_ptrs.data_ptr(),
+                                           None if out_caps is None else out_caps.data_ptr(), out_bytes.data_ptr(),
+                                           None if d_codes is None else d_codes.data_ptr(), status.data_ptr()),
+            "ghf_decode_images_batch")
+        return res
+
+    def decode_images_batch_stats(self, d_stats):
+        """d_stats: an int64 CUDA tensor [2] that later decode_images_batch calls add {rounds, passes} to; None: off"""
+        self._chk(self.L.ghf_decode_images_batch_stats(self.h, None if d_stats is None else d_stats.data_ptr()),
+                  "ghf_decode_images_batch_stats")
 
     # ---- seekable streams: the seek table (the persistent form of the side-car) ----------------
     def seek_pack(self, index, d_stream=None, stream_bytes=0, d_table=None, n=None):

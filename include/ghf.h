@@ -282,8 +282,9 @@ int ghf_decode_range(ghf_ctx* ctx, const uint8_t* d_stream, size_t stream_bytes,
  * and d_n_symbols[i] (what the compress call was given) -> d_out_ptrs[i][0 .. d_n_symbols[i]), d_out_bytes[i] <- that
  * size.  The tables pass the checks of ghf_decode (complete prefix code) before anything is decoded; every segment must
  * land on its recorded end and the end mark must follow the last symbol.  No byte outside d_stream_ptrs[i][0 ..
- * d_stream_bytes[i]) is read, whatever tables and side-car hold.  A stream without side-car (a file the reference
- * wrote) goes through ghf_decode(index = NULL).
+ * d_stream_bytes[i]) is read, whatever tables and side-car hold.  Streams without side-car, tables or sizes (files the
+ * reference wrote, stored images of ghf_compress_batch) go through ghf_decode_images_batch below; one large stream
+ * through ghf_decode(index = NULL).
  *
  * Failures are PER ITEM: d_item_status[i] <- a ghf_status_code (GHF_OK is written as well):
  *   GHF_E_EMPTY   the item has 0 bytes            GHF_E_INVAL  more than max_item_bytes; null / misaligned item pointer
@@ -330,6 +331,45 @@ int ghf_decode_batch(ghf_ctx* ctx, const uint8_t* const* d_stream_ptrs, const ui
                      const ghf_code* d_codes /* [count] */, const ghf_batch_index* index, const uint64_t* d_n_symbols,
                      uint32_t count, uint8_t* const* d_out_ptrs, const uint64_t* d_out_caps, uint64_t* d_out_bytes,
                      int* d_item_status /* [count] */);
+
+/* No reference counterpart (the reference decodes one file per process, include/compressor.h:87-92).
+ * Decode `count` standalone .crs2 images that come with nothing else -- files the reference wrote, or images of
+ * ghf_compress_batch whose tables and side-car are gone.  ONE launch, one workgroup per item, asynchronous on the
+ * context's stream, never synchronises; every array is DEVICE memory.
+ * d_out_ptrs == NULL (then d_out_caps is ignored): sizes only -- d_out_bytes[i] <- what item i decodes to.
+ *
+ * Item i = the image at d_stream_ptrs[i] (16-byte aligned), d_stream_bytes[i] of it.  The header is parsed on the device
+ * with every check ghf_parse_header makes; the body is decoded from bit 8 * (1040 + 8 * max_len) until the first end
+ * mark, as ghf_decode does: d_stream_bytes[i] may exceed the stream, what lies behind the end mark is not decoded.  The
+ * result goes to d_out_ptrs[i][0 .. n_i) (no alignment needed), d_out_bytes[i] <- n_i.  On success only d_out[0 .. n_i)
+ * is written; on failure nothing at or beyond d_out_caps[i] is written and d_out_bytes[i] = 0.  No byte outside
+ * d_stream_ptrs[i][0 .. d_stream_bytes[i]) is ever read, whatever the header says.  d_codes[i] (optional) receives
+ * exactly what ghf_parse_header returns for the same header (untouched when the item fails before its header is
+ * accepted).  The one-symbol image of GHF_EMPTY_OK (1049 bytes) is accepted and decodes to nothing: GHF_OK, 0 bytes.
+ *
+ * d_item_status[i] <- (GHF_OK is written as well)
+ *   GHF_E_INVAL   null or misaligned stream pointer; null output pointer in decode mode; d_stream_bytes[i] greater than
+ *                 ghf_compress_bound(GHF_BATCH_MAX_ITEM)
+ *   GHF_E_FORMAT  ghf_parse_header would refuse the header (a stream shorter than its header included)
+ *   GHF_E_CAP     the item decodes to more than d_out_caps[i] (sizes only: the true count is reported with GHF_OK)
+ *   GHF_E_CORRUPT the stream ends before a whole end mark has been found (with a complete prefix code the only
+ *                 corruption any decoder can see)
+ * As in the other batch calls failures are per item and never latch the context's status word.  Call-level errors
+ * (returned at once, nothing queued): null d_stream_ptrs / d_stream_bytes / d_out_bytes / d_item_status, d_out_ptrs
+ * without d_out_caps: GHF_E_INVAL.  count == 0 queues nothing.  The context's plan, histogram, prepared-table and K6
+ * caches are left alone.
+ * The workgroup finds the code boundaries itself, in rounds of 256 subsequences of 512 bits that settle in at most 256
+ * passes each: codes that barely self-synchronise (8/9-bit codes of uniform bytes) cost up to
+ * one lane decoding the item front to back. */
+int ghf_decode_images_batch(ghf_ctx* ctx, const uint8_t* const* d_stream_ptrs, const uint64_t* d_stream_bytes,
+                            uint32_t count, uint8_t* const* d_out_ptrs, const uint64_t* d_out_caps,
+                            uint64_t* d_out_bytes, ghf_code* d_codes /* [count], optional OUT */,
+                            int* d_item_status /* [count] */);
+/* No reference counterpart.  Host only, nothing queued: d_stats (device u64[2], 8-byte aligned; NULL, the default:
+ * nowhere) -- every later ghf_decode_images_batch on this context adds, over all items that reached their body,
+ * d_stats[0] += rounds and d_stats[1] += passes.  The caller zeroes the two words; tools/batch_images_bench.py reads
+ * them to hold the observed passes per round against the bound of 256. */
+int ghf_decode_images_batch_stats(ghf_ctx* ctx, uint64_t* d_stats);
 
 /* Multi-GPU decode of a stream that has no side-car ("per-rank self-sync + one all-gather of symbol
  * counts"; the reference's decoders, canonical_huff_encoder.cc:377-568, are single-stream).  The caller cuts the body
