@@ -37,7 +37,7 @@ constexpr int kStageCapBits = (kStageWords - 8) * 32;
 // K7 decode / K6 side-car reconstruction
 constexpr int kDecPairBitsMax = 10;
 constexpr int kDecLutBitsMax = 12;
-// K7 / K6 keep the direct table in LDS as 32-bit entries, replicated (ghf_decode.hip): 64 KiB of slots + a small region
+// K7 / K6 keep the direct table in LDS as 32-bit entries, replicated (ghf_dec_core.h): 64 KiB of slots + a small region
 constexpr int kDec7LutLog2 = 14;
 constexpr int kDec7LutSlots = 1 << kDec7LutLog2;
 constexpr int kDec7SmallSlots = 1024;  // pair mode (max_len <= 5): the one-symbol table for ragged tails and the end mark, 32 copies
@@ -73,7 +73,7 @@ struct DecTables {
   // workgroups of the running k_decode that have finished; the last one zeroes the counters again (and this word), so
   // that tables stay usable for any number of launches
   uint32_t done;
-  // The direct table(s) exactly as K7 / K6 keep them in LDS (ghf_decode.hip: 32-bit entries, replicated): written once by the
+  // The direct table(s) exactly as K7 / K6 keep them in LDS (ghf_dec_core.h: 32-bit entries, replicated): written once by the
   // table kernels, pulled in by every workgroup with 16-byte loads (round 3 replicated a compact table in every workgroup's
   // prologue: ~3 us per launch of K7 and of every K6 kernel).  One-symbol table: index = the next lut_bits stream bits,
   //   entry = symbol | length << 8 | bit 16: end mark | bit 17: no code of <= lut_bits bits starts with these bits
@@ -231,15 +231,8 @@ struct SyncParams {
   uint64_t* tile_sum;  // [nsub / 256 + 2] symbols per tile, then (in place) their exclusive scan
 };
 
-// kernel launchers (ghf_kernels.hip); all asynchronous on `s`
-void launch_sync_pass(const SyncParams& p, hipStream_t s);
-void launch_sync_counts(const SyncParams& p, uint64_t* d_total, hipStream_t s);
-// deterministic seeding of p.start[] (function-composition scan); ws = sync_scan_workspace(p.nsub) bytes, 256-byte aligned
-size_t sync_scan_workspace(uint64_t nsub);
-void launch_sync_scan(const SyncParams& p, uint8_t* ws, uint32_t stride /* 16: max_len <= 16 is known; 64: it may exceed 32 (.crs); else 32 */,
-                      uint32_t entry /* bit at which the first code begins, < stride */, hipStream_t s);
-void launch_sync_index(const SyncParams& p, uint64_t* d_seg_abs, uint64_t n_symbols, uint64_t* d_chunk_bit, uint32_t* d_seg_bit,
-                       hipStream_t s);
+// ---- kernel launchers; all asynchronous on `s` ---------------------------------------------------------------------------
+// ghf_kernels.hip
 // K1 scratch, all zero between launches: 32 replicas of the 256 totals, the arrival counter (word 8192), 16 ticket
 // counters (word 8208 + 16 k, one 128-byte line each)
 constexpr size_t kHistAccWords = 32 * 256 + 16 + 16 * 16;
@@ -251,25 +244,38 @@ void launch_plan(const uint8_t* d_in, uint64_t n, uint32_t chunk, uint32_t nchun
                  const ghf_code* d_code, uint64_t* d_chunk_off, uint64_t* d_total_bits, hipStream_t s);
 // in-place exclusive scan of d_v[0..count), d_v[count] = total, *d_total = total (one workgroup)
 void launch_scan(uint64_t* d_v, uint32_t count, uint64_t* d_total, hipStream_t s);
-void launch_emit(const EmitParams& p, hipStream_t s);
-void launch_build_decode_tables(const ghf_code* d_code, DecTables* d_dt, int* d_status, hipStream_t s);
-constexpr uint64_t kDecMaxGroups = 0xFFFF0000ull;  // groups of 4096 symbols one k_decode launch takes (2^44 symbols)
-void launch_decode(const DecParams& p, hipStream_t s);
-void launch_seek_pack(const SeekPackParams& p, hipStream_t s);
-void launch_seek_expand(const SeekExpandParams& p, hipStream_t s);
-void launch_decode_head(const DecHeadParams& p, hipStream_t s);
 void launch_crs_build_code(const uint64_t* d_hist, ghf_tree* d_tree, ghf_code* d_code, uint64_t* d_start_bit, int* d_status,
                            hipStream_t s);
 void launch_crs_finish(const ghf_tree* d_tree, const uint64_t* d_total_bits, uint8_t* d_out, uint64_t* d_out_bytes, int* d_status,
                        hipStream_t s);
-void launch_crs_decode_tables(const ghf_tree* d_tree, DecTables* d_dt, int* d_status, hipStream_t s);
 void launch_stream_copy(const uint8_t* d_src, uint8_t* d_dst, uint64_t n, bool nt, hipStream_t s);
 void launch_store_u64(uint64_t* d_dst, const uint64_t* d_src_opt, uint64_t add, hipStream_t s);
 void launch_load_u16(uint64_t* d_dst, const uint16_t* d_src, hipStream_t s);
+void launch_shard_start(const ghf_code* d_code, const uint64_t* d_totals, int rank, uint64_t* d_start_bit, hipStream_t s);
+// ghf_emit.hip
+void launch_emit(const EmitParams& p, hipStream_t s);
+// ghf_decode.hip: the decode tables and K7
+void launch_build_decode_tables(const ghf_code* d_code, DecTables* d_dt, int* d_status, hipStream_t s);
+void launch_crs_decode_tables(const ghf_tree* d_tree, DecTables* d_dt, int* d_status, hipStream_t s);
+constexpr uint64_t kDecMaxGroups = 0xFFFF0000ull;  // groups of 4096 symbols one k_decode launch takes (2^44 symbols)
+void launch_decode(const DecParams& p, hipStream_t s);
+// ghf_sync.hip: K6
+void launch_sync_pass(const SyncParams& p, hipStream_t s);
+void launch_sync_counts(const SyncParams& p, uint64_t* d_total, hipStream_t s);
+// deterministic seeding of p.start[] (function-composition scan); ws = sync_scan_workspace(p.nsub) bytes, 256-byte aligned
+size_t sync_scan_workspace(uint64_t nsub);
+void launch_sync_scan(const SyncParams& p, uint8_t* ws, uint32_t stride /* 16: max_len <= 16 is known; 64: it may exceed 32 (.crs); else 32 */,
+                      uint32_t entry /* bit at which the first code begins, < stride */, hipStream_t s);
+void launch_sync_index(const SyncParams& p, uint64_t* d_seg_abs, uint64_t n_symbols, uint64_t* d_chunk_bit, uint32_t* d_seg_bit,
+                       hipStream_t s);
+// ghf_seek.hip: the seek table and the range head
+void launch_seek_pack(const SeekPackParams& p, hipStream_t s);
+void launch_seek_expand(const SeekExpandParams& p, hipStream_t s);
+void launch_decode_head(const DecHeadParams& p, hipStream_t s);
+// ghf_batch.hip
 void launch_compress_batch(const BatchCompressParams& p, uint32_t count, hipStream_t s);  // one launch, grid = count
 void launch_decode_batch(const BatchDecodeParams& p, uint32_t count, hipStream_t s);
 void launch_decode_images_batch(const BatchImagesParams& p, uint32_t count, hipStream_t s);  // one launch; p.out_ptrs null: sizes only
-void launch_shard_start(const ghf_code* d_code, const uint64_t* d_totals, int rank, uint64_t* d_start_bit, hipStream_t s);
 
 }  // namespace ghf
 #endif

@@ -1,0 +1,237 @@
+// golden-huffman_amd/csrc/ghf_seek.hip -- the seek table (k_seek_pack, k_seek_expand) and the range head (k_decode_head),
+// gfx950 / wave64.
+#include "ghf_dec_core.h"
+
+namespace ghf {
+
+// ------------------------------------------------------------------------------------------------
+// The seek table (no reference counterpart: the .crs2 wire format has no sync points; DESIGN.md "Seekable .crs2"):
+// the side-car in a form small enough to keep beside the file.  Per block of 4096 symbols the absolute start bit and
+// the bit lengths of its eight runs of 512 symbols; k_seek_expand turns that back into the full side-car by decoding
+// code LENGTHS only, one lane per run.  A table comes from disk: nothing in it is trusted.
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_seek_pack(SeekPackParams P) {
+  const uint64_t g = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  uint64_t* const t64 = reinterpret_cast<uint64_t*>(P.table);
+  if (g == 0) {
+    t64[0] = kSeekMagic;
+    t64[1] = (uint64_t)kSeekVersion | ((uint64_t)P.flags << 32);
+    t64[2] = P.n_symbols;
+    t64[3] = (uint64_t)kBlockSymbols | ((uint64_t)kRunSymbols << 32);
+    t64[4] = P.n_blocks;
+    t64[5] = 0;
+    t64[6] = 0;
+    t64[7] = 0;
+  }
+  if (g >= P.n_blocks) return;
+  const uint64_t seg0 = g * (kBlockSymbols / kSegSymbols);
+  uint32_t prev = 0, bad = 0;
+  uint64_t w[2] = {0, 0};
+#pragma unroll
+  for (int k = 0; k < kRunsPerBlock; ++k) {
+    const uint64_t first = seg0 + (uint64_t)k * kRunSegs;
+    uint32_t r = 0;
+    if (first < P.n_segs) {
+      const uint64_t last = first + kRunSegs - 1;
+      const uint32_t e = P.seg_bit[last < P.n_segs ? last : P.n_segs - 1];
+      r = e - prev;
+      prev = e;
+    }
+    bad |= r > 0xFFFFu ? 1u : 0u;
+    w[k >> 2] |= (uint64_t)(r & 0xFFFFu) << (16 * (k & 3));
+  }
+  uint64_t* const rec = t64 + kSeekHeaderBytes / 8 + g * (kSeekRecordBytes / 8);
+  rec[0] = P.chunk_bit[g];
+  rec[1] = w[0];
+  rec[2] = w[1];
+  if (bad) latch_status(P.status, GHF_E_CORRUPT);  // a side-car whose segment ends do not grow: not one of ours
+}
+
+// A lane's cursor over the stream in global memory: big-endian words in order, from whole 16-byte vectors (the stream's
+// last, incomplete one: byte loads; behind the stream: zeros -- no address outside stream[0 .. bytes) is ever formed into
+// a load, whatever the start bit).  The vector behind the current one is always in flight.
+struct SeekCursor {
+  const uint8_t* s;
+  uint64_t bytes, full_bytes;
+  uint64_t vnext;  // the next vector to request
+  uint4 cur, nxt;
+  uint32_t left;   // words of `cur` not yet handed out
+  uint64_t W;
+  uint32_t nextw, o;
+  __device__ __forceinline__ uint4 load(uint64_t v) const {
+    const uint64_t b = v << 4;
+    uint4 r = make_uint4(0, 0, 0, 0);
+    if (b + 16 <= full_bytes) {
+      r = *reinterpret_cast<const uint4*>(s + b);
+      r = make_uint4(bswap32(r.x), bswap32(r.y), bswap32(r.z), bswap32(r.w));
+    } else if (b < bytes) {
+      uint32_t q[4] = {0, 0, 0, 0};
+#pragma unroll
+      for (int j = 0; j < 16; ++j)
+        if (b + j < bytes) q[j >> 2] |= (uint32_t)s[b + j] << (24 - 8 * (j & 3));
+      r = make_uint4(q[0], q[1], q[2], q[3]);
+    }
+    return r;
+  }
+  __device__ __forceinline__ uint32_t word() {
+    if (left == 0) {
+      cur = nxt;
+      nxt = load(vnext);
+      ++vnext;
+      left = 4;
+    }
+    const uint32_t w = cur.x;
+    cur.x = cur.y;
+    cur.y = cur.z;
+    cur.z = cur.w;
+    --left;
+    return w;
+  }
+  // bit <= 8 * bytes (the callers check)
+  __device__ __forceinline__ void open(const uint8_t* stream, uint64_t stream_bytes, uint64_t bit) {
+    s = stream;
+    bytes = stream_bytes;
+    full_bytes = stream_bytes & ~15ull;
+    const uint64_t widx = bit >> 5;
+    const uint64_t v = widx >> 2;
+    cur = load(v);
+    nxt = load(v + 1);
+    vnext = v + 2;
+    left = 4;
+    for (uint32_t k = (uint32_t)(widx & 3u); k; --k) (void)word();
+    const uint32_t w0 = word(), w1 = word();
+    W = win_open(w0, w1);
+    nextw = word();
+    o = (uint32_t)(bit & 31u);
+  }
+  // entry (symbol | length << 8 | kEntEnd) of the code at the cursor; the cursor moves behind it
+  __device__ __forceinline__ uint32_t step(const DecLds& L, const DecLut& T, int lut_bits, int max_len) {
+    while (o >= 32u) {  // (a code of up to 64 bits moves the cursor by up to two words)
+      win_shift(W, nextw, o);
+      nextw = word();
+    }
+    uint32_t ent = dec_lookup(T, win_peek(W, o));
+    if (ent & kEntNone) ent = dec_long_entry_at(L, W, nextw, o, lut_bits, max_len);
+    o += (ent >> 8) & 0xFFu;
+    return ent;
+  }
+};
+
+constexpr int kSeekThreads = 1024;
+
+// One lane per run of 512 symbols.  The lane starts at start_bit + (the lengths of the runs in front of it), decodes code
+// lengths only, writes the end of each of its eight segments relative to the block, and must land exactly on the run's
+// recorded end; lane 0 of a block writes chunk_bit and checks that the block's runs add up to the next record's start.
+// A table that fails either test, or names a bit outside the stream, latches GHF_E_CORRUPT.  Touches neither the ticket
+// counters nor `done` of DecTables.
+__global__ __launch_bounds__(kSeekThreads) void k_seek_expand(SeekExpandParams P) {
+  __shared__ DecLds L;
+  const int tid = threadIdx.x;
+  if (tid == 0) L.status0 = *P.status;
+  const int lut_bits = P.dt->lut_bits, max_len = P.dt->max_len, pair_bits = P.dt->pair_bits;
+  dec_lds_load(L, P.dt, tid, kSeekThreads);
+  __syncthreads();
+  if (L.status0 != 0) return;
+  const uint64_t r = P.g0 * kRunsPerBlock + (uint64_t)blockIdx.x * kSeekThreads + (uint32_t)tid;
+  const uint64_t g = r >> 3;
+  const uint32_t k = (uint32_t)r & 7u;
+  if (g >= P.g1 || g >= P.n_blocks) return;
+  const uint64_t* const rec = reinterpret_cast<const uint64_t*>(P.records) + g * (kSeekRecordBytes / 8);
+  const uint64_t start = rec[0];
+  const uint64_t w0 = rec[1], w1 = rec[2];
+  const uint64_t next_start = (g + 1 < P.n_blocks) ? rec[3] : 0;
+  uint32_t before = 0, mine = 0, total = 0;
+#pragma unroll
+  for (int j = 0; j < kRunsPerBlock; ++j) {
+    const uint32_t b = (uint32_t)(((j < 4 ? w0 : w1) >> (16 * (j & 3))) & 0xFFFFu);
+    before += (uint32_t)j < k ? b : 0u;
+    mine = (uint32_t)j == k ? b : mine;
+    total += b;
+  }
+  const uint64_t end_bit = P.stream_bytes * 8;
+  bool bad = start > end_bit || total > end_bit - start;
+  if (k == 0) {
+    P.chunk_bit[g - P.g0] = bad ? 0ull : start;
+    if (g + 1 < P.n_blocks && next_start - start != (uint64_t)total) bad = true;
+  }
+  const uint64_t sym0 = g * kBlockSymbols + (uint64_t)k * kRunSymbols;
+  const uint32_t nsym = sym0 >= P.n_symbols ? 0u : (P.n_symbols - sym0 >= (uint64_t)kRunSymbols ? (uint32_t)kRunSymbols : (uint32_t)(P.n_symbols - sym0));
+  uint32_t* const seg_out = P.seg_bit + (g - P.g0) * (kBlockSymbols / kSegSymbols) + k * kRunSegs;
+  if (bad || nsym == 0) {
+    if (nsym == 0 && mine != 0) bad = true;  // runs behind the stream's last symbol are empty
+    for (uint32_t j = 0; j * kSegSymbols < nsym; ++j) seg_out[j] = 0;
+    if (bad) latch_status(P.status, GHF_E_CORRUPT);
+    return;
+  }
+  const DecLut T = dec_lut1(L.lut, lut_bits, pair_bits, tid & 63);
+  SeekCursor c;
+  c.open(P.stream, P.stream_bytes, start + before);
+  uint32_t used = 0, acc = 0;
+#pragma unroll 1
+  for (uint32_t done = 0; done < nsym;) {
+    const uint32_t stop = done + (uint32_t)kSegSymbols < nsym ? done + (uint32_t)kSegSymbols : nsym;
+#pragma unroll 1
+    for (; done < stop; ++done) {
+      const uint32_t ent = c.step(L, T, lut_bits, max_len);
+      acc |= ent;
+      used += (ent >> 8) & 0xFFu;
+    }
+    seg_out[(stop - 1) / kSegSymbols] = before + used;
+  }
+  if (used != mine || (acc & (kEntEnd | kEntNone))) latch_status(P.status, GHF_E_CORRUPT);
+}
+
+// The head of a range that does not begin on a block boundary: one wave, one lane per segment of the block, same tables;
+// a lane decodes its segment from the side-car's start and stores the symbols of [lo, hi) only.  A segment that is decoded
+// to its end is checked against the side-car like K7 does.
+__global__ __launch_bounds__(64) void k_decode_head(DecHeadParams P) {
+  __shared__ DecLds L;
+  const int lane = threadIdx.x;
+  if (lane == 0) L.status0 = *P.status;
+  const int lut_bits = P.dt->lut_bits, max_len = P.dt->max_len, pair_bits = P.dt->pair_bits;
+  dec_lds_load(L, P.dt, lane, 64);
+  __syncthreads();
+  if (L.status0 != 0) return;
+  const uint64_t a = P.blk_sym0 + (uint64_t)lane * kSegSymbols;  // my segment: symbols [a, b)
+  if (a >= P.n_symbols) return;
+  const uint64_t b = P.n_symbols - a >= (uint64_t)kSegSymbols ? a + kSegSymbols : P.n_symbols;
+  if (b <= P.lo || a >= P.hi) return;
+  const uint64_t B0 = P.chunk_bit[0];
+  const uint32_t start = lane ? P.seg_bit[lane - 1] : 0u;
+  const uint32_t end = P.seg_bit[lane];
+  const uint64_t end_bit = P.stream_bytes * 8;
+  if (end < start || B0 > end_bit || (uint64_t)end > end_bit - B0) {
+    latch_status(P.status, GHF_E_CORRUPT);
+    return;
+  }
+  const DecLut T = dec_lut1(L.lut, lut_bits, pair_bits, lane);
+  SeekCursor c;
+  c.open(P.stream, P.stream_bytes, B0 + start);
+  const uint64_t stop = b < P.hi ? b : P.hi;
+  uint32_t used = 0, acc = 0;
+#pragma unroll 1
+  for (uint64_t i = a; i < stop; ++i) {
+    const uint32_t ent = c.step(L, T, lut_bits, max_len);
+    acc |= ent;
+    used += (ent >> 8) & 0xFFu;
+    if (i >= P.lo) P.out[i - P.lo] = (uint8_t)ent;
+  }
+  const bool whole = stop == b && b < P.n_symbols;  // (the stream's last segment: what follows it is K7's business)
+  if ((whole && used != end - start) || (acc & (kEntEnd | kEntNone))) latch_status(P.status, GHF_E_CORRUPT);
+}
+
+void launch_seek_pack(const SeekPackParams& p, hipStream_t s) {
+  const uint64_t blocks = (p.n_blocks + 255) / 256;
+  hipLaunchKernelGGL(k_seek_pack, dim3((uint32_t)(blocks ? blocks : 1)), dim3(256), 0, s, p);
+}
+void launch_seek_expand(const SeekExpandParams& p, hipStream_t s) {
+  if (p.g1 <= p.g0) return;
+  const uint64_t lanes = (p.g1 - p.g0) * kRunsPerBlock;
+  hipLaunchKernelGGL(k_seek_expand, dim3((uint32_t)((lanes + kSeekThreads - 1) / kSeekThreads)), dim3(kSeekThreads), 0, s, p);
+}
+void launch_decode_head(const DecHeadParams& p, hipStream_t s) {
+  if (p.hi <= p.lo) return;
+  hipLaunchKernelGGL(k_decode_head, dim3(1), dim3(64), 0, s, p);
+}
+
+}  // namespace ghf

@@ -1,4 +1,4 @@
-"""K6's class walk (csrc/ghf_decode.hip: k6_jump and the table kernel's chain loop) is plain C++ apart from its qualifiers:
+"""K6's class walk (csrc/ghf_sync.hip: k6_jump and the table kernel's chain loop) is plain C++ apart from its qualifiers:
 compiled for the HOST here and run against single-step decoding on random masks, for both class lengths.  (The masks
 themselves -- k6_classes: bit-matrix transposes with v_perm_b32 / v_alignbit_b32 -- are GPU code; they are pinned by the
 -m gpu stream tests, and their arithmetic by scratch-free Python models of the same steps in this file.)"""
@@ -8,7 +8,7 @@ import subprocess
 import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-SRC = os.path.join(HERE, "..", "golden-huffman_amd", "csrc", "ghf_decode.hip")
+SRC = os.path.join(HERE, "..", "golden-huffman_amd", "csrc", "ghf_sync.hip")
 
 MAIN = r'''
 template <int CLEN> void run(const uint64_t* F, const uint64_t* G, uint32_t* land, uint32_t* cnt, uint32_t* eo) {

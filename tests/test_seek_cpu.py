@@ -105,7 +105,7 @@ def test_seek_kernels_use_no_scratch_and_fit_two_workgroups_per_cu():
     """k_seek_expand and k_decode_head keep K7's 68 KiB table image in LDS and a per-lane stream cursor in registers; a
     build that spills is refused here (spilled builds of such kernels have misbehaved on the GPU).  The
     expand kernel's occupancy is an LDS question: at most 80 KiB, so that two 16-wave workgroups share a CU."""
-    text = _kernel_asm("ghf_decode")
+    text = _kernel_asm("ghf_seek")
     for sym in ("_ZN3ghf13k_seek_expandENS_16SeekExpandParamsE", "_ZN3ghf13k_decode_headENS_13DecHeadParamsE",
                 "_ZN3ghf11k_seek_packENS_14SeekPackParamsE"):
         meta = re.search(r"\.name:\s+%s\b(.*?)\.wavefront_size" % re.escape(sym), text, flags=re.S)
