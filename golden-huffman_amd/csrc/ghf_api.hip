@@ -7,6 +7,7 @@
 #include <new>
 #include <string>
 
+#include "ghf_code_rules.h"
 #include "ghf_ctx.h"
 
 using namespace ghf;
@@ -29,6 +30,24 @@ inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 
 // the part of "this side-car is one of ours" that packing and decoding both ask for
 inline bool index_has_arrays(const ghf_index* ix) {
   return ix->d_chunk_bit && ix->d_seg_bit && ix->chunk_symbols == (uint32_t)kBlockSymbols && ix->seg_symbols == (uint32_t)kSegSymbols;
+}
+// ... and its counts are the ones its n_symbols implies
+inline bool index_matches_n(const ghf_index* ix) {
+  return index_has_arrays(ix) && ix->n_segs == segs_for(ix->n_symbols) && ix->n_chunks == blocks_for(ix->n_symbols);
+}
+inline bool index_is_whole(const ghf_index* ix) { return index_matches_n(ix) && ix->n_chunks < kDecMaxGroups; }
+
+// ghf_index and ghf_batch_index: waits for the stream, then frees the two arrays
+template <class Index>
+int free_index_arrays(ghf_ctx* c, Index* idx) {
+  if (!c || !idx) return GHF_E_INVAL;
+  GHF_HIP(c, hipSetDevice(c->device));
+  GHF_HIP(c, hipStreamSynchronize(c->stream));
+  if (idx->d_chunk_bit) (void)hipFree(idx->d_chunk_bit);
+  if (idx->d_seg_bit) (void)hipFree(idx->d_seg_bit);
+  idx->d_chunk_bit = nullptr;
+  idx->d_seg_bit = nullptr;
+  return GHF_OK;
 }
 
 }  // namespace
@@ -252,13 +271,13 @@ int ghf_event_sync(ghf_event* e) {
 
 // ---------------------------------------------------------------------------------------------- encode
 uint32_t ghf_chunk_symbols(size_t n) { return chunk_symbols_for(n); }
-size_t ghf_header_bytes(int max_len) { return 1040 + 8 * (size_t)max_len; }
+size_t ghf_header_bytes(int max_len) { return header_bytes_for((size_t)max_len); }
 
 size_t ghf_compress_bound(size_t n) {
   // header (max_len <= 32) + 9 bits per symbol (a 257-symbol Huffman code never loses to the 9-bit
   // fixed-length code) + end mark, rounded up to whole 16-byte units + one spare unit
   const size_t bits = 9 * (n + 1);
-  size_t b = 1040 + 8 * 32 + (bits + 7) / 8;
+  size_t b = header_bytes_for(32) + (bits + 7) / 8;
   return ((b + 15) & ~(size_t)15) + 16;
 }
 
@@ -398,11 +417,7 @@ int ghf_index_alloc(ghf_ctx* c, size_t n_symbols, ghf_index* out) {
   if (!c || !out) return GHF_E_INVAL;
   GHF_HIP(c, hipSetDevice(c->device));
   std::memset(out, 0, sizeof *out);
-  out->n_symbols = n_symbols;
-  out->chunk_symbols = kBlockSymbols;
-  out->seg_symbols = kSegSymbols;
-  out->n_chunks = (n_symbols + kBlockSymbols - 1) / kBlockSymbols;
-  out->n_segs = (n_symbols + kSegSymbols - 1) / kSegSymbols;
+  index_shape(n_symbols, out);
   GHF_HIP(c, hipMalloc(&out->d_chunk_bit, std::max<size_t>(out->n_chunks, 1) * sizeof(uint64_t)));
   hipError_t e = hipMalloc(&out->d_seg_bit, std::max<size_t>(out->n_segs, 1) * sizeof(uint32_t));
   if (e != hipSuccess) {
@@ -413,16 +428,7 @@ int ghf_index_alloc(ghf_ctx* c, size_t n_symbols, ghf_index* out) {
   return GHF_OK;
 }
 
-int ghf_index_free(ghf_ctx* c, ghf_index* idx) {
-  if (!c || !idx) return GHF_E_INVAL;
-  GHF_HIP(c, hipSetDevice(c->device));
-  GHF_HIP(c, hipStreamSynchronize(c->stream));
-  if (idx->d_chunk_bit) (void)hipFree(idx->d_chunk_bit);
-  if (idx->d_seg_bit) (void)hipFree(idx->d_seg_bit);
-  idx->d_chunk_bit = nullptr;
-  idx->d_seg_bit = nullptr;
-  return GHF_OK;
-}
+int ghf_index_free(ghf_ctx* c, ghf_index* idx) { return free_index_arrays(c, idx); }
 
 // ---------------------------------------------------------------------------------------------- batches
 size_t ghf_compress_batch_bound(size_t max_item_bytes) { return ghf_compress_bound(max_item_bytes); }
@@ -433,8 +439,8 @@ int ghf_batch_index_alloc(ghf_ctx* c, uint32_t count, size_t max_item_bytes, ghf
   std::memset(out, 0, sizeof *out);
   out->count = count;
   out->max_item_bytes = max_item_bytes;
-  out->blocks_per_item = (max_item_bytes + kBlockSymbols - 1) / kBlockSymbols;
-  out->segs_per_item = (max_item_bytes + kSegSymbols - 1) / kSegSymbols;
+  out->blocks_per_item = blocks_for(max_item_bytes);
+  out->segs_per_item = segs_for(max_item_bytes);
   GHF_HIP(c, hipMalloc(&out->d_chunk_bit, std::max<size_t>((size_t)count * out->blocks_per_item, 1) * sizeof(uint64_t)));
   hipError_t e = hipMalloc(&out->d_seg_bit, std::max<size_t>((size_t)count * out->segs_per_item, 1) * sizeof(uint32_t));
   if (e != hipSuccess) {
@@ -445,25 +451,12 @@ int ghf_batch_index_alloc(ghf_ctx* c, uint32_t count, size_t max_item_bytes, ghf
   return GHF_OK;
 }
 
-int ghf_batch_index_free(ghf_ctx* c, ghf_batch_index* idx) {
-  if (!c || !idx) return GHF_E_INVAL;
-  GHF_HIP(c, hipSetDevice(c->device));
-  GHF_HIP(c, hipStreamSynchronize(c->stream));
-  if (idx->d_chunk_bit) (void)hipFree(idx->d_chunk_bit);
-  if (idx->d_seg_bit) (void)hipFree(idx->d_seg_bit);
-  idx->d_chunk_bit = nullptr;
-  idx->d_seg_bit = nullptr;
-  return GHF_OK;
-}
+int ghf_batch_index_free(ghf_ctx* c, ghf_batch_index* idx) { return free_index_arrays(c, idx); }
 
 int ghf_batch_index_item(const ghf_batch_index* idx, uint32_t i, size_t n_i, ghf_index* view) {
   if (!idx || !view || i >= idx->count || n_i > idx->max_item_bytes) return GHF_E_INVAL;
   std::memset(view, 0, sizeof *view);
-  view->n_symbols = n_i;
-  view->chunk_symbols = kBlockSymbols;
-  view->seg_symbols = kSegSymbols;
-  view->n_chunks = (n_i + kBlockSymbols - 1) / kBlockSymbols;
-  view->n_segs = (n_i + kSegSymbols - 1) / kSegSymbols;
+  index_shape(n_i, view);
   view->d_chunk_bit = idx->d_chunk_bit ? idx->d_chunk_bit + (size_t)i * idx->blocks_per_item : nullptr;
   view->d_seg_bit = idx->d_seg_bit ? idx->d_seg_bit + (size_t)i * idx->segs_per_item : nullptr;
   return GHF_OK;
@@ -473,8 +466,7 @@ int ghf_batch_index_item(const ghf_batch_index* idx, uint32_t i, size_t n_i, ghf
 static bool batch_index_covers(const ghf_batch_index* ix, uint32_t count, size_t max_item_bytes) {
   return ix->d_chunk_bit && ix->d_seg_bit && ix->count >= count && ix->max_item_bytes >= max_item_bytes &&
          ix->max_item_bytes <= GHF_BATCH_MAX_ITEM &&
-         ix->blocks_per_item == (ix->max_item_bytes + kBlockSymbols - 1) / kBlockSymbols &&
-         ix->segs_per_item == (ix->max_item_bytes + kSegSymbols - 1) / kSegSymbols;
+         ix->blocks_per_item == blocks_for(ix->max_item_bytes) && ix->segs_per_item == segs_for(ix->max_item_bytes);
 }
 
 int ghf_compress_batch(ghf_ctx* c, const uint8_t* const* d_in_ptrs, const uint64_t* d_in_bytes, size_t max_item_bytes,
@@ -573,73 +565,55 @@ static inline uint32_t be32(const uint8_t* p) {
   return ((uint32_t)p[0] << 24) | ((uint32_t)p[1] << 16) | ((uint32_t)p[2] << 8) | (uint32_t)p[3];
 }
 
-// canonical_huff_encoder.cc:349-374, plus the validation the reference does not do.
+// canonical_huff_encoder.cc:349-374, plus the validation the reference does not do: the rules of ghf_code_rules.h
+// (section 1), which k_decode_images_batch applies to the same words on the device.
 int ghf_parse_header(const uint8_t* h, size_t n, ghf_code* code, size_t* header_bytes) {
   if (!h || !code) return GHF_E_INVAL;
-  if (n < 1040) return GHF_E_FORMAT;
-  if (be32(h) != GHF_NSYM) return GHF_E_FORMAT;
+  if (n < kHeaderFixedBytes || !hdr_count_ok(be32(h))) return GHF_E_FORMAT;  // *code is untouched
   std::memset(code, 0, sizeof *code);
-  const uint8_t* p = h + 4;
-  for (int i = 0; i < GHF_NSYM; ++i, p += 4) code->symbol[i] = be32(p);
+  for (int i = 0; i < GHF_NSYM; ++i) code->symbol[i] = be32(h + 4 * (1 + i));
+  const uint8_t* p = h + 4 * (1 + GHF_NSYM);
   const uint32_t min_len = be32(p), max_len = be32(p + 4);
-  p += 8;
-  if (max_len < 1 || max_len > 32 || min_len < 1 || min_len > max_len) return GHF_E_FORMAT;
-  if (n < 1040 + 8 * (size_t)max_len) return GHF_E_FORMAT;
+  if (!hdr_shape_ok(be32(h), min_len, max_len, n)) return GHF_E_FORMAT;
   code->min_len = (int32_t)min_len;
   code->max_len = (int32_t)max_len;
+  p += 8;
   for (uint32_t i = 1; i <= max_len; ++i, p += 8) {
     code->start_pos[i] = be32(p);
     code->first_code[i] = be32(p + 4);
   }
-  // used symbols are a prefix of symbol_[], all distinct, the end mark among them
   uint32_t used = 0;
-  while (used < GHF_NSYM && code->symbol[used] != 0xFFFFFFFFu) ++used;
-  bool seen[GHF_NSYM] = {false};
+  while (used < GHF_NSYM && code->symbol[used] != kSymUnused) ++used;
+  bool seen[GHF_NSYM] = {false};  // the used symbols are all distinct, the end mark among them
   for (uint32_t i = 0; i < GHF_NSYM; ++i) {
     const uint32_t s = code->symbol[i];
-    if (i < used) {
-      if (s >= GHF_NSYM || seen[s]) return GHF_E_FORMAT;
-      seen[s] = true;
-    } else if (s != 0xFFFFFFFFu) {
-      return GHF_E_FORMAT;
-    }
+    if (!hdr_symbol_ok(i, s, used) || (i < used && seen[s])) return GHF_E_FORMAT;
+    if (i < used) seen[s] = true;
   }
   if (!seen[GHF_NSYM - 1]) return GHF_E_FORMAT;
-  // one symbol only: the empty stream of GHF_EMPTY_OK -- the end mark alone, code "0" (not a complete code: checked here, not below)
   if (used == 1) {
-    if (max_len != 1 || code->first_code[1] != 0 || code->start_pos[1] != 0) return GHF_E_FORMAT;
+    if (!hdr_lone_end_mark_ok((int)max_len, code->start_pos, code->first_code)) return GHF_E_FORMAT;
     code->length[GHF_NSYM - 1] = 1;
     code->codeword[GHF_NSYM - 1] = 0;
-    if (header_bytes) *header_bytes = 1040 + 8;
+    if (header_bytes) *header_bytes = header_bytes_for(1);
     return GHF_OK;
   }
   // rebuild per-symbol lengths/codewords; the code must be the canonical complete prefix code
-  uint64_t kraft = 0;  // in units of 2^-32
-  for (uint32_t len = min_len; len <= max_len; ++len) {
-    const uint32_t a = code->start_pos[len];
-    const uint32_t b = (len < max_len) ? code->start_pos[len + 1] : used;
-    if (a > b || b > used) return GHF_E_FORMAT;
-    if (len == min_len && a != 0) return GHF_E_FORMAT;
-    const uint64_t fc = code->first_code[len];
-    if (fc + (b - a) > (1ull << len)) return GHF_E_FORMAT;
+  unsigned long long kraft = 0;  // in units of 2^-32
+  for (uint32_t len = 1; len <= max_len; ++len) {
+    unsigned long long term;
+    if (!hdr_len_ok((int)len, (int)min_len, (int)max_len, used, code->start_pos, code->first_code, &term)) return GHF_E_FORMAT;
+    kraft += term;
+    if (len < min_len) continue;
+    const uint32_t a = code->start_pos[len], b = (len < max_len) ? code->start_pos[len + 1] : used;
     for (uint32_t r = 0; r < b - a; ++r) {
       const uint32_t s = code->symbol[a + r];
       code->length[s] = len;
-      code->codeword[s] = (uint32_t)fc + r;
-    }
-    kraft += (uint64_t)(b - a) << (32 - len);
-    if (len < max_len) {
-      // canonical_huff_encoder.cc:109-114: first_code[l] = (first_code[l+1] + num[l+1]) / 2
-      const uint32_t nb = ((len + 1 < max_len) ? code->start_pos[len + 2] : used) - code->start_pos[len + 1];
-      if (fc != ((uint64_t)code->first_code[len + 1] + nb) / 2) return GHF_E_FORMAT;
-    } else if (fc != 0) {
-      return GHF_E_FORMAT;
+      code->codeword[s] = code->first_code[len] + r;
     }
   }
-  for (uint32_t i = 1; i < min_len; ++i)
-    if (code->first_code[i] != 1024) return GHF_E_FORMAT;  // canonical_huff_encoder.cc:119-121
   if (kraft != (1ull << 32)) return GHF_E_FORMAT;
-  if (header_bytes) *header_bytes = 1040 + 8 * (size_t)max_len;
+  if (header_bytes) *header_bytes = header_bytes_for(max_len);
   return GHF_OK;
 }
 
@@ -767,7 +741,7 @@ static int settle_boundaries(ghf_ctx* c, SyncParams& p, uint8_t* scan_ws, const 
 
 // sizes c->fidx for n symbols and queues the kernel that fills it from the settled boundaries
 static int build_sidecar(ghf_ctx* c, const SyncParams& p, uint64_t n, uint32_t flags) {
-  const uint64_t n_chunks = (n + kBlockSymbols - 1) / kBlockSymbols, n_segs = (n + kSegSymbols - 1) / kSegSymbols;
+  const uint64_t n_chunks = blocks_for(n), n_segs = segs_for(n);
   ghf_index& ix = c->fidx;
   if (n) {  // (d_seg_abs has one entry more than there are segments)
     int rc = grow(c, c->seg_bit, n_segs);
@@ -777,11 +751,7 @@ static int build_sidecar(ghf_ctx* c, const SyncParams& p, uint64_t n, uint32_t f
     ix.d_chunk_bit = c->chunk_bit.p;
     if (rc) return rc;
   }
-  ix.n_symbols = n;
-  ix.chunk_symbols = kBlockSymbols;
-  ix.seg_symbols = kSegSymbols;
-  ix.n_chunks = n_chunks;
-  ix.n_segs = n_segs;
+  index_shape(n, &ix);
   ix.flags = flags;
   if (n) launch_sync_index(p, c->seg_abs.p, n, ix.d_chunk_bit, ix.d_seg_bit, c->stream);
   GHF_HIP(c, hipGetLastError());
@@ -877,7 +847,7 @@ static int sync_piece(ghf_ctx* c, const char* who, RebuildRequest q, const ghf_c
     GHF_HIP(c, hipMemcpyAsync(c->h->code_lens, &d_code->min_len, sizeof c->h->code_lens, hipMemcpyDeviceToHost, c->stream));
     GHF_HIP(c, hipStreamSynchronize(c->stream));
     const int32_t min_len = c->h->code_lens[0], max_len = c->h->code_lens[1];
-    if (max_len < 1 || max_len > 32 || min_len < 1 || min_len > max_len) return fail(c, GHF_E_FORMAT, "bad min_len / max_len in tables");
+    if (!len_bounds_ok(min_len, max_len)) return fail(c, GHF_E_FORMAT, "bad min_len / max_len in tables");
     q.max_len = max_len;
     q.scan_at_once = max_len - min_len <= 1;
   } else {
@@ -931,9 +901,7 @@ static int nothing_decoded(ghf_ctx* c, uint64_t* d_out_bytes) {
 // p: stream, stream_bytes, out, out_bytes and no_end_mark as the caller has them; the rest is filled here.
 static int decode_with_index(ghf_ctx* c, const char* who, const ghf_index* index, size_t cap, DecParams p) {
   const std::string f = std::string(who) + ": ";
-  if (!index_has_arrays(index) || index->n_segs != (index->n_symbols + kSegSymbols - 1) / kSegSymbols ||
-      index->n_chunks != (index->n_symbols + kBlockSymbols - 1) / kBlockSymbols)
-    return fail(c, GHF_E_INVAL, (f + "malformed index").c_str());
+  if (!index_matches_n(index)) return fail(c, GHF_E_INVAL, (f + "malformed index").c_str());
   if (cap < index->n_symbols) return fail(c, GHF_E_CAP, (f + "output capacity below n_symbols").c_str());
   if (index->n_chunks >= kDecMaxGroups) return fail(c, GHF_E_INVAL, (f + "more than 2^44 symbols in one call").c_str());
   p.dt = c->d_dt;
@@ -976,7 +944,7 @@ int ghf_decode(ghf_ctx* c, const uint8_t* d_stream, size_t stream_bytes, const g
 
 // ---------------------------------------------------------------------------------------------- seek table
 // (no reference counterpart; the format: DESIGN.md "Seekable .crs2")
-size_t ghf_seek_bytes(size_t n_symbols) { return kSeekHeaderBytes + kSeekRecordBytes * (size_t)seek_blocks_for(n_symbols); }
+size_t ghf_seek_bytes(size_t n_symbols) { return kSeekHeaderBytes + kSeekRecordBytes * (size_t)blocks_for(n_symbols); }
 
 static inline uint32_t le32(const uint8_t* p) {
   return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
@@ -992,7 +960,7 @@ int ghf_seek_parse(const uint8_t* h, size_t bytes, ghf_seek_info* info) {
   const uint64_t n = le64(h + 16), n_blocks = le64(h + 32);
   if (flags & ~(uint32_t)GHF_INDEX_NO_END_MARK) return GHF_E_FORMAT;
   if (le32(h + 24) != (uint32_t)kBlockSymbols || le32(h + 28) != (uint32_t)kRunSymbols) return GHF_E_FORMAT;
-  if (n_blocks != seek_blocks_for(n) || n_blocks >= kDecMaxGroups) return GHF_E_FORMAT;
+  if (n_blocks != blocks_for(n) || n_blocks >= kDecMaxGroups) return GHF_E_FORMAT;
   for (size_t i = 40; i < kSeekHeaderBytes; ++i)
     if (h[i]) return GHF_E_FORMAT;
   if (bytes != kSeekHeaderBytes + kSeekRecordBytes * (size_t)n_blocks) return GHF_E_FORMAT;  // truncated, or something behind it
@@ -1007,15 +975,10 @@ int ghf_seek_parse(const uint8_t* h, size_t bytes, ghf_seek_info* info) {
 static int seek_table_ok(ghf_ctx* c, const char* who, const ghf_seek_info* info, const uint8_t* d_table, size_t table_bytes) {
   const std::string f = std::string(who) + ": ";
   if (!aligned16(d_table)) return fail(c, GHF_E_INVAL, (f + "d_table must be 16-byte aligned").c_str());
-  if (info->version != kSeekVersion || (info->flags & ~(uint32_t)GHF_INDEX_NO_END_MARK) || info->n_blocks != seek_blocks_for(info->n_symbols) ||
+  if (info->version != kSeekVersion || (info->flags & ~(uint32_t)GHF_INDEX_NO_END_MARK) || info->n_blocks != blocks_for(info->n_symbols) ||
       info->n_blocks >= kDecMaxGroups || table_bytes != ghf_seek_bytes(info->n_symbols))
     return fail(c, GHF_E_FORMAT, (f + "the seek table does not have the size its header implies").c_str());
   return GHF_OK;
-}
-
-static bool index_is_whole(const ghf_index* ix) {
-  return index_has_arrays(ix) && ix->n_segs == (ix->n_symbols + kSegSymbols - 1) / kSegSymbols &&
-         ix->n_chunks == (ix->n_symbols + kBlockSymbols - 1) / kBlockSymbols && ix->n_chunks < kDecMaxGroups;
 }
 
 int ghf_seek_pack(ghf_ctx* c, const ghf_index* index, const uint8_t* d_stream, size_t stream_bytes, uint8_t* d_table, size_t cap) {
@@ -1033,8 +996,8 @@ int ghf_seek_pack(ghf_ctx* c, const ghf_index* index, const uint8_t* d_stream, s
   p.chunk_bit = index->d_chunk_bit;
   p.seg_bit = index->d_seg_bit;
   p.n_symbols = index->n_symbols;
-  p.n_blocks = seek_blocks_for(index->n_symbols);
-  p.n_segs = (index->n_symbols + kSegSymbols - 1) / kSegSymbols;
+  p.n_blocks = blocks_for(index->n_symbols);
+  p.n_segs = segs_for(index->n_symbols);
   p.flags = index->flags & (uint32_t)GHF_INDEX_NO_END_MARK;
   p.table = d_table;
   p.status = c->d_status;
@@ -1105,7 +1068,7 @@ int ghf_decode_range(ghf_ctx* c, const uint8_t* d_stream, size_t stream_bytes, c
   if (!d_out) return GHF_E_INVAL;
   GHF_HIP(c, hipSetDevice(c->device));
   const uint64_t end = first + count;
-  const uint64_t gA = first / kBlockSymbols, gB = (end + kBlockSymbols - 1) / kBlockSymbols;  // the covered blocks [gA, gB)
+  const uint64_t gA = first / kBlockSymbols, gB = blocks_for(end);  // the covered blocks [gA, gB)
   launch_build_decode_tables(d_code, c->d_dt, c->d_status, c->stream);
   c->prepared.forget();
   const uint64_t* chunk_bit;
@@ -1148,7 +1111,7 @@ int ghf_decode_range(ghf_ctx* c, const uint8_t* d_stream, size_t stream_bytes, c
     p.chunk_bit = chunk_bit + (gI - gA);
     p.seg_bit = seg_bit + (gI - gA) * (kBlockSymbols / kSegSymbols);
     p.n_symbols = end - gI * kBlockSymbols;
-    p.n_segs = (p.n_symbols + kSegSymbols - 1) / kSegSymbols;
+    p.n_segs = segs_for(p.n_symbols);
     p.no_end_mark = (end == n && !(flags & GHF_INDEX_NO_END_MARK)) ? 0u : 1u;
     p.out = d_out + (gI * kBlockSymbols - first);
     p.out_bytes = nullptr;

@@ -6,6 +6,7 @@
 // over five launches (K1, K2+K3, K4, K5 and the header) happens inside the workgroup; the one-wavefront code build, which
 // costs a looping caller 0.26 ms per item on an idle GPU, is hidden by the other workgroups resident on the same CU.
 #include "ghf_build_code.h"
+#include "ghf_code_rules.h"
 
 namespace ghf {
 
@@ -145,7 +146,7 @@ __global__ __launch_bounds__(kBatchThreads) void k_compress_batch(BatchCompressP
   }
   __syncthreads();
   const uint32_t end_len = S.tab[GHF_NSYM - 1].x, end_cw = S.tab[GHF_NSYM - 1].y;
-  const uint32_t hdr_bytes = 1040u + 8u * (uint32_t)max_len;
+  const uint32_t hdr_bytes = header_bytes_for((uint32_t)max_len);
   const uint64_t image_bits = 8ull * hdr_bytes + S.body_bits + end_len;
   const uint64_t image_bytes = (image_bits + 7) >> 3;
   if (image_bytes > cap) {
@@ -264,16 +265,8 @@ __global__ __launch_bounds__(kBatchThreads) void k_compress_batch(BatchCompressP
 constexpr int kBatchDecRoundSegs = kBatchThreads;
 constexpr int kBatchDecRoundBytes = kBatchDecRoundSegs * kSegSymbols;  // 16 KiB
 
-// the decode tables of one item in LDS, shared by k_decode_batch and k_decode_images_batch
-struct BatchDecTab {
-  uint16_t lut[1 << kDecLutBitsMax];  // sym | len << 9; 0: the code is longer than lut_bits
-  uint32_t fcl[36];                   // first_code[len] << (32 - len); 0xFFFFFFFF outside [min_len, max_len]
-  uint32_t sp[36];
-  uint16_t symbol[GHF_NSYM + 3];
-};
-
 struct BatchDecodeLds {
-  BatchDecTab t;
+  CodeTab t;  // the item's decode tables (ghf_code_rules.h)
   alignas(16) uint32_t stage[kBatchDecRoundBytes / 4 + 4];
   unsigned long long kraft;
   int bad;
@@ -292,28 +285,10 @@ __device__ __forceinline__ uint32_t batch_stream_word(const uint8_t* __restrict_
   return r;
 }
 
-// the code of `from` .. `to` bits that the window starts with, as sym | len << 9 (0: none): the codes the direct table
-// does not hold (from = its width + 1), and every code while that table is being filled (from = min_len)
-__device__ __forceinline__ uint32_t batch_search_code(const BatchDecTab& T, uint32_t win, int from, int to) {
-  for (int len = from; len <= to; ++len) {
-    const uint32_t f = T.fcl[len];
-    if (win >= f) {
-      const uint32_t k = T.sp[len] + ((win - f) >> (32 - len));
-      return (k < (uint32_t)GHF_NSYM ? (uint32_t)T.symbol[k] : 256u) | ((uint32_t)len << 9);
-    }
-  }
-  return 0;
-}
-
-// the direct table of lb = min(max_len, 12) bits from fcl / sp / symbol (the caller puts a barrier on both sides)
-__device__ __forceinline__ void batch_fill_lut(BatchDecTab& T, int min_len, int lb, int tid) {
-  for (uint32_t idx = tid; idx < (1u << lb); idx += kBatchThreads) T.lut[idx] = (uint16_t)batch_search_code(T, idx << (32 - lb), min_len, lb);
-}
-
 // sym | len << 9 of the code the 32-bit window starts with; len == 0: no code does
-__device__ __forceinline__ uint32_t batch_decode_one(const BatchDecTab& T, uint32_t win, int lb, int long_from, int max_len) {
+__device__ __forceinline__ uint32_t batch_decode_one(const CodeTab& T, uint32_t win, int lb, int long_from, int max_len) {
   const uint32_t ent = T.lut[win >> (32 - lb)];
-  return ent ? ent : batch_search_code(T, win, long_from, max_len);
+  return ent ? ent : tab_search(T, win, long_from, max_len);
 }
 
 // the bit cursor of the batch decoders: 64 stream bits from word `wi` on, `o` (< 32) of them consumed
@@ -370,7 +345,7 @@ __global__ __launch_bounds__(kBatchThreads) void k_decode_batch(BatchDecodeParam
   else if (n64 > P.max_item_bytes || !stream || !out || (reinterpret_cast<uintptr_t>(stream) & 15u)) refuse = GHF_E_INVAL;
   else if (n64 > P.out_caps[item]) refuse = GHF_E_CAP;
   const int max_len = code->max_len, min_len = code->min_len;
-  if (!refuse && (max_len < 1 || max_len > 32 || min_len < 1 || min_len > max_len)) refuse = GHF_E_FORMAT;
+  if (!refuse && !len_bounds_ok(min_len, max_len)) refuse = GHF_E_FORMAT;
   if (refuse) {
     if (tid == 0) {
       P.item_status[item] = refuse;
@@ -379,8 +354,7 @@ __global__ __launch_bounds__(kBatchThreads) void k_decode_batch(BatchDecodeParam
     return;
   }
   const uint32_t n = (uint32_t)n64;
-  // the checks of k_build_decode_tables: a complete prefix code (Kraft equality), lengths within [min_len, max_len],
-  // first codes that fit their length, start positions inside symbol[]
+  // a complete prefix code (ghf_code_rules.h, section 2), and its tables
   if (tid == 0) {
     S.kraft = 0;
     S.bad = 0;
@@ -389,28 +363,10 @@ __global__ __launch_bounds__(kBatchThreads) void k_decode_batch(BatchDecodeParam
   __syncthreads();
   {
     unsigned long long k = 0;
-    int b = 0;
-    for (int i = tid; i < GHF_NSYM; i += kBatchThreads) {
-      const uint32_t l = code->length[i];
-      if (l) {
-        if ((int)l < min_len || (int)l > max_len) b = 1;
-        else k += 1ull << (32 - l);
-      }
-    }
-    uint32_t f = 0xFFFFFFFFu, p = 0;
-    if (tid >= min_len && tid <= max_len) {
-      const uint32_t fc = code->first_code[tid];
-      p = code->start_pos[tid];
-      if ((tid < 32 && fc > (1u << tid)) || p > (uint32_t)GHF_NSYM) b = 1;
-      f = fc << (32 - tid);
-    }
-    if (tid < 36) {
-      S.t.fcl[tid] = f;
-      S.t.sp[tid] = p;
-    }
-    for (int i = tid; i < GHF_NSYM; i += kBatchThreads) S.t.symbol[i] = (uint16_t)(code->symbol[i] > 256u ? 256u : code->symbol[i]);
+    if (!code_share_ok(code, min_len, max_len, tid, kBatchThreads, &k)) atomicOr(&S.bad, 1);
     if (k) atomicAdd(&S.kraft, k);
-    if (b) atomicOr(&S.bad, 1);
+    if (tid < 36) tab_load_row(S.t, tid, min_len, max_len, code->first_code, code->start_pos);
+    for (int i = tid; i < GHF_NSYM; i += kBatchThreads) S.t.symbol[i] = tab_symbol(code->symbol[i]);
   }
   __syncthreads();
   if (S.bad || S.kraft != (1ull << 32)) {
@@ -421,13 +377,13 @@ __global__ __launch_bounds__(kBatchThreads) void k_decode_batch(BatchDecodeParam
     return;
   }
   const int lb = max_len < kDecLutBitsMax ? max_len : kDecLutBitsMax;
-  batch_fill_lut(S.t, min_len, lb, tid);
+  tab_fill_lut(S.t, min_len, lb, tid, kBatchThreads);
   __syncthreads();
 
   const uint64_t* const chunk_bit = P.chunk_bit + (uint64_t)item * P.blocks_per_item;
   const uint32_t* const seg_bit = P.seg_bit + (uint64_t)item * P.segs_per_item;
   const uint64_t end_bit = stream_bytes * 8;
-  const uint32_t nsegs = (n + kSegSymbols - 1) / kSegSymbols;
+  const uint32_t nsegs = (uint32_t)segs_for(n);
   const int long_from = lb + 1 > min_len ? lb + 1 : min_len;
 
 #pragma unroll 1
@@ -489,7 +445,7 @@ __global__ __launch_bounds__(kBatchThreads) void k_decode_batch(BatchDecodeParam
 
 // ----------------------------------------------------------------------------------------------------------------------
 // decode of standalone images (ghf_decode_images_batch): the image alone is enough.  The workgroup
-// parses and validates the header with every check ghf_parse_header makes, fills the same tables k_decode_batch uses,
+// parses and validates the header with every check ghf_parse_header makes (written out: see section 1), fills the same tables,
 // then finds the code boundaries itself: rounds of 256 subsequences of 512 bits, one per lane, settled by passes in
 // which lane k restarts from where lane k - 1 landed until nothing moves at or in front of the first end mark (lane 0
 // starts at an exactly known bit, so the fixed point is the true segmentation).  A scan of the lanes' symbol counts gives
@@ -502,7 +458,7 @@ constexpr uint32_t kImgNone = 0xFFFFFFFFu;
 constexpr uint32_t kImgEndMark = 1, kImgCutOff = 2;  // why a lane stopped inside its subsequence
 
 struct BatchImagesLds {
-  BatchDecTab t;
+  CodeTab t;
   // header phase: the raw symbol[] words, length / codeword by symbol, seen[], the raw start_pos / first_code words
   alignas(16) uint32_t stage[kImgStageBytes / 4 + 4];
   uint16_t over[2][kBatchThreads];  // bits each lane's last code runs past its subsequence; written in pass p, read in p + 1
@@ -540,14 +496,19 @@ __global__ __launch_bounds__(kBatchThreads) void k_decode_images_batch(BatchImag
     return finish(GHF_E_INVAL, 0);
 
   // ---- 1. the header: canonical_huff_encoder.cc:349-374 with the checks of ghf_parse_header ----
-  // lengths are bounded before the header's size is trusted, the size against stream_bytes before the tables are read
-  if (stream_bytes < 1040) return finish(GHF_E_FORMAT, 0);
+  // lengths are bounded before the header's size is trusted, the size against stream_bytes before the tables are read.
+  // The rules are hdr_shape_ok, hdr_symbol_ok, hdr_len_ok and hdr_lone_end_mark_ok of ghf_code_rules.h, WRITTEN OUT here:
+  // called as functions (any one of them, even len_bounds_ok alone) they re-lay this kernel, and both instantiations
+  // measured 1 .. 7 % slower on the MI355X although the round loops kept the parent's opcodes (profiles/code_rules/
+  // README.md).  In this form the listing is the parent's.  tests/header_cases.py holds one corrupted header per rule and
+  // tests/test_gpu_batch_images.py asks that this copy and the host parser give the same verdicts.
+  if (stream_bytes < kHeaderFixedBytes) return finish(GHF_E_FORMAT, 0);
   const uint32_t* __restrict__ const hw = reinterpret_cast<const uint32_t*>(stream);
   const uint32_t min_len_u = bswap32(hw[GHF_NSYM + 1]), max_len_u = bswap32(hw[GHF_NSYM + 2]);
   if (bswap32(hw[0]) != (uint32_t)GHF_NSYM || max_len_u < 1 || max_len_u > 32 || min_len_u < 1 || min_len_u > max_len_u)
     return finish(GHF_E_FORMAT, 0);
   const int min_len = (int)min_len_u, max_len = (int)max_len_u;
-  const uint32_t hdr_bytes = 1040u + 8u * max_len_u;
+  const uint32_t hdr_bytes = header_bytes_for(max_len_u);
   if (stream_bytes < hdr_bytes) return finish(GHF_E_FORMAT, 0);
 
   uint32_t* const raw = S.stage;                     // symbol[] as stored
@@ -575,7 +536,7 @@ __global__ __launch_bounds__(kBatchThreads) void k_decode_images_batch(BatchImag
   }
   __syncthreads();
   for (int i = tid; i < GHF_NSYM; i += kBatchThreads)
-    if (raw[i] == 0xFFFFFFFFu) atomicMin(&S.used, (uint32_t)i);
+    if (raw[i] == kSymUnused) atomicMin(&S.used, (uint32_t)i);
   __syncthreads();
   const uint32_t used = S.used;  // used symbols are a prefix of symbol[], all distinct, the end mark among them
   {
@@ -625,13 +586,8 @@ __global__ __launch_bounds__(kBatchThreads) void k_decode_images_batch(BatchImag
       }
     }
   }
-  // the tables k_decode_batch builds from a ghf_code
-  if (tid < 36) {
-    const bool in = tid >= min_len && tid <= max_len;
-    S.t.fcl[tid] = in ? fcraw[tid] << (32 - tid) : 0xFFFFFFFFu;
-    S.t.sp[tid] = in ? spraw[tid] : 0u;
-  }
-  for (int i = tid; i < GHF_NSYM; i += kBatchThreads) S.t.symbol[i] = (uint16_t)(raw[i] > 256u ? 256u : raw[i]);
+  if (tid < 36) tab_load_row(S.t, tid, min_len, max_len, fcraw, spraw);
+  for (int i = tid; i < GHF_NSYM; i += kBatchThreads) S.t.symbol[i] = tab_symbol(raw[i]);
   __syncthreads();
   if (P.codes) {
     ghf_code* const code = P.codes + item;
@@ -655,7 +611,7 @@ __global__ __launch_bounds__(kBatchThreads) void k_decode_images_batch(BatchImag
   }
   const int lb = max_len < kDecLutBitsMax ? max_len : kDecLutBitsMax;
   const int long_from = lb + 1 > min_len ? lb + 1 : min_len;
-  batch_fill_lut(S.t, min_len, lb, tid);
+  tab_fill_lut(S.t, min_len, lb, tid, kBatchThreads);
   __syncthreads();  // (the header's scratch in the stage is dead from here on)
 
   // ---- 2. + 3. rounds of 256 subsequences ----

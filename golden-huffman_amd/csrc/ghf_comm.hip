@@ -149,7 +149,7 @@ int ghf_comm_allgather_total(ghf_ctx* c, ghf_comm* m, const uint64_t* d_total, u
 }
 
 size_t ghf_shard_bound(size_t n) {
-  size_t b = 1040 + 8 * 32 + 4 * n + 8;
+  size_t b = header_bytes_for(32) + 4 * n + 8;
   return ((b + 15) & ~(size_t)15) + 32;
 }
 
@@ -167,7 +167,7 @@ int ghf_shard_bytes(ghf_ctx* c, const ghf_code* d_code, const uint64_t* d_totals
   if (e != hipSuccess) return fail(c, GHF_E_HIP, "ghf_shard_bytes: copy totals / code lengths to host");
   if (lens[1] < 1 || lens[1] > 32 || eof_len > 32) return fail(c, GHF_E_FORMAT, "ghf_shard_bytes: bad max_len in tables");
   // the arithmetic of K5's emit_begin (ghf_emit.hip): the shard's first bit, its last, the 16-byte units between
-  uint64_t start = 8ull * (1040ull + 8ull * (uint64_t)lens[1]);
+  uint64_t start = 8ull * header_bytes_for((uint64_t)lens[1]);
   for (int h = 0; h < rank; ++h) start += tot[(size_t)h];
   uint64_t end = start + tot[(size_t)rank];
   if (rank == world - 1) end = (end + eof_len + 7) & ~7ull;  // end mark + padding to a byte

@@ -1,6 +1,7 @@
 // golden-huffman_amd/csrc/ghf_decode.hip -- the decode-table kernels and K7 (table-driven block-parallel decode),
 // gfx950 / wave64.  (K6, the side-car reconstruction for streams that come without one: ghf_sync.hip; the seek table and
 // the range head: ghf_seek.hip; what they share: ghf_dec_core.h.)  File:line citations are relative to the reference tree.
+#include "ghf_code_rules.h"
 #include "ghf_dec_core.h"
 
 namespace ghf {
@@ -19,6 +20,9 @@ __device__ __forceinline__ void dec_image_fill(DecTables* __restrict__ dt, const
   uint4* const img4 = reinterpret_cast<uint4*>(dt->image);
   if (pb) {
     const int r2 = GHF_DEC_COPY_SHIFT(pb);
+    // (unrolled sixteen times, as the compiler does now that k_build_decode_tables keeps CodeTab in LDS, that kernel takes 94
+    //  registers; the pragma can go if it stops doing so)
+#pragma unroll 1
     for (int g = tid; g < (1 << (pb + r2 - 2)); g += nthreads) {
       const uint32_t e = lut2[(4 * g) >> r2];
       img4[g] = make_uint4(e, e, e, e);
@@ -38,22 +42,18 @@ __device__ __forceinline__ void dec_image_fill(DecTables* __restrict__ dt, const
 
 __global__ __launch_bounds__(256) void k_build_decode_tables(const ghf_code* __restrict__ code, DecTables* __restrict__ dt,
                                                              int* __restrict__ status) {
-  __shared__ uint32_t fcl[36];
-  __shared__ uint32_t sp[36];
+  __shared__ CodeTab T;  // fcl / sp / symbol and the one-symbol direct table (ghf_code_rules.h)
   __shared__ unsigned long long kraft;
   __shared__ int bad;
-  __shared__ uint16_t s_lut[1 << kDecLutBitsMax];    // sym | len << 9 ; 0 = code longer than lut_bits
   __shared__ uint32_t s_lut2[1 << kDecPairBitsMax];  // sym0 | sym1 << 8 | (len0 + len1) << 16 ; bit 30 = not two data symbols
   const int tid = threadIdx.x;
   const int max_len = code->max_len, min_len = code->min_len;
-  if (max_len < 1 || max_len > 32 || min_len < 1 || min_len > max_len) {
+  if (!len_bounds_ok(min_len, max_len)) {
     if (tid == 0) latch_status(status, GHF_E_FORMAT);
     return;
   }
   // The tables may come from anywhere (ghf_parse_header checks a header on the host; a caller's own ghf_code is not
-  // checked by anyone else).  A Huffman code over >= 2 symbols is COMPLETE: the lengths satisfy Kraft with equality
-  // (sum of 2^-len == 1), every length lies in [min_len, max_len], first codes fit their length and start positions
-  // stay inside symbol[].  Anything else would leave table entries without a code (length 0) and is refused.
+  // checked by anyone else): a complete prefix code, or refused (ghf_code_rules.h, section 2).
   if (tid == 0) {
     kraft = 0;
     bad = 0;
@@ -61,20 +61,8 @@ __global__ __launch_bounds__(256) void k_build_decode_tables(const ghf_code* __r
   __syncthreads();
   {
     unsigned long long k = 0;
-    int b = 0;
-    for (int i = tid; i < GHF_NSYM; i += 256) {
-      const uint32_t l = code->length[i];
-      if (l) {
-        if ((int)l < min_len || (int)l > max_len) b = 1;
-        else k += 1ull << (32 - l);
-      }
-    }
-    if (tid >= min_len && tid <= max_len) {
-      const uint32_t fc = code->first_code[tid];
-      if ((tid < 32 && fc > (1u << tid)) || code->start_pos[tid] > (uint32_t)GHF_NSYM) b = 1;
-    }
+    if (!code_share_ok(code, min_len, max_len, tid, 256, &k)) atomicOr(&bad, 1);
     if (k) atomicAdd(&kraft, k);
-    if (b) atomicOr(&bad, 1);
   }
   __syncthreads();
   const bool lone_end_mark = max_len == 1 && kraft == (1ull << 31) && code->length[GHF_NSYM - 1] == 1;  // GHF_EMPTY_OK's stream
@@ -84,17 +72,11 @@ __global__ __launch_bounds__(256) void k_build_decode_tables(const ghf_code* __r
   }
   const int lb = max_len < kDecLutBitsMax ? max_len : kDecLutBitsMax;
   if (tid < 36) {
-    uint32_t f = 0xFFFFFFFFu, p = 0;
-    if (tid >= min_len && tid <= max_len) {
-      f = code->first_code[tid] << (32 - tid);
-      p = code->start_pos[tid];
-    }
-    fcl[tid] = f;
-    sp[tid] = p;
-    dt->fc_left[tid] = f;
-    dt->start_pos[tid] = p;
+    tab_load_row(T, tid, min_len, max_len, code->first_code, code->start_pos);
+    dt->fc_left[tid] = T.fcl[tid];
+    dt->start_pos[tid] = T.sp[tid];
   }
-  for (int i = tid; i < GHF_NSYM; i += 256) dt->symbol[i] = (uint16_t)(code->symbol[i] > 256u ? 256u : code->symbol[i]);
+  for (int i = tid; i < GHF_NSYM; i += 256) dt->symbol[i] = T.symbol[i] = tab_symbol(code->symbol[i]);
   // two symbols per lookup when any two codes fit the index (small alphabets: 16-symbol data has max_len 5)
   const int pb = 2 * max_len <= kDecPairBitsMax ? 2 * max_len : 0;
   if (tid == 0) {
@@ -108,31 +90,21 @@ __global__ __launch_bounds__(256) void k_build_decode_tables(const ghf_code* __r
   }
   if (tid < 16) dt->ticket[tid * 32] = 0;
   __syncthreads();
-  auto one = [&](uint32_t v, int upto) -> uint32_t {  // sym | len << 9 of the code of <= upto bits at the top of v; 0: none
-    for (int len = min_len; len <= upto; ++len) {
-      if (v >= fcl[len]) {
-        const uint32_t k = sp[len] + ((v - fcl[len]) >> (32 - len));
-        const uint32_t sym = k < GHF_NSYM ? code->symbol[k] : 256u;
-        return (sym > 256u ? 256u : sym) | ((uint32_t)len << 9);
-      }
-    }
-    return 0u;
-  };
-  for (uint32_t idx = tid; idx < (1u << lb); idx += 256) s_lut[idx] = (uint16_t)one(idx << (32 - lb), lb);
+  tab_fill_lut(T, min_len, lb, tid, 256);
   for (uint32_t idx = tid; pb && idx < (1u << pb); idx += 256) {
     const uint32_t v = idx << (32 - pb);
-    const uint32_t e0 = one(v, max_len);
+    const uint32_t e0 = tab_search(T, v, min_len, max_len);
     uint32_t ent = (1u << 30) | (1u << 16);  // not a data symbol: flagged, one bit consumed
     if (e0 && (e0 & 0x1FFu) != 256u) {
       const uint32_t l0 = e0 >> 9;
-      const uint32_t e1 = one(v << l0, max_len);
+      const uint32_t e1 = tab_search(T, v << l0, min_len, max_len);
       if (e1 && (e1 & 0x1FFu) != 256u) ent = (e0 & 0xFFu) | ((e1 & 0xFFu) << 8) | ((l0 + (e1 >> 9)) << 16);
       else ent = (1u << 30) | (l0 << 16);
     }
     s_lut2[idx] = ent;
   }
   __syncthreads();
-  dec_image_fill(dt, s_lut, s_lut2, lb, pb, tid, 256);
+  dec_image_fill(dt, T.lut, s_lut2, lb, pb, tid, 256);
 }
 
 // .crs: the same direct table, filled by walking the tree DecodeHuffTree::do_build_tree would rebuild

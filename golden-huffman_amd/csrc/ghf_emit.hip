@@ -610,7 +610,7 @@ __device__ __forceinline__ bool emit_begin(const EmitParams& P, EmitGeom& G, int
   const int tid = threadIdx.x;
   if (tid == 0) *status0 = *P.status;  // a previous stage failed -> uniform exit (checked below: its round trip overlaps the others)
   G.max_len = P.code->max_len;
-  G.start_bit = P.d_start_bit ? *P.d_start_bit : 8ull * (1040ull + 8ull * (uint64_t)G.max_len);
+  G.start_bit = P.d_start_bit ? *P.d_start_bit : 8ull * header_bytes_for((uint64_t)G.max_len);
   G.origin_byte = (P.flags & GHF_EMIT_REBASE) ? ((G.start_bit >> 7) << 4) : 0ull;
   // where the stream ends; does it fit?  (every workgroup computes the same answer from the same few words)
   uint64_t end = G.start_bit + P.chunk_off[P.nchunks];
@@ -734,7 +734,7 @@ __global__ __launch_bounds__(64) void k_emit_empty(EmitParams P) {
     if (lane == 0) latch_status(P.status, GHF_E_FORMAT);
     return;
   }
-  const uint64_t S = P.d_start_bit ? *P.d_start_bit : 8ull * (1040ull + 8ull * (uint64_t)max_len);
+  const uint64_t S = P.d_start_bit ? *P.d_start_bit : 8ull * header_bytes_for((uint64_t)max_len);
   const uint64_t origin = (P.flags & GHF_EMIT_REBASE) ? ((S >> 7) << 4) : 0ull;
   const uint32_t el = last ? P.code->length[GHF_NSYM - 1] : 0u;
   const uint64_t end = last ? ((S + el + 7) & ~7ull) : S;

@@ -42,6 +42,21 @@ constexpr int kDec7LutLog2 = 14;
 constexpr int kDec7LutSlots = 1 << kDec7LutLog2;
 constexpr int kDec7SmallSlots = 1024;  // pair mode (max_len <= 5): the one-symbol table for ragged tails and the end mark, 32 copies
 
+// the .crs2 header: the count word, symbol[257], min_len, max_len, then a (start_pos, first_code) row per length 1..max_len
+constexpr uint64_t kHeaderFixedBytes = 4 * (GHF_NSYM + 3);  // 1040
+template <class T>  // in the type of its argument: kernels that count in 32 bits keep doing so
+__host__ __device__ constexpr inline T header_bytes_for(T max_len) { return (T)kHeaderFixedBytes + 8 * max_len; }
+// the side-car of n symbols: blocks (one absolute bit each) and segments (one relative end bit each)
+__host__ __device__ constexpr inline uint64_t blocks_for(uint64_t n) { return (n + kBlockSymbols - 1) / kBlockSymbols; }
+__host__ __device__ constexpr inline uint64_t segs_for(uint64_t n) { return (n + kSegSymbols - 1) / kSegSymbols; }
+inline void index_shape(uint64_t n, ghf_index* ix) {  // everything of a ghf_index but its flags and its arrays
+  ix->n_symbols = n;
+  ix->chunk_symbols = kBlockSymbols;
+  ix->seg_symbols = kSegSymbols;
+  ix->n_chunks = blocks_for(n);
+  ix->n_segs = segs_for(n);
+}
+
 inline uint32_t chunk_symbols_for(uint64_t n) {
   const uint64_t per_slot = (n + kEmitSlots - 1) / kEmitSlots;
   uint64_t c = (per_slot + kChunkQuantum - 1) / kChunkQuantum * kChunkQuantum;
@@ -124,7 +139,6 @@ constexpr size_t kSeekHeaderBytes = 64;
 constexpr size_t kSeekRecordBytes = 24;
 constexpr uint64_t kSeekMagic = 0x314B454553464847ull;  // "GHFSEEK1"
 constexpr uint32_t kSeekVersion = 1;
-inline uint64_t seek_blocks_for(uint64_t n) { return (n + kBlockSymbols - 1) / kBlockSymbols; }
 
 struct SeekPackParams {
   const uint64_t* chunk_bit;

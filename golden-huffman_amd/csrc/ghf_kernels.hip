@@ -581,7 +581,7 @@ void launch_load_u16(uint64_t* d_dst, const uint16_t* d_src, hipStream_t s) { hi
 
 // multi-GPU: this rank's absolute start bit = header bits + body bits of all lower ranks
 __global__ void k_shard_start(const ghf_code* code, const uint64_t* totals, int rank, uint64_t* start_bit) {
-  uint64_t b = 8ull * (1040ull + 8ull * (uint64_t)code->max_len);
+  uint64_t b = 8ull * header_bytes_for((uint64_t)code->max_len);
   for (int r = 0; r < rank; ++r) b += totals[r];
   *start_bit = b;
 }

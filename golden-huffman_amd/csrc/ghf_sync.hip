@@ -794,7 +794,7 @@ void launch_sync_counts(const SyncParams& p, uint64_t* d_total, hipStream_t s) {
 }
 void launch_sync_index(const SyncParams& p, uint64_t* d_seg_abs, uint64_t n_symbols, uint64_t* d_chunk_bit, uint32_t* d_seg_bit,
                        hipStream_t s) {
-  const uint64_t n_segs = (n_symbols + kSegSymbols - 1) / kSegSymbols;
+  const uint64_t n_segs = segs_for(n_symbols);
   const uint64_t trips = (p.nsub + kK6Threads - 1) / kK6Threads;
   hipLaunchKernelGGL(k_sync_index, dim3((uint32_t)(trips < 256 ? (trips ? trips : 1) : 256)), dim3(kK6Threads), 0, s, p, d_seg_abs, n_segs, n_symbols);
   if (n_segs) hipLaunchKernelGGL(k_sync_finalize, dim3((uint32_t)((n_segs + 255) / 256)), dim3(256), 0, s, d_seg_abs, n_segs,

@@ -1,0 +1,144 @@
+"""Corrupted .crs2 headers and ghf_code tables, one broken rule each (golden-huffman_amd/csrc/ghf_code_rules.h).
+
+Shared by tests/test_header_rules_cpu.py (ghf_parse_header on the host), tests/test_gpu_batch_images.py (the same
+headers through k_decode_images_batch), tests/test_gpu_batch.py and tests/test_gpu_parity.py (the code rules through
+k_decode_batch and k_build_decode_tables).  Everything starts from the oracle's image of one 4 KiB item; nothing here
+comes from the library under test.  The returned arrays are shared: callers copy before they change one.
+
+Where the format allows, a case leaves every other rule intact (the recurrence, first_code[max_len], first_code[1], the
+symbol cases, the lone end mark, every code case).  Some rules cannot be broken alone: the recurrence pins every
+first_code, so a first_code that overflows its length also breaks it; start positions are counts, so moving one changes
+the Kraft sum, and one beyond `used` is also above its successor."""
+import functools
+
+import numpy as np
+
+import datagen as dg
+from oracle import oracle as orc
+
+NSYM = 257
+# the names of header_cases()'s cases, in order (static: test modules parametrise over them without running the oracle)
+CASE_NAMES = [
+    "count word is not 257", "max_len 0", "max_len 33", "min_len 0", "min_len > max_len", "truncated to 1039 bytes",
+    "truncated to header_bytes - 1", "a used symbol >= 257", "a symbol twice", "a word behind the first unused slot",
+    "no end mark among the used symbols", "start_pos[min_len] != 0", "start_pos decreases", "a start_pos exceeds used",
+    "first_code + count > 2^len", "recurrence broken at one length", "first_code[max_len] != 0", "first_code[1] != 1024",
+    "lone end mark with max_len 2", "lone end mark with first_code[1] = 1",
+]
+UNUSED = 0xFFFFFFFF
+MIN_LEN_AT, MAX_LEN_AT, ROWS_AT = 4 * (NSYM + 1), 4 * (NSYM + 2), 4 * (NSYM + 3)  # 1032, 1036, 1040
+
+
+def word(img, at):
+    return int.from_bytes(img[at : at + 4].tobytes(), "big")
+
+
+def put(img, at, value):
+    """a copy of img with the big-endian word at byte `at` replaced"""
+    out = img.copy()
+    out[at : at + 4] = np.frombuffer(int(value).to_bytes(4, "big"), dtype=np.uint8)
+    return out
+
+
+def sym_at(i):
+    return 4 * (1 + i)
+
+
+def sp_at(length):
+    return ROWS_AT + 8 * (length - 1)
+
+
+def fc_at(length):
+    return sp_at(length) + 4
+
+
+@functools.lru_cache(maxsize=None)
+def header_cases():
+    """-> (data, image, empty image, [(name, corrupted image)]): every corrupted image breaks one header rule"""
+    data = dg.make("zipf", 4096, seed=17)
+    img = orc.compress(data)
+    min_len, max_len = word(img, MIN_LEN_AT), word(img, MAX_LEN_AT)
+    assert min_len >= 2 and max_len >= min_len + 2, (min_len, max_len)
+    hdr = ROWS_AT + 8 * max_len
+    symbol = [word(img, sym_at(i)) for i in range(NSYM)]
+    used = symbol.index(UNUSED)
+    assert 3 <= used and used + 1 < NSYM and all(s == UNUSED for s in symbol[used:])
+    sp = {l: word(img, sp_at(l)) for l in range(1, max_len + 1)}
+    fc = {l: word(img, fc_at(l)) for l in range(1, max_len + 1)}
+    assert sp[min_len] == 0 and sp[min_len + 1] >= 1 and fc[max_len] == 0 and fc[1] == 1024
+    end_at = symbol.index(NSYM - 1)
+    plain = [i for i in range(used) if i != end_at]  # positions of data symbols
+    absent = next(v for v in range(256) if v not in symbol[:used])
+    mid = min_len + 1  # a length strictly between min_len and max_len
+
+    empty = orc.compress_empty()
+    assert empty.size == 1049 and word(empty, MAX_LEN_AT) == 1
+    # the lone end mark with max_len = 2: a second (start_pos, first_code) row is there, so only that rule is broken
+    empty2 = np.concatenate([put(empty, MAX_LEN_AT, 2)[:1048], np.zeros(8, dtype=np.uint8), empty[1048:]])
+
+    cases = [
+        ("count word is not 257", put(img, 0, 256)),
+        ("max_len 0", put(img, MAX_LEN_AT, 0)),
+        ("max_len 33", put(img, MAX_LEN_AT, 33)),
+        ("min_len 0", put(img, MIN_LEN_AT, 0)),
+        ("min_len > max_len", put(img, MIN_LEN_AT, max_len + 1)),
+        ("truncated to 1039 bytes", img[:1039].copy()),
+        ("truncated to header_bytes - 1", img[: hdr - 1].copy()),
+        ("a used symbol >= 257", put(img, sym_at(plain[0]), 257)),
+        ("a symbol twice", put(img, sym_at(plain[0]), symbol[plain[1]])),
+        ("a word behind the first unused slot", put(img, sym_at(used + 1), absent)),
+        ("no end mark among the used symbols", put(img, sym_at(end_at), absent)),
+        ("start_pos[min_len] != 0", put(img, sp_at(min_len), 1)),
+        ("start_pos decreases", put(img, sp_at(min_len + 2), sp[min_len + 1] - 1)),
+        ("a start_pos exceeds used", put(img, sp_at(max_len), used + 1)),
+        ("first_code + count > 2^len", put(img, fc_at(min_len), 1 << min_len)),
+        ("recurrence broken at one length", put(img, fc_at(mid), fc[mid] + 1)),
+        ("first_code[max_len] != 0", put(img, fc_at(max_len), 1)),
+        ("first_code[1] != 1024", put(img, fc_at(1), 0)),
+        ("lone end mark with max_len 2", empty2),
+        ("lone end mark with first_code[1] = 1", put(empty, fc_at(1), 1)),
+    ]
+    assert [name for name, _ in cases] == CASE_NAMES
+    return data, img, empty, cases
+
+
+def bad_codes(good, make):
+    """four corrupted copies of the ghf_code `good` (ctypes, any class with its fields): [(name, code)].
+    make(bytes) -> a new code object"""
+    min_len, max_len = good.min_len, good.max_len
+    assert min_len >= 2 and max_len >= min_len + 2
+    longest = next(s for s in range(256) if good.length[s] == max_len)
+    shortest = next(s for s in range(256) if good.length[s] == min_len)
+    # symbols whose Kraft terms add up to 2^-min_len: without their codes, one code may be a bit shorter and Kraft stays 1
+    drop, rest = [], 1 << (32 - min_len)
+    for s in sorted((s for s in range(256) if good.length[s] and s != shortest), key=lambda s: good.length[s]):
+        if rest and (1 << (32 - good.length[s])) <= rest:
+            drop.append(s)
+            rest -= 1 << (32 - good.length[s])
+    assert rest == 0
+    out = []
+
+    def case(name, change):
+        c = make(bytes(good))
+        change(c)
+        out.append((name, c))
+
+    def below(c):  # only this rule: the Kraft sum is still 1
+        c.length[shortest] = min_len - 1
+        for s in drop:
+            c.length[s] = 0
+
+    def shorter(c):
+        c.length[longest] = max_len - 1  # Kraft sum > 1
+
+    def wide(c):
+        c.first_code[min_len] = (1 << min_len) + 1
+
+    def far(c):
+        c.start_pos[min_len + 1] = 258
+
+    case("a length below min_len", below)
+    case("one length shortened: Kraft above 1", shorter)
+    case("first_code[len] = 2^len + 1", wide)
+    case("start_pos[len] = 258", far)
+    return out

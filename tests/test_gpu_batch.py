@@ -15,6 +15,7 @@ import pytest
 import datagen as dg
 import pkgload
 from cases import CASES, sweep_crs2_inputs
+from header_cases import bad_codes, header_cases
 from oracle import oracle as orc
 
 pytestmark = pytest.mark.gpu
@@ -354,6 +355,32 @@ def test_decode_failures_are_per_item(env):
                 assert int(out_bytes[i]) == d.size and np.array_equal(outs[i], d), i
             else:
                 assert int(out_bytes[i]) == 0, i
+            assert np.all(guards[i][0] == GUARD) and np.all(guards[i][1] == GUARD), i
+    finally:
+        b.free()
+
+
+def test_decode_refuses_codes_that_are_not_complete(env):
+    """the code rules of ghf_code_rules.h through k_decode_batch: the four corrupted tables of tests/header_cases.py
+    (tests/test_gpu_parity.py puts the same four through k_build_decode_tables) and two good ones in one launch"""
+    ghf, ctx, torch = env
+    data = header_cases()[0]
+    b = Batch(ghf, ctx, torch, [data] * 6).run()
+    try:
+        assert np.all(b.h_status == OK) and np.array_equal(b.image(0), header_cases()[1])
+        bad = bad_codes(b.code(0), ghf.Code.from_buffer_copy)
+        assert len(bad) == 4
+        codes = b.h_codes.copy()
+        for i, (name, c) in zip((0, 1, 3, 4), bad):
+            codes[i] = np.frombuffer(bytes(c), dtype=np.uint8)
+        status, out_bytes, outs, guards = decode_batch(b, codes=torch.from_numpy(codes).cuda())
+        print("status", status.tolist(), [name for name, _ in bad])
+        assert status.tolist() == [E_FORMAT, E_FORMAT, OK, E_FORMAT, E_FORMAT, OK]
+        for i in range(6):
+            if status[i] == OK:
+                assert int(out_bytes[i]) == data.size and np.array_equal(outs[i], data), i
+            else:
+                assert int(out_bytes[i]) == 0 and np.all(outs[i] == GUARD), i
             assert np.all(guards[i][0] == GUARD) and np.all(guards[i][1] == GUARD), i
     finally:
         b.free()

@@ -16,6 +16,7 @@ import pytest
 import datagen as dg
 import pkgload
 from cases import CASES, sweep_crs2_inputs
+from header_cases import header_cases
 from oracle import oracle as orc
 
 pytestmark = pytest.mark.gpu
@@ -301,6 +302,47 @@ def test_failures_are_per_item(env, golden):
     status, nbytes, outs, guards, _ = run(env, Images(torch, gimg[:3]), caps=[d.size for d in good[:3]], null_out=(1,))
     assert status.tolist() == [OK, E_INVAL, OK] and int(nbytes[1]) == 0
     assert np.array_equal(outs[0], good[0]) and np.array_equal(outs[2], good[2]) and np.all(outs[1] == GUARD)
+
+
+# ------------------------------------------------------------------------------ 6b. host and device state the same rules
+def test_header_rules_agree_with_the_host_parser(env):
+    """every corrupted header of tests/header_cases.py (one broken rule each), good items between them, in one launch:
+    GHF_E_FORMAT exactly where ghf_parse_header refuses, with outputs and sizes-only"""
+    ghf, ctx, torch = env
+    data, img, empty, cases = header_cases()
+    images, datas, labels = [img], [data], ["good"]
+    for name, bad in cases:
+        images += [bad, img]
+        datas += [data, data]
+        labels += [name, "good"]
+    images.append(empty)
+    datas.append(data[:0])
+    labels.append("empty")
+    want = []
+    for im_ in images:
+        try:
+            ghf.parse_header(im_)
+            want.append(OK)
+        except ghf.GhfError as e:
+            assert e.status == E_FORMAT
+            want.append(E_FORMAT)
+    assert want == [OK] + [E_FORMAT, OK] * len(cases) + [OK]  # tests/test_header_rules_cpu.py, case by case
+    im = Images(torch, images)
+    status, nbytes, outs, guards, _ = run(env, im, caps=[4096] * len(images))
+    for i, l in enumerate(labels):
+        print("decode %-40s status %d bytes %d (want %d)" % (l, status[i], nbytes[i], want[i]))
+    assert status.tolist() == want
+    for i, l in enumerate(labels):
+        assert np.all(guards[i][0] == GUARD) and np.all(guards[i][1] == GUARD), l
+        if want[i] != OK:
+            assert int(nbytes[i]) == 0 and np.all(outs[i] == GUARD), l  # refused before anything was written
+        elif l == "empty":
+            assert int(nbytes[i]) == 0 and np.all(outs[i] == GUARD), l
+        else:
+            assert int(nbytes[i]) == data.size and np.array_equal(outs[i], data), l
+    status, nbytes, _, _, _ = run(env, im)
+    assert status.tolist() == want
+    assert nbytes.tolist() == [d.size if w == OK else 0 for d, w in zip(datas, want)]
 
 
 # ------------------------------------------------------------------------------ 7. the empty image

@@ -700,6 +700,29 @@ def test_decode_refuses_tables_that_are_not_a_complete_code(env):
     ctx.index_free(idx)
 
 
+def test_code_rules_through_the_single_stream_table_builder(env):
+    """the four corrupted tables of tests/header_cases.py (tests/test_gpu_batch.py puts the same four through
+    k_decode_batch) through k_build_decode_tables: each ghf_decode latches GHF_E_FORMAT, the good code decodes afterwards"""
+    from header_cases import bad_codes, header_cases
+
+    ghf, ctx, torch = env
+    data = header_cases()[0]
+    d_in, d_out, nb, d_code, idx = run_compress(ghf, ctx, torch, data)
+    assert np.array_equal(d_out[:nb].cpu().numpy(), header_cases()[1])
+    bad = bad_codes(ctx.code_to_host(d_code), ghf.Code.from_buffer_copy)
+    assert len(bad) == 4
+    for name, c in bad:
+        back = torch.full((data.size + 64,), 0xA5, dtype=torch.uint8, device=d_out.device)
+        ctx.decode(d_out, nb, ctx.code_to_device(c), idx, d_out=back)
+        assert ghf.lib().ghf_sync(ctx.h) == 6, name
+        ghf.lib().ghf_clear_status(ctx.h)
+        assert torch.all(back == 0xA5).item(), name  # nothing decoded
+    back, _ = ctx.decode(d_out, nb, d_code, idx)
+    ctx.sync()
+    assert np.array_equal(back[: data.size].cpu().numpy(), data)
+    ctx.index_free(idx)
+
+
 @pytest.mark.parametrize("n", [(64 << 20) + 3, (160 << 20) + 1])
 def test_wide_codes_many_chunks_bit_exact(env, n):
     """codes longer than 16 bits (K5's 64-bit table entries, two half-wave passes) over thousands of chunks: counts
