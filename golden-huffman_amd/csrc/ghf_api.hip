@@ -68,6 +68,7 @@ const char* ghf_status_string(int s) {
     case GHF_E_CORRUPT: return "corrupt stream";
     case GHF_E_NOMEM: return "out of memory";
     case GHF_E_SINGLE: return "one distinct byte value (.crs: undefined in the reference)";
+    case GHF_E_NOCODE: return "a byte value without a code in the shared code";
     default: return "unknown status";
   }
 }
@@ -557,6 +558,89 @@ int ghf_decode_images_batch(ghf_ctx* c, const uint8_t* const* d_stream_ptrs, con
 int ghf_decode_images_batch_stats(ghf_ctx* c, uint64_t* d_stats) {
   if (!c || (reinterpret_cast<uintptr_t>(d_stats) & 7u)) return GHF_E_INVAL;
   c->images_stats = d_stats;
+  return GHF_OK;
+}
+
+// ---------------------------------------------------------------------------------------------- shared-code batches
+int ghf_histogram_batch(ghf_ctx* c, const uint8_t* const* d_in_ptrs, const uint64_t* d_in_bytes, size_t max_item_bytes,
+                        uint32_t count, unsigned flags, uint64_t* d_hist) {
+  if (!c) return GHF_E_INVAL;
+  if (max_item_bytes == 0 || max_item_bytes > GHF_BATCH_MAX_ITEM)
+    return fail(c, GHF_E_INVAL, "ghf_histogram_batch: max_item_bytes must be 1 .. GHF_BATCH_MAX_ITEM");
+  if (flags & ~GHF_HIST_COVER_ALL) return fail(c, GHF_E_INVAL, "ghf_histogram_batch: unknown flags");
+  if (!d_in_ptrs || !d_in_bytes || !d_hist) return GHF_E_INVAL;
+  if (count == 0) return GHF_OK;
+  GHF_HIP(c, hipSetDevice(c->device));
+  BatchHistParams p;
+  p.in_ptrs = d_in_ptrs;
+  p.in_bytes = d_in_bytes;
+  p.max_item_bytes = max_item_bytes;
+  p.count = count;
+  p.hist = d_hist;
+  launch_histogram_batch(p, flags, c->stream);
+  GHF_HIP(c, hipGetLastError());
+  return GHF_OK;
+}
+
+size_t ghf_compress_batch_shared_bound(size_t max_item_bytes) { return (4 * max_item_bytes + 4 + 15) & ~(size_t)15; }
+
+int ghf_compress_batch_shared(ghf_ctx* c, const uint8_t* const* d_in_ptrs, const uint64_t* d_in_bytes, size_t max_item_bytes,
+                              uint32_t count, const ghf_code* d_code, uint8_t* const* d_out_ptrs, const uint64_t* d_out_caps,
+                              uint64_t* d_out_bytes, const ghf_batch_index* index, int* d_item_status) {
+  if (!c) return GHF_E_INVAL;
+  if (max_item_bytes == 0 || max_item_bytes > GHF_BATCH_MAX_ITEM)
+    return fail(c, GHF_E_INVAL, "ghf_compress_batch_shared: max_item_bytes must be 1 .. GHF_BATCH_MAX_ITEM");
+  if (index && !batch_index_covers(index, count, max_item_bytes))
+    return fail(c, GHF_E_INVAL, "ghf_compress_batch_shared: index does not cover (count, max_item_bytes) (use ghf_batch_index_alloc)");
+  if (!d_code || !aligned16(d_code)) return fail(c, GHF_E_INVAL, "ghf_compress_batch_shared: d_code is null or not 16-byte aligned");
+  if (!d_in_ptrs || !d_in_bytes || !d_out_ptrs || !d_out_caps || !d_out_bytes || !d_item_status) return GHF_E_INVAL;
+  if (count == 0) return GHF_OK;
+  GHF_HIP(c, hipSetDevice(c->device));
+  BatchSharedCompressParams p;
+  p.in_ptrs = d_in_ptrs;
+  p.in_bytes = d_in_bytes;
+  p.max_item_bytes = max_item_bytes;
+  p.code = d_code;
+  p.out_ptrs = d_out_ptrs;
+  p.out_caps = d_out_caps;
+  p.out_bytes = d_out_bytes;
+  p.chunk_bit = index ? index->d_chunk_bit : nullptr;
+  p.seg_bit = index ? index->d_seg_bit : nullptr;
+  p.blocks_per_item = index ? index->blocks_per_item : 0;
+  p.segs_per_item = index ? index->segs_per_item : 0;
+  p.item_status = d_item_status;
+  launch_compress_batch_shared(p, count, c->stream);
+  GHF_HIP(c, hipGetLastError());
+  return GHF_OK;
+}
+
+int ghf_decode_batch_shared(ghf_ctx* c, const uint8_t* const* d_stream_ptrs, const uint64_t* d_stream_bytes, const ghf_code* d_code,
+                            const ghf_batch_index* index, const uint64_t* d_n_symbols, uint32_t count, uint8_t* const* d_out_ptrs,
+                            const uint64_t* d_out_caps, uint64_t* d_out_bytes, int* d_item_status) {
+  if (!c || !index) return GHF_E_INVAL;
+  if (!batch_index_covers(index, count, 1))
+    return fail(c, GHF_E_INVAL, "ghf_decode_batch_shared: index does not cover count items (use ghf_batch_index_alloc)");
+  if (!d_code || !aligned16(d_code)) return fail(c, GHF_E_INVAL, "ghf_decode_batch_shared: d_code is null or not 16-byte aligned");
+  if (!d_stream_ptrs || !d_stream_bytes || !d_n_symbols || !d_out_ptrs || !d_out_caps || !d_out_bytes || !d_item_status)
+    return GHF_E_INVAL;
+  if (count == 0) return GHF_OK;
+  GHF_HIP(c, hipSetDevice(c->device));
+  BatchSharedDecodeParams p;
+  p.stream_ptrs = d_stream_ptrs;
+  p.stream_bytes = d_stream_bytes;
+  p.code = d_code;
+  p.chunk_bit = index->d_chunk_bit;
+  p.seg_bit = index->d_seg_bit;
+  p.blocks_per_item = index->blocks_per_item;
+  p.segs_per_item = index->segs_per_item;
+  p.max_item_bytes = index->max_item_bytes;
+  p.n_symbols = d_n_symbols;
+  p.out_ptrs = d_out_ptrs;
+  p.out_caps = d_out_caps;
+  p.out_bytes = d_out_bytes;
+  p.item_status = d_item_status;
+  launch_decode_batch_shared(p, count, c->stream);
+  GHF_HIP(c, hipGetLastError());
   return GHF_OK;
 }
 

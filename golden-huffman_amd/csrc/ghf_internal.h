@@ -215,6 +215,42 @@ struct BatchImagesParams {
   uint64_t* stats;            // may be null: [0] += rounds, [1] += passes of every item that reached its body
 };
 
+// ---- batches under one shared code (ghf_batch_shared.hip): an item's output is its body alone; every array is device memory
+struct BatchHistParams {
+  const uint8_t* const* in_ptrs;
+  const uint64_t* in_bytes;
+  uint64_t max_item_bytes;
+  uint32_t count;
+  uint64_t* hist;  // [GHF_NSYM]; slots 0 .. 255 are zero when the kernel starts
+};
+struct BatchSharedCompressParams {
+  const uint8_t* const* in_ptrs;
+  const uint64_t* in_bytes;
+  uint64_t max_item_bytes;
+  const ghf_code* code;   // one for the batch, never null
+  uint8_t* const* out_ptrs;
+  const uint64_t* out_caps;
+  uint64_t* out_bytes;
+  uint64_t* chunk_bit;    // side-car slices (may both be null), bits counted from byte 0 of the item's body
+  uint32_t* seg_bit;
+  uint64_t blocks_per_item, segs_per_item;
+  int* item_status;
+};
+struct BatchSharedDecodeParams {
+  const uint8_t* const* stream_ptrs;  // the bodies
+  const uint64_t* stream_bytes;
+  const ghf_code* code;
+  const uint64_t* chunk_bit;
+  const uint32_t* seg_bit;
+  uint64_t blocks_per_item, segs_per_item;
+  uint64_t max_item_bytes;
+  const uint64_t* n_symbols;
+  uint8_t* const* out_ptrs;
+  const uint64_t* out_caps;
+  uint64_t* out_bytes;
+  int* item_status;
+};
+
 // K6: side-car reconstruction for foreign streams
 enum SyncKind : uint32_t {  // what SyncParams::no_eof carries
   kSyncCrs2 = 0,   // a whole .crs2: ends with the end mark
@@ -290,6 +326,10 @@ void launch_decode_head(const DecHeadParams& p, hipStream_t s);
 void launch_compress_batch(const BatchCompressParams& p, uint32_t count, hipStream_t s);  // one launch, grid = count
 void launch_decode_batch(const BatchDecodeParams& p, uint32_t count, hipStream_t s);
 void launch_decode_images_batch(const BatchImagesParams& p, uint32_t count, hipStream_t s);  // one launch; p.out_ptrs null: sizes only
+// ghf_batch_shared.hip
+void launch_histogram_batch(const BatchHistParams& p, uint32_t flags, hipStream_t s);  // zeroes p.hist, counts, finishes
+void launch_compress_batch_shared(const BatchSharedCompressParams& p, uint32_t count, hipStream_t s);  // one launch, grid = count
+void launch_decode_batch_shared(const BatchSharedDecodeParams& p, uint32_t count, hipStream_t s);
 
 }  // namespace ghf
 #endif

@@ -11,6 +11,7 @@ EMIT_HEADER = 4
 INDEX_NO_END_MARK = 1
 CODE_LIMIT = 1
 BATCH_MAX_ITEM = 1 << 20  # GHF_BATCH_MAX_ITEM: the largest item of ghf_compress_batch / ghf_decode_batch
+HIST_COVER_ALL = 1  # GHF_HIST_COVER_ALL (ghf_histogram_batch): every count of 0 becomes 1
 EMPTY_OK = 2  # opt-in: n == 0 -> header of the one-symbol code + 0x7F (builder's definition, parity unpinned)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -18,7 +19,7 @@ LIB_PATH = os.path.join(_HERE, "lib", "libghf.so")
 
 STATUS = {0: "ok", 1: "invalid argument", 2: "HIP error / no device", 3: "empty input", 4: "code longer than 32 bits",
           5: "output capacity too small", 6: "not a .crs2 / .crs header", 7: "corrupt stream", 8: "out of memory",
-          9: "one distinct byte value (.crs)"}
+          9: "one distinct byte value (.crs)", 10: "a byte value without a code in the shared code"}
 
 
 class GhfError(RuntimeError):
@@ -130,6 +131,7 @@ EXPORTS = [
     "ghf_seek_bytes", "ghf_seek_parse", "ghf_seek_pack", "ghf_seek_expand", "ghf_decode_range",
     "ghf_compress_batch_bound", "ghf_batch_index_alloc", "ghf_batch_index_free", "ghf_batch_index_item",
     "ghf_compress_batch", "ghf_decode_batch", "ghf_decode_images_batch", "ghf_decode_images_batch_stats",
+    "ghf_histogram_batch", "ghf_compress_batch_shared_bound", "ghf_compress_batch_shared", "ghf_decode_batch_shared",
 ]
 COMM_ID_BYTES = 128
 
@@ -232,6 +234,11 @@ def lib():
     L.ghf_decode_batch.argtypes = [vp, vp, vp, vp, C.POINTER(BatchIndex), vp, C.c_uint32, vp, vp, vp, vp]
     L.ghf_decode_images_batch.argtypes = [vp, vp, vp, C.c_uint32, vp, vp, vp, vp, vp]
     L.ghf_decode_images_batch_stats.argtypes = [vp, vp]
+    L.ghf_histogram_batch.argtypes = [vp, vp, vp, sz, C.c_uint32, C.c_uint, vp]
+    L.ghf_compress_batch_shared_bound.argtypes = [sz]
+    L.ghf_compress_batch_shared_bound.restype = sz
+    L.ghf_compress_batch_shared.argtypes = [vp, vp, vp, sz, C.c_uint32, vp, vp, vp, vp, C.POINTER(BatchIndex), vp]
+    L.ghf_decode_batch_shared.argtypes = [vp, vp, vp, vp, C.POINTER(BatchIndex), vp, C.c_uint32, vp, vp, vp, vp]
     _lib = L
     return L
 
@@ -251,6 +258,11 @@ def compress_bound(n):
 def compress_batch_bound(max_item_bytes):
     """capacity that suffices for every item of a batch whose items have at most max_item_bytes"""
     return int(lib().ghf_compress_batch_bound(max_item_bytes))
+
+
+def compress_batch_shared_bound(max_item_bytes):
+    """capacity that suffices for the BODY of every item of a shared-code batch, under any code of <= 32 bits"""
+    return int(lib().ghf_compress_batch_shared_bound(max_item_bytes))
 
 
 def batch_index_item(bidx, i, n_i):
@@ -630,6 +642,80 @@ class Context:
                                            None if d_codes is None else d_codes.data_ptr(), status.data_ptr()),
             "ghf_decode_images_batch")
         return res
+
+    # ---- shared-code batches: one code for the whole batch, an item's output is its body alone ----
+    def _item_arrays(self, items, sizes):
+        """(ptrs, sizes) of a list of CUDA uint8 tensors, or of ONE packed tensor cut by `sizes`"""
+        if sizes is None:
+            return [x.data_ptr() if x.numel() else 0 for x in items], [int(x.numel()) for x in items]
+        sizes = [int(v) for v in sizes]
+        base, ptrs, at = items.data_ptr(), [], 0
+        for v in sizes:
+            ptrs.append(base + at)
+            at += v
+        return ptrs, sizes
+
+    def histogram_batch(self, items, sizes=None, max_item_bytes=None, flags=0, out=None):
+        """the byte counts of all items in one int64[257] CUDA tensor (slot 256 = 1), ready for build_code.  items / sizes
+        as in compress_batch; flags: HIST_COVER_ALL.  No host synchronisation."""
+        ptrs, sizes = self._item_arrays(items, sizes)
+        if max_item_bytes is None:
+            max_item_bytes = max(max(sizes, default=1), 1)
+        hist = self.torch.empty(NSYM, dtype=self.torch.int64, device=self.device) if out is None else out
+        in_ptrs, in_bytes = self._i64(ptrs), self._i64(sizes)
+        self._chk(self.L.ghf_histogram_batch(self.h, in_ptrs.data_ptr(), in_bytes.data_ptr(), max_item_bytes, len(sizes), flags,
+                                             hist.data_ptr()), "ghf_histogram_batch")
+        return hist
+
+    def compress_batch_shared(self, items, d_code, sizes=None, max_item_bytes=None, d_out=None, out_stride=None, index=None):
+        """compress_batch under the one code `d_code` (e.g. build_code(histogram_batch(items))): item i's BODY goes to
+        d_out[i * out_stride ..).  -> dict(out, out_stride, out_bytes int64[count], status int32[count], code, in_ptrs,
+        in_bytes, out_ptrs, out_caps, count, max_item_bytes)"""
+        t = self.torch
+        ptrs, sizes = self._item_arrays(items, sizes)
+        count = len(sizes)
+        if max_item_bytes is None:
+            max_item_bytes = max(max(sizes, default=1), 1)
+        if out_stride is None:
+            out_stride = compress_batch_shared_bound(max_item_bytes)
+        if d_out is None:
+            d_out = t.empty(max(count * out_stride, 16), dtype=t.uint8, device=self.device)
+        in_ptrs, in_bytes = self._i64(ptrs), self._i64(sizes)
+        out_ptrs = d_out.data_ptr() + t.arange(count, dtype=t.int64, device=self.device) * out_stride
+        out_caps = t.full((max(count, 1),), out_stride, dtype=t.int64, device=self.device)
+        out_bytes = t.zeros(max(count, 1), dtype=t.int64, device=self.device)
+        status = t.full((max(count, 1),), -1, dtype=t.int32, device=self.device)
+        self._chk(
+            self.L.ghf_compress_batch_shared(self.h, in_ptrs.data_ptr(), in_bytes.data_ptr(), max_item_bytes, count,
+                                             d_code.data_ptr(), out_ptrs.data_ptr(), out_caps.data_ptr(), out_bytes.data_ptr(),
+                                             None if index is None else C.byref(index), status.data_ptr()),
+            "ghf_compress_batch_shared")
+        return {"out": d_out, "out_stride": out_stride, "out_bytes": out_bytes[:count], "status": status[:count], "code": d_code,
+                "in_ptrs": in_ptrs, "in_bytes": in_bytes, "out_ptrs": out_ptrs, "out_caps": out_caps, "count": count,
+                "max_item_bytes": max_item_bytes, "keep": items}
+
+    def decode_batch_shared(self, stream_ptrs, stream_bytes, d_code, index, n_symbols, d_out=None, out_stride=None, out_ptrs=None,
+                            out_caps=None):
+        """decode_batch with one code for all items: stream_ptrs / stream_bytes are the bodies (e.g. out_ptrs and
+        out_bytes of compress_batch_shared).  -> dict(out, out_stride, out_bytes int64[count], status int32[count])"""
+        t = self.torch
+        count = int(n_symbols.numel())
+        if out_ptrs is None:
+            if out_stride is None:
+                out_stride = (int(index.max_item_bytes) + 15) & ~15
+            if d_out is None:
+                d_out = t.empty(max(count * out_stride, 16), dtype=t.uint8, device=self.device)
+            out_ptrs = d_out.data_ptr() + t.arange(count, dtype=t.int64, device=self.device) * out_stride
+            out_caps = t.full((max(count, 1),), out_stride, dtype=t.int64, device=self.device)
+        out_bytes = t.zeros(max(count, 1), dtype=t.int64, device=self.device)
+        status = t.full((max(count, 1),), -1, dtype=t.int32, device=self.device)
+        self._chk(
+            self.L.ghf_decode_batch_shared(self.h, stream_ptrs.data_ptr(), stream_bytes.data_ptr(), d_code.data_ptr(),
+                                           C.byref(index), n_symbols.data_ptr(), count, out_ptrs.data_ptr(), out_caps.data_ptr(),
+                                           out_bytes.data_ptr(), status.data_ptr()),
+            "ghf_decode_batch_shared")
+        return {"out": d_out, "out_stride": out_stride, "out_bytes": out_bytes[:count], "status": status[:count],
+                "out_ptrs": out_ptrs, "out_caps": out_caps}
 
     def decode_images_batch_stats(self, d_stats):
         """d_stats: an int64 CUDA tensor [2] that later decode_images_batch calls add {rounds, passes} to; None: off"""

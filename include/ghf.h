@@ -33,8 +33,9 @@ enum ghf_status_code {
   GHF_E_FORMAT = 6,  /* not a .crs2 header */
   GHF_E_CORRUPT = 7, /* stream does not decode to the expected symbol count / end mark */
   GHF_E_NOMEM = 8,
-  GHF_E_SINGLE = 9 /* .crs only: one distinct byte value -- the lone leaf gets the empty code and the reference's
-                      decoder dereferences a NULL child (include/huff_tree.cc:255-271); undefined there, refused here */
+  GHF_E_SINGLE = 9, /* .crs only: one distinct byte value -- the lone leaf gets the empty code and the reference's
+                       decoder dereferences a NULL child (include/huff_tree.cc:255-271); undefined there, refused here */
+  GHF_E_NOCODE = 10 /* shared-code batches: an item holds a byte value to which the shared code gives no code */
 };
 
 /* The encoder's tables -- mirrors the private members of CanonicalHuffEncoder,
@@ -370,6 +371,68 @@ int ghf_decode_images_batch(ghf_ctx* ctx, const uint8_t* const* d_stream_ptrs, c
  * d_stats[0] += rounds and d_stats[1] += passes.  The caller zeroes the two words; tools/batch_images_bench.py reads
  * them to hold the observed passes per round against the bound of 256. */
 int ghf_decode_images_batch_stats(ghf_ctx* ctx, uint64_t* d_stats);
+
+/* ---- shared-code batches: one code for many small items ---------------------------------------------
+ * No reference counterpart (the reference compresses one file per process, include/compressor.h:62-73).  The batch calls
+ * above give every item a code of its own: 1040 + 8 * max_len bytes of header per image and 3604 bytes of tables per
+ * item for the decoder -- as much as a 4 KiB item itself.  These calls put ONE code under the whole batch.  The header is
+ * stored once; item i's output is its BODY alone: the codes of its bytes MSB-first from bit 0, the end mark, 1-bits up
+ * to the byte -- exactly the bytes ghf_encode_emit writes for (d_in, n, d_code, a device start bit of 0, GHF_EMIT_LAST).
+ * The .crs2 format does not change: a body is byte-aligned behind its header, so header(code) || body(i) (the header
+ * from ghf_write_header) is a complete standalone .crs2 image that the reference's decoders, ghf_decode and
+ * ghf_decode_images_batch read.
+ *
+ * Conventions are those of the batch calls above: every array is DEVICE memory; asynchronous on the context's stream,
+ * never synchronises; failures are per item (GHF_OK is written as well, d_out_bytes[i] = 0 on failure) and never latch
+ * the context's status word; the context's caches are left alone; count == 0 queues nothing.  Call-level errors (returned
+ * at once, nothing queued): null arrays, max_item_bytes == 0 or > GHF_BATCH_MAX_ITEM, an index whose geometry does not
+ * cover (count, max_item_bytes), unknown flags, a null or not 16-byte aligned d_code: GHF_E_INVAL.  Input and decode-output
+ * pointers need no alignment; compress-output and decode-stream pointers are 16-byte aligned.
+ *
+ * The code: ghf_build_code or ghf_build_code_ex(GHF_CODE_LIMIT) on the histogram of ghf_histogram_batch, or any other
+ * ghf_code in device memory (one trained on a sample; one from ghf_parse_header, copied up).  Both kernels check it
+ * before they trust it: a d_code that is not a complete prefix code of lengths <= 32 with a code for the end mark (the
+ * rules ghf_decode_batch applies to an item's tables) gives GHF_E_FORMAT on EVERY item, and nothing is written.
+ * Not supported here: bodies without a side-car (prepend the header and use ghf_decode_images_batch, or keep a seek
+ * table per item: ghf_batch_index_item -> ghf_seek_pack), GHF_EMPTY_OK items, and the .crs format. */
+#define GHF_HIST_COVER_ALL 1u /* ghf_histogram_batch: every count of 0 becomes 1 */
+
+/* No reference counterpart; see above.  d_hist[0..255] <- the byte counts summed over all items, d_hist[256] <- 1: what
+ * ghf_histogram gives for the items' concatenation.  d_hist (device u64[257]) is overwritten, the caller zeroes nothing.
+ * Items of 0 bytes, with a null pointer or of more than max_item_bytes contribute nothing (ghf_compress_batch_shared is
+ * what reports them).  GHF_HIST_COVER_ALL: every count of 0 becomes 1, so the code built from the result has a code
+ * for every byte value and later items compress whatever they hold. */
+int ghf_histogram_batch(ghf_ctx* ctx, const uint8_t* const* d_in_ptrs, const uint64_t* d_in_bytes, size_t max_item_bytes,
+                        uint32_t count, unsigned flags, uint64_t* d_hist /* [257] */);
+
+/* No reference counterpart.  Host only: (4 * max_item_bytes + 4 + 15) & ~15, a capacity that suffices for the body of
+ * every item under any code of <= 32 bits. */
+size_t ghf_compress_batch_shared_bound(size_t max_item_bytes);
+
+/* No reference counterpart; see above.  Item i = d_in_ptrs[i][0 .. d_in_bytes[i]) -> its body at d_out_ptrs[i],
+ * d_out_bytes[i] <- its size.  Nothing at or beyond d_out_caps[i] is written, and a refused item writes nothing at all:
+ * the size is known from a pricing pass before the first store.  index (optional): item i's slice receives the side-car
+ * of that body; chunk_bit counts from byte 0 of the body, a segment end is relative to its block.
+ * d_item_status[i] <-
+ *   GHF_E_EMPTY   the item has 0 bytes            GHF_E_INVAL  more than max_item_bytes; null / misaligned item pointer
+ *   GHF_E_CAP     the body is larger than d_out_caps[i]
+ *   GHF_E_NOCODE  the item holds a byte value to which d_code gives no code
+ *   GHF_E_FORMAT  (every item) d_code is not a complete prefix code */
+int ghf_compress_batch_shared(ghf_ctx* ctx, const uint8_t* const* d_in_ptrs, const uint64_t* d_in_bytes,
+                              size_t max_item_bytes, uint32_t count, const ghf_code* d_code, uint8_t* const* d_out_ptrs,
+                              const uint64_t* d_out_caps, uint64_t* d_out_bytes,
+                              const ghf_batch_index* index /* optional */, int* d_item_status /* [count] */);
+
+/* No reference counterpart; see above.  ghf_decode_batch with one d_code for all items and bodies that start at bit 0:
+ * item i = the body at d_stream_ptrs[i] (d_stream_bytes[i] of it), item i's slice of `index` and d_n_symbols[i] ->
+ * d_out_ptrs[i][0 .. d_n_symbols[i]).  max_item_bytes is index->max_item_bytes.  Every segment must land on its recorded
+ * end and the end mark must follow the last symbol (GHF_E_CORRUPT); GHF_E_CAP, GHF_E_EMPTY, GHF_E_INVAL as in
+ * ghf_decode_batch; GHF_E_FORMAT (every item) for a d_code that is not a complete prefix code.  No byte outside
+ * d_stream_ptrs[i][0 .. d_stream_bytes[i]) is read, whatever code and side-car hold. */
+int ghf_decode_batch_shared(ghf_ctx* ctx, const uint8_t* const* d_stream_ptrs, const uint64_t* d_stream_bytes,
+                            const ghf_code* d_code, const ghf_batch_index* index, const uint64_t* d_n_symbols,
+                            uint32_t count, uint8_t* const* d_out_ptrs, const uint64_t* d_out_caps,
+                            uint64_t* d_out_bytes, int* d_item_status /* [count] */);
 
 /* Multi-GPU decode of a stream that has no side-car ("per-rank self-sync + one all-gather of symbol
  * counts"; the reference's decoders, canonical_huff_encoder.cc:377-568, are single-stream).  The caller cuts the body
