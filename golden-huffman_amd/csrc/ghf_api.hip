@@ -644,6 +644,29 @@ int ghf_decode_batch_shared(ghf_ctx* c, const uint8_t* const* d_stream_ptrs, con
   return GHF_OK;
 }
 
+int ghf_decode_bodies_batch_shared(ghf_ctx* c, const uint8_t* const* d_stream_ptrs, const uint64_t* d_stream_bytes,
+                                   const ghf_code* d_code, uint32_t count, uint8_t* const* d_out_ptrs, const uint64_t* d_out_caps,
+                                   uint64_t* d_out_bytes, int* d_item_status) {
+  if (!c || !d_stream_ptrs || !d_stream_bytes || !d_out_bytes || !d_item_status) return GHF_E_INVAL;
+  if (d_out_ptrs && !d_out_caps) return fail(c, GHF_E_INVAL, "ghf_decode_bodies_batch_shared: d_out_ptrs without d_out_caps");
+  if (!d_code || !aligned16(d_code)) return fail(c, GHF_E_INVAL, "ghf_decode_bodies_batch_shared: d_code is null or not 16-byte aligned");
+  if (count == 0) return GHF_OK;
+  GHF_HIP(c, hipSetDevice(c->device));
+  BatchSharedBodiesParams p;
+  p.stream_ptrs = d_stream_ptrs;
+  p.stream_bytes = d_stream_bytes;
+  p.max_stream_bytes = ghf_compress_batch_shared_bound(GHF_BATCH_MAX_ITEM);
+  p.code = d_code;
+  p.out_ptrs = d_out_ptrs;
+  p.out_caps = d_out_caps;
+  p.out_bytes = d_out_bytes;
+  p.item_status = d_item_status;
+  p.stats = c->images_stats;
+  launch_decode_bodies_batch_shared(p, count, c->stream);
+  GHF_HIP(c, hipGetLastError());
+  return GHF_OK;
+}
+
 // ---------------------------------------------------------------------------------------------- decode
 static inline uint32_t be32(const uint8_t* p) {
   return ((uint32_t)p[0] << 24) | ((uint32_t)p[1] << 16) | ((uint32_t)p[2] << 8) | (uint32_t)p[3];

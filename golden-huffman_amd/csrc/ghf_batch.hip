@@ -341,12 +341,7 @@ __global__ __launch_bounds__(kBatchThreads) void k_decode_batch(BatchDecodeParam
 // starts at an exactly known bit, so the fixed point is the true segmentation).  A scan of the lanes' symbol counts gives
 // the output offsets; under kWrite the lanes decode once more into a 16 KiB stage that leaves slice by slice.
 // ----------------------------------------------------------------------------------------------------------------------
-constexpr uint32_t kImgSubBits = 512;
-constexpr uint32_t kImgRoundBits = kBatchThreads * kImgSubBits;
-constexpr uint32_t kImgStageBytes = 16 * 1024;
-constexpr uint32_t kImgNone = 0xFFFFFFFFu;
-constexpr uint32_t kImgEndMark = 1, kImgCutOff = 2;  // why a lane stopped inside its subsequence
-
+// (kImgSubBits, kImgRoundBits, kImgStageBytes, kImgNone, kImgEndMark, kImgCutOff: ghf_batch_core.h)
 struct BatchImagesLds {
   CodeTab t;
   // header phase: the raw symbol[] words, length / codeword by symbol, seen[], the raw start_pos / first_code words

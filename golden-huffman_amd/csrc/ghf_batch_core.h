@@ -1,6 +1,7 @@
 // golden-huffman_amd/csrc/ghf_batch_core.h -- the device helpers of the one-workgroup-per-item kernels, shared by
 // ghf_batch.hip (one code per item) and ghf_batch_shared.hip (one code for the batch): the round geometry, the item
-// loads for any alignment, the LDS stage of the packer, the bounded stream reads and the bit cursor of the decoders.
+// loads for any alignment, the LDS stage of the packer, the bounded stream reads and the bit cursor of the decoders, and
+// the round loop of the decoders that find the code boundaries themselves (batch_decode_rounds).
 #ifndef GHF_BATCH_CORE_H_
 #define GHF_BATCH_CORE_H_
 #include "ghf_code_rules.h"
@@ -117,6 +118,145 @@ __device__ __forceinline__ void batch_store_stage(uint8_t* dst, const uint32_t* 
   }
   const uint32_t tail0 = head + 16u * nvec;
   if (tail0 + (uint32_t)tid < rbytes) dst[tail0 + tid] = sb[tail0 + tid];
+}
+
+// ----------------------------------------------------------------------------------------------------------------------
+// the round loop of the decoders that get nothing but the bytes (k_decode_images_batch, DESIGN.md section 10;
+// k_decode_bodies_batch_shared, section 13): the workgroup finds the code boundaries itself.  Rounds of 256 subsequences
+// of 512 bits, one per lane, settled by passes in which lane k restarts from where lane k - 1 landed until nothing moves
+// at or in front of the first end mark (lane 0 starts at an exactly known bit, so the fixed point is the true
+// segmentation).  A scan of the lanes' symbol counts gives the output offsets; under kWrite the lanes decode once more
+// into a 16 KiB stage that leaves slice by slice.
+// ----------------------------------------------------------------------------------------------------------------------
+constexpr uint32_t kImgSubBits = 512;
+constexpr uint32_t kImgRoundBits = kBatchThreads * kImgSubBits;
+constexpr uint32_t kImgStageBytes = 16 * 1024;
+constexpr uint32_t kImgNone = 0xFFFFFFFFu;
+constexpr uint32_t kImgEndMark = 1, kImgCutOff = 2;  // why a lane stopped inside its subsequence
+
+struct BatchRoundsLds {  // next to a CodeTab and a stage of kImgStageBytes / 4 + 4 words
+  uint16_t over[2][kBatchThreads];  // bits each lane's last code runs past its subsequence; written in pass p, read in p + 1
+  uint32_t mins[3][2];              // [pass % 3]{first lane whose start moved, first lane that met the end (mark) of the stream}
+  uint32_t wave_tot[kBatchWaves];
+  uint32_t stop_kind;
+};
+// tid 0, with a barrier between this and batch_decode_rounds
+__device__ __forceinline__ void batch_rounds_init(BatchRoundsLds& R) {
+  for (int b = 0; b < 3; ++b) R.mins[b][0] = R.mins[b][1] = kImgNone;
+}
+
+// Every lane of the workgroup calls it with the same arguments; T holds the filled tables (a barrier lies behind
+// tab_fill_lut).  The first code starts at stream bit `first_bit`; stream_bytes * 8 fits 32 bits.  -> GHF_OK and *total =
+// the symbols in front of the first end mark, GHF_E_CORRUPT (the stream ends before a whole end mark) or GHF_E_CAP (more
+// than `cap` symbols; seen before any store of the round that would cross it).  No byte outside stream[0 .. stream_bytes)
+// is read; under kWrite only out[0 .. min(total, cap)) is written.  rounds / passes: += what the item took.
+template <bool kWrite>
+__device__ __forceinline__ int batch_decode_rounds(const CodeTab& T, uint32_t* stage, BatchRoundsLds& R,
+                                                   const uint8_t* __restrict__ stream, uint64_t stream_bytes, uint32_t first_bit,
+                                                   uint64_t cap, uint8_t* __restrict__ out, int lb, int long_from, int max_len,
+                                                   uint32_t* total_out, uint32_t& rounds, uint32_t& passes) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const uint32_t end_bit = (uint32_t)stream_bytes * 8u;
+  uint32_t base = first_bit;  // first bit of the round's subsequence 0
+  uint32_t carry = 0;         // bits the previous round's last code runs into this one: lane 0's start, exact
+  uint32_t total = 0;         // symbols of the rounds before this one
+  uint32_t pb = 0, po = 0;    // pass % 3, pass % 2
+#pragma unroll 1
+  for (;;) {
+    ++rounds;
+    const uint32_t sub0 = base + (uint32_t)tid * kImgSubBits, sub_end = sub0 + kImgSubBits;
+    uint32_t start = kImgNone, cnt = 0, stop = 0, over = 0;
+    uint32_t round_passes = 0, first_stop;
+#pragma unroll 1
+    for (;;) {
+      const uint32_t in = tid == 0 ? carry : round_passes == 0 ? 0u : (uint32_t)R.over[po][tid - 1];
+      const bool moved = in != start;
+      if (moved) {  // code lengths only, from `in` until the lane leaves its subsequence, the end mark or the stream's end
+        start = in;
+        cnt = 0;
+        stop = 0;
+        uint32_t pos = sub0 + in;
+        BatchCursor cur;
+        cur.seek(stream, stream_bytes, pos);
+#pragma unroll 1
+        while (pos < sub_end) {
+          const uint32_t ent = batch_decode_one(T, cur.window(), lb, long_from, max_len);
+          const uint32_t len = ent >> 9;
+          if (len == 0 || pos >= end_bit || len > end_bit - pos) {  // the code (an end mark too) must lie wholly inside the stream
+            stop = kImgCutOff;
+            break;
+          }
+          if ((ent & 0x1FFu) == 256u) {
+            stop = kImgEndMark;
+            break;
+          }
+          ++cnt;
+          pos += len;
+          cur.skip(stream, stream_bytes, len);
+        }
+        over = stop ? 0u : pos - sub_end;
+      }
+      R.over[po ^ 1u][tid] = (uint16_t)over;
+      const unsigned long long m_moved = __ballot(moved), m_stop = __ballot(stop != 0);
+      if (lane == 0) {
+        if (m_moved) atomicMin(&R.mins[pb][0], (uint32_t)(wave * 64 + __builtin_ctzll(m_moved)));
+        if (m_stop) atomicMin(&R.mins[pb][1], (uint32_t)(wave * 64 + __builtin_ctzll(m_stop)));
+      }
+      const uint32_t nb = pb == 2 ? 0u : pb + 1;
+      if (tid == 0) R.mins[nb][0] = R.mins[nb][1] = kImgNone;  // last read two barriers ago, next written behind this one
+      __syncthreads();
+      const uint32_t first_moved = R.mins[pb][0];
+      first_stop = R.mins[pb][1];
+      pb = nb;
+      po ^= 1u;
+      ++round_passes;
+      // settled: nothing moved at or in front of the first stop -- and lanes 0 .. p are exact after pass p in any case
+      if (first_moved == kImgNone || first_moved > first_stop || first_stop < round_passes) break;
+    }
+    passes += round_passes;
+    const uint32_t mine = (uint32_t)tid <= first_stop ? cnt : 0u;  // (first_stop == kImgNone: every lane counts)
+    const uint32_t incl = wave_incl_scan_u32(mine);
+    if (lane == 63) R.wave_tot[wave] = incl;
+    if ((uint32_t)tid == first_stop) R.stop_kind = stop;
+    __syncthreads();
+    uint32_t before = 0, round_total = 0;
+#pragma unroll
+    for (int w = 0; w < kBatchWaves; ++w) {
+      const uint32_t t = R.wave_tot[w];
+      before += w < wave ? t : 0u;
+      round_total += t;
+    }
+    const uint32_t stop_kind = first_stop == kImgNone ? 0u : R.stop_kind;
+    if (stop_kind == kImgCutOff) return GHF_E_CORRUPT;  // the stream ends before a whole end mark
+    if ((uint64_t)total + round_total > cap) return GHF_E_CAP;  // before any store of the round
+    if (kWrite) {
+      const uint32_t rel = before + incl - mine;  // of the lane's first symbol in the round's output
+      uint32_t i = 0;
+      BatchCursor cur;
+      if (mine) cur.seek(stream, stream_bytes, sub0 + start);
+      uint8_t* const sb = reinterpret_cast<uint8_t*>(stage);
+#pragma unroll 1
+      for (uint32_t lo = 0; lo < round_total; lo += kImgStageBytes) {  // (min_len 1: a round holds up to 128 Ki symbols)
+        while (i < mine && rel + i < lo + kImgStageBytes) {
+          const uint32_t ent = batch_decode_one(T, cur.window(), lb, long_from, max_len);
+          sb[rel + i - lo] = (uint8_t)ent;
+          cur.skip(stream, stream_bytes, ent >> 9);
+          ++i;
+        }
+        __syncthreads();
+        const uint32_t rbytes = round_total - lo < kImgStageBytes ? round_total - lo : kImgStageBytes;
+        batch_store_stage(out + total + lo, stage, rbytes, tid);
+        __syncthreads();
+      }
+    }
+    total += round_total;
+    if (stop_kind == kImgEndMark) {
+      *total_out = total;
+      return GHF_OK;
+    }
+    carry = R.over[po][kBatchThreads - 1];
+    base += kImgRoundBits;
+  }
 }
 
 }  // namespace ghf

@@ -1,5 +1,6 @@
 // golden-huffman_amd/csrc/ghf_batch_shared.hip -- many small items under ONE code (ghf_histogram_batch,
-// ghf_compress_batch_shared, ghf_decode_batch_shared, include/ghf.h).
+// ghf_compress_batch_shared, ghf_decode_batch_shared, ghf_decode_bodies_batch_shared, include/ghf.h; DESIGN.md
+// sections 12 and 13).
 //
 // ghf_batch.hip gives every item a code of its own: a header of 1040 + 8 max_len bytes per image, 3604 bytes of tables per
 // item for the decoder and a one-wavefront code build inside every workgroup.  Here the code comes from the caller (built
@@ -362,6 +363,74 @@ __global__ __launch_bounds__(kBatchThreads) void k_decode_batch_shared(BatchShar
   finish(ok ? GHF_OK : GHF_E_CORRUPT, ok ? n : 0);
 }
 
+// ----------------------------------------------------------------------------------------------------------------------
+// decode of bodies that come with nothing else (ghf_decode_bodies_batch_shared): the front of
+// k_decode_batch_shared (the code is vetted before the item is looked at), then the round loop of k_decode_images_batch
+// from body bit 0 (batch_decode_rounds, ghf_batch_core.h): the workgroup finds the code boundaries and the size itself.
+// ----------------------------------------------------------------------------------------------------------------------
+struct BatchSharedBodiesLds {
+  CodeTab t;  // the shared code's decode tables (ghf_code_rules.h)
+  alignas(16) uint32_t stage[kImgStageBytes / 4 + 4];
+  BatchRoundsLds r;
+  unsigned long long kraft;
+  int bad;
+};
+static_assert(sizeof(BatchSharedBodiesLds) <= 40 * 1024, "four workgroups per CU");
+
+template <bool kWrite>
+__global__ __launch_bounds__(kBatchThreads) void k_decode_bodies_batch_shared(BatchSharedBodiesParams P) {
+  __shared__ BatchSharedBodiesLds S;
+  const int tid = threadIdx.x;
+  const uint32_t item = blockIdx.x;
+  const ghf_code* __restrict__ const code = P.code;
+  uint32_t rounds = 0, passes = 0;
+  auto finish = [&](int status, uint64_t n) {  // every lane of the workgroup takes the same exit
+    if (tid == 0) {
+      P.item_status[item] = status;
+      P.out_bytes[item] = status == GHF_OK ? n : 0;
+      if (P.stats && rounds) {
+        atomicAdd(reinterpret_cast<unsigned long long*>(P.stats), (unsigned long long)rounds);
+        atomicAdd(reinterpret_cast<unsigned long long*>(P.stats) + 1, (unsigned long long)passes);
+      }
+    }
+  };
+  // a complete prefix code (ghf_code_rules.h, section 2), and its tables
+  const int max_len = code->max_len, min_len = code->min_len;
+  if (!len_bounds_ok(min_len, max_len)) return finish(GHF_E_FORMAT, 0);
+  if (tid == 0) {
+    S.kraft = 0;
+    S.bad = 0;
+    batch_rounds_init(S.r);
+  }
+  __syncthreads();
+  {
+    unsigned long long k = 0;
+    if (!code_share_ok(code, min_len, max_len, tid, kBatchThreads, &k)) atomicOr(&S.bad, 1);
+    if (k) atomicAdd(&S.kraft, k);
+    if (tid < 36) tab_load_row(S.t, tid, min_len, max_len, code->first_code, code->start_pos);
+    for (int i = tid; i < GHF_NSYM; i += kBatchThreads) S.t.symbol[i] = tab_symbol(code->symbol[i]);
+  }
+  __syncthreads();
+  if (S.bad || S.kraft != (1ull << 32)) return finish(GHF_E_FORMAT, 0);
+
+  const uint64_t stream_bytes = P.stream_bytes[item];
+  const uint8_t* __restrict__ const stream = P.stream_ptrs[item];
+  uint8_t* __restrict__ const out = kWrite ? P.out_ptrs[item] : nullptr;
+  const uint64_t cap = kWrite ? P.out_caps[item] : ~0ull;
+  if (!stream || (reinterpret_cast<uintptr_t>(stream) & 15u) || (kWrite && !out) || stream_bytes > P.max_stream_bytes)
+    return finish(GHF_E_INVAL, 0);
+
+  const int lb = max_len < kDecLutBitsMax ? max_len : kDecLutBitsMax;
+  const int long_from = lb + 1 > min_len ? lb + 1 : min_len;
+  tab_fill_lut(S.t, min_len, lb, tid, kBatchThreads);
+  __syncthreads();
+
+  uint32_t total = 0;  // stream_bytes <= ghf_compress_batch_shared_bound(1 MiB): every bit offset fits 32 bits
+  const int status = batch_decode_rounds<kWrite>(S.t, S.stage, S.r, stream, stream_bytes, 0u, cap, out, lb, long_from, max_len,
+                                                 &total, rounds, passes);
+  finish(status, total);
+}
+
 void launch_histogram_batch(const BatchHistParams& p, uint32_t flags, hipStream_t s) {
   if (p.count == 0) return;
   (void)hipMemsetAsync(p.hist, 0, 256 * sizeof(uint64_t), s);  // (slot 256 is the finish kernel's)
@@ -376,6 +445,12 @@ void launch_compress_batch_shared(const BatchSharedCompressParams& p, uint32_t c
 void launch_decode_batch_shared(const BatchSharedDecodeParams& p, uint32_t count, hipStream_t s) {
   if (count == 0) return;
   hipLaunchKernelGGL(k_decode_batch_shared, dim3(count), dim3(kBatchThreads), 0, s, p);
+}
+
+void launch_decode_bodies_batch_shared(const BatchSharedBodiesParams& p, uint32_t count, hipStream_t s) {
+  if (count == 0) return;
+  if (p.out_ptrs) hipLaunchKernelGGL(k_decode_bodies_batch_shared<true>, dim3(count), dim3(kBatchThreads), 0, s, p);
+  else hipLaunchKernelGGL(k_decode_bodies_batch_shared<false>, dim3(count), dim3(kBatchThreads), 0, s, p);
 }
 
 }  // namespace ghf

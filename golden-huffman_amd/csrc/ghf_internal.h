@@ -250,6 +250,18 @@ struct BatchSharedDecodeParams {
   uint64_t* out_bytes;
   int* item_status;
 };
+// bodies under one code, nothing else (ghf_decode_bodies_batch_shared): code boundaries and sizes are found by the workgroup
+struct BatchSharedBodiesParams {
+  const uint8_t* const* stream_ptrs;  // the bodies
+  const uint64_t* stream_bytes;
+  uint64_t max_stream_bytes;  // ghf_compress_batch_shared_bound(GHF_BATCH_MAX_ITEM): the workgroup's bit offsets fit 32 bits
+  const ghf_code* code;       // one for the batch, never null
+  uint8_t* const* out_ptrs;   // null: sizes only (out_caps is ignored)
+  const uint64_t* out_caps;
+  uint64_t* out_bytes;
+  int* item_status;
+  uint64_t* stats;            // may be null: [0] += rounds, [1] += passes of every item that reached its body
+};
 
 // K6: side-car reconstruction for foreign streams
 enum SyncKind : uint32_t {  // what SyncParams::no_eof carries
@@ -330,6 +342,7 @@ void launch_decode_images_batch(const BatchImagesParams& p, uint32_t count, hipS
 void launch_histogram_batch(const BatchHistParams& p, uint32_t flags, hipStream_t s);  // zeroes p.hist, counts, finishes
 void launch_compress_batch_shared(const BatchSharedCompressParams& p, uint32_t count, hipStream_t s);  // one launch, grid = count
 void launch_decode_batch_shared(const BatchSharedDecodeParams& p, uint32_t count, hipStream_t s);
+void launch_decode_bodies_batch_shared(const BatchSharedBodiesParams& p, uint32_t count, hipStream_t s);  // one launch; p.out_ptrs null: sizes only
 
 }  // namespace ghf
 #endif

@@ -132,6 +132,7 @@ EXPORTS = [
     "ghf_compress_batch_bound", "ghf_batch_index_alloc", "ghf_batch_index_free", "ghf_batch_index_item",
     "ghf_compress_batch", "ghf_decode_batch", "ghf_decode_images_batch", "ghf_decode_images_batch_stats",
     "ghf_histogram_batch", "ghf_compress_batch_shared_bound", "ghf_compress_batch_shared", "ghf_decode_batch_shared",
+    "ghf_decode_bodies_batch_shared",
 ]
 COMM_ID_BYTES = 128
 
@@ -239,6 +240,7 @@ def lib():
     L.ghf_compress_batch_shared_bound.restype = sz
     L.ghf_compress_batch_shared.argtypes = [vp, vp, vp, sz, C.c_uint32, vp, vp, vp, vp, C.POINTER(BatchIndex), vp]
     L.ghf_decode_batch_shared.argtypes = [vp, vp, vp, vp, C.POINTER(BatchIndex), vp, C.c_uint32, vp, vp, vp, vp]
+    L.ghf_decode_bodies_batch_shared.argtypes = [vp, vp, vp, vp, C.c_uint32, vp, vp, vp, vp]
     _lib = L
     return L
 
@@ -717,8 +719,40 @@ class Context:
         return {"out": d_out, "out_stride": out_stride, "out_bytes": out_bytes[:count], "status": status[:count],
                 "out_ptrs": out_ptrs, "out_caps": out_caps}
 
+    def decode_bodies_batch_shared(self, stream_ptrs, stream_bytes, d_code, out=None, caps=None):
+        """Bodies under the one code `d_code` and nothing else: no side-car, no sizes.  stream_ptrs / stream_bytes: int64
+        CUDA tensors [count] (e.g. out_ptrs and out_bytes of compress_batch_shared, or stored bodies copied up).
+        out=None: the sizes pass -> dict(out_bytes int64[count], status int32[count]).
+        Otherwise the decode pass, with out / caps as in decode_images_batch -> dict(out, out_stride, out_bytes, status,
+        out_ptrs, out_caps)"""
+        t = self.torch
+        count = int(stream_bytes.numel())
+        out_bytes = t.zeros(max(count, 1), dtype=t.int64, device=self.device)
+        status = t.full((max(count, 1),), -1, dtype=t.int32, device=self.device)
+        res = {"out_bytes": out_bytes[:count], "status": status[:count]}
+        out_ptrs = out_caps = None
+        if out is not None:
+            if caps is None:
+                raise ValueError("decode_bodies_batch_shared: the decode pass needs caps (e.g. the out_bytes of the sizes pass)")
+            if out is True:
+                out_stride = (int(caps.max().item()) + 15) & ~15 if count else 16
+                out = t.empty(max(count * out_stride, 16), dtype=t.uint8, device=self.device)
+            else:
+                out_stride = int(out.numel()) // max(count, 1)
+            out_ptrs = out.data_ptr() + t.arange(count, dtype=t.int64, device=self.device) * out_stride
+            out_caps = t.clamp(caps.to(t.int64), max=out_stride).contiguous()
+            res.update(out=out, out_stride=out_stride, out_ptrs=out_ptrs, out_caps=out_caps)
+        self._chk(
+            self.L.ghf_decode_bodies_batch_shared(self.h, stream_ptrs.data_ptr(), stream_bytes.data_ptr(), d_code.data_ptr(), count,
+                                                  None if out_ptrs is None else out_ptrs.data_ptr(),
+                                                  None if out_caps is None else out_caps.data_ptr(), out_bytes.data_ptr(),
+                                                  status.data_ptr()),
+            "ghf_decode_bodies_batch_shared")
+        return res
+
     def decode_images_batch_stats(self, d_stats):
-        """d_stats: an int64 CUDA tensor [2] that later decode_images_batch calls add {rounds, passes} to; None: off"""
+        """d_stats: an int64 CUDA tensor [2] that later decode_images_batch and decode_bodies_batch_shared calls add
+        {rounds, passes} to; None: off"""
         self._chk(self.L.ghf_decode_images_batch_stats(self.h, None if d_stats is None else d_stats.data_ptr()),
                   "ghf_decode_images_batch_stats")
 

@@ -369,7 +369,8 @@ int ghf_decode_images_batch(ghf_ctx* ctx, const uint8_t* const* d_stream_ptrs, c
 /* No reference counterpart.  Host only, nothing queued: d_stats (device u64[2], 8-byte aligned; NULL, the default:
  * nowhere) -- every later ghf_decode_images_batch on this context adds, over all items that reached their body,
  * d_stats[0] += rounds and d_stats[1] += passes.  The caller zeroes the two words; tools/batch_images_bench.py reads
- * them to hold the observed passes per round against the bound of 256. */
+ * them to hold the observed passes per round against the bound of 256.  ghf_decode_bodies_batch_shared (below) runs the
+ * same rounds and passes and adds its own to the same two words. */
 int ghf_decode_images_batch_stats(ghf_ctx* ctx, uint64_t* d_stats);
 
 /* ---- shared-code batches: one code for many small items ---------------------------------------------
@@ -393,8 +394,8 @@ int ghf_decode_images_batch_stats(ghf_ctx* ctx, uint64_t* d_stats);
  * ghf_code in device memory (one trained on a sample; one from ghf_parse_header, copied up).  Both kernels check it
  * before they trust it: a d_code that is not a complete prefix code of lengths <= 32 with a code for the end mark (the
  * rules ghf_decode_batch applies to an item's tables) gives GHF_E_FORMAT on EVERY item, and nothing is written.
- * Not supported here: bodies without a side-car (prepend the header and use ghf_decode_images_batch, or keep a seek
- * table per item: ghf_batch_index_item -> ghf_seek_pack), GHF_EMPTY_OK items, and the .crs format. */
+ * Bodies whose side-car and sizes are gone (stored bodies, read back by another process) go through
+ * ghf_decode_bodies_batch_shared below.  Not supported here: GHF_EMPTY_OK items, and the .crs format. */
 #define GHF_HIST_COVER_ALL 1u /* ghf_histogram_batch: every count of 0 becomes 1 */
 
 /* No reference counterpart; see above.  d_hist[0..255] <- the byte counts summed over all items, d_hist[256] <- 1: what
@@ -433,6 +434,37 @@ int ghf_decode_batch_shared(ghf_ctx* ctx, const uint8_t* const* d_stream_ptrs, c
                             const ghf_code* d_code, const ghf_batch_index* index, const uint64_t* d_n_symbols,
                             uint32_t count, uint8_t* const* d_out_ptrs, const uint64_t* d_out_caps,
                             uint64_t* d_out_bytes, int* d_item_status /* [count] */);
+
+/* No reference counterpart; see above.  ghf_decode_images_batch for bodies under one code: the fourth corner of
+ * {a code per item, one shared code} x {live side-car, nothing but the bytes}.  No side-car, no sizes and no per-item
+ * tables are passed.  ONE launch whatever count is, one workgroup per item.
+ * d_out_ptrs == NULL (then d_out_caps is ignored): sizes only -- d_out_bytes[i] <- what item i decodes to.
+ *
+ * Item i = the body at d_stream_ptrs[i] (16-byte aligned), d_stream_bytes[i] of it.  The body is decoded from bit 0 until
+ * the first end mark: d_stream_bytes[i] may exceed the body, what lies behind the end mark is not decoded.  The result
+ * goes to d_out_ptrs[i][0 .. n_i) (no alignment needed), d_out_bytes[i] <- n_i.  On success only d_out[0 .. n_i) is
+ * written; on failure nothing at or beyond d_out_caps[i] is written and d_out_bytes[i] = 0.  No byte outside
+ * d_stream_ptrs[i][0 .. d_stream_bytes[i]) is ever read, whatever the code holds.  A body whose first code is the end
+ * mark decodes to nothing: GHF_OK, 0 bytes (as in ghf_decode and ghf_decode_images_batch).
+ *
+ * The code is vetted before any item is looked at, with the rules ghf_decode_batch_shared applies: a d_code that is not a
+ * complete prefix code of lengths <= 32 gives GHF_E_FORMAT on EVERY item, and nothing is written.  The lone-end-mark code
+ * of GHF_EMPTY_OK is not complete and is refused the same way.
+ *
+ * d_item_status[i] <- (GHF_OK is written as well)
+ *   GHF_E_INVAL   null or misaligned stream pointer; null output pointer in decode mode; d_stream_bytes[i] greater than
+ *                 ghf_compress_batch_shared_bound(GHF_BATCH_MAX_ITEM) (every bit offset then fits 32 bits)
+ *   GHF_E_CAP     the item decodes to more than d_out_caps[i]; checked before any store of the round that would cross it
+ *                 (sizes only: the true count is reported with GHF_OK)
+ *   GHF_E_CORRUPT the stream ends before a whole end mark has been found; d_stream_bytes[i] == 0 is this case
+ *   GHF_E_FORMAT  (every item) d_code is not a complete prefix code
+ * Call-level errors (returned at once, nothing queued): null d_stream_ptrs / d_stream_bytes / d_out_bytes /
+ * d_item_status, d_out_ptrs without d_out_caps, a null or not 16-byte aligned d_code: GHF_E_INVAL.
+ * The workgroup finds the code boundaries itself, in the rounds and passes of ghf_decode_images_batch (DESIGN.md sections
+ * 10 and 13); the words named by ghf_decode_images_batch_stats receive this call's rounds and passes too. */
+int ghf_decode_bodies_batch_shared(ghf_ctx* ctx, const uint8_t* const* d_stream_ptrs, const uint64_t* d_stream_bytes,
+                                   const ghf_code* d_code, uint32_t count, uint8_t* const* d_out_ptrs,
+                                   const uint64_t* d_out_caps, uint64_t* d_out_bytes, int* d_item_status /* [count] */);
 
 /* Multi-GPU decode of a stream that has no side-car ("per-rank self-sync + one all-gather of symbol
  * counts"; the reference's decoders, canonical_huff_encoder.cc:377-568, are single-stream).  The caller cuts the body
