@@ -139,6 +139,7 @@ int ghf_ctx_destroy(ghf_ctx* c) {
   release(c->range_seg);
   release(c->range_chunk);
   release(c->batch_codes);
+  release(c->planes);
   if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
   delete c;
   return GHF_OK;
@@ -1047,6 +1048,114 @@ int ghf_decode(ghf_ctx* c, const uint8_t* d_stream, size_t stream_bytes, const g
   p.out = d_out;
   p.out_bytes = d_out_bytes;
   return decode_with_index(c, "ghf_decode", index, cap, p);
+}
+
+// ---------------------------------------------------------------------------------------------- byte planes
+// (no reference counterpart)
+size_t ghf_planes_slot_bytes(size_t n_elems) { return (ghf_compress_bound(n_elems) + 15) & ~(size_t)15; }
+
+static inline bool elem_bytes_ok(uint32_t e) { return e == 2 || e == 4 || e == 8; }
+static inline bool elems_overflow(size_t n_elems, uint32_t e) { return n_elems > (size_t)-1 / e; }
+// ... and for the calls that go through the workspace, whose planes sit at n_elems rounded up to 256
+static inline bool workspace_overflow(size_t n_elems, uint32_t e) { return elems_overflow(n_elems, e) || elems_overflow(n_elems + 255, e); }
+
+// what ghf_planes_split and ghf_planes_merge check alike: `d_inter` is the interleaved side
+static int planes_args(ghf_ctx* c, const char* who, const uint8_t* d_inter, const uint8_t* d_planes, size_t plane_stride, size_t n_elems,
+                       uint32_t elem_bytes) {
+  if (!c || !d_inter || !d_planes) return GHF_E_INVAL;
+  const std::string f = std::string(who) + ": ";
+  if (!elem_bytes_ok(elem_bytes)) return fail(c, GHF_E_INVAL, (f + "elem_bytes must be 2, 4 or 8").c_str());
+  if (!aligned16(d_inter) || !aligned16(d_planes) || (plane_stride & 15u))
+    return fail(c, GHF_E_INVAL, (f + "pointers and plane_stride must be multiples of 16").c_str());
+  if (elems_overflow(n_elems, elem_bytes)) return fail(c, GHF_E_INVAL, (f + "n_elems * elem_bytes overflows").c_str());
+  if (n_elems == 0) return fail(c, GHF_E_EMPTY, (f + "no elements").c_str());
+  if (plane_stride < n_elems) return fail(c, GHF_E_CAP, (f + "plane_stride below n_elems").c_str());
+  return GHF_OK;
+}
+
+int ghf_planes_split(ghf_ctx* c, const uint8_t* d_in, size_t n_elems, uint32_t elem_bytes, uint8_t* d_planes, size_t plane_stride) {
+  const int rc = planes_args(c, "ghf_planes_split", d_in, d_planes, plane_stride, n_elems, elem_bytes);
+  if (rc) return rc;
+  GHF_HIP(c, hipSetDevice(c->device));
+  launch_planes_split(d_in, n_elems, elem_bytes, d_planes, plane_stride, c->stream);
+  GHF_HIP(c, hipGetLastError());
+  return GHF_OK;
+}
+
+int ghf_planes_merge(ghf_ctx* c, const uint8_t* d_planes, size_t plane_stride, size_t n_elems, uint32_t elem_bytes, uint8_t* d_out) {
+  const int rc = planes_args(c, "ghf_planes_merge", d_out, d_planes, plane_stride, n_elems, elem_bytes);
+  if (rc) return rc;
+  GHF_HIP(c, hipSetDevice(c->device));
+  launch_planes_merge(d_planes, plane_stride, n_elems, elem_bytes, d_out, nullptr, c->stream);
+  GHF_HIP(c, hipGetLastError());
+  return GHF_OK;
+}
+
+// the context's plane workspace for n_elems elements (workspace_overflow has cleared them): *stride <- the distance
+// between two planes
+static int planes_workspace(ghf_ctx* c, size_t n_elems, uint32_t elem_bytes, size_t* stride) {
+  *stride = (n_elems + 255) & ~(size_t)255;
+  return grow(c, c->planes, *stride * elem_bytes);
+}
+
+int ghf_compress_planes(ghf_ctx* c, const uint8_t* d_in, size_t n_elems, uint32_t elem_bytes, uint8_t* d_out, size_t slot_bytes,
+                        uint64_t* d_out_bytes, ghf_code* d_codes, const ghf_index* indexes) {
+  if (!c || !d_in || !d_out || !d_out_bytes) return GHF_E_INVAL;
+  if (!elem_bytes_ok(elem_bytes)) return fail(c, GHF_E_INVAL, "ghf_compress_planes: elem_bytes must be 2, 4 or 8");
+  if (!aligned16(d_in) || !aligned16(d_out) || (slot_bytes & 15u))
+    return fail(c, GHF_E_INVAL, "ghf_compress_planes: d_in, d_out and slot_bytes must be multiples of 16");
+  if (workspace_overflow(n_elems, elem_bytes)) return fail(c, GHF_E_INVAL, "ghf_compress_planes: n_elems * elem_bytes overflows");
+  for (uint32_t p = 0; indexes && p < elem_bytes; ++p)
+    if (indexes[p].n_symbols != n_elems || !index_has_arrays(&indexes[p]))
+      return fail(c, GHF_E_INVAL, "ghf_compress_planes: an index does not match n_elems (use ghf_index_alloc)");
+  if (n_elems == 0) return fail(c, GHF_E_EMPTY, "ghf_compress_planes: no elements");
+  if (slot_bytes < ghf_planes_slot_bytes(n_elems)) return fail(c, GHF_E_CAP, "ghf_compress_planes: slot_bytes below ghf_planes_slot_bytes(n_elems)");
+  GHF_HIP(c, hipSetDevice(c->device));
+  size_t stride = 0;
+  int rc = planes_workspace(c, n_elems, elem_bytes, &stride);
+  if (rc) return rc;
+  launch_planes_split(d_in, n_elems, elem_bytes, c->planes.p, stride, c->stream);
+  GHF_HIP(c, hipGetLastError());
+  for (uint32_t p = 0; p < elem_bytes && !rc; ++p)  // compressor.h:62-73, once per plane
+    rc = ghf_compress(c, c->planes.p + p * stride, n_elems, d_out + p * slot_bytes, slot_bytes, d_out_bytes + p,
+                      d_codes ? d_codes + p : nullptr, indexes ? indexes + p : nullptr);
+  // the workspace is private and the next call refills the same addresses with other bytes
+  c->hist.forget();
+  c->plan.forget();
+  return rc;
+}
+
+int ghf_decode_planes(ghf_ctx* c, const uint8_t* const* h_stream_ptrs, const size_t* h_stream_bytes, const ghf_code* d_codes,
+                      const ghf_index* indexes, size_t n_elems, uint32_t elem_bytes, uint8_t* d_out, size_t cap, uint64_t* d_out_bytes) {
+  if (!c || !h_stream_ptrs || !h_stream_bytes || !d_codes || !d_out) return GHF_E_INVAL;
+  if (!elem_bytes_ok(elem_bytes)) return fail(c, GHF_E_INVAL, "ghf_decode_planes: elem_bytes must be 2, 4 or 8");
+  for (uint32_t p = 0; p < elem_bytes; ++p)
+    if (!h_stream_ptrs[p] || !aligned16(h_stream_ptrs[p])) return fail(c, GHF_E_INVAL, "ghf_decode_planes: a stream pointer is null or not 16-byte aligned");
+  if (!aligned16(d_out)) return fail(c, GHF_E_INVAL, "ghf_decode_planes: d_out must be 16-byte aligned");
+  if (workspace_overflow(n_elems, elem_bytes)) return fail(c, GHF_E_INVAL, "ghf_decode_planes: n_elems * elem_bytes overflows");
+  for (uint32_t p = 0; indexes && p < elem_bytes; ++p)
+    if (indexes[p].n_symbols != n_elems || !index_is_whole(&indexes[p]))
+      return fail(c, GHF_E_INVAL, "ghf_decode_planes: an index does not cover exactly n_elems symbols");
+  if (n_elems == 0) return fail(c, GHF_E_EMPTY, "ghf_decode_planes: no elements");
+  if (cap < n_elems * elem_bytes) return fail(c, GHF_E_CAP, "ghf_decode_planes: output capacity below n_elems * elem_bytes");
+  GHF_HIP(c, hipSetDevice(c->device));
+  size_t stride = 0;
+  int rc = planes_workspace(c, n_elems, elem_bytes, &stride);
+  if (rc) return rc;
+  for (uint32_t p = 0; p < elem_bytes; ++p) {
+    if (!indexes) {  // the side-car-less path: synchronises, and keeps the side-car for the decode that follows
+      uint64_t n_p = 0;
+      if ((rc = ghf_decoded_size(c, h_stream_ptrs[p], h_stream_bytes[p], d_codes + p, &n_p))) return rc;
+      if (n_p != n_elems) return fail(c, GHF_E_CORRUPT, "ghf_decode_planes: a plane does not decode to n_elems bytes");
+    }
+    if ((rc = ghf_decode(c, h_stream_ptrs[p], h_stream_bytes[p], d_codes + p, indexes ? indexes + p : nullptr, c->planes.p + p * stride,
+                         stride, nullptr)))
+      return rc;
+  }
+  launch_planes_merge(c->planes.p, stride, n_elems, elem_bytes, d_out, c->d_status, c->stream);  // nothing is stored behind a failed decode
+  if (d_out_bytes) launch_store_u64(d_out_bytes, nullptr, (uint64_t)n_elems * elem_bytes, c->stream);
+  GHF_HIP(c, hipGetLastError());
+  return GHF_OK;
 }
 
 // ---------------------------------------------------------------------------------------------- seek table

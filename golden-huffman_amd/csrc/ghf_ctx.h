@@ -135,6 +135,9 @@ struct ghf_ctx {
   ghf::DevBuf<uint64_t> range_chunk;
   // ghf_compress_batch without d_codes: one table set per item (describes nothing between calls)
   ghf::DevBuf<ghf_code> batch_codes;
+  // ghf_compress_planes / ghf_decode_planes: elem_bytes byte planes at a stride rounded up to 256 bytes.  Private to the two
+  // calls and rewritten by each: what K1 and K4 remember about an address inside it is forgotten before the call returns
+  ghf::DevBuf<uint8_t> planes;
   // ghf_decode_images_batch_stats: where the image decoder counts its rounds and passes (the caller's; null = nowhere)
   uint64_t* images_stats = nullptr;
   std::string err;

@@ -42,6 +42,14 @@ constexpr int kDec7LutLog2 = 14;
 constexpr int kDec7LutSlots = 1 << kDec7LutLog2;
 constexpr int kDec7SmallSlots = 1024;  // pair mode (max_len <= 5): the one-symbol table for ragged tails and the end mark, 32 copies
 
+// byte planes (ghf_planes.hip): one wave = one workgroup moves a tile of 64 * max(E, 4) 16-byte vectors of the interleaved
+// side at a time -- 2048 elements of 2 bytes, 1024 of 4 or 8 -- through an LDS tile of its own
+constexpr uint32_t kPlanesGroups = 256 * 16;      // one resident round: 16 one-wave workgroups on each of the 256 CUs
+constexpr uint32_t kPlanesLdsBytes = 9 * 1024;    // per workgroup: 64 rows of (8 + 1) vectors at E = 8; 6 KiB (E = 2), 5 KiB (E = 4)
+__host__ __device__ constexpr inline uint32_t planes_tile_elems(uint32_t elem_bytes) {
+  return (uint32_t)kWave * (elem_bytes < 4 ? 4 : elem_bytes) * 16 / elem_bytes;
+}
+
 // the .crs2 header: the count word, symbol[257], min_len, max_len, then a (start_pos, first_code) row per length 1..max_len
 constexpr uint64_t kHeaderFixedBytes = 4 * (GHF_NSYM + 3);  // 1040
 template <class T>  // in the type of its argument: kernels that count in 32 bits keep doing so
@@ -343,6 +351,12 @@ void launch_histogram_batch(const BatchHistParams& p, uint32_t flags, hipStream_
 void launch_compress_batch_shared(const BatchSharedCompressParams& p, uint32_t count, hipStream_t s);  // one launch, grid = count
 void launch_decode_batch_shared(const BatchSharedDecodeParams& p, uint32_t count, hipStream_t s);
 void launch_decode_bodies_batch_shared(const BatchSharedBodiesParams& p, uint32_t count, hipStream_t s);  // one launch; p.out_ptrs null: sizes only
+// ghf_planes.hip: byte planes of elements of 2, 4 or 8 bytes (n_elems > 0; every pointer and plane_stride 16-byte aligned)
+void launch_planes_split(const uint8_t* d_in, uint64_t n_elems, uint32_t elem_bytes, uint8_t* d_planes, uint64_t plane_stride,
+                         hipStream_t s);
+// d_status (may be null): the launch stores nothing when the word is non-zero
+void launch_planes_merge(const uint8_t* d_planes, uint64_t plane_stride, uint64_t n_elems, uint32_t elem_bytes, uint8_t* d_out,
+                         const int* d_status, hipStream_t s);
 
 }  // namespace ghf
 #endif

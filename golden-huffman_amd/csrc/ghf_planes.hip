@@ -1,0 +1,209 @@
+// golden-huffman_amd/csrc/ghf_planes.hip -- byte planes of typed elements.
+// k_planes_split<E>: d_in[0 .. n_elems * E) -> E planes, byte b of element k at planes + b * plane_stride + k.
+// k_planes_merge<E>: the inverse.  E = 2, 4, 8.  Both move N bytes in and N bytes out and nothing else; they are judged as
+// streaming kernels against k_stream_copy (ghf_kernels.hip) and keep its access shape: every global access of the main loop
+// is one 16-byte vector per lane with consecutive lanes on consecutive vectors -- on the interleaved side and on every
+// plane --, max(E, 4) loads are in flight per lane before the first use, the non-temporal hint on both sides, and one
+// resident round of workgroups that each stream through a contiguous slab of tiles.
+//
+// One wave = one workgroup = one tile at a time.  A tile is 64 * max(E, 4) vectors of the interleaved side, cut into ROWS
+// of E vectors = 16 elements.  The row is the unit of the transposition: a lane that holds a row's E vectors turns them
+// into one 16-byte vector of each plane with v_perm_b32 alone (byte 4x4 transposes).  Rows reach their lanes through the
+// wave's LDS tile: the interleaved side is loaded (stored) with lane l on vector 64 j + l, the row side reads (writes) the
+// E consecutive vectors of row l.  A row is padded by one vector, (E + 1) * 16 bytes: the ds_read_b128 / ds_write_b128 of
+// the row side, 16 lanes (8 lanes) at that stride, then fall on distinct banks for every E (12, 20, 36 dwords: 4 * odd).
+// The LDS carries 2 N bytes at 16 bytes per lane and instruction; no barrier is needed, the tile is private to its wave.
+#include "ghf_device.h"
+
+namespace ghf {
+
+namespace {
+
+template <int E>
+struct PlanesGeom {
+  static constexpr int kVec = E < 4 ? 4 : E;           // 16-byte loads in flight per lane
+  static constexpr int kRows = kWave * kVec / E;       // rows of 16 elements per tile
+  static constexpr int kRowsPerLane = kVec / E;        // 2 (E = 2) or 1
+  static constexpr int kRowVec = E + 1;                // a row in LDS, in vectors: padded by one
+  static constexpr uint32_t kTile = planes_tile_elems(E);
+  static_assert(kTile == (uint32_t)kRows * 16, "the tile the host counts with");
+  static_assert(kRows * kRowVec * 16 <= (int)kPlanesLdsBytes, "the LDS budget of DESIGN.md section 14");
+};
+
+__device__ __forceinline__ uint32_t perm(uint32_t hi, uint32_t lo, uint32_t sel) { return __builtin_amdgcn_perm(hi, lo, sel); }
+
+// 4x4 byte transpose: o[b] byte k = byte b of i_k.  Its own inverse.
+__device__ __forceinline__ void transpose4(uint32_t i0, uint32_t i1, uint32_t i2, uint32_t i3, uint32_t& o0, uint32_t& o1,
+                                           uint32_t& o2, uint32_t& o3) {
+  const uint32_t lo01 = perm(i1, i0, 0x05010400u), hi01 = perm(i1, i0, 0x07030602u);  // {i0.b0 i1.b0 i0.b1 i1.b1}, {.. b2 .. b3}
+  const uint32_t lo23 = perm(i3, i2, 0x05010400u), hi23 = perm(i3, i2, 0x07030602u);
+  o0 = perm(lo23, lo01, 0x05040100u);
+  o1 = perm(lo23, lo01, 0x07060302u);
+  o2 = perm(hi23, hi01, 0x05040100u);
+  o3 = perm(hi23, hi01, 0x07060302u);
+}
+
+__device__ __forceinline__ uint32_t& word(uint4& v, int q) { return q == 0 ? v.x : q == 1 ? v.y : q == 2 ? v.z : v.w; }
+__device__ __forceinline__ uint32_t word(const uint4& v, int q) { return q == 0 ? v.x : q == 1 ? v.y : q == 2 ? v.z : v.w; }
+
+// a row's E vectors (16 elements) -> one vector of each plane.  Dword d of the row is word d % 4 of r[d / 4].
+template <int E>
+__device__ __forceinline__ void row_to_planes(const uint4 (&r)[E], uint4 (&p)[E]) {
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {  // elements 4 q .. 4 q + 3 -> dword q of every plane
+    if constexpr (E == 2) {
+      const uint32_t a = word(r[q / 2], 2 * q % 4), b = word(r[q / 2], 2 * q % 4 + 1);
+      word(p[0], q) = perm(b, a, 0x06040200u);
+      word(p[1], q) = perm(b, a, 0x07050301u);
+    } else if constexpr (E == 4) {
+      transpose4(r[q].x, r[q].y, r[q].z, r[q].w, word(p[0], q), word(p[1], q), word(p[2], q), word(p[3], q));
+    } else {  // an element is two dwords: the even ones hold planes 0..3, the odd ones planes 4..7
+      transpose4(r[2 * q].x, r[2 * q].z, r[2 * q + 1].x, r[2 * q + 1].z, word(p[0], q), word(p[1], q), word(p[2], q), word(p[3], q));
+      transpose4(r[2 * q].y, r[2 * q].w, r[2 * q + 1].y, r[2 * q + 1].w, word(p[4], q), word(p[5], q), word(p[6], q), word(p[7], q));
+    }
+  }
+}
+
+template <int E>
+__device__ __forceinline__ void planes_to_row(const uint4 (&p)[E], uint4 (&r)[E]) {
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    if constexpr (E == 2) {
+      const uint32_t a = word(p[0], q), b = word(p[1], q);
+      word(r[q / 2], 2 * q % 4) = perm(b, a, 0x05010400u);
+      word(r[q / 2], 2 * q % 4 + 1) = perm(b, a, 0x07030602u);
+    } else if constexpr (E == 4) {
+      transpose4(word(p[0], q), word(p[1], q), word(p[2], q), word(p[3], q), r[q].x, r[q].y, r[q].z, r[q].w);
+    } else {
+      transpose4(word(p[0], q), word(p[1], q), word(p[2], q), word(p[3], q), r[2 * q].x, r[2 * q].z, r[2 * q + 1].x, r[2 * q + 1].z);
+      transpose4(word(p[4], q), word(p[5], q), word(p[6], q), word(p[7], q), r[2 * q].y, r[2 * q].w, r[2 * q + 1].y, r[2 * q + 1].w);
+    }
+  }
+}
+
+// the hint of k_stream_copy<true>, K1 and K7 on both sides: every byte is touched once.  (`make nt_ab` builds the -DGHF_PLANES_NT=0
+// variant for the A/B of DESIGN.md section 14, tools/planes_nt_ab.py.)
+#ifndef GHF_PLANES_NT
+#define GHF_PLANES_NT 1
+#endif
+__device__ __forceinline__ uint4 ld16(const uint4* p) { return GHF_PLANES_NT ? load_stream(p) : *p; }
+__device__ __forceinline__ void st16(uint4* p, const uint4& v) {
+  if (GHF_PLANES_NT) store_stream(p, v);
+  else *p = v;
+}
+
+// the slab of whole tiles this workgroup streams through (as k_stream_copy cuts its vectors), and the ragged end: the
+// elements behind the last whole tile, one per lane, spread over the grid (launch_planes makes the grid wide enough)
+struct Slab {
+  uint64_t lo, end, tail;
+};
+__device__ __forceinline__ Slab slab_of(uint64_t n_elems, uint32_t tile) {
+  const uint64_t nt = n_elems / tile, per = (nt + gridDim.x - 1) / gridDim.x;
+  const uint64_t lo = (uint64_t)blockIdx.x * per;
+  return {lo, lo + per < nt ? lo + per : nt, nt * tile + (uint64_t)blockIdx.x * kWave + threadIdx.x};
+}
+
+}  // namespace
+
+template <int E>
+__global__ __launch_bounds__(kWave) void k_planes_split(const uint8_t* __restrict__ in, uint64_t n_elems, uint8_t* __restrict__ planes,
+                                                        uint64_t plane_stride) {
+  using G = PlanesGeom<E>;
+  __shared__ uint4 tile[G::kRows * G::kRowVec];
+  const uint32_t lane = threadIdx.x;
+  const Slab s = slab_of(n_elems, G::kTile);
+  for (uint64_t t = s.lo; t < s.end; ++t) {
+    const uint4* src = reinterpret_cast<const uint4*>(in) + t * (kWave * G::kVec);
+    uint4 x[G::kVec];
+#pragma unroll
+    for (int j = 0; j < G::kVec; ++j) x[j] = ld16(src + j * kWave + lane);
+#pragma unroll
+    for (int j = 0; j < G::kVec; ++j) {
+      const uint32_t v = j * kWave + lane;
+      tile[(v / E) * G::kRowVec + v % E] = x[j];
+    }
+    wave_sync();
+#pragma unroll
+    for (int r = 0; r < G::kRowsPerLane; ++r) {
+      const uint32_t row = r * kWave + lane;
+      uint4 y[E], p[E];
+#pragma unroll
+      for (int j = 0; j < E; ++j) y[j] = tile[row * G::kRowVec + j];
+      row_to_planes<E>(y, p);
+#pragma unroll
+      for (int b = 0; b < E; ++b) st16(reinterpret_cast<uint4*>(planes + b * plane_stride) + t * G::kRows + row, p[b]);
+    }
+    wave_sync();
+  }
+  for (uint64_t k = s.tail; k < n_elems; k += (uint64_t)gridDim.x * kWave) {  // the ragged end: byte by byte
+#pragma unroll
+    for (int b = 0; b < E; ++b) planes[b * plane_stride + k] = in[k * E + b];
+  }
+}
+
+// status (may be null): the context's latched status word; a launch that finds it non-zero stores nothing (one read per
+// workgroup, the convention of k_decode) -- the planes of a failed decode are not merged
+template <int E>
+__global__ __launch_bounds__(kWave) void k_planes_merge(const uint8_t* __restrict__ planes, uint64_t plane_stride, uint64_t n_elems,
+                                                        uint8_t* __restrict__ out, const int* __restrict__ status) {
+  using G = PlanesGeom<E>;
+  __shared__ uint4 tile[G::kRows * G::kRowVec];
+  if (status && __builtin_amdgcn_readfirstlane(*status) != 0) return;
+  const uint32_t lane = threadIdx.x;
+  const Slab s = slab_of(n_elems, G::kTile);
+  for (uint64_t t = s.lo; t < s.end; ++t) {
+    uint4 p[G::kRowsPerLane][E];
+#pragma unroll
+    for (int r = 0; r < G::kRowsPerLane; ++r)
+#pragma unroll
+      for (int b = 0; b < E; ++b)
+        p[r][b] = ld16(reinterpret_cast<const uint4*>(planes + b * plane_stride) + t * G::kRows + r * kWave + lane);
+#pragma unroll
+    for (int r = 0; r < G::kRowsPerLane; ++r) {
+      const uint32_t row = r * kWave + lane;
+      uint4 y[E];
+      planes_to_row<E>(p[r], y);
+#pragma unroll
+      for (int j = 0; j < E; ++j) tile[row * G::kRowVec + j] = y[j];
+    }
+    wave_sync();
+    uint4* dst = reinterpret_cast<uint4*>(out) + t * (kWave * G::kVec);
+#pragma unroll
+    for (int j = 0; j < G::kVec; ++j) {
+      const uint32_t v = j * kWave + lane;
+      st16(dst + j * kWave + lane, tile[(v / E) * G::kRowVec + v % E]);
+    }
+    wave_sync();
+  }
+  for (uint64_t k = s.tail; k < n_elems; k += (uint64_t)gridDim.x * kWave) {
+#pragma unroll
+    for (int b = 0; b < E; ++b) out[k * E + b] = planes[b * plane_stride + k];
+  }
+}
+
+// one resident round: kPlanesGroups one-wave workgroups, each with a slab of whole tiles; at least one lane per element of
+// the ragged end
+static uint32_t planes_grid(uint64_t n_elems, uint32_t elem_bytes) {
+  const uint32_t tile = planes_tile_elems(elem_bytes);
+  const uint64_t nt = n_elems / tile, tail_waves = (n_elems % tile + kWave - 1) / kWave;
+  const uint64_t g = nt > tail_waves ? nt : tail_waves;
+  return (uint32_t)(g > kPlanesGroups ? kPlanesGroups : g);
+}
+
+void launch_planes_split(const uint8_t* d_in, uint64_t n_elems, uint32_t elem_bytes, uint8_t* d_planes, uint64_t plane_stride,
+                         hipStream_t s) {
+  const dim3 grid(planes_grid(n_elems, elem_bytes)), block(kWave);
+  if (elem_bytes == 2) hipLaunchKernelGGL(k_planes_split<2>, grid, block, 0, s, d_in, n_elems, d_planes, plane_stride);
+  else if (elem_bytes == 4) hipLaunchKernelGGL(k_planes_split<4>, grid, block, 0, s, d_in, n_elems, d_planes, plane_stride);
+  else hipLaunchKernelGGL(k_planes_split<8>, grid, block, 0, s, d_in, n_elems, d_planes, plane_stride);
+}
+
+void launch_planes_merge(const uint8_t* d_planes, uint64_t plane_stride, uint64_t n_elems, uint32_t elem_bytes, uint8_t* d_out,
+                         const int* d_status, hipStream_t s) {
+  const dim3 grid(planes_grid(n_elems, elem_bytes)), block(kWave);
+  if (elem_bytes == 2) hipLaunchKernelGGL(k_planes_merge<2>, grid, block, 0, s, d_planes, plane_stride, n_elems, d_out, d_status);
+  else if (elem_bytes == 4) hipLaunchKernelGGL(k_planes_merge<4>, grid, block, 0, s, d_planes, plane_stride, n_elems, d_out, d_status);
+  else hipLaunchKernelGGL(k_planes_merge<8>, grid, block, 0, s, d_planes, plane_stride, n_elems, d_out, d_status);
+}
+
+}  // namespace ghf

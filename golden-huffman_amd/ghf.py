@@ -12,6 +12,13 @@ INDEX_NO_END_MARK = 1
 CODE_LIMIT = 1
 BATCH_MAX_ITEM = 1 << 20  # GHF_BATCH_MAX_ITEM: the largest item of ghf_compress_batch / ghf_decode_batch
 HIST_COVER_ALL = 1  # GHF_HIST_COVER_ALL (ghf_histogram_batch): every count of 0 becomes 1
+PLANES_MAX = 8  # GHF_PLANES_MAX: the widest element of the byte-plane calls
+PLANES_ELEM_BYTES = (2, 4, 8)
+# ghf_internal.h planes_tile_elems / kPlanesGroups: the elements one wave of k_planes_split / k_planes_merge moves at a time
+# (tests/test_planes_cpu.py holds them against the kernels' LDS tiles), and the one-wave workgroups of one resident round.
+# Tests size their ragged and second-round cases with them; nothing in the library's behaviour depends on them.
+PLANES_TILE = {2: 2048, 4: 1024, 8: 1024}
+PLANES_GROUPS = 256 * 16
 EMPTY_OK = 2  # opt-in: n == 0 -> header of the one-symbol code + 0x7F (builder's definition, parity unpinned)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -133,6 +140,7 @@ EXPORTS = [
     "ghf_compress_batch", "ghf_decode_batch", "ghf_decode_images_batch", "ghf_decode_images_batch_stats",
     "ghf_histogram_batch", "ghf_compress_batch_shared_bound", "ghf_compress_batch_shared", "ghf_decode_batch_shared",
     "ghf_decode_bodies_batch_shared",
+    "ghf_planes_slot_bytes", "ghf_planes_split", "ghf_planes_merge", "ghf_compress_planes", "ghf_decode_planes",
 ]
 COMM_ID_BYTES = 128
 
@@ -241,6 +249,12 @@ def lib():
     L.ghf_compress_batch_shared.argtypes = [vp, vp, vp, sz, C.c_uint32, vp, vp, vp, vp, C.POINTER(BatchIndex), vp]
     L.ghf_decode_batch_shared.argtypes = [vp, vp, vp, vp, C.POINTER(BatchIndex), vp, C.c_uint32, vp, vp, vp, vp]
     L.ghf_decode_bodies_batch_shared.argtypes = [vp, vp, vp, vp, C.c_uint32, vp, vp, vp, vp]
+    L.ghf_planes_slot_bytes.argtypes = [sz]
+    L.ghf_planes_slot_bytes.restype = sz
+    L.ghf_planes_split.argtypes = [vp, vp, sz, C.c_uint32, vp, sz]
+    L.ghf_planes_merge.argtypes = [vp, vp, sz, sz, C.c_uint32, vp]
+    L.ghf_compress_planes.argtypes = [vp, vp, sz, C.c_uint32, vp, sz, vp, vp, C.POINTER(Index)]
+    L.ghf_decode_planes.argtypes = [vp, C.POINTER(vp), C.POINTER(sz), vp, C.POINTER(Index), sz, C.c_uint32, vp, sz, vp]
     _lib = L
     return L
 
@@ -265,6 +279,11 @@ def compress_batch_bound(max_item_bytes):
 def compress_batch_shared_bound(max_item_bytes):
     """capacity that suffices for the BODY of every item of a shared-code batch, under any code of <= 32 bits"""
     return int(lib().ghf_compress_batch_shared_bound(max_item_bytes))
+
+
+def planes_slot_bytes(n_elems):
+    """a slot that suffices for the image of any byte plane of n_elems elements (a multiple of 16)"""
+    return int(lib().ghf_planes_slot_bytes(n_elems))
 
 
 def batch_index_item(bidx, i, n_i):
@@ -755,6 +774,74 @@ class Context:
         {rounds, passes} to; None: off"""
         self._chk(self.L.ghf_decode_images_batch_stats(self.h, None if d_stats is None else d_stats.data_ptr()),
                   "ghf_decode_images_batch_stats")
+
+    # ---- byte planes: elements of 2, 4 or 8 bytes, one ordinary .crs2 image per byte position ---------
+    planes_slot_bytes = staticmethod(planes_slot_bytes)
+
+    def planes_split(self, d_in, elem_bytes, n_elems=None, d_planes=None, plane_stride=None):
+        """byte b of element k of d_in -> d_planes[b * plane_stride + k].  -> (d_planes uint8, plane_stride)"""
+        n_elems = d_in.numel() * d_in.element_size() // elem_bytes if n_elems is None else n_elems
+        if plane_stride is None:
+            plane_stride = (n_elems + 255) & ~255
+        if d_planes is None:
+            d_planes = self.empty_u8(plane_stride * elem_bytes)
+        self._chk(self.L.ghf_planes_split(self.h, d_in.data_ptr(), n_elems, elem_bytes, d_planes.data_ptr(), plane_stride),
+                  "ghf_planes_split")
+        return d_planes, plane_stride
+
+    def planes_merge(self, d_planes, plane_stride, n_elems, elem_bytes, d_out=None):
+        """the inverse of planes_split.  -> d_out uint8[n_elems * elem_bytes]"""
+        if d_out is None:
+            d_out = self.empty_u8(n_elems * elem_bytes)
+        self._chk(self.L.ghf_planes_merge(self.h, d_planes.data_ptr(), plane_stride, n_elems, elem_bytes, d_out.data_ptr()),
+                  "ghf_planes_merge")
+        return d_out
+
+    def planes_index_alloc(self, n_elems, elem_bytes):
+        """elem_bytes side-cars of n_elems symbols as the ctypes array compress_planes / decode_planes take"""
+        arr = (Index * elem_bytes)()
+        for p in range(elem_bytes):
+            self._chk(self.L.ghf_index_alloc(self.h, n_elems, C.byref(arr[p])), "ghf_index_alloc")
+        return arr
+
+    def planes_index_free(self, arr):
+        for ix in arr:
+            self.L.ghf_index_free(self.h, C.byref(ix))
+
+    def compress_planes(self, d_in, elem_bytes, n_elems=None, d_out=None, slot_bytes=None, d_codes=None, indexes=None):
+        """d_in: a CUDA tensor of elements (any dtype; elem_bytes says how wide an element is).  Plane p's .crs2 image goes to
+        d_out[p * slot_bytes ..); no host synchronisation.  indexes: None or planes_index_alloc(n_elems, elem_bytes).
+        -> dict(out, slot_bytes, out_bytes int64[elem_bytes], codes uint8[elem_bytes, sizeof(Code)], n_elems, elem_bytes)"""
+        t = self.torch
+        n_elems = d_in.numel() * d_in.element_size() // elem_bytes if n_elems is None else n_elems
+        if slot_bytes is None:
+            slot_bytes = planes_slot_bytes(n_elems)
+        if d_out is None:
+            d_out = self.empty_u8(slot_bytes * elem_bytes)
+        if d_codes is None:
+            d_codes = t.zeros((elem_bytes, C.sizeof(Code)), dtype=t.uint8, device=self.device)
+        out_bytes = t.zeros(elem_bytes, dtype=t.int64, device=self.device)
+        self._chk(
+            self.L.ghf_compress_planes(self.h, d_in.data_ptr(), n_elems, elem_bytes, d_out.data_ptr(), slot_bytes,
+                                       out_bytes.data_ptr(), d_codes.data_ptr(), indexes),
+            "ghf_compress_planes")
+        return {"out": d_out, "slot_bytes": slot_bytes, "out_bytes": out_bytes, "codes": d_codes, "n_elems": n_elems,
+                "elem_bytes": elem_bytes}
+
+    def decode_planes(self, streams, stream_bytes, d_codes, n_elems, elem_bytes, indexes=None, d_out=None, cap=None, nbytes=None):
+        """streams: elem_bytes CUDA uint8 tensors (e.g. the slots of compress_planes), stream_bytes: their sizes as host
+        ints.  indexes=None: the side-car-less path (synchronises).  -> (d_out uint8, nbytes int64[1] device)"""
+        ptrs = (C.c_void_p * elem_bytes)(*[x.data_ptr() for x in streams])
+        sizes = (C.c_size_t * elem_bytes)(*[int(v) for v in stream_bytes])
+        if d_out is None:
+            d_out = self.empty_u8(n_elems * elem_bytes)
+        if nbytes is None:
+            nbytes = self.torch.zeros(1, dtype=self.torch.int64, device=self.device)
+        self._chk(
+            self.L.ghf_decode_planes(self.h, ptrs, sizes, d_codes.data_ptr(), indexes, n_elems, elem_bytes, d_out.data_ptr(),
+                                     d_out.numel() if cap is None else cap, nbytes.data_ptr()),
+            "ghf_decode_planes")
+        return d_out, nbytes
 
     # ---- seekable streams: the seek table (the persistent form of the side-car) ----------------
     def seek_pack(self, index, d_stream=None, stream_bytes=0, d_table=None, n=None):

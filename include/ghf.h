@@ -466,6 +466,64 @@ int ghf_decode_bodies_batch_shared(ghf_ctx* ctx, const uint8_t* const* d_stream_
                                    const ghf_code* d_code, uint32_t count, uint8_t* const* d_out_ptrs,
                                    const uint64_t* d_out_caps, uint64_t* d_out_bytes, int* d_item_status /* [count] */);
 
+/* ---- byte planes: typed elements (bf16 / fp32 / 64-bit) as one .crs2 image per byte position --------
+ * No reference counterpart (the reference compresses one flat run of bytes per process, include/compressor.h:62-73, and
+ * reads one back, include/compressor.h:87-92).  Callers that hold elements of 2, 4 or 8 bytes lose most of the skew of the
+ * high (sign / exponent) byte when all bytes share one histogram.  These calls split the elements into elem_bytes PLANES
+ * -- plane b holds byte b of every element, in element order (the "shuffle" filter of Blosc, ZipNN and HDF5) -- and
+ * compress every plane by itself.  The .crs2 format does not change: EACH PLANE IS AN ORDINARY STANDALONE .crs2 IMAGE of
+ * the bytes d_in[b], d_in[b + E], d_in[b + 2 E] ..., byte-identical to what ghf_compress (and so the reference) writes for
+ * them; the reference's decoders, ghf_decode, the seek table and ghf_decode_range read it as any other.
+ *
+ * elem_bytes is 2, 4 or 8.  Every device pointer is 16-byte aligned and so are plane_stride and slot_bytes.  These
+ * call-level errors are returned at once with nothing queued, checked before anything touches HIP: a null context or
+ * required pointer, another elem_bytes, a misaligned pointer / plane_stride / slot_bytes, n_elems * elem_bytes beyond
+ * size_t, an indexes[p] that does not cover n_elems: GHF_E_INVAL; then n_elems == 0: GHF_E_EMPTY; then plane_stride <
+ * n_elems, slot_bytes < ghf_planes_slot_bytes(n_elems), cap < n_elems * elem_bytes: GHF_E_CAP.  "Nothing queued" holds for
+ * these conditions only: whatever else an inner ghf_compress / ghf_decoded_size / ghf_decode refuses for one plane (a
+ * stream shorter than its header, an allocation that fails) is returned when that plane is reached, behind the split and
+ * the planes queued before it; d_out of ghf_decode_planes is still untouched then, the merge comes last. */
+#define GHF_PLANES_MAX 8
+
+/* No reference counterpart.  Host only: (ghf_compress_bound(n_elems) + 15) & ~15, a slot that suffices for any plane of
+ * n_elems bytes. */
+size_t ghf_planes_slot_bytes(size_t n_elems);
+
+/* No reference counterpart (generalises the flat input of include/compressor.h:62-73).  Asynchronous on the stream, never
+ * synchronises: byte b of element k of d_in[0 .. n_elems * elem_bytes) goes to d_planes[b * plane_stride + k].  Only
+ * [0, n_elems) of every plane is written.  One streaming kernel: 16 bytes per lane on both sides, the transposition in
+ * registers and a wave-private LDS tile. */
+int ghf_planes_split(ghf_ctx* ctx, const uint8_t* d_in, size_t n_elems, uint32_t elem_bytes, uint8_t* d_planes,
+                     size_t plane_stride);
+/* No reference counterpart (generalises the flat output of include/compressor.h:87-92).  The inverse of ghf_planes_split:
+ * only d_out[0 .. n_elems * elem_bytes) is written.  Does not look at the context's status word. */
+int ghf_planes_merge(ghf_ctx* ctx, const uint8_t* d_planes, size_t plane_stride, size_t n_elems, uint32_t elem_bytes,
+                     uint8_t* d_out);
+
+/* No reference counterpart: Compressor::compress(), include/compressor.h:62-73, once per byte plane.  Asynchronous on the
+ * stream, no host synchronisation: splits d_in into a workspace of the context that grows on demand, then does for
+ * p = 0 .. elem_bytes - 1 exactly what ghf_compress does for plane p: the image goes to d_out + p * slot_bytes, its size to
+ * d_out_bytes[p] (device u64[elem_bytes]); d_codes[p] (device, optional) and indexes[p] (a HOST array of elem_bytes
+ * side-cars, each from ghf_index_alloc(n_elems); optional) are filled as ghf_compress fills d_code and index.  Device-side
+ * failures latch as for ghf_compress.  An indexes[p] that was not allocated for n_elems: GHF_E_INVAL, nothing queued. */
+int ghf_compress_planes(ghf_ctx* ctx, const uint8_t* d_in, size_t n_elems, uint32_t elem_bytes, uint8_t* d_out,
+                        size_t slot_bytes, uint64_t* d_out_bytes, ghf_code* d_codes, const ghf_index* indexes);
+
+/* No reference counterpart: Decompressor::decompress(), include/compressor.h:87-92, once per byte plane.  ghf_decode of
+ * plane p = the image at h_stream_ptrs[p] (a HOST array of elem_bytes device pointers), h_stream_bytes[p] (HOST) of it,
+ * with d_codes[p] (device) and indexes[p], into the context's workspace; then the merge into d_out[0 .. n_elems *
+ * elem_bytes), d_out_bytes (device u64, optional) <- that size.
+ * indexes != NULL (a HOST array of elem_bytes side-cars): the call never synchronises.  Every indexes[p].n_symbols must
+ * equal n_elems: GHF_E_INVAL otherwise, nothing queued.
+ * indexes == NULL: every plane takes the side-car-less path, which SYNCHRONISES with the host as ghf_decoded_size and
+ * ghf_decode(index = NULL) do.  A plane that decodes to another size than n_elems: GHF_E_CORRUPT is returned and no merge
+ * is queued (d_out is untouched).
+ * The merge does not run on the planes of a failed decode: a launch that finds the context's latched status non-zero stores
+ * nothing (the convention of the decode kernel itself); ghf_sync reports the status. */
+int ghf_decode_planes(ghf_ctx* ctx, const uint8_t* const* h_stream_ptrs, const size_t* h_stream_bytes,
+                      const ghf_code* d_codes, const ghf_index* indexes, size_t n_elems, uint32_t elem_bytes, uint8_t* d_out,
+                      size_t cap, uint64_t* d_out_bytes);
+
 /* Multi-GPU decode of a stream that has no side-car ("per-rank self-sync + one all-gather of symbol
  * counts"; the reference's decoders, canonical_huff_encoder.cc:377-568, are single-stream).  The caller cuts the body
  * at byte positions; a rank's piece is its own bytes followed by >= 8 bytes of look-ahead from the next piece (zeros
