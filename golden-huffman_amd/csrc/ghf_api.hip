@@ -668,6 +668,146 @@ int ghf_decode_bodies_batch_shared(ghf_ctx* c, const uint8_t* const* d_stream_pt
   return GHF_OK;
 }
 
+// ---------------------------------------------------------------------------------------------- shared-code batches of byte planes
+static inline bool planes_elem_ok(uint32_t elem_bytes) { return elem_bytes == 2 || elem_bytes == 4 || elem_bytes == 8; }
+// max_item_bytes of a batch of elements: 1 .. GHF_BATCH_MAX_ITEM and a whole number of elements
+static inline bool planes_item_ok(size_t max_item_bytes, uint32_t elem_bytes) {
+  return max_item_bytes != 0 && max_item_bytes <= GHF_BATCH_MAX_ITEM && max_item_bytes % elem_bytes == 0;
+}
+
+int ghf_histogram_batch_planes(ghf_ctx* c, const uint8_t* const* d_in_ptrs, const uint64_t* d_in_bytes, size_t max_item_bytes,
+                               uint32_t count, uint32_t elem_bytes, unsigned flags, uint64_t* d_hists) {
+  if (!c) return GHF_E_INVAL;
+  if (!planes_elem_ok(elem_bytes)) return fail(c, GHF_E_INVAL, "ghf_histogram_batch_planes: elem_bytes must be 2, 4 or 8");
+  if (!planes_item_ok(max_item_bytes, elem_bytes))
+    return fail(c, GHF_E_INVAL, "ghf_histogram_batch_planes: max_item_bytes must be 1 .. GHF_BATCH_MAX_ITEM and a multiple of elem_bytes");
+  if (flags & ~GHF_HIST_COVER_ALL) return fail(c, GHF_E_INVAL, "ghf_histogram_batch_planes: unknown flags");
+  if (!d_in_ptrs || !d_in_bytes || !d_hists) return GHF_E_INVAL;
+  if (count == 0) return GHF_OK;
+  GHF_HIP(c, hipSetDevice(c->device));
+  BatchPlanesHistParams p;
+  p.in_ptrs = d_in_ptrs;
+  p.in_bytes = d_in_bytes;
+  p.max_item_bytes = max_item_bytes;
+  p.count = count;
+  p.hists = d_hists;
+  launch_histogram_batch_planes(p, elem_bytes, flags, c->stream);
+  GHF_HIP(c, hipGetLastError());
+  return GHF_OK;
+}
+
+int ghf_build_codes(ghf_ctx* c, const uint64_t* d_hists, uint32_t n_codes, ghf_code* d_codes, unsigned flags) {
+  if (!c || !d_hists || !d_codes || n_codes == 0 || n_codes > GHF_PLANES_MAX || (flags & ~(unsigned)(GHF_CODE_LIMIT | GHF_EMPTY_OK)))
+    return GHF_E_INVAL;
+  GHF_HIP(c, hipSetDevice(c->device));
+  launch_build_codes(d_hists, n_codes, d_codes, c->d_status, flags, c->stream);
+  GHF_HIP(c, hipGetLastError());
+  for (uint32_t k = 0; k < n_codes; ++k) {  // as ghf_build_code_ex: the tables changed, what was derived from them is stale
+    if (c->plan.code == d_codes + k) c->plan.forget();
+    if (c->prepared.describes(d_codes + k)) c->prepared.forget();
+  }
+  return GHF_OK;
+}
+
+size_t ghf_compress_batch_planes_shared_bound(size_t max_item_bytes, uint32_t elem_bytes) {
+  return planes_elem_ok(elem_bytes) ? ghf_compress_batch_shared_bound(max_item_bytes / elem_bytes) : 0;
+}
+
+// the index covers count * elem_bytes slots of max_item_bytes / elem_bytes symbols (the product fits: count is 32 bits wide)
+static bool planes_index_covers(const ghf_batch_index* ix, uint32_t count, uint32_t elem_bytes, size_t plane_symbols) {
+  return (uint64_t)count * elem_bytes <= 0xFFFFFFFFull && batch_index_covers(ix, count * elem_bytes, plane_symbols);
+}
+
+int ghf_compress_batch_planes_shared(ghf_ctx* c, const uint8_t* const* d_in_ptrs, const uint64_t* d_in_bytes, size_t max_item_bytes,
+                                     uint32_t count, uint32_t elem_bytes, const ghf_code* d_codes, uint8_t* const* d_out_ptrs,
+                                     const uint64_t* d_out_caps, uint64_t* d_out_bytes, const ghf_batch_index* index,
+                                     int* d_item_status) {
+  if (!c) return GHF_E_INVAL;
+  if (!planes_elem_ok(elem_bytes)) return fail(c, GHF_E_INVAL, "ghf_compress_batch_planes_shared: elem_bytes must be 2, 4 or 8");
+  if (!planes_item_ok(max_item_bytes, elem_bytes))
+    return fail(c, GHF_E_INVAL, "ghf_compress_batch_planes_shared: max_item_bytes must be 1 .. GHF_BATCH_MAX_ITEM and a multiple of elem_bytes");
+  if ((uint64_t)count * elem_bytes > 0xFFFFFFFFull) return fail(c, GHF_E_INVAL, "ghf_compress_batch_planes_shared: count * elem_bytes beyond 32 bits");
+  if (index && !planes_index_covers(index, count, elem_bytes, max_item_bytes / elem_bytes))
+    return fail(c, GHF_E_INVAL, "ghf_compress_batch_planes_shared: index does not cover (count * elem_bytes, max_item_bytes / elem_bytes)");
+  if (!d_codes || !aligned16(d_codes)) return fail(c, GHF_E_INVAL, "ghf_compress_batch_planes_shared: d_codes is null or not 16-byte aligned");
+  if (!d_in_ptrs || !d_in_bytes || !d_out_ptrs || !d_out_caps || !d_out_bytes || !d_item_status) return GHF_E_INVAL;
+  if (count == 0) return GHF_OK;
+  GHF_HIP(c, hipSetDevice(c->device));
+  BatchPlanesCompressParams p;
+  p.in_ptrs = d_in_ptrs;
+  p.in_bytes = d_in_bytes;
+  p.max_item_bytes = max_item_bytes;
+  p.codes = d_codes;
+  p.out_ptrs = d_out_ptrs;
+  p.out_caps = d_out_caps;
+  p.out_bytes = d_out_bytes;
+  p.chunk_bit = index ? index->d_chunk_bit : nullptr;
+  p.seg_bit = index ? index->d_seg_bit : nullptr;
+  p.blocks_per_item = index ? index->blocks_per_item : 0;
+  p.segs_per_item = index ? index->segs_per_item : 0;
+  p.item_status = d_item_status;
+  launch_compress_batch_planes_shared(p, count, elem_bytes, c->stream);
+  GHF_HIP(c, hipGetLastError());
+  return GHF_OK;
+}
+
+int ghf_decode_batch_planes_shared(ghf_ctx* c, const uint8_t* const* d_stream_ptrs, const uint64_t* d_stream_bytes,
+                                   const ghf_code* d_codes, const ghf_batch_index* index, const uint64_t* d_n_elems, uint32_t count,
+                                   uint32_t elem_bytes, uint8_t* const* d_out_ptrs, const uint64_t* d_out_caps, uint64_t* d_out_bytes,
+                                   int* d_item_status) {
+  if (!c || !index) return GHF_E_INVAL;
+  if (!planes_elem_ok(elem_bytes)) return fail(c, GHF_E_INVAL, "ghf_decode_batch_planes_shared: elem_bytes must be 2, 4 or 8");
+  if (!planes_index_covers(index, count, elem_bytes, 1))
+    return fail(c, GHF_E_INVAL, "ghf_decode_batch_planes_shared: index does not cover count * elem_bytes slots");
+  if (!d_codes || !aligned16(d_codes)) return fail(c, GHF_E_INVAL, "ghf_decode_batch_planes_shared: d_codes is null or not 16-byte aligned");
+  if (!d_stream_ptrs || !d_stream_bytes || !d_n_elems || !d_out_ptrs || !d_out_caps || !d_out_bytes || !d_item_status)
+    return GHF_E_INVAL;
+  if (count == 0) return GHF_OK;
+  GHF_HIP(c, hipSetDevice(c->device));
+  BatchPlanesDecodeParams p;
+  p.stream_ptrs = d_stream_ptrs;
+  p.stream_bytes = d_stream_bytes;
+  p.codes = d_codes;
+  p.chunk_bit = index->d_chunk_bit;
+  p.seg_bit = index->d_seg_bit;
+  p.blocks_per_item = index->blocks_per_item;
+  p.segs_per_item = index->segs_per_item;
+  p.max_plane_symbols = index->max_item_bytes;
+  p.n_elems = d_n_elems;
+  p.out_ptrs = d_out_ptrs;
+  p.out_caps = d_out_caps;
+  p.out_bytes = d_out_bytes;
+  p.item_status = d_item_status;
+  launch_decode_batch_planes_shared(p, count, elem_bytes, c->stream);
+  GHF_HIP(c, hipGetLastError());
+  return GHF_OK;
+}
+
+int ghf_decode_bodies_batch_planes_shared(ghf_ctx* c, const uint8_t* const* d_stream_ptrs, const uint64_t* d_stream_bytes,
+                                          const ghf_code* d_codes, uint32_t count, uint32_t elem_bytes, uint8_t* const* d_out_ptrs,
+                                          const uint64_t* d_out_caps, uint64_t* d_out_bytes, int* d_item_status) {
+  if (!c || !d_stream_ptrs || !d_stream_bytes || !d_out_bytes || !d_item_status) return GHF_E_INVAL;
+  if (!planes_elem_ok(elem_bytes)) return fail(c, GHF_E_INVAL, "ghf_decode_bodies_batch_planes_shared: elem_bytes must be 2, 4 or 8");
+  if (d_out_ptrs && !d_out_caps) return fail(c, GHF_E_INVAL, "ghf_decode_bodies_batch_planes_shared: d_out_ptrs without d_out_caps");
+  if (!d_codes || !aligned16(d_codes))
+    return fail(c, GHF_E_INVAL, "ghf_decode_bodies_batch_planes_shared: d_codes is null or not 16-byte aligned");
+  if (count == 0) return GHF_OK;
+  GHF_HIP(c, hipSetDevice(c->device));
+  BatchPlanesBodiesParams p;
+  p.stream_ptrs = d_stream_ptrs;
+  p.stream_bytes = d_stream_bytes;
+  p.max_stream_bytes = ghf_compress_batch_shared_bound(GHF_BATCH_MAX_ITEM);
+  p.codes = d_codes;
+  p.out_ptrs = d_out_ptrs;
+  p.out_caps = d_out_caps;
+  p.out_bytes = d_out_bytes;
+  p.item_status = d_item_status;
+  p.stats = c->images_stats;
+  launch_decode_bodies_batch_planes_shared(p, count, elem_bytes, c->stream);
+  GHF_HIP(c, hipGetLastError());
+  return GHF_OK;
+}
+
 // ---------------------------------------------------------------------------------------------- decode
 static inline uint32_t be32(const uint8_t* p) {
   return ((uint32_t)p[0] << 24) | ((uint32_t)p[1] << 16) | ((uint32_t)p[2] << 8) | (uint32_t)p[3];

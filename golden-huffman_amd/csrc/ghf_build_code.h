@@ -299,6 +299,11 @@ __device__ __forceinline__ void code_sync() {
   else wave_sync();
 }
 
+struct HistCounts {  // the counts as K1 leaves them: u64[257] in global memory (k_build_code, k_build_codes)
+  const unsigned long long* __restrict__ hist;
+  __device__ __forceinline__ long long operator()(int s) const { return (long long)hist[s]; }
+};
+
 // The body.  counts(s) = the count of symbol s (0..256; the end mark's is 1), as a long long.  Failures (GHF_E_EMPTY,
 // GHF_E_CODELEN) are latched at *status -- the context's status word, or a word of the caller's own -- and end the body;
 // *out is then not (completely) written.  s_ndata: one LDS int.

@@ -271,6 +271,54 @@ struct BatchSharedBodiesParams {
   uint64_t* stats;            // may be null: [0] += rounds, [1] += passes of every item that reached its body
 };
 
+// ---- shared-code batches of byte planes (ghf_batch_planes.hip): items of elements of elem_bytes = E bytes, one code per
+// byte plane; slot j = i * E + p is plane p of item i.  Every array is device memory
+struct BatchPlanesHistParams {
+  const uint8_t* const* in_ptrs;
+  const uint64_t* in_bytes;
+  uint64_t max_item_bytes;
+  uint32_t count;
+  uint64_t* hists;  // [E][GHF_NSYM]; all zero when the kernel starts
+};
+struct BatchPlanesCompressParams {
+  const uint8_t* const* in_ptrs;  // [count]
+  const uint64_t* in_bytes;
+  uint64_t max_item_bytes;        // a multiple of E
+  const ghf_code* codes;          // [E], never null
+  uint8_t* const* out_ptrs;       // [count * E], as are the four below
+  const uint64_t* out_caps;
+  uint64_t* out_bytes;
+  uint64_t* chunk_bit;            // side-car slices per slot (may both be null)
+  uint32_t* seg_bit;
+  uint64_t blocks_per_item, segs_per_item;
+  int* item_status;
+};
+struct BatchPlanesDecodeParams {
+  const uint8_t* const* stream_ptrs;  // [count * E] the bodies
+  const uint64_t* stream_bytes;
+  const ghf_code* codes;              // [E]
+  const uint64_t* chunk_bit;          // slices per slot
+  const uint32_t* seg_bit;
+  uint64_t blocks_per_item, segs_per_item;
+  uint64_t max_plane_symbols;         // what a slice of the index covers
+  const uint64_t* n_elems;            // [count], as are the four below
+  uint8_t* const* out_ptrs;
+  const uint64_t* out_caps;           // bytes
+  uint64_t* out_bytes;
+  int* item_status;
+};
+struct BatchPlanesBodiesParams {
+  const uint8_t* const* stream_ptrs;  // [count * E] the bodies
+  const uint64_t* stream_bytes;
+  uint64_t max_stream_bytes;          // as BatchSharedBodiesParams
+  const ghf_code* codes;              // [E]
+  uint8_t* const* out_ptrs;           // [count]; null: sizes only (out_caps is ignored)
+  const uint64_t* out_caps;           // bytes
+  uint64_t* out_bytes;
+  int* item_status;
+  uint64_t* stats;                    // may be null: [0] += rounds, [1] += passes of every plane that reached its body
+};
+
 // K6: side-car reconstruction for foreign streams
 enum SyncKind : uint32_t {  // what SyncParams::no_eof carries
   kSyncCrs2 = 0,   // a whole .crs2: ends with the end mark
@@ -351,6 +399,14 @@ void launch_histogram_batch(const BatchHistParams& p, uint32_t flags, hipStream_
 void launch_compress_batch_shared(const BatchSharedCompressParams& p, uint32_t count, hipStream_t s);  // one launch, grid = count
 void launch_decode_batch_shared(const BatchSharedDecodeParams& p, uint32_t count, hipStream_t s);
 void launch_decode_bodies_batch_shared(const BatchSharedBodiesParams& p, uint32_t count, hipStream_t s);  // one launch; p.out_ptrs null: sizes only
+// d_hists[k][256] <- 1 and, under GHF_HIST_COVER_ALL, every count of 0 <- 1, for k < n_hists (behind the counting kernel)
+void launch_histogram_batch_finish(uint64_t* d_hists, uint32_t n_hists, uint32_t flags, hipStream_t s);
+// ghf_batch_planes.hip: elem_bytes is 2, 4 or 8
+void launch_histogram_batch_planes(const BatchPlanesHistParams& p, uint32_t elem_bytes, uint32_t flags, hipStream_t s);  // zeroes, counts, finishes
+void launch_build_codes(const uint64_t* d_hists, uint32_t n_codes, ghf_code* d_codes, int* d_status, uint32_t flags, hipStream_t s);
+void launch_compress_batch_planes_shared(const BatchPlanesCompressParams& p, uint32_t count, uint32_t elem_bytes, hipStream_t s);  // grid = count * E
+void launch_decode_batch_planes_shared(const BatchPlanesDecodeParams& p, uint32_t count, uint32_t elem_bytes, hipStream_t s);      // grid = count
+void launch_decode_bodies_batch_planes_shared(const BatchPlanesBodiesParams& p, uint32_t count, uint32_t elem_bytes, hipStream_t s);
 // ghf_planes.hip: byte planes of elements of 2, 4 or 8 bytes (n_elems > 0; every pointer and plane_stride 16-byte aligned)
 void launch_planes_split(const uint8_t* d_in, uint64_t n_elems, uint32_t elem_bytes, uint8_t* d_planes, uint64_t plane_stride,
                          hipStream_t s);

@@ -214,10 +214,6 @@ void launch_histogram(const uint8_t* d_in, uint64_t n, uint32_t chunk, uint32_t 
                      add ? 1u : 0u);
 }
 
-struct HistCounts {  // the counts as K1 leaves them: u64[257] in global memory
-  const unsigned long long* __restrict__ hist;
-  __device__ __forceinline__ long long operator()(int s) const { return (long long)hist[s]; }
-};
 template <bool LIMIT>
 __global__ __launch_bounds__(64) void k_build_code(const unsigned long long* __restrict__ hist, ghf_code* __restrict__ out,
                                                    int* __restrict__ status, uint32_t empty_ok) {

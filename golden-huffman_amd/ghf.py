@@ -141,6 +141,8 @@ EXPORTS = [
     "ghf_histogram_batch", "ghf_compress_batch_shared_bound", "ghf_compress_batch_shared", "ghf_decode_batch_shared",
     "ghf_decode_bodies_batch_shared",
     "ghf_planes_slot_bytes", "ghf_planes_split", "ghf_planes_merge", "ghf_compress_planes", "ghf_decode_planes",
+    "ghf_histogram_batch_planes", "ghf_build_codes", "ghf_compress_batch_planes_shared_bound",
+    "ghf_compress_batch_planes_shared", "ghf_decode_batch_planes_shared", "ghf_decode_bodies_batch_planes_shared",
 ]
 COMM_ID_BYTES = 128
 
@@ -255,6 +257,14 @@ def lib():
     L.ghf_planes_merge.argtypes = [vp, vp, sz, sz, C.c_uint32, vp]
     L.ghf_compress_planes.argtypes = [vp, vp, sz, C.c_uint32, vp, sz, vp, vp, C.POINTER(Index)]
     L.ghf_decode_planes.argtypes = [vp, C.POINTER(vp), C.POINTER(sz), vp, C.POINTER(Index), sz, C.c_uint32, vp, sz, vp]
+    u32 = C.c_uint32
+    L.ghf_histogram_batch_planes.argtypes = [vp, vp, vp, sz, u32, u32, C.c_uint, vp]
+    L.ghf_build_codes.argtypes = [vp, vp, u32, vp, C.c_uint]
+    L.ghf_compress_batch_planes_shared_bound.argtypes = [sz, u32]
+    L.ghf_compress_batch_planes_shared_bound.restype = sz
+    L.ghf_compress_batch_planes_shared.argtypes = [vp, vp, vp, sz, u32, u32, vp, vp, vp, vp, C.POINTER(BatchIndex), vp]
+    L.ghf_decode_batch_planes_shared.argtypes = [vp, vp, vp, vp, C.POINTER(BatchIndex), vp, u32, u32, vp, vp, vp, vp]
+    L.ghf_decode_bodies_batch_planes_shared.argtypes = [vp, vp, vp, vp, u32, u32, vp, vp, vp, vp]
     _lib = L
     return L
 
@@ -279,6 +289,11 @@ def compress_batch_bound(max_item_bytes):
 def compress_batch_shared_bound(max_item_bytes):
     """capacity that suffices for the BODY of every item of a shared-code batch, under any code of <= 32 bits"""
     return int(lib().ghf_compress_batch_shared_bound(max_item_bytes))
+
+
+def compress_batch_planes_shared_bound(max_item_bytes, elem_bytes):
+    """capacity that suffices for every slot (item, plane) of a shared-code batch of elements of elem_bytes bytes"""
+    return int(lib().ghf_compress_batch_planes_shared_bound(max_item_bytes, elem_bytes))
 
 
 def planes_slot_bytes(n_elems):
@@ -774,6 +789,114 @@ class Context:
         {rounds, passes} to; None: off"""
         self._chk(self.L.ghf_decode_images_batch_stats(self.h, None if d_stats is None else d_stats.data_ptr()),
                   "ghf_decode_images_batch_stats")
+
+    # ---- shared-code batches of typed elements: one code per byte plane; slot j = i * elem_bytes + p ----
+    def histogram_batch_planes(self, items, elem_bytes, sizes=None, max_item_bytes=None, flags=0, out=None):
+        """the byte counts of every byte plane of all items: an int64[elem_bytes, 257] CUDA tensor, ready for build_codes.
+        items / sizes (in bytes) as in compress_batch; flags: HIST_COVER_ALL.  No host synchronisation."""
+        ptrs, sizes = self._item_arrays(items, sizes)
+        if max_item_bytes is None:
+            max_item_bytes = -(-max(max(sizes, default=1), 1) // elem_bytes) * elem_bytes
+        hists = self.torch.empty((elem_bytes, NSYM), dtype=self.torch.int64, device=self.device) if out is None else out
+        in_ptrs, in_bytes = self._i64(ptrs), self._i64(sizes)
+        self._chk(self.L.ghf_histogram_batch_planes(self.h, in_ptrs.data_ptr(), in_bytes.data_ptr(), max_item_bytes, len(sizes),
+                                                    elem_bytes, flags, hists.data_ptr()), "ghf_histogram_batch_planes")
+        return hists
+
+    def build_codes(self, d_hists, d_codes=None, flags=0):
+        """d_hists: int64[n, 257] -> uint8[n, sizeof(Code)]: n exact code builds in one launch"""
+        n = int(d_hists.numel()) // NSYM
+        if d_codes is None:
+            d_codes = self.torch.zeros((n, C.sizeof(Code)), dtype=self.torch.uint8, device=self.device)
+        self._chk(self.L.ghf_build_codes(self.h, d_hists.data_ptr(), n, d_codes.data_ptr(), flags), "ghf_build_codes")
+        return d_codes
+
+    def compress_batch_planes_shared(self, items, d_codes, elem_bytes, sizes=None, max_item_bytes=None, d_out=None, out_stride=None,
+                                     index=None):
+        """compress_batch_shared per byte plane: slot i * elem_bytes + p holds the BODY of plane p of item i under d_codes[p],
+        at d_out[slot * out_stride ..).  index: None or batch_index_alloc(count * elem_bytes, max_item_bytes // elem_bytes).
+        -> dict(out, out_stride, out_bytes int64[slots], status int32[slots], codes, in_ptrs, in_bytes, out_ptrs, out_caps,
+                count, elem_bytes, max_item_bytes, n_elems int64[count])"""
+        t = self.torch
+        ptrs, sizes = self._item_arrays(items, sizes)
+        count = len(sizes)
+        slots = count * elem_bytes
+        if max_item_bytes is None:
+            max_item_bytes = -(-max(max(sizes, default=1), 1) // elem_bytes) * elem_bytes
+        if out_stride is None:
+            out_stride = compress_batch_planes_shared_bound(max_item_bytes, elem_bytes)
+        if d_out is None:
+            d_out = t.empty(max(slots * out_stride, 16), dtype=t.uint8, device=self.device)
+        in_ptrs, in_bytes = self._i64(ptrs), self._i64(sizes)
+        out_ptrs = d_out.data_ptr() + t.arange(slots, dtype=t.int64, device=self.device) * out_stride
+        out_caps = t.full((max(slots, 1),), out_stride, dtype=t.int64, device=self.device)
+        out_bytes = t.zeros(max(slots, 1), dtype=t.int64, device=self.device)
+        status = t.full((max(slots, 1),), -1, dtype=t.int32, device=self.device)
+        self._chk(
+            self.L.ghf_compress_batch_planes_shared(self.h, in_ptrs.data_ptr(), in_bytes.data_ptr(), max_item_bytes, count, elem_bytes,
+                                                    d_codes.data_ptr(), out_ptrs.data_ptr(), out_caps.data_ptr(), out_bytes.data_ptr(),
+                                                    None if index is None else C.byref(index), status.data_ptr()),
+            "ghf_compress_batch_planes_shared")
+        return {"out": d_out, "out_stride": out_stride, "out_bytes": out_bytes[:slots], "status": status[:slots], "codes": d_codes,
+                "in_ptrs": in_ptrs, "in_bytes": in_bytes, "out_ptrs": out_ptrs, "out_caps": out_caps, "count": count,
+                "elem_bytes": elem_bytes, "max_item_bytes": max_item_bytes, "n_elems": in_bytes // elem_bytes, "keep": items}
+
+    def _planes_out(self, count, out_stride, d_out):
+        t = self.torch
+        if d_out is None:
+            d_out = t.empty(max(count * out_stride, 16), dtype=t.uint8, device=self.device)
+        out_ptrs = d_out.data_ptr() + t.arange(count, dtype=t.int64, device=self.device) * out_stride
+        return d_out, out_ptrs, t.full((max(count, 1),), out_stride, dtype=t.int64, device=self.device)
+
+    def decode_batch_planes_shared(self, stream_ptrs, stream_bytes, d_codes, index, n_elems, elem_bytes, d_out=None, out_stride=None,
+                                   out_ptrs=None, out_caps=None):
+        """the way back with the live side-car: stream_ptrs / stream_bytes int64[count * elem_bytes] (out_ptrs and out_bytes
+        of compress_batch_planes_shared), n_elems int64[count].  Item i is decoded to d_out[i * out_stride ..) unless
+        out_ptrs / out_caps (bytes) say otherwise.  -> dict(out, out_stride, out_bytes int64[count], status int32[count])"""
+        t = self.torch
+        count = int(n_elems.numel())
+        if out_ptrs is None:
+            if out_stride is None:
+                out_stride = (int(index.max_item_bytes) * elem_bytes + 15) & ~15
+            d_out, out_ptrs, out_caps = self._planes_out(count, out_stride, d_out)
+        out_bytes = t.zeros(max(count, 1), dtype=t.int64, device=self.device)
+        status = t.full((max(count, 1),), -1, dtype=t.int32, device=self.device)
+        self._chk(
+            self.L.ghf_decode_batch_planes_shared(self.h, stream_ptrs.data_ptr(), stream_bytes.data_ptr(), d_codes.data_ptr(),
+                                                  C.byref(index), n_elems.data_ptr(), count, elem_bytes, out_ptrs.data_ptr(),
+                                                  out_caps.data_ptr(), out_bytes.data_ptr(), status.data_ptr()),
+            "ghf_decode_batch_planes_shared")
+        return {"out": d_out, "out_stride": out_stride, "out_bytes": out_bytes[:count], "status": status[:count],
+                "out_ptrs": out_ptrs, "out_caps": out_caps}
+
+    def decode_bodies_batch_planes_shared(self, stream_ptrs, stream_bytes, d_codes, elem_bytes, out=None, caps=None):
+        """the way back from nothing but the bytes: stream_ptrs / stream_bytes int64[count * elem_bytes].
+        out=None: the sizes pass -> dict(out_bytes int64[count] (bytes), status int32[count]).
+        Otherwise the decode pass, with out / caps (bytes per item) as in decode_images_batch."""
+        t = self.torch
+        count = int(stream_bytes.numel()) // elem_bytes
+        out_bytes = t.zeros(max(count, 1), dtype=t.int64, device=self.device)
+        status = t.full((max(count, 1),), -1, dtype=t.int32, device=self.device)
+        res = {"out_bytes": out_bytes[:count], "status": status[:count]}
+        out_ptrs = out_caps = None
+        if out is not None:
+            if caps is None:
+                raise ValueError("decode_bodies_batch_planes_shared: the decode pass needs caps (e.g. the out_bytes of the sizes pass)")
+            if out is True:
+                out_stride = (int(caps.max().item()) + 15) & ~15 if count else 16
+                out = t.empty(max(count * out_stride, 16), dtype=t.uint8, device=self.device)
+            else:
+                out_stride = int(out.numel()) // max(count, 1)
+            out_ptrs = out.data_ptr() + t.arange(count, dtype=t.int64, device=self.device) * out_stride
+            out_caps = t.clamp(caps.to(t.int64), max=out_stride).contiguous()
+            res.update(out=out, out_stride=out_stride, out_ptrs=out_ptrs, out_caps=out_caps)
+        self._chk(
+            self.L.ghf_decode_bodies_batch_planes_shared(self.h, stream_ptrs.data_ptr(), stream_bytes.data_ptr(), d_codes.data_ptr(),
+                                                         count, elem_bytes, None if out_ptrs is None else out_ptrs.data_ptr(),
+                                                         None if out_caps is None else out_caps.data_ptr(), out_bytes.data_ptr(),
+                                                         status.data_ptr()),
+            "ghf_decode_bodies_batch_planes_shared")
+        return res
 
     # ---- byte planes: elements of 2, 4 or 8 bytes, one ordinary .crs2 image per byte position ---------
     planes_slot_bytes = staticmethod(planes_slot_bytes)

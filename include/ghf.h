@@ -524,6 +524,89 @@ int ghf_decode_planes(ghf_ctx* ctx, const uint8_t* const* h_stream_ptrs, const s
                       const ghf_code* d_codes, const ghf_index* indexes, size_t n_elems, uint32_t elem_bytes, uint8_t* d_out,
                       size_t cap, uint64_t* d_out_bytes);
 
+/* ---- shared-code batches of typed elements: one code per byte plane for many small items -------------
+ * No reference counterpart (the reference compresses one flat run of bytes per process, include/compressor.h:62-73, and
+ * reads one back, include/compressor.h:87-92).  The shared-code batch calls put one code under thousands of small flat
+ * items; the byte-plane calls give the byte positions of ONE large buffer a code each.  These calls do both: an item is a
+ * run of elements of elem_bytes = E (2, 4 or 8) bytes, plane p of it is the bytes in[p], in[p + E], in[p + 2 E] ..., and
+ * ONE code per plane lies under the whole batch.  The planes are never materialised.  The .crs2 format does not change:
+ * "slot" j = i * E + p names (item i, plane p); its output is the BODY that ghf_compress_batch_shared writes for the
+ * plane's bytes under d_codes[p], so ghf_write_header(d_codes + p) || body(j) is a standalone .crs2 image of the plane that
+ * the reference's decoders, ghf_decode and ghf_decode_images_batch read.
+ *
+ * Conventions are those of the shared-code batch calls: every array is DEVICE memory; asynchronous on the context's
+ * stream, never synchronises; failures are per slot or per item and never latch the context's status word (ghf_build_codes
+ * latches as ghf_build_code_ex does); the context's caches are left alone (ghf_build_codes forgets what was derived from
+ * the codes it overwrites, as ghf_build_code_ex does); count == 0 queues nothing.  Call-level errors
+ * (returned at once, nothing queued, checked before anything touches HIP): a null context or array, an elem_bytes other
+ * than 2, 4 or 8, max_item_bytes == 0, > GHF_BATCH_MAX_ITEM or not a multiple of elem_bytes, an index whose geometry does
+ * not cover (count * elem_bytes, max_item_bytes / elem_bytes), unknown flags, null or not 16-byte aligned d_codes:
+ * GHF_E_INVAL. */
+
+/* No reference counterpart (include/compressor.h:62-73 counts one flat run; 87-92 reads one back).  One pass over the
+ * items: d_hists[p] (device u64[elem_bytes][257], overwritten) <- what ghf_histogram_batch gives for the items' plane-p
+ * bytes, slot 256 = 1, GHF_HIST_COVER_ALL honoured per plane.  Items of 0 bytes, with a null pointer, of more than
+ * max_item_bytes or whose size is not a multiple of elem_bytes contribute nothing (ghf_compress_batch_planes_shared
+ * reports them). */
+int ghf_histogram_batch_planes(ghf_ctx* ctx, const uint8_t* const* d_in_ptrs, const uint64_t* d_in_bytes,
+                               size_t max_item_bytes, uint32_t count, uint32_t elem_bytes, unsigned flags,
+                               uint64_t* d_hists /* [elem_bytes][257] */);
+
+/* No reference counterpart (include/compressor.h:62-73 builds one code per file; 87-92 reads one).  n_codes (1 ..
+ * GHF_PLANES_MAX) exact code builds in ONE launch: d_codes[k] is bit-identical to what ghf_build_code_ex(d_hists + 257 k,
+ * d_codes + k, flags) leaves, and device failures latch exactly as there.  As there too, and unlike the other calls of
+ * this group, it touches the context's caches: what the context derived from the former contents of one of d_codes (the
+ * plan or the prepared tables of a ghf_compress / ghf_decode under that code) is forgotten, since the tables change.
+ * n_codes == 0 or > GHF_PLANES_MAX: GHF_E_INVAL. */
+int ghf_build_codes(ghf_ctx* ctx, const uint64_t* d_hists /* [n_codes][257] */, uint32_t n_codes,
+                    ghf_code* d_codes /* [n_codes] */, unsigned flags);
+
+/* No reference counterpart (include/compressor.h:62-73, 87-92).  Host only: ghf_compress_batch_shared_bound(max_item_bytes
+ * / elem_bytes), a capacity that suffices for every slot under any code of <= 32 bits; 0 for another elem_bytes. */
+size_t ghf_compress_batch_planes_shared_bound(size_t max_item_bytes, uint32_t elem_bytes);
+
+/* No reference counterpart (generalises include/compressor.h:62-73; 87-92 is the way back).  Item i = d_in_ptrs[i][0 ..
+ * d_in_bytes[i]) (no alignment needed); slot j = i * elem_bytes + p receives the body of plane p under d_codes[p]
+ * (device ghf_code[elem_bytes], 16-byte aligned) at d_out_ptrs[j] (16-byte aligned), d_out_bytes[j] <- its size: byte for
+ * byte what ghf_compress_batch_shared writes for the plane's bytes.  Nothing at or beyond d_out_caps[j] is written, and a
+ * refused slot writes nothing.  index (optional): a ghf_batch_index allocated for count * elem_bytes items of
+ * max_item_bytes / elem_bytes; slice j receives the side-car ghf_compress_batch_shared would fill for that plane.
+ * d_item_status[j] <- as ghf_compress_batch_shared (GHF_E_EMPTY, GHF_E_INVAL, GHF_E_CAP, GHF_E_NOCODE per slot), and
+ *   GHF_E_INVAL   on all elem_bytes slots of an item whose size is not a multiple of elem_bytes
+ *   GHF_E_FORMAT  only on the slots of a plane whose code is not a complete prefix code */
+int ghf_compress_batch_planes_shared(ghf_ctx* ctx, const uint8_t* const* d_in_ptrs, const uint64_t* d_in_bytes,
+                                     size_t max_item_bytes, uint32_t count, uint32_t elem_bytes, const ghf_code* d_codes,
+                                     uint8_t* const* d_out_ptrs, const uint64_t* d_out_caps, uint64_t* d_out_bytes,
+                                     const ghf_batch_index* index /* optional */, int* d_item_status /* [count * elem_bytes] */);
+
+/* No reference counterpart (include/compressor.h:62-73 is the way there; generalises 87-92).  The bodies of
+ * ghf_compress_batch_planes_shared with their live side-car: slot j = the body at d_stream_ptrs[j] (16-byte aligned),
+ * d_stream_bytes[j] of it, and slice j of `index`.  Output and status are PER ITEM: byte p of element k of item i goes to
+ * d_out_ptrs[i][k * elem_bytes + p] (no alignment needed), d_out_bytes[i] <- d_n_elems[i] * elem_bytes; d_out_caps[i] is in
+ * bytes.  Every plane passes the segment-end and end-mark checks of ghf_decode_batch_shared.  d_item_status[i] <-
+ * GHF_E_EMPTY (0 elements), GHF_E_INVAL (more elements than a slice of the index covers; a null or misaligned stream
+ * pointer of any plane; a null output pointer), GHF_E_CAP, GHF_E_CORRUPT; GHF_E_FORMAT on EVERY item if any of the
+ * elem_bytes codes is not a complete prefix code, and nothing is written. */
+int ghf_decode_batch_planes_shared(ghf_ctx* ctx, const uint8_t* const* d_stream_ptrs, const uint64_t* d_stream_bytes,
+                                   const ghf_code* d_codes, const ghf_batch_index* index, const uint64_t* d_n_elems,
+                                   uint32_t count, uint32_t elem_bytes, uint8_t* const* d_out_ptrs,
+                                   const uint64_t* d_out_caps, uint64_t* d_out_bytes, int* d_item_status /* [count] */);
+
+/* No reference counterpart (include/compressor.h:62-73 is the way there; generalises 87-92).  ghf_decode_bodies_batch_shared
+ * for the slots of ghf_compress_batch_planes_shared: nothing but the bytes, no side-car, no sizes.  d_out_ptrs == NULL
+ * (then d_out_caps is ignored): sizes only.  Each plane of item i is decoded from bit 0 to its first end mark and written
+ * as in ghf_decode_batch_planes_shared; d_out_bytes[i] <- n_i * elem_bytes.  d_item_status[i] <-
+ *   GHF_E_INVAL   as ghf_decode_bodies_batch_shared, for any plane of the item
+ *   GHF_E_CORRUPT a plane's stream ends before a whole end mark; the planes decode to different numbers of symbols
+ *   GHF_E_CAP     n_i * elem_bytes > d_out_caps[i]: a plane's cap is d_out_caps[i] / elem_bytes symbols, checked before any
+ *                 store of the round that would cross it; nothing at or beyond d_out_caps[i] is written
+ *   GHF_E_FORMAT  (every item) one of the codes is not a complete prefix code
+ * The words named by ghf_decode_images_batch_stats receive this call's rounds and passes too. */
+int ghf_decode_bodies_batch_planes_shared(ghf_ctx* ctx, const uint8_t* const* d_stream_ptrs, const uint64_t* d_stream_bytes,
+                                          const ghf_code* d_codes, uint32_t count, uint32_t elem_bytes,
+                                          uint8_t* const* d_out_ptrs, const uint64_t* d_out_caps, uint64_t* d_out_bytes,
+                                          int* d_item_status /* [count] */);
+
 /* Multi-GPU decode of a stream that has no side-car ("per-rank self-sync + one all-gather of symbol
  * counts"; the reference's decoders, canonical_huff_encoder.cc:377-568, are single-stream).  The caller cuts the body
  * at byte positions; a rank's piece is its own bytes followed by >= 8 bytes of look-ahead from the next piece (zeros
