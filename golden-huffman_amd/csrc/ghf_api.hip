@@ -808,6 +808,81 @@ int ghf_decode_bodies_batch_planes_shared(ghf_ctx* c, const uint8_t* const* d_st
   return GHF_OK;
 }
 
+// ---------------------------------------------------------------------------------------------- stored shared-code bodies
+size_t ghf_batch_seek_bytes(size_t n_symbols) { return (size_t)batch_seek_bytes_for(n_symbols); }
+size_t ghf_batch_seek_bound(size_t max_item_bytes) { return (ghf_batch_seek_bytes(max_item_bytes) + 15) & ~(size_t)15; }
+
+int ghf_batch_seek_pack(ghf_ctx* c, const ghf_batch_index* index, const uint64_t* d_in_bytes, uint32_t count, uint32_t elem_bytes,
+                        uint8_t* const* d_rec_ptrs, const uint64_t* d_rec_caps, uint64_t* d_rec_bytes, int* d_slot_status) {
+  if (!c || !index) return GHF_E_INVAL;
+  if (elem_bytes != 1 && !planes_elem_ok(elem_bytes)) return fail(c, GHF_E_INVAL, "ghf_batch_seek_pack: elem_bytes must be 1, 2, 4 or 8");
+  if (!planes_index_covers(index, count, elem_bytes, 1))
+    return fail(c, GHF_E_INVAL, "ghf_batch_seek_pack: index does not cover count * elem_bytes slots (use ghf_batch_index_alloc)");
+  if (!d_in_bytes || !d_rec_ptrs || !d_rec_caps || !d_rec_bytes || !d_slot_status) return GHF_E_INVAL;
+  if (count == 0) return GHF_OK;
+  GHF_HIP(c, hipSetDevice(c->device));
+  BatchSeekPackParams p;
+  p.chunk_bit = index->d_chunk_bit;
+  p.seg_bit = index->d_seg_bit;
+  p.blocks_per_item = index->blocks_per_item;
+  p.segs_per_item = index->segs_per_item;
+  p.max_slice_symbols = index->max_item_bytes;
+  p.in_bytes = d_in_bytes;
+  p.elem_bytes = elem_bytes;
+  p.rec_ptrs = d_rec_ptrs;
+  p.rec_caps = d_rec_caps;
+  p.rec_bytes = d_rec_bytes;
+  p.slot_status = d_slot_status;
+  launch_batch_seek_pack(p, count * elem_bytes, c->stream);
+  GHF_HIP(c, hipGetLastError());
+  return GHF_OK;
+}
+
+// the two decoders of stored bodies: elem_bytes = 1 is the flat call
+static int decode_bodies_batch_seek(ghf_ctx* c, const char* who, const uint8_t* const* d_stream_ptrs, const uint64_t* d_stream_bytes,
+                                    const uint8_t* const* d_rec_ptrs, const uint64_t* d_rec_bytes, const ghf_code* d_codes, uint32_t count,
+                                    uint32_t elem_bytes, uint8_t* const* d_out_ptrs, const uint64_t* d_out_caps, uint64_t* d_out_bytes,
+                                    int* d_item_status) {
+  if (!c || !d_stream_ptrs || !d_stream_bytes || !d_rec_ptrs || !d_rec_bytes || !d_out_bytes || !d_item_status) return GHF_E_INVAL;
+  if (elem_bytes != 1 && !planes_elem_ok(elem_bytes)) return fail(c, GHF_E_INVAL, (std::string(who) + ": elem_bytes must be 2, 4 or 8").c_str());
+  if (d_out_ptrs && !d_out_caps) return fail(c, GHF_E_INVAL, (std::string(who) + ": d_out_ptrs without d_out_caps").c_str());
+  if (!d_codes || !aligned16(d_codes)) return fail(c, GHF_E_INVAL, (std::string(who) + ": the code array is null or not 16-byte aligned").c_str());
+  if (count == 0) return GHF_OK;
+  GHF_HIP(c, hipSetDevice(c->device));
+  BatchSeekDecodeParams p;
+  p.stream_ptrs = d_stream_ptrs;
+  p.stream_bytes = d_stream_bytes;
+  p.rec_ptrs = d_rec_ptrs;
+  p.rec_bytes = d_rec_bytes;
+  p.max_stream_bytes = ghf_compress_batch_shared_bound(GHF_BATCH_MAX_ITEM);
+  p.codes = d_codes;
+  p.out_ptrs = d_out_ptrs;
+  p.out_caps = d_out_caps;
+  p.out_bytes = d_out_bytes;
+  p.item_status = d_item_status;
+  launch_decode_bodies_batch_seek(p, count, elem_bytes, c->stream);
+  GHF_HIP(c, hipGetLastError());
+  return GHF_OK;
+}
+
+int ghf_decode_bodies_batch_shared_seek(ghf_ctx* c, const uint8_t* const* d_stream_ptrs, const uint64_t* d_stream_bytes,
+                                        const uint8_t* const* d_rec_ptrs, const uint64_t* d_rec_bytes, const ghf_code* d_code,
+                                        uint32_t count, uint8_t* const* d_out_ptrs, const uint64_t* d_out_caps, uint64_t* d_out_bytes,
+                                        int* d_item_status) {
+  return decode_bodies_batch_seek(c, "ghf_decode_bodies_batch_shared_seek", d_stream_ptrs, d_stream_bytes, d_rec_ptrs, d_rec_bytes, d_code,
+                                  count, 1, d_out_ptrs, d_out_caps, d_out_bytes, d_item_status);
+}
+
+int ghf_decode_bodies_batch_planes_shared_seek(ghf_ctx* c, const uint8_t* const* d_stream_ptrs, const uint64_t* d_stream_bytes,
+                                               const uint8_t* const* d_rec_ptrs, const uint64_t* d_rec_bytes, const ghf_code* d_codes,
+                                               uint32_t count, uint32_t elem_bytes, uint8_t* const* d_out_ptrs,
+                                               const uint64_t* d_out_caps, uint64_t* d_out_bytes, int* d_item_status) {
+  if (c && !planes_elem_ok(elem_bytes))
+    return fail(c, GHF_E_INVAL, "ghf_decode_bodies_batch_planes_shared_seek: elem_bytes must be 2, 4 or 8");
+  return decode_bodies_batch_seek(c, "ghf_decode_bodies_batch_planes_shared_seek", d_stream_ptrs, d_stream_bytes, d_rec_ptrs, d_rec_bytes,
+                                  d_codes, count, elem_bytes, d_out_ptrs, d_out_caps, d_out_bytes, d_item_status);
+}
+
 // ---------------------------------------------------------------------------------------------- decode
 static inline uint32_t be32(const uint8_t* p) {
   return ((uint32_t)p[0] << 24) | ((uint32_t)p[1] << 16) | ((uint32_t)p[2] << 8) | (uint32_t)p[3];

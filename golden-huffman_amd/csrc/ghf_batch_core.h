@@ -4,7 +4,9 @@
 // bounded stream reads and the bit cursor of the decoders, the packer of the shared-code kernels
 // (batch_shared_compress_body, over a flat item or one byte plane of it), and the round loops of the decoders: the one
 // that follows a side-car (batch_decode_segments) and the one that finds the code boundaries itself
-// (batch_decode_rounds), each over the way its stage leaves (StoreFlat, StorePlane).
+// (batch_decode_rounds), each over the way its stage leaves (StoreFlat, StorePlane).  Behind them what ghf_batch_seek.hip
+// (stored bodies with a run record each) adds: the decoders' front stated once (batch_code_ok, batch_code_tables) and
+// the round loop that follows a record (batch_decode_runs).
 #ifndef GHF_BATCH_CORE_H_
 #define GHF_BATCH_CORE_H_
 #include "ghf_code_rules.h"
@@ -651,6 +653,144 @@ __device__ __forceinline__ int batch_decode_rounds(const CodeTab& T, uint32_t* s
     }
     carry = R.over[po][kBatchThreads - 1];
     base += kImgRoundBits;
+  }
+}
+
+// ----------------------------------------------------------------------------------------------------------------------
+// the front of the decoders of stored bodies (ghf_batch_seek.hip): the code check and the table
+// fill of k_decode_batch_shared, stated once.  (The kernels above keep their written-out copies: their listings are
+// held, sections 11 and 13.)
+// ----------------------------------------------------------------------------------------------------------------------
+struct CodeVetLds {
+  unsigned long long kraft;
+  int bad;
+};
+// every lane of the workgroup; barriers on both sides are inside.  -> `code` is a complete prefix code of lengths <= 32
+// (ghf_code_rules.h, section 2)
+__device__ __forceinline__ bool batch_code_ok(CodeVetLds& V, const ghf_code* __restrict__ code, int tid) {
+  const int max_len = code->max_len, min_len = code->min_len;
+  __syncthreads();  // the lanes are done with what the call before this one left in V
+  if (tid == 0) {
+    V.kraft = 0;
+    V.bad = len_bounds_ok(min_len, max_len) ? 0 : 1;
+  }
+  __syncthreads();
+  if (len_bounds_ok(min_len, max_len)) {  // (the same in every lane) nothing below trusts a length before this has passed
+    unsigned long long k = 0;
+    if (!code_share_ok(code, min_len, max_len, tid, kBatchThreads, &k)) atomicOr(&V.bad, 1);
+    if (k) atomicAdd(&V.kraft, k);
+  }
+  __syncthreads();
+  return V.bad == 0 && V.kraft == (1ull << 32);
+}
+// the tables of one vetted code; every lane of the workgroup, barriers on both sides are inside
+__device__ __forceinline__ void batch_code_tables(CodeTab& T, const ghf_code* __restrict__ code, int tid, int& lb, int& long_from,
+                                                  int& max_len) {
+  const int min_len = code->min_len;
+  max_len = code->max_len;
+  __syncthreads();  // the lanes are done with the tables of the code before this one
+  if (tid < 36) tab_load_row(T, tid, min_len, max_len, code->first_code, code->start_pos);
+  for (int i = tid; i < GHF_NSYM; i += kBatchThreads) T.symbol[i] = tab_symbol(code->symbol[i]);
+  __syncthreads();
+  lb = max_len < kDecLutBitsMax ? max_len : kDecLutBitsMax;
+  long_from = lb + 1 > min_len ? lb + 1 : min_len;
+  tab_fill_lut(T, min_len, lb, tid, kBatchThreads);
+  __syncthreads();
+}
+
+// ----------------------------------------------------------------------------------------------------------------------
+// the round loop of the decoders that follow a stored run record (k_decode_bodies_batch_shared_seek and its planes form):
+// rounds of 256 runs of 128 symbols, one per lane.  Lane t loads run_bits[r0 + t]; a workgroup scan plus the bits of the
+// rounds before gives the bit its run starts at; the lane decodes its run once, straight into the stage, and must land
+// on the recorded end (behind the last run the end mark must follow, whole).  Every lane of the workgroup calls it with
+// the same arguments; S.t holds the filled tables (a barrier lies behind batch_code_tables).  S.err (zero when the first
+// call starts) is raised on the first round that fails, and that round and the ones behind it are not stored.  Nothing in
+// the record is trusted: run_bits[] is [0, ceil(n / 128)) u16 behind the record's 8 header bytes, which the caller has
+// held against the record's size; no byte outside stream[0 .. stream_bytes) is read (stream_bytes * 8 fits 32 bits, and
+// so does any sum of 8192 run lengths).
+//
+// The stage is linear -- symbol s of the round at byte s -- so that StoreFlat / StorePlane take it as they take the
+// stages above.  A lane's run is 128 consecutive bytes, so lanes lie 32 banks apart and a dword store per four symbols
+// would put the 64 lanes of a wave on two banks; the lane collects 16 symbols in four registers and writes them with one
+// ds_write_b128 instead: an eighth of the stores, each touching four banks.
+// ----------------------------------------------------------------------------------------------------------------------
+constexpr uint32_t kBatchSeekRoundRuns = kBatchThreads;
+constexpr uint32_t kBatchSeekRoundBytes = kBatchSeekRoundRuns * kBatchRunSymbols;  // 32 KiB
+
+template <class Lds, class Store>  // Lds: a CodeTab t, stage[kBatchSeekRoundBytes / 4 + 4], wave_bits[kBatchWaves], an int err
+__device__ __forceinline__ void batch_decode_runs(Lds& S, const uint8_t* stream, uint64_t stream_bytes, const uint8_t* rec, uint32_t n,
+                                                  uint8_t* out, int lb, int long_from, int max_len, const Store& store) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const uint32_t end_bit = (uint32_t)stream_bytes * 8u;
+  const uint32_t nruns = (uint32_t)batch_runs_for(n);
+  const uint16_t* const run_bits = reinterpret_cast<const uint16_t*>(rec + kBatchSeekHeadBytes);
+  uint32_t carry = 0;  // the bits of the rounds before this one
+#pragma unroll 1
+  for (uint32_t r0 = 0; r0 < nruns; r0 += kBatchSeekRoundRuns) {
+    const uint32_t run = r0 + (uint32_t)tid;
+    const uint32_t bits = run < nruns ? (uint32_t)run_bits[run] : 0u;
+    const uint32_t incl = wave_incl_scan_u32(bits);
+    if (lane == 63) S.wave_bits[wave] = incl;
+    __syncthreads();
+    uint32_t before = 0, round_bits = 0;
+#pragma unroll
+    for (int w = 0; w < kBatchWaves; ++w) {
+      const uint32_t t = S.wave_bits[w];
+      before += w < wave ? t : 0u;
+      round_bits += t;
+    }
+    if (run < nruns) {
+      const uint32_t start = carry + before + incl - bits;
+      const uint32_t cnt = n - run * kBatchRunSymbols < kBatchRunSymbols ? n - run * kBatchRunSymbols : kBatchRunSymbols;
+      const bool is_last = run + 1 == nruns;
+      // bounds first: the run lies inside the stream (the end mark behind the last one is held as it is decoded)
+      bool bad = start > end_bit || bits > end_bit - start;
+      if (!bad) {
+        BatchCursor cur;
+        cur.seek(stream, stream_bytes, start);
+        uint32_t used = 0;
+        uint4 q = make_uint4(0, 0, 0, 0);  // the last four words of symbols, oldest first
+        uint4* const mine = reinterpret_cast<uint4*>(&S.stage[tid * (kBatchRunSymbols / 4)]);
+        const uint32_t nwords = (cnt + 3u) >> 2;
+#pragma unroll 1
+        for (uint32_t w = 0; w < nwords && !bad; ++w) {
+          uint32_t word = 0;
+#pragma unroll
+          for (uint32_t k = 0; k < 4; ++k) {
+            if (4u * w + k < cnt) {
+              const uint32_t ent = batch_decode_one(S.t, cur.window(), lb, long_from, max_len);
+              const uint32_t sym = ent & 0x1FFu, len = ent >> 9;
+              if (len == 0 || sym == 256u) bad = true;  // no code starts with these bits, or an end mark among the data
+              used += len;
+              word |= (sym & 0xFFu) << (8u * k);
+              cur.skip(stream, stream_bytes, len);
+            }
+          }
+          q = make_uint4(q.y, q.z, q.w, word);
+          if ((w & 3u) == 3u) mine[w >> 2] = q;
+        }
+        if (!bad && (nwords & 3u)) {  // the run's last, incomplete group of 16
+#pragma unroll 1
+          for (uint32_t w = nwords & 3u; w < 4u; ++w) q = make_uint4(q.y, q.z, q.w, 0u);
+          mine[nwords >> 2] = q;
+        }
+        if (used != bits) bad = true;  // the run does not land on its recorded end
+        if (!bad && is_last) {
+          const uint32_t ent = batch_decode_one(S.t, cur.window(), lb, long_from, max_len);
+          const uint32_t len = ent >> 9;
+          // the end mark is missing behind the last symbol, or the stream ends inside it
+          if (len == 0 || (ent & 0x1FFu) != 256u || len > end_bit - (start + bits)) bad = true;
+        }
+      }
+      if (bad) S.err = 1;
+    }
+    __syncthreads();
+    if (S.err) return;  // (the same in every lane)
+    const uint32_t rb = r0 * kBatchRunSymbols;
+    const uint32_t rbytes = n - rb < kBatchSeekRoundBytes ? n - rb : kBatchSeekRoundBytes;
+    store(out, rb, S.stage, rbytes, tid);
+    __syncthreads();
+    carry += round_bits;
   }
 }
 

@@ -319,6 +319,44 @@ struct BatchPlanesBodiesParams {
   uint64_t* stats;                    // may be null: [0] += rounds, [1] += passes of every plane that reached its body
 };
 
+// ---- stored shared-code bodies (ghf_batch_seek.hip): the run record, the persistent form of one
+// slice of a ghf_batch_index.  u32 magic, u32 n_symbols, u16 run_bits[ceil(n_symbols / 128)], zeros up to a multiple of 8;
+// all little-endian.  A run never straddles a side-car block: 32 runs of two segments each make one.
+constexpr uint32_t kBatchSeekMagic = 0x31524247u;  // "GBR1"
+constexpr uint32_t kBatchRunSymbols = 128;
+constexpr uint32_t kBatchRunSegs = kBatchRunSymbols / kSegSymbols;         // 2
+constexpr uint32_t kBatchRunsPerBlock = kBlockSymbols / kBatchRunSymbols;  // 32
+constexpr uint32_t kBatchSeekHeadBytes = 8;
+__host__ __device__ constexpr inline uint64_t batch_runs_for(uint64_t n) { return (n + kBatchRunSymbols - 1) / kBatchRunSymbols; }
+__host__ __device__ constexpr inline uint64_t batch_seek_bytes_for(uint64_t n) {
+  return (kBatchSeekHeadBytes + 2 * batch_runs_for(n) + 7) & ~7ull;
+}
+struct BatchSeekPackParams {
+  const uint64_t* chunk_bit;  // the side-car slices, slot j at j * blocks_per_item / j * segs_per_item
+  const uint32_t* seg_bit;
+  uint64_t blocks_per_item, segs_per_item;
+  uint64_t max_slice_symbols;  // what a slice covers
+  const uint64_t* in_bytes;    // [count]: slot j holds in_bytes[j / elem_bytes] / elem_bytes symbols
+  uint32_t elem_bytes;         // 1, 2, 4 or 8
+  uint8_t* const* rec_ptrs;    // [count * elem_bytes], as are the three below
+  const uint64_t* rec_caps;
+  uint64_t* rec_bytes;
+  int* slot_status;
+};
+// bodies and their records under one code (elem_bytes = 1: item = slot) or one code per byte plane
+struct BatchSeekDecodeParams {
+  const uint8_t* const* stream_ptrs;  // [count * elem_bytes] the bodies
+  const uint64_t* stream_bytes;
+  const uint8_t* const* rec_ptrs;     // [count * elem_bytes] the records
+  const uint64_t* rec_bytes;
+  uint64_t max_stream_bytes;          // as BatchSharedBodiesParams
+  const ghf_code* codes;              // [elem_bytes]
+  uint8_t* const* out_ptrs;           // [count]; null: sizes only (out_caps is ignored)
+  const uint64_t* out_caps;           // bytes
+  uint64_t* out_bytes;
+  int* item_status;
+};
+
 // K6: side-car reconstruction for foreign streams
 enum SyncKind : uint32_t {  // what SyncParams::no_eof carries
   kSyncCrs2 = 0,   // a whole .crs2: ends with the end mark
@@ -407,6 +445,9 @@ void launch_build_codes(const uint64_t* d_hists, uint32_t n_codes, ghf_code* d_c
 void launch_compress_batch_planes_shared(const BatchPlanesCompressParams& p, uint32_t count, uint32_t elem_bytes, hipStream_t s);  // grid = count * E
 void launch_decode_batch_planes_shared(const BatchPlanesDecodeParams& p, uint32_t count, uint32_t elem_bytes, hipStream_t s);      // grid = count
 void launch_decode_bodies_batch_planes_shared(const BatchPlanesBodiesParams& p, uint32_t count, uint32_t elem_bytes, hipStream_t s);
+// ghf_batch_seek.hip: elem_bytes is 1 (flat items), 2, 4 or 8
+void launch_batch_seek_pack(const BatchSeekPackParams& p, uint32_t slots, hipStream_t s);  // one launch, grid = slots
+void launch_decode_bodies_batch_seek(const BatchSeekDecodeParams& p, uint32_t count, uint32_t elem_bytes, hipStream_t s);  // grid = count
 // ghf_planes.hip: byte planes of elements of 2, 4 or 8 bytes (n_elems > 0; every pointer and plane_stride 16-byte aligned)
 void launch_planes_split(const uint8_t* d_in, uint64_t n_elems, uint32_t elem_bytes, uint8_t* d_planes, uint64_t plane_stride,
                          hipStream_t s);

@@ -143,6 +143,8 @@ EXPORTS = [
     "ghf_planes_slot_bytes", "ghf_planes_split", "ghf_planes_merge", "ghf_compress_planes", "ghf_decode_planes",
     "ghf_histogram_batch_planes", "ghf_build_codes", "ghf_compress_batch_planes_shared_bound",
     "ghf_compress_batch_planes_shared", "ghf_decode_batch_planes_shared", "ghf_decode_bodies_batch_planes_shared",
+    "ghf_batch_seek_bytes", "ghf_batch_seek_bound", "ghf_batch_seek_pack", "ghf_decode_bodies_batch_shared_seek",
+    "ghf_decode_bodies_batch_planes_shared_seek",
 ]
 COMM_ID_BYTES = 128
 
@@ -265,6 +267,13 @@ def lib():
     L.ghf_compress_batch_planes_shared.argtypes = [vp, vp, vp, sz, u32, u32, vp, vp, vp, vp, C.POINTER(BatchIndex), vp]
     L.ghf_decode_batch_planes_shared.argtypes = [vp, vp, vp, vp, C.POINTER(BatchIndex), vp, u32, u32, vp, vp, vp, vp]
     L.ghf_decode_bodies_batch_planes_shared.argtypes = [vp, vp, vp, vp, u32, u32, vp, vp, vp, vp]
+    L.ghf_batch_seek_bytes.argtypes = [sz]
+    L.ghf_batch_seek_bytes.restype = sz
+    L.ghf_batch_seek_bound.argtypes = [sz]
+    L.ghf_batch_seek_bound.restype = sz
+    L.ghf_batch_seek_pack.argtypes = [vp, C.POINTER(BatchIndex), vp, u32, u32, vp, vp, vp, vp]
+    L.ghf_decode_bodies_batch_shared_seek.argtypes = [vp, vp, vp, vp, vp, vp, u32, vp, vp, vp, vp]
+    L.ghf_decode_bodies_batch_planes_shared_seek.argtypes = [vp, vp, vp, vp, vp, vp, u32, u32, vp, vp, vp, vp]
     _lib = L
     return L
 
@@ -294,6 +303,16 @@ def compress_batch_shared_bound(max_item_bytes):
 def compress_batch_planes_shared_bound(max_item_bytes, elem_bytes):
     """capacity that suffices for every slot (item, plane) of a shared-code batch of elements of elem_bytes bytes"""
     return int(lib().ghf_compress_batch_planes_shared_bound(max_item_bytes, elem_bytes))
+
+
+def batch_seek_bytes(n_symbols):
+    """size of the run record of a shared-code body of n_symbols: 8 + 2 * ceil(n / 128), rounded up to 8"""
+    return int(lib().ghf_batch_seek_bytes(n_symbols))
+
+
+def batch_seek_bound(max_item_bytes):
+    """a 16-byte aligned slot that suffices for the run record of every body of up to max_item_bytes symbols"""
+    return int(lib().ghf_batch_seek_bound(max_item_bytes))
 
 
 def planes_slot_bytes(n_elems):
@@ -896,6 +915,85 @@ class Context:
                                                          None if out_caps is None else out_caps.data_ptr(), out_bytes.data_ptr(),
                                                          status.data_ptr()),
             "ghf_decode_bodies_batch_planes_shared")
+        return res
+
+    # ---- stored shared-code bodies: one run record per body, the persistent form of a slice of a BatchIndex ----
+    def batch_seek_pack(self, index, in_bytes, elem_bytes=1, d_rec=None, rec_stride=None):
+        """the live side-car of compress_batch_shared (elem_bytes 1) or compress_batch_planes_shared (2, 4, 8) -> one run
+        record per body, slot j at d_rec[j * rec_stride ..).  in_bytes: int64[count], the items' sizes in bytes (the
+        in_bytes of the compress call).  -> dict(rec, rec_stride, rec_ptrs, rec_caps, rec_bytes int64[slots], status
+        int32[slots])"""
+        t = self.torch
+        count = int(in_bytes.numel())
+        slots = count * elem_bytes
+        if rec_stride is None:
+            rec_stride = batch_seek_bound(int(index.max_item_bytes))
+        if d_rec is None:
+            d_rec = t.empty(max(slots * rec_stride, 16), dtype=t.uint8, device=self.device)
+        rec_ptrs = d_rec.data_ptr() + t.arange(slots, dtype=t.int64, device=self.device) * rec_stride
+        rec_caps = t.full((max(slots, 1),), rec_stride, dtype=t.int64, device=self.device)
+        rec_bytes = t.zeros(max(slots, 1), dtype=t.int64, device=self.device)
+        status = t.full((max(slots, 1),), -1, dtype=t.int32, device=self.device)
+        self._chk(
+            self.L.ghf_batch_seek_pack(self.h, C.byref(index), in_bytes.data_ptr(), count, elem_bytes, rec_ptrs.data_ptr(),
+                                       rec_caps.data_ptr(), rec_bytes.data_ptr(), status.data_ptr()),
+            "ghf_batch_seek_pack")
+        return {"rec": d_rec, "rec_stride": rec_stride, "rec_ptrs": rec_ptrs, "rec_caps": rec_caps, "rec_bytes": rec_bytes[:slots],
+                "status": status[:slots]}
+
+    def _seek_out(self, count, out, caps, who):
+        t = self.torch
+        if out is None:
+            return None, None, {}
+        if caps is None:
+            raise ValueError(who + ": the decode pass needs caps (e.g. the out_bytes of the sizes pass)")
+        if out is True:
+            out_stride = (int(caps.max().item()) + 15) & ~15 if count else 16
+            out = t.empty(max(count * out_stride, 16), dtype=t.uint8, device=self.device)
+        else:
+            out_stride = int(out.numel()) // max(count, 1)
+        out_ptrs = out.data_ptr() + t.arange(count, dtype=t.int64, device=self.device) * out_stride
+        out_caps = t.clamp(caps.to(t.int64), max=out_stride).contiguous()
+        return out_ptrs, out_caps, dict(out=out, out_stride=out_stride, out_ptrs=out_ptrs, out_caps=out_caps)
+
+    def decode_bodies_batch_shared_seek(self, stream_ptrs, stream_bytes, rec_ptrs, rec_bytes, d_code, out=None, caps=None):
+        """Stored bodies under the one code `d_code`, each with its run record: int64 CUDA tensors [count] of pointers and
+        sizes.  out=None: the sizes pass (the records' shapes are checked, the streams are not read) -> dict(out_bytes,
+        status).  Otherwise the decode pass, with out / caps as in decode_bodies_batch_shared."""
+        t = self.torch
+        count = int(stream_bytes.numel())
+        out_bytes = t.zeros(max(count, 1), dtype=t.int64, device=self.device)
+        status = t.full((max(count, 1),), -1, dtype=t.int32, device=self.device)
+        res = {"out_bytes": out_bytes[:count], "status": status[:count]}
+        out_ptrs, out_caps, more = self._seek_out(count, out, caps, "decode_bodies_batch_shared_seek")
+        res.update(more)
+        self._chk(
+            self.L.ghf_decode_bodies_batch_shared_seek(self.h, stream_ptrs.data_ptr(), stream_bytes.data_ptr(), rec_ptrs.data_ptr(),
+                                                       rec_bytes.data_ptr(), d_code.data_ptr(), count,
+                                                       None if out_ptrs is None else out_ptrs.data_ptr(),
+                                                       None if out_caps is None else out_caps.data_ptr(), out_bytes.data_ptr(),
+                                                       status.data_ptr()),
+            "ghf_decode_bodies_batch_shared_seek")
+        return res
+
+    def decode_bodies_batch_planes_shared_seek(self, stream_ptrs, stream_bytes, rec_ptrs, rec_bytes, d_codes, elem_bytes, out=None,
+                                               caps=None):
+        """the same for the slots of compress_batch_planes_shared: stream_* / rec_* int64[count * elem_bytes]; out / caps
+        (bytes per item) as in decode_bodies_batch_planes_shared."""
+        t = self.torch
+        count = int(stream_bytes.numel()) // elem_bytes
+        out_bytes = t.zeros(max(count, 1), dtype=t.int64, device=self.device)
+        status = t.full((max(count, 1),), -1, dtype=t.int32, device=self.device)
+        res = {"out_bytes": out_bytes[:count], "status": status[:count]}
+        out_ptrs, out_caps, more = self._seek_out(count, out, caps, "decode_bodies_batch_planes_shared_seek")
+        res.update(more)
+        self._chk(
+            self.L.ghf_decode_bodies_batch_planes_shared_seek(self.h, stream_ptrs.data_ptr(), stream_bytes.data_ptr(),
+                                                              rec_ptrs.data_ptr(), rec_bytes.data_ptr(), d_codes.data_ptr(), count,
+                                                              elem_bytes, None if out_ptrs is None else out_ptrs.data_ptr(),
+                                                              None if out_caps is None else out_caps.data_ptr(),
+                                                              out_bytes.data_ptr(), status.data_ptr()),
+            "ghf_decode_bodies_batch_planes_shared_seek")
         return res
 
     # ---- byte planes: elements of 2, 4 or 8 bytes, one ordinary .crs2 image per byte position ---------

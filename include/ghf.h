@@ -607,6 +607,89 @@ int ghf_decode_bodies_batch_planes_shared(ghf_ctx* ctx, const uint8_t* const* d_
                                           uint8_t* const* d_out_ptrs, const uint64_t* d_out_caps, uint64_t* d_out_bytes,
                                           int* d_item_status /* [count] */);
 
+/* ---- stored shared-code bodies: the run record, the persistent form of a batch's side-car -------------
+ * No reference counterpart (the reference compresses one file per process, include/compressor.h:62-73, and reads one back,
+ * include/compressor.h:87-92).  ghf_decode_batch_shared and ghf_decode_batch_planes_shared need the live ghf_batch_index:
+ * 6.25 % of the input in device memory, gone with the process that compressed.  The bodies-only calls need nothing but the
+ * bytes and find every code boundary again, which codes of 7 to 10 bits (uniform bytes, mantissa planes) make slow.  A
+ * RUN RECORD is what a stored body keeps beside it instead: ghf_batch_seek_pack writes one per body from the live
+ * side-car, and the two _seek decoders read (body, record, the one code) in ONE launch, one workgroup per item, every
+ * symbol decoded once.  No existing call and no .crs2 byte changes.
+ *
+ * A body is an item of ghf_compress_batch_shared, or slot i * elem_bytes + p of ghf_compress_batch_planes_shared.  Its
+ * record, all fields little-endian:
+ *     +0  u32 magic      "GBR1" (0x31524247)
+ *     +4  u32 n_symbols  1 .. GHF_BATCH_MAX_ITEM: what the body decodes to
+ *     +8  u16 run_bits[ceil(n_symbols / 128)]   the bits the codes of data symbols [128 r, 128 r + 128) take; the last
+ *                                               run may be short; the end mark is not counted
+ *         zero bytes up to a multiple of 8
+ * 72 bytes for an item of 4 KiB (1.8 %), 1032 for one of 64 KiB (1.6 %).
+ *
+ * Conventions are those of the shared-code batch calls: every array is DEVICE memory; asynchronous on the context's
+ * stream, never synchronises; failures are per slot or per item (GHF_OK is written as well; the size reported for a failed
+ * one is 0) and never latch the context's status word; the context's caches are left alone; count == 0 queues nothing.
+ * Call-level errors (returned at once, nothing queued, checked before anything touches HIP): a null context or array
+ * (d_out_ptrs may be null, see below), an elem_bytes the call does not take, an index that does not cover count *
+ * elem_bytes slots, d_out_ptrs without d_out_caps, a null or not 16-byte aligned code array: GHF_E_INVAL.  Stream and
+ * record pointers are 16-byte aligned; decode outputs need no alignment.  Not supported: images of ghf_compress_batch
+ * (a code per item), and the .crs format. */
+
+/* No reference counterpart (include/compressor.h:62-73, 87-92).  Host only: 8 + 2 * ceil(n_symbols / 128), rounded up to
+ * 8: the size of the record of a body of n_symbols. */
+size_t ghf_batch_seek_bytes(size_t n_symbols);
+/* No reference counterpart (include/compressor.h:62-73, 87-92).  Host only: ghf_batch_seek_bytes(max_item_bytes) rounded up
+ * to 16, so that the slots of many records can be cut from one aligned buffer. */
+size_t ghf_batch_seek_bound(size_t max_item_bytes);
+
+/* No reference counterpart (include/compressor.h:62-73, 87-92).  The live side-car of a shared-code compress call -> one
+ * record per body, in one launch.  elem_bytes 1: `index` is the one ghf_compress_batch_shared filled, body i has
+ * d_in_bytes[i] symbols.  elem_bytes 2, 4, 8: the one ghf_compress_batch_planes_shared filled (count * elem_bytes slices),
+ * slot i * elem_bytes + p has d_in_bytes[i] / elem_bytes symbols.  Slot j's record goes to d_rec_ptrs[j] (16-byte aligned),
+ * d_rec_bytes[j] <- its size.  A refused slot writes nothing and reports 0 bytes.  d_slot_status[j] <-
+ *   GHF_E_EMPTY   0 symbols
+ *   GHF_E_INVAL   more symbols than a slice of the index covers; a size that is not a multiple of elem_bytes; a null or
+ *                 misaligned record pointer
+ *   GHF_E_CAP     the record is larger than d_rec_caps[j]
+ *   GHF_E_CORRUPT the slice is not the side-car of a body: chunk_bit[0] != 0 (the images of ghf_compress_batch start behind
+ *                 their header), a block that does not start where its predecessor's last segment ends, segment ends that
+ *                 do not grow, a run of more than 65535 bits */
+int ghf_batch_seek_pack(ghf_ctx* ctx, const ghf_batch_index* index, const uint64_t* d_in_bytes /* [count] */, uint32_t count,
+                        uint32_t elem_bytes, uint8_t* const* d_rec_ptrs /* [count * elem_bytes] */,
+                        const uint64_t* d_rec_caps, uint64_t* d_rec_bytes, int* d_slot_status /* [count * elem_bytes] */);
+
+/* No reference counterpart (include/compressor.h:62-73 is the way there; generalises 87-92).  Item i = the body at
+ * d_stream_ptrs[i] (d_stream_bytes[i] of it, which may exceed the body) and its record at d_rec_ptrs[i] (d_rec_bytes[i] of
+ * it) -> d_out_ptrs[i][0 .. n_i), d_out_bytes[i] <- n_i, the record's n_symbols.  d_out_ptrs == NULL (then d_out_caps is
+ * ignored): sizes only -- the pointers and each record's shape are checked, d_out_bytes[i] <- n_i, the stream is not read.
+ * The code is vetted first, with the rules of ghf_decode_batch_shared: GHF_E_FORMAT on EVERY item, nothing written.  Then,
+ * per item, nothing in a record is trusted.  d_item_status[i] <-
+ *   GHF_E_INVAL   a null or misaligned stream or record pointer; a null output pointer in decode mode; d_stream_bytes[i]
+ *                 greater than ghf_compress_batch_shared_bound(GHF_BATCH_MAX_ITEM)
+ *   GHF_E_FORMAT  the record: wrong magic, n_symbols of 0 or above GHF_BATCH_MAX_ITEM, d_rec_bytes[i] !=
+ *                 ghf_batch_seek_bytes(n_symbols)
+ *   GHF_E_CAP     n_symbols > d_out_caps[i]; checked before any store
+ *   GHF_E_CORRUPT a run starts or ends beyond bit 8 * d_stream_bytes[i]; a run does not land exactly on its recorded end;
+ *                 a window starts no code; an end mark lies among the data; the end mark does not follow the last symbol
+ *                 whole
+ * No byte outside stream[0 .. d_stream_bytes[i]) or record[0 .. d_rec_bytes[i]) is read; nothing at or beyond d_out_caps[i]
+ * is written (an item that fails with GHF_E_CORRUPT may have written in front of it). */
+int ghf_decode_bodies_batch_shared_seek(ghf_ctx* ctx, const uint8_t* const* d_stream_ptrs, const uint64_t* d_stream_bytes,
+                                        const uint8_t* const* d_rec_ptrs, const uint64_t* d_rec_bytes, const ghf_code* d_code,
+                                        uint32_t count, uint8_t* const* d_out_ptrs, const uint64_t* d_out_caps,
+                                        uint64_t* d_out_bytes, int* d_item_status /* [count] */);
+
+/* No reference counterpart (include/compressor.h:62-73 is the way there; generalises 87-92).  The same for the slots of
+ * ghf_compress_batch_planes_shared: d_stream_ptrs / d_stream_bytes / d_rec_ptrs / d_rec_bytes are [count * elem_bytes],
+ * d_codes is [elem_bytes]; output and status are PER ITEM and written as in ghf_decode_batch_planes_shared, d_out_bytes[i]
+ * <- n_i * elem_bytes, d_out_caps[i] is in bytes.  All elem_bytes codes (GHF_E_FORMAT on every item) and all elem_bytes
+ * pointers and record headers of an item are vetted before its first store.  Status as above, for any plane of the item,
+ * and GHF_E_CORRUPT when the records of one item disagree on n_symbols; GHF_E_CAP: n_symbols * elem_bytes > d_out_caps[i]. */
+int ghf_decode_bodies_batch_planes_shared_seek(ghf_ctx* ctx, const uint8_t* const* d_stream_ptrs /* [count * elem_bytes] */,
+                                               const uint64_t* d_stream_bytes, const uint8_t* const* d_rec_ptrs /* [count * elem_bytes] */,
+                                               const uint64_t* d_rec_bytes, const ghf_code* d_codes /* [elem_bytes] */, uint32_t count,
+                                               uint32_t elem_bytes, uint8_t* const* d_out_ptrs /* [count] */,
+                                               const uint64_t* d_out_caps, uint64_t* d_out_bytes, int* d_item_status /* [count] */);
+
 /* Multi-GPU decode of a stream that has no side-car ("per-rank self-sync + one all-gather of symbol
  * counts"; the reference's decoders, canonical_huff_encoder.cc:377-568, are single-stream).  The caller cuts the body
  * at byte positions; a rank's piece is its own bytes followed by >= 8 bytes of look-ahead from the next piece (zeros
