@@ -14,6 +14,7 @@ import datagen as dg
 import pkgload
 from cases import CASES, INLINE_CRS2
 from oracle import oracle as orc
+from range_worlds import expected_table
 
 pytestmark = pytest.mark.gpu
 
@@ -36,22 +37,6 @@ def env():
 
 def to_dev(torch, a):
     return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def expected_table(data, length, first_bit, flags=0):
-    """the table image of `data` coded with `length[]`, its first code at bit `first_bit` of the buffer"""
-    n = data.size
-    nb = -(-n // 4096)
-    cum = np.zeros(n + 1, dtype=np.int64)
-    np.cumsum(np.asarray(length, dtype=np.int64)[data], out=cum[1:])
-    rec = np.zeros(nb, dtype=REC)
-    rec["start"] = first_bit + cum[0:n:4096][:nb]
-    edges = np.minimum(np.arange(nb * 8 + 1, dtype=np.int64) * 512, n)
-    runs = np.diff(cum[edges]).reshape(nb, 8)
-    assert runs.max(initial=0) <= 0xFFFF
-    rec["run"] = runs
-    hdr = b"GHFSEEK1" + struct.pack("<IIQIIQ", 1, flags, n, 4096, 512, nb)
-    return np.frombuffer(hdr + bytes(64 - len(hdr)) + rec.tobytes(), dtype=np.uint8).copy()
 
 
 def compress_with_index(ctx, torch, data):
