@@ -1,12 +1,13 @@
 // golden-huffman_amd/csrc/ghf_batch_core.h -- the device helpers of the one-workgroup-per-item kernels, shared by
-// ghf_batch.hip (one code per item), ghf_batch_shared.hip (one code for the batch) and ghf_batch_planes.hip (one code per
-// byte plane of the batch): the round geometry, the item loads for any alignment, the LDS stage of the packer, the
-// bounded stream reads and the bit cursor of the decoders, the packer of the shared-code kernels
-// (batch_shared_compress_body, over a flat item or one byte plane of it), and the round loops of the decoders: the one
-// that follows a side-car (batch_decode_segments) and the one that finds the code boundaries itself
-// (batch_decode_rounds), each over the way its stage leaves (StoreFlat, StorePlane).  Behind them what ghf_batch_seek.hip
-// (stored bodies with a run record each) adds: the decoders' front stated once (batch_code_ok, batch_code_tables) and
-// the round loop that follows a record (batch_decode_runs).
+// ghf_batch.hip (one code per item), ghf_batch_shared.hip (one code for the batch), ghf_batch_planes.hip (one code per
+// byte plane of the batch) and ghf_batch_seek.hip (stored bodies with a run record each): the round geometry, the item
+// loads for any alignment, the LDS stage of the packer, the bounded stream reads and the bit cursor of the decoders, the
+// packer of the shared-code kernels (batch_shared_compress_body, over a flat item or one byte plane of it), and what a
+// decoder is made of: the table fill of one vetted code (batch_code_tables) with the code check in front of it
+// (batch_code_ok), and the three round loops -- the one that follows a side-car (batch_decode_segments), the one that
+// finds the code boundaries itself (batch_decode_rounds) and the one that follows a run record (batch_decode_runs) --
+// each over the way its stage leaves (StoreFlat, StorePlane).  Which kernels call them and which still carry a
+// written-out copy, and why: profiles/batch_core/README.md.
 #ifndef GHF_BATCH_CORE_H_
 #define GHF_BATCH_CORE_H_
 #include "ghf_code_rules.h"
@@ -449,11 +450,11 @@ struct StorePlane {  // out[(base + s) * E + p]: byte plane p of elements of E b
 };
 
 // ----------------------------------------------------------------------------------------------------------------------
-// the round loop of the decoders that follow a live side-car (k_decode_batch_shared, k_decode_batch_planes_shared): rounds
-// of 256 segments of 64 symbols, one per lane, from the recorded bit of each.  Every lane of the workgroup calls it with
-// the same arguments; S.t holds the filled tables (a barrier lies behind tab_fill_lut).  Every segment must land on its
-// recorded end and the end mark must follow the last symbol: S.err (zero when the first call starts) is raised
-// otherwise, and the round is stored all the same.  No byte outside stream[0 .. stream_bytes) is read.  (No __restrict__
+// the round loop of the decoders that follow a live side-car (k_decode_batch_shared, k_decode_batch_planes_shared; written
+// out once more in k_decode_batch): rounds of 256 segments of 64 symbols, one per lane, from the recorded bit of each.  Every
+// lane of the workgroup calls it with the same arguments; S.t holds the filled tables (a barrier lies behind
+// batch_code_tables).  Every segment must land on its recorded end and the end mark must follow the last symbol: S.err
+// (zero when the first call starts) is raised otherwise, and the round is stored all the same.  No byte outside stream[0 .. stream_bytes) is read.  (No __restrict__
 // on stream / out: with it the compiler unrolls batch_store_stage's vector loop with dword stores.)
 // ----------------------------------------------------------------------------------------------------------------------
 template <class Lds, class Store>  // Lds: the kernel's __shared__ struct with a CodeTab t, the stage and an int err
@@ -657,9 +658,11 @@ __device__ __forceinline__ int batch_decode_rounds(const CodeTab& T, uint32_t* s
 }
 
 // ----------------------------------------------------------------------------------------------------------------------
-// the front of the decoders of stored bodies (ghf_batch_seek.hip): the code check and the table
-// fill of k_decode_batch_shared, stated once.  (The kernels above keep their written-out copies: their listings are
-// held, sections 11 and 13.)
+// the front of the decoders that are handed a ghf_code, stated once: the code check (ghf_batch_seek.hip) and the table
+// fill (ghf_batch_seek.hip, ghf_batch_planes.hip, whose E codes are vetted in one go by planes_codes_ok).  k_decode_batch,
+// k_decode_batch_shared and k_decode_bodies_batch_shared keep their written-out copies of both: called from there the
+// functions re-lay those kernels, and the measurement that has to clear a re-laid listing was not made
+// (profiles/batch_core/README.md; DESIGN.md sections 11, 13 and 16).
 // ----------------------------------------------------------------------------------------------------------------------
 struct CodeVetLds {
   unsigned long long kraft;

@@ -138,20 +138,6 @@ __device__ __forceinline__ bool planes_codes_ok(PlanesVetLds& V, const ghf_code*
   for (int p = 0; p < E; ++p) ok &= V.kraft[p] == (1ull << 32);
   return ok;
 }
-// the tables of one vetted code; every lane of the workgroup, barriers on both sides are inside
-__device__ __forceinline__ void planes_fill_tab(CodeTab& T, const ghf_code* __restrict__ code, int tid, int& lb, int& long_from,
-                                                int& max_len) {
-  const int min_len = code->min_len;
-  max_len = code->max_len;
-  __syncthreads();  // the previous plane's lanes are done with T
-  if (tid < 36) tab_load_row(T, tid, min_len, max_len, code->first_code, code->start_pos);
-  for (int i = tid; i < GHF_NSYM; i += kBatchThreads) T.symbol[i] = tab_symbol(code->symbol[i]);
-  __syncthreads();
-  lb = max_len < kDecLutBitsMax ? max_len : kDecLutBitsMax;
-  long_from = lb + 1 > min_len ? lb + 1 : min_len;
-  tab_fill_lut(T, min_len, lb, tid, kBatchThreads);
-  __syncthreads();
-}
 
 struct BatchPlanesDecodeLds {
   CodeTab t;  // the tables of the plane in work
@@ -192,7 +178,7 @@ __global__ __launch_bounds__(kBatchThreads) void k_decode_batch_planes_shared(Ba
   for (uint32_t p = 0; p < E; ++p) {
     const size_t slot = (size_t)item * E + p;
     int lb, long_from, max_len;
-    planes_fill_tab(S.t, P.codes + p, tid, lb, long_from, max_len);
+    batch_code_tables(S.t, P.codes + p, tid, lb, long_from, max_len);
     batch_decode_segments(S, P.stream_ptrs[slot], P.stream_bytes[slot], P.chunk_bit + slot * P.blocks_per_item,
                           P.seg_bit + slot * P.segs_per_item, n, out, lb, long_from, max_len, StorePlane<E>{p});
   }
@@ -235,8 +221,8 @@ __global__ __launch_bounds__(kBatchThreads) void k_decode_bodies_batch_planes_sh
   for (uint32_t p = 0; p < E && status == GHF_OK; ++p) {
     const size_t slot = (size_t)item * E + p;
     int lb, long_from, max_len;
-    if (tid == 0) batch_rounds_init(S.r);  // (the barriers of planes_fill_tab lie between this and the rounds)
-    planes_fill_tab(S.t, P.codes + p, tid, lb, long_from, max_len);
+    if (tid == 0) batch_rounds_init(S.r);  // (the barriers of batch_code_tables lie between this and the rounds)
+    batch_code_tables(S.t, P.codes + p, tid, lb, long_from, max_len);
     uint32_t total = 0;  // stream_bytes <= ghf_compress_batch_shared_bound(1 MiB): every bit offset fits 32 bits
     status = batch_decode_rounds<kWrite>(S.t, S.stage, S.r, P.stream_ptrs[slot], P.stream_bytes[slot], 0u, cap, out, lb, long_from,
                                          max_len, &total, rounds, passes, StorePlane<E>{p});

@@ -2,7 +2,7 @@
 
 Shared by tests/test_header_rules_cpu.py (ghf_parse_header on the host), tests/test_gpu_batch_images.py (the same
 headers through k_decode_images_batch), tests/test_gpu_batch.py and tests/test_gpu_parity.py (the code rules through
-k_decode_batch and k_build_decode_tables).  Everything starts from the oracle's image of one 4 KiB item; nothing here
+k_decode_batch and k_build_decode_tables) and tests/test_gpu_batch_shared.py (vet_branch_codes through the shared-code decoders).  Everything starts from the oracle's image of one 4 KiB item; nothing here
 comes from the library under test.  The returned arrays are shared: callers copy before they change one.
 
 Where the format allows, a case leaves every other rule intact (the recurrence, first_code[max_len], first_code[1], the
@@ -141,4 +141,24 @@ def bad_codes(good, make):
     case("one length shortened: Kraft above 1", shorter)
     case("first_code[len] = 2^len + 1", wide)
     case("start_pos[len] = 258", far)
+    return out
+
+
+def vet_branch_codes(good, make):
+    """two corrupted copies of the ghf_code `good`, one for each way the batch decoders' code check (batch_code_ok,
+    ghf_batch_core.h) refuses: the length bounds, and a Kraft sum that is not 1 behind bounds that hold.  [(name, code)]"""
+    lo = good.min_len
+    assert lo < good.max_len and good.start_pos[lo + 1] > good.start_pos[lo]
+    out = []
+    c = make(bytes(good))
+    c.max_len = 33
+    out.append(("max_len 33", c))
+    # the last symbol of the shortest length moves one length up, in length[] and in the per-length tables alike: every
+    # length stays inside [min_len, max_len] and every row keeps its bounds, only the Kraft sum falls below 1
+    c = make(bytes(good))
+    s = good.symbol[good.start_pos[lo + 1] - 1]
+    assert good.length[s] == lo
+    c.length[s] = lo + 1
+    c.start_pos[lo + 1] -= 1
+    out.append(("one length raised by one: Kraft below 1", c))
     return out

@@ -15,7 +15,7 @@ import pytest
 import datagen as dg
 import pkgload
 from cases import CASES, sweep_crs2_inputs
-from header_cases import bad_codes, header_cases
+from header_cases import bad_codes, header_cases, vet_branch_codes
 from oracle import oracle as orc
 
 pytestmark = pytest.mark.gpu
@@ -106,7 +106,7 @@ class Batch:
             self.bidx = None
 
 
-def decode_batch(b, n_symbols=None, stream_bytes=None, codes=None, d_stream=None):
+def decode_batch(b, n_symbols=None, stream_bytes=None, codes=None, d_stream=None, caps=None):
     """ghf_decode_batch on the outputs of Batch `b`: every output at an unaligned address between guard bytes.
     -> (status, out_bytes, list of decoded arrays, list of (front guard, back guard) arrays)"""
     ghf, ctx, torch = b.ghf, b.ctx, b.torch
@@ -115,7 +115,7 @@ def decode_batch(b, n_symbols=None, stream_bytes=None, codes=None, d_stream=None
     d_out = torch.full((b.count * ostride + 64,), GUARD, dtype=torch.uint8).cuda()
     ooff = [i * ostride + 17 + (i % 15) for i in range(b.count)]  # misalignments 1..15 (+ 17)
     out_ptrs = i64(torch, [d_out.data_ptr() + o for o in ooff])
-    out_caps = i64(torch, [b.max_item] * b.count)
+    out_caps = i64(torch, [b.max_item] * b.count if caps is None else caps)
     out_bytes = torch.full((b.count,), -1, dtype=torch.int64).cuda()
     status = torch.full((b.count,), -1, dtype=torch.int32).cuda()
     sp = b.out_ptrs if d_stream is None else i64(torch, [d_stream.data_ptr() + i * b.stride for i in range(b.count)])
@@ -382,6 +382,41 @@ def test_decode_refuses_codes_that_are_not_complete(env):
             else:
                 assert int(out_bytes[i]) == 0 and np.all(outs[i] == GUARD), i
             assert np.all(guards[i][0] == GUARD) and np.all(guards[i][1] == GUARD), i
+    finally:
+        b.free()
+
+
+@pytest.mark.parametrize("refusal", ["empty", "cap"])
+def test_an_items_own_refusal_comes_before_its_codes(env, refusal):
+    """the order of k_decode_batch's verdicts: GHF_E_EMPTY / GHF_E_CAP of an item are reported although its code is
+    broken as well (by its length bounds, by its Kraft sum: the two ways batch_code_ok refuses), never GHF_E_FORMAT.
+    Three items of 65 bytes: one whole segment and a ragged one"""
+    ghf, ctx, torch = env
+    datas = [dg.make("zipf", 65, seed=6100 + i) for i in range(3)]
+    b = Batch(ghf, ctx, torch, datas).run()
+    try:
+        assert np.all(b.h_status == OK)
+        n_symbols, caps = [65, 65, 65], [b.max_item] * 3
+        if refusal == "empty":
+            n_symbols[1] = 0
+        else:
+            caps[1] = 64
+        want = [OK, E_EMPTY if refusal == "empty" else E_CAP, OK]
+        for name, c in vet_branch_codes(b.code(1), ghf.Code.from_buffer_copy):
+            codes = b.h_codes.copy()
+            codes[1] = np.frombuffer(bytes(c), dtype=np.uint8)
+            d_codes = torch.from_numpy(codes).cuda()
+            status, out_bytes, outs, guards = decode_batch(b, codes=d_codes)  # the code alone: it is refused
+            assert status.tolist() == [OK, E_FORMAT, OK], name
+            status, out_bytes, outs, guards = decode_batch(b, n_symbols=n_symbols, codes=d_codes, caps=caps)
+            print(name, status.tolist(), out_bytes.tolist())
+            assert status.tolist() == want, name
+            assert out_bytes.tolist() == [65, 0, 65], name
+            for i in (0, 2):
+                assert np.array_equal(outs[i], datas[i]), (name, i)
+            assert np.all(outs[1] == GUARD), name  # nothing of the refused item is written
+            for i in range(3):
+                assert np.all(guards[i][0] == GUARD) and np.all(guards[i][1] == GUARD), (name, i)
     finally:
         b.free()
 

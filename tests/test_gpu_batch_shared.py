@@ -12,7 +12,7 @@ import pytest
 import datagen as dg
 import pkgload
 from cases import CASES
-from header_cases import bad_codes
+from header_cases import bad_codes, vet_branch_codes
 from oracle import oracle as orc
 
 pytestmark = pytest.mark.gpu
@@ -535,6 +535,61 @@ def test_decode_failures_are_per_item(env):
         assert status.tolist() == [E_FORMAT] * b.count and np.all(out_bytes == 0)
         for i in range(b.count):
             assert np.all(outs[i] == GUARD) and np.all(guards[i][0] == GUARD) and np.all(guards[i][1] == GUARD), i
+    finally:
+        b.free()
+
+
+@pytest.mark.parametrize("refusal", ["empty", "cap"])
+def test_a_broken_shared_code_comes_before_an_items_own_refusal(env, refusal):
+    """the order of the verdicts of k_decode_batch_shared and k_decode_bodies_batch_shared: the code is vetted before the
+    item is looked at, so a code broken by its length bounds or by its Kraft sum (the two ways batch_code_ok refuses) gives
+    GHF_E_FORMAT on every item, the one with a refusal of its own included, and no byte of any output is written.  Three
+    items of 65 bytes: one whole segment and a ragged one.  (ghf_decode_bodies_batch_shared takes no symbol counts: there
+    item 1's own refusal is the cap of 64 in both cases.)"""
+    ghf, ctx, torch = env
+    datas = [dg.make("zipf", 65, seed=6200 + i) for i in range(3)]
+    w = World(env, datas, 4096)
+    b = w.b
+    try:
+        assert np.all(b.h_status == OK)
+        n_symbols, caps = [65, 65, 65], [4096] * 3
+        if refusal == "empty":
+            n_symbols[1] = 0
+        else:
+            caps[1] = 64
+        mine = E_EMPTY if refusal == "empty" else E_CAP
+
+        def bodies(d_code):  # ghf_decode_bodies_batch_shared into 65-byte slots between guard bytes, item 1 capped at 64
+            d_out = torch.full((3 * 128,), GUARD, dtype=torch.uint8).cuda()
+            out_ptrs = i64(torch, [d_out.data_ptr() + 128 * i + 17 + i for i in range(3)])
+            out_bytes = torch.full((3,), -1, dtype=torch.int64).cuda()
+            status = torch.full((3,), -1, dtype=torch.int32).cuda()
+            out_caps = i64(torch, [65, 64, 65])
+            rc = ghf.lib().ghf_decode_bodies_batch_shared(ctx.h, b.out_ptrs.data_ptr(), b.out_bytes.data_ptr(), d_code.data_ptr(), 3,
+                                                          out_ptrs.data_ptr(), out_caps.data_ptr(), out_bytes.data_ptr(),
+                                                          status.data_ptr())
+            assert rc == 0, rc
+            ctx.sync()
+            return status.cpu().numpy(), out_bytes.cpu().numpy(), d_out.cpu().numpy()
+
+        # the good code: item 1's own refusal is real, its neighbours decode
+        status, out_bytes, outs, guards = decode_shared(b, n_symbols=n_symbols, caps=caps)
+        assert status.tolist() == [OK, mine, OK] and out_bytes.tolist() == [65, 0, 65]
+        assert np.array_equal(outs[0], datas[0]) and np.array_equal(outs[2], datas[2])
+        status, out_bytes, h = bodies(b.d_code)
+        assert status.tolist() == [OK, E_CAP, OK] and out_bytes.tolist() == [65, 0, 65]
+        assert np.array_equal(h[17:82], datas[0]) and np.array_equal(h[256 + 19 :][:65], datas[2])
+        for name, c in vet_branch_codes(ghf.Code.from_buffer_copy(bytes(w.code)), ghf.Code.from_buffer_copy):
+            d_code = code_to_device(torch, c)
+            status, out_bytes, outs, guards = decode_shared(b, n_symbols=n_symbols, caps=caps, d_code=d_code)
+            print(name, status.tolist(), out_bytes.tolist())
+            assert status.tolist() == [E_FORMAT] * 3 and out_bytes.tolist() == [0, 0, 0], name
+            for i in range(3):
+                assert np.all(outs[i] == GUARD) and np.all(guards[i][0] == GUARD) and np.all(guards[i][1] == GUARD), (name, i)
+            status, out_bytes, h = bodies(d_code)
+            print(name, "bodies", status.tolist(), out_bytes.tolist())
+            assert status.tolist() == [E_FORMAT] * 3 and out_bytes.tolist() == [0, 0, 0], name
+            assert np.all(h == GUARD), name
     finally:
         b.free()
 
