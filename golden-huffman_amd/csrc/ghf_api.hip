@@ -138,6 +138,7 @@ int ghf_ctx_destroy(ghf_ctx* c) {
   release(c->chunk_bit);
   release(c->range_seg);
   release(c->range_chunk);
+  release(c->range_dt);
   release(c->batch_codes);
   release(c->planes);
   if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
@@ -1306,6 +1307,18 @@ int ghf_planes_merge(ghf_ctx* c, const uint8_t* d_planes, size_t plane_stride, s
   return GHF_OK;
 }
 
+int ghf_planes_merge_range(ghf_ctx* c, const uint8_t* d_planes, size_t plane_stride, size_t first, size_t count, uint32_t elem_bytes,
+                           uint8_t* d_out) {
+  if (c && first + count < first) return fail(c, GHF_E_INVAL, "ghf_planes_merge_range: first + count overflows");
+  int rc = planes_args(c, "ghf_planes_merge_range", d_out, d_planes, plane_stride, count, elem_bytes);
+  if (!rc && plane_stride < first + count) rc = fail(c, GHF_E_CAP, "ghf_planes_merge_range: plane_stride below first + count");
+  if (rc) return rc;
+  GHF_HIP(c, hipSetDevice(c->device));
+  launch_planes_merge_range(d_planes, plane_stride, first, count, elem_bytes, d_out, nullptr, c->stream);
+  GHF_HIP(c, hipGetLastError());
+  return GHF_OK;
+}
+
 // the context's plane workspace for n_elems elements (workspace_overflow has cleared them): *stride <- the distance
 // between two planes
 static int planes_workspace(ghf_ctx* c, size_t n_elems, uint32_t elem_bytes, size_t* stride) {
@@ -1549,6 +1562,105 @@ int ghf_decode_range(ghf_ctx* c, const uint8_t* d_stream, size_t stream_bytes, c
     p.status = c->d_status;
     launch_decode(p, c->stream);
   }
+  GHF_HIP(c, hipGetLastError());
+  return GHF_OK;
+}
+
+// ---------------------------------------------------------------------------------------------- element range of byte planes
+// (no reference counterpart)
+int ghf_decode_planes_range(ghf_ctx* c, const uint8_t* const* h_stream_ptrs, const size_t* h_stream_bytes, const ghf_code* d_codes,
+                            const ghf_index* indexes, const ghf_seek_info* h_infos, const uint8_t* const* h_table_ptrs,
+                            const size_t* h_table_bytes, uint32_t elem_bytes, uint64_t first, uint64_t count, uint8_t* d_out, size_t cap) {
+  if (!c || !h_stream_ptrs || !h_stream_bytes || !d_codes || !d_out) return GHF_E_INVAL;
+  if (!elem_bytes_ok(elem_bytes)) return fail(c, GHF_E_INVAL, "ghf_decode_planes_range: elem_bytes must be 2, 4 or 8");
+  const bool by_table = h_infos || h_table_ptrs || h_table_bytes;
+  if ((indexes != nullptr) == by_table || (by_table && !(h_infos && h_table_ptrs && h_table_bytes)))
+    return fail(c, GHF_E_INVAL, "ghf_decode_planes_range: exactly one of indexes / (h_infos, h_table_ptrs, h_table_bytes) must be given");
+  for (uint32_t p = 0; p < elem_bytes; ++p) {
+    if (!h_stream_ptrs[p] || !aligned16(h_stream_ptrs[p]))
+      return fail(c, GHF_E_INVAL, "ghf_decode_planes_range: a stream pointer is null or not 16-byte aligned");
+    if (by_table && (!h_table_ptrs[p] || !aligned16(h_table_ptrs[p])))
+      return fail(c, GHF_E_INVAL, "ghf_decode_planes_range: a table pointer is null or not 16-byte aligned");
+  }
+  if (!aligned16(d_out)) return fail(c, GHF_E_INVAL, "ghf_decode_planes_range: d_out must be 16-byte aligned");
+  const uint64_t n_elems = by_table ? h_infos[0].n_symbols : indexes[0].n_symbols;
+  for (uint32_t p = 0; p < elem_bytes; ++p) {
+    if (!by_table && indexes[p].n_symbols != 0 && !index_is_whole(&indexes[p]))
+      return fail(c, GHF_E_INVAL, "ghf_decode_planes_range: malformed index");
+    if ((by_table ? h_infos[p].n_symbols : indexes[p].n_symbols) != n_elems)
+      return fail(c, GHF_E_INVAL, "ghf_decode_planes_range: the planes disagree on n_symbols");
+  }
+  if (first > n_elems || count > n_elems - first) return fail(c, GHF_E_INVAL, "ghf_decode_planes_range: first + count exceeds n_elems");
+  // the workspace holds the range from the start of its first block (below), and a vector more for the merge's second load
+  const size_t lead = (size_t)(first % kBlockSymbols);
+  if (count > (size_t)-1 - lead - 16 || workspace_overflow((size_t)count + lead + 16, elem_bytes))
+    return fail(c, GHF_E_INVAL, "ghf_decode_planes_range: count * elem_bytes overflows");
+  for (uint32_t p = 0; by_table && p < elem_bytes; ++p) {  // every plane before anything is queued for the first
+    const int rc = seek_table_ok(c, "ghf_decode_planes_range", h_infos + p, h_table_ptrs[p], h_table_bytes[p]);
+    if (rc) return rc;
+  }
+  if (cap < count * elem_bytes) return fail(c, GHF_E_CAP, "ghf_decode_planes_range: output capacity below count * elem_bytes");
+  if (count == 0) return GHF_OK;
+  GHF_HIP(c, hipSetDevice(c->device));
+  // Every plane is decoded from the start of the block that holds `first`: plane p's byte `first - lead` lands on the
+  // 16-byte aligned start of its workspace plane, so every later byte sits at an address congruent to its index modulo 16 --
+  // what K7's 16-byte store path asks for -- and no block is entered in its middle: ghf_decode_range queues no k_decode_head,
+  // whose one wave walks up to a block serially (DESIGN.md section 17 has the measurement).  The up to 4095 symbols in front
+  // of the range are one K7 block of work; the merge skips them and takes the skew out.
+  size_t stride = 0;
+  int rc = planes_workspace(c, (size_t)count + lead + 16, elem_bytes, &stride);
+  if (rc) return rc;
+  const uint64_t from = first - lead, end = first + count;
+  if (!by_table) {
+    for (uint32_t p = 0; p < elem_bytes; ++p)
+      if ((rc = ghf_decode_range(c, h_stream_ptrs[p], h_stream_bytes[p], d_codes + p, indexes + p, nullptr, nullptr, 0, from, end - from,
+                                 c->planes.p + p * stride, stride)))
+        return rc;
+  } else {
+    // From tables ghf_decode_range would expand every plane by itself, and k_seek_expand has a latency floor -- a lane walks
+    // its 512 symbols serially -- that a range does not shrink: E floors one after the other cost more than decoding the
+    // whole tensor from side-cars.  So: all E table sets first, ONE launch that expands the covered blocks of all planes
+    // (k_seek_expand_planes), then K7 per plane on that view, set up as ghf_decode_range sets it up (the range begins on a
+    // block, so there is no head).
+    const uint64_t gA = from / kBlockSymbols, gB = blocks_for(end), nb = gB - gA;
+    const size_t segs_per_block = kBlockSymbols / kSegSymbols;
+    if (!(rc = grow(c, c->range_dt, elem_bytes))) rc = grow(c, c->range_chunk, nb * elem_bytes, 1024);
+    if (!rc) rc = grow(c, c->range_seg, nb * elem_bytes * segs_per_block, 1024 * 64);
+    if (rc) return rc;
+    SeekExpandPlanesParams a = {};
+    for (uint32_t p = 0; p < elem_bytes; ++p) {
+      launch_build_decode_tables(d_codes + p, c->range_dt.p + p, c->d_status, c->stream);
+      SeekExpandParams& x = a.plane[p];
+      x.records = h_table_ptrs[p] + kSeekHeaderBytes;
+      x.stream = h_stream_ptrs[p];
+      x.stream_bytes = h_stream_bytes[p];
+      x.dt = c->range_dt.p + p;
+      x.n_symbols = n_elems;
+      x.n_blocks = h_infos[p].n_blocks;
+      x.g0 = gA;
+      x.g1 = gB;
+      x.chunk_bit = c->range_chunk.p + p * nb;
+      x.seg_bit = c->range_seg.p + p * nb * segs_per_block;
+      x.status = c->d_status;
+    }
+    launch_seek_expand_planes(a, elem_bytes, c->stream);
+    for (uint32_t p = 0; p < elem_bytes; ++p) {
+      DecParams d = {};
+      d.stream = h_stream_ptrs[p];
+      d.stream_bytes = h_stream_bytes[p];
+      d.dt = c->range_dt.p + p;
+      d.chunk_bit = a.plane[p].chunk_bit;
+      d.seg_bit = a.plane[p].seg_bit;
+      d.n_symbols = end - from;
+      d.n_segs = segs_for(d.n_symbols);
+      d.no_end_mark = (end == n_elems && !(h_infos[p].flags & GHF_INDEX_NO_END_MARK)) ? 0u : 1u;
+      d.out = c->planes.p + p * stride;
+      d.out_bytes = nullptr;
+      d.status = c->d_status;
+      launch_decode(d, c->stream);
+    }
+  }
+  launch_planes_merge_range(c->planes.p, stride, lead, count, elem_bytes, d_out, c->d_status, c->stream);  // nothing behind a failed decode
   GHF_HIP(c, hipGetLastError());
   return GHF_OK;
 }

@@ -133,6 +133,9 @@ struct ghf_ctx {
   // ghf_decode_range from a seek table: the side-car of the covered blocks only (describes nothing between calls)
   ghf::DevBuf<uint32_t> range_seg;
   ghf::DevBuf<uint64_t> range_chunk;
+  // ghf_decode_planes_range from seek tables: one set of decode tables per plane, alive together for the one expansion
+  // launch of all planes and then for each plane's K7 (describes nothing between calls)
+  ghf::DevBuf<ghf::DecTables> range_dt;
   // ghf_compress_batch without d_codes: one table set per item (describes nothing between calls)
   ghf::DevBuf<ghf_code> batch_codes;
   // ghf_compress_planes / ghf_decode_planes: elem_bytes byte planes at a stride rounded up to 256 bytes.  Private to the two

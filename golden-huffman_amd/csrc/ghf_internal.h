@@ -168,6 +168,10 @@ struct SeekExpandParams {
   uint32_t* seg_bit;
   int* status;
 };
+// the same blocks of up to GHF_PLANES_MAX streams of one n_symbols in one launch: plane[p] as above, with equal g0 and g1
+struct SeekExpandPlanesParams {
+  SeekExpandParams plane[GHF_PLANES_MAX];
+};
 // the part [lo, hi) of ONE block (hi <= the block's end) -> out[0 .. hi - lo)
 struct DecHeadParams {
   const uint8_t* stream;
@@ -427,6 +431,7 @@ void launch_sync_index(const SyncParams& p, uint64_t* d_seg_abs, uint64_t n_symb
 // ghf_seek.hip: the seek table and the range head
 void launch_seek_pack(const SeekPackParams& p, hipStream_t s);
 void launch_seek_expand(const SeekExpandParams& p, hipStream_t s);
+void launch_seek_expand_planes(const SeekExpandPlanesParams& a, uint32_t planes, hipStream_t s);
 void launch_decode_head(const DecHeadParams& p, hipStream_t s);
 // ghf_batch.hip
 void launch_compress_batch(const BatchCompressParams& p, uint32_t count, hipStream_t s);  // one launch, grid = count
@@ -454,6 +459,9 @@ void launch_planes_split(const uint8_t* d_in, uint64_t n_elems, uint32_t elem_by
 // d_status (may be null): the launch stores nothing when the word is non-zero
 void launch_planes_merge(const uint8_t* d_planes, uint64_t plane_stride, uint64_t n_elems, uint32_t elem_bytes, uint8_t* d_out,
                          const int* d_status, hipStream_t s);
+// elements [first, first + count) of the planes (count > 0); reads [first & ~15, (first + count + 15) & ~15) of every plane
+void launch_planes_merge_range(const uint8_t* d_planes, uint64_t plane_stride, uint64_t first, uint64_t count, uint32_t elem_bytes,
+                               uint8_t* d_out, const int* d_status, hipStream_t s);
 
 }  // namespace ghf
 #endif

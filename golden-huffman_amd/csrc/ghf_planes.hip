@@ -181,6 +181,69 @@ __global__ __launch_bounds__(kWave) void k_planes_merge(const uint8_t* __restric
   }
 }
 
+// bytes [skew, skew + 16) of the 32 bytes lo || hi, skew = 1 .. 15 and wave-uniform: the dword part of the skew picks five of
+// the eight dwords (two rounds of uniform v_cndmask_b32), the byte part funnels neighbours with v_alignbyte_b32
+__device__ __forceinline__ uint4 funnel16(const uint4& lo, const uint4& hi, uint32_t skew) {
+  const bool by1 = skew & 4u, by2 = skew & 8u;
+  const uint32_t y0 = by1 ? lo.y : lo.x, y1 = by1 ? lo.z : lo.y, y2 = by1 ? lo.w : lo.z, y3 = by1 ? hi.x : lo.w;
+  const uint32_t y4 = by1 ? hi.y : hi.x, y5 = by1 ? hi.z : hi.y, y6 = by1 ? hi.w : hi.z;
+  const uint32_t x0 = by2 ? y2 : y0, x1 = by2 ? y3 : y1, x2 = by2 ? y4 : y2, x3 = by2 ? y5 : y3, x4 = by2 ? y6 : y4;
+  const uint32_t b = skew & 3u;
+  return make_uint4(__builtin_amdgcn_alignbyte(x1, x0, b), __builtin_amdgcn_alignbyte(x2, x1, b),
+                    __builtin_amdgcn_alignbyte(x3, x2, b), __builtin_amdgcn_alignbyte(x4, x3, b));
+}
+
+// k_planes_merge for a run of elements that starts `skew` = 1 .. 15 bytes into a 16-byte vector of every plane (DESIGN.md
+// section 17): out[0 .. n_elems * E) <- elements [skew, skew + n_elems) of the planes.  `planes` itself is 16-byte aligned
+// (the caller has taken first & ~15 into it; skew == 0 is k_planes_merge's).  The same tiles, slabs, LDS rows and stores; on
+// the plane side a lane loads the two ALIGNED vectors that hold its 16 bytes and funnels them.  The second vector of the
+// last row of the last whole tile ends at or before the vector that holds element skew + n_elems - 1 (skew > 0), so
+// nothing outside [0, (skew + n_elems + 15) & ~15) of a plane is read.
+template <int E>
+__global__ __launch_bounds__(kWave) void k_planes_merge_range(const uint8_t* __restrict__ planes, uint64_t plane_stride, uint32_t skew,
+                                                              uint64_t n_elems, uint8_t* __restrict__ out,
+                                                              const int* __restrict__ status) {
+  using G = PlanesGeom<E>;
+  __shared__ uint4 tile[G::kRows * G::kRowVec];
+  if (status && __builtin_amdgcn_readfirstlane(*status) != 0) return;
+  const uint32_t lane = threadIdx.x;
+  skew = __builtin_amdgcn_readfirstlane(skew);
+  const Slab s = slab_of(n_elems, G::kTile);
+  for (uint64_t t = s.lo; t < s.end; ++t) {
+    uint4 lo[G::kRowsPerLane][E], hi[G::kRowsPerLane][E];
+#pragma unroll
+    for (int r = 0; r < G::kRowsPerLane; ++r)
+#pragma unroll
+      for (int b = 0; b < E; ++b) {
+        const uint4* v = reinterpret_cast<const uint4*>(planes + b * plane_stride) + t * G::kRows + r * kWave + lane;
+        lo[r][b] = ld16(v);
+        hi[r][b] = ld16(v + 1);
+      }
+#pragma unroll
+    for (int r = 0; r < G::kRowsPerLane; ++r) {
+      const uint32_t row = r * kWave + lane;
+      uint4 p[E], y[E];
+#pragma unroll
+      for (int b = 0; b < E; ++b) p[b] = funnel16(lo[r][b], hi[r][b], skew);
+      planes_to_row<E>(p, y);
+#pragma unroll
+      for (int j = 0; j < E; ++j) tile[row * G::kRowVec + j] = y[j];
+    }
+    wave_sync();
+    uint4* dst = reinterpret_cast<uint4*>(out) + t * (kWave * G::kVec);
+#pragma unroll
+    for (int j = 0; j < G::kVec; ++j) {
+      const uint32_t v = j * kWave + lane;
+      st16(dst + j * kWave + lane, tile[(v / E) * G::kRowVec + v % E]);
+    }
+    wave_sync();
+  }
+  for (uint64_t k = s.tail; k < n_elems; k += (uint64_t)gridDim.x * kWave) {
+#pragma unroll
+    for (int b = 0; b < E; ++b) out[k * E + b] = planes[b * plane_stride + skew + k];
+  }
+}
+
 // one resident round: kPlanesGroups one-wave workgroups, each with a slab of whole tiles; at least one lane per element of
 // the ragged end
 static uint32_t planes_grid(uint64_t n_elems, uint32_t elem_bytes) {
@@ -204,6 +267,18 @@ void launch_planes_merge(const uint8_t* d_planes, uint64_t plane_stride, uint64_
   if (elem_bytes == 2) hipLaunchKernelGGL(k_planes_merge<2>, grid, block, 0, s, d_planes, plane_stride, n_elems, d_out, d_status);
   else if (elem_bytes == 4) hipLaunchKernelGGL(k_planes_merge<4>, grid, block, 0, s, d_planes, plane_stride, n_elems, d_out, d_status);
   else hipLaunchKernelGGL(k_planes_merge<8>, grid, block, 0, s, d_planes, plane_stride, n_elems, d_out, d_status);
+}
+
+// elements [first, first + count) of the planes; a range that starts on a vector is k_planes_merge on the shifted planes
+void launch_planes_merge_range(const uint8_t* d_planes, uint64_t plane_stride, uint64_t first, uint64_t count, uint32_t elem_bytes,
+                               uint8_t* d_out, const int* d_status, hipStream_t s) {
+  const uint32_t skew = (uint32_t)(first & 15u);
+  const uint8_t* base = d_planes + (first - skew);
+  if (skew == 0) return launch_planes_merge(base, plane_stride, count, elem_bytes, d_out, d_status, s);
+  const dim3 grid(planes_grid(count, elem_bytes)), block(kWave);
+  if (elem_bytes == 2) hipLaunchKernelGGL(k_planes_merge_range<2>, grid, block, 0, s, base, plane_stride, skew, count, d_out, d_status);
+  else if (elem_bytes == 4) hipLaunchKernelGGL(k_planes_merge_range<4>, grid, block, 0, s, base, plane_stride, skew, count, d_out, d_status);
+  else hipLaunchKernelGGL(k_planes_merge_range<8>, grid, block, 0, s, base, plane_stride, skew, count, d_out, d_status);
 }
 
 }  // namespace ghf

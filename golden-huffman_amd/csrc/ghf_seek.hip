@@ -124,15 +124,18 @@ constexpr int kSeekThreads = 1024;
 // recorded end; lane 0 of a block writes chunk_bit and checks that the block's runs add up to the next record's start.
 // A table that fails either test, or names a bit outside the stream, latches GHF_E_CORRUPT.  Touches neither the ticket
 // counters nor `done` of DecTables.
-__global__ __launch_bounds__(kSeekThreads) void k_seek_expand(SeekExpandParams P) {
-  __shared__ DecLds L;
-  const int tid = threadIdx.x;
-  if (tid == 0) L.status0 = *P.status;
-  const int lut_bits = P.dt->lut_bits, max_len = P.dt->max_len, pair_bits = P.dt->pair_bits;
-  dec_lds_load(L, P.dt, tid, kSeekThreads);
-  __syncthreads();
-  if (L.status0 != 0) return;
-  const uint64_t r = P.g0 * kRunsPerBlock + (uint64_t)blockIdx.x * kSeekThreads + (uint32_t)tid;
+// r: the run, counted from the table's first block; L: the tables of P.dt, loaded by the caller.
+//
+// kRounds = false is k_seek_expand's walk: a SeekCursor per lane.  Its refills are data dependent, so in every step some lane
+// of the wave refills, and the wave waits for a vector load in every step: measured, 0.37 us per symbol, 0.19 ms for a run
+// whatever the range.  kRounds = true (k_seek_expand_planes; codes of up to 32 bits) walks in ROUNDS instead: all lanes
+// load their next vector in the same instruction, one round ahead, and a lane then decodes whatever starts inside the words
+// it has, with no memory access inside a round.  W holds two stream words and `o` the offset of the next code from W's top;
+// feeding a word drops W's upper word.  The walk opens with o = 64 + (the start bit's offset in its vector): the code "starts"
+// that far behind two words that are not there yet, and the first words fed only bring o down.
+template <bool kRounds>
+__device__ __forceinline__ void seek_expand_run(const SeekExpandParams& P, const DecLds& L, int lut_bits, int max_len, int pair_bits,
+                                                uint64_t r, int tid) {
   const uint64_t g = r >> 3;
   const uint32_t k = (uint32_t)r & 7u;
   if (g >= P.g1 || g >= P.n_blocks) return;
@@ -165,20 +168,88 @@ __global__ __launch_bounds__(kSeekThreads) void k_seek_expand(SeekExpandParams P
   }
   const DecLut T = dec_lut1(L.lut, lut_bits, pair_bits, tid & 63);
   SeekCursor c;
-  c.open(P.stream, P.stream_bytes, start + before);
   uint32_t used = 0, acc = 0;
+  if (kRounds && max_len <= 32) {
+    const uint64_t B = start + before;
+    c.s = P.stream;
+    c.bytes = P.stream_bytes;
+    c.full_bytes = P.stream_bytes & ~15ull;
+    uint64_t v = B >> 7;
+    uint4 cur = c.load(v), nxt = c.load(v + 1);
+    v += 2;
+    uint64_t W = 0;
+    uint32_t o = 64u + (uint32_t)(B & 127u), done = 0;
+    auto feed = [&](uint32_t nw) {
+      while (o < 32u && done < nsym) {
+        const uint32_t hi = win_peek(W, o);
+        uint32_t ent = dec_lookup(T, hi);
+        if (ent & kEntNone) ent = dec_long_entry(L, hi, lut_bits, max_len);
+        const uint32_t len = (ent >> 8) & 0xFFu;
+        acc |= ent;
+        used += len;
+        o += len;
+        ++done;
+        if ((done & (uint32_t)(kSegSymbols - 1)) == 0 || done == nsym) seg_out[(done - 1) / kSegSymbols] = before + used;
+      }
+      if (o >= 32u) {
+        W = (W << 32) | nw;
+        o -= 32u;
+      }
+    };
 #pragma unroll 1
-  for (uint32_t done = 0; done < nsym;) {
-    const uint32_t stop = done + (uint32_t)kSegSymbols < nsym ? done + (uint32_t)kSegSymbols : nsym;
-#pragma unroll 1
-    for (; done < stop; ++done) {
-      const uint32_t ent = c.step(L, T, lut_bits, max_len);
-      acc |= ent;
-      used += (ent >> 8) & 0xFFu;
+    while (__any(done < nsym)) {
+      const uint4 x = cur;
+      cur = nxt;
+      nxt = done < nsym ? c.load(v) : make_uint4(0, 0, 0, 0);
+      ++v;
+      feed(x.x);
+      feed(x.y);
+      feed(x.z);
+      feed(x.w);
     }
-    seg_out[(stop - 1) / kSegSymbols] = before + used;
+  } else {
+    c.open(P.stream, P.stream_bytes, start + before);
+#pragma unroll 1
+    for (uint32_t done = 0; done < nsym;) {
+      const uint32_t stop = done + (uint32_t)kSegSymbols < nsym ? done + (uint32_t)kSegSymbols : nsym;
+#pragma unroll 1
+      for (; done < stop; ++done) {
+        const uint32_t ent = c.step(L, T, lut_bits, max_len);
+        acc |= ent;
+        used += (ent >> 8) & 0xFFu;
+      }
+      seg_out[(stop - 1) / kSegSymbols] = before + used;
+    }
   }
   if (used != mine || (acc & (kEntEnd | kEntNone))) latch_status(P.status, GHF_E_CORRUPT);
+}
+
+__global__ __launch_bounds__(kSeekThreads) void k_seek_expand(SeekExpandParams P) {
+  __shared__ DecLds L;
+  const int tid = threadIdx.x;
+  if (tid == 0) L.status0 = *P.status;
+  const int lut_bits = P.dt->lut_bits, max_len = P.dt->max_len, pair_bits = P.dt->pair_bits;
+  dec_lds_load(L, P.dt, tid, kSeekThreads);
+  __syncthreads();
+  if (L.status0 != 0) return;
+  seek_expand_run<false>(P, L, lut_bits, max_len, pair_bits, P.g0 * kRunsPerBlock + (uint64_t)blockIdx.x * kSeekThreads + (uint32_t)tid, tid);
+}
+
+// The same for the covered blocks of up to GHF_PLANES_MAX streams in ONE launch (ghf_decode_planes_range; DESIGN.md
+// section 17): blockIdx.y names the stream, every stream has its own tables, and all of them cover the blocks [g0, g1) of
+// streams of one n_symbols.  A lane's walk over its 512 symbols is serial, so the launch cannot take less than one walk;
+// what it can avoid is paying that once per plane, and crowding sixteen waves onto one CU when the range is small: the
+// workgroup is as narrow as the launch's waves allow (launch_seek_expand_planes), down to one wave.
+__global__ __launch_bounds__(kSeekThreads) void k_seek_expand_planes(SeekExpandPlanesParams A) {
+  __shared__ DecLds L;
+  const SeekExpandParams& P = A.plane[blockIdx.y];
+  const int tid = threadIdx.x;
+  if (tid == 0) L.status0 = *P.status;
+  const int lut_bits = P.dt->lut_bits, max_len = P.dt->max_len, pair_bits = P.dt->pair_bits;
+  dec_lds_load(L, P.dt, tid, (int)blockDim.x);
+  __syncthreads();
+  if (L.status0 != 0) return;
+  seek_expand_run<true>(P, L, lut_bits, max_len, pair_bits, P.g0 * kRunsPerBlock + (uint64_t)blockIdx.x * blockDim.x + (uint32_t)tid, tid);
 }
 
 // The head of a range that does not begin on a block boundary: one wave, one lane per segment of the block, same tables;
@@ -228,6 +299,16 @@ void launch_seek_expand(const SeekExpandParams& p, hipStream_t s) {
   if (p.g1 <= p.g0) return;
   const uint64_t lanes = (p.g1 - p.g0) * kRunsPerBlock;
   hipLaunchKernelGGL(k_seek_expand, dim3((uint32_t)((lanes + kSeekThreads - 1) / kSeekThreads)), dim3(kSeekThreads), 0, s, p);
+}
+// one resident round where the range allows it: two workgroups of these tables fit on a CU, so up to 512 workgroups, each
+// of as few waves (1 .. 16) as that takes
+void launch_seek_expand_planes(const SeekExpandPlanesParams& a, uint32_t planes, hipStream_t s) {
+  const SeekExpandParams& p = a.plane[0];
+  if (p.g1 <= p.g0 || planes == 0) return;
+  const uint64_t lanes = (p.g1 - p.g0) * kRunsPerBlock, waves = (lanes + 63) / 64 * planes;
+  const uint64_t per = (waves + 511) / 512;
+  const uint32_t threads = 64u * (uint32_t)(per < 1 ? 1 : per > kSeekThreads / 64 ? kSeekThreads / 64 : per);
+  hipLaunchKernelGGL(k_seek_expand_planes, dim3((uint32_t)((lanes + threads - 1) / threads), planes), dim3(threads), 0, s, a);
 }
 void launch_decode_head(const DecHeadParams& p, hipStream_t s) {
   if (p.hi <= p.lo) return;

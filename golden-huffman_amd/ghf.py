@@ -145,6 +145,7 @@ EXPORTS = [
     "ghf_compress_batch_planes_shared", "ghf_decode_batch_planes_shared", "ghf_decode_bodies_batch_planes_shared",
     "ghf_batch_seek_bytes", "ghf_batch_seek_bound", "ghf_batch_seek_pack", "ghf_decode_bodies_batch_shared_seek",
     "ghf_decode_bodies_batch_planes_shared_seek",
+    "ghf_planes_merge_range", "ghf_decode_planes_range",
 ]
 COMM_ID_BYTES = 128
 
@@ -274,6 +275,9 @@ def lib():
     L.ghf_batch_seek_pack.argtypes = [vp, C.POINTER(BatchIndex), vp, u32, u32, vp, vp, vp, vp]
     L.ghf_decode_bodies_batch_shared_seek.argtypes = [vp, vp, vp, vp, vp, vp, u32, vp, vp, vp, vp]
     L.ghf_decode_bodies_batch_planes_shared_seek.argtypes = [vp, vp, vp, vp, vp, vp, u32, u32, vp, vp, vp, vp]
+    L.ghf_planes_merge_range.argtypes = [vp, vp, sz, sz, sz, u32, vp]
+    L.ghf_decode_planes_range.argtypes = [vp, C.POINTER(vp), C.POINTER(sz), vp, C.POINTER(Index), C.POINTER(SeekInfo),
+                                          C.POINTER(vp), C.POINTER(sz), u32, u64, u64, vp, sz]
     _lib = L
     return L
 
@@ -1063,6 +1067,36 @@ class Context:
                                      d_out.numel() if cap is None else cap, nbytes.data_ptr()),
             "ghf_decode_planes")
         return d_out, nbytes
+
+    def planes_merge_range(self, d_planes, plane_stride, first, count, elem_bytes, d_out=None):
+        """elements [first, first + count) of the planes, interleaved.  -> d_out uint8[count * elem_bytes]"""
+        if d_out is None:
+            d_out = self.empty_u8(count * elem_bytes)
+        self._chk(self.L.ghf_planes_merge_range(self.h, d_planes.data_ptr(), plane_stride, first, count, elem_bytes,
+                                                d_out.data_ptr()), "ghf_planes_merge_range")
+        return d_out
+
+    def decode_planes_range(self, streams, stream_bytes, d_codes, elem_bytes, first, count, indexes=None, infos=None,
+                            d_tables=None, table_bytes=None, d_out=None, cap=None):
+        """d_out[0 .. count * elem_bytes) = elements [first, first + count) of the planes' decoded elements.  streams,
+        stream_bytes, d_codes as for decode_planes; give either indexes (planes_index_alloc) or infos (elem_bytes SeekInfo)
+        with d_tables (elem_bytes CUDA uint8 tensors).  Never synchronises.  -> d_out uint8"""
+        ptrs = (C.c_void_p * elem_bytes)(*[x.data_ptr() for x in streams])
+        sizes = (C.c_size_t * elem_bytes)(*[int(v) for v in stream_bytes])
+        h_infos = t_ptrs = t_bytes = None
+        if infos is not None:
+            h_infos = (SeekInfo * elem_bytes)(*infos)
+            t_ptrs = (C.c_void_p * elem_bytes)(*[x.data_ptr() for x in d_tables])
+            if table_bytes is None:
+                table_bytes = [seek_bytes(i.n_symbols) for i in infos]
+            t_bytes = (C.c_size_t * elem_bytes)(*[int(v) for v in table_bytes])
+        if d_out is None:
+            d_out = self.empty_u8(count * elem_bytes)
+        self._chk(
+            self.L.ghf_decode_planes_range(self.h, ptrs, sizes, d_codes.data_ptr(), indexes, h_infos, t_ptrs, t_bytes, elem_bytes,
+                                           first, count, d_out.data_ptr(), d_out.numel() if cap is None else cap),
+            "ghf_decode_planes_range")
+        return d_out
 
     # ---- seekable streams: the seek table (the persistent form of the side-car) ----------------
     def seek_pack(self, index, d_stream=None, stream_bytes=0, d_table=None, n=None):

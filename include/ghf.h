@@ -690,6 +690,44 @@ int ghf_decode_bodies_batch_planes_shared_seek(ghf_ctx* ctx, const uint8_t* cons
                                                uint32_t elem_bytes, uint8_t* const* d_out_ptrs /* [count] */,
                                                const uint64_t* d_out_caps, uint64_t* d_out_bytes, int* d_item_status /* [count] */);
 
+/* ---- byte planes: an element range ---------------------------------------------
+ * No reference counterpart (generalises the flat output of include/compressor.h:87-92).  ghf_planes_merge for elements
+ * [first, first + count) of the planes: d_out[0 .. count * elem_bytes) receives them and nothing else is written.
+ * d_planes, plane_stride and d_out are 16-byte aligned as for ghf_planes_merge; first is arbitrary.  Only bytes
+ * [first & ~15, (first + count + 15) & ~15) of a plane are read, and these must lie inside plane_stride.  Asynchronous on
+ * the stream; does not look at the context's status word.  Checked before anything touches HIP: a null context or pointer,
+ * another elem_bytes, misalignment, first + count or count * elem_bytes beyond size_t: GHF_E_INVAL; then count == 0:
+ * GHF_E_EMPTY; then plane_stride < first + count: GHF_E_CAP.  One streaming kernel of ghf_planes_merge's shape; a first that
+ * is no multiple of 16 costs a second aligned 16-byte load per plane vector and a byte funnel in registers. */
+int ghf_planes_merge_range(ghf_ctx* ctx, const uint8_t* d_planes, size_t plane_stride, size_t first, size_t count,
+                           uint32_t elem_bytes, uint8_t* d_out);
+
+/* No reference counterpart: Decompressor::decompress(), include/compressor.h:87-92, for a part of a typed tensor.
+ * d_out[0 .. count * elem_bytes) receives elements [first, first + count) of what the elem_bytes plane images decode to:
+ * every plane is decoded from the start of the 4096-symbol block that holds `first` into the context's workspace (as
+ * ghf_decode_range does it; from tables one launch expands the covered blocks of all planes), then ghf_planes_merge_range
+ * takes the part asked for.  Asynchronous on the stream, never synchronises.  h_stream_ptrs / h_stream_bytes / d_codes
+ * are those of ghf_decode_planes (HOST arrays of elem_bytes entries, d_codes on the device).  Exactly one source of
+ * block starts is given, the other is NULL:
+ *   indexes                                  elem_bytes live side-cars (a HOST array);
+ *   (h_infos, h_table_ptrs, h_table_bytes)   elem_bytes parsed seek tables (HOST arrays); the table images are DEVICE
+ *                                            memory, 16-byte aligned.  Only the covered blocks are expanded.
+ * n_elems is what the side-cars or tables say; all of them must agree.  A stream that has neither is not served here: index
+ * it once with ghf_decoded_size + ghf_seek_pack(index = NULL) and keep the table.
+ * Checked in this order, all before anything is queued: a null context or required pointer, another elem_bytes, both
+ * sources or neither, a stream / table / output pointer that is null or misaligned, a malformed index, planes that disagree
+ * on n_symbols, first + count > n_elems, count * elem_bytes beyond size_t: GHF_E_INVAL; a table whose table_bytes is not what
+ * its header implies (any plane): GHF_E_FORMAT; cap < count * elem_bytes: GHF_E_CAP; count == 0: GHF_OK, nothing queued (the
+ * rule of ghf_decode_range).
+ * As in ghf_decode_planes the merge stores nothing when a decode before it latched GHF_E_CORRUPT or GHF_E_FORMAT; ghf_sync
+ * reports the status.  From side-cars the context's caches are left as ghf_decode_range leaves them (the tables of
+ * ghf_decode_prepare are forgotten); from seek tables the call builds its tables in a buffer of its own and does not touch
+ * the prepared tables. */
+int ghf_decode_planes_range(ghf_ctx* ctx, const uint8_t* const* h_stream_ptrs, const size_t* h_stream_bytes,
+                            const ghf_code* d_codes, const ghf_index* indexes, const ghf_seek_info* h_infos,
+                            const uint8_t* const* h_table_ptrs, const size_t* h_table_bytes, uint32_t elem_bytes,
+                            uint64_t first, uint64_t count, uint8_t* d_out, size_t cap);
+
 /* Multi-GPU decode of a stream that has no side-car ("per-rank self-sync + one all-gather of symbol
  * counts"; the reference's decoders, canonical_huff_encoder.cc:377-568, are single-stream).  The caller cuts the body
  * at byte positions; a rank's piece is its own bytes followed by >= 8 bytes of look-ahead from the next piece (zeros
