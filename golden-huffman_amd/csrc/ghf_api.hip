@@ -104,6 +104,9 @@ int ghf_ctx_create(int device, ghf_ctx** out) {
   GHF_STEP(hipMalloc(&c->d_dt, sizeof(DecTables)));
   GHF_STEP(hipMalloc(&c->d, sizeof(Scalars)));
   GHF_STEP(hipHostMalloc(&c->h, sizeof(Scalars), hipHostMallocDefault));
+  GHF_STEP(hipMalloc(&c->d_planes_hist_acc, kPlanesHistAccWords * sizeof(uint64_t)));
+  GHF_STEP(hipMemset(c->d_planes_hist_acc, 0, kPlanesHistAccWords * sizeof(uint64_t)));
+  GHF_STEP(hipMalloc(&c->d_planes_hists, (size_t)GHF_PLANES_MAX * GHF_NSYM * sizeof(uint64_t)));
   GHF_STEP(hipMemset(c->d_status, 0, sizeof(int)));
 #undef GHF_STEP
   if (e != hipSuccess) {
@@ -127,6 +130,8 @@ int ghf_ctx_destroy(ghf_ctx* c) {
   if (c->d_code) (void)hipFree(c->d_code);
   if (c->d_tree) (void)hipFree(c->d_tree);
   if (c->d_dt) (void)hipFree(c->d_dt);
+  if (c->d_planes_hist_acc) (void)hipFree(c->d_planes_hist_acc);
+  if (c->d_planes_hists) (void)hipFree(c->d_planes_hists);
   if (c->d) (void)hipFree(c->d);
   if (c->h) (void)hipHostFree(c->h);
   release(c->chunk_hist);
@@ -1348,6 +1353,84 @@ int ghf_compress_planes(ghf_ctx* c, const uint8_t* d_in, size_t n_elems, uint32_
     rc = ghf_compress(c, c->planes.p + p * stride, n_elems, d_out + p * slot_bytes, slot_bytes, d_out_bytes + p,
                       d_codes ? d_codes + p : nullptr, indexes ? indexes + p : nullptr);
   // the workspace is private and the next call refills the same addresses with other bytes
+  c->hist.forget();
+  c->plan.forget();
+  return rc;
+}
+
+// ---------------------------------------------------------------------------------------------- byte planes in stages
+// (no reference counterpart)
+// k_histogram_planes and its finish on the stream.  The finish is what leaves the replicas zero for the next call: if it
+// cannot be queued behind a counting launch that was, a memset takes its place before the error is returned
+static int histogram_planes_into(ghf_ctx* c, const char* who, const uint8_t* d_in, size_t n_elems, uint32_t elem_bytes, unsigned flags,
+                                 uint64_t* d_hists) {
+  const hipError_t e = launch_histogram_planes(d_in, n_elems, elem_bytes, flags, c->d_planes_hist_acc, d_hists, c->stream);
+  if (e == hipSuccess) return GHF_OK;
+  (void)hipMemsetAsync(c->d_planes_hist_acc, 0, kPlanesHistAccWords * sizeof(uint64_t), c->stream);
+  return fail(c, GHF_E_HIP, who, e);
+}
+
+int ghf_histogram_planes(ghf_ctx* c, const uint8_t* d_in, size_t n_elems, uint32_t elem_bytes, unsigned flags, uint64_t* d_hists) {
+  if (!c || !d_in || !d_hists) return GHF_E_INVAL;
+  if (!elem_bytes_ok(elem_bytes)) return fail(c, GHF_E_INVAL, "ghf_histogram_planes: elem_bytes must be 2, 4 or 8");
+  if (!aligned16(d_in)) return fail(c, GHF_E_INVAL, "ghf_histogram_planes: d_in must be 16-byte aligned");
+  if (flags & ~GHF_HIST_COVER_ALL) return fail(c, GHF_E_INVAL, "ghf_histogram_planes: unknown flags");
+  if (elems_overflow(n_elems, elem_bytes)) return fail(c, GHF_E_INVAL, "ghf_histogram_planes: n_elems * elem_bytes overflows");
+  if (n_elems == 0) return fail(c, GHF_E_EMPTY, "ghf_histogram_planes: no elements");
+  GHF_HIP(c, hipSetDevice(c->device));
+  return histogram_planes_into(c, "ghf_histogram_planes: launch", d_in, n_elems, elem_bytes, flags, d_hists);
+}
+
+int ghf_planes_image_bytes(ghf_ctx* c, const uint64_t* d_hists, const ghf_code* d_codes, uint32_t elem_bytes, uint64_t* d_bytes) {
+  if (!c || !d_hists || !d_codes || !d_bytes) return GHF_E_INVAL;
+  if (!elem_bytes_ok(elem_bytes)) return fail(c, GHF_E_INVAL, "ghf_planes_image_bytes: elem_bytes must be 2, 4 or 8");
+  GHF_HIP(c, hipSetDevice(c->device));
+  launch_planes_image_bytes(d_hists, d_codes, elem_bytes, d_bytes, c->stream);
+  GHF_HIP(c, hipGetLastError());
+  return GHF_OK;
+}
+
+int ghf_compress_planes_coded(ghf_ctx* c, const uint8_t* d_in, size_t n_elems, uint32_t elem_bytes, ghf_code* d_codes, unsigned flags,
+                              uint8_t* d_out, size_t slot_bytes, uint64_t* d_out_bytes, const ghf_index* indexes) {
+  if (!c || !d_in || !d_out || !d_out_bytes || !d_codes) return GHF_E_INVAL;
+  if (!elem_bytes_ok(elem_bytes)) return fail(c, GHF_E_INVAL, "ghf_compress_planes_coded: elem_bytes must be 2, 4 or 8");
+  if (!aligned16(d_in) || !aligned16(d_out) || (slot_bytes & 15u) || !aligned16(d_codes))
+    return fail(c, GHF_E_INVAL, "ghf_compress_planes_coded: d_in, d_out, d_codes and slot_bytes must be multiples of 16");
+  if (flags & ~GHF_PLANES_BUILD_CODES) return fail(c, GHF_E_INVAL, "ghf_compress_planes_coded: unknown flags");
+  if (workspace_overflow(n_elems, elem_bytes)) return fail(c, GHF_E_INVAL, "ghf_compress_planes_coded: n_elems * elem_bytes overflows");
+  for (uint32_t p = 0; indexes && p < elem_bytes; ++p)
+    if (indexes[p].n_symbols != n_elems || !index_has_arrays(&indexes[p]))
+      return fail(c, GHF_E_INVAL, "ghf_compress_planes_coded: an index does not match n_elems (use ghf_index_alloc)");
+  if (n_elems == 0) return fail(c, GHF_E_EMPTY, "ghf_compress_planes_coded: no elements");
+  if (slot_bytes < ghf_planes_slot_bytes(n_elems))
+    return fail(c, GHF_E_CAP, "ghf_compress_planes_coded: slot_bytes below ghf_planes_slot_bytes(n_elems)");
+  GHF_HIP(c, hipSetDevice(c->device));
+  size_t stride = 0;
+  int rc = planes_workspace(c, n_elems, elem_bytes, &stride);
+  if (rc) return rc;
+  // compressor.h:63 for all planes in one pass over the interleaved buffer, then compressor.h:64 for all planes in one launch --
+  // or the caller's codes, held against the counts
+  if ((rc = histogram_planes_into(c, "ghf_compress_planes_coded: histogram launch", d_in, n_elems, elem_bytes, 0, c->d_planes_hists))) return rc;
+  if (flags & GHF_PLANES_BUILD_CODES) {
+    if ((rc = ghf_build_codes(c, c->d_planes_hists, elem_bytes, d_codes, 0))) return rc;
+  } else {
+    launch_planes_vet_codes(c->d_planes_hists, d_codes, elem_bytes, c->d_status, c->stream);
+    GHF_HIP(c, hipGetLastError());
+  }
+  launch_planes_split(d_in, n_elems, elem_bytes, c->planes.p, stride, c->stream);
+  GHF_HIP(c, hipGetLastError());
+  // K1 has not seen these planes: whatever it remembers about an address inside the workspace is of another call, and the
+  // planner counts each plane itself (k_chunk_bits_direct)
+  c->hist.forget();
+  for (uint32_t p = 0; p < elem_bytes && !rc; ++p) {  // compressor.h:70-72, once per plane: what ghf_compress_ex does behind its code build
+    const uint8_t* plane = c->planes.p + p * stride;
+    if ((rc = ghf_encode_plan(c, plane, n_elems, d_codes + p, &c->d->total_bits))) break;
+    if ((rc = ghf_encode_emit(c, plane, n_elems, d_codes + p, nullptr, GHF_EMIT_LAST | GHF_EMIT_HEADER, d_out + p * slot_bytes, slot_bytes,
+                              indexes ? indexes + p : nullptr, c->d->end)))
+      break;
+    launch_store_u64(d_out_bytes + p, &c->d->end[1], 0, c->stream);
+    GHF_HIP(c, hipGetLastError());
+  }
   c->hist.forget();
   c->plan.forget();
   return rc;

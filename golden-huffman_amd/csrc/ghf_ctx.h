@@ -141,6 +141,13 @@ struct ghf_ctx {
   // ghf_compress_planes / ghf_decode_planes: elem_bytes byte planes at a stride rounded up to 256 bytes.  Private to the two
   // calls and rewritten by each: what K1 and K4 remember about an address inside it is forgotten before the call returns
   ghf::DevBuf<uint8_t> planes;
+  // ghf_histogram_planes / ghf_compress_planes_coded: the 32 replicas k_histogram_planes adds its totals into (zero between
+  // launches), and the E x 257 counts of the tensor a ghf_compress_planes_coded is working on (describe nothing between calls).
+  // The replicas are zeroed by k_histogram_planes_finish, the launch behind every counting launch: the invariant holds as
+  // long as that pair is queued whole.  Where the second launch fails, the host queues a memset of the replicas instead
+  // (histogram_planes_into, ghf_api.hip), so that a later histogram on this context does not start from stale sums.
+  uint64_t* d_planes_hist_acc = nullptr;
+  uint64_t* d_planes_hists = nullptr;  // [GHF_PLANES_MAX][257]
   // ghf_decode_images_batch_stats: where the image decoder counts its rounds and passes (the caller's; null = nowhere)
   uint64_t* images_stats = nullptr;
   std::string err;

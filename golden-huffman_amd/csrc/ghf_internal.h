@@ -49,6 +49,15 @@ constexpr uint32_t kPlanesLdsBytes = 9 * 1024;    // per workgroup: 64 rows of (
 __host__ __device__ constexpr inline uint32_t planes_tile_elems(uint32_t elem_bytes) {
   return (uint32_t)kWave * (elem_bytes < 4 ? 4 : elem_bytes) * 16 / elem_bytes;
 }
+// the one-pass plane histograms (ghf_planes_hist.hip): K1's 32 KiB of u32 counters, bins[256][32], whose
+// 32 columns are E planes x 32 / E replicas
+constexpr int kPlanesHistThreads = 256;
+constexpr int kPlanesHistCols = 32;
+constexpr uint32_t kPlanesHistGroups = 256 * 4;    // one resident round: 4 workgroups on each of the 256 CUs, as K1
+constexpr uint32_t kPlanesHistTileVecs = kPlanesHistThreads * 4;  // a tile: four 16-byte vectors per thread, 16 KiB
+constexpr uint32_t kPlanesHistFlushTiles = 3;      // u32 counters -> u64 sums every 48 KiB of a workgroup's input (K1: every chunk)
+static_assert((uint64_t)(kPlanesHistFlushTiles + 1) * kPlanesHistTileVecs * 16 < (1ull << 32), "a u32 counter never wraps between two flushes");
+constexpr size_t kPlanesHistAccWords = 32 * GHF_PLANES_MAX * 256;  // 32 replicas of the E x 256 totals, all zero between launches
 
 // the .crs2 header: the count word, symbol[257], min_len, max_len, then a (start_pos, first_code) row per length 1..max_len
 constexpr uint64_t kHeaderFixedBytes = 4 * (GHF_NSYM + 3);  // 1040
@@ -462,6 +471,15 @@ void launch_planes_merge(const uint8_t* d_planes, uint64_t plane_stride, uint64_
 // elements [first, first + count) of the planes (count > 0); reads [first & ~15, (first + count + 15) & ~15) of every plane
 void launch_planes_merge_range(const uint8_t* d_planes, uint64_t plane_stride, uint64_t first, uint64_t count, uint32_t elem_bytes,
                                uint8_t* d_out, const int* d_status, hipStream_t s);
+// ghf_planes_hist.hip: elem_bytes is 2, 4 or 8, n_elems > 0, d_in 16-byte aligned.  d_acc: kPlanesHistAccWords words, zero
+// between launches.  Two launches: the counting kernel, then the finish (replica sums, slot 256, GHF_HIST_COVER_ALL), which
+// is also what zeroes d_acc again.  -> the first launch error; after an error of the finish launch d_acc is the caller's to clear
+hipError_t launch_histogram_planes(const uint8_t* d_in, uint64_t n_elems, uint32_t elem_bytes, uint32_t flags, uint64_t* d_acc,
+                                   uint64_t* d_hists, hipStream_t s);
+// d_bytes[p] <- image size of counts d_hists[p] under d_codes[p]; 0: the code is not complete or misses a counted byte
+void launch_planes_image_bytes(const uint64_t* d_hists, const ghf_code* d_codes, uint32_t elem_bytes, uint64_t* d_bytes, hipStream_t s);
+// latches GHF_E_FORMAT (a code is not a complete prefix code) or GHF_E_NOCODE (a counted byte has no code) at *d_status
+void launch_planes_vet_codes(const uint64_t* d_hists, const ghf_code* d_codes, uint32_t elem_bytes, int* d_status, hipStream_t s);
 
 }  // namespace ghf
 #endif

@@ -19,6 +19,13 @@ PLANES_ELEM_BYTES = (2, 4, 8)
 # Tests size their ragged and second-round cases with them; nothing in the library's behaviour depends on them.
 PLANES_TILE = {2: 2048, 4: 1024, 8: 1024}
 PLANES_GROUPS = 256 * 16
+# ghf_internal.h kPlanesHistGroups / kPlanesHistTileVecs * 16 / kPlanesHistFlushTiles: the persistent workgroups of
+# k_histogram_planes, the bytes of one of its tiles, and the tiles between two flushes of a workgroup's u32 counters (tests
+# size their second-round and past-the-flush cases with them; tests/test_planes_coded_cpu.py holds them against the source)
+PLANES_HIST_GROUPS = 256 * 4
+PLANES_HIST_TILE_BYTES = 16384
+PLANES_HIST_FLUSH_TILES = 3
+PLANES_BUILD_CODES = 1  # GHF_PLANES_BUILD_CODES (ghf_compress_planes_coded): d_codes is filled from the tensor's own counts
 EMPTY_OK = 2  # opt-in: n == 0 -> header of the one-symbol code + 0x7F (builder's definition, parity unpinned)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -146,6 +153,7 @@ EXPORTS = [
     "ghf_batch_seek_bytes", "ghf_batch_seek_bound", "ghf_batch_seek_pack", "ghf_decode_bodies_batch_shared_seek",
     "ghf_decode_bodies_batch_planes_shared_seek",
     "ghf_planes_merge_range", "ghf_decode_planes_range",
+    "ghf_histogram_planes", "ghf_planes_image_bytes", "ghf_compress_planes_coded",
 ]
 COMM_ID_BYTES = 128
 
@@ -275,6 +283,9 @@ def lib():
     L.ghf_batch_seek_pack.argtypes = [vp, C.POINTER(BatchIndex), vp, u32, u32, vp, vp, vp, vp]
     L.ghf_decode_bodies_batch_shared_seek.argtypes = [vp, vp, vp, vp, vp, vp, u32, vp, vp, vp, vp]
     L.ghf_decode_bodies_batch_planes_shared_seek.argtypes = [vp, vp, vp, vp, vp, vp, u32, u32, vp, vp, vp, vp]
+    L.ghf_histogram_planes.argtypes = [vp, vp, sz, u32, C.c_uint, vp]
+    L.ghf_planes_image_bytes.argtypes = [vp, vp, vp, u32, vp]
+    L.ghf_compress_planes_coded.argtypes = [vp, vp, sz, u32, vp, C.c_uint, vp, sz, vp, C.POINTER(Index)]
     L.ghf_planes_merge_range.argtypes = [vp, vp, sz, sz, sz, u32, vp]
     L.ghf_decode_planes_range.argtypes = [vp, C.POINTER(vp), C.POINTER(sz), vp, C.POINTER(Index), C.POINTER(SeekInfo),
                                           C.POINTER(vp), C.POINTER(sz), u32, u64, u64, vp, sz]
@@ -1050,6 +1061,46 @@ class Context:
             self.L.ghf_compress_planes(self.h, d_in.data_ptr(), n_elems, elem_bytes, d_out.data_ptr(), slot_bytes,
                                        out_bytes.data_ptr(), d_codes.data_ptr(), indexes),
             "ghf_compress_planes")
+        return {"out": d_out, "slot_bytes": slot_bytes, "out_bytes": out_bytes, "codes": d_codes, "n_elems": n_elems,
+                "elem_bytes": elem_bytes}
+
+    def histogram_planes(self, d_in, elem_bytes, n_elems=None, flags=0, out=None):
+        """the byte counts of every byte plane of one tensor, in one pass: an int64[elem_bytes, 257] CUDA tensor, ready for
+        build_codes.  flags: HIST_COVER_ALL.  No host synchronisation."""
+        n_elems = d_in.numel() * d_in.element_size() // elem_bytes if n_elems is None else n_elems
+        hists = self.torch.empty((elem_bytes, NSYM), dtype=self.torch.int64, device=self.device) if out is None else out
+        self._chk(self.L.ghf_histogram_planes(self.h, d_in.data_ptr(), n_elems, elem_bytes, flags, hists.data_ptr()),
+                  "ghf_histogram_planes")
+        return hists
+
+    def planes_image_bytes(self, d_hists, d_codes, elem_bytes, out=None):
+        """what planes with the counts d_hists (int64[elem_bytes, 257]) compress to under d_codes: int64[elem_bytes], 0 for
+        a plane whose code is not complete or misses a counted byte.  No host synchronisation."""
+        nbytes = self.torch.zeros(elem_bytes, dtype=self.torch.int64, device=self.device) if out is None else out
+        self._chk(self.L.ghf_planes_image_bytes(self.h, d_hists.data_ptr(), d_codes.data_ptr(), elem_bytes, nbytes.data_ptr()),
+                  "ghf_planes_image_bytes")
+        return nbytes
+
+    def compress_planes_coded(self, d_in, elem_bytes, d_codes=None, flags=None, n_elems=None, d_out=None, slot_bytes=None,
+                              indexes=None):
+        """compress_planes with one histogram pass and the codes either built in one launch (d_codes None or flags
+        PLANES_BUILD_CODES: they are returned) or brought by the caller (d_codes uint8[elem_bytes, sizeof(Code)], flags 0).
+        No host synchronisation.  -> the dict of compress_planes"""
+        t = self.torch
+        n_elems = d_in.numel() * d_in.element_size() // elem_bytes if n_elems is None else n_elems
+        if flags is None:
+            flags = PLANES_BUILD_CODES if d_codes is None else 0
+        if slot_bytes is None:
+            slot_bytes = planes_slot_bytes(n_elems)
+        if d_out is None:
+            d_out = self.empty_u8(slot_bytes * elem_bytes)
+        if d_codes is None:
+            d_codes = t.zeros((elem_bytes, C.sizeof(Code)), dtype=t.uint8, device=self.device)
+        out_bytes = t.zeros(elem_bytes, dtype=t.int64, device=self.device)
+        self._chk(
+            self.L.ghf_compress_planes_coded(self.h, d_in.data_ptr(), n_elems, elem_bytes, d_codes.data_ptr(), flags,
+                                             d_out.data_ptr(), slot_bytes, out_bytes.data_ptr(), indexes),
+            "ghf_compress_planes_coded")
         return {"out": d_out, "slot_bytes": slot_bytes, "out_bytes": out_bytes, "codes": d_codes, "n_elems": n_elems,
                 "elem_bytes": elem_bytes}
 

@@ -35,7 +35,8 @@ enum ghf_status_code {
   GHF_E_NOMEM = 8,
   GHF_E_SINGLE = 9, /* .crs only: one distinct byte value -- the lone leaf gets the empty code and the reference's
                        decoder dereferences a NULL child (include/huff_tree.cc:255-271); undefined there, refused here */
-  GHF_E_NOCODE = 10 /* shared-code batches: an item holds a byte value to which the shared code gives no code */
+  GHF_E_NOCODE = 10 /* shared-code batches: an item holds a byte value to which the shared code gives no code;
+                       ghf_compress_planes_coded: a plane holds a byte value to which the caller's d_codes[p] gives none */
 };
 
 /* The encoder's tables -- mirrors the private members of CanonicalHuffEncoder,
@@ -523,6 +524,52 @@ int ghf_compress_planes(ghf_ctx* ctx, const uint8_t* d_in, size_t n_elems, uint3
 int ghf_decode_planes(ghf_ctx* ctx, const uint8_t* const* h_stream_ptrs, const size_t* h_stream_bytes,
                       const ghf_code* d_codes, const ghf_index* indexes, size_t n_elems, uint32_t elem_bytes, uint8_t* d_out,
                       size_t cap, uint64_t* d_out_bytes);
+
+/* ---- byte planes in stages: the plane histograms of one large typed buffer in one pass, what
+ * it would compress to, and compression under codes the caller brings.  Conventions and call-level errors are those of
+ * the byte-plane calls above. */
+
+/* No reference counterpart (generalises the flat count of include/encoder.h:123-150, which include/compressor.h:62-73
+ * runs once per file).  Asynchronous on the stream, never synchronises; one pass over d_in[0 .. n_elems * elem_bytes),
+ * nothing behind it is read: d_hists[p][0 .. 255] (device u64[elem_bytes][257], overwritten) <- the counts of the bytes
+ * d_in[p], d_in[p + E], ..., exactly what ghf_histogram gives for plane p of ghf_planes_split; d_hists[p][256] = 1.  flags:
+ * GHF_HIST_COVER_ALL, honoured per plane.  Leaves the context's caches alone.  A null context or pointer, another
+ * elem_bytes, d_in not 16-byte aligned, unknown flags, n_elems * elem_bytes beyond size_t: GHF_E_INVAL; then n_elems == 0:
+ * GHF_E_EMPTY; nothing queued. */
+int ghf_histogram_planes(ghf_ctx* ctx, const uint8_t* d_in, size_t n_elems, uint32_t elem_bytes, unsigned flags,
+                         uint64_t* d_hists /* [elem_bytes][257] */);
+
+/* No reference counterpart (include/compressor.h:62-73 learns a file's compressed size by compressing it; the sum is
+ * the one include/encoder.h:123-150 would make over the counts).  Asynchronous, never synchronises, one tiny launch:
+ * d_bytes[p] (device u64[elem_bytes]) <- ghf_header_bytes(max_len of d_codes[p]) + ceil((sum over b < 256 of d_hists[p][b] *
+ * length_p[b] + length_p[256]) / 8), the exact size of the image any compress call writes for a plane with these counts
+ * under that code; 0 when d_codes[p] is not a complete prefix code or gives no code to a byte with a non-zero count (or
+ * to the end mark).  Latches nothing, leaves the context's caches alone.  A null context or pointer, another elem_bytes:
+ * GHF_E_INVAL. */
+int ghf_planes_image_bytes(ghf_ctx* ctx, const uint64_t* d_hists /* [elem_bytes][257] */, const ghf_code* d_codes,
+                           uint32_t elem_bytes, uint64_t* d_bytes /* [elem_bytes] */);
+
+/* No reference counterpart: Compressor::compress(), include/compressor.h:62-73, once per byte plane, with its count
+ * (include/encoder.h:123-150) made for all planes in one pass and its code either built for all planes in one launch or
+ * brought by the caller.  Arguments, their checks and the order of the checks are ghf_compress_planes'; in addition d_codes
+ * (device, [elem_bytes]) is required -- null or not 16-byte aligned: GHF_E_INVAL -- and unknown flags are GHF_E_INVAL.
+ * Asynchronous on the stream, never synchronises.  On the stream: ghf_histogram_planes into counters of the context; the
+ * codes (below); ghf_planes_split into the context's workspace; per plane ghf_encode_plan and ghf_encode_emit(GHF_EMIT_HEADER |
+ * GHF_EMIT_LAST, indexes[p]) into d_out + p * slot_bytes, d_out_bytes[p] <- the image's size.  The plan and histogram caches
+ * of the context are forgotten, as by ghf_compress_planes.
+ * GHF_PLANES_BUILD_CODES: d_codes is OUT, filled by one ghf_build_codes launch from the counts; every image, size, code and
+ * side-car is then byte for byte what ghf_compress_planes writes.
+ * Without it d_codes is IN (trained on another tensor, parsed from a stored header): plane p's image is
+ * ghf_write_header(d_codes + p) followed by the body under that code, an ordinary .crs2 that the reference, ghf_decode,
+ * ghf_decode_planes, the seek table and the range calls read.  The codes are vetted on the device first: one that is not a
+ * complete prefix code latches GHF_E_FORMAT on the context's status word, a plane that holds a byte value to which its code
+ * gives no code latches GHF_E_NOCODE (train with GHF_HIST_COVER_ALL to rule that out).
+ * A latched status stops everything behind it: nothing reaches d_out, d_out_bytes is UNSPECIFIED; ghf_sync reports the
+ * status and ghf_clear_status makes the context usable again. */
+#define GHF_PLANES_BUILD_CODES 1u
+int ghf_compress_planes_coded(ghf_ctx* ctx, const uint8_t* d_in, size_t n_elems, uint32_t elem_bytes,
+                              ghf_code* d_codes /* [elem_bytes] 16-byte aligned: in or out with BUILD_CODES */, unsigned flags,
+                              uint8_t* d_out, size_t slot_bytes, uint64_t* d_out_bytes, const ghf_index* indexes);
 
 /* ---- shared-code batches of typed elements: one code per byte plane for many small items -------------
  * No reference counterpart (the reference compresses one flat run of bytes per process, include/compressor.h:62-73, and
