@@ -1280,13 +1280,25 @@ static inline bool elems_overflow(size_t n_elems, uint32_t e) { return n_elems >
 // ... and for the calls that go through the workspace, whose planes sit at n_elems rounded up to 256
 static inline bool workspace_overflow(size_t n_elems, uint32_t e) { return elems_overflow(n_elems, e) || elems_overflow(n_elems + 255, e); }
 
+// The calls against a base share the implementation of their plain calls: a Base says whether the
+// call has one, and d_base is null exactly where it has none -- which is what selects the plain kernels in the launchers.
+// A delta call with a null or misaligned d_base is refused where the other pointers are.
+struct Base {
+  bool delta;
+  const uint8_t* p;
+  bool null() const { return delta && !p; }
+  bool misaligned() const { return delta && !aligned16(p); }
+};
+static inline Base no_base() { return {false, nullptr}; }
+static inline Base base_of(const uint8_t* d_base) { return {true, d_base}; }
+
 // what ghf_planes_split and ghf_planes_merge check alike: `d_inter` is the interleaved side
 static int planes_args(ghf_ctx* c, const char* who, const uint8_t* d_inter, const uint8_t* d_planes, size_t plane_stride, size_t n_elems,
-                       uint32_t elem_bytes) {
-  if (!c || !d_inter || !d_planes) return GHF_E_INVAL;
+                       uint32_t elem_bytes, Base base) {
+  if (!c || !d_inter || !d_planes || base.null()) return GHF_E_INVAL;
   const std::string f = std::string(who) + ": ";
   if (!elem_bytes_ok(elem_bytes)) return fail(c, GHF_E_INVAL, (f + "elem_bytes must be 2, 4 or 8").c_str());
-  if (!aligned16(d_inter) || !aligned16(d_planes) || (plane_stride & 15u))
+  if (!aligned16(d_inter) || !aligned16(d_planes) || (plane_stride & 15u) || base.misaligned())
     return fail(c, GHF_E_INVAL, (f + "pointers and plane_stride must be multiples of 16").c_str());
   if (elems_overflow(n_elems, elem_bytes)) return fail(c, GHF_E_INVAL, (f + "n_elems * elem_bytes overflows").c_str());
   if (n_elems == 0) return fail(c, GHF_E_EMPTY, (f + "no elements").c_str());
@@ -1294,34 +1306,47 @@ static int planes_args(ghf_ctx* c, const char* who, const uint8_t* d_inter, cons
   return GHF_OK;
 }
 
+static int planes_split(ghf_ctx* c, const char* who, const uint8_t* d_in, Base base, size_t n_elems, uint32_t elem_bytes,
+                        uint8_t* d_planes, size_t plane_stride) {
+  const int rc = planes_args(c, who, d_in, d_planes, plane_stride, n_elems, elem_bytes, base);
+  if (rc) return rc;
+  GHF_HIP(c, hipSetDevice(c->device));
+  launch_planes_split(d_in, base.p, n_elems, elem_bytes, d_planes, plane_stride, c->stream);
+  GHF_HIP(c, hipGetLastError());
+  return GHF_OK;
+}
 int ghf_planes_split(ghf_ctx* c, const uint8_t* d_in, size_t n_elems, uint32_t elem_bytes, uint8_t* d_planes, size_t plane_stride) {
-  const int rc = planes_args(c, "ghf_planes_split", d_in, d_planes, plane_stride, n_elems, elem_bytes);
+  return planes_split(c, "ghf_planes_split", d_in, no_base(), n_elems, elem_bytes, d_planes, plane_stride);
+}
+
+static int planes_merge(ghf_ctx* c, const char* who, const uint8_t* d_planes, size_t plane_stride, Base base, size_t n_elems,
+                        uint32_t elem_bytes, uint8_t* d_out) {
+  const int rc = planes_args(c, who, d_out, d_planes, plane_stride, n_elems, elem_bytes, base);
   if (rc) return rc;
   GHF_HIP(c, hipSetDevice(c->device));
-  launch_planes_split(d_in, n_elems, elem_bytes, d_planes, plane_stride, c->stream);
+  launch_planes_merge(d_planes, plane_stride, base.p, n_elems, elem_bytes, d_out, nullptr, c->stream);
   GHF_HIP(c, hipGetLastError());
   return GHF_OK;
 }
-
 int ghf_planes_merge(ghf_ctx* c, const uint8_t* d_planes, size_t plane_stride, size_t n_elems, uint32_t elem_bytes, uint8_t* d_out) {
-  const int rc = planes_args(c, "ghf_planes_merge", d_out, d_planes, plane_stride, n_elems, elem_bytes);
+  return planes_merge(c, "ghf_planes_merge", d_planes, plane_stride, no_base(), n_elems, elem_bytes, d_out);
+}
+
+static int planes_merge_range(ghf_ctx* c, const char* who, const uint8_t* d_planes, size_t plane_stride, Base base, size_t first,
+                              size_t count, uint32_t elem_bytes, uint8_t* d_out) {
+  const std::string f = std::string(who) + ": ";
+  if (c && first + count < first) return fail(c, GHF_E_INVAL, (f + "first + count overflows").c_str());
+  int rc = planes_args(c, who, d_out, d_planes, plane_stride, count, elem_bytes, base);
+  if (!rc && plane_stride < first + count) rc = fail(c, GHF_E_CAP, (f + "plane_stride below first + count").c_str());
   if (rc) return rc;
   GHF_HIP(c, hipSetDevice(c->device));
-  launch_planes_merge(d_planes, plane_stride, n_elems, elem_bytes, d_out, nullptr, c->stream);
+  launch_planes_merge_range(d_planes, plane_stride, base.p, first, count, elem_bytes, d_out, nullptr, c->stream);
   GHF_HIP(c, hipGetLastError());
   return GHF_OK;
 }
-
 int ghf_planes_merge_range(ghf_ctx* c, const uint8_t* d_planes, size_t plane_stride, size_t first, size_t count, uint32_t elem_bytes,
                            uint8_t* d_out) {
-  if (c && first + count < first) return fail(c, GHF_E_INVAL, "ghf_planes_merge_range: first + count overflows");
-  int rc = planes_args(c, "ghf_planes_merge_range", d_out, d_planes, plane_stride, count, elem_bytes);
-  if (!rc && plane_stride < first + count) rc = fail(c, GHF_E_CAP, "ghf_planes_merge_range: plane_stride below first + count");
-  if (rc) return rc;
-  GHF_HIP(c, hipSetDevice(c->device));
-  launch_planes_merge_range(d_planes, plane_stride, first, count, elem_bytes, d_out, nullptr, c->stream);
-  GHF_HIP(c, hipGetLastError());
-  return GHF_OK;
+  return planes_merge_range(c, "ghf_planes_merge_range", d_planes, plane_stride, no_base(), first, count, elem_bytes, d_out);
 }
 
 // the context's plane workspace for n_elems elements (workspace_overflow has cleared them): *stride <- the distance
@@ -1347,7 +1372,7 @@ int ghf_compress_planes(ghf_ctx* c, const uint8_t* d_in, size_t n_elems, uint32_
   size_t stride = 0;
   int rc = planes_workspace(c, n_elems, elem_bytes, &stride);
   if (rc) return rc;
-  launch_planes_split(d_in, n_elems, elem_bytes, c->planes.p, stride, c->stream);
+  launch_planes_split(d_in, nullptr, n_elems, elem_bytes, c->planes.p, stride, c->stream);
   GHF_HIP(c, hipGetLastError());
   for (uint32_t p = 0; p < elem_bytes && !rc; ++p)  // compressor.h:62-73, once per plane
     rc = ghf_compress(c, c->planes.p + p * stride, n_elems, d_out + p * slot_bytes, slot_bytes, d_out_bytes + p,
@@ -1362,23 +1387,28 @@ int ghf_compress_planes(ghf_ctx* c, const uint8_t* d_in, size_t n_elems, uint32_
 // (no reference counterpart)
 // k_histogram_planes and its finish on the stream.  The finish is what leaves the replicas zero for the next call: if it
 // cannot be queued behind a counting launch that was, a memset takes its place before the error is returned
-static int histogram_planes_into(ghf_ctx* c, const char* who, const uint8_t* d_in, size_t n_elems, uint32_t elem_bytes, unsigned flags,
-                                 uint64_t* d_hists) {
-  const hipError_t e = launch_histogram_planes(d_in, n_elems, elem_bytes, flags, c->d_planes_hist_acc, d_hists, c->stream);
+static int histogram_planes_into(ghf_ctx* c, const char* who, const uint8_t* d_in, const uint8_t* d_base, size_t n_elems,
+                                 uint32_t elem_bytes, unsigned flags, uint64_t* d_hists) {
+  const hipError_t e = launch_histogram_planes(d_in, d_base, n_elems, elem_bytes, flags, c->d_planes_hist_acc, d_hists, c->stream);
   if (e == hipSuccess) return GHF_OK;
   (void)hipMemsetAsync(c->d_planes_hist_acc, 0, kPlanesHistAccWords * sizeof(uint64_t), c->stream);
   return fail(c, GHF_E_HIP, who, e);
 }
 
-int ghf_histogram_planes(ghf_ctx* c, const uint8_t* d_in, size_t n_elems, uint32_t elem_bytes, unsigned flags, uint64_t* d_hists) {
-  if (!c || !d_in || !d_hists) return GHF_E_INVAL;
-  if (!elem_bytes_ok(elem_bytes)) return fail(c, GHF_E_INVAL, "ghf_histogram_planes: elem_bytes must be 2, 4 or 8");
-  if (!aligned16(d_in)) return fail(c, GHF_E_INVAL, "ghf_histogram_planes: d_in must be 16-byte aligned");
-  if (flags & ~GHF_HIST_COVER_ALL) return fail(c, GHF_E_INVAL, "ghf_histogram_planes: unknown flags");
-  if (elems_overflow(n_elems, elem_bytes)) return fail(c, GHF_E_INVAL, "ghf_histogram_planes: n_elems * elem_bytes overflows");
-  if (n_elems == 0) return fail(c, GHF_E_EMPTY, "ghf_histogram_planes: no elements");
+static int histogram_planes(ghf_ctx* c, const char* who, const uint8_t* d_in, Base base, size_t n_elems, uint32_t elem_bytes,
+                            unsigned flags, uint64_t* d_hists) {
+  if (!c || !d_in || !d_hists || base.null()) return GHF_E_INVAL;
+  const std::string f = std::string(who) + ": ";
+  if (!elem_bytes_ok(elem_bytes)) return fail(c, GHF_E_INVAL, (f + "elem_bytes must be 2, 4 or 8").c_str());
+  if (!aligned16(d_in) || base.misaligned()) return fail(c, GHF_E_INVAL, (f + "d_in and d_base must be 16-byte aligned").c_str());
+  if (flags & ~GHF_HIST_COVER_ALL) return fail(c, GHF_E_INVAL, (f + "unknown flags").c_str());
+  if (elems_overflow(n_elems, elem_bytes)) return fail(c, GHF_E_INVAL, (f + "n_elems * elem_bytes overflows").c_str());
+  if (n_elems == 0) return fail(c, GHF_E_EMPTY, (f + "no elements").c_str());
   GHF_HIP(c, hipSetDevice(c->device));
-  return histogram_planes_into(c, "ghf_histogram_planes: launch", d_in, n_elems, elem_bytes, flags, d_hists);
+  return histogram_planes_into(c, (f + "launch").c_str(), d_in, base.p, n_elems, elem_bytes, flags, d_hists);
+}
+int ghf_histogram_planes(ghf_ctx* c, const uint8_t* d_in, size_t n_elems, uint32_t elem_bytes, unsigned flags, uint64_t* d_hists) {
+  return histogram_planes(c, "ghf_histogram_planes", d_in, no_base(), n_elems, elem_bytes, flags, d_hists);
 }
 
 int ghf_planes_image_bytes(ghf_ctx* c, const uint64_t* d_hists, const ghf_code* d_codes, uint32_t elem_bytes, uint64_t* d_bytes) {
@@ -1390,34 +1420,35 @@ int ghf_planes_image_bytes(ghf_ctx* c, const uint64_t* d_hists, const ghf_code* 
   return GHF_OK;
 }
 
-int ghf_compress_planes_coded(ghf_ctx* c, const uint8_t* d_in, size_t n_elems, uint32_t elem_bytes, ghf_code* d_codes, unsigned flags,
-                              uint8_t* d_out, size_t slot_bytes, uint64_t* d_out_bytes, const ghf_index* indexes) {
-  if (!c || !d_in || !d_out || !d_out_bytes || !d_codes) return GHF_E_INVAL;
-  if (!elem_bytes_ok(elem_bytes)) return fail(c, GHF_E_INVAL, "ghf_compress_planes_coded: elem_bytes must be 2, 4 or 8");
-  if (!aligned16(d_in) || !aligned16(d_out) || (slot_bytes & 15u) || !aligned16(d_codes))
-    return fail(c, GHF_E_INVAL, "ghf_compress_planes_coded: d_in, d_out, d_codes and slot_bytes must be multiples of 16");
-  if (flags & ~GHF_PLANES_BUILD_CODES) return fail(c, GHF_E_INVAL, "ghf_compress_planes_coded: unknown flags");
-  if (workspace_overflow(n_elems, elem_bytes)) return fail(c, GHF_E_INVAL, "ghf_compress_planes_coded: n_elems * elem_bytes overflows");
+static int compress_planes_coded(ghf_ctx* c, const char* who, const uint8_t* d_in, Base base, size_t n_elems, uint32_t elem_bytes,
+                                 ghf_code* d_codes, unsigned flags, uint8_t* d_out, size_t slot_bytes, uint64_t* d_out_bytes,
+                                 const ghf_index* indexes) {
+  if (!c || !d_in || !d_out || !d_out_bytes || !d_codes || base.null()) return GHF_E_INVAL;
+  const std::string f = std::string(who) + ": ";
+  if (!elem_bytes_ok(elem_bytes)) return fail(c, GHF_E_INVAL, (f + "elem_bytes must be 2, 4 or 8").c_str());
+  if (!aligned16(d_in) || !aligned16(d_out) || (slot_bytes & 15u) || !aligned16(d_codes) || base.misaligned())
+    return fail(c, GHF_E_INVAL, (f + "d_in, d_base, d_out, d_codes and slot_bytes must be multiples of 16").c_str());
+  if (flags & ~GHF_PLANES_BUILD_CODES) return fail(c, GHF_E_INVAL, (f + "unknown flags").c_str());
+  if (workspace_overflow(n_elems, elem_bytes)) return fail(c, GHF_E_INVAL, (f + "n_elems * elem_bytes overflows").c_str());
   for (uint32_t p = 0; indexes && p < elem_bytes; ++p)
     if (indexes[p].n_symbols != n_elems || !index_has_arrays(&indexes[p]))
-      return fail(c, GHF_E_INVAL, "ghf_compress_planes_coded: an index does not match n_elems (use ghf_index_alloc)");
-  if (n_elems == 0) return fail(c, GHF_E_EMPTY, "ghf_compress_planes_coded: no elements");
-  if (slot_bytes < ghf_planes_slot_bytes(n_elems))
-    return fail(c, GHF_E_CAP, "ghf_compress_planes_coded: slot_bytes below ghf_planes_slot_bytes(n_elems)");
+      return fail(c, GHF_E_INVAL, (f + "an index does not match n_elems (use ghf_index_alloc)").c_str());
+  if (n_elems == 0) return fail(c, GHF_E_EMPTY, (f + "no elements").c_str());
+  if (slot_bytes < ghf_planes_slot_bytes(n_elems)) return fail(c, GHF_E_CAP, (f + "slot_bytes below ghf_planes_slot_bytes(n_elems)").c_str());
   GHF_HIP(c, hipSetDevice(c->device));
   size_t stride = 0;
   int rc = planes_workspace(c, n_elems, elem_bytes, &stride);
   if (rc) return rc;
   // compressor.h:63 for all planes in one pass over the interleaved buffer, then compressor.h:64 for all planes in one launch --
   // or the caller's codes, held against the counts
-  if ((rc = histogram_planes_into(c, "ghf_compress_planes_coded: histogram launch", d_in, n_elems, elem_bytes, 0, c->d_planes_hists))) return rc;
+  if ((rc = histogram_planes_into(c, (f + "histogram launch").c_str(), d_in, base.p, n_elems, elem_bytes, 0, c->d_planes_hists))) return rc;
   if (flags & GHF_PLANES_BUILD_CODES) {
     if ((rc = ghf_build_codes(c, c->d_planes_hists, elem_bytes, d_codes, 0))) return rc;
   } else {
     launch_planes_vet_codes(c->d_planes_hists, d_codes, elem_bytes, c->d_status, c->stream);
     GHF_HIP(c, hipGetLastError());
   }
-  launch_planes_split(d_in, n_elems, elem_bytes, c->planes.p, stride, c->stream);
+  launch_planes_split(d_in, base.p, n_elems, elem_bytes, c->planes.p, stride, c->stream);
   GHF_HIP(c, hipGetLastError());
   // K1 has not seen these planes: whatever it remembers about an address inside the workspace is of another call, and the
   // planner counts each plane itself (k_chunk_bits_direct)
@@ -1435,20 +1466,27 @@ int ghf_compress_planes_coded(ghf_ctx* c, const uint8_t* d_in, size_t n_elems, u
   c->plan.forget();
   return rc;
 }
+int ghf_compress_planes_coded(ghf_ctx* c, const uint8_t* d_in, size_t n_elems, uint32_t elem_bytes, ghf_code* d_codes, unsigned flags,
+                              uint8_t* d_out, size_t slot_bytes, uint64_t* d_out_bytes, const ghf_index* indexes) {
+  return compress_planes_coded(c, "ghf_compress_planes_coded", d_in, no_base(), n_elems, elem_bytes, d_codes, flags, d_out, slot_bytes,
+                               d_out_bytes, indexes);
+}
 
-int ghf_decode_planes(ghf_ctx* c, const uint8_t* const* h_stream_ptrs, const size_t* h_stream_bytes, const ghf_code* d_codes,
-                      const ghf_index* indexes, size_t n_elems, uint32_t elem_bytes, uint8_t* d_out, size_t cap, uint64_t* d_out_bytes) {
-  if (!c || !h_stream_ptrs || !h_stream_bytes || !d_codes || !d_out) return GHF_E_INVAL;
-  if (!elem_bytes_ok(elem_bytes)) return fail(c, GHF_E_INVAL, "ghf_decode_planes: elem_bytes must be 2, 4 or 8");
+static int decode_planes(ghf_ctx* c, const char* who, const uint8_t* const* h_stream_ptrs, const size_t* h_stream_bytes,
+                         const ghf_code* d_codes, const ghf_index* indexes, Base base, size_t n_elems, uint32_t elem_bytes, uint8_t* d_out,
+                         size_t cap, uint64_t* d_out_bytes) {
+  if (!c || !h_stream_ptrs || !h_stream_bytes || !d_codes || !d_out || base.null()) return GHF_E_INVAL;
+  const std::string f = std::string(who) + ": ";
+  if (!elem_bytes_ok(elem_bytes)) return fail(c, GHF_E_INVAL, (f + "elem_bytes must be 2, 4 or 8").c_str());
   for (uint32_t p = 0; p < elem_bytes; ++p)
-    if (!h_stream_ptrs[p] || !aligned16(h_stream_ptrs[p])) return fail(c, GHF_E_INVAL, "ghf_decode_planes: a stream pointer is null or not 16-byte aligned");
-  if (!aligned16(d_out)) return fail(c, GHF_E_INVAL, "ghf_decode_planes: d_out must be 16-byte aligned");
-  if (workspace_overflow(n_elems, elem_bytes)) return fail(c, GHF_E_INVAL, "ghf_decode_planes: n_elems * elem_bytes overflows");
+    if (!h_stream_ptrs[p] || !aligned16(h_stream_ptrs[p])) return fail(c, GHF_E_INVAL, (f + "a stream pointer is null or not 16-byte aligned").c_str());
+  if (!aligned16(d_out) || base.misaligned()) return fail(c, GHF_E_INVAL, (f + "d_out and d_base must be 16-byte aligned").c_str());
+  if (workspace_overflow(n_elems, elem_bytes)) return fail(c, GHF_E_INVAL, (f + "n_elems * elem_bytes overflows").c_str());
   for (uint32_t p = 0; indexes && p < elem_bytes; ++p)
     if (indexes[p].n_symbols != n_elems || !index_is_whole(&indexes[p]))
-      return fail(c, GHF_E_INVAL, "ghf_decode_planes: an index does not cover exactly n_elems symbols");
-  if (n_elems == 0) return fail(c, GHF_E_EMPTY, "ghf_decode_planes: no elements");
-  if (cap < n_elems * elem_bytes) return fail(c, GHF_E_CAP, "ghf_decode_planes: output capacity below n_elems * elem_bytes");
+      return fail(c, GHF_E_INVAL, (f + "an index does not cover exactly n_elems symbols").c_str());
+  if (n_elems == 0) return fail(c, GHF_E_EMPTY, (f + "no elements").c_str());
+  if (cap < n_elems * elem_bytes) return fail(c, GHF_E_CAP, (f + "output capacity below n_elems * elem_bytes").c_str());
   GHF_HIP(c, hipSetDevice(c->device));
   size_t stride = 0;
   int rc = planes_workspace(c, n_elems, elem_bytes, &stride);
@@ -1457,16 +1495,21 @@ int ghf_decode_planes(ghf_ctx* c, const uint8_t* const* h_stream_ptrs, const siz
     if (!indexes) {  // the side-car-less path: synchronises, and keeps the side-car for the decode that follows
       uint64_t n_p = 0;
       if ((rc = ghf_decoded_size(c, h_stream_ptrs[p], h_stream_bytes[p], d_codes + p, &n_p))) return rc;
-      if (n_p != n_elems) return fail(c, GHF_E_CORRUPT, "ghf_decode_planes: a plane does not decode to n_elems bytes");
+      if (n_p != n_elems) return fail(c, GHF_E_CORRUPT, (f + "a plane does not decode to n_elems bytes").c_str());
     }
     if ((rc = ghf_decode(c, h_stream_ptrs[p], h_stream_bytes[p], d_codes + p, indexes ? indexes + p : nullptr, c->planes.p + p * stride,
                          stride, nullptr)))
       return rc;
   }
-  launch_planes_merge(c->planes.p, stride, n_elems, elem_bytes, d_out, c->d_status, c->stream);  // nothing is stored behind a failed decode
+  launch_planes_merge(c->planes.p, stride, base.p, n_elems, elem_bytes, d_out, c->d_status, c->stream);  // nothing is stored behind a failed decode
   if (d_out_bytes) launch_store_u64(d_out_bytes, nullptr, (uint64_t)n_elems * elem_bytes, c->stream);
   GHF_HIP(c, hipGetLastError());
   return GHF_OK;
+}
+int ghf_decode_planes(ghf_ctx* c, const uint8_t* const* h_stream_ptrs, const size_t* h_stream_bytes, const ghf_code* d_codes,
+                      const ghf_index* indexes, size_t n_elems, uint32_t elem_bytes, uint8_t* d_out, size_t cap, uint64_t* d_out_bytes) {
+  return decode_planes(c, "ghf_decode_planes", h_stream_ptrs, h_stream_bytes, d_codes, indexes, no_base(), n_elems, elem_bytes, d_out, cap,
+                       d_out_bytes);
 }
 
 // ---------------------------------------------------------------------------------------------- seek table
@@ -1651,38 +1694,40 @@ int ghf_decode_range(ghf_ctx* c, const uint8_t* d_stream, size_t stream_bytes, c
 
 // ---------------------------------------------------------------------------------------------- element range of byte planes
 // (no reference counterpart)
-int ghf_decode_planes_range(ghf_ctx* c, const uint8_t* const* h_stream_ptrs, const size_t* h_stream_bytes, const ghf_code* d_codes,
-                            const ghf_index* indexes, const ghf_seek_info* h_infos, const uint8_t* const* h_table_ptrs,
-                            const size_t* h_table_bytes, uint32_t elem_bytes, uint64_t first, uint64_t count, uint8_t* d_out, size_t cap) {
-  if (!c || !h_stream_ptrs || !h_stream_bytes || !d_codes || !d_out) return GHF_E_INVAL;
-  if (!elem_bytes_ok(elem_bytes)) return fail(c, GHF_E_INVAL, "ghf_decode_planes_range: elem_bytes must be 2, 4 or 8");
+static int decode_planes_range(ghf_ctx* c, const char* who, const uint8_t* const* h_stream_ptrs, const size_t* h_stream_bytes,
+                               const ghf_code* d_codes, const ghf_index* indexes, const ghf_seek_info* h_infos,
+                               const uint8_t* const* h_table_ptrs, const size_t* h_table_bytes, Base base, uint32_t elem_bytes,
+                               uint64_t first, uint64_t count, uint8_t* d_out, size_t cap) {
+  if (!c || !h_stream_ptrs || !h_stream_bytes || !d_codes || !d_out || base.null()) return GHF_E_INVAL;
+  const std::string f = std::string(who) + ": ";
+  if (!elem_bytes_ok(elem_bytes)) return fail(c, GHF_E_INVAL, (f + "elem_bytes must be 2, 4 or 8").c_str());
   const bool by_table = h_infos || h_table_ptrs || h_table_bytes;
   if ((indexes != nullptr) == by_table || (by_table && !(h_infos && h_table_ptrs && h_table_bytes)))
-    return fail(c, GHF_E_INVAL, "ghf_decode_planes_range: exactly one of indexes / (h_infos, h_table_ptrs, h_table_bytes) must be given");
+    return fail(c, GHF_E_INVAL, (f + "exactly one of indexes / (h_infos, h_table_ptrs, h_table_bytes) must be given").c_str());
   for (uint32_t p = 0; p < elem_bytes; ++p) {
     if (!h_stream_ptrs[p] || !aligned16(h_stream_ptrs[p]))
-      return fail(c, GHF_E_INVAL, "ghf_decode_planes_range: a stream pointer is null or not 16-byte aligned");
+      return fail(c, GHF_E_INVAL, (f + "a stream pointer is null or not 16-byte aligned").c_str());
     if (by_table && (!h_table_ptrs[p] || !aligned16(h_table_ptrs[p])))
-      return fail(c, GHF_E_INVAL, "ghf_decode_planes_range: a table pointer is null or not 16-byte aligned");
+      return fail(c, GHF_E_INVAL, (f + "a table pointer is null or not 16-byte aligned").c_str());
   }
-  if (!aligned16(d_out)) return fail(c, GHF_E_INVAL, "ghf_decode_planes_range: d_out must be 16-byte aligned");
+  if (!aligned16(d_out) || base.misaligned()) return fail(c, GHF_E_INVAL, (f + "d_out and d_base must be 16-byte aligned").c_str());
   const uint64_t n_elems = by_table ? h_infos[0].n_symbols : indexes[0].n_symbols;
   for (uint32_t p = 0; p < elem_bytes; ++p) {
     if (!by_table && indexes[p].n_symbols != 0 && !index_is_whole(&indexes[p]))
-      return fail(c, GHF_E_INVAL, "ghf_decode_planes_range: malformed index");
+      return fail(c, GHF_E_INVAL, (f + "malformed index").c_str());
     if ((by_table ? h_infos[p].n_symbols : indexes[p].n_symbols) != n_elems)
-      return fail(c, GHF_E_INVAL, "ghf_decode_planes_range: the planes disagree on n_symbols");
+      return fail(c, GHF_E_INVAL, (f + "the planes disagree on n_symbols").c_str());
   }
-  if (first > n_elems || count > n_elems - first) return fail(c, GHF_E_INVAL, "ghf_decode_planes_range: first + count exceeds n_elems");
+  if (first > n_elems || count > n_elems - first) return fail(c, GHF_E_INVAL, (f + "first + count exceeds n_elems").c_str());
   // the workspace holds the range from the start of its first block (below), and a vector more for the merge's second load
   const size_t lead = (size_t)(first % kBlockSymbols);
   if (count > (size_t)-1 - lead - 16 || workspace_overflow((size_t)count + lead + 16, elem_bytes))
-    return fail(c, GHF_E_INVAL, "ghf_decode_planes_range: count * elem_bytes overflows");
+    return fail(c, GHF_E_INVAL, (f + "count * elem_bytes overflows").c_str());
   for (uint32_t p = 0; by_table && p < elem_bytes; ++p) {  // every plane before anything is queued for the first
-    const int rc = seek_table_ok(c, "ghf_decode_planes_range", h_infos + p, h_table_ptrs[p], h_table_bytes[p]);
+    const int rc = seek_table_ok(c, who, h_infos + p, h_table_ptrs[p], h_table_bytes[p]);
     if (rc) return rc;
   }
-  if (cap < count * elem_bytes) return fail(c, GHF_E_CAP, "ghf_decode_planes_range: output capacity below count * elem_bytes");
+  if (cap < count * elem_bytes) return fail(c, GHF_E_CAP, (f + "output capacity below count * elem_bytes").c_str());
   if (count == 0) return GHF_OK;
   GHF_HIP(c, hipSetDevice(c->device));
   // Every plane is decoded from the start of the block that holds `first`: plane p's byte `first - lead` lands on the
@@ -1743,9 +1788,52 @@ int ghf_decode_planes_range(ghf_ctx* c, const uint8_t* const* h_stream_ptrs, con
       launch_decode(d, c->stream);
     }
   }
-  launch_planes_merge_range(c->planes.p, stride, lead, count, elem_bytes, d_out, c->d_status, c->stream);  // nothing behind a failed decode
+  launch_planes_merge_range(c->planes.p, stride, base.p, lead, count, elem_bytes, d_out, c->d_status, c->stream);  // nothing behind a failed decode
   GHF_HIP(c, hipGetLastError());
   return GHF_OK;
+}
+int ghf_decode_planes_range(ghf_ctx* c, const uint8_t* const* h_stream_ptrs, const size_t* h_stream_bytes, const ghf_code* d_codes,
+                            const ghf_index* indexes, const ghf_seek_info* h_infos, const uint8_t* const* h_table_ptrs,
+                            const size_t* h_table_bytes, uint32_t elem_bytes, uint64_t first, uint64_t count, uint8_t* d_out, size_t cap) {
+  return decode_planes_range(c, "ghf_decode_planes_range", h_stream_ptrs, h_stream_bytes, d_codes, indexes, h_infos, h_table_ptrs,
+                             h_table_bytes, no_base(), elem_bytes, first, count, d_out, cap);
+}
+
+// ---------------------------------------------------------------------------------------------- byte planes against a base
+// (no reference counterpart): the calls above with the XOR against d_base in their streaming kernels
+int ghf_histogram_planes_delta(ghf_ctx* c, const uint8_t* d_in, const uint8_t* d_base, size_t n_elems, uint32_t elem_bytes, unsigned flags,
+                               uint64_t* d_hists) {
+  return histogram_planes(c, "ghf_histogram_planes_delta", d_in, base_of(d_base), n_elems, elem_bytes, flags, d_hists);
+}
+int ghf_planes_split_delta(ghf_ctx* c, const uint8_t* d_in, const uint8_t* d_base, size_t n_elems, uint32_t elem_bytes, uint8_t* d_planes,
+                           size_t plane_stride) {
+  return planes_split(c, "ghf_planes_split_delta", d_in, base_of(d_base), n_elems, elem_bytes, d_planes, plane_stride);
+}
+int ghf_planes_merge_delta(ghf_ctx* c, const uint8_t* d_planes, size_t plane_stride, const uint8_t* d_base, size_t n_elems,
+                           uint32_t elem_bytes, uint8_t* d_out) {
+  return planes_merge(c, "ghf_planes_merge_delta", d_planes, plane_stride, base_of(d_base), n_elems, elem_bytes, d_out);
+}
+int ghf_planes_merge_range_delta(ghf_ctx* c, const uint8_t* d_planes, size_t plane_stride, const uint8_t* d_base, size_t first, size_t count,
+                                 uint32_t elem_bytes, uint8_t* d_out) {
+  return planes_merge_range(c, "ghf_planes_merge_range_delta", d_planes, plane_stride, base_of(d_base), first, count, elem_bytes, d_out);
+}
+int ghf_compress_planes_delta(ghf_ctx* c, const uint8_t* d_in, const uint8_t* d_base, size_t n_elems, uint32_t elem_bytes, ghf_code* d_codes,
+                              unsigned flags, uint8_t* d_out, size_t slot_bytes, uint64_t* d_out_bytes, const ghf_index* indexes) {
+  return compress_planes_coded(c, "ghf_compress_planes_delta", d_in, base_of(d_base), n_elems, elem_bytes, d_codes, flags, d_out, slot_bytes,
+                               d_out_bytes, indexes);
+}
+int ghf_decode_planes_delta(ghf_ctx* c, const uint8_t* const* h_stream_ptrs, const size_t* h_stream_bytes, const ghf_code* d_codes,
+                            const ghf_index* indexes, const uint8_t* d_base, size_t n_elems, uint32_t elem_bytes, uint8_t* d_out, size_t cap,
+                            uint64_t* d_out_bytes) {
+  return decode_planes(c, "ghf_decode_planes_delta", h_stream_ptrs, h_stream_bytes, d_codes, indexes, base_of(d_base), n_elems, elem_bytes,
+                       d_out, cap, d_out_bytes);
+}
+int ghf_decode_planes_range_delta(ghf_ctx* c, const uint8_t* const* h_stream_ptrs, const size_t* h_stream_bytes, const ghf_code* d_codes,
+                                  const ghf_index* indexes, const ghf_seek_info* h_infos, const uint8_t* const* h_table_ptrs,
+                                  const size_t* h_table_bytes, const uint8_t* d_base, uint32_t elem_bytes, uint64_t first, uint64_t count,
+                                  uint8_t* d_out, size_t cap) {
+  return decode_planes_range(c, "ghf_decode_planes_range_delta", h_stream_ptrs, h_stream_bytes, d_codes, indexes, h_infos, h_table_ptrs,
+                             h_table_bytes, base_of(d_base), elem_bytes, first, count, d_out, cap);
 }
 
 // ---------------------------------------------------------------------------------------------- .crs

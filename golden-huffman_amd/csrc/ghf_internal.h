@@ -462,20 +462,24 @@ void launch_decode_bodies_batch_planes_shared(const BatchPlanesBodiesParams& p, 
 // ghf_batch_seek.hip: elem_bytes is 1 (flat items), 2, 4 or 8
 void launch_batch_seek_pack(const BatchSeekPackParams& p, uint32_t slots, hipStream_t s);  // one launch, grid = slots
 void launch_decode_bodies_batch_seek(const BatchSeekDecodeParams& p, uint32_t count, uint32_t elem_bytes, hipStream_t s);  // grid = count
-// ghf_planes.hip: byte planes of elements of 2, 4 or 8 bytes (n_elems > 0; every pointer and plane_stride 16-byte aligned)
-void launch_planes_split(const uint8_t* d_in, uint64_t n_elems, uint32_t elem_bytes, uint8_t* d_planes, uint64_t plane_stride,
-                         hipStream_t s);
-// d_status (may be null): the launch stores nothing when the word is non-zero
-void launch_planes_merge(const uint8_t* d_planes, uint64_t plane_stride, uint64_t n_elems, uint32_t elem_bytes, uint8_t* d_out,
-                         const int* d_status, hipStream_t s);
+// ghf_planes.hip: byte planes of elements of 2, 4 or 8 bytes (n_elems > 0; every pointer and plane_stride 16-byte aligned).
+// d_base (may be null) in every launch: the interleaved side is taken against it -- the planes of
+// d_in ^ d_base, d_out = merge ^ d_base -- by the _delta kernels; null launches exactly the plain kernel
+void launch_planes_split(const uint8_t* d_in, const uint8_t* d_base, uint64_t n_elems, uint32_t elem_bytes, uint8_t* d_planes,
+                         uint64_t plane_stride, hipStream_t s);
+// d_status (may be null): the launch stores nothing when the word is non-zero.  d_base == d_out is allowed
+void launch_planes_merge(const uint8_t* d_planes, uint64_t plane_stride, const uint8_t* d_base, uint64_t n_elems, uint32_t elem_bytes,
+                         uint8_t* d_out, const int* d_status, hipStream_t s);
 // elements [first, first + count) of the planes (count > 0); reads [first & ~15, (first + count + 15) & ~15) of every plane
-void launch_planes_merge_range(const uint8_t* d_planes, uint64_t plane_stride, uint64_t first, uint64_t count, uint32_t elem_bytes,
-                               uint8_t* d_out, const int* d_status, hipStream_t s);
+// and d_base[0 .. count * elem_bytes), the base of the range itself
+void launch_planes_merge_range(const uint8_t* d_planes, uint64_t plane_stride, const uint8_t* d_base, uint64_t first, uint64_t count,
+                               uint32_t elem_bytes, uint8_t* d_out, const int* d_status, hipStream_t s);
 // ghf_planes_hist.hip: elem_bytes is 2, 4 or 8, n_elems > 0, d_in 16-byte aligned.  d_acc: kPlanesHistAccWords words, zero
 // between launches.  Two launches: the counting kernel, then the finish (replica sums, slot 256, GHF_HIST_COVER_ALL), which
-// is also what zeroes d_acc again.  -> the first launch error; after an error of the finish launch d_acc is the caller's to clear
-hipError_t launch_histogram_planes(const uint8_t* d_in, uint64_t n_elems, uint32_t elem_bytes, uint32_t flags, uint64_t* d_acc,
-                                   uint64_t* d_hists, hipStream_t s);
+// is also what zeroes d_acc again.  -> the first launch error; after an error of the finish launch d_acc is the caller's to clear.
+// d_base (may be null, else 16-byte aligned): the counts are those of d_in ^ d_base
+hipError_t launch_histogram_planes(const uint8_t* d_in, const uint8_t* d_base, uint64_t n_elems, uint32_t elem_bytes, uint32_t flags,
+                                   uint64_t* d_acc, uint64_t* d_hists, hipStream_t s);
 // d_bytes[p] <- image size of counts d_hists[p] under d_codes[p]; 0: the code is not complete or misses a counted byte
 void launch_planes_image_bytes(const uint64_t* d_hists, const ghf_code* d_codes, uint32_t elem_bytes, uint64_t* d_bytes, hipStream_t s);
 // latches GHF_E_FORMAT (a code is not a complete prefix code) or GHF_E_NOCODE (a counted byte has no code) at *d_status

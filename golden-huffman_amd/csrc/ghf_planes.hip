@@ -244,6 +244,152 @@ __global__ __launch_bounds__(kWave) void k_planes_merge_range(const uint8_t* __r
   }
 }
 
+// ----------------------------------------------------------------------------------------------------------------------
+// The same three kernels against a BASE tensor: the planes are those of in ^ base, the merge gives
+// back planes ^ base.  `base` holds the bytes of the interleaved side and is read with the interleaved side's access
+// shape: lane l on vector 64 j + l of the tile, 16 bytes per lane, the non-temporal hint.  Its max(E, 4) loads are issued
+// together with the tile's other loads, before the first LDS instruction, and the XOR is applied to registers: on the way
+// into the LDS tile in the split, on the way out of it in the merges (whose base load so never waits behind the
+// transposition).  Tiles, slabs, LDS rows, grid and the bytewise ragged end are the parents'; nothing outside
+// base[0 .. n_elems * E) is read.  The bodies stand beside the parents' and do not share code with them, so that the
+// parents' instruction streams stay what they were.
+// ----------------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ uint4 xor16(const uint4& a, const uint4& b) { return make_uint4(a.x ^ b.x, a.y ^ b.y, a.z ^ b.z, a.w ^ b.w); }
+
+template <int E>
+__global__ __launch_bounds__(kWave) void k_planes_split_delta(const uint8_t* __restrict__ in, const uint8_t* __restrict__ base,
+                                                              uint64_t n_elems, uint8_t* __restrict__ planes, uint64_t plane_stride) {
+  using G = PlanesGeom<E>;
+  __shared__ uint4 tile[G::kRows * G::kRowVec];
+  const uint32_t lane = threadIdx.x;
+  const Slab s = slab_of(n_elems, G::kTile);
+  for (uint64_t t = s.lo; t < s.end; ++t) {
+    const uint4* src = reinterpret_cast<const uint4*>(in) + t * (kWave * G::kVec);
+    const uint4* bsrc = reinterpret_cast<const uint4*>(base) + t * (kWave * G::kVec);
+    uint4 x[G::kVec], d[G::kVec];
+#pragma unroll
+    for (int j = 0; j < G::kVec; ++j) x[j] = ld16(src + j * kWave + lane);
+#pragma unroll
+    for (int j = 0; j < G::kVec; ++j) d[j] = ld16(bsrc + j * kWave + lane);
+#pragma unroll
+    for (int j = 0; j < G::kVec; ++j) {
+      const uint32_t v = j * kWave + lane;
+      tile[(v / E) * G::kRowVec + v % E] = xor16(x[j], d[j]);
+    }
+    wave_sync();
+#pragma unroll
+    for (int r = 0; r < G::kRowsPerLane; ++r) {
+      const uint32_t row = r * kWave + lane;
+      uint4 y[E], p[E];
+#pragma unroll
+      for (int j = 0; j < E; ++j) y[j] = tile[row * G::kRowVec + j];
+      row_to_planes<E>(y, p);
+#pragma unroll
+      for (int b = 0; b < E; ++b) st16(reinterpret_cast<uint4*>(planes + b * plane_stride) + t * G::kRows + row, p[b]);
+    }
+    wave_sync();
+  }
+  for (uint64_t k = s.tail; k < n_elems; k += (uint64_t)gridDim.x * kWave) {  // the ragged end: byte by byte
+#pragma unroll
+    for (int b = 0; b < E; ++b) planes[b * plane_stride + k] = in[k * E + b] ^ base[k * E + b];
+  }
+}
+
+// `out` and `base` may be the SAME pointer ("XOR the delta into the base") and carry no __restrict__: a lane reads the base
+// vector (the base bytes of the ragged end) that it overwrites itself, and every load of a tile's base is issued before
+// the tile's first store.  status: as in k_planes_merge
+template <int E>
+__global__ __launch_bounds__(kWave) void k_planes_merge_delta(const uint8_t* __restrict__ planes, uint64_t plane_stride,
+                                                              const uint8_t* base, uint64_t n_elems, uint8_t* out,
+                                                              const int* __restrict__ status) {
+  using G = PlanesGeom<E>;
+  __shared__ uint4 tile[G::kRows * G::kRowVec];
+  if (status && __builtin_amdgcn_readfirstlane(*status) != 0) return;
+  const uint32_t lane = threadIdx.x;
+  const Slab s = slab_of(n_elems, G::kTile);
+  for (uint64_t t = s.lo; t < s.end; ++t) {
+    const uint4* bsrc = reinterpret_cast<const uint4*>(base) + t * (kWave * G::kVec);
+    uint4 p[G::kRowsPerLane][E], d[G::kVec];
+#pragma unroll
+    for (int r = 0; r < G::kRowsPerLane; ++r)
+#pragma unroll
+      for (int b = 0; b < E; ++b)
+        p[r][b] = ld16(reinterpret_cast<const uint4*>(planes + b * plane_stride) + t * G::kRows + r * kWave + lane);
+#pragma unroll
+    for (int j = 0; j < G::kVec; ++j) d[j] = ld16(bsrc + j * kWave + lane);
+#pragma unroll
+    for (int r = 0; r < G::kRowsPerLane; ++r) {
+      const uint32_t row = r * kWave + lane;
+      uint4 y[E];
+      planes_to_row<E>(p[r], y);
+#pragma unroll
+      for (int j = 0; j < E; ++j) tile[row * G::kRowVec + j] = y[j];
+    }
+    wave_sync();
+    uint4* dst = reinterpret_cast<uint4*>(out) + t * (kWave * G::kVec);
+#pragma unroll
+    for (int j = 0; j < G::kVec; ++j) {
+      const uint32_t v = j * kWave + lane;
+      st16(dst + j * kWave + lane, xor16(tile[(v / E) * G::kRowVec + v % E], d[j]));
+    }
+    wave_sync();
+  }
+  for (uint64_t k = s.tail; k < n_elems; k += (uint64_t)gridDim.x * kWave) {
+#pragma unroll
+    for (int b = 0; b < E; ++b) out[k * E + b] = planes[b * plane_stride + k] ^ base[k * E + b];
+  }
+}
+
+// k_planes_merge_range against a base: the planes start `skew` = 1 .. 15 bytes into a vector, `base` does not -- it holds
+// the range's own elements, base[0 .. n_elems * E), aligned and indexed exactly like `out` (and may be `out`)
+template <int E>
+__global__ __launch_bounds__(kWave) void k_planes_merge_range_delta(const uint8_t* __restrict__ planes, uint64_t plane_stride,
+                                                                    uint32_t skew, const uint8_t* base, uint64_t n_elems, uint8_t* out,
+                                                                    const int* __restrict__ status) {
+  using G = PlanesGeom<E>;
+  __shared__ uint4 tile[G::kRows * G::kRowVec];
+  if (status && __builtin_amdgcn_readfirstlane(*status) != 0) return;
+  const uint32_t lane = threadIdx.x;
+  skew = __builtin_amdgcn_readfirstlane(skew);
+  const Slab s = slab_of(n_elems, G::kTile);
+  for (uint64_t t = s.lo; t < s.end; ++t) {
+    const uint4* bsrc = reinterpret_cast<const uint4*>(base) + t * (kWave * G::kVec);
+    uint4 lo[G::kRowsPerLane][E], hi[G::kRowsPerLane][E], d[G::kVec];
+#pragma unroll
+    for (int r = 0; r < G::kRowsPerLane; ++r)
+#pragma unroll
+      for (int b = 0; b < E; ++b) {
+        const uint4* v = reinterpret_cast<const uint4*>(planes + b * plane_stride) + t * G::kRows + r * kWave + lane;
+        lo[r][b] = ld16(v);
+        hi[r][b] = ld16(v + 1);
+      }
+#pragma unroll
+    for (int j = 0; j < G::kVec; ++j) d[j] = ld16(bsrc + j * kWave + lane);
+#pragma unroll
+    for (int r = 0; r < G::kRowsPerLane; ++r) {
+      const uint32_t row = r * kWave + lane;
+      uint4 p[E], y[E];
+#pragma unroll
+      for (int b = 0; b < E; ++b) p[b] = funnel16(lo[r][b], hi[r][b], skew);
+      planes_to_row<E>(p, y);
+#pragma unroll
+      for (int j = 0; j < E; ++j) tile[row * G::kRowVec + j] = y[j];
+    }
+    wave_sync();
+    uint4* dst = reinterpret_cast<uint4*>(out) + t * (kWave * G::kVec);
+#pragma unroll
+    for (int j = 0; j < G::kVec; ++j) {
+      const uint32_t v = j * kWave + lane;
+      st16(dst + j * kWave + lane, xor16(tile[(v / E) * G::kRowVec + v % E], d[j]));
+    }
+    wave_sync();
+  }
+  for (uint64_t k = s.tail; k < n_elems; k += (uint64_t)gridDim.x * kWave) {
+#pragma unroll
+    for (int b = 0; b < E; ++b) out[k * E + b] = planes[b * plane_stride + skew + k] ^ base[k * E + b];
+  }
+}
+
 // one resident round: kPlanesGroups one-wave workgroups, each with a slab of whole tiles; at least one lane per element of
 // the ragged end
 static uint32_t planes_grid(uint64_t n_elems, uint32_t elem_bytes) {
@@ -253,32 +399,57 @@ static uint32_t planes_grid(uint64_t n_elems, uint32_t elem_bytes) {
   return (uint32_t)(g > kPlanesGroups ? kPlanesGroups : g);
 }
 
-void launch_planes_split(const uint8_t* d_in, uint64_t n_elems, uint32_t elem_bytes, uint8_t* d_planes, uint64_t plane_stride,
-                         hipStream_t s) {
+// d_base == nullptr: the plain kernel; else the planes of d_in ^ d_base, on the same grid
+void launch_planes_split(const uint8_t* d_in, const uint8_t* d_base, uint64_t n_elems, uint32_t elem_bytes, uint8_t* d_planes,
+                         uint64_t plane_stride, hipStream_t s) {
   const dim3 grid(planes_grid(n_elems, elem_bytes)), block(kWave);
-  if (elem_bytes == 2) hipLaunchKernelGGL(k_planes_split<2>, grid, block, 0, s, d_in, n_elems, d_planes, plane_stride);
-  else if (elem_bytes == 4) hipLaunchKernelGGL(k_planes_split<4>, grid, block, 0, s, d_in, n_elems, d_planes, plane_stride);
-  else hipLaunchKernelGGL(k_planes_split<8>, grid, block, 0, s, d_in, n_elems, d_planes, plane_stride);
+  if (!d_base) {
+    if (elem_bytes == 2) hipLaunchKernelGGL(k_planes_split<2>, grid, block, 0, s, d_in, n_elems, d_planes, plane_stride);
+    else if (elem_bytes == 4) hipLaunchKernelGGL(k_planes_split<4>, grid, block, 0, s, d_in, n_elems, d_planes, plane_stride);
+    else hipLaunchKernelGGL(k_planes_split<8>, grid, block, 0, s, d_in, n_elems, d_planes, plane_stride);
+  } else {
+    if (elem_bytes == 2) hipLaunchKernelGGL(k_planes_split_delta<2>, grid, block, 0, s, d_in, d_base, n_elems, d_planes, plane_stride);
+    else if (elem_bytes == 4) hipLaunchKernelGGL(k_planes_split_delta<4>, grid, block, 0, s, d_in, d_base, n_elems, d_planes, plane_stride);
+    else hipLaunchKernelGGL(k_planes_split_delta<8>, grid, block, 0, s, d_in, d_base, n_elems, d_planes, plane_stride);
+  }
 }
 
-void launch_planes_merge(const uint8_t* d_planes, uint64_t plane_stride, uint64_t n_elems, uint32_t elem_bytes, uint8_t* d_out,
-                         const int* d_status, hipStream_t s) {
+// d_base == nullptr: the plain kernel; else d_out = merge(planes) ^ d_base, d_base == d_out allowed
+void launch_planes_merge(const uint8_t* d_planes, uint64_t plane_stride, const uint8_t* d_base, uint64_t n_elems, uint32_t elem_bytes,
+                         uint8_t* d_out, const int* d_status, hipStream_t s) {
   const dim3 grid(planes_grid(n_elems, elem_bytes)), block(kWave);
-  if (elem_bytes == 2) hipLaunchKernelGGL(k_planes_merge<2>, grid, block, 0, s, d_planes, plane_stride, n_elems, d_out, d_status);
-  else if (elem_bytes == 4) hipLaunchKernelGGL(k_planes_merge<4>, grid, block, 0, s, d_planes, plane_stride, n_elems, d_out, d_status);
-  else hipLaunchKernelGGL(k_planes_merge<8>, grid, block, 0, s, d_planes, plane_stride, n_elems, d_out, d_status);
+  if (!d_base) {
+    if (elem_bytes == 2) hipLaunchKernelGGL(k_planes_merge<2>, grid, block, 0, s, d_planes, plane_stride, n_elems, d_out, d_status);
+    else if (elem_bytes == 4) hipLaunchKernelGGL(k_planes_merge<4>, grid, block, 0, s, d_planes, plane_stride, n_elems, d_out, d_status);
+    else hipLaunchKernelGGL(k_planes_merge<8>, grid, block, 0, s, d_planes, plane_stride, n_elems, d_out, d_status);
+  } else {
+    if (elem_bytes == 2) hipLaunchKernelGGL(k_planes_merge_delta<2>, grid, block, 0, s, d_planes, plane_stride, d_base, n_elems, d_out, d_status);
+    else if (elem_bytes == 4) hipLaunchKernelGGL(k_planes_merge_delta<4>, grid, block, 0, s, d_planes, plane_stride, d_base, n_elems, d_out, d_status);
+    else hipLaunchKernelGGL(k_planes_merge_delta<8>, grid, block, 0, s, d_planes, plane_stride, d_base, n_elems, d_out, d_status);
+  }
 }
 
-// elements [first, first + count) of the planes; a range that starts on a vector is k_planes_merge on the shifted planes
-void launch_planes_merge_range(const uint8_t* d_planes, uint64_t plane_stride, uint64_t first, uint64_t count, uint32_t elem_bytes,
-                               uint8_t* d_out, const int* d_status, hipStream_t s) {
+// elements [first, first + count) of the planes; a range that starts on a vector is k_planes_merge on the shifted planes.
+// d_base (may be null) holds base elements [first, first + count) at d_base[0 .. count * elem_bytes): it carries no skew,
+// only the planes do
+void launch_planes_merge_range(const uint8_t* d_planes, uint64_t plane_stride, const uint8_t* d_base, uint64_t first, uint64_t count,
+                               uint32_t elem_bytes, uint8_t* d_out, const int* d_status, hipStream_t s) {
   const uint32_t skew = (uint32_t)(first & 15u);
-  const uint8_t* base = d_planes + (first - skew);
-  if (skew == 0) return launch_planes_merge(base, plane_stride, count, elem_bytes, d_out, d_status, s);
+  const uint8_t* from = d_planes + (first - skew);
+  if (skew == 0) return launch_planes_merge(from, plane_stride, d_base, count, elem_bytes, d_out, d_status, s);
   const dim3 grid(planes_grid(count, elem_bytes)), block(kWave);
-  if (elem_bytes == 2) hipLaunchKernelGGL(k_planes_merge_range<2>, grid, block, 0, s, base, plane_stride, skew, count, d_out, d_status);
-  else if (elem_bytes == 4) hipLaunchKernelGGL(k_planes_merge_range<4>, grid, block, 0, s, base, plane_stride, skew, count, d_out, d_status);
-  else hipLaunchKernelGGL(k_planes_merge_range<8>, grid, block, 0, s, base, plane_stride, skew, count, d_out, d_status);
+  if (!d_base) {
+    if (elem_bytes == 2) hipLaunchKernelGGL(k_planes_merge_range<2>, grid, block, 0, s, from, plane_stride, skew, count, d_out, d_status);
+    else if (elem_bytes == 4) hipLaunchKernelGGL(k_planes_merge_range<4>, grid, block, 0, s, from, plane_stride, skew, count, d_out, d_status);
+    else hipLaunchKernelGGL(k_planes_merge_range<8>, grid, block, 0, s, from, plane_stride, skew, count, d_out, d_status);
+  } else {
+    if (elem_bytes == 2)
+      hipLaunchKernelGGL(k_planes_merge_range_delta<2>, grid, block, 0, s, from, plane_stride, skew, d_base, count, d_out, d_status);
+    else if (elem_bytes == 4)
+      hipLaunchKernelGGL(k_planes_merge_range_delta<4>, grid, block, 0, s, from, plane_stride, skew, d_base, count, d_out, d_status);
+    else
+      hipLaunchKernelGGL(k_planes_merge_range_delta<8>, grid, block, 0, s, from, plane_stride, skew, d_base, count, d_out, d_status);
+  }
 }
 
 }  // namespace ghf

@@ -141,6 +141,93 @@ __global__ __launch_bounds__(kPlanesHistThreads, 4) void k_histogram_planes(cons
     if (total[g]) atomicAdd(&mine[((g + q_t) % E) * 256 + tid], total[g]);
 }
 
+// k_histogram_planes of in ^ base: the same counters, bank rotation, flush rule, grid and ragged end.
+// A tile is four vectors of `in` AND the four vectors of `base` at the same offsets, eight non-temporal loads that are in
+// flight while the tile before it is counted.  A step XORs the arrived tile in registers -- its base registers are dead
+// from then on and receive the next tile's base --, issues the next tile's eight loads and then counts: three buffers of
+// four vectors are live, not four, which is what keeps the kernel at its parent's 128 registers and four workgroups on a
+// CU.  Nothing outside in[0 .. n_bytes) and base[0 .. n_bytes) is read.  The body stands beside its parent's and shares
+// only the lane helpers, so that the parent's instruction stream stays what it was.
+template <int E>
+__global__ __launch_bounds__(kPlanesHistThreads, 4) void k_histogram_planes_delta(const uint8_t* __restrict__ in,
+                                                                               const uint8_t* __restrict__ base, uint64_t n_bytes,
+                                                                               unsigned long long* __restrict__ acc /* [32][E][256] */) {
+  constexpr uint32_t R = kPlanesHistCols / E;
+  __shared__ __attribute__((aligned(16))) uint32_t lh[256 * kPlanesHistCols];
+  uint8_t* const lds = reinterpret_cast<uint8_t*>(lh);
+  const uint32_t tid = threadIdx.x;
+  const PlanesHistLane<E> L(tid);
+  const uint64_t nvec = n_bytes >> 4, ntiles = nvec / kPlanesHistTileVecs;
+  const uint4* const src = reinterpret_cast<const uint4*>(in);
+  const uint4* const bsrc = reinterpret_cast<const uint4*>(base);
+  auto load_tile = [&](uint64_t t, uint4 (&x)[4], uint4 (&d)[4]) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) x[j] = load_stream(src + t * kPlanesHistTileVecs + j * kPlanesHistThreads + tid);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) d[j] = load_stream(bsrc + t * kPlanesHistTileVecs + j * kPlanesHistThreads + tid);
+  };
+  uint64_t t = blockIdx.x;
+  uint4 cur[4] = {}, nxt[4], d[4] = {};
+  if (t < ntiles) load_tile(t, cur, d);  // the first round trip to HBM hides behind the clearing of the counters
+  for (uint32_t i = tid; i < 256 * kPlanesHistCols; i += kPlanesHistThreads) lh[i] = 0;
+  __syncthreads();
+
+  // thread t owns bin t: the sums of k_histogram_planes.  A group's u32 sum at the flush before is the low half of its
+  // total (both start at 0 and gain the same differences mod 2^32), so it is not kept a second time: E registers that the
+  // third buffer needs
+  unsigned long long total[E];
+#pragma unroll
+  for (int g = 0; g < E; ++g) total[g] = 0;
+  const uint32_t q_t = tid / R, r_t = tid % R;
+  auto flush = [&]() {
+    __syncthreads();
+#pragma unroll
+    for (uint32_t g = 0; g < E; ++g) {
+      const uint32_t col = (tid << 5) | (((g + q_t) % E) * R);
+      uint32_t s = 0;
+#pragma unroll
+      for (uint32_t r = 0; r < R; ++r) s += lh[col | ((r + r_t) % R)];
+      total[g] += (uint32_t)(s - (uint32_t)total[g]);
+    }
+    __syncthreads();
+  };
+
+  uint32_t since = 0;  // tiles since the last flush; the same in every lane
+  // counts tile t out of a ^ d while the tile after it is on its way into (b, d)
+  auto step = [&](uint4 (&a)[4], uint4 (&b)[4]) {
+    const uint64_t tn = t + gridDim.x;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) a[j] = make_uint4(a[j].x ^ d[j].x, a[j].y ^ d[j].y, a[j].z ^ d[j].z, a[j].w ^ d[j].w);
+    load_tile(tn < ntiles ? tn : t, b, d);  // behind the last tile: a redundant, harmless load (see k_histogram_planes)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) planes_hist_vec<E>(lds, L, a[j]);
+    if (++since == kPlanesHistFlushTiles) {
+      flush();
+      since = 0;
+    }
+    t = tn;
+  };
+  while (t < ntiles) {  // the two input buffers swap roles without a register copy
+    step(cur, nxt);
+    if (t >= ntiles) break;
+    step(nxt, cur);
+  }
+  // the ragged end belongs to the workgroup that would take tile `ntiles`: whole vectors, then single bytes
+  if (ntiles % gridDim.x == blockIdx.x) {
+    for (uint64_t v = ntiles * kPlanesHistTileVecs + tid; v < nvec; v += kPlanesHistThreads) {
+      const uint4 x = src[v], y = bsrc[v];
+      planes_hist_vec<E>(lds, L, make_uint4(x.x ^ y.x, x.y ^ y.y, x.z ^ y.z, x.w ^ y.w));
+    }
+    const uint64_t k = (nvec << 4) + tid;  // a multiple of 16 plus tid: plane tid % E
+    if (k < n_bytes) atomicAdd(&lh[((uint32_t)(uint8_t)(in[k] ^ base[k]) << 5) | ((tid % E) * R)], 1u);
+  }
+  flush();
+  unsigned long long* const mine = acc + (uint64_t)(blockIdx.x & 31u) * (E * 256);
+#pragma unroll
+  for (uint32_t g = 0; g < E; ++g)
+    if (total[g]) atomicAdd(&mine[((g + q_t) % E) * 256 + tid], total[g]);
+}
+
 // behind k_histogram_planes on the same stream, one workgroup per plane: sums the 32 replicas and zeroes them again, then
 // the end mark counts once (include/encoder.h:123-129); cover: no count stays 0
 __global__ __launch_bounds__(256) void k_histogram_planes_finish(unsigned long long* __restrict__ acc, uint32_t elem_bytes,
@@ -239,14 +326,21 @@ static uint32_t planes_hist_grid(uint64_t n_bytes) {
   return (uint32_t)(g > kPlanesHistGroups ? kPlanesHistGroups : g);
 }
 // -> the first launch error.  An error of the counting launch means that nothing was queued: the replicas are still zero
-hipError_t launch_histogram_planes(const uint8_t* d_in, uint64_t n_elems, uint32_t elem_bytes, uint32_t flags, uint64_t* d_acc,
-                                   uint64_t* d_hists, hipStream_t s) {
+// d_base == nullptr: the plain count; else the count of d_in ^ d_base (the same grid, the same finish)
+hipError_t launch_histogram_planes(const uint8_t* d_in, const uint8_t* d_base, uint64_t n_elems, uint32_t elem_bytes, uint32_t flags,
+                                   uint64_t* d_acc, uint64_t* d_hists, hipStream_t s) {
   const uint64_t n_bytes = n_elems * elem_bytes;
   const dim3 grid(planes_hist_grid(n_bytes)), block(kPlanesHistThreads);
   unsigned long long* const acc = reinterpret_cast<unsigned long long*>(d_acc);
-  if (elem_bytes == 2) hipLaunchKernelGGL(k_histogram_planes<2>, grid, block, 0, s, d_in, n_bytes, acc);
-  else if (elem_bytes == 4) hipLaunchKernelGGL(k_histogram_planes<4>, grid, block, 0, s, d_in, n_bytes, acc);
-  else hipLaunchKernelGGL(k_histogram_planes<8>, grid, block, 0, s, d_in, n_bytes, acc);
+  if (!d_base) {
+    if (elem_bytes == 2) hipLaunchKernelGGL(k_histogram_planes<2>, grid, block, 0, s, d_in, n_bytes, acc);
+    else if (elem_bytes == 4) hipLaunchKernelGGL(k_histogram_planes<4>, grid, block, 0, s, d_in, n_bytes, acc);
+    else hipLaunchKernelGGL(k_histogram_planes<8>, grid, block, 0, s, d_in, n_bytes, acc);
+  } else {
+    if (elem_bytes == 2) hipLaunchKernelGGL(k_histogram_planes_delta<2>, grid, block, 0, s, d_in, d_base, n_bytes, acc);
+    else if (elem_bytes == 4) hipLaunchKernelGGL(k_histogram_planes_delta<4>, grid, block, 0, s, d_in, d_base, n_bytes, acc);
+    else hipLaunchKernelGGL(k_histogram_planes_delta<8>, grid, block, 0, s, d_in, d_base, n_bytes, acc);
+  }
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(k_histogram_planes_finish, dim3(elem_bytes), dim3(256), 0, s, acc, elem_bytes, d_hists,

@@ -154,6 +154,8 @@ EXPORTS = [
     "ghf_decode_bodies_batch_planes_shared_seek",
     "ghf_planes_merge_range", "ghf_decode_planes_range",
     "ghf_histogram_planes", "ghf_planes_image_bytes", "ghf_compress_planes_coded",
+    "ghf_histogram_planes_delta", "ghf_planes_split_delta", "ghf_planes_merge_delta", "ghf_planes_merge_range_delta",
+    "ghf_compress_planes_delta", "ghf_decode_planes_delta", "ghf_decode_planes_range_delta",
 ]
 COMM_ID_BYTES = 128
 
@@ -287,6 +289,14 @@ def lib():
     L.ghf_planes_image_bytes.argtypes = [vp, vp, vp, u32, vp]
     L.ghf_compress_planes_coded.argtypes = [vp, vp, sz, u32, vp, C.c_uint, vp, sz, vp, C.POINTER(Index)]
     L.ghf_planes_merge_range.argtypes = [vp, vp, sz, sz, sz, u32, vp]
+    L.ghf_histogram_planes_delta.argtypes = [vp, vp, vp, sz, u32, C.c_uint, vp]
+    L.ghf_planes_split_delta.argtypes = [vp, vp, vp, sz, u32, vp, sz]
+    L.ghf_planes_merge_delta.argtypes = [vp, vp, sz, vp, sz, u32, vp]
+    L.ghf_planes_merge_range_delta.argtypes = [vp, vp, sz, vp, sz, sz, u32, vp]
+    L.ghf_compress_planes_delta.argtypes = [vp, vp, vp, sz, u32, vp, C.c_uint, vp, sz, vp, C.POINTER(Index)]
+    L.ghf_decode_planes_delta.argtypes = [vp, C.POINTER(vp), C.POINTER(sz), vp, C.POINTER(Index), vp, sz, u32, vp, sz, vp]
+    L.ghf_decode_planes_range_delta.argtypes = [vp, C.POINTER(vp), C.POINTER(sz), vp, C.POINTER(Index), C.POINTER(SeekInfo),
+                                                C.POINTER(vp), C.POINTER(sz), vp, u32, C.c_uint64, C.c_uint64, vp, sz]
     L.ghf_decode_planes_range.argtypes = [vp, C.POINTER(vp), C.POINTER(sz), vp, C.POINTER(Index), C.POINTER(SeekInfo),
                                           C.POINTER(vp), C.POINTER(sz), u32, u64, u64, vp, sz]
     _lib = L
@@ -1147,6 +1157,109 @@ class Context:
             self.L.ghf_decode_planes_range(self.h, ptrs, sizes, d_codes.data_ptr(), indexes, h_infos, t_ptrs, t_bytes, elem_bytes,
                                            first, count, d_out.data_ptr(), d_out.numel() if cap is None else cap),
             "ghf_decode_planes_range")
+        return d_out
+
+    # ---- byte planes against a base tensor: the calls above on d_in ^ d_base, the XOR inside their
+    # streaming kernels.  d_base: a CUDA tensor of the same bytes as d_in / d_out (the range calls: of the range's own
+    # elements); it may be d_out itself in the merging calls ----------------------------------------------------------
+    @staticmethod
+    def _base_ptr(d_base):
+        return None if d_base is None else d_base.data_ptr()
+
+    def histogram_planes_delta(self, d_in, d_base, elem_bytes, n_elems=None, flags=0, out=None):
+        """histogram_planes of d_in ^ d_base in one pass over both; nothing is materialised.  -> int64[elem_bytes, 257]"""
+        n_elems = d_in.numel() * d_in.element_size() // elem_bytes if n_elems is None else n_elems
+        hists = self.torch.empty((elem_bytes, NSYM), dtype=self.torch.int64, device=self.device) if out is None else out
+        self._chk(self.L.ghf_histogram_planes_delta(self.h, d_in.data_ptr(), self._base_ptr(d_base), n_elems, elem_bytes, flags,
+                                                    hists.data_ptr()), "ghf_histogram_planes_delta")
+        return hists
+
+    def planes_split_delta(self, d_in, d_base, elem_bytes, n_elems=None, d_planes=None, plane_stride=None):
+        """planes_split of d_in ^ d_base.  -> (d_planes uint8, plane_stride)"""
+        n_elems = d_in.numel() * d_in.element_size() // elem_bytes if n_elems is None else n_elems
+        if plane_stride is None:
+            plane_stride = (n_elems + 255) & ~255
+        if d_planes is None:
+            d_planes = self.empty_u8(plane_stride * elem_bytes)
+        self._chk(self.L.ghf_planes_split_delta(self.h, d_in.data_ptr(), self._base_ptr(d_base), n_elems, elem_bytes,
+                                                d_planes.data_ptr(), plane_stride), "ghf_planes_split_delta")
+        return d_planes, plane_stride
+
+    def planes_merge_delta(self, d_planes, plane_stride, d_base, n_elems, elem_bytes, d_out=None):
+        """d_out = planes_merge(d_planes) ^ d_base; d_out may be d_base.  -> d_out uint8[n_elems * elem_bytes]"""
+        if d_out is None:
+            d_out = self.empty_u8(n_elems * elem_bytes)
+        self._chk(self.L.ghf_planes_merge_delta(self.h, d_planes.data_ptr(), plane_stride, self._base_ptr(d_base), n_elems, elem_bytes,
+                                                d_out.data_ptr()), "ghf_planes_merge_delta")
+        return d_out
+
+    def planes_merge_range_delta(self, d_planes, plane_stride, d_base, first, count, elem_bytes, d_out=None):
+        """planes_merge_range ^ d_base, where d_base holds base elements [first, first + count) and is indexed like d_out
+        (and may be d_out).  -> d_out uint8[count * elem_bytes]"""
+        if d_out is None:
+            d_out = self.empty_u8(count * elem_bytes)
+        self._chk(self.L.ghf_planes_merge_range_delta(self.h, d_planes.data_ptr(), plane_stride, self._base_ptr(d_base), first, count,
+                                                      elem_bytes, d_out.data_ptr()), "ghf_planes_merge_range_delta")
+        return d_out
+
+    def compress_planes_delta(self, d_in, d_base, elem_bytes, d_codes=None, flags=None, n_elems=None, d_out=None, slot_bytes=None,
+                              indexes=None):
+        """compress_planes_coded of d_in ^ d_base: every image is an ordinary .crs2 of a plane of the XOR.  No host
+        synchronisation.  -> the dict of compress_planes"""
+        t = self.torch
+        n_elems = d_in.numel() * d_in.element_size() // elem_bytes if n_elems is None else n_elems
+        if flags is None:
+            flags = PLANES_BUILD_CODES if d_codes is None else 0
+        if slot_bytes is None:
+            slot_bytes = planes_slot_bytes(n_elems)
+        if d_out is None:
+            d_out = self.empty_u8(slot_bytes * elem_bytes)
+        if d_codes is None:
+            d_codes = t.zeros((elem_bytes, C.sizeof(Code)), dtype=t.uint8, device=self.device)
+        out_bytes = t.zeros(elem_bytes, dtype=t.int64, device=self.device)
+        self._chk(
+            self.L.ghf_compress_planes_delta(self.h, d_in.data_ptr(), self._base_ptr(d_base), n_elems, elem_bytes, d_codes.data_ptr(),
+                                             flags, d_out.data_ptr(), slot_bytes, out_bytes.data_ptr(), indexes),
+            "ghf_compress_planes_delta")
+        return {"out": d_out, "slot_bytes": slot_bytes, "out_bytes": out_bytes, "codes": d_codes, "n_elems": n_elems,
+                "elem_bytes": elem_bytes}
+
+    def decode_planes_delta(self, streams, stream_bytes, d_codes, d_base, n_elems, elem_bytes, indexes=None, d_out=None, cap=None,
+                            nbytes=None):
+        """decode_planes, then ^ d_base in the merge; d_out may be d_base (behind a latched status it then still holds the
+        base).  indexes=None synchronises.  -> (d_out uint8, nbytes int64[1] device)"""
+        ptrs = (C.c_void_p * elem_bytes)(*[x.data_ptr() for x in streams])
+        sizes = (C.c_size_t * elem_bytes)(*[int(v) for v in stream_bytes])
+        if d_out is None:
+            d_out = self.empty_u8(n_elems * elem_bytes)
+        if nbytes is None:
+            nbytes = self.torch.zeros(1, dtype=self.torch.int64, device=self.device)
+        self._chk(
+            self.L.ghf_decode_planes_delta(self.h, ptrs, sizes, d_codes.data_ptr(), indexes, self._base_ptr(d_base), n_elems, elem_bytes,
+                                           d_out.data_ptr(), d_out.numel() if cap is None else cap, nbytes.data_ptr()),
+            "ghf_decode_planes_delta")
+        return d_out, nbytes
+
+    def decode_planes_range_delta(self, streams, stream_bytes, d_codes, d_base, elem_bytes, first, count, indexes=None, infos=None,
+                                  d_tables=None, table_bytes=None, d_out=None, cap=None):
+        """decode_planes_range, then ^ d_base in the merge: d_base holds base elements [first, first + count), indexed like
+        d_out, and may be d_out.  Never synchronises.  -> d_out uint8"""
+        ptrs = (C.c_void_p * elem_bytes)(*[x.data_ptr() for x in streams])
+        sizes = (C.c_size_t * elem_bytes)(*[int(v) for v in stream_bytes])
+        h_infos = t_ptrs = t_bytes = None
+        if infos is not None:
+            h_infos = (SeekInfo * elem_bytes)(*infos)
+            t_ptrs = (C.c_void_p * elem_bytes)(*[x.data_ptr() for x in d_tables])
+            if table_bytes is None:
+                table_bytes = [seek_bytes(i.n_symbols) for i in infos]
+            t_bytes = (C.c_size_t * elem_bytes)(*[int(v) for v in table_bytes])
+        if d_out is None:
+            d_out = self.empty_u8(count * elem_bytes)
+        self._chk(
+            self.L.ghf_decode_planes_range_delta(self.h, ptrs, sizes, d_codes.data_ptr(), indexes, h_infos, t_ptrs, t_bytes,
+                                                 self._base_ptr(d_base), elem_bytes, first, count, d_out.data_ptr(),
+                                                 d_out.numel() if cap is None else cap),
+            "ghf_decode_planes_range_delta")
         return d_out
 
     # ---- seekable streams: the seek table (the persistent form of the side-car) ----------------

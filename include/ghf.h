@@ -775,6 +775,77 @@ int ghf_decode_planes_range(ghf_ctx* ctx, const uint8_t* const* h_stream_ptrs, c
                             const uint8_t* const* h_table_ptrs, const size_t* h_table_bytes, uint32_t elem_bytes,
                             uint64_t first, uint64_t count, uint8_t* d_out, size_t cap);
 
+/* ---- byte planes against a base tensor: XOR-delta compress, decode, range -----
+ * Callers that hold a SERIES of tensors -- successive checkpoints, a fine-tuned model beside its base, optimizer state
+ * step after step -- compress `new ^ base` instead of `new`: the sign / exponent byte and the top mantissa bits of an
+ * element rarely change, so the high planes of the XOR are almost all zeros.  XOR is lossless for every bit pattern and
+ * its own inverse.  These calls are the byte-plane calls above with the XOR inside the streaming kernels that touch every
+ * interleaved vector anyway: nothing is materialised, and the .crs2 format does not change -- EVERY PLANE IS AN ORDINARY
+ * STANDALONE .crs2 IMAGE, of the bytes of d_in ^ d_base, which the reference, ghf_decode, the seek table and the range
+ * calls read.
+ *
+ * d_base is device memory, 16-byte aligned, and holds the same n_elems * elem_bytes bytes as d_in / d_out (for the two
+ * range calls: count * elem_bytes bytes, see there); nothing outside them is read.  Conventions, argument checks, the
+ * order of the checks and the error codes of every call are those of the plain call it mirrors; in addition a null d_base
+ * is refused where the other null pointers are and a misaligned one where the other misaligned pointers are: GHF_E_INVAL,
+ * nothing queued, checked before anything touches HIP.
+ * In the merging calls (ghf_planes_merge_delta, ghf_planes_merge_range_delta, ghf_decode_planes_delta,
+ * ghf_decode_planes_range_delta) d_base == d_out is allowed, "XOR the delta into the base": every lane reads the base
+ * vector it then overwrites.  ANY OTHER OVERLAP of d_base with d_out, and any overlap of either with the planes, is
+ * undefined. */
+
+/* No reference counterpart (generalises the flat count of include/encoder.h:123-150, which include/compressor.h:62-73
+ * runs once per file).  ghf_histogram_planes of d_in ^ d_base in one pass over both buffers: d_hists (device
+ * u64[elem_bytes][257]) feeds ghf_build_codes and ghf_planes_image_bytes unchanged, so "delta or plain, which is smaller?"
+ * costs two histogram passes. */
+int ghf_histogram_planes_delta(ghf_ctx* ctx, const uint8_t* d_in, const uint8_t* d_base, size_t n_elems, uint32_t elem_bytes,
+                               unsigned flags, uint64_t* d_hists /* [elem_bytes][257] */);
+
+/* No reference counterpart (generalises the flat input of include/compressor.h:62-73).  ghf_planes_split of d_in ^ d_base:
+ * byte b of element k of the XOR goes to d_planes[b * plane_stride + k]. */
+int ghf_planes_split_delta(ghf_ctx* ctx, const uint8_t* d_in, const uint8_t* d_base, size_t n_elems, uint32_t elem_bytes,
+                           uint8_t* d_planes, size_t plane_stride);
+
+/* No reference counterpart (generalises the flat output of include/compressor.h:87-92).  The inverse of
+ * ghf_planes_split_delta: d_out[0 .. n_elems * elem_bytes) <- ghf_planes_merge of the planes, XOR d_base.  d_base == d_out
+ * is allowed.  Does not look at the context's status word. */
+int ghf_planes_merge_delta(ghf_ctx* ctx, const uint8_t* d_planes, size_t plane_stride, const uint8_t* d_base, size_t n_elems,
+                           uint32_t elem_bytes, uint8_t* d_out);
+
+/* No reference counterpart (generalises the flat output of include/compressor.h:87-92).  ghf_planes_merge_range with the
+ * XOR: d_base[0 .. count * elem_bytes) holds base elements [first, first + count) -- the caller's shard or rows of the base,
+ * 16-byte aligned and indexed exactly like d_out, whatever `first` is.  d_base == d_out is allowed. */
+int ghf_planes_merge_range_delta(ghf_ctx* ctx, const uint8_t* d_planes, size_t plane_stride, const uint8_t* d_base, size_t first,
+                                 size_t count, uint32_t elem_bytes, uint8_t* d_out);
+
+/* No reference counterpart: Compressor::compress(), include/compressor.h:62-73, once per byte plane of d_in ^ d_base, its
+ * count (include/encoder.h:123-150) made in one pass.  ghf_compress_planes_coded of d_in ^ d_base: the same flags
+ * (GHF_PLANES_BUILD_CODES or the caller's d_codes), the same vetting, the same latching of GHF_E_FORMAT / GHF_E_NOCODE
+ * (d_out_bytes UNSPECIFIED behind a latched status).  On the stream: ghf_histogram_planes_delta into counters of the
+ * context; the codes; ghf_planes_split_delta into the workspace; per plane the unchanged ghf_encode_plan and
+ * ghf_encode_emit.  Every image, size, code and side-car is byte for byte what ghf_compress_planes_coded writes for a
+ * buffer that holds d_in ^ d_base; the context's caches are forgotten as there. */
+int ghf_compress_planes_delta(ghf_ctx* ctx, const uint8_t* d_in, const uint8_t* d_base, size_t n_elems, uint32_t elem_bytes,
+                              ghf_code* d_codes /* [elem_bytes] 16-byte aligned: in or out with BUILD_CODES */, unsigned flags,
+                              uint8_t* d_out, size_t slot_bytes, uint64_t* d_out_bytes, const ghf_index* indexes);
+
+/* No reference counterpart: Decompressor::decompress(), include/compressor.h:87-92, once per byte plane.
+ * ghf_decode_planes with ghf_planes_merge_delta last: d_out <- what the images decode to, XOR d_base.  indexes == NULL
+ * SYNCHRONISES as it does there.  d_base == d_out is allowed.  Behind a latched status the merge stores nothing: in place,
+ * d_out then still holds the base. */
+int ghf_decode_planes_delta(ghf_ctx* ctx, const uint8_t* const* h_stream_ptrs, const size_t* h_stream_bytes,
+                            const ghf_code* d_codes, const ghf_index* indexes, const uint8_t* d_base, size_t n_elems,
+                            uint32_t elem_bytes, uint8_t* d_out, size_t cap, uint64_t* d_out_bytes);
+
+/* No reference counterpart: Decompressor::decompress(), include/compressor.h:87-92, for a part of a typed tensor.
+ * ghf_decode_planes_range with ghf_planes_merge_range_delta last, from live side-cars or from seek tables: d_base[0 ..
+ * count * elem_bytes) holds base elements [first, first + count), as for ghf_planes_merge_range_delta; d_base == d_out is
+ * allowed.  count == 0: GHF_OK, nothing queued. */
+int ghf_decode_planes_range_delta(ghf_ctx* ctx, const uint8_t* const* h_stream_ptrs, const size_t* h_stream_bytes,
+                                  const ghf_code* d_codes, const ghf_index* indexes, const ghf_seek_info* h_infos,
+                                  const uint8_t* const* h_table_ptrs, const size_t* h_table_bytes, const uint8_t* d_base,
+                                  uint32_t elem_bytes, uint64_t first, uint64_t count, uint8_t* d_out, size_t cap);
+
 /* Multi-GPU decode of a stream that has no side-car ("per-rank self-sync + one all-gather of symbol
  * counts"; the reference's decoders, canonical_huff_encoder.cc:377-568, are single-stream).  The caller cuts the body
  * at byte positions; a rank's piece is its own bytes followed by >= 8 bytes of look-ahead from the next piece (zeros
