@@ -12,6 +12,7 @@
 namespace ghf {
 
 struct LdsCounts {  // the workgroup's 256 byte counts; the end mark counts once (include/encoder.h:123-129)
+  static constexpr bool kAnyCount = false;  // 32-bit bins of an item of at most 1 MiB: far inside the builder's domain
   const uint32_t* bins;
   __device__ __forceinline__ long long operator()(int s) const { return s < 256 ? (long long)bins[s] : 1ll; }
 };

@@ -299,14 +299,27 @@ __device__ __forceinline__ void code_sync() {
   else wave_sync();
 }
 
+// The counts' domain (include/ghf.h, ghf_build_code): a heap entry has 64 - 9 = GHF_HIST_TOTAL_BITS bits for a node's
+// weight and the root's weight is the sum of all counts, so that sum must stay below 2^55.  `mine` = the sum of this lane's
+// counts, `any_big` = one of them is 2^55 or more by itself (with none that big, a sum of 257 cannot wrap 64 bits).
+// Registers only: one ballot, one wave reduction, one compare.  Wave-uniform result.
+__device__ __forceinline__ bool counts_out_of_domain(u64t mine, bool any_big) {
+  if (__ballot(any_big)) return true;
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) mine += __shfl_xor(mine, d, 64);
+  return (mine >> GHF_HIST_TOTAL_BITS) != 0;
+}
+
 struct HistCounts {  // the counts as K1 leaves them: u64[257] in global memory (k_build_code, k_build_codes)
+  static constexpr bool kAnyCount = true;  // caller-supplied 64-bit counts: held to the domain before the first push
   const unsigned long long* __restrict__ hist;
   __device__ __forceinline__ long long operator()(int s) const { return (long long)hist[s]; }
 };
 
-// The body.  counts(s) = the count of symbol s (0..256; the end mark's is 1), as a long long.  Failures (GHF_E_EMPTY,
-// GHF_E_CODELEN) are latched at *status -- the context's status word, or a word of the caller's own -- and end the body;
-// *out is then not (completely) written.  s_ndata: one LDS int.
+// The body.  counts(s) = the count of symbol s (0..256; the end mark's is 1), as a long long; Counts::kAnyCount says
+// whether their sum can reach 2^55 at all (else the domain check is compiled out).  Failures (GHF_E_INVAL for counts out
+// of the domain, GHF_E_EMPTY, GHF_E_CODELEN) are latched at *status -- the context's status word, or a word of the
+// caller's own -- and end the body; *out is then not (completely) written.  s_ndata: one LDS int.
 template <bool LIMIT, bool ONE_WAVE_GROUP, class QLds, class Counts>
 __device__ __forceinline__ void build_code_body(HeapLds& heap, QLds& Q, CodeLds& cl, int& s_ndata, const Counts counts,
                                                 ghf_code* __restrict__ out, int* __restrict__ status, uint32_t empty_ok,
@@ -320,6 +333,19 @@ __device__ __forceinline__ void build_code_body(HeapLds& heap, QLds& Q, CodeLds&
     fr[j] = s < GHF_NSYM ? counts(s) : 0ll;
     if constexpr (LIMIT) {
       if (s < GHF_NSYM) Q.freq[s] = fr[j];
+    }
+  }
+  if constexpr (Counts::kAnyCount) {
+    u64t mine = 0;
+    bool any_big = false;
+#pragma unroll
+    for (int j = 0; j < 5; ++j) {
+      mine += (u64t)fr[j];
+      any_big |= ((u64t)fr[j] >> GHF_HIST_TOTAL_BITS) != 0;
+    }
+    if (counts_out_of_domain(mine, any_big)) {  // a weight would wrap in the heap word: refused, *out untouched
+      if (lane == 0) latch_status(status, GHF_E_INVAL);
+      return;
     }
   }
   for (int s = lane; s < GHF_NSYM; s += 64) heap.cur[s] = (uint16_t)s;

@@ -260,6 +260,20 @@ __global__ __launch_bounds__(64) void k_crs_build_code(const unsigned long long*
   __shared__ ghf_tree tree;
   __builtin_amdgcn_s_setprio(3);  // see k_build_code
   const int lane = threadIdx.x;
+  {  // the counts' domain (see counts_out_of_domain): the 256 counts read here sum to less than 2^55, or nothing is built
+    u64t mine = 0;
+    bool any_big = false;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const u64t f = hist[lane + 64 * j];
+      mine += f;
+      any_big |= (f >> GHF_HIST_TOTAL_BITS) != 0;
+    }
+    if (counts_out_of_domain(mine, any_big)) {
+      if (lane == 0) latch_status(status, GHF_E_INVAL);
+      return;
+    }
+  }
   for (int s = lane; s < GHF_NSYM; s += 64) heap.cur[s] = (uint16_t)s;
   for (int i = lane; i < GHF_NSYM + 256 + 7; i += 64) {
     heap.parent[i] = 0;

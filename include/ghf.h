@@ -129,7 +129,15 @@ int ghf_histogram_add(ghf_ctx* ctx, const uint8_t* d_in, size_t n, uint64_t* d_h
 
 /* ---- K2+K3: CanonicalHuffEncoder::gen_encode = get_encoding_length + do_gen_encode,
  *      include/canonical_huff_encoder.cc:35-42,289-345,69-141 -- on ONE wavefront, emulating
- *      libstdc++'s priority_queue order exactly.  d_hist is not modified. */
+ *      libstdc++'s priority_queue order exactly.  d_hist is not modified.
+ *      The counts' domain: the 257 counts of d_hist must sum to less than 2^GHF_HIST_TOTAL_BITS = 2^55.  A heap entry
+ *      is (weight << 9) | symbol index in one 64-bit word -- 9 bits for the 257 indices leave 55 for the weight, and the
+ *      root's weight is the sum of all counts -- so beyond that a weight would wrap and the result would be a well-formed
+ *      code for other counts.  Such a histogram (ghf_histogram_add and ghf_comm_allreduce_hist accumulate without a limit
+ *      of their own; a caller may pass any counts) latches GHF_E_INVAL before anything is built, and d_code is not
+ *      written.  The reference counts in 64-bit integers and has no such edge, but no input of fewer than 2^55 - 1 bytes
+ *      (32 PiB) reaches it. */
+#define GHF_HIST_TOTAL_BITS 55
 int ghf_build_code(ghf_ctx* ctx, const uint64_t* d_hist, ghf_code* d_code);
 
 /* ---- a5: CanonicalHuffEncoder::write_encode_info, include/canonical_huff_encoder.cc:210-242 ------
@@ -604,6 +612,8 @@ int ghf_histogram_batch_planes(ghf_ctx* ctx, const uint8_t* const* d_in_ptrs, co
  * d_codes + k, flags) leaves, and device failures latch exactly as there.  As there too, and unlike the other calls of
  * this group, it touches the context's caches: what the context derived from the former contents of one of d_codes (the
  * plan or the prepared tables of a ghf_compress / ghf_decode under that code) is forgotten, since the tables change.
+ * Every histogram is held to the counts' domain stated at ghf_build_code (sum below 2^GHF_HIST_TOTAL_BITS): one that is
+ * not latches GHF_E_INVAL and leaves its d_codes[k] unwritten, the other codes of the launch are built as usual.
  * n_codes == 0 or > GHF_PLANES_MAX: GHF_E_INVAL. */
 int ghf_build_codes(ghf_ctx* ctx, const uint64_t* d_hists /* [n_codes][257] */, uint32_t n_codes,
                     ghf_code* d_codes /* [n_codes] */, unsigned flags);
@@ -949,7 +959,9 @@ typedef struct ghf_tree {
 
 /* EncodeHuffTree::build_tree + gen_encode + serialize_tree (include/huff_tree.cc:138-187) on one wavefront.
  * d_hist: ghf_histogram()'s output (slot [256] is ignored).  d_code receives length[] / codeword[] for K4/K5; when the
- * tree is deeper than 32, codeword[] holds bits 0..31 of every code and symbol[] bits 32..63 (else symbol[] = 0xFFFFFFFF). */
+ * tree is deeper than 32, codeword[] holds bits 0..31 of every code and symbol[] bits 32..63 (else symbol[] = 0xFFFFFFFF).
+ * The counts' domain is the one stated at ghf_build_code, over the 256 counts read here: a sum of 2^GHF_HIST_TOTAL_BITS or
+ * more latches GHF_E_INVAL, and neither d_tree nor d_code is written. */
 int ghf_crs_build_code(ghf_ctx* ctx, const uint64_t* d_hist, ghf_tree* d_tree, ghf_code* d_code);
 
 /* Compressor<NormalHuffEncoder<>>::compress() (include/compressor.h:62-73, normal_huff_encoder.h:136-186).
