@@ -107,6 +107,8 @@ int ghf_ctx_create(int device, ghf_ctx** out) {
   GHF_STEP(hipMalloc(&c->d_planes_hist_acc, kPlanesHistAccWords * sizeof(uint64_t)));
   GHF_STEP(hipMemset(c->d_planes_hist_acc, 0, kPlanesHistAccWords * sizeof(uint64_t)));
   GHF_STEP(hipMalloc(&c->d_planes_hists, (size_t)GHF_PLANES_MAX * GHF_NSYM * sizeof(uint64_t)));
+  GHF_STEP(hipMalloc(&c->d_sparse_counts, kSparseGroups * sizeof(uint64_t)));
+  GHF_STEP(hipMalloc(&c->d_sparse_offs, kSparseOffWords * sizeof(uint64_t)));
   GHF_STEP(hipMemset(c->d_status, 0, sizeof(int)));
 #undef GHF_STEP
   if (e != hipSuccess) {
@@ -132,6 +134,8 @@ int ghf_ctx_destroy(ghf_ctx* c) {
   if (c->d_dt) (void)hipFree(c->d_dt);
   if (c->d_planes_hist_acc) (void)hipFree(c->d_planes_hist_acc);
   if (c->d_planes_hists) (void)hipFree(c->d_planes_hists);
+  if (c->d_sparse_counts) (void)hipFree(c->d_sparse_counts);
+  if (c->d_sparse_offs) (void)hipFree(c->d_sparse_offs);
   if (c->d) (void)hipFree(c->d);
   if (c->h) (void)hipHostFree(c->h);
   release(c->chunk_hist);
@@ -146,6 +150,7 @@ int ghf_ctx_destroy(ghf_ctx* c) {
   release(c->range_dt);
   release(c->batch_codes);
   release(c->planes);
+  release(c->sparse);
   if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
   delete c;
   return GHF_OK;
@@ -1998,6 +2003,230 @@ int ghf_crs_decode(ghf_ctx* c, const uint8_t* d_stream, size_t stream_bytes, int
   p.out = d_out;
   p.out_bytes = d_out_bytes;
   return decode_with_index(c, "ghf_crs_decode", index, cap, p);
+}
+
+// ---------------------------------------------------------------------------------------------- zero-suppressed byte planes
+// (no reference counterpart)
+size_t ghf_sparse_mask_bytes(size_t n) { return n / 8 + (n % 8 != 0); }
+
+int ghf_sparse_split(ghf_ctx* c, const uint8_t* d_in, size_t n, uint8_t* d_mask, uint8_t* d_vals, size_t vals_cap, uint64_t* d_n_vals) {
+  if (!c || !d_in || !d_mask || !d_n_vals || (vals_cap && !d_vals)) return GHF_E_INVAL;
+  if (!aligned16(d_in) || !aligned16(d_mask) || !aligned16(d_vals) || (reinterpret_cast<uintptr_t>(d_n_vals) & 7u))
+    return fail(c, GHF_E_INVAL, "ghf_sparse_split: d_in, d_mask and d_vals must be 16-byte aligned, d_n_vals 8-byte aligned");
+  if (n > (size_t)-1 - kSparseTile) return fail(c, GHF_E_INVAL, "ghf_sparse_split: n overflows");
+  if (n == 0) return fail(c, GHF_E_EMPTY, "ghf_sparse_split: no bytes");
+  GHF_HIP(c, hipSetDevice(c->device));
+  launch_sparse_split(d_in, n, d_mask, d_vals, vals_cap, d_n_vals, c->d_sparse_counts, c->d_sparse_offs, c->d_status, c->stream);
+  GHF_HIP(c, hipGetLastError());
+  return GHF_OK;
+}
+
+int ghf_sparse_merge(ghf_ctx* c, const uint8_t* d_mask, const uint8_t* d_vals, size_t n_vals, size_t n, uint8_t* d_out) {
+  if (!c || !d_mask || !d_out || (n_vals && !d_vals)) return GHF_E_INVAL;
+  if (!aligned16(d_mask) || !aligned16(d_vals) || !aligned16(d_out))
+    return fail(c, GHF_E_INVAL, "ghf_sparse_merge: d_mask, d_vals and d_out must be 16-byte aligned");
+  if (n > (size_t)-1 - kSparseTile) return fail(c, GHF_E_INVAL, "ghf_sparse_merge: n overflows");
+  if (n == 0) return fail(c, GHF_E_EMPTY, "ghf_sparse_merge: no bytes");
+  GHF_HIP(c, hipSetDevice(c->device));
+  launch_sparse_merge(d_mask, d_vals, n_vals, n, d_out, c->d_sparse_counts, c->d_sparse_offs, c->d_status, c->stream);
+  GHF_HIP(c, hipGetLastError());
+  return GHF_OK;
+}
+
+// sparse_planes as the compress call (GHF_SPARSE_AUTO alone, or bits below elem_bytes) or the decode (bits only) takes it
+static inline bool sparse_planes_ok(unsigned sparse_planes, uint32_t elem_bytes, bool may_be_auto) {
+  if (sparse_planes == GHF_SPARSE_AUTO) return may_be_auto;
+  return (sparse_planes >> elem_bytes) == 0;
+}
+
+// the context's second workspace for one sparse plane of n_elems bytes: the mask at [0, *mask_stride), the values behind it
+static int sparse_workspace(ghf_ctx* c, size_t n_elems, size_t* mask_stride) {
+  *mask_stride = (ghf_sparse_mask_bytes(n_elems) + 255) & ~(size_t)255;
+  return grow(c, c->sparse, *mask_stride + ((n_elems + 255) & ~(size_t)255));
+}
+
+static void free_indexes(ghf_ctx* c, ghf_index* ix, uint32_t count) {
+  for (uint32_t j = 0; j < count; ++j)
+    if (ix[j].d_chunk_bit || ix[j].d_seg_bit) (void)free_index_arrays(c, &ix[j]);
+  std::memset(ix, 0, count * sizeof *ix);
+}
+
+static int compress_planes_sparse(ghf_ctx* c, const char* who, const uint8_t* d_in, Base base, size_t n_elems, uint32_t elem_bytes,
+                                  unsigned sparse_planes, uint8_t* d_out, size_t slot_bytes, uint64_t* d_out_bytes, ghf_code* d_codes,
+                                  ghf_index* h_indexes, unsigned* h_sparse_planes, size_t* h_n_vals) {
+  if (!c || !d_in || !d_out || !d_out_bytes || !h_sparse_planes || !h_n_vals || base.null()) return GHF_E_INVAL;
+  const std::string f = std::string(who) + ": ";
+  if (!elem_bytes_ok(elem_bytes)) return fail(c, GHF_E_INVAL, (f + "elem_bytes must be 2, 4 or 8").c_str());
+  if (!aligned16(d_in) || !aligned16(d_out) || (slot_bytes & 15u) || !aligned16(d_codes) || base.misaligned())
+    return fail(c, GHF_E_INVAL, (f + "d_in, d_base, d_out, d_codes and slot_bytes must be multiples of 16").c_str());
+  if (!sparse_planes_ok(sparse_planes, elem_bytes, true))
+    return fail(c, GHF_E_INVAL, (f + "sparse_planes is GHF_SPARSE_AUTO alone or has bits below elem_bytes only").c_str());
+  if (workspace_overflow(n_elems, elem_bytes)) return fail(c, GHF_E_INVAL, (f + "n_elems * elem_bytes overflows").c_str());
+  if (n_elems == 0) return fail(c, GHF_E_EMPTY, (f + "no elements").c_str());
+  if (slot_bytes < ghf_planes_slot_bytes(n_elems)) return fail(c, GHF_E_CAP, (f + "slot_bytes below ghf_planes_slot_bytes(n_elems)").c_str());
+  GHF_HIP(c, hipSetDevice(c->device));
+  const uint32_t E = elem_bytes;
+  size_t stride = 0, mask_stride = 0;
+  int rc = planes_workspace(c, n_elems, E, &stride);
+  if (!rc) rc = sparse_workspace(c, n_elems, &mask_stride);
+  if (!rc && !d_codes) rc = grow(c, c->batch_codes, 2 * GHF_PLANES_MAX);
+  if (rc) return rc;
+  ghf_code* codes = d_codes ? d_codes : c->batch_codes.p;
+  // compressor.h:63 for all planes in one pass, and THE ONE WAIT of the call: count_p[0] says how many values plane p has
+  if ((rc = histogram_planes_into(c, (f + "histogram launch").c_str(), d_in, base.p, n_elems, E, 0, c->d_planes_hists))) return rc;
+  uint64_t counts[GHF_PLANES_MAX * GHF_NSYM];
+  GHF_HIP(c, hipMemcpyAsync(counts, c->d_planes_hists, (size_t)E * GHF_NSYM * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+  GHF_HIP(c, hipStreamSynchronize(c->stream));
+  unsigned chosen = 0;
+  for (uint32_t p = 0; p < E; ++p) {
+    const uint64_t zeros = counts[(size_t)p * GHF_NSYM];
+    if (zeros > n_elems) return fail(c, GHF_E_HIP, (f + "the plane counts did not arrive").c_str());
+    h_n_vals[p] = n_elems - (size_t)zeros;
+    if (sparse_planes == GHF_SPARSE_AUTO ? zeros >= n_elems - n_elems / 4 : (sparse_planes >> p) & 1u) chosen |= 1u << p;
+  }
+  *h_sparse_planes = chosen;
+  const size_t mask_bytes = ghf_sparse_mask_bytes(n_elems);
+  if (h_indexes) {  // one side-car per stored stream, of that stream's own symbol count
+    std::memset(h_indexes, 0, 2 * E * sizeof *h_indexes);
+    for (uint32_t p = 0; p < E && !rc; ++p) {
+      const bool sparse = (chosen >> p) & 1u;
+      rc = ghf_index_alloc(c, sparse ? mask_bytes : n_elems, &h_indexes[p]);
+      if (!rc && sparse && h_n_vals[p]) rc = ghf_index_alloc(c, h_n_vals[p], &h_indexes[E + p]);
+    }
+    if (rc) {
+      free_indexes(c, h_indexes, 2 * E);
+      return rc;
+    }
+  }
+  GHF_HIP(c, hipMemsetAsync(d_out_bytes, 0, 2 * E * sizeof(uint64_t), c->stream));  // the empty slots
+  launch_planes_split(d_in, base.p, n_elems, E, c->planes.p, stride, c->stream);
+  GHF_HIP(c, hipGetLastError());
+  uint8_t *d_mask = c->sparse.p, *d_vals = c->sparse.p + mask_stride;
+  for (uint32_t p = 0; p < E && !rc; ++p) {
+    const uint8_t* plane = c->planes.p + p * stride;
+    // K1 has not seen what stands at these addresses now: the workspaces are refilled for every plane
+    c->hist.forget();
+    c->plan.forget();
+    if (!((chosen >> p) & 1u)) {  // what ghf_compress_planes_coded(GHF_PLANES_BUILD_CODES) queues for the plane
+      if ((rc = ghf_build_codes(c, c->d_planes_hists + (size_t)p * GHF_NSYM, 1, codes + p, 0))) break;
+      if ((rc = ghf_encode_plan(c, plane, n_elems, codes + p, &c->d->total_bits))) break;
+      if ((rc = ghf_encode_emit(c, plane, n_elems, codes + p, nullptr, GHF_EMIT_LAST | GHF_EMIT_HEADER, d_out + p * slot_bytes, slot_bytes,
+                                h_indexes ? h_indexes + p : nullptr, c->d->end)))
+        break;
+      launch_store_u64(d_out_bytes + p, &c->d->end[1], 0, c->stream);
+      GHF_HIP(c, hipGetLastError());
+      continue;
+    }
+    launch_sparse_split(plane, n_elems, d_mask, d_vals, n_elems, c->d_sparse_offs + kSparseOffWords - 1, c->d_sparse_counts, c->d_sparse_offs,
+                        c->d_status, c->stream);
+    GHF_HIP(c, hipGetLastError());
+    // compressor.h:62-73 for the mask and for the values, each a byte string of its own
+    if ((rc = ghf_compress(c, d_mask, mask_bytes, d_out + p * slot_bytes, slot_bytes, d_out_bytes + p, codes + p,
+                           h_indexes ? h_indexes + p : nullptr)))
+      break;
+    if (h_n_vals[p])
+      rc = ghf_compress(c, d_vals, h_n_vals[p], d_out + (E + p) * slot_bytes, slot_bytes, d_out_bytes + E + p, codes + E + p,
+                        h_indexes ? h_indexes + E + p : nullptr);
+  }
+  c->hist.forget();
+  c->plan.forget();
+  return rc;
+}
+
+int ghf_compress_planes_sparse(ghf_ctx* c, const uint8_t* d_in, size_t n_elems, uint32_t elem_bytes, unsigned sparse_planes, uint8_t* d_out,
+                               size_t slot_bytes, uint64_t* d_out_bytes, ghf_code* d_codes, ghf_index* h_indexes, unsigned* h_sparse_planes,
+                               size_t* h_n_vals) {
+  return compress_planes_sparse(c, "ghf_compress_planes_sparse", d_in, no_base(), n_elems, elem_bytes, sparse_planes, d_out, slot_bytes,
+                                d_out_bytes, d_codes, h_indexes, h_sparse_planes, h_n_vals);
+}
+int ghf_compress_planes_sparse_delta(ghf_ctx* c, const uint8_t* d_in, const uint8_t* d_base, size_t n_elems, uint32_t elem_bytes,
+                                     unsigned sparse_planes, uint8_t* d_out, size_t slot_bytes, uint64_t* d_out_bytes, ghf_code* d_codes,
+                                     ghf_index* h_indexes, unsigned* h_sparse_planes, size_t* h_n_vals) {
+  return compress_planes_sparse(c, "ghf_compress_planes_sparse_delta", d_in, base_of(d_base), n_elems, elem_bytes, sparse_planes, d_out,
+                                slot_bytes, d_out_bytes, d_codes, h_indexes, h_sparse_planes, h_n_vals);
+}
+
+// ghf_decode of one stored stream of `symbols` bytes into the workspace at d_to[0 .. cap)
+static int decode_stored(ghf_ctx* c, const std::string& f, const uint8_t* d_stream, size_t stream_bytes, const ghf_code* d_code,
+                         const ghf_index* index, size_t symbols, uint8_t* d_to, size_t cap) {
+  int rc;
+  if (!index) {  // the side-car-less path: synchronises, and keeps the side-car for the decode that follows
+    uint64_t got = 0;
+    if ((rc = ghf_decoded_size(c, d_stream, stream_bytes, d_code, &got))) return rc;
+    if (got != symbols) return fail(c, GHF_E_CORRUPT, (f + "a stream does not decode to the size its plane gives it").c_str());
+  }
+  return ghf_decode(c, d_stream, stream_bytes, d_code, index, d_to, cap, nullptr);
+}
+
+static int decode_planes_sparse(ghf_ctx* c, const char* who, const uint8_t* const* h_stream_ptrs, const size_t* h_stream_bytes,
+                                const ghf_code* d_codes, const ghf_index* indexes, Base base, unsigned sparse_planes, const size_t* h_n_vals,
+                                size_t n_elems, uint32_t elem_bytes, uint8_t* d_out, size_t cap, uint64_t* d_out_bytes) {
+  if (!c || !h_stream_ptrs || !h_stream_bytes || !d_codes || !d_out || !h_n_vals || base.null()) return GHF_E_INVAL;
+  const std::string f = std::string(who) + ": ";
+  if (!elem_bytes_ok(elem_bytes)) return fail(c, GHF_E_INVAL, (f + "elem_bytes must be 2, 4 or 8").c_str());
+  const uint32_t E = elem_bytes;
+  if (!sparse_planes_ok(sparse_planes, E, false))
+    return fail(c, GHF_E_INVAL, (f + "sparse_planes has bits below elem_bytes only (the mask the compress call reported)").c_str());
+  const size_t mask_bytes = ghf_sparse_mask_bytes(n_elems);
+  // slot j is stored when it is a plane's own slot, or the values slot of a sparse plane that has values
+  auto symbols_of = [&](uint32_t j) -> size_t {
+    const uint32_t p = j % E;
+    const bool sparse = (sparse_planes >> p) & 1u;
+    if (j < E) return sparse ? mask_bytes : n_elems;
+    return sparse ? h_n_vals[p] : 0;
+  };
+  for (uint32_t p = 0; p < E; ++p)
+    if (((sparse_planes >> p) & 1u) && h_n_vals[p] > n_elems) return fail(c, GHF_E_INVAL, (f + "a plane has more values than elements").c_str());
+  for (uint32_t j = 0; j < 2 * E; ++j)
+    if ((j < E || symbols_of(j)) && (!h_stream_ptrs[j] || !aligned16(h_stream_ptrs[j])))
+      return fail(c, GHF_E_INVAL, (f + "a stream pointer is null or not 16-byte aligned").c_str());
+  if (!aligned16(d_out) || base.misaligned()) return fail(c, GHF_E_INVAL, (f + "d_out and d_base must be 16-byte aligned").c_str());
+  if (workspace_overflow(n_elems, E)) return fail(c, GHF_E_INVAL, (f + "n_elems * elem_bytes overflows").c_str());
+  for (uint32_t j = 0; indexes && j < 2 * E; ++j)
+    if ((j < E || symbols_of(j)) && (indexes[j].n_symbols != symbols_of(j) || !index_is_whole(&indexes[j])))
+      return fail(c, GHF_E_INVAL, (f + "an index does not cover exactly the symbols of its stream").c_str());
+  if (n_elems == 0) return fail(c, GHF_E_EMPTY, (f + "no elements").c_str());
+  if (cap < n_elems * E) return fail(c, GHF_E_CAP, (f + "output capacity below n_elems * elem_bytes").c_str());
+  GHF_HIP(c, hipSetDevice(c->device));
+  size_t stride = 0, mask_stride = 0;
+  int rc = planes_workspace(c, n_elems, E, &stride);
+  if (!rc && sparse_planes) rc = sparse_workspace(c, n_elems, &mask_stride);
+  if (rc) return rc;
+  for (uint32_t p = 0; p < E; ++p) {
+    uint8_t* plane = c->planes.p + p * stride;
+    if (!((sparse_planes >> p) & 1u)) {
+      if ((rc = decode_stored(c, f, h_stream_ptrs[p], h_stream_bytes[p], d_codes + p, indexes ? indexes + p : nullptr, n_elems, plane, stride)))
+        return rc;
+      continue;
+    }
+    uint8_t *d_mask = c->sparse.p, *d_vals = c->sparse.p + mask_stride;
+    if ((rc = decode_stored(c, f, h_stream_ptrs[p], h_stream_bytes[p], d_codes + p, indexes ? indexes + p : nullptr, mask_bytes, d_mask,
+                            mask_stride)))
+      return rc;
+    if (h_n_vals[p] &&
+        (rc = decode_stored(c, f, h_stream_ptrs[E + p], h_stream_bytes[E + p], d_codes + E + p, indexes ? indexes + E + p : nullptr,
+                            h_n_vals[p], d_vals, c->sparse.cap - mask_stride)))
+      return rc;
+    launch_sparse_merge(d_mask, d_vals, h_n_vals[p], n_elems, plane, c->d_sparse_counts, c->d_sparse_offs, c->d_status, c->stream);
+    GHF_HIP(c, hipGetLastError());
+  }
+  launch_planes_merge(c->planes.p, stride, base.p, n_elems, E, d_out, c->d_status, c->stream);  // nothing is stored behind a latched status
+  if (d_out_bytes) launch_store_u64(d_out_bytes, nullptr, (uint64_t)n_elems * E, c->stream);
+  GHF_HIP(c, hipGetLastError());
+  return GHF_OK;
+}
+
+int ghf_decode_planes_sparse(ghf_ctx* c, const uint8_t* const* h_stream_ptrs, const size_t* h_stream_bytes, const ghf_code* d_codes,
+                             const ghf_index* indexes, unsigned sparse_planes, const size_t* h_n_vals, size_t n_elems, uint32_t elem_bytes,
+                             uint8_t* d_out, size_t cap, uint64_t* d_out_bytes) {
+  return decode_planes_sparse(c, "ghf_decode_planes_sparse", h_stream_ptrs, h_stream_bytes, d_codes, indexes, no_base(), sparse_planes,
+                              h_n_vals, n_elems, elem_bytes, d_out, cap, d_out_bytes);
+}
+int ghf_decode_planes_sparse_delta(ghf_ctx* c, const uint8_t* const* h_stream_ptrs, const size_t* h_stream_bytes, const ghf_code* d_codes,
+                                   const ghf_index* indexes, const uint8_t* d_base, unsigned sparse_planes, const size_t* h_n_vals,
+                                   size_t n_elems, uint32_t elem_bytes, uint8_t* d_out, size_t cap, uint64_t* d_out_bytes) {
+  return decode_planes_sparse(c, "ghf_decode_planes_sparse_delta", h_stream_ptrs, h_stream_bytes, d_codes, indexes, base_of(d_base),
+                              sparse_planes, h_n_vals, n_elems, elem_bytes, d_out, cap, d_out_bytes);
 }
 
 }  // extern "C"

@@ -148,6 +148,13 @@ struct ghf_ctx {
   // (histogram_planes_into, ghf_api.hip), so that a later histogram on this context does not start from stale sums.
   uint64_t* d_planes_hist_acc = nullptr;
   uint64_t* d_planes_hists = nullptr;  // [GHF_PLANES_MAX][257]
+  // ghf_sparse_split / ghf_sparse_merge: the counts of the workgroups' slabs and their exclusive
+  // offsets, written and read by the three launches of one call and by nothing else (describe nothing between calls)
+  uint64_t* d_sparse_counts = nullptr;  // [kSparseGroups]
+  uint64_t* d_sparse_offs = nullptr;    // [kSparseOffWords]
+  // ghf_compress_planes_sparse / ghf_decode_planes_sparse: the mask and the values of ONE sparse plane at a time, the mask at
+  // [0, mask_stride), the values behind it.  Private to the two calls and refilled for every sparse plane, as `planes` is
+  ghf::DevBuf<uint8_t> sparse;
   // ghf_decode_images_batch_stats: where the image decoder counts its rounds and passes (the caller's; null = nowhere)
   uint64_t* images_stats = nullptr;
   std::string err;

@@ -58,6 +58,12 @@ constexpr uint32_t kPlanesHistTileVecs = kPlanesHistThreads * 4;  // a tile: fou
 constexpr uint32_t kPlanesHistFlushTiles = 3;      // u32 counters -> u64 sums every 48 KiB of a workgroup's input (K1: every chunk)
 static_assert((uint64_t)(kPlanesHistFlushTiles + 1) * kPlanesHistTileVecs * 16 < (1ull << 32), "a u32 counter never wraps between two flushes");
 constexpr size_t kPlanesHistAccWords = 32 * GHF_PLANES_MAX * 256;  // 32 replicas of the E x 256 totals, all zero between launches
+// zero-suppressed byte strings (ghf_sparse.hip): one wave = one workgroup takes kSparseTile bytes of the
+// string at a time, 64 lanes x 4 vectors of 16 bytes; one resident round of workgroups with a contiguous slab of tiles each
+constexpr uint32_t kSparseTile = 4096;
+constexpr uint32_t kSparseGroups = 256 * 16;       // as kPlanesGroups; also the most counts the one-workgroup scan takes, in ONE step
+constexpr uint32_t kSparseLdsBytes = 258 * 16;     // the compacted side of a tile at any byte phase: (15 + 4096 + 15) / 16 + 1 vectors
+constexpr size_t kSparseOffWords = kSparseGroups + 2;  // offs[groups] = the total; the last word: n_vals of a split inside a plane call
 
 // the .crs2 header: the count word, symbol[257], min_len, max_len, then a (start_pos, first_code) row per length 1..max_len
 constexpr uint64_t kHeaderFixedBytes = 4 * (GHF_NSYM + 3);  // 1040
@@ -474,6 +480,14 @@ void launch_planes_merge(const uint8_t* d_planes, uint64_t plane_stride, const u
 // and d_base[0 .. count * elem_bytes), the base of the range itself
 void launch_planes_merge_range(const uint8_t* d_planes, uint64_t plane_stride, const uint8_t* d_base, uint64_t first, uint64_t count,
                                uint32_t elem_bytes, uint8_t* d_out, const int* d_status, hipStream_t s);
+// ghf_sparse.hip: n > 0, d_in / d_mask / d_vals / d_out 16-byte aligned.  d_counts: kSparseGroups words, d_offs: kSparseOffWords
+// words, both private to the three launches each call queues (count, scan, move).
+// split: mask[0 .. (n + 7) / 8) and *d_n_vals are always written; n_vals > vals_cap latches GHF_E_CAP and d_vals stays untouched
+void launch_sparse_split(const uint8_t* d_in, uint64_t n, uint8_t* d_mask, uint8_t* d_vals, uint64_t vals_cap, uint64_t* d_n_vals,
+                         uint64_t* d_counts, uint64_t* d_offs, int* d_status, hipStream_t s);
+// merge: nothing is stored when *d_status is non-zero; set bits other than n_vals, or a set pad bit, latch GHF_E_CORRUPT
+void launch_sparse_merge(const uint8_t* d_mask, const uint8_t* d_vals, uint64_t n_vals, uint64_t n, uint8_t* d_out, uint64_t* d_counts,
+                         uint64_t* d_offs, int* d_status, hipStream_t s);
 // ghf_planes_hist.hip: elem_bytes is 2, 4 or 8, n_elems > 0, d_in 16-byte aligned.  d_acc: kPlanesHistAccWords words, zero
 // between launches.  Two launches: the counting kernel, then the finish (replica sums, slot 256, GHF_HIST_COVER_ALL), which
 // is also what zeroes d_acc again.  -> the first launch error; after an error of the finish launch d_acc is the caller's to clear.

@@ -26,6 +26,14 @@ PLANES_HIST_GROUPS = 256 * 4
 PLANES_HIST_TILE_BYTES = 16384
 PLANES_HIST_FLUSH_TILES = 3
 PLANES_BUILD_CODES = 1  # GHF_PLANES_BUILD_CODES (ghf_compress_planes_coded): d_codes is filled from the tensor's own counts
+# ghf_internal.h kSparseTile / kSparseGroups: the bytes of the string one wave of the ghf_sparse.hip kernels takes at a time,
+# and the one-wave workgroups of one resident round (beyond SPARSE_TILE * SPARSE_GROUPS bytes a workgroup takes more than one
+# tile).  The scan takes one count per workgroup and so never more than ONE step of SPARSE_SCAN counts.  Tests stand on these
+# edges (tests/test_sparse_cpu.py holds them against the source); nothing in the library's behaviour depends on them.
+SPARSE_TILE = 4096
+SPARSE_GROUPS = 256 * 16
+SPARSE_SCAN = SPARSE_GROUPS
+SPARSE_AUTO = 0x80000000  # GHF_SPARSE_AUTO (ghf_compress_planes_sparse): planes with at least 3/4 zero bytes are stored sparse
 EMPTY_OK = 2  # opt-in: n == 0 -> header of the one-symbol code + 0x7F (builder's definition, parity unpinned)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -156,6 +164,8 @@ EXPORTS = [
     "ghf_histogram_planes", "ghf_planes_image_bytes", "ghf_compress_planes_coded",
     "ghf_histogram_planes_delta", "ghf_planes_split_delta", "ghf_planes_merge_delta", "ghf_planes_merge_range_delta",
     "ghf_compress_planes_delta", "ghf_decode_planes_delta", "ghf_decode_planes_range_delta",
+    "ghf_sparse_mask_bytes", "ghf_sparse_split", "ghf_sparse_merge", "ghf_compress_planes_sparse",
+    "ghf_compress_planes_sparse_delta", "ghf_decode_planes_sparse", "ghf_decode_planes_sparse_delta",
 ]
 COMM_ID_BYTES = 128
 
@@ -299,6 +309,18 @@ def lib():
                                                 C.POINTER(vp), C.POINTER(sz), vp, u32, C.c_uint64, C.c_uint64, vp, sz]
     L.ghf_decode_planes_range.argtypes = [vp, C.POINTER(vp), C.POINTER(sz), vp, C.POINTER(Index), C.POINTER(SeekInfo),
                                           C.POINTER(vp), C.POINTER(sz), u32, u64, u64, vp, sz]
+    L.ghf_sparse_mask_bytes.argtypes = [sz]
+    L.ghf_sparse_mask_bytes.restype = sz
+    L.ghf_sparse_split.argtypes = [vp, vp, sz, vp, vp, sz, vp]
+    L.ghf_sparse_merge.argtypes = [vp, vp, vp, sz, sz, vp]
+    L.ghf_compress_planes_sparse.argtypes = [vp, vp, sz, u32, C.c_uint, vp, sz, vp, vp, C.POINTER(Index), C.POINTER(C.c_uint),
+                                             C.POINTER(sz)]
+    L.ghf_compress_planes_sparse_delta.argtypes = [vp, vp, vp, sz, u32, C.c_uint, vp, sz, vp, vp, C.POINTER(Index),
+                                                   C.POINTER(C.c_uint), C.POINTER(sz)]
+    L.ghf_decode_planes_sparse.argtypes = [vp, C.POINTER(vp), C.POINTER(sz), vp, C.POINTER(Index), C.c_uint, C.POINTER(sz), sz, u32,
+                                           vp, sz, vp]
+    L.ghf_decode_planes_sparse_delta.argtypes = [vp, C.POINTER(vp), C.POINTER(sz), vp, C.POINTER(Index), vp, C.c_uint, C.POINTER(sz),
+                                                 sz, u32, vp, sz, vp]
     _lib = L
     return L
 
@@ -343,6 +365,11 @@ def batch_seek_bound(max_item_bytes):
 def planes_slot_bytes(n_elems):
     """a slot that suffices for the image of any byte plane of n_elems elements (a multiple of 16)"""
     return int(lib().ghf_planes_slot_bytes(n_elems))
+
+
+def sparse_mask_bytes(n):
+    """(n + 7) // 8: the bytes of the mask of a byte string of n bytes in the sparse form"""
+    return int(lib().ghf_sparse_mask_bytes(n))
 
 
 def batch_index_item(bidx, i, n_i):
@@ -1261,6 +1288,109 @@ class Context:
                                                  d_out.numel() if cap is None else cap),
             "ghf_decode_planes_range_delta")
         return d_out
+
+    # ---- zero-suppressed byte planes: a byte string as a bit mask of its non-zero bytes plus those
+    # bytes; planes that are almost all zeros stored as two ordinary .crs2 images, mask and values -------------------------
+    sparse_mask_bytes = staticmethod(sparse_mask_bytes)
+
+    def sparse_split(self, d_in, n=None, d_mask=None, d_vals=None, vals_cap=None, n_vals=None):
+        """d_in uint8[n] -> (d_mask uint8[(n + 7) // 8], d_vals uint8, n_vals int64[1] device).  No host synchronisation.
+        More than vals_cap (default: d_vals.numel(), or n) non-zero bytes latch GHF_E_CAP: d_vals is then untouched, the mask
+        and n_vals are written."""
+        t = self.torch
+        n = d_in.numel() if n is None else n
+        if d_mask is None:
+            d_mask = self.empty_u8(sparse_mask_bytes(n))
+        if d_vals is None:
+            d_vals = self.empty_u8(n if vals_cap is None else max(vals_cap, 1))
+        if vals_cap is None:
+            vals_cap = d_vals.numel()
+        if n_vals is None:
+            n_vals = t.zeros(1, dtype=t.int64, device=self.device)
+        self._chk(self.L.ghf_sparse_split(self.h, d_in.data_ptr(), n, d_mask.data_ptr(), d_vals.data_ptr(), vals_cap, n_vals.data_ptr()),
+                  "ghf_sparse_split")
+        return d_mask, d_vals, n_vals
+
+    def sparse_merge(self, d_mask, d_vals, n_vals, n, d_out=None):
+        """the inverse of sparse_split (n_vals: a host int; d_vals may be None when it is 0).  -> d_out uint8[n].  A mask whose
+        set bits do not number n_vals, or with a set pad bit, latches GHF_E_CORRUPT and nothing is stored."""
+        if d_out is None:
+            d_out = self.empty_u8(n)
+        self._chk(self.L.ghf_sparse_merge(self.h, d_mask.data_ptr(), None if d_vals is None else d_vals.data_ptr(), n_vals, n,
+                                          d_out.data_ptr()), "ghf_sparse_merge")
+        return d_out
+
+    def _compress_planes_sparse(self, d_in, d_base, delta, elem_bytes, sparse_planes, n_elems, d_out, slot_bytes, d_codes, indexes):
+        t = self.torch
+        n_elems = d_in.numel() * d_in.element_size() // elem_bytes if n_elems is None else n_elems
+        if slot_bytes is None:
+            slot_bytes = planes_slot_bytes(n_elems)
+        if d_out is None:
+            d_out = self.empty_u8(slot_bytes * 2 * elem_bytes)
+        if d_codes is None:
+            d_codes = t.zeros((2 * elem_bytes, C.sizeof(Code)), dtype=t.uint8, device=self.device)
+        out_bytes = t.zeros(2 * elem_bytes, dtype=t.int64, device=self.device)
+        idx = (Index * (2 * elem_bytes))() if indexes else None
+        chosen, n_vals = C.c_uint(0), (C.c_size_t * elem_bytes)()
+        if delta:
+            rc = self.L.ghf_compress_planes_sparse_delta(self.h, d_in.data_ptr(), self._base_ptr(d_base), n_elems, elem_bytes,
+                                                         sparse_planes, d_out.data_ptr(), slot_bytes, out_bytes.data_ptr(),
+                                                         d_codes.data_ptr(), idx, C.byref(chosen), n_vals)
+        else:
+            rc = self.L.ghf_compress_planes_sparse(self.h, d_in.data_ptr(), n_elems, elem_bytes, sparse_planes, d_out.data_ptr(),
+                                                   slot_bytes, out_bytes.data_ptr(), d_codes.data_ptr(), idx, C.byref(chosen), n_vals)
+        self._chk(rc, "ghf_compress_planes_sparse_delta" if delta else "ghf_compress_planes_sparse")
+        return {"out": d_out, "slot_bytes": slot_bytes, "out_bytes": out_bytes, "codes": d_codes, "n_elems": n_elems,
+                "elem_bytes": elem_bytes, "sparse_planes": int(chosen.value), "n_vals": [int(v) for v in n_vals], "indexes": idx}
+
+    def compress_planes_sparse(self, d_in, elem_bytes, sparse_planes=SPARSE_AUTO, n_elems=None, d_out=None, slot_bytes=None,
+                               d_codes=None, indexes=False):
+        """the byte planes of d_in, the planes in sparse_planes (a bit per plane, or SPARSE_AUTO: at least 3/4 zero bytes) stored
+        as mask + values: 2 * elem_bytes slots, slot p = plane p or its mask, slot elem_bytes + p = its values or empty.
+        SYNCHRONISES once (the plane counts).  indexes=True: the call allocates a side-car per stored stream (free them with
+        planes_index_free).  -> the dict of compress_planes over 2 * elem_bytes slots, plus sparse_planes (the planes stored
+        sparse), n_vals (host ints, per plane) and indexes (a ctypes Index array or None)"""
+        return self._compress_planes_sparse(d_in, None, False, elem_bytes, sparse_planes, n_elems, d_out, slot_bytes, d_codes, indexes)
+
+    def compress_planes_sparse_delta(self, d_in, d_base, elem_bytes, sparse_planes=SPARSE_AUTO, n_elems=None, d_out=None,
+                                     slot_bytes=None, d_codes=None, indexes=False):
+        """compress_planes_sparse of d_in ^ d_base (the XOR inside the histogram and split kernels).  -> the same dict"""
+        return self._compress_planes_sparse(d_in, d_base, True, elem_bytes, sparse_planes, n_elems, d_out, slot_bytes, d_codes, indexes)
+
+    def _decode_planes_sparse(self, streams, stream_bytes, d_codes, d_base, delta, sparse_planes, n_vals, n_elems, elem_bytes, indexes,
+                              d_out, cap, nbytes):
+        ptrs = (C.c_void_p * (2 * elem_bytes))(*[None if x is None else x.data_ptr() for x in streams])
+        sizes = (C.c_size_t * (2 * elem_bytes))(*[int(v) for v in stream_bytes])
+        h_n_vals = (C.c_size_t * elem_bytes)(*[int(v) for v in n_vals])
+        if d_out is None:
+            d_out = self.empty_u8(n_elems * elem_bytes)
+        if nbytes is None:
+            nbytes = self.torch.zeros(1, dtype=self.torch.int64, device=self.device)
+        cap = d_out.numel() if cap is None else cap
+        if delta:
+            rc = self.L.ghf_decode_planes_sparse_delta(self.h, ptrs, sizes, d_codes.data_ptr(), indexes, self._base_ptr(d_base),
+                                                       sparse_planes, h_n_vals, n_elems, elem_bytes, d_out.data_ptr(), cap,
+                                                       nbytes.data_ptr())
+        else:
+            rc = self.L.ghf_decode_planes_sparse(self.h, ptrs, sizes, d_codes.data_ptr(), indexes, sparse_planes, h_n_vals, n_elems,
+                                                 elem_bytes, d_out.data_ptr(), cap, nbytes.data_ptr())
+        self._chk(rc, "ghf_decode_planes_sparse_delta" if delta else "ghf_decode_planes_sparse")
+        return d_out, nbytes
+
+    def decode_planes_sparse(self, streams, stream_bytes, d_codes, sparse_planes, n_vals, n_elems, elem_bytes, indexes=None,
+                             d_out=None, cap=None, nbytes=None):
+        """streams: 2 * elem_bytes CUDA uint8 tensors (None for an empty slot), stream_bytes: their sizes as host ints;
+        sparse_planes and n_vals as compress_planes_sparse returned them.  indexes=None synchronises per stream.
+        -> (d_out uint8, nbytes int64[1] device)"""
+        return self._decode_planes_sparse(streams, stream_bytes, d_codes, None, False, sparse_planes, n_vals, n_elems, elem_bytes,
+                                          indexes, d_out, cap, nbytes)
+
+    def decode_planes_sparse_delta(self, streams, stream_bytes, d_codes, d_base, sparse_planes, n_vals, n_elems, elem_bytes,
+                                   indexes=None, d_out=None, cap=None, nbytes=None):
+        """decode_planes_sparse, then ^ d_base in the merge; d_out may be d_base (behind a latched status it then still holds
+        the base).  -> (d_out uint8, nbytes int64[1] device)"""
+        return self._decode_planes_sparse(streams, stream_bytes, d_codes, d_base, True, sparse_planes, n_vals, n_elems, elem_bytes,
+                                          indexes, d_out, cap, nbytes)
 
     # ---- seekable streams: the seek table (the persistent form of the side-car) ----------------
     def seek_pack(self, index, d_stream=None, stream_bytes=0, d_table=None, n=None):

@@ -994,6 +994,103 @@ int ghf_crs_decoded_size(ghf_ctx* ctx, const uint8_t* d_stream, size_t stream_by
 int ghf_crs_sync_piece(ghf_ctx* ctx, const uint8_t* d_piece, size_t piece_bytes, uint32_t first_bit, uint64_t end_bit,
                        const ghf_tree* d_tree, uint64_t* landing, uint64_t* n_symbols);
 
+/* ---- zero-suppressed byte planes: sparse split / merge, compress, decode --------
+ * No symbol of a Huffman code costs less than one bit, so a byte plane of nothing but zeros -- the high planes of
+ * `new ^ base` in a series of tensors, a frozen layer -- still stores n / 8 bytes.  THE SPARSE FORM of a byte string
+ * x[0 .. n) is two byte strings and nothing else (no container, no magic, no header):
+ *   mask: ghf_sparse_mask_bytes(n) = (n + 7) / 8 bytes; bit k & 7 of mask[k >> 3] is 1 exactly when x[k] != 0 (LSB first:
+ *         numpy's packbits(x != 0, bitorder="little")); the bits behind n in the last mask byte are 0;
+ *   vals: the n_vals non-zero bytes of x, in order.
+ * Each is compressed as ghf_compress compresses any byte string: EVERY STORED STREAM IS AN ORDINARY STANDALONE .crs2
+ * IMAGE.  The mask of such a plane is almost all 0x00 and costs one bit per MASK byte, 1/64 byte per element.
+ *
+ * Every device pointer is 16-byte aligned (d_n_vals: 8-byte).  Call-level refusals come before anything touches HIP, with
+ * nothing queued, in the order of the byte-plane calls: a null context or required pointer, another elem_bytes, a
+ * misaligned pointer or slot_bytes, a size beyond size_t, a sparse_planes with a bit at or above elem_bytes,
+ * GHF_SPARSE_AUTO together with an explicit bit, GHF_SPARSE_AUTO in a decode (which is told what was chosen), an index
+ * that does not carry its stream's symbol count: GHF_E_INVAL; then n == 0: GHF_E_EMPTY; then slot_bytes or cap too small:
+ * GHF_E_CAP.  In the decodes d_base == d_out is allowed, as in ghf_decode_planes_delta; any other overlap is undefined. */
+#define GHF_SPARSE_AUTO 0x80000000u
+
+/* No reference counterpart (a size the flat buffers of include/compressor.h:62-73 do not need).  Host only:
+ * (n + 7) / 8, the bytes of the mask of a string of n bytes. */
+size_t ghf_sparse_mask_bytes(size_t n);
+
+/* No reference counterpart (generalises the flat input of include/compressor.h:62-73).  Asynchronous on the stream, never
+ * synchronises, does not look at the context's status word.  d_in[0 .. n) -> d_mask[0 .. ghf_sparse_mask_bytes(n)),
+ * d_vals[0 .. n_vals), *d_n_vals (device u64) <- n_vals; nothing else is written.  Three launches (count, scan, move): no
+ * kernel waits for another workgroup.  n_vals is known on the device behind the scan: n_vals > vals_cap latches GHF_E_CAP,
+ * d_vals then stays untouched while d_mask and *d_n_vals -- the capacity that would have sufficed -- are written.  d_vals
+ * may be null when vals_cap is 0. */
+int ghf_sparse_split(ghf_ctx* ctx, const uint8_t* d_in, size_t n, uint8_t* d_mask, uint8_t* d_vals, size_t vals_cap,
+                     uint64_t* d_n_vals);
+
+/* No reference counterpart (generalises the flat output of include/compressor.h:87-92).  The inverse of ghf_sparse_split:
+ * only d_out[0 .. n) is written.  Asynchronous, never synchronises.  A launch that finds the context's status word
+ * non-zero stores nothing.  Set bits among the first n that do not number n_vals, or a set pad bit, latch GHF_E_CORRUPT
+ * and nothing is stored.  The value bytes are not inspected: a zero among them is copied.  n_vals == 0 is allowed and
+ * d_vals may then be null. */
+int ghf_sparse_merge(ghf_ctx* ctx, const uint8_t* d_mask, const uint8_t* d_vals, size_t n_vals, size_t n, uint8_t* d_out);
+
+/* No reference counterpart: Compressor::compress(), include/compressor.h:62-73, once per stored stream of the byte planes
+ * of d_in.  d_out has 2 * elem_bytes slots of slot_bytes >= ghf_planes_slot_bytes(n_elems).  Slot p holds plane p's image
+ * if the plane is dense, the image of its MASK if it is sparse; slot elem_bytes + p holds the image of its VALUES, or
+ * nothing (d_out_bytes[elem_bytes + p] = 0, the slot unwritten) when the plane is dense or has no non-zero byte.  Every
+ * image is byte for byte what ghf_compress writes for that byte string, d_out_bytes[j] (device u64[2 * elem_bytes]) its
+ * size and d_codes[j] (device [2 * elem_bytes], optional) its code.
+ * sparse_planes: bit p set = plane p is stored sparse; or GHF_SPARSE_AUTO: plane p is sparse when at least n_elems -
+ * n_elems / 4 of its bytes are zero.  That is a rule, not a minimum: the second stream has a header of its own, and for
+ * a few thousand elements it can outweigh the gain.  *h_sparse_planes (HOST) <- the planes stored sparse, h_n_vals[p]
+ * (HOST [elem_bytes]) <- the non-zero bytes of plane p, of every plane: both are what the decode must be told.
+ * The call SYNCHRONISES with the host ONCE: it queues ghf_histogram_planes into counters of the context and waits for
+ * the elem_bytes x 257 counts, which give h_n_vals and the choice.  Everything behind that is queued without a further
+ * wait: ghf_planes_split into the workspace; for a dense plane what ghf_compress_planes_coded(GHF_PLANES_BUILD_CODES)
+ * queues; for a sparse plane ghf_sparse_split into a second workspace of the context that grows on demand, then what
+ * ghf_compress queues for the mask and for the values.
+ * h_indexes (HOST [2 * elem_bytes], optional OUT): the call itself runs ghf_index_alloc for every stream it stores, with
+ * that stream's symbol count (n_elems, ghf_sparse_mask_bytes(n_elems) or h_n_vals[p]), and the side-car is filled;
+ * entries of empty slots are zeroed.  The caller frees them with ghf_index_free.
+ * Device failures latch as for ghf_compress_planes_coded (d_out_bytes UNSPECIFIED behind a latched status); the context's
+ * plan and histogram caches are forgotten as there. */
+int ghf_compress_planes_sparse(ghf_ctx* ctx, const uint8_t* d_in, size_t n_elems, uint32_t elem_bytes, unsigned sparse_planes,
+                               uint8_t* d_out, size_t slot_bytes, uint64_t* d_out_bytes /* [2 * elem_bytes] */,
+                               ghf_code* d_codes /* [2 * elem_bytes], optional OUT */,
+                               ghf_index* h_indexes /* [2 * elem_bytes], optional OUT */, unsigned* h_sparse_planes /* OUT */,
+                               size_t* h_n_vals /* [elem_bytes] OUT */);
+
+/* No reference counterpart: Compressor::compress(), include/compressor.h:62-73, once per stored stream of the byte planes
+ * of d_in ^ d_base.  ghf_compress_planes_sparse with ghf_histogram_planes_delta and
+ * ghf_planes_split_delta in front; SYNCHRONISES ONCE as it does.  A null or misaligned d_base: GHF_E_INVAL. */
+int ghf_compress_planes_sparse_delta(ghf_ctx* ctx, const uint8_t* d_in, const uint8_t* d_base, size_t n_elems, uint32_t elem_bytes,
+                                     unsigned sparse_planes, uint8_t* d_out, size_t slot_bytes,
+                                     uint64_t* d_out_bytes /* [2 * elem_bytes] */, ghf_code* d_codes /* [2 * elem_bytes], optional OUT */,
+                                     ghf_index* h_indexes /* [2 * elem_bytes], optional OUT */, unsigned* h_sparse_planes /* OUT */,
+                                     size_t* h_n_vals /* [elem_bytes] OUT */);
+
+/* No reference counterpart: Decompressor::decompress(), include/compressor.h:87-92, once per stored stream.  sparse_planes
+ * and h_n_vals (HOST [elem_bytes]; read for the sparse planes) are what the compress call reported.  A dense plane
+ * decodes exactly as in ghf_decode_planes.  A sparse plane decodes its mask (ghf_sparse_mask_bytes(n_elems) symbols) and,
+ * if h_n_vals[p] > 0, its values into the second workspace; ghf_sparse_merge then writes the plane into the plane
+ * workspace.  The merge into d_out comes last and stores nothing behind a latched status.  Codes and pointers of empty
+ * slots are ignored.
+ * indexes != NULL (HOST [2 * elem_bytes]): the call never synchronises; the index of every stored stream must carry that
+ * stream's symbol count, GHF_E_INVAL otherwise, nothing queued.  indexes == NULL SYNCHRONISES per stream as
+ * ghf_decode_planes does; a stream that decodes to another size: GHF_E_CORRUPT is returned before any merge. */
+int ghf_decode_planes_sparse(ghf_ctx* ctx, const uint8_t* const* h_stream_ptrs /* [2 * elem_bytes] */,
+                             const size_t* h_stream_bytes /* [2 * elem_bytes] */, const ghf_code* d_codes /* [2 * elem_bytes] */,
+                             const ghf_index* indexes /* [2 * elem_bytes] or NULL */, unsigned sparse_planes,
+                             const size_t* h_n_vals /* [elem_bytes] */, size_t n_elems, uint32_t elem_bytes, uint8_t* d_out, size_t cap,
+                             uint64_t* d_out_bytes);
+
+/* No reference counterpart: Decompressor::decompress(), include/compressor.h:87-92, once per stored stream.
+ * ghf_decode_planes_sparse with ghf_planes_merge_delta last: d_out <- the planes, XOR d_base.  d_base == d_out is allowed;
+ * behind a latched status d_out then still holds the base.  indexes == NULL SYNCHRONISES as there. */
+int ghf_decode_planes_sparse_delta(ghf_ctx* ctx, const uint8_t* const* h_stream_ptrs /* [2 * elem_bytes] */,
+                                   const size_t* h_stream_bytes /* [2 * elem_bytes] */, const ghf_code* d_codes /* [2 * elem_bytes] */,
+                                   const ghf_index* indexes /* [2 * elem_bytes] or NULL */, const uint8_t* d_base, unsigned sparse_planes,
+                                   const size_t* h_n_vals /* [elem_bytes] */, size_t n_elems, uint32_t elem_bytes, uint8_t* d_out,
+                                   size_t cap, uint64_t* d_out_bytes);
+
 #ifdef __cplusplus
 }
 #endif
