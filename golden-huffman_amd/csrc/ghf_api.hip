@@ -2051,19 +2051,32 @@ static void free_indexes(ghf_ctx* c, ghf_index* ix, uint32_t count) {
   std::memset(ix, 0, count * sizeof *ix);
 }
 
+// where the ranked compress calls want the rank tables of their sparse planes; the plain calls want none
+struct RankOut {
+  bool wanted;
+  uint8_t* p;
+  size_t slot_bytes;
+  bool null() const { return wanted && !p; }
+  bool misaligned() const { return wanted && (!aligned16(p) || (slot_bytes & 15u)); }
+};
+static inline RankOut no_ranks() { return {false, nullptr, 0}; }
+
 static int compress_planes_sparse(ghf_ctx* c, const char* who, const uint8_t* d_in, Base base, size_t n_elems, uint32_t elem_bytes,
                                   unsigned sparse_planes, uint8_t* d_out, size_t slot_bytes, uint64_t* d_out_bytes, ghf_code* d_codes,
-                                  ghf_index* h_indexes, unsigned* h_sparse_planes, size_t* h_n_vals) {
-  if (!c || !d_in || !d_out || !d_out_bytes || !h_sparse_planes || !h_n_vals || base.null()) return GHF_E_INVAL;
+                                  ghf_index* h_indexes, unsigned* h_sparse_planes, size_t* h_n_vals, RankOut ranks) {
+  if (!c || !d_in || !d_out || !d_out_bytes || !h_sparse_planes || !h_n_vals || base.null() || ranks.null()) return GHF_E_INVAL;
   const std::string f = std::string(who) + ": ";
   if (!elem_bytes_ok(elem_bytes)) return fail(c, GHF_E_INVAL, (f + "elem_bytes must be 2, 4 or 8").c_str());
   if (!aligned16(d_in) || !aligned16(d_out) || (slot_bytes & 15u) || !aligned16(d_codes) || base.misaligned())
     return fail(c, GHF_E_INVAL, (f + "d_in, d_base, d_out, d_codes and slot_bytes must be multiples of 16").c_str());
+  if (ranks.misaligned()) return fail(c, GHF_E_INVAL, (f + "d_ranks and rank_slot_bytes must be multiples of 16").c_str());
   if (!sparse_planes_ok(sparse_planes, elem_bytes, true))
     return fail(c, GHF_E_INVAL, (f + "sparse_planes is GHF_SPARSE_AUTO alone or has bits below elem_bytes only").c_str());
   if (workspace_overflow(n_elems, elem_bytes)) return fail(c, GHF_E_INVAL, (f + "n_elems * elem_bytes overflows").c_str());
   if (n_elems == 0) return fail(c, GHF_E_EMPTY, (f + "no elements").c_str());
   if (slot_bytes < ghf_planes_slot_bytes(n_elems)) return fail(c, GHF_E_CAP, (f + "slot_bytes below ghf_planes_slot_bytes(n_elems)").c_str());
+  if (ranks.wanted && ranks.slot_bytes < ghf_sparse_rank_bytes(n_elems))
+    return fail(c, GHF_E_CAP, (f + "rank_slot_bytes below ghf_sparse_rank_bytes(n_elems)").c_str());
   GHF_HIP(c, hipSetDevice(c->device));
   const uint32_t E = elem_bytes;
   size_t stride = 0, mask_stride = 0;
@@ -2119,6 +2132,9 @@ static int compress_planes_sparse(ghf_ctx* c, const char* who, const uint8_t* d_
     }
     launch_sparse_split(plane, n_elems, d_mask, d_vals, n_elems, c->d_sparse_offs + kSparseOffWords - 1, c->d_sparse_counts, c->d_sparse_offs,
                         c->d_status, c->stream);
+    // the plane's rank table, while its mask stands in the workspace; the split is done with the counts and offsets
+    if (ranks.wanted)
+      launch_sparse_rank_pack(d_mask, n_elems, ranks.p + p * ranks.slot_bytes, c->d_sparse_counts, c->d_sparse_offs, c->d_status, c->stream);
     GHF_HIP(c, hipGetLastError());
     // compressor.h:62-73 for the mask and for the values, each a byte string of its own
     if ((rc = ghf_compress(c, d_mask, mask_bytes, d_out + p * slot_bytes, slot_bytes, d_out_bytes + p, codes + p,
@@ -2137,13 +2153,13 @@ int ghf_compress_planes_sparse(ghf_ctx* c, const uint8_t* d_in, size_t n_elems, 
                                size_t slot_bytes, uint64_t* d_out_bytes, ghf_code* d_codes, ghf_index* h_indexes, unsigned* h_sparse_planes,
                                size_t* h_n_vals) {
   return compress_planes_sparse(c, "ghf_compress_planes_sparse", d_in, no_base(), n_elems, elem_bytes, sparse_planes, d_out, slot_bytes,
-                                d_out_bytes, d_codes, h_indexes, h_sparse_planes, h_n_vals);
+                                d_out_bytes, d_codes, h_indexes, h_sparse_planes, h_n_vals, no_ranks());
 }
 int ghf_compress_planes_sparse_delta(ghf_ctx* c, const uint8_t* d_in, const uint8_t* d_base, size_t n_elems, uint32_t elem_bytes,
                                      unsigned sparse_planes, uint8_t* d_out, size_t slot_bytes, uint64_t* d_out_bytes, ghf_code* d_codes,
                                      ghf_index* h_indexes, unsigned* h_sparse_planes, size_t* h_n_vals) {
   return compress_planes_sparse(c, "ghf_compress_planes_sparse_delta", d_in, base_of(d_base), n_elems, elem_bytes, sparse_planes, d_out,
-                                slot_bytes, d_out_bytes, d_codes, h_indexes, h_sparse_planes, h_n_vals);
+                                slot_bytes, d_out_bytes, d_codes, h_indexes, h_sparse_planes, h_n_vals, no_ranks());
 }
 
 // ghf_decode of one stored stream of `symbols` bytes into the workspace at d_to[0 .. cap)
@@ -2227,6 +2243,279 @@ int ghf_decode_planes_sparse_delta(ghf_ctx* c, const uint8_t* const* h_stream_pt
                                    size_t n_elems, uint32_t elem_bytes, uint8_t* d_out, size_t cap, uint64_t* d_out_bytes) {
   return decode_planes_sparse(c, "ghf_decode_planes_sparse_delta", h_stream_ptrs, h_stream_bytes, d_codes, indexes, base_of(d_base),
                               sparse_planes, h_n_vals, n_elems, elem_bytes, d_out, cap, d_out_bytes);
+}
+
+// ---------------------------------------------------------------------------------------------- element range of sparse planes
+// (no reference counterpart)
+static inline uint64_t rank_blocks_for(uint64_t n) { return n / kSparseRankElems + (n % kSparseRankElems != 0); }
+
+size_t ghf_sparse_rank_bytes(size_t n) { return kSparseRankHeaderBytes + 8 * ((size_t)rank_blocks_for(n) + 1); }
+
+int ghf_sparse_rank_pack(ghf_ctx* c, const uint8_t* d_mask, size_t n, uint8_t* d_table, size_t cap) {
+  if (!c || !d_mask || !d_table) return GHF_E_INVAL;
+  if (!aligned16(d_mask) || !aligned16(d_table)) return fail(c, GHF_E_INVAL, "ghf_sparse_rank_pack: d_mask and d_table must be 16-byte aligned");
+  if (n > (size_t)-1 - kSparseRankElems) return fail(c, GHF_E_INVAL, "ghf_sparse_rank_pack: n overflows");
+  if (n == 0) return fail(c, GHF_E_EMPTY, "ghf_sparse_rank_pack: no bytes");
+  if (cap < ghf_sparse_rank_bytes(n)) return fail(c, GHF_E_CAP, "ghf_sparse_rank_pack: table capacity below ghf_sparse_rank_bytes(n)");
+  GHF_HIP(c, hipSetDevice(c->device));
+  launch_sparse_rank_pack(d_mask, n, d_table, c->d_sparse_counts, c->d_sparse_offs, c->d_status, c->stream);
+  GHF_HIP(c, hipGetLastError());
+  return GHF_OK;
+}
+
+// The table is not trusted: everything one entry can be held against without the mask is checked here.  Whether the entries
+// are the mask's own ranks is not: a range call holds the DIFFERENCE of the two entries it reads against the mask's set bits
+// (the sparse merge's count) and nothing more, so two entries wrong by the same amount pass.
+int ghf_sparse_rank_parse(const uint8_t* h, size_t bytes, ghf_sparse_rank_info* info) {
+  if (!h || !info) return GHF_E_INVAL;
+  std::memset(info, 0, sizeof *info);
+  if (bytes < kSparseRankHeaderBytes + 8) return GHF_E_FORMAT;
+  if (le64(h) != kSparseRankMagic || le32(h + 8) != kSparseRankVersion || le32(h + 12) != kSparseRankElems) return GHF_E_FORMAT;
+  const uint64_t n = le64(h + 16), n_vals = le64(h + 24), nb = le64(h + 32);
+  if (nb != rank_blocks_for(n) || n_vals > n) return GHF_E_FORMAT;
+  for (size_t i = 40; i < kSparseRankHeaderBytes; ++i)
+    if (h[i]) return GHF_E_FORMAT;
+  if ((bytes - kSparseRankHeaderBytes) / 8 != nb + 1 || (bytes & 7u)) return GHF_E_FORMAT;  // truncated, or something behind it
+  const uint8_t* cum = h + kSparseRankHeaderBytes;
+  uint64_t prev = le64(cum);
+  if (prev != 0) return GHF_E_FORMAT;
+  for (uint64_t j = 1; j <= nb; ++j) {
+    const uint64_t v = le64(cum + 8 * j), elems = j < nb ? kSparseRankElems : n - (nb - 1) * kSparseRankElems;
+    if (v < prev || v - prev > elems) return GHF_E_FORMAT;  // a rank block has no more non-zero bytes than bytes
+    prev = v;
+  }
+  if (prev != n_vals) return GHF_E_FORMAT;
+  info->n = n;
+  info->n_vals = n_vals;
+  info->n_blocks = nb;
+  info->version = kSparseRankVersion;
+  return GHF_OK;
+}
+
+int ghf_sparse_merge_at(ghf_ctx* c, const uint8_t* d_mask, const uint8_t* d_vals, size_t vals_skip, size_t n_vals, size_t n, uint8_t* d_out) {
+  if (!c || !d_mask || !d_out || (n_vals && !d_vals)) return GHF_E_INVAL;
+  if (!aligned16(d_mask) || !aligned16(d_vals) || !aligned16(d_out))
+    return fail(c, GHF_E_INVAL, "ghf_sparse_merge_at: d_mask, d_vals and d_out must be 16-byte aligned");
+  if (n > (size_t)-1 - kSparseTile || vals_skip + n_vals < vals_skip) return fail(c, GHF_E_INVAL, "ghf_sparse_merge_at: n or vals_skip + n_vals overflows");
+  if (n == 0) return fail(c, GHF_E_EMPTY, "ghf_sparse_merge_at: no bytes");
+  GHF_HIP(c, hipSetDevice(c->device));
+  launch_sparse_merge_at(d_mask, d_vals, vals_skip, n_vals, n, d_out, c->d_sparse_counts, c->d_sparse_offs, c->d_status, c->stream);
+  GHF_HIP(c, hipGetLastError());
+  return GHF_OK;
+}
+
+int ghf_compress_planes_sparse_ranked(ghf_ctx* c, const uint8_t* d_in, size_t n_elems, uint32_t elem_bytes, unsigned sparse_planes,
+                                      uint8_t* d_out, size_t slot_bytes, uint64_t* d_out_bytes, ghf_code* d_codes, ghf_index* h_indexes,
+                                      unsigned* h_sparse_planes, size_t* h_n_vals, uint8_t* d_ranks, size_t rank_slot_bytes) {
+  return compress_planes_sparse(c, "ghf_compress_planes_sparse_ranked", d_in, no_base(), n_elems, elem_bytes, sparse_planes, d_out, slot_bytes,
+                                d_out_bytes, d_codes, h_indexes, h_sparse_planes, h_n_vals, {true, d_ranks, rank_slot_bytes});
+}
+int ghf_compress_planes_sparse_ranked_delta(ghf_ctx* c, const uint8_t* d_in, const uint8_t* d_base, size_t n_elems, uint32_t elem_bytes,
+                                            unsigned sparse_planes, uint8_t* d_out, size_t slot_bytes, uint64_t* d_out_bytes,
+                                            ghf_code* d_codes, ghf_index* h_indexes, unsigned* h_sparse_planes, size_t* h_n_vals,
+                                            uint8_t* d_ranks, size_t rank_slot_bytes) {
+  return compress_planes_sparse(c, "ghf_compress_planes_sparse_ranked_delta", d_in, base_of(d_base), n_elems, elem_bytes, sparse_planes, d_out,
+                                slot_bytes, d_out_bytes, d_codes, h_indexes, h_sparse_planes, h_n_vals, {true, d_ranks, rank_slot_bytes});
+}
+
+// one stored stream of a range call: which symbols of it the call decodes, and where to
+struct RangePart {
+  uint32_t slot;      // in the caller's arrays of 2 * elem_bytes
+  uint64_t lo, hi;    // symbols [lo, hi) of the stream; lo is a multiple of kBlockSymbols
+  uint64_t symbols;   // of the whole stream
+  uint8_t* to;        // symbol lo lands here (16-byte aligned)
+  size_t cap;
+};
+
+static int decode_planes_sparse_range(ghf_ctx* c, const char* who, const uint8_t* const* h_stream_ptrs, const size_t* h_stream_bytes,
+                                      const ghf_code* d_codes, const ghf_index* indexes, const ghf_seek_info* h_infos,
+                                      const uint8_t* const* h_table_ptrs, const size_t* h_table_bytes,
+                                      const ghf_sparse_rank_info* h_rank_infos, const uint8_t* const* h_rank_ptrs, Base base,
+                                      unsigned sparse_planes, size_t n_elems, uint32_t elem_bytes, uint64_t first, uint64_t count,
+                                      uint8_t* d_out, size_t cap) {
+  if (!c || !h_stream_ptrs || !h_stream_bytes || !d_codes || !d_out || base.null()) return GHF_E_INVAL;
+  const std::string f = std::string(who) + ": ";
+  if (!elem_bytes_ok(elem_bytes)) return fail(c, GHF_E_INVAL, (f + "elem_bytes must be 2, 4 or 8").c_str());
+  const uint32_t E = elem_bytes;
+  const bool by_table = h_infos || h_table_ptrs || h_table_bytes;
+  if ((indexes != nullptr) == by_table || (by_table && !(h_infos && h_table_ptrs && h_table_bytes)))
+    return fail(c, GHF_E_INVAL, (f + "exactly one of indexes / (h_infos, h_table_ptrs, h_table_bytes) must be given").c_str());
+  // what ghf_decode_planes_range asks of a plane, of one stored stream
+  auto pointers_ok = [&](uint32_t j) {
+    return h_stream_ptrs[j] && aligned16(h_stream_ptrs[j]) && (!by_table || (h_table_ptrs[j] && aligned16(h_table_ptrs[j])));
+  };
+  auto symbols_of = [&](uint32_t j) -> uint64_t { return by_table ? h_infos[j].n_symbols : indexes[j].n_symbols; };
+  auto index_ok = [&](uint32_t j) { return by_table || indexes[j].n_symbols == 0 || index_is_whole(&indexes[j]); };
+  for (uint32_t p = 0; p < E; ++p)
+    if (!pointers_ok(p)) return fail(c, GHF_E_INVAL, (f + "a stream or table pointer is null or not 16-byte aligned").c_str());
+  if (!aligned16(d_out) || base.misaligned()) return fail(c, GHF_E_INVAL, (f + "d_out and d_base must be 16-byte aligned").c_str());
+  for (uint32_t p = 0; p < E; ++p)
+    if (!index_ok(p)) return fail(c, GHF_E_INVAL, (f + "malformed index").c_str());
+  if (first > n_elems || count > n_elems - first) return fail(c, GHF_E_INVAL, (f + "first + count exceeds n_elems").c_str());
+  // the workspace holds the range from the start of its first rank block to the end of its last, and a vector more
+  const size_t slack = 2 * (size_t)kSparseRankElems + 16;
+  if (count > (size_t)-1 - slack || workspace_overflow((size_t)count + slack, E))
+    return fail(c, GHF_E_INVAL, (f + "count * elem_bytes overflows").c_str());
+  for (uint32_t p = 0; by_table && p < E; ++p) {
+    const int rc = seek_table_ok(c, who, h_infos + p, h_table_ptrs[p], h_table_bytes[p]);
+    if (rc) return rc;
+  }
+  if (cap < count * E) return fail(c, GHF_E_CAP, (f + "output capacity below count * elem_bytes").c_str());
+  // ... and what the sparse form adds
+  if (!sparse_planes_ok(sparse_planes, E, false))
+    return fail(c, GHF_E_INVAL, (f + "sparse_planes has bits below elem_bytes only (the mask the compress call reported)").c_str());
+  if (sparse_planes && (!h_rank_infos || !h_rank_ptrs)) return fail(c, GHF_E_INVAL, (f + "sparse planes need their rank tables").c_str());
+  const uint64_t mask_bytes = ghf_sparse_mask_bytes(n_elems);
+  for (uint32_t p = 0; p < E; ++p) {
+    if (!((sparse_planes >> p) & 1u)) continue;
+    if (!h_rank_ptrs[p]) return fail(c, GHF_E_INVAL, (f + "a sparse plane has no rank table").c_str());
+    if (h_rank_infos[p].n != n_elems) return fail(c, GHF_E_INVAL, (f + "a rank table is not one of n_elems elements").c_str());
+    if (h_rank_infos[p].version != kSparseRankVersion || h_rank_infos[p].n_blocks != rank_blocks_for(n_elems) || h_rank_infos[p].n_vals > n_elems)
+      return fail(c, GHF_E_FORMAT, (f + "a rank info is not what ghf_sparse_rank_parse fills in").c_str());
+  }
+  for (uint32_t p = 0; p < E; ++p) {
+    const bool sparse = (sparse_planes >> p) & 1u;
+    if (symbols_of(p) != (sparse ? mask_bytes : (uint64_t)n_elems))
+      return fail(c, GHF_E_INVAL, sparse ? (f + "a mask stream does not have ghf_sparse_mask_bytes(n_elems) symbols").c_str()
+                                         : (f + "a dense stream does not have n_elems symbols").c_str());
+    if (!sparse || h_rank_infos[p].n_vals == 0) continue;  // the values slot of any other plane is ignored
+    if (!pointers_ok(E + p)) return fail(c, GHF_E_INVAL, (f + "a stream or table pointer is null or not 16-byte aligned").c_str());
+    if (!index_ok(E + p)) return fail(c, GHF_E_INVAL, (f + "malformed index").c_str());
+    if (symbols_of(E + p) != h_rank_infos[p].n_vals)
+      return fail(c, GHF_E_INVAL, (f + "a values stream does not have the symbols its rank table counts").c_str());
+    if (by_table) {
+      const int rc = seek_table_ok(c, who, h_infos + E + p, h_table_ptrs[E + p], h_table_bytes[E + p]);
+      if (rc) return rc;
+    }
+  }
+  if (count == 0) return GHF_OK;
+  if (!sparse_planes)  // nothing sparse: the origin of section 17, and its call
+    return decode_planes_range(c, who, h_stream_ptrs, h_stream_bytes, d_codes, indexes, h_infos, h_table_ptrs, h_table_bytes, base, E, first,
+                               count, d_out, cap);
+  // THE PLAN.  The common origin of all planes is the start of the rank block that holds `first`: a multiple of 4096 for a
+  // dense plane, of 4096 mask bytes for a mask, and the values in front of it number cum[b0].  A sparse plane is rebuilt for the
+  // whole rank blocks [b0, b1) (cut at n_elems): the sub-string's mask bytes are whole, so its last mask byte obeys the pad rule.
+  const uint64_t from = first - first % kSparseRankElems, end = first + count;
+  const uint64_t b0 = from / kSparseRankElems, b1 = rank_blocks_for(end);
+  const uint64_t sub_n = std::min<uint64_t>(b1 * kSparseRankElems, n_elems) - from;
+  const uint64_t m_lo = b0 * (kSparseRankElems / 8), m_hi = std::min<uint64_t>(b1 * (kSparseRankElems / 8), mask_bytes);
+  uint64_t v_lo[GHF_PLANES_MAX] = {}, v_hi[GHF_PLANES_MAX] = {};
+  for (uint32_t p = 0; p < E; ++p) {
+    if (!((sparse_planes >> p) & 1u)) continue;
+    const uint8_t* cum = h_rank_ptrs[p] + kSparseRankHeaderBytes;
+    v_lo[p] = le64(cum + 8 * b0);
+    v_hi[p] = le64(cum + 8 * b1);
+    if (v_lo[p] > v_hi[p] || v_hi[p] > h_rank_infos[p].n_vals || v_hi[p] - v_lo[p] > sub_n)
+      return fail(c, GHF_E_FORMAT, (f + "the rank table's entries for the range are not ordered ranks").c_str());
+  }
+  GHF_HIP(c, hipSetDevice(c->device));
+  size_t stride = 0;
+  int rc = planes_workspace(c, (size_t)sub_n + 16, E, &stride);
+  // the second workspace: the sub-string's mask, and behind it its values from the start of their first seek block
+  const size_t mask_stride = ((size_t)(m_hi - m_lo) + 255) & ~(size_t)255;
+  const size_t vals_room = ((size_t)sub_n + kBlockSymbols + 255) & ~(size_t)255;
+  if (!rc) rc = grow(c, c->sparse, mask_stride + vals_room);
+  if (rc) return rc;
+  uint8_t *d_mask = c->sparse.p, *d_vals = c->sparse.p + mask_stride;
+  RangePart parts[2 * GHF_PLANES_MAX];
+  uint32_t n_parts = 0;
+  for (uint32_t p = 0; p < E; ++p) {
+    if (!((sparse_planes >> p) & 1u)) {
+      parts[n_parts++] = {p, from, end, n_elems, c->planes.p + p * stride, stride};
+      continue;
+    }
+    parts[n_parts++] = {p, m_lo, m_hi, mask_bytes, d_mask, mask_stride};
+    if (v_hi[p] > v_lo[p]) parts[n_parts++] = {E + p, v_lo[p] - v_lo[p] % kBlockSymbols, v_hi[p], h_rank_infos[p].n_vals, d_vals, vals_room};
+  }
+  // behind the last stored stream of a sparse plane (its values, or its mask when the sub-string has none): the plane's merge
+  auto merge_behind = [&](uint32_t j) {
+    const uint32_t p = j % E;
+    if (((sparse_planes >> p) & 1u) && (j >= E || v_hi[p] == v_lo[p]))
+      launch_sparse_merge_at(d_mask, d_vals, v_lo[p] % kBlockSymbols, v_hi[p] - v_lo[p], sub_n, c->planes.p + p * stride, c->d_sparse_counts,
+                             c->d_sparse_offs, c->d_status, c->stream);
+  };
+  if (by_table) {
+    // One launch expands the covered blocks of every stored stream (k_seek_expand_streams): expanding each by itself would
+    // pay k_seek_expand's latency floor up to 2 E times (DESIGN.md section 17 has the measurement).  Every stream gets tables of
+    // its own, alive until its K7 has run.
+    const size_t segs_per_block = kBlockSymbols / kSegSymbols;
+    size_t blocks = 0;
+    for (uint32_t i = 0; i < n_parts; ++i) blocks += (size_t)(blocks_for(parts[i].hi) - parts[i].lo / kBlockSymbols);
+    if (!(rc = grow(c, c->range_dt, 2 * GHF_PLANES_MAX))) rc = grow(c, c->range_chunk, blocks, 1024);
+    if (!rc) rc = grow(c, c->range_seg, blocks * segs_per_block, 1024 * 64);
+    if (rc) return rc;
+    SeekExpandStreamsParams a = {};
+    size_t at = 0;
+    uint32_t stored = 0;
+    for (uint32_t i = 0; i < n_parts; ++i) stored |= 1u << parts[i].slot;
+    launch_build_decode_tables_slots(d_codes, c->range_dt.p, 2 * E, stored, c->d_status, c->stream);  // range_dt[j]: the tables of slot j
+    for (uint32_t i = 0; i < n_parts; ++i) {
+      const uint32_t j = parts[i].slot;
+      SeekExpandParams& x = a.stream[i];
+      x.records = h_table_ptrs[j] + kSeekHeaderBytes;
+      x.stream = h_stream_ptrs[j];
+      x.stream_bytes = h_stream_bytes[j];
+      x.dt = c->range_dt.p + j;
+      x.n_symbols = parts[i].symbols;
+      x.n_blocks = h_infos[j].n_blocks;
+      x.g0 = parts[i].lo / kBlockSymbols;
+      x.g1 = blocks_for(parts[i].hi);
+      x.chunk_bit = c->range_chunk.p + at;
+      x.seg_bit = c->range_seg.p + at * segs_per_block;
+      x.status = c->d_status;
+      at += (size_t)(x.g1 - x.g0);
+    }
+    launch_seek_expand_streams(a, n_parts, c->stream);
+    GHF_HIP(c, hipGetLastError());
+    for (uint32_t i = 0; i < n_parts; ++i) {  // K7 on the expanded view, set up as ghf_decode_planes_range sets it up
+      const uint32_t j = parts[i].slot;
+      DecParams d = {};
+      d.stream = h_stream_ptrs[j];
+      d.stream_bytes = h_stream_bytes[j];
+      d.dt = c->range_dt.p + j;
+      d.chunk_bit = a.stream[i].chunk_bit;
+      d.seg_bit = a.stream[i].seg_bit;
+      d.n_symbols = parts[i].hi - parts[i].lo;
+      d.n_segs = segs_for(d.n_symbols);
+      d.no_end_mark = (parts[i].hi == parts[i].symbols && !(h_infos[j].flags & GHF_INDEX_NO_END_MARK)) ? 0u : 1u;
+      d.out = parts[i].to;
+      d.out_bytes = nullptr;
+      d.status = c->d_status;
+      launch_decode(d, c->stream);
+      merge_behind(j);
+    }
+  } else {
+    for (uint32_t i = 0; i < n_parts; ++i) {
+      const uint32_t j = parts[i].slot;
+      if ((rc = ghf_decode_range(c, h_stream_ptrs[j], h_stream_bytes[j], d_codes + j, indexes + j, nullptr, nullptr, 0, parts[i].lo,
+                                 parts[i].hi - parts[i].lo, parts[i].to, parts[i].cap)))
+        return rc;
+      merge_behind(j);
+    }
+  }
+  // nothing reaches d_out behind a failed decode or a count that does not match the rank table
+  launch_planes_merge_range(c->planes.p, stride, base.p, first - from, count, E, d_out, c->d_status, c->stream);
+  GHF_HIP(c, hipGetLastError());
+  return GHF_OK;
+}
+
+int ghf_decode_planes_sparse_range(ghf_ctx* c, const uint8_t* const* h_stream_ptrs, const size_t* h_stream_bytes, const ghf_code* d_codes,
+                                   const ghf_index* indexes, const ghf_seek_info* h_infos, const uint8_t* const* h_table_ptrs,
+                                   const size_t* h_table_bytes, const ghf_sparse_rank_info* h_rank_infos, const uint8_t* const* h_rank_ptrs,
+                                   unsigned sparse_planes, size_t n_elems, uint32_t elem_bytes, uint64_t first, uint64_t count, uint8_t* d_out,
+                                   size_t cap) {
+  return decode_planes_sparse_range(c, "ghf_decode_planes_sparse_range", h_stream_ptrs, h_stream_bytes, d_codes, indexes, h_infos, h_table_ptrs,
+                                    h_table_bytes, h_rank_infos, h_rank_ptrs, no_base(), sparse_planes, n_elems, elem_bytes, first, count, d_out,
+                                    cap);
+}
+int ghf_decode_planes_sparse_range_delta(ghf_ctx* c, const uint8_t* const* h_stream_ptrs, const size_t* h_stream_bytes, const ghf_code* d_codes,
+                                         const ghf_index* indexes, const ghf_seek_info* h_infos, const uint8_t* const* h_table_ptrs,
+                                         const size_t* h_table_bytes, const ghf_sparse_rank_info* h_rank_infos,
+                                         const uint8_t* const* h_rank_ptrs, const uint8_t* d_base, unsigned sparse_planes, size_t n_elems,
+                                         uint32_t elem_bytes, uint64_t first, uint64_t count, uint8_t* d_out, size_t cap) {
+  return decode_planes_sparse_range(c, "ghf_decode_planes_sparse_range_delta", h_stream_ptrs, h_stream_bytes, d_codes, indexes, h_infos,
+                                    h_table_ptrs, h_table_bytes, h_rank_infos, h_rank_ptrs, base_of(d_base), sparse_planes, n_elems, elem_bytes,
+                                    first, count, d_out, cap);
 }
 
 }  // extern "C"

@@ -40,8 +40,8 @@ __device__ __forceinline__ void dec_image_fill(DecTables* __restrict__ dt, const
   }
 }
 
-__global__ __launch_bounds__(256) void k_build_decode_tables(const ghf_code* __restrict__ code, DecTables* __restrict__ dt,
-                                                             int* __restrict__ status) {
+// (the body of the two kernels below: 256 threads, one workgroup per code)
+__device__ __forceinline__ void build_decode_tables(const ghf_code* __restrict__ code, DecTables* __restrict__ dt, int* __restrict__ status) {
   __shared__ CodeTab T;  // fcl / sp / symbol and the one-symbol direct table (ghf_code_rules.h)
   __shared__ unsigned long long kraft;
   __shared__ int bad;
@@ -107,6 +107,20 @@ __global__ __launch_bounds__(256) void k_build_decode_tables(const ghf_code* __r
   dec_image_fill(dt, T.lut, s_lut2, lb, pb, tid, 256);
 }
 
+__global__ __launch_bounds__(256) void k_build_decode_tables(const ghf_code* __restrict__ code, DecTables* __restrict__ dt,
+                                                             int* __restrict__ status) {
+  build_decode_tables(code, dt, status);
+}
+
+// The tables of several codes in ONE launch (ghf_decode_planes_sparse_range from seek tables: up to sixteen stored streams,
+// whose tables would otherwise be sixteen launches of one workgroup, one behind the other): workgroup j builds dts[j] from
+// codes[j] if bit j of `slots` is set
+__global__ __launch_bounds__(256) void k_build_decode_tables_slots(const ghf_code* __restrict__ codes, DecTables* __restrict__ dts, uint32_t slots,
+                                                                   int* __restrict__ status) {
+  if (!((slots >> blockIdx.x) & 1u)) return;
+  build_decode_tables(codes + blockIdx.x, dts + blockIdx.x, status);
+}
+
 // .crs: the same direct table, filled by walking the tree DecodeHuffTree::do_build_tree would rebuild
 // (include/huff_tree.cc:289-303); what the table cannot resolve is walked bit by bit like decode_byte does (:255-271).
 __global__ __launch_bounds__(256) void k_crs_decode_tables(const ghf_tree* __restrict__ tree, DecTables* __restrict__ dt,
@@ -170,6 +184,10 @@ void launch_crs_decode_tables(const ghf_tree* d_tree, DecTables* d_dt, int* d_st
 
 void launch_build_decode_tables(const ghf_code* d_code, DecTables* d_dt, int* d_status, hipStream_t s) {
   hipLaunchKernelGGL(k_build_decode_tables, dim3(1), dim3(256), 0, s, d_code, d_dt, d_status);
+}
+void launch_build_decode_tables_slots(const ghf_code* d_codes, DecTables* d_dts, uint32_t count, uint32_t slots, int* d_status, hipStream_t s) {
+  if (count == 0 || slots == 0) return;
+  hipLaunchKernelGGL(k_build_decode_tables_slots, dim3(count), dim3(256), 0, s, d_codes, d_dts, slots, d_status);
 }
 
 template <bool STAGED>

@@ -64,6 +64,14 @@ constexpr uint32_t kSparseTile = 4096;
 constexpr uint32_t kSparseGroups = 256 * 16;       // as kPlanesGroups; also the most counts the one-workgroup scan takes, in ONE step
 constexpr uint32_t kSparseLdsBytes = 258 * 16;     // the compacted side of a tile at any byte phase: (15 + 4096 + 15) / 16 + 1 vectors
 constexpr size_t kSparseOffWords = kSparseGroups + 2;  // offs[groups] = the total; the last word: n_vals of a split inside a plane call
+// the rank table of a sparse string: a 64-byte header, then cum[0 .. blocks] as u64, little-endian;
+// cum[j] = the non-zero bytes in front of element kSparseRankElems * j.  A rank block is 4096 mask bytes: one seek block of
+// the mask's stream
+constexpr uint32_t kSparseRankElems = 32768;
+constexpr size_t kSparseRankHeaderBytes = 64;
+constexpr uint64_t kSparseRankMagic = 0x314B4E4152464847ull;  // "GHFRANK1"
+constexpr uint32_t kSparseRankVersion = 1;
+static_assert(kSparseRankElems == 8 * kBlockSymbols, "a rank block of the mask is one seek block");
 
 // the .crs2 header: the count word, symbol[257], min_len, max_len, then a (start_pos, first_code) row per length 1..max_len
 constexpr uint64_t kHeaderFixedBytes = 4 * (GHF_NSYM + 3);  // 1040
@@ -187,6 +195,13 @@ struct SeekExpandParams {
 struct SeekExpandPlanesParams {
   SeekExpandParams plane[GHF_PLANES_MAX];
 };
+// up to kSeekStreamsMax streams in one launch, every one with its own n_symbols, tables and blocks [g0, g1) (the mask and
+// values streams of ghf_decode_planes_sparse_range).  16 x 88 bytes: well inside the 4 KiB of kernel arguments
+constexpr uint32_t kSeekStreamsMax = 2 * GHF_PLANES_MAX;
+struct SeekExpandStreamsParams {
+  SeekExpandParams stream[kSeekStreamsMax];
+};
+static_assert(sizeof(SeekExpandStreamsParams) <= 4096 - 64, "the parameter block stays under the kernel-argument limit");
 // the part [lo, hi) of ONE block (hi <= the block's end) -> out[0 .. hi - lo)
 struct DecHeadParams {
   const uint8_t* stream;
@@ -431,6 +446,8 @@ void launch_shard_start(const ghf_code* d_code, const uint64_t* d_totals, int ra
 void launch_emit(const EmitParams& p, hipStream_t s);
 // ghf_decode.hip: the decode tables and K7
 void launch_build_decode_tables(const ghf_code* d_code, DecTables* d_dt, int* d_status, hipStream_t s);
+// d_dts[j] from d_codes[j] for every j < count with bit j of `slots` set, in one launch
+void launch_build_decode_tables_slots(const ghf_code* d_codes, DecTables* d_dts, uint32_t count, uint32_t slots, int* d_status, hipStream_t s);
 void launch_crs_decode_tables(const ghf_tree* d_tree, DecTables* d_dt, int* d_status, hipStream_t s);
 constexpr uint64_t kDecMaxGroups = 0xFFFF0000ull;  // groups of 4096 symbols one k_decode launch takes (2^44 symbols)
 void launch_decode(const DecParams& p, hipStream_t s);
@@ -447,6 +464,8 @@ void launch_sync_index(const SyncParams& p, uint64_t* d_seg_abs, uint64_t n_symb
 void launch_seek_pack(const SeekPackParams& p, hipStream_t s);
 void launch_seek_expand(const SeekExpandParams& p, hipStream_t s);
 void launch_seek_expand_planes(const SeekExpandPlanesParams& a, uint32_t planes, hipStream_t s);
+// streams whose [g0, g1) is empty take no part; nothing is queued when all are
+void launch_seek_expand_streams(const SeekExpandStreamsParams& a, uint32_t streams, hipStream_t s);
 void launch_decode_head(const DecHeadParams& p, hipStream_t s);
 // ghf_batch.hip
 void launch_compress_batch(const BatchCompressParams& p, uint32_t count, hipStream_t s);  // one launch, grid = count
@@ -488,6 +507,13 @@ void launch_sparse_split(const uint8_t* d_in, uint64_t n, uint8_t* d_mask, uint8
 // merge: nothing is stored when *d_status is non-zero; set bits other than n_vals, or a set pad bit, latch GHF_E_CORRUPT
 void launch_sparse_merge(const uint8_t* d_mask, const uint8_t* d_vals, uint64_t n_vals, uint64_t n, uint8_t* d_out, uint64_t* d_counts,
                          uint64_t* d_offs, int* d_status, hipStream_t s);
+// the same with the values at d_vals[vals_skip .. vals_skip + n_vals): d_vals 16-byte aligned, vals_skip arbitrary
+void launch_sparse_merge_at(const uint8_t* d_mask, const uint8_t* d_vals, uint64_t vals_skip, uint64_t n_vals, uint64_t n, uint8_t* d_out,
+                            uint64_t* d_counts, uint64_t* d_offs, int* d_status, hipStream_t s);
+// mask of a string of n bytes -> its rank table at d_table (16-byte aligned, kSparseRankHeaderBytes + 8 * (blocks + 1) bytes);
+// three launches (count, scan, write); a set pad bit latches GHF_E_CORRUPT; nothing is stored behind a latched status
+void launch_sparse_rank_pack(const uint8_t* d_mask, uint64_t n, uint8_t* d_table, uint64_t* d_counts, uint64_t* d_offs, int* d_status,
+                             hipStream_t s);
 // ghf_planes_hist.hip: elem_bytes is 2, 4 or 8, n_elems > 0, d_in 16-byte aligned.  d_acc: kPlanesHistAccWords words, zero
 // between launches.  Two launches: the counting kernel, then the finish (replica sums, slot 256, GHF_HIST_COVER_ALL), which
 // is also what zeroes d_acc again.  -> the first launch error; after an error of the finish launch d_acc is the caller's to clear.

@@ -73,6 +73,22 @@ struct SeekCursor {
     }
     return r;
   }
+  // the same vector as it stands in memory (the step walk swaps a word where it takes it: a swap behind the load would make
+  // the wave wait for the vector where it asked for it)
+  __device__ __forceinline__ uint4 load_raw(uint64_t v) const {
+    const uint64_t b = v << 4;
+    uint4 r = make_uint4(0, 0, 0, 0);
+    if (b + 16 <= full_bytes) {
+      r = *reinterpret_cast<const uint4*>(s + b);
+    } else if (b < bytes) {
+      uint32_t q[4] = {0, 0, 0, 0};
+#pragma unroll
+      for (int j = 0; j < 16; ++j)
+        if (b + j < bytes) q[j >> 2] |= (uint32_t)s[b + j] << (8 * (j & 3));
+      r = make_uint4(q[0], q[1], q[2], q[3]);
+    }
+    return r;
+  }
   __device__ __forceinline__ uint32_t word() {
     if (left == 0) {
       cur = nxt;
@@ -133,7 +149,17 @@ constexpr int kSeekThreads = 1024;
 // it has, with no memory access inside a round.  W holds two stream words and `o` the offset of the next code from W's top;
 // feeding a word drops W's upper word.  The walk opens with o = 64 + (the start bit's offset in its vector): the code "starts"
 // that far behind two words that are not there yet, and the first words fed only bring o down.
-template <bool kRounds>
+//
+// kSteps (k_seek_expand_streams; codes of up to 32 bits) walks in STEPS.  In a round every lane decodes the codes that start in
+// ITS word while the wave waits for the lane with the most of them, word after word: on streams whose code lengths vary --
+// the masks and values of sparse planes: 1 to 19 bits -- a wave made 1400 passes through the decode chain for its 512 symbols
+// (measured: 1035 cycles per symbol on the values of a bf16 delta plane, 357 on a mask of 1-bit codes; the loads and the
+// miss path together were under 3 % of it).  Here a pass of the wave is one symbol of every lane, 512 passes for a run,
+// whatever the lengths.  A lane owns three vectors: `cur`, which it takes words from, `nxt` behind it and `fut` in flight.
+// Every T = 128 / max_len - 1 symbols -- no lane can use up more than one vector in between -- the wave stops at a refill point:
+// it waits for the vectors requested at the last one, and a lane whose `nxt` has moved up gets `fut` and requests the next.
+// Between two refill points there is no memory access but the side-car's own stores.
+template <bool kRounds, bool kSteps = false>
 __device__ __forceinline__ void seek_expand_run(const SeekExpandParams& P, const DecLds& L, int lut_bits, int max_len, int pair_bits,
                                                 uint64_t r, int tid) {
   const uint64_t g = r >> 3;
@@ -169,7 +195,65 @@ __device__ __forceinline__ void seek_expand_run(const SeekExpandParams& P, const
   const DecLut T = dec_lut1(L.lut, lut_bits, pair_bits, tid & 63);
   SeekCursor c;
   uint32_t used = 0, acc = 0;
-  if (kRounds && max_len <= 32) {
+  if (kSteps && max_len <= 32) {
+    const uint64_t B = start + before;
+    c.s = P.stream;
+    c.bytes = P.stream_bytes;
+    c.full_bytes = P.stream_bytes & ~15ull;
+    uint64_t v = B >> 7;
+    uint4 cur = c.load_raw(v), nxt = c.load_raw(v + 1), fut = c.load_raw(v + 2);
+    v += 3;
+    uint32_t left = 4;       // words of `cur` not yet taken
+    bool have_nxt = true;    // false: nxt has moved up into cur and fut has not yet moved up into nxt
+    auto take = [&]() -> uint32_t {  // the stream's next word
+      if (left == 0) {       // (have_nxt holds here: see T)
+        cur = nxt;
+        have_nxt = false;
+        left = 4;
+      }
+      const uint32_t w = bswap32(cur.x);
+      cur.x = cur.y;
+      cur.y = cur.z;
+      cur.z = cur.w;
+      --left;
+      return w;
+    };
+    for (uint32_t k0 = (uint32_t)(B >> 5) & 3u; k0; --k0) (void)take();
+    const uint32_t w0 = take(), w1 = take();
+    uint64_t W = win_open(w0, w1);
+    uint32_t o = (uint32_t)(B & 31u), done = 0;
+    // Behind a refill point nxt is whole: a lane holds at least four words it has not taken.  A word is taken in front of a
+    // symbol, when o >= 32; o is at most 31 + max_len where the span begins, so T symbols take at most
+    // (31 + (T + 1) max_len) / 32 words: four with T = 128 / max_len - 1.  Four words move nxt up at most once.
+    const uint32_t span = 128u / (uint32_t)max_len - 1u;  // T: 3 (max_len 32) .. 127
+#pragma unroll 1
+    while (__any(done < nsym)) {
+      if (!have_nxt) {  // fut was requested at the last refill point (or in front of the walk): this is where the wave waits for it
+        nxt = fut;
+        have_nxt = true;
+        fut = done < nsym ? c.load_raw(v) : make_uint4(0, 0, 0, 0);
+        ++v;
+      }
+#pragma unroll 1
+      for (uint32_t t = 0; t < span; ++t) {
+        if (done < nsym) {
+          if (o >= 32u) {
+            W = (W << 32) | take();
+            o -= 32u;
+          }
+          const uint32_t hi = win_peek(W, o);
+          uint32_t ent = dec_lookup(T, hi);
+          if (ent & kEntNone) ent = dec_long_entry(L, hi, lut_bits, max_len);
+          const uint32_t len = (ent >> 8) & 0xFFu;
+          acc |= ent;
+          used += len;
+          o += len;
+          ++done;
+          if ((done & (uint32_t)(kSegSymbols - 1)) == 0 || done == nsym) seg_out[(done - 1) / kSegSymbols] = before + used;
+        }
+      }
+    }
+  } else if (kRounds && max_len <= 32) {
     const uint64_t B = start + before;
     c.s = P.stream;
     c.bytes = P.stream_bytes;
@@ -252,6 +336,23 @@ __global__ __launch_bounds__(kSeekThreads) void k_seek_expand_planes(SeekExpandP
   seek_expand_run<true>(P, L, lut_bits, max_len, pair_bits, P.g0 * kRunsPerBlock + (uint64_t)blockIdx.x * blockDim.x + (uint32_t)tid, tid);
 }
 
+// The same for streams that have nothing in common (ghf_decode_planes_sparse_range): the planes, masks
+// and values of one tensor, every one with its own n_symbols, its own tables and its own blocks [g0, g1).  blockIdx.y names the
+// stream and grid.x is sized by the widest one: a workgroup beyond its stream's own runs -- and every workgroup of a slot with
+// g1 == g0, whose other fields are then not looked at -- leaves before it loads a table.
+__global__ __launch_bounds__(kSeekThreads) void k_seek_expand_streams(SeekExpandStreamsParams A) {
+  __shared__ DecLds L;
+  const SeekExpandParams& P = A.stream[blockIdx.y];
+  if ((uint64_t)blockIdx.x * blockDim.x >= (P.g1 - P.g0) * kRunsPerBlock) return;
+  const int tid = threadIdx.x;
+  if (tid == 0) L.status0 = *P.status;
+  const int lut_bits = P.dt->lut_bits, max_len = P.dt->max_len, pair_bits = P.dt->pair_bits;
+  dec_lds_load(L, P.dt, tid, (int)blockDim.x);
+  __syncthreads();
+  if (L.status0 != 0) return;
+  seek_expand_run<true, true>(P, L, lut_bits, max_len, pair_bits, P.g0 * kRunsPerBlock + (uint64_t)blockIdx.x * blockDim.x + (uint32_t)tid, tid);
+}
+
 // The head of a range that does not begin on a block boundary: one wave, one lane per segment of the block, same tables;
 // a lane decodes its segment from the side-car's start and stores the symbols of [lo, hi) only.  A segment that is decoded
 // to its end is checked against the side-car like K7 does.
@@ -309,6 +410,21 @@ void launch_seek_expand_planes(const SeekExpandPlanesParams& a, uint32_t planes,
   const uint64_t per = (waves + 511) / 512;
   const uint32_t threads = 64u * (uint32_t)(per < 1 ? 1 : per > kSeekThreads / 64 ? kSeekThreads / 64 : per);
   hipLaunchKernelGGL(k_seek_expand_planes, dim3((uint32_t)((lanes + threads - 1) / threads), planes), dim3(threads), 0, s, a);
+}
+// the same rule with the streams' own widths: the waves of all streams decide how narrow a workgroup may be, the widest
+// stream decides grid.x
+void launch_seek_expand_streams(const SeekExpandStreamsParams& a, uint32_t streams, hipStream_t s) {
+  uint64_t widest = 0, waves = 0;
+  for (uint32_t j = 0; j < streams; ++j) {
+    const SeekExpandParams& p = a.stream[j];
+    const uint64_t lanes = p.g1 > p.g0 ? (p.g1 - p.g0) * kRunsPerBlock : 0;
+    widest = lanes > widest ? lanes : widest;
+    waves += (lanes + 63) / 64;
+  }
+  if (widest == 0) return;
+  const uint64_t per = (waves + 511) / 512;
+  const uint32_t threads = 64u * (uint32_t)(per < 1 ? 1 : per > kSeekThreads / 64 ? kSeekThreads / 64 : per);
+  hipLaunchKernelGGL(k_seek_expand_streams, dim3((uint32_t)((widest + threads - 1) / threads), streams), dim3(threads), 0, s, a);
 }
 void launch_decode_head(const DecHeadParams& p, hipStream_t s) {
   if (p.hi <= p.lo) return;

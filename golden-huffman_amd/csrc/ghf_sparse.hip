@@ -288,15 +288,17 @@ __device__ __forceinline__ uint4 window16(const uint32_t* lds32, uint32_t o) {
 // and a set pad bit (the count) keep every byte of `out` as it was.  The masks of the next tile are requested behind the
 // values of this one, so that one memory round trip stands in front of a tile's stores, not two.  A lane takes the (up to
 // 16) values of a vector out of the LDS tile as one 16-byte window and deals them out in registers.
-__global__ __launch_bounds__(kWave) void k_sparse_merge_move(const uint8_t* __restrict__ mask, const uint8_t* __restrict__ vals, uint64_t n,
-                                                             uint8_t* __restrict__ out, const uint64_t* __restrict__ offs,
-                                                             const int* __restrict__ status) {
-  __shared__ uint4 stage[kStageVecs];
+// `skip`: where the string's first value stands in vals (k_sparse_merge_move: 0; k_sparse_merge_move_at: the caller's
+// vals_skip).  It is one more term of the workgroup's base offset and of nothing else: the tile stands in the LDS at the phase
+// (skip + its offset) & 15, which the 4128 bytes cover like any other.
+__device__ __forceinline__ void sparse_merge_move(uint4 (&stage)[kStageVecs], const uint8_t* __restrict__ mask, const uint8_t* __restrict__ vals,
+                                                  uint64_t skip, uint64_t n, uint8_t* __restrict__ out, const uint64_t* __restrict__ offs,
+                                                  const int* __restrict__ status) {
   const uint32_t* s32 = reinterpret_cast<const uint32_t*>(stage);
   if (__builtin_amdgcn_readfirstlane(*status) != 0) return;
   const uint32_t lane = threadIdx.x;
   const Slab s = slab_of(n);
-  uint64_t base = offs[blockIdx.x];
+  uint64_t base = skip + offs[blockIdx.x];
   uint32_t m[kVec] = {0, 0, 0, 0};
   if (s.lo < s.end) load_masks(mask, n, s.lo, lane, m);
   for (uint64_t t = s.lo; t < s.end; ++t) {
@@ -340,6 +342,83 @@ __global__ __launch_bounds__(kWave) void k_sparse_merge_move(const uint8_t* __re
   }
 }
 
+__global__ __launch_bounds__(kWave) void k_sparse_merge_move(const uint8_t* __restrict__ mask, const uint8_t* __restrict__ vals, uint64_t n,
+                                                             uint8_t* __restrict__ out, const uint64_t* __restrict__ offs,
+                                                             const int* __restrict__ status) {
+  __shared__ uint4 stage[kStageVecs];
+  sparse_merge_move(stage, mask, vals, 0, n, out, offs, status);
+}
+
+// ghf_sparse_merge_at: the values are vals[skip .. skip + n_vals).  Nothing in front of
+// vals[skip & ~15] and nothing behind the vector that holds the last value is read.  A sibling, not a parameter of the kernel
+// above: that one keeps its symbol and its listing.
+__global__ __launch_bounds__(kWave) void k_sparse_merge_move_at(const uint8_t* __restrict__ mask, const uint8_t* __restrict__ vals, uint64_t skip,
+                                                                uint64_t n, uint8_t* __restrict__ out, const uint64_t* __restrict__ offs,
+                                                                const int* __restrict__ status) {
+  __shared__ uint4 stage[kStageVecs];
+  sparse_merge_move(stage, mask, vals, skip, n, out, offs, status);
+}
+
+// ---- the rank table, launch 3: cum[j] = the non-zero bytes in front of element kSparseRankElems * j ------
+// Launches 1 and 2 are k_sparse_merge_count and k_sparse_scan.  Every workgroup walks the mask bytes of its slab again, eight
+// tiles (one rank block: 4096 mask bytes, four vectors per lane) at a time.  Exactly one of eight consecutive tiles opens a rank
+// block; if it lies in the slab this workgroup owns it, whichever slab the rest of the block falls into, and stores its cum
+// entry: the slab's offset, the vectors walked so far, and the vectors of this step in front of the tile.  The workgroup with
+// the string's last tile also stores cum[blocks] and the header.  Stores nothing behind a latched status.
+constexpr uint32_t kRankTiles = kSparseRankElems / kSparseTile;  // 8
+constexpr uint32_t kMaskTileVecs = kMaskTileBytes / 16;          // 32
+static_assert(kRankTiles * kMaskTileVecs == kTileVecs, "a rank block of mask bytes is one step of the wave");
+__global__ __launch_bounds__(kWave) void k_sparse_rank_write(const uint8_t* __restrict__ mask, uint64_t n, const uint64_t* __restrict__ offs,
+                                                             uint64_t* __restrict__ table, const int* __restrict__ status) {
+  if (__builtin_amdgcn_readfirstlane(*status) != 0) return;
+  const uint32_t lane = threadIdx.x;
+  const Slab s = slab_of(n);
+  if (s.lo >= s.end) return;
+  const uint64_t mb = (n + 7) / 8;
+  const uint64_t lo = s.lo * kMaskTileBytes, hi = s.end * kMaskTileBytes < mb ? s.end * kMaskTileBytes : mb;  // lo is a multiple of 16
+  const uint64_t nv = (hi - lo + 15) / 16;
+  uint64_t* const cum = table + kSparseRankHeaderBytes / 8;
+  uint64_t running = offs[blockIdx.x];
+  for (uint64_t t0 = s.lo; t0 < s.end; t0 += kRankTiles) {
+    const uint64_t v0 = (t0 - s.lo) * kMaskTileVecs;
+    const uint64_t opens = (t0 + kRankTiles - 1) & ~(uint64_t)(kRankTiles - 1);  // the tile of [t0, t0 + 8) that opens a rank block
+    const uint32_t cut = (uint32_t)(opens - t0) * kMaskTileVecs;                 // this step's vectors in front of it
+    uint4 x[kVec];
+#pragma unroll
+    for (int j = 0; j < kVec; ++j) {
+      const uint64_t v = v0 + j * kWave + lane;
+      x[j] = make_uint4(0, 0, 0, 0);
+      if (v < nv) x[j] = ld16(mask + lo + v * 16);
+    }
+    uint32_t all = 0, front = 0;
+#pragma unroll
+    for (int j = 0; j < kVec; ++j) {
+      const uint64_t v = v0 + j * kWave + lane;
+      if (v < nv && hi - lo - v * 16 < 16) x[j] = trim16(x[j], (int)(hi - lo - v * 16));  // behind the last mask byte: not ours
+      const uint32_t c = __builtin_popcount(x[j].x) + __builtin_popcount(x[j].y) + __builtin_popcount(x[j].z) + __builtin_popcount(x[j].w);
+      all += c;
+      front += (uint32_t)(j * kWave) + lane < cut ? c : 0u;
+    }
+    const uint32_t front_sum = wave_last_u32(wave_incl_scan_u32(front)), all_sum = wave_last_u32(wave_incl_scan_u32(all));
+    if (lane == 0 && opens < s.end) cum[opens / kRankTiles] = running + front_sum;
+    running += all_sum;
+  }
+  const uint64_t nt = (n + kSparseTile - 1) / kSparseTile;
+  if (s.end == nt) {
+    const uint64_t blocks = (n + kSparseRankElems - 1) / kSparseRankElems;
+    if (lane == 0) cum[blocks] = running;
+    if (lane < kSparseRankHeaderBytes / 8) {
+      const uint64_t w = lane == 0   ? kSparseRankMagic
+                         : lane == 1 ? (uint64_t)kSparseRankElems << 32 | kSparseRankVersion
+                         : lane == 2 ? n
+                         : lane == 3 ? running
+                         : lane == 4 ? blocks
+                                     : 0ull;
+      table[lane] = w;
+    }
+  }
+}
+
 // one resident round: kSparseGroups one-wave workgroups, each with a slab of tiles
 static uint32_t sparse_grid(uint64_t n) {
   const uint64_t nt = (n + kSparseTile - 1) / kSparseTile;
@@ -362,6 +441,25 @@ void launch_sparse_merge(const uint8_t* d_mask, const uint8_t* d_vals, uint64_t 
   hipLaunchKernelGGL(k_sparse_merge_count, grid, block, 0, s, d_mask, n, d_counts, d_status);
   hipLaunchKernelGGL(k_sparse_scan, dim3(1), dim3(kScanThreads), 0, s, d_counts, groups, d_offs, n_vals, (uint64_t*)nullptr, d_status);
   hipLaunchKernelGGL(k_sparse_merge_move, grid, block, 0, s, d_mask, d_vals, n, d_out, d_offs, d_status);
+}
+
+void launch_sparse_merge_at(const uint8_t* d_mask, const uint8_t* d_vals, uint64_t vals_skip, uint64_t n_vals, uint64_t n, uint8_t* d_out,
+                            uint64_t* d_counts, uint64_t* d_offs, int* d_status, hipStream_t s) {
+  const uint32_t groups = sparse_grid(n);
+  const dim3 grid(groups), block(kWave);
+  hipLaunchKernelGGL(k_sparse_merge_count, grid, block, 0, s, d_mask, n, d_counts, d_status);
+  hipLaunchKernelGGL(k_sparse_scan, dim3(1), dim3(kScanThreads), 0, s, d_counts, groups, d_offs, n_vals, (uint64_t*)nullptr, d_status);
+  hipLaunchKernelGGL(k_sparse_merge_move_at, grid, block, 0, s, d_mask, d_vals, vals_skip, n, d_out, d_offs, d_status);
+}
+
+void launch_sparse_rank_pack(const uint8_t* d_mask, uint64_t n, uint8_t* d_table, uint64_t* d_counts, uint64_t* d_offs, int* d_status,
+                             hipStream_t s) {
+  const uint32_t groups = sparse_grid(n);
+  const dim3 grid(groups), block(kWave);
+  hipLaunchKernelGGL(k_sparse_merge_count, grid, block, 0, s, d_mask, n, d_counts, d_status);
+  // the scan as the split uses it, with no capacity to exceed; the total goes to the spare word behind offs[groups]
+  hipLaunchKernelGGL(k_sparse_scan, dim3(1), dim3(kScanThreads), 0, s, d_counts, groups, d_offs, ~0ull, d_offs + kSparseOffWords - 1, d_status);
+  hipLaunchKernelGGL(k_sparse_rank_write, grid, block, 0, s, d_mask, n, d_offs, reinterpret_cast<uint64_t*>(d_table), d_status);
 }
 
 }  // namespace ghf

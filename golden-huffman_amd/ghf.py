@@ -33,6 +33,7 @@ PLANES_BUILD_CODES = 1  # GHF_PLANES_BUILD_CODES (ghf_compress_planes_coded): d_
 SPARSE_TILE = 4096
 SPARSE_GROUPS = 256 * 16
 SPARSE_SCAN = SPARSE_GROUPS
+SPARSE_RANK_ELEMS = 32768  # GHF_SPARSE_RANK_ELEMS: the elements of a rank block: 4096 mask bytes, one seek block
 SPARSE_AUTO = 0x80000000  # GHF_SPARSE_AUTO (ghf_compress_planes_sparse): planes with at least 3/4 zero bytes are stored sparse
 EMPTY_OK = 2  # opt-in: n == 0 -> header of the one-symbol code + 0x7F (builder's definition, parity unpinned)
 
@@ -110,6 +111,12 @@ class SeekInfo(C.Structure):
     _fields_ = [("n_symbols", C.c_uint64), ("n_blocks", C.c_uint64), ("flags", C.c_uint32), ("version", C.c_uint32)]
 
 
+class SparseRankInfo(C.Structure):
+    """ghf_sparse_rank_info: what ghf_sparse_rank_parse reads from a rank table"""
+
+    _fields_ = [("n", C.c_uint64), ("n_vals", C.c_uint64), ("n_blocks", C.c_uint64), ("version", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 class Tree(C.Structure):
     """ghf_tree == the reference's HuffTree for the .crs format (include/huff_tree.h:98-176): node ids 0..255 are
     leaves (the key), 256 + i is the i-th parent, left[i] / right[i] its children."""
@@ -166,6 +173,9 @@ EXPORTS = [
     "ghf_compress_planes_delta", "ghf_decode_planes_delta", "ghf_decode_planes_range_delta",
     "ghf_sparse_mask_bytes", "ghf_sparse_split", "ghf_sparse_merge", "ghf_compress_planes_sparse",
     "ghf_compress_planes_sparse_delta", "ghf_decode_planes_sparse", "ghf_decode_planes_sparse_delta",
+    "ghf_sparse_rank_bytes", "ghf_sparse_rank_pack", "ghf_sparse_rank_parse", "ghf_sparse_merge_at",
+    "ghf_compress_planes_sparse_ranked", "ghf_compress_planes_sparse_ranked_delta", "ghf_decode_planes_sparse_range",
+    "ghf_decode_planes_sparse_range_delta",
 ]
 COMM_ID_BYTES = 128
 
@@ -321,6 +331,17 @@ def lib():
                                            vp, sz, vp]
     L.ghf_decode_planes_sparse_delta.argtypes = [vp, C.POINTER(vp), C.POINTER(sz), vp, C.POINTER(Index), vp, C.c_uint, C.POINTER(sz),
                                                  sz, u32, vp, sz, vp]
+    L.ghf_sparse_rank_bytes.argtypes = [sz]
+    L.ghf_sparse_rank_bytes.restype = sz
+    L.ghf_sparse_rank_pack.argtypes = [vp, vp, sz, vp, sz]
+    L.ghf_sparse_rank_parse.argtypes = [vp, sz, C.POINTER(SparseRankInfo)]
+    L.ghf_sparse_merge_at.argtypes = [vp, vp, vp, sz, sz, sz, vp]
+    L.ghf_compress_planes_sparse_ranked.argtypes = L.ghf_compress_planes_sparse.argtypes + [vp, sz]
+    L.ghf_compress_planes_sparse_ranked_delta.argtypes = L.ghf_compress_planes_sparse_delta.argtypes + [vp, sz]
+    sparse_range_front = [vp, C.POINTER(vp), C.POINTER(sz), vp, C.POINTER(Index), C.POINTER(SeekInfo), C.POINTER(vp), C.POINTER(sz),
+                          C.POINTER(SparseRankInfo), C.POINTER(vp)]
+    L.ghf_decode_planes_sparse_range.argtypes = sparse_range_front + [C.c_uint, sz, u32, u64, u64, vp, sz]
+    L.ghf_decode_planes_sparse_range_delta.argtypes = sparse_range_front + [vp, C.c_uint, sz, u32, u64, u64, vp, sz]
     _lib = L
     return L
 
@@ -370,6 +391,39 @@ def planes_slot_bytes(n_elems):
 def sparse_mask_bytes(n):
     """(n + 7) // 8: the bytes of the mask of a byte string of n bytes in the sparse form"""
     return int(lib().ghf_sparse_mask_bytes(n))
+
+
+def sparse_rank_bytes(n):
+    """64 + 8 * (ceil(n / 32768) + 1): the bytes of the rank table of a byte string of n bytes"""
+    return int(lib().ghf_sparse_rank_bytes(n))
+
+
+def sparse_rank_parse(host_bytes):
+    """host-side validation of a whole rank table (header, size and every step of cum). -> SparseRankInfo"""
+    import numpy as np
+
+    a = np.ascontiguousarray(host_bytes, dtype=np.uint8)
+    info = SparseRankInfo()
+    rc = lib().ghf_sparse_rank_parse(a.ctypes.data, a.size, C.byref(info))
+    if rc:
+        raise GhfError(rc, "ghf_sparse_rank_parse")
+    return info
+
+
+def sparse_rank_table(x):
+    """the rank table of the byte string x as numpy computes it (for tests): uint8[64 + 8 * (ceil(n / 32768) + 1)]"""
+    import numpy as np
+
+    x = np.ascontiguousarray(x, dtype=np.uint8).ravel()
+    n = x.size
+    nb = -(-n // SPARSE_RANK_ELEMS)
+    nz = np.concatenate([[0], np.cumsum(x != 0, dtype=np.uint64)]).astype(np.uint64)
+    cum = nz[np.minimum(np.arange(nb + 1, dtype=np.int64) * SPARSE_RANK_ELEMS, n)]
+    head = np.zeros(8, dtype="<u8")
+    head[0] = int.from_bytes(b"GHFRANK1", "little")
+    head[1] = 1 | SPARSE_RANK_ELEMS << 32
+    head[2], head[3], head[4] = n, int(nz[n]), nb
+    return np.concatenate([head, cum.astype("<u8")]).view(np.uint8)
 
 
 def batch_index_item(bidx, i, n_i):
@@ -1391,6 +1445,124 @@ class Context:
         the base).  -> (d_out uint8, nbytes int64[1] device)"""
         return self._decode_planes_sparse(streams, stream_bytes, d_codes, d_base, True, sparse_planes, n_vals, n_elems, elem_bytes,
                                           indexes, d_out, cap, nbytes)
+
+    # ---- an element range of zero-suppressed byte planes (DESIGN.md section 21): rank tables, the merge with values that start
+    # anywhere, the compress calls that write rank tables, the range decode -------------------------------------------------
+    sparse_rank_bytes = staticmethod(sparse_rank_bytes)
+    sparse_rank_parse = staticmethod(sparse_rank_parse)
+
+    def sparse_rank_pack(self, d_mask, n, d_table=None, cap=None):
+        """mask (device) of a byte string of n bytes -> its rank table image in device memory.  No host synchronisation."""
+        if d_table is None:
+            d_table = self.empty_u8(sparse_rank_bytes(n))
+        self._chk(self.L.ghf_sparse_rank_pack(self.h, d_mask.data_ptr(), n, d_table.data_ptr(), d_table.numel() if cap is None else cap),
+                  "ghf_sparse_rank_pack")
+        return d_table
+
+    def sparse_merge_at(self, d_mask, d_vals, vals_skip, n_vals, n, d_out=None):
+        """sparse_merge with the values at d_vals[vals_skip : vals_skip + n_vals] (d_vals itself 16-byte aligned).  -> d_out"""
+        if d_out is None:
+            d_out = self.empty_u8(n)
+        self._chk(self.L.ghf_sparse_merge_at(self.h, d_mask.data_ptr(), None if d_vals is None else d_vals.data_ptr(), vals_skip, n_vals, n,
+                                             d_out.data_ptr()), "ghf_sparse_merge_at")
+        return d_out
+
+    def _compress_planes_sparse_ranked(self, d_in, d_base, delta, elem_bytes, sparse_planes, n_elems, d_out, slot_bytes, d_codes, indexes,
+                                       d_ranks, rank_slot_bytes):
+        t = self.torch
+        n_elems = d_in.numel() * d_in.element_size() // elem_bytes if n_elems is None else n_elems
+        if slot_bytes is None:
+            slot_bytes = planes_slot_bytes(n_elems)
+        if rank_slot_bytes is None:
+            rank_slot_bytes = (sparse_rank_bytes(n_elems) + 15) & ~15
+        if d_out is None:
+            d_out = self.empty_u8(slot_bytes * 2 * elem_bytes)
+        if d_ranks is None:
+            d_ranks = self.empty_u8(rank_slot_bytes * elem_bytes)
+        if d_codes is None:
+            d_codes = t.zeros((2 * elem_bytes, C.sizeof(Code)), dtype=t.uint8, device=self.device)
+        out_bytes = t.zeros(2 * elem_bytes, dtype=t.int64, device=self.device)
+        idx = (Index * (2 * elem_bytes))() if indexes else None
+        chosen, n_vals = C.c_uint(0), (C.c_size_t * elem_bytes)()
+        if delta:
+            rc = self.L.ghf_compress_planes_sparse_ranked_delta(self.h, d_in.data_ptr(), self._base_ptr(d_base), n_elems, elem_bytes,
+                                                                sparse_planes, d_out.data_ptr(), slot_bytes, out_bytes.data_ptr(),
+                                                                d_codes.data_ptr(), idx, C.byref(chosen), n_vals, d_ranks.data_ptr(),
+                                                                rank_slot_bytes)
+        else:
+            rc = self.L.ghf_compress_planes_sparse_ranked(self.h, d_in.data_ptr(), n_elems, elem_bytes, sparse_planes, d_out.data_ptr(),
+                                                          slot_bytes, out_bytes.data_ptr(), d_codes.data_ptr(), idx, C.byref(chosen), n_vals,
+                                                          d_ranks.data_ptr(), rank_slot_bytes)
+        self._chk(rc, "ghf_compress_planes_sparse_ranked_delta" if delta else "ghf_compress_planes_sparse_ranked")
+        return {"out": d_out, "slot_bytes": slot_bytes, "out_bytes": out_bytes, "codes": d_codes, "n_elems": n_elems,
+                "elem_bytes": elem_bytes, "sparse_planes": int(chosen.value), "n_vals": [int(v) for v in n_vals], "indexes": idx,
+                "ranks": d_ranks, "rank_slot_bytes": rank_slot_bytes}
+
+    def compress_planes_sparse_ranked(self, d_in, elem_bytes, sparse_planes=SPARSE_AUTO, n_elems=None, d_out=None, slot_bytes=None,
+                                      d_codes=None, indexes=False, d_ranks=None, rank_slot_bytes=None):
+        """compress_planes_sparse, and the rank table of every sparse plane in slot p of `ranks` (device uint8, elem_bytes slots
+        of rank_slot_bytes; slots of dense planes stay unwritten).  -> the same dict plus ranks and rank_slot_bytes"""
+        return self._compress_planes_sparse_ranked(d_in, None, False, elem_bytes, sparse_planes, n_elems, d_out, slot_bytes, d_codes,
+                                                   indexes, d_ranks, rank_slot_bytes)
+
+    def compress_planes_sparse_ranked_delta(self, d_in, d_base, elem_bytes, sparse_planes=SPARSE_AUTO, n_elems=None, d_out=None,
+                                            slot_bytes=None, d_codes=None, indexes=False, d_ranks=None, rank_slot_bytes=None):
+        """compress_planes_sparse_ranked of d_in ^ d_base.  -> the same dict"""
+        return self._compress_planes_sparse_ranked(d_in, d_base, True, elem_bytes, sparse_planes, n_elems, d_out, slot_bytes, d_codes,
+                                                   indexes, d_ranks, rank_slot_bytes)
+
+    def _decode_planes_sparse_range(self, streams, stream_bytes, d_codes, d_base, delta, sparse_planes, ranks, n_elems, elem_bytes, first,
+                                    count, indexes, infos, d_tables, table_bytes, d_out, cap):
+        import numpy as np
+
+        slots = 2 * elem_bytes
+        ptrs = (C.c_void_p * slots)(*[None if x is None else x.data_ptr() for x in streams])
+        sizes = (C.c_size_t * slots)(*[int(v) for v in stream_bytes])
+        h_infos = t_ptrs = t_bytes = None
+        if infos is not None:
+            h_infos = (SeekInfo * slots)(*[SeekInfo() if i is None else i for i in infos])
+            t_ptrs = (C.c_void_p * slots)(*[None if x is None else x.data_ptr() for x in d_tables])
+            if table_bytes is None:
+                table_bytes = [0 if i is None else seek_bytes(i.n_symbols) for i in infos]
+            t_bytes = (C.c_size_t * slots)(*[int(v) for v in table_bytes])
+        r_infos = r_ptrs = None
+        keep = []
+        if ranks is not None:  # per plane: None, or (SparseRankInfo, the table as host bytes)
+            r_infos, r_ptrs = (SparseRankInfo * elem_bytes)(), (C.c_void_p * elem_bytes)()
+            for p, r in enumerate(ranks):
+                if r is None:
+                    continue
+                r_infos[p] = r[0]
+                if r[1] is not None:
+                    keep.append(np.ascontiguousarray(r[1], dtype=np.uint8))
+                    r_ptrs[p] = keep[-1].ctypes.data
+        if d_out is None:
+            d_out = self.empty_u8(count * elem_bytes)
+        cap = d_out.numel() if cap is None else cap
+        if delta:
+            rc = self.L.ghf_decode_planes_sparse_range_delta(self.h, ptrs, sizes, d_codes.data_ptr(), indexes, h_infos, t_ptrs, t_bytes,
+                                                             r_infos, r_ptrs, self._base_ptr(d_base), sparse_planes, n_elems, elem_bytes,
+                                                             first, count, d_out.data_ptr(), cap)
+        else:
+            rc = self.L.ghf_decode_planes_sparse_range(self.h, ptrs, sizes, d_codes.data_ptr(), indexes, h_infos, t_ptrs, t_bytes, r_infos,
+                                                       r_ptrs, sparse_planes, n_elems, elem_bytes, first, count, d_out.data_ptr(), cap)
+        self._chk(rc, "ghf_decode_planes_sparse_range_delta" if delta else "ghf_decode_planes_sparse_range")
+        return d_out
+
+    def decode_planes_sparse_range(self, streams, stream_bytes, d_codes, sparse_planes, ranks, n_elems, elem_bytes, first, count,
+                                   indexes=None, infos=None, d_tables=None, table_bytes=None, d_out=None, cap=None):
+        """d_out[0 : count * elem_bytes] = elements [first, first + count) of a tensor stored by compress_planes_sparse[_ranked].
+        streams / stream_bytes / infos / d_tables: 2 * elem_bytes entries (None for an empty slot); ranks: per plane None or
+        (SparseRankInfo, the table as HOST bytes); give either indexes or (infos, d_tables).  Never synchronises.  -> d_out"""
+        return self._decode_planes_sparse_range(streams, stream_bytes, d_codes, None, False, sparse_planes, ranks, n_elems, elem_bytes,
+                                                first, count, indexes, infos, d_tables, table_bytes, d_out, cap)
+
+    def decode_planes_sparse_range_delta(self, streams, stream_bytes, d_codes, d_base, sparse_planes, ranks, n_elems, elem_bytes, first,
+                                         count, indexes=None, infos=None, d_tables=None, table_bytes=None, d_out=None, cap=None):
+        """decode_planes_sparse_range, then ^ d_base in the merge: d_base holds base elements [first, first + count), indexed like
+        d_out, and may be d_out.  -> d_out"""
+        return self._decode_planes_sparse_range(streams, stream_bytes, d_codes, d_base, True, sparse_planes, ranks, n_elems, elem_bytes,
+                                                first, count, indexes, infos, d_tables, table_bytes, d_out, cap)
 
     # ---- seekable streams: the seek table (the persistent form of the side-car) ----------------
     def seek_pack(self, index, d_stream=None, stream_bytes=0, d_table=None, n=None):

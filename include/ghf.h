@@ -994,6 +994,123 @@ int ghf_crs_decoded_size(ghf_ctx* ctx, const uint8_t* d_stream, size_t stream_by
 int ghf_crs_sync_piece(ghf_ctx* ctx, const uint8_t* d_piece, size_t piece_bytes, uint32_t first_bit, uint64_t end_bit,
                        const ghf_tree* d_tree, uint64_t* landing, uint64_t* n_symbols);
 
+/* ---- an element range of zero-suppressed byte planes: rank tables, range decode ---
+ * The sparse form (the next section) stores a plane as a mask and its non-zero bytes.  The values of elements
+ * [first, first + count) stand in the values string at offset rank(first), the number of non-zero bytes in front of
+ * `first`, and nothing stored says what that is.  THE RANK TABLE of a string of n bytes says it for every multiple of
+ * GHF_SPARSE_RANK_ELEMS = 32768 elements -- 4096 mask bytes, exactly one 4096-symbol seek block of the mask's stream.
+ * With nb = ceil(n / 32768), little-endian:
+ *   64-byte header: "GHFRANK1", u32 version = 1, u32 block_elems = 32768, u64 n, u64 n_vals, u64 n_blocks = nb, zeros;
+ *   u64 cum[nb + 1]: cum[j] = the non-zero bytes of x[0 .. 32768 j); cum[0] = 0, cum[nb] = n_vals.
+ * 64 + 8 (nb + 1) bytes, 0.024 % of a plane.  It is persistent (the caller stores it beside the images) and NOT TRUSTED:
+ * the parse checks what can be checked without the mask; a range call checks the DIFFERENCE of the two entries it reads
+ * against the mask's set bits and nothing more.  Two entries wrong by the same amount pass, and the range then returns
+ * wrong bytes with GHF_OK: the table guards against damage, not against a forger.
+ * Every device pointer is 16-byte aligned unless said otherwise.  The range calls never synchronise. */
+#define GHF_SPARSE_RANK_ELEMS 32768u
+typedef struct ghf_sparse_rank_info {
+  uint64_t n, n_vals, n_blocks;
+  uint32_t version, reserved;
+} ghf_sparse_rank_info;
+
+/* No reference counterpart (a size the flat buffers of include/compressor.h:62-73 do not need).  Host only:
+ * 64 + 8 * (ceil(n / 32768) + 1), the bytes of the rank table of a string of n bytes. */
+size_t ghf_sparse_rank_bytes(size_t n);
+
+/* No reference counterpart (an index into the flat input of include/compressor.h:62-73).  Asynchronous on the stream,
+ * never synchronises: the mask of a string of n bytes (d_mask, device) -> its rank table image at d_table (device, cap
+ * >= ghf_sparse_rank_bytes of n, else GHF_E_CAP); the caller brings it to the host with ghf_copy_d2h.  Three launches in
+ * the shape of the sparse split -- popcounts per workgroup slab, the scan, a write pass -- and no kernel waits for
+ * another workgroup.  A null pointer, misalignment: GHF_E_INVAL; n == 0: GHF_E_EMPTY.  A set pad bit in the last mask
+ * byte latches GHF_E_CORRUPT; behind a latched status nothing is stored. */
+int ghf_sparse_rank_pack(ghf_ctx* ctx, const uint8_t* d_mask, size_t n, uint8_t* d_table, size_t cap);
+
+/* No reference counterpart (validates an index into the flat output of include/compressor.h:87-92).  Host only, no GPU,
+ * nothing queued: h_table[0 .. bytes) is the whole table.  GHF_E_FORMAT: a wrong magic, version or block size; n_blocks
+ * or `bytes` other than n implies; a non-zero reserved byte; cum[0] != 0; a cum that decreases; a step above 32768, or
+ * above the elements of the last block; cum[nb] != n_vals.  *info <- n, n_vals, n_blocks, version. */
+int ghf_sparse_rank_parse(const uint8_t* h_table, size_t bytes, ghf_sparse_rank_info* info);
+
+/* No reference counterpart (generalises the flat output of include/compressor.h:87-92).  The sparse merge of the next
+ * section with the values at d_vals[vals_skip .. vals_skip + n_vals): d_vals stays 16-byte aligned, vals_skip is
+ * arbitrary.  Nothing outside d_vals[vals_skip & ~15 .. vals_skip + n_vals), rounded up to the vector that holds the
+ * last value, is read.  Every guarantee carries over: only d_out[0 .. n) is written; a launch that finds the status word
+ * non-zero stores nothing; set bits that do not number n_vals, or a set pad bit, latch GHF_E_CORRUPT and nothing is
+ * stored.  Refusals as there, and vals_skip + n_vals beyond size_t: GHF_E_INVAL. */
+int ghf_sparse_merge_at(ghf_ctx* ctx, const uint8_t* d_mask, const uint8_t* d_vals, size_t vals_skip, size_t n_vals, size_t n,
+                        uint8_t* d_out);
+
+/* No reference counterpart: Compressor::compress(), include/compressor.h:62-73, once per stored stream, and the rank
+ * table of every sparse plane.  The sparse compress of the next section -- images, sizes, codes, side-cars,
+ * *h_sparse_planes, h_n_vals and the ONE host wait are byte for byte its own -- plus: d_ranks (device) has elem_bytes
+ * slots of rank_slot_bytes (a multiple of 16, >= ghf_sparse_rank_bytes of n_elems, else GHF_E_CAP; a null or
+ * misaligned d_ranks: GHF_E_INVAL).  Slot p receives the table of plane p if the plane is stored sparse, queued behind
+ * the plane's split while its mask is still in the workspace; slots of dense planes stay unwritten. */
+int ghf_compress_planes_sparse_ranked(ghf_ctx* ctx, const uint8_t* d_in, size_t n_elems, uint32_t elem_bytes, unsigned sparse_planes,
+                                      uint8_t* d_out, size_t slot_bytes, uint64_t* d_out_bytes /* [2 * elem_bytes] */,
+                                      ghf_code* d_codes /* [2 * elem_bytes], optional OUT */,
+                                      ghf_index* h_indexes /* [2 * elem_bytes], optional OUT */, unsigned* h_sparse_planes /* OUT */,
+                                      size_t* h_n_vals /* [elem_bytes] OUT */, uint8_t* d_ranks, size_t rank_slot_bytes);
+
+/* No reference counterpart: Compressor::compress(), include/compressor.h:62-73, once per stored stream of the byte planes
+ * of d_in ^ d_base, and the rank table of every sparse plane.  The call above with the XOR in the histogram and split
+ * kernels.  A null or misaligned d_base: GHF_E_INVAL. */
+int ghf_compress_planes_sparse_ranked_delta(ghf_ctx* ctx, const uint8_t* d_in, const uint8_t* d_base, size_t n_elems,
+                                            uint32_t elem_bytes, unsigned sparse_planes, uint8_t* d_out, size_t slot_bytes,
+                                            uint64_t* d_out_bytes /* [2 * elem_bytes] */,
+                                            ghf_code* d_codes /* [2 * elem_bytes], optional OUT */,
+                                            ghf_index* h_indexes /* [2 * elem_bytes], optional OUT */,
+                                            unsigned* h_sparse_planes /* OUT */, size_t* h_n_vals /* [elem_bytes] OUT */,
+                                            uint8_t* d_ranks, size_t rank_slot_bytes);
+
+/* No reference counterpart: Decompressor::decompress(), include/compressor.h:87-92, for a part of a typed tensor stored
+ * sparse.  d_out[0 .. count * elem_bytes) receives elements [first, first + count).  Asynchronous, never synchronises,
+ * from side-cars or from seek tables.  The arrays of 2 * elem_bytes entries are indexed like the slots of the sparse
+ * compress: j < elem_bytes is plane j or its mask, elem_bytes + p the values of plane p.  Exactly one source of block
+ * starts is given, by the rule of ghf_decode_planes_range: indexes, or (h_infos, h_table_ptrs, h_table_bytes) with the
+ * seek-table images in DEVICE memory.  h_rank_infos / h_rank_ptrs (HOST [elem_bytes]): the parsed rank table of every
+ * sparse plane and its image in HOST memory; entries of dense planes are not looked at, and both may be NULL when
+ * sparse_planes is 0 -- the call is then ghf_decode_planes_range on the same images.
+ * THE PLAN with a sparse plane: the common origin is from = first - first % 32768; b0 = from / 32768, b1 = ceil((first
+ * + count) / 32768).  A dense plane is decoded from `from` as ghf_decode_planes_range does it.  A sparse plane reads
+ * v_lo = cum[b0] and v_hi = cum[b1] on the host, decodes mask bytes [4096 b0, min(4096 b1, mask bytes)) and, if v_hi >
+ * v_lo, values [v_lo - v_lo % 4096, v_hi) -- both begin on a seek block -- and ghf_sparse_merge_at (vals_skip = v_lo %
+ * 4096, n_vals = v_hi - v_lo, n = min(32768 b1, n_elems) - from) writes the plane into the plane workspace: its count
+ * check holds v_hi - v_lo, not the entries themselves, against the mask.  ghf_planes_merge_range comes last and stores nothing behind a
+ * latched status.  At most 32767 elements per plane are decoded in front of the range and 32767 behind it.  From seek
+ * tables ONE launch expands the covered blocks of all stored streams.
+ * Checked before anything is queued, in the order of ghf_decode_planes_range (with n_elems the argument), then:
+ * GHF_SPARSE_AUTO or a bit at or above elem_bytes, a null rank pointer of a sparse plane, a rank info whose n is not
+ * n_elems, a dense stream whose symbol count is not n_elems, a mask stream whose count is not ghf_sparse_mask_bytes of
+ * n_elems, a values stream whose count is not the rank table's n_vals (its pointers, index and table are checked like a
+ * plane's; the slot is ignored when n_vals == 0): GHF_E_INVAL; then count == 0: GHF_OK, nothing queued; then the two cum
+ * entries read not ordered, above n_vals, or further apart than the sub-string has elements: GHF_E_FORMAT. */
+int ghf_decode_planes_sparse_range(ghf_ctx* ctx, const uint8_t* const* h_stream_ptrs /* [2 * elem_bytes] */,
+                                   const size_t* h_stream_bytes /* [2 * elem_bytes] */, const ghf_code* d_codes /* [2 * elem_bytes] */,
+                                   const ghf_index* indexes /* [2 * elem_bytes] or NULL */,
+                                   const ghf_seek_info* h_infos /* [2 * elem_bytes] or NULL */,
+                                   const uint8_t* const* h_table_ptrs /* [2 * elem_bytes] or NULL */,
+                                   const size_t* h_table_bytes /* [2 * elem_bytes] or NULL */,
+                                   const ghf_sparse_rank_info* h_rank_infos /* [elem_bytes] */,
+                                   const uint8_t* const* h_rank_ptrs /* [elem_bytes] */, unsigned sparse_planes, size_t n_elems,
+                                   uint32_t elem_bytes, uint64_t first, uint64_t count, uint8_t* d_out, size_t cap);
+
+/* No reference counterpart: Decompressor::decompress(), include/compressor.h:87-92, for a part of a typed tensor stored
+ * sparse against a base.  The call above with ghf_planes_merge_range_delta last: d_base[0 .. count * elem_bytes) holds
+ * the caller's shard of the base, indexed like d_out, and d_base == d_out is allowed; behind a latched status d_out then
+ * still holds the base. */
+int ghf_decode_planes_sparse_range_delta(ghf_ctx* ctx, const uint8_t* const* h_stream_ptrs /* [2 * elem_bytes] */,
+                                         const size_t* h_stream_bytes /* [2 * elem_bytes] */,
+                                         const ghf_code* d_codes /* [2 * elem_bytes] */,
+                                         const ghf_index* indexes /* [2 * elem_bytes] or NULL */,
+                                         const ghf_seek_info* h_infos /* [2 * elem_bytes] or NULL */,
+                                         const uint8_t* const* h_table_ptrs /* [2 * elem_bytes] or NULL */,
+                                         const size_t* h_table_bytes /* [2 * elem_bytes] or NULL */,
+                                         const ghf_sparse_rank_info* h_rank_infos /* [elem_bytes] */,
+                                         const uint8_t* const* h_rank_ptrs /* [elem_bytes] */, const uint8_t* d_base,
+                                         unsigned sparse_planes, size_t n_elems, uint32_t elem_bytes, uint64_t first, uint64_t count,
+                                         uint8_t* d_out, size_t cap);
+
 /* ---- zero-suppressed byte planes: sparse split / merge, compress, decode --------
  * No symbol of a Huffman code costs less than one bit, so a byte plane of nothing but zeros -- the high planes of
  * `new ^ base` in a series of tensors, a frozen layer -- still stores n / 8 bytes.  THE SPARSE FORM of a byte string
