@@ -8,6 +8,7 @@ NSYM = 257
 EMIT_LAST = 1
 EMIT_REBASE = 2
 EMIT_HEADER = 4
+EMIT_LONG_CODES = 8  # GHF_EMIT_LONG_CODES: the tables may hold codes of 33..64 bits (a .crs tree deeper than 32)
 INDEX_NO_END_MARK = 1
 CODE_LIMIT = 1
 BATCH_MAX_ITEM = 1 << 20  # GHF_BATCH_MAX_ITEM: the largest item of ghf_compress_batch / ghf_decode_batch

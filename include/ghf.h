@@ -980,7 +980,10 @@ int ghf_crs_parse_header(const uint8_t* h_stream, size_t n, ghf_tree* tree, size
  * d_stream / stream_bytes: the .crs image from its first byte, with -- when left_bits != 0 -- the stored last byte
  * appended behind the body (so that the code bits are contiguous); stream_bytes counts that byte.
  * index == NULL: the side-car is rebuilt on the GPU (K6) and the stream must end exactly on a code boundary,
- * left_bits bits before its last byte ends. */
+ * left_bits bits before its last byte ends.
+ * Errors are latched as for ghf_decode: behind GHF_E_FORMAT (a malformed d_tree) nothing is written; GHF_E_CORRUPT from a
+ * segment that does not end where the side-car says is found behind that segment's stores, so d_out[0 .. n_symbols) may
+ * hold decoded bytes then (never a byte behind them).  GHF_E_CORRUPT from K6 comes before anything is decoded. */
 int ghf_crs_decode(ghf_ctx* ctx, const uint8_t* d_stream, size_t stream_bytes, int left_bits, const ghf_tree* d_tree,
                    const ghf_index* index, uint8_t* d_out, size_t cap, uint64_t* d_out_bytes);
 int ghf_crs_decoded_size(ghf_ctx* ctx, const uint8_t* d_stream, size_t stream_bytes, int left_bits, const ghf_tree* d_tree,

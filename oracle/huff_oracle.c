@@ -520,6 +520,28 @@ int orc_crs_decompress(const uint8_t* in, size_t n, uint8_t* out, size_t cap, si
   return 0;
 }
 
+/* decode_byte's walk (include/huff_tree.cc:255-271) over a bit range of a body, for the pieces of tests/crs_sweep.py: a code
+ * is taken if it STARTS in [from, to); it may end behind `to`, not behind nbits */
+long orc_crs_walk(const orc_tree* t, const uint8_t* body, uint64_t nbits, uint64_t from, uint64_t to, uint8_t* out, size_t cap,
+                  uint64_t* next) {
+  long n = 0;
+  uint64_t pos = from;
+  while (pos < to) {
+    int cur = t->root;
+    uint64_t p = pos;
+    while (t->left[cur] >= 0) {
+      if (p >= nbits) return -1;
+      cur = ((body[p >> 3] >> (7 - (p & 7))) & 1) ? t->right[cur] : t->left[cur];
+      p++;
+    }
+    if ((size_t)n >= cap) return -2;
+    out[n++] = (uint8_t)cur;
+    pos = p;
+  }
+  *next = pos;
+  return n;
+}
+
 /* ================================================================== SURVEY 8(f) N4: length-limited codes (opt-in)
  * NOT a restatement of the reference: include/canonical_huff_encoder.h:43-44 simply cannot represent a code longer
  * than 32 bits, so on such inputs the reference is undefined.  This is the definition libghf.so's opt-in

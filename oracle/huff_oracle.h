@@ -90,6 +90,11 @@ size_t orc_crs_parse_tree(const uint8_t* in, size_t n, orc_tree* t);
 size_t orc_crs_bound(size_t n);
 int orc_crs_compress(const uint8_t* in, size_t n, uint8_t* out, size_t cap, size_t* out_n);
 int orc_crs_decompress(const uint8_t* in, size_t n, uint8_t* out, size_t cap, size_t* out_n);
+/* decode under a given tree (tests/crs_sweep.py: one piece of a body): the codes that start in bits [from, to) of `body`
+ * (MSB first, `nbits` bits of it exist).  returns their number, -1 if one of them runs past nbits, -2 if out is too small;
+ * *next <- the bit behind the last of them (from, if there is none) */
+long orc_crs_walk(const orc_tree* t, const uint8_t* body, uint64_t nbits, uint64_t from, uint64_t to, uint8_t* out, size_t cap,
+                  uint64_t* next);
 
 /* ---------------------------------------------------------------- opt-in length limit (not reference behaviour) */
 int orc_limit_lengths(const int64_t hist[ORC_NSYM], uint32_t length[ORC_NSYM], int limit);

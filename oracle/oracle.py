@@ -114,6 +114,8 @@ def lib():
         L.orc_crs_compress.restype = C.c_int
         L.orc_crs_decompress.argtypes = [u8p, C.c_size_t, u8p, C.c_size_t, C.POINTER(C.c_size_t)]
         L.orc_crs_decompress.restype = C.c_int
+        L.orc_crs_walk.argtypes = [C.POINTER(OrcTree), u8p, C.c_uint64, C.c_uint64, C.c_uint64, u8p, C.c_size_t, C.POINTER(C.c_uint64)]
+        L.orc_crs_walk.restype = C.c_long
         _lib = L
     return _lib
 
@@ -266,6 +268,25 @@ def crs_decompress(crs, cap=None):
     if rc:
         raise ValueError("orc_crs_decompress rc=%d" % rc)
     return out[: n.value].copy()
+
+
+def crs_parse_tree(header):
+    """the tree of a preorder header (the restatement of DecodeHuffTree::do_build_tree) -> OrcTree"""
+    a, p = _u8(header)
+    t = OrcTree()
+    if lib().orc_crs_parse_tree(p, a.size, C.byref(t)) != a.size:
+        raise ValueError("bad .crs tree")
+    return t
+
+
+def crs_walk(tree, body, nbits, start, end, out):
+    """the codes that start in bits [start, end) of `body` under `tree`, written to `out` -> (their number, the bit behind
+    the last one); raises if a code runs past nbits"""
+    nxt = C.c_uint64(0)
+    n = lib().orc_crs_walk(C.byref(tree), body.ctypes.data, nbits, start, end, out.ctypes.data, out.size, C.byref(nxt))
+    if n < 0:
+        raise ValueError("orc_crs_walk rc=%d" % n)
+    return n, nxt.value
 
 
 # ------------------------------------------------------------------ the compiled reference (build container only)
