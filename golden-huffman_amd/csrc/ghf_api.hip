@@ -106,7 +106,7 @@ int ghf_ctx_create(int device, ghf_ctx** out) {
   GHF_STEP(hipHostMalloc(&c->h, sizeof(Scalars), hipHostMallocDefault));
   GHF_STEP(hipMalloc(&c->d_planes_hist_acc, kPlanesHistAccWords * sizeof(uint64_t)));
   GHF_STEP(hipMemset(c->d_planes_hist_acc, 0, kPlanesHistAccWords * sizeof(uint64_t)));
-  GHF_STEP(hipMalloc(&c->d_planes_hists, (size_t)GHF_PLANES_MAX * GHF_NSYM * sizeof(uint64_t)));
+  GHF_STEP(hipMalloc(&c->d_planes_hists, ((size_t)GHF_PLANES_MAX * GHF_NSYM + GHF_PLANES_MAX) * sizeof(uint64_t)));
   GHF_STEP(hipMalloc(&c->d_sparse_counts, kSparseGroups * sizeof(uint64_t)));
   GHF_STEP(hipMalloc(&c->d_sparse_offs, kSparseOffWords * sizeof(uint64_t)));
   GHF_STEP(hipMemset(c->d_status, 0, sizeof(int)));
@@ -2039,6 +2039,14 @@ static inline bool sparse_planes_ok(unsigned sparse_planes, uint32_t elem_bytes,
   return (sparse_planes >> elem_bytes) == 0;
 }
 
+// raw_planes beside sparse_planes: GHF_RAW_AUTO alone where the call may choose, or bits below
+// elem_bytes; a plane has one form, so where both masks are explicit they share no bit
+static inline bool forms_ok(unsigned raw_planes, unsigned sparse_planes, uint32_t elem_bytes, bool may_be_auto) {
+  if (raw_planes == GHF_RAW_AUTO) return may_be_auto;
+  if ((raw_planes >> elem_bytes) != 0) return false;
+  return sparse_planes == GHF_SPARSE_AUTO || (raw_planes & sparse_planes) == 0;
+}
+
 // the context's second workspace for one sparse plane of n_elems bytes: the mask at [0, *mask_stride), the values behind it
 static int sparse_workspace(ghf_ctx* c, size_t n_elems, size_t* mask_stride) {
   *mask_stride = (ghf_sparse_mask_bytes(n_elems) + 255) & ~(size_t)255;
@@ -2175,15 +2183,21 @@ static int decode_stored(ghf_ctx* c, const std::string& f, const uint8_t* d_stre
 }
 
 static int decode_planes_sparse(ghf_ctx* c, const char* who, const uint8_t* const* h_stream_ptrs, const size_t* h_stream_bytes,
-                                const ghf_code* d_codes, const ghf_index* indexes, Base base, unsigned sparse_planes, const size_t* h_n_vals,
-                                size_t n_elems, uint32_t elem_bytes, uint8_t* d_out, size_t cap, uint64_t* d_out_bytes) {
-  if (!c || !h_stream_ptrs || !h_stream_bytes || !d_codes || !d_out || !h_n_vals || base.null()) return GHF_E_INVAL;
+                                const ghf_code* d_codes, const ghf_index* indexes, Base base, unsigned raw_planes, unsigned sparse_planes,
+                                const size_t* h_n_vals, size_t n_elems, uint32_t elem_bytes, uint8_t* d_out, size_t cap,
+                                uint64_t* d_out_bytes) {
+  // the codes of raw planes are not looked at: a tensor of nothing but raw planes needs none
+  const bool all_raw = elem_bytes_ok(elem_bytes) && raw_planes == (1u << elem_bytes) - 1u;
+  if (!c || !h_stream_ptrs || !h_stream_bytes || (!d_codes && !all_raw) || !d_out || !h_n_vals || base.null()) return GHF_E_INVAL;
   const std::string f = std::string(who) + ": ";
   if (!elem_bytes_ok(elem_bytes)) return fail(c, GHF_E_INVAL, (f + "elem_bytes must be 2, 4 or 8").c_str());
   const uint32_t E = elem_bytes;
   if (!sparse_planes_ok(sparse_planes, E, false))
     return fail(c, GHF_E_INVAL, (f + "sparse_planes has bits below elem_bytes only (the mask the compress call reported)").c_str());
+  if (!forms_ok(raw_planes, sparse_planes, E, false))
+    return fail(c, GHF_E_INVAL, (f + "raw_planes has bits below elem_bytes only, none of them a sparse plane's").c_str());
   const size_t mask_bytes = ghf_sparse_mask_bytes(n_elems);
+  auto raw = [&](uint32_t p) { return ((raw_planes >> p) & 1u) != 0; };
   // slot j is stored when it is a plane's own slot, or the values slot of a sparse plane that has values
   auto symbols_of = [&](uint32_t j) -> size_t {
     const uint32_t p = j % E;
@@ -2199,16 +2213,19 @@ static int decode_planes_sparse(ghf_ctx* c, const char* who, const uint8_t* cons
   if (!aligned16(d_out) || base.misaligned()) return fail(c, GHF_E_INVAL, (f + "d_out and d_base must be 16-byte aligned").c_str());
   if (workspace_overflow(n_elems, E)) return fail(c, GHF_E_INVAL, (f + "n_elems * elem_bytes overflows").c_str());
   for (uint32_t j = 0; indexes && j < 2 * E; ++j)
-    if ((j < E || symbols_of(j)) && (indexes[j].n_symbols != symbols_of(j) || !index_is_whole(&indexes[j])))
+    if ((j < E || symbols_of(j)) && !raw(j % E) && (indexes[j].n_symbols != symbols_of(j) || !index_is_whole(&indexes[j])))
       return fail(c, GHF_E_INVAL, (f + "an index does not cover exactly the symbols of its stream").c_str());
+  for (uint32_t p = 0; p < E; ++p)  // a raw plane is its n_elems bytes and nothing else
+    if (raw(p) && h_stream_bytes[p] != n_elems) return fail(c, GHF_E_INVAL, (f + "a raw plane does not have n_elems bytes").c_str());
   if (n_elems == 0) return fail(c, GHF_E_EMPTY, (f + "no elements").c_str());
   if (cap < n_elems * E) return fail(c, GHF_E_CAP, (f + "output capacity below n_elems * elem_bytes").c_str());
   GHF_HIP(c, hipSetDevice(c->device));
   size_t stride = 0, mask_stride = 0;
-  int rc = planes_workspace(c, n_elems, E, &stride);
+  int rc = all_raw ? GHF_OK : planes_workspace(c, n_elems, E, &stride);
   if (!rc && sparse_planes) rc = sparse_workspace(c, n_elems, &mask_stride);
   if (rc) return rc;
   for (uint32_t p = 0; p < E; ++p) {
+    if (raw(p)) continue;  // never copied: the merge reads it where it lies
     uint8_t* plane = c->planes.p + p * stride;
     if (!((sparse_planes >> p) & 1u)) {
       if ((rc = decode_stored(c, f, h_stream_ptrs[p], h_stream_bytes[p], d_codes + p, indexes ? indexes + p : nullptr, n_elems, plane, stride)))
@@ -2226,7 +2243,14 @@ static int decode_planes_sparse(ghf_ctx* c, const char* who, const uint8_t* cons
     launch_sparse_merge(d_mask, d_vals, h_n_vals[p], n_elems, plane, c->d_sparse_counts, c->d_sparse_offs, c->d_status, c->stream);
     GHF_HIP(c, hipGetLastError());
   }
-  launch_planes_merge(c->planes.p, stride, base.p, n_elems, E, d_out, c->d_status, c->stream);  // nothing is stored behind a latched status
+  // nothing is stored behind a latched status
+  if (!raw_planes) {
+    launch_planes_merge(c->planes.p, stride, base.p, n_elems, E, d_out, c->d_status, c->stream);
+  } else {
+    const uint8_t* from[GHF_PLANES_MAX];
+    for (uint32_t p = 0; p < E; ++p) from[p] = raw(p) ? h_stream_ptrs[p] : c->planes.p + p * stride;
+    launch_planes_merge_from(from, base.p, n_elems, E, d_out, c->d_status, c->stream);
+  }
   if (d_out_bytes) launch_store_u64(d_out_bytes, nullptr, (uint64_t)n_elems * E, c->stream);
   GHF_HIP(c, hipGetLastError());
   return GHF_OK;
@@ -2235,13 +2259,13 @@ static int decode_planes_sparse(ghf_ctx* c, const char* who, const uint8_t* cons
 int ghf_decode_planes_sparse(ghf_ctx* c, const uint8_t* const* h_stream_ptrs, const size_t* h_stream_bytes, const ghf_code* d_codes,
                              const ghf_index* indexes, unsigned sparse_planes, const size_t* h_n_vals, size_t n_elems, uint32_t elem_bytes,
                              uint8_t* d_out, size_t cap, uint64_t* d_out_bytes) {
-  return decode_planes_sparse(c, "ghf_decode_planes_sparse", h_stream_ptrs, h_stream_bytes, d_codes, indexes, no_base(), sparse_planes,
+  return decode_planes_sparse(c, "ghf_decode_planes_sparse", h_stream_ptrs, h_stream_bytes, d_codes, indexes, no_base(), 0, sparse_planes,
                               h_n_vals, n_elems, elem_bytes, d_out, cap, d_out_bytes);
 }
 int ghf_decode_planes_sparse_delta(ghf_ctx* c, const uint8_t* const* h_stream_ptrs, const size_t* h_stream_bytes, const ghf_code* d_codes,
                                    const ghf_index* indexes, const uint8_t* d_base, unsigned sparse_planes, const size_t* h_n_vals,
                                    size_t n_elems, uint32_t elem_bytes, uint8_t* d_out, size_t cap, uint64_t* d_out_bytes) {
-  return decode_planes_sparse(c, "ghf_decode_planes_sparse_delta", h_stream_ptrs, h_stream_bytes, d_codes, indexes, base_of(d_base),
+  return decode_planes_sparse(c, "ghf_decode_planes_sparse_delta", h_stream_ptrs, h_stream_bytes, d_codes, indexes, base_of(d_base), 0,
                               sparse_planes, h_n_vals, n_elems, elem_bytes, d_out, cap, d_out_bytes);
 }
 
@@ -2331,18 +2355,22 @@ static int decode_planes_sparse_range(ghf_ctx* c, const char* who, const uint8_t
                                       const ghf_code* d_codes, const ghf_index* indexes, const ghf_seek_info* h_infos,
                                       const uint8_t* const* h_table_ptrs, const size_t* h_table_bytes,
                                       const ghf_sparse_rank_info* h_rank_infos, const uint8_t* const* h_rank_ptrs, Base base,
-                                      unsigned sparse_planes, size_t n_elems, uint32_t elem_bytes, uint64_t first, uint64_t count,
-                                      uint8_t* d_out, size_t cap) {
-  if (!c || !h_stream_ptrs || !h_stream_bytes || !d_codes || !d_out || base.null()) return GHF_E_INVAL;
+                                      unsigned raw_planes, unsigned sparse_planes, size_t n_elems, uint32_t elem_bytes, uint64_t first,
+                                      uint64_t count, uint8_t* d_out, size_t cap) {
+  // the codes of raw planes are not looked at: a tensor of nothing but raw planes needs none
+  const bool all_raw = elem_bytes_ok(elem_bytes) && raw_planes == (1u << elem_bytes) - 1u;
+  if (!c || !h_stream_ptrs || !h_stream_bytes || (!d_codes && !all_raw) || !d_out || base.null()) return GHF_E_INVAL;
   const std::string f = std::string(who) + ": ";
   if (!elem_bytes_ok(elem_bytes)) return fail(c, GHF_E_INVAL, (f + "elem_bytes must be 2, 4 or 8").c_str());
   const uint32_t E = elem_bytes;
   const bool by_table = h_infos || h_table_ptrs || h_table_bytes;
   if ((indexes != nullptr) == by_table || (by_table && !(h_infos && h_table_ptrs && h_table_bytes)))
     return fail(c, GHF_E_INVAL, (f + "exactly one of indexes / (h_infos, h_table_ptrs, h_table_bytes) must be given").c_str());
+  // a raw plane has a stream pointer and a size and nothing else: its index, info and table are not read
+  auto raw = [&](uint32_t p) { return ((raw_planes >> p) & 1u) != 0; };
   // what ghf_decode_planes_range asks of a plane, of one stored stream
   auto pointers_ok = [&](uint32_t j) {
-    return h_stream_ptrs[j] && aligned16(h_stream_ptrs[j]) && (!by_table || (h_table_ptrs[j] && aligned16(h_table_ptrs[j])));
+    return h_stream_ptrs[j] && aligned16(h_stream_ptrs[j]) && (!by_table || raw(j) || (h_table_ptrs[j] && aligned16(h_table_ptrs[j])));
   };
   auto symbols_of = [&](uint32_t j) -> uint64_t { return by_table ? h_infos[j].n_symbols : indexes[j].n_symbols; };
   auto index_ok = [&](uint32_t j) { return by_table || indexes[j].n_symbols == 0 || index_is_whole(&indexes[j]); };
@@ -2350,13 +2378,14 @@ static int decode_planes_sparse_range(ghf_ctx* c, const char* who, const uint8_t
     if (!pointers_ok(p)) return fail(c, GHF_E_INVAL, (f + "a stream or table pointer is null or not 16-byte aligned").c_str());
   if (!aligned16(d_out) || base.misaligned()) return fail(c, GHF_E_INVAL, (f + "d_out and d_base must be 16-byte aligned").c_str());
   for (uint32_t p = 0; p < E; ++p)
-    if (!index_ok(p)) return fail(c, GHF_E_INVAL, (f + "malformed index").c_str());
+    if (!raw(p) && !index_ok(p)) return fail(c, GHF_E_INVAL, (f + "malformed index").c_str());
   if (first > n_elems || count > n_elems - first) return fail(c, GHF_E_INVAL, (f + "first + count exceeds n_elems").c_str());
   // the workspace holds the range from the start of its first rank block to the end of its last, and a vector more
   const size_t slack = 2 * (size_t)kSparseRankElems + 16;
   if (count > (size_t)-1 - slack || workspace_overflow((size_t)count + slack, E))
     return fail(c, GHF_E_INVAL, (f + "count * elem_bytes overflows").c_str());
   for (uint32_t p = 0; by_table && p < E; ++p) {
+    if (raw(p)) continue;
     const int rc = seek_table_ok(c, who, h_infos + p, h_table_ptrs[p], h_table_bytes[p]);
     if (rc) return rc;
   }
@@ -2364,6 +2393,11 @@ static int decode_planes_sparse_range(ghf_ctx* c, const char* who, const uint8_t
   // ... and what the sparse form adds
   if (!sparse_planes_ok(sparse_planes, E, false))
     return fail(c, GHF_E_INVAL, (f + "sparse_planes has bits below elem_bytes only (the mask the compress call reported)").c_str());
+  // ... and the raw form
+  if (!forms_ok(raw_planes, sparse_planes, E, false))
+    return fail(c, GHF_E_INVAL, (f + "raw_planes has bits below elem_bytes only, none of them a sparse plane's").c_str());
+  for (uint32_t p = 0; p < E; ++p)
+    if (raw(p) && h_stream_bytes[p] != n_elems) return fail(c, GHF_E_INVAL, (f + "a raw plane does not have n_elems bytes").c_str());
   if (sparse_planes && (!h_rank_infos || !h_rank_ptrs)) return fail(c, GHF_E_INVAL, (f + "sparse planes need their rank tables").c_str());
   const uint64_t mask_bytes = ghf_sparse_mask_bytes(n_elems);
   for (uint32_t p = 0; p < E; ++p) {
@@ -2374,6 +2408,7 @@ static int decode_planes_sparse_range(ghf_ctx* c, const char* who, const uint8_t
       return fail(c, GHF_E_FORMAT, (f + "a rank info is not what ghf_sparse_rank_parse fills in").c_str());
   }
   for (uint32_t p = 0; p < E; ++p) {
+    if (raw(p)) continue;
     const bool sparse = (sparse_planes >> p) & 1u;
     if (symbols_of(p) != (sparse ? mask_bytes : (uint64_t)n_elems))
       return fail(c, GHF_E_INVAL, sparse ? (f + "a mask stream does not have ghf_sparse_mask_bytes(n_elems) symbols").c_str()
@@ -2389,15 +2424,18 @@ static int decode_planes_sparse_range(ghf_ctx* c, const char* who, const uint8_t
     }
   }
   if (count == 0) return GHF_OK;
-  if (!sparse_planes)  // nothing sparse: the origin of section 17, and its call
+  if (!sparse_planes && !raw_planes)  // nothing sparse: the origin of section 17, and its call
     return decode_planes_range(c, who, h_stream_ptrs, h_stream_bytes, d_codes, indexes, h_infos, h_table_ptrs, h_table_bytes, base, E, first,
                                count, d_out, cap);
   // THE PLAN.  The common origin of all planes is the start of the rank block that holds `first`: a multiple of 4096 for a
   // dense plane, of 4096 mask bytes for a mask, and the values in front of it number cum[b0].  A sparse plane is rebuilt for the
   // whole rank blocks [b0, b1) (cut at n_elems): the sub-string's mask bytes are whole, so its last mask byte obeys the pad rule.
-  const uint64_t from = first - first % kSparseRankElems, end = first + count;
+  // With raw planes and no sparse one the origin is section 17's, the start of the seek block that holds `first`.  A raw plane has
+  // no part in the plan: nothing of it is decoded or copied, the merge reads it at stream + first.
+  const uint64_t origin = sparse_planes ? kSparseRankElems : kBlockSymbols;
+  const uint64_t from = first - first % origin, end = first + count;
   const uint64_t b0 = from / kSparseRankElems, b1 = rank_blocks_for(end);
-  const uint64_t sub_n = std::min<uint64_t>(b1 * kSparseRankElems, n_elems) - from;
+  const uint64_t sub_n = (sparse_planes ? std::min<uint64_t>(b1 * kSparseRankElems, n_elems) : end) - from;
   const uint64_t m_lo = b0 * (kSparseRankElems / 8), m_hi = std::min<uint64_t>(b1 * (kSparseRankElems / 8), mask_bytes);
   uint64_t v_lo[GHF_PLANES_MAX] = {}, v_hi[GHF_PLANES_MAX] = {};
   for (uint32_t p = 0; p < E; ++p) {
@@ -2410,16 +2448,17 @@ static int decode_planes_sparse_range(ghf_ctx* c, const char* who, const uint8_t
   }
   GHF_HIP(c, hipSetDevice(c->device));
   size_t stride = 0;
-  int rc = planes_workspace(c, (size_t)sub_n + 16, E, &stride);
+  int rc = all_raw ? GHF_OK : planes_workspace(c, (size_t)sub_n + 16, E, &stride);
   // the second workspace: the sub-string's mask, and behind it its values from the start of their first seek block
   const size_t mask_stride = ((size_t)(m_hi - m_lo) + 255) & ~(size_t)255;
   const size_t vals_room = ((size_t)sub_n + kBlockSymbols + 255) & ~(size_t)255;
-  if (!rc) rc = grow(c, c->sparse, mask_stride + vals_room);
+  if (!rc && sparse_planes) rc = grow(c, c->sparse, mask_stride + vals_room);
   if (rc) return rc;
   uint8_t *d_mask = c->sparse.p, *d_vals = c->sparse.p + mask_stride;
   RangePart parts[2 * GHF_PLANES_MAX];
   uint32_t n_parts = 0;
   for (uint32_t p = 0; p < E; ++p) {
+    if (raw(p)) continue;
     if (!((sparse_planes >> p) & 1u)) {
       parts[n_parts++] = {p, from, end, n_elems, c->planes.p + p * stride, stride};
       continue;
@@ -2434,7 +2473,9 @@ static int decode_planes_sparse_range(ghf_ctx* c, const char* who, const uint8_t
       launch_sparse_merge_at(d_mask, d_vals, v_lo[p] % kBlockSymbols, v_hi[p] - v_lo[p], sub_n, c->planes.p + p * stride, c->d_sparse_counts,
                              c->d_sparse_offs, c->d_status, c->stream);
   };
-  if (by_table) {
+  if (!n_parts) {
+    // every plane is raw: the merge below is the whole call
+  } else if (by_table) {
     // One launch expands the covered blocks of every stored stream (k_seek_expand_streams): expanding each by itself would
     // pay k_seek_expand's latency floor up to 2 E times (DESIGN.md section 17 has the measurement).  Every stream gets tables of
     // its own, alive until its K7 has run.
@@ -2494,7 +2535,15 @@ static int decode_planes_sparse_range(ghf_ctx* c, const char* who, const uint8_t
     }
   }
   // nothing reaches d_out behind a failed decode or a count that does not match the rank table
-  launch_planes_merge_range(c->planes.p, stride, base.p, first - from, count, E, d_out, c->d_status, c->stream);
+  if (!raw_planes) {
+    launch_planes_merge_range(c->planes.p, stride, base.p, first - from, count, E, d_out, c->d_status, c->stream);
+  } else {
+    // the workspace planes start 256-byte aligned at element `from`, a multiple of 4096, and a raw plane 16-byte aligned at
+    // element 0: the run's first byte stands first % 16 behind a vector in every one of them
+    const uint8_t* src[GHF_PLANES_MAX];
+    for (uint32_t p = 0; p < E; ++p) src[p] = raw(p) ? h_stream_ptrs[p] + first : c->planes.p + p * stride + (first - from);
+    launch_planes_merge_from(src, base.p, count, E, d_out, c->d_status, c->stream);
+  }
   GHF_HIP(c, hipGetLastError());
   return GHF_OK;
 }
@@ -2505,8 +2554,8 @@ int ghf_decode_planes_sparse_range(ghf_ctx* c, const uint8_t* const* h_stream_pt
                                    unsigned sparse_planes, size_t n_elems, uint32_t elem_bytes, uint64_t first, uint64_t count, uint8_t* d_out,
                                    size_t cap) {
   return decode_planes_sparse_range(c, "ghf_decode_planes_sparse_range", h_stream_ptrs, h_stream_bytes, d_codes, indexes, h_infos, h_table_ptrs,
-                                    h_table_bytes, h_rank_infos, h_rank_ptrs, no_base(), sparse_planes, n_elems, elem_bytes, first, count, d_out,
-                                    cap);
+                                    h_table_bytes, h_rank_infos, h_rank_ptrs, no_base(), 0, sparse_planes, n_elems, elem_bytes, first, count,
+                                    d_out, cap);
 }
 int ghf_decode_planes_sparse_range_delta(ghf_ctx* c, const uint8_t* const* h_stream_ptrs, const size_t* h_stream_bytes, const ghf_code* d_codes,
                                          const ghf_index* indexes, const ghf_seek_info* h_infos, const uint8_t* const* h_table_ptrs,
@@ -2514,8 +2563,215 @@ int ghf_decode_planes_sparse_range_delta(ghf_ctx* c, const uint8_t* const* h_str
                                          const uint8_t* const* h_rank_ptrs, const uint8_t* d_base, unsigned sparse_planes, size_t n_elems,
                                          uint32_t elem_bytes, uint64_t first, uint64_t count, uint8_t* d_out, size_t cap) {
   return decode_planes_sparse_range(c, "ghf_decode_planes_sparse_range_delta", h_stream_ptrs, h_stream_bytes, d_codes, indexes, h_infos,
-                                    h_table_ptrs, h_table_bytes, h_rank_infos, h_rank_ptrs, base_of(d_base), sparse_planes, n_elems, elem_bytes,
-                                    first, count, d_out, cap);
+                                    h_table_ptrs, h_table_bytes, h_rank_infos, h_rank_ptrs, base_of(d_base), 0, sparse_planes, n_elems,
+                                    elem_bytes, first, count, d_out, cap);
+}
+
+// ---------------------------------------------------------------------------------------------- byte planes in three forms
+// (no reference counterpart).  In this family d_base is optional: null is the plain call
+static inline Base base_opt(const uint8_t* d_base) { return d_base ? base_of(d_base) : no_base(); }
+
+// what the three pointer calls check alike: `d_inter` is the interleaved side, `h_ptrs` the host array of plane addresses;
+// *skew <- their common address mod 16 (the split wants 0)
+static int plane_ptrs_args(ghf_ctx* c, const char* who, const uint8_t* d_inter, const uint8_t* const* h_ptrs, const uint8_t* d_base,
+                           size_t n_elems, uint32_t elem_bytes, uint32_t* skew) {
+  if (!c || !d_inter || !h_ptrs) return GHF_E_INVAL;
+  const std::string f = std::string(who) + ": ";
+  if (!elem_bytes_ok(elem_bytes)) return fail(c, GHF_E_INVAL, (f + "elem_bytes must be 2, 4 or 8").c_str());
+  for (uint32_t p = 0; p < elem_bytes; ++p)
+    if (!h_ptrs[p]) return fail(c, GHF_E_INVAL, (f + "a plane pointer is null").c_str());
+  *skew = (uint32_t)(reinterpret_cast<uintptr_t>(h_ptrs[0]) & 15u);
+  for (uint32_t p = 1; p < elem_bytes; ++p)
+    if ((reinterpret_cast<uintptr_t>(h_ptrs[p]) & 15u) != *skew)
+      return fail(c, GHF_E_INVAL, (f + "the plane pointers do not have the same address modulo 16").c_str());
+  if (!aligned16(d_inter) || !aligned16(d_base)) return fail(c, GHF_E_INVAL, (f + "d_in / d_out and d_base must be 16-byte aligned").c_str());
+  if (elems_overflow(n_elems, elem_bytes)) return fail(c, GHF_E_INVAL, (f + "n_elems * elem_bytes overflows").c_str());
+  if (n_elems == 0) return fail(c, GHF_E_EMPTY, (f + "no elements").c_str());
+  return GHF_OK;
+}
+
+int ghf_planes_split_to(ghf_ctx* c, const uint8_t* d_in, const uint8_t* d_base, size_t n_elems, uint32_t elem_bytes,
+                        uint8_t* const* h_plane_ptrs) {
+  uint32_t skew = 0;
+  const int rc = plane_ptrs_args(c, "ghf_planes_split_to", d_in, h_plane_ptrs, d_base, n_elems, elem_bytes, &skew);
+  if (rc) return rc;
+  if (skew) return fail(c, GHF_E_INVAL, "ghf_planes_split_to: the plane pointers must be 16-byte aligned");
+  GHF_HIP(c, hipSetDevice(c->device));
+  launch_planes_split_to(d_in, d_base, n_elems, elem_bytes, h_plane_ptrs, c->stream);
+  GHF_HIP(c, hipGetLastError());
+  return GHF_OK;
+}
+
+int ghf_planes_merge_from(ghf_ctx* c, const uint8_t* const* h_plane_ptrs, const uint8_t* d_base, size_t n_elems, uint32_t elem_bytes,
+                          uint8_t* d_out) {
+  uint32_t skew = 0;
+  const int rc = plane_ptrs_args(c, "ghf_planes_merge_from", d_out, h_plane_ptrs, d_base, n_elems, elem_bytes, &skew);
+  if (rc) return rc;
+  if (skew) return fail(c, GHF_E_INVAL, "ghf_planes_merge_from: the plane pointers must be 16-byte aligned");
+  GHF_HIP(c, hipSetDevice(c->device));
+  launch_planes_merge_from(h_plane_ptrs, d_base, n_elems, elem_bytes, d_out, nullptr, c->stream);
+  GHF_HIP(c, hipGetLastError());
+  return GHF_OK;
+}
+
+int ghf_planes_merge_range_from(ghf_ctx* c, const uint8_t* const* h_plane_ptrs, const uint8_t* d_base, size_t count, uint32_t elem_bytes,
+                                uint8_t* d_out) {
+  uint32_t skew = 0;
+  const int rc = plane_ptrs_args(c, "ghf_planes_merge_range_from", d_out, h_plane_ptrs, d_base, count, elem_bytes, &skew);
+  if (rc) return rc;
+  GHF_HIP(c, hipSetDevice(c->device));
+  launch_planes_merge_from(h_plane_ptrs, d_base, count, elem_bytes, d_out, nullptr, c->stream);  // the common skew picks the kernel
+  GHF_HIP(c, hipGetLastError());
+  return GHF_OK;
+}
+
+int ghf_compress_planes_forms(ghf_ctx* c, const uint8_t* d_in, const uint8_t* d_base, size_t n_elems, uint32_t elem_bytes,
+                              unsigned raw_planes, unsigned sparse_planes, uint8_t* d_out, size_t slot_bytes, uint64_t* d_out_bytes,
+                              ghf_code* d_codes, ghf_index* h_indexes, uint8_t* d_ranks, size_t rank_slot_bytes, unsigned* h_raw_planes,
+                              unsigned* h_sparse_planes, size_t* h_n_vals) {
+  if (!c || !d_in || !d_out || !d_out_bytes || !h_raw_planes || !h_sparse_planes || !h_n_vals) return GHF_E_INVAL;
+  const char* f = "ghf_compress_planes_forms: ";
+  auto say = [&](const char* what) { return std::string(f) + what; };
+  if (!elem_bytes_ok(elem_bytes)) return fail(c, GHF_E_INVAL, say("elem_bytes must be 2, 4 or 8").c_str());
+  const uint32_t E = elem_bytes;
+  if (!aligned16(d_in) || !aligned16(d_out) || (slot_bytes & 15u) || !aligned16(d_codes) || !aligned16(d_base))
+    return fail(c, GHF_E_INVAL, say("d_in, d_base, d_out, d_codes and slot_bytes must be multiples of 16").c_str());
+  if (d_ranks && (!aligned16(d_ranks) || (rank_slot_bytes & 15u)))
+    return fail(c, GHF_E_INVAL, say("d_ranks and rank_slot_bytes must be multiples of 16").c_str());
+  if (!sparse_planes_ok(sparse_planes, E, true))
+    return fail(c, GHF_E_INVAL, say("sparse_planes is GHF_SPARSE_AUTO alone or has bits below elem_bytes only").c_str());
+  if (!forms_ok(raw_planes, sparse_planes, E, true))
+    return fail(c, GHF_E_INVAL, say("raw_planes is GHF_RAW_AUTO alone or has bits below elem_bytes only, none of them a sparse plane's").c_str());
+  if (workspace_overflow(n_elems, E)) return fail(c, GHF_E_INVAL, say("n_elems * elem_bytes overflows").c_str());
+  if (n_elems == 0) return fail(c, GHF_E_EMPTY, say("no elements").c_str());
+  if (slot_bytes < ghf_planes_slot_bytes(n_elems)) return fail(c, GHF_E_CAP, say("slot_bytes below ghf_planes_slot_bytes(n_elems)").c_str());
+  if (d_ranks && rank_slot_bytes < ghf_sparse_rank_bytes(n_elems))
+    return fail(c, GHF_E_CAP, say("rank_slot_bytes below ghf_sparse_rank_bytes(n_elems)").c_str());
+  GHF_HIP(c, hipSetDevice(c->device));
+  const bool raw_auto = raw_planes == GHF_RAW_AUTO, sparse_auto = sparse_planes == GHF_SPARSE_AUTO;
+  const unsigned all = (1u << E) - 1u;
+  // the counts are needed on the HOST for a choice and for the value counts of sparse planes, on the device for every code
+  const bool wait = raw_auto || sparse_auto || sparse_planes != 0;
+  int rc = GHF_OK;
+  // [0, 2 MAX): the codes of the stored streams when the caller wants none; [2 MAX, 3 MAX): the codes the choice is priced with
+  if ((rc = grow(c, c->batch_codes, 3 * GHF_PLANES_MAX))) return rc;
+  ghf_code* codes = d_codes ? d_codes : c->batch_codes.p;
+  ghf_code* priced = c->batch_codes.p + 2 * GHF_PLANES_MAX;
+  uint64_t* d_prices = c->d_planes_hists + (size_t)GHF_PLANES_MAX * GHF_NSYM;
+  if (wait || raw_planes != all)
+    if ((rc = histogram_planes_into(c, say("histogram launch").c_str(), d_in, d_base, n_elems, E, 0, c->d_planes_hists))) return rc;
+  unsigned raw_chosen = raw_auto ? 0u : raw_planes, sparse_chosen = sparse_auto ? 0u : sparse_planes;
+  std::memset(h_n_vals, 0, E * sizeof *h_n_vals);
+  if (wait) {
+    // THE ONE WAIT of the call.  With GHF_RAW_AUTO the codes of all planes and the sizes of their images are queued in front of
+    // it, and one copy brings the counts and the sizes back; the dense planes are then packed with those codes
+    if (raw_auto) {
+      if ((rc = ghf_build_codes(c, c->d_planes_hists, E, priced, 0))) return rc;
+      launch_planes_image_bytes(c->d_planes_hists, priced, E, d_prices, c->stream);
+      GHF_HIP(c, hipGetLastError());
+    }
+    uint64_t got[GHF_PLANES_MAX * GHF_NSYM + GHF_PLANES_MAX];
+    GHF_HIP(c, hipMemcpyAsync(got, c->d_planes_hists, sizeof got, hipMemcpyDeviceToHost, c->stream));
+    GHF_HIP(c, hipStreamSynchronize(c->stream));
+    const uint64_t* prices = got + (size_t)GHF_PLANES_MAX * GHF_NSYM;
+    // a sparse plane stores two headers: at or below that size the raw form is the smaller one whatever the plane holds
+    const bool sparse_pays = !raw_auto || n_elems > 2 * ghf_header_bytes(1);
+    for (uint32_t p = 0; p < E; ++p) {
+      const uint64_t zeros = got[(size_t)p * GHF_NSYM];
+      if (zeros > n_elems) return fail(c, GHF_E_HIP, say("the plane counts did not arrive").c_str());
+      h_n_vals[p] = n_elems - (size_t)zeros;
+      if (sparse_auto && !((raw_chosen >> p) & 1u) && sparse_pays && zeros >= n_elems - n_elems / 4) sparse_chosen |= 1u << p;
+      // prices[p] == 0: the plane has no code (a count at or above 2^55); it stays dense, and the dense path latches why
+      if (raw_auto && !((sparse_chosen >> p) & 1u) && prices[p] >= n_elems) raw_chosen |= 1u << p;
+    }
+  }
+  *h_raw_planes = raw_chosen;
+  *h_sparse_planes = sparse_chosen;
+  auto raw = [&](uint32_t p) { return ((raw_chosen >> p) & 1u) != 0; };
+  auto sparse = [&](uint32_t p) { return ((sparse_chosen >> p) & 1u) != 0; };
+  size_t stride = 0, mask_stride = 0;
+  if (raw_chosen != all) rc = planes_workspace(c, n_elems, E, &stride);
+  if (!rc && sparse_chosen) rc = sparse_workspace(c, n_elems, &mask_stride);
+  if (rc) return rc;
+  const size_t mask_bytes = ghf_sparse_mask_bytes(n_elems);
+  if (h_indexes) {  // one side-car per stream that has a code, of that stream's own symbol count; a raw plane has none
+    std::memset(h_indexes, 0, 2 * E * sizeof *h_indexes);
+    for (uint32_t p = 0; p < E && !rc; ++p) {
+      if (raw(p)) continue;
+      rc = ghf_index_alloc(c, sparse(p) ? mask_bytes : n_elems, &h_indexes[p]);
+      if (!rc && sparse(p) && h_n_vals[p]) rc = ghf_index_alloc(c, h_n_vals[p], &h_indexes[E + p]);
+    }
+    if (rc) {
+      free_indexes(c, h_indexes, 2 * E);
+      return rc;
+    }
+  }
+  GHF_HIP(c, hipMemsetAsync(d_out_bytes, 0, 2 * E * sizeof(uint64_t), c->stream));  // the empty slots
+  // the split writes a raw plane straight into its slot and every other plane into the workspace
+  if (!raw_chosen) {
+    launch_planes_split(d_in, d_base, n_elems, E, c->planes.p, stride, c->stream);
+  } else {
+    uint8_t* to[GHF_PLANES_MAX];
+    for (uint32_t p = 0; p < E; ++p) to[p] = raw(p) ? d_out + p * slot_bytes : c->planes.p + p * stride;
+    launch_planes_split_to(d_in, d_base, n_elems, E, to, c->stream);
+  }
+  GHF_HIP(c, hipGetLastError());
+  uint8_t *d_mask = c->sparse.p, *d_vals = c->sparse.p + mask_stride;
+  for (uint32_t p = 0; p < E && !rc; ++p) {
+    if (raw(p)) {
+      launch_store_u64(d_out_bytes + p, nullptr, (uint64_t)n_elems, c->stream);
+      GHF_HIP(c, hipGetLastError());
+      continue;
+    }
+    const uint8_t* plane = c->planes.p + p * stride;
+    // K1 has not seen what stands at these addresses now: the workspaces are refilled for every plane
+    c->hist.forget();
+    c->plan.forget();
+    if (!sparse(p)) {  // what ghf_compress_planes_coded(GHF_PLANES_BUILD_CODES) queues for the plane
+      const ghf_code* code = raw_auto ? priced + p : codes + p;
+      if (!raw_auto && (rc = ghf_build_codes(c, c->d_planes_hists + (size_t)p * GHF_NSYM, 1, codes + p, 0))) break;
+      if ((rc = ghf_encode_plan(c, plane, n_elems, code, &c->d->total_bits))) break;
+      if ((rc = ghf_encode_emit(c, plane, n_elems, code, nullptr, GHF_EMIT_LAST | GHF_EMIT_HEADER, d_out + p * slot_bytes, slot_bytes,
+                                h_indexes ? h_indexes + p : nullptr, c->d->end)))
+        break;
+      launch_store_u64(d_out_bytes + p, &c->d->end[1], 0, c->stream);
+      GHF_HIP(c, hipGetLastError());
+      if (raw_auto && d_codes) GHF_HIP(c, hipMemcpyAsync(d_codes + p, code, sizeof(ghf_code), hipMemcpyDeviceToDevice, c->stream));
+      continue;
+    }
+    launch_sparse_split(plane, n_elems, d_mask, d_vals, n_elems, c->d_sparse_offs + kSparseOffWords - 1, c->d_sparse_counts, c->d_sparse_offs,
+                        c->d_status, c->stream);
+    // the plane's rank table, while its mask stands in the workspace; the split is done with the counts and offsets
+    if (d_ranks) launch_sparse_rank_pack(d_mask, n_elems, d_ranks + p * rank_slot_bytes, c->d_sparse_counts, c->d_sparse_offs, c->d_status, c->stream);
+    GHF_HIP(c, hipGetLastError());
+    // compressor.h:62-73 for the mask and for the values, each a byte string of its own
+    if ((rc = ghf_compress(c, d_mask, mask_bytes, d_out + p * slot_bytes, slot_bytes, d_out_bytes + p, codes + p,
+                           h_indexes ? h_indexes + p : nullptr)))
+      break;
+    if (h_n_vals[p])
+      rc = ghf_compress(c, d_vals, h_n_vals[p], d_out + (E + p) * slot_bytes, slot_bytes, d_out_bytes + E + p, codes + E + p,
+                        h_indexes ? h_indexes + E + p : nullptr);
+  }
+  c->hist.forget();
+  c->plan.forget();
+  return rc;
+}
+
+int ghf_decode_planes_forms(ghf_ctx* c, const uint8_t* const* h_stream_ptrs, const size_t* h_stream_bytes, const ghf_code* d_codes,
+                            const ghf_index* indexes, const uint8_t* d_base, unsigned raw_planes, unsigned sparse_planes,
+                            const size_t* h_n_vals, size_t n_elems, uint32_t elem_bytes, uint8_t* d_out, size_t cap, uint64_t* d_out_bytes) {
+  return decode_planes_sparse(c, "ghf_decode_planes_forms", h_stream_ptrs, h_stream_bytes, d_codes, indexes, base_opt(d_base), raw_planes,
+                              sparse_planes, h_n_vals, n_elems, elem_bytes, d_out, cap, d_out_bytes);
+}
+
+int ghf_decode_planes_forms_range(ghf_ctx* c, const uint8_t* const* h_stream_ptrs, const size_t* h_stream_bytes, const ghf_code* d_codes,
+                                  const ghf_index* indexes, const ghf_seek_info* h_infos, const uint8_t* const* h_table_ptrs,
+                                  const size_t* h_table_bytes, const ghf_sparse_rank_info* h_rank_infos, const uint8_t* const* h_rank_ptrs,
+                                  const uint8_t* d_base, unsigned raw_planes, unsigned sparse_planes, size_t n_elems, uint32_t elem_bytes,
+                                  uint64_t first, uint64_t count, uint8_t* d_out, size_t cap) {
+  return decode_planes_sparse_range(c, "ghf_decode_planes_forms_range", h_stream_ptrs, h_stream_bytes, d_codes, indexes, h_infos,
+                                    h_table_ptrs, h_table_bytes, h_rank_infos, h_rank_ptrs, base_opt(d_base), raw_planes, sparse_planes,
+                                    n_elems, elem_bytes, first, count, d_out, cap);
 }
 
 }  // extern "C"

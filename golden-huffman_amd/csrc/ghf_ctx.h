@@ -147,7 +147,7 @@ struct ghf_ctx {
   // long as that pair is queued whole.  Where the second launch fails, the host queues a memset of the replicas instead
   // (histogram_planes_into, ghf_api.hip), so that a later histogram on this context does not start from stale sums.
   uint64_t* d_planes_hist_acc = nullptr;
-  uint64_t* d_planes_hists = nullptr;  // [GHF_PLANES_MAX][257]
+  uint64_t* d_planes_hists = nullptr;  // [GHF_PLANES_MAX][257], and behind them [GHF_PLANES_MAX] image sizes (ghf_compress_planes_forms)
   // ghf_sparse_split / ghf_sparse_merge: the counts of the workgroups' slabs and their exclusive
   // offsets, written and read by the three launches of one call and by nothing else (describe nothing between calls)
   uint64_t* d_sparse_counts = nullptr;  // [kSparseGroups]

@@ -499,6 +499,14 @@ void launch_planes_merge(const uint8_t* d_planes, uint64_t plane_stride, const u
 // and d_base[0 .. count * elem_bytes), the base of the range itself
 void launch_planes_merge_range(const uint8_t* d_planes, uint64_t plane_stride, const uint8_t* d_base, uint64_t first, uint64_t count,
                                uint32_t elem_bytes, uint8_t* d_out, const int* d_status, hipStream_t s);
+// the same with one device address per plane, read from a HOST array of elem_bytes entries.
+// split_to: every h_dst[b] 16-byte aligned.  merge_from: h_src[b] is plane b's byte of the first element and all elem_bytes
+// addresses are equal mod 16; that remainder is the skew (0: the unskewed kernel), and [h_src[b] & ~15, (h_src[b] + n_elems
+// + 15) & ~15) of every plane is read.  d_base, d_status: as above
+void launch_planes_split_to(const uint8_t* d_in, const uint8_t* d_base, uint64_t n_elems, uint32_t elem_bytes, uint8_t* const* h_dst,
+                            hipStream_t s);
+void launch_planes_merge_from(const uint8_t* const* h_src, const uint8_t* d_base, uint64_t n_elems, uint32_t elem_bytes, uint8_t* d_out,
+                              const int* d_status, hipStream_t s);
 // ghf_sparse.hip: n > 0, d_in / d_mask / d_vals / d_out 16-byte aligned.  d_counts: kSparseGroups words, d_offs: kSparseOffWords
 // words, both private to the three launches each call queues (count, scan, move).
 // split: mask[0 .. (n + 7) / 8) and *d_n_vals are always written; n_vals > vals_cap latches GHF_E_CAP and d_vals stays untouched

@@ -452,4 +452,210 @@ void launch_planes_merge_range(const uint8_t* d_planes, uint64_t plane_stride, c
   }
 }
 
+// ----------------------------------------------------------------------------------------------------------------------
+// The same three kernels with ONE ADDRESS PER PLANE: a plane stored raw lives in the caller's image,
+// the others in the context's workspace, and one base pointer and one stride cannot name both.  The E addresses travel by
+// value in the kernel arguments: they are wave-uniform, every index into them is a constant once the loops are unrolled,
+// and they stay in SGPRs.  kDelta: the interleaved side is taken against `base`, loaded and applied exactly as in the
+// _delta kernels above; without it `base` is not looked at.  Tiles, slabs, LDS rows, grid, load depth and the bytewise
+// ragged end are the parents'.  The bodies stand beside the parents' and share no code with them.
+// ----------------------------------------------------------------------------------------------------------------------
+template <int E>
+struct PlaneDsts {
+  uint8_t* p[E];
+};
+template <int E>
+struct PlaneSrcs {
+  const uint8_t* p[E];
+};
+
+template <int E, bool kDelta>
+__global__ __launch_bounds__(kWave) void k_planes_split_to(const uint8_t* __restrict__ in, const uint8_t* __restrict__ base,
+                                                           uint64_t n_elems, PlaneDsts<E> dst) {
+  using G = PlanesGeom<E>;
+  __shared__ uint4 tile[G::kRows * G::kRowVec];
+  const uint32_t lane = threadIdx.x;
+  const Slab s = slab_of(n_elems, G::kTile);
+  for (uint64_t t = s.lo; t < s.end; ++t) {
+    const uint4* src = reinterpret_cast<const uint4*>(in) + t * (kWave * G::kVec);
+    uint4 x[G::kVec], d[G::kVec];
+#pragma unroll
+    for (int j = 0; j < G::kVec; ++j) x[j] = ld16(src + j * kWave + lane);
+    if constexpr (kDelta) {
+      const uint4* bsrc = reinterpret_cast<const uint4*>(base) + t * (kWave * G::kVec);
+#pragma unroll
+      for (int j = 0; j < G::kVec; ++j) d[j] = ld16(bsrc + j * kWave + lane);
+    }
+#pragma unroll
+    for (int j = 0; j < G::kVec; ++j) {
+      const uint32_t v = j * kWave + lane;
+      if constexpr (kDelta) tile[(v / E) * G::kRowVec + v % E] = xor16(x[j], d[j]);
+      else tile[(v / E) * G::kRowVec + v % E] = x[j];
+    }
+    wave_sync();
+#pragma unroll
+    for (int r = 0; r < G::kRowsPerLane; ++r) {
+      const uint32_t row = r * kWave + lane;
+      uint4 y[E], p[E];
+#pragma unroll
+      for (int j = 0; j < E; ++j) y[j] = tile[row * G::kRowVec + j];
+      row_to_planes<E>(y, p);
+#pragma unroll
+      for (int b = 0; b < E; ++b) st16(reinterpret_cast<uint4*>(dst.p[b] + (t * G::kRows + r * kWave) * 16) + lane, p[b]);
+    }
+    wave_sync();
+  }
+  for (uint64_t k = s.tail; k < n_elems; k += (uint64_t)gridDim.x * kWave) {  // the ragged end: byte by byte
+#pragma unroll
+    for (int b = 0; b < E; ++b) {
+      if constexpr (kDelta) dst.p[b][k] = in[k * E + b] ^ base[k * E + b];
+      else dst.p[b][k] = in[k * E + b];
+    }
+  }
+}
+
+// `out` and `base` may be the same pointer, as in k_planes_merge_delta; status: as in k_planes_merge
+template <int E, bool kDelta>
+__global__ __launch_bounds__(kWave) void k_planes_merge_from(PlaneSrcs<E> src, const uint8_t* base, uint64_t n_elems, uint8_t* out,
+                                                             const int* __restrict__ status) {
+  using G = PlanesGeom<E>;
+  __shared__ uint4 tile[G::kRows * G::kRowVec];
+  if (status && __builtin_amdgcn_readfirstlane(*status) != 0) return;
+  const uint32_t lane = threadIdx.x;
+  const Slab s = slab_of(n_elems, G::kTile);
+  for (uint64_t t = s.lo; t < s.end; ++t) {
+    uint4 p[G::kRowsPerLane][E], d[G::kVec];
+#pragma unroll
+    for (int r = 0; r < G::kRowsPerLane; ++r)
+#pragma unroll
+      for (int b = 0; b < E; ++b) p[r][b] = ld16(reinterpret_cast<const uint4*>(src.p[b] + (t * G::kRows + r * kWave) * 16) + lane);
+    if constexpr (kDelta) {
+      const uint4* bsrc = reinterpret_cast<const uint4*>(base) + t * (kWave * G::kVec);
+#pragma unroll
+      for (int j = 0; j < G::kVec; ++j) d[j] = ld16(bsrc + j * kWave + lane);
+      __builtin_amdgcn_sched_barrier(0);  // every load of the tile is issued before the first use: none sinks below the transposition
+    }
+#pragma unroll
+    for (int r = 0; r < G::kRowsPerLane; ++r) {
+      const uint32_t row = r * kWave + lane;
+      uint4 y[E];
+      planes_to_row<E>(p[r], y);
+#pragma unroll
+      for (int j = 0; j < E; ++j) tile[row * G::kRowVec + j] = y[j];
+    }
+    wave_sync();
+    uint4* dst = reinterpret_cast<uint4*>(out) + t * (kWave * G::kVec);
+#pragma unroll
+    for (int j = 0; j < G::kVec; ++j) {
+      const uint32_t v = j * kWave + lane;
+      if constexpr (kDelta) st16(dst + j * kWave + lane, xor16(tile[(v / E) * G::kRowVec + v % E], d[j]));
+      else st16(dst + j * kWave + lane, tile[(v / E) * G::kRowVec + v % E]);
+    }
+    wave_sync();
+  }
+  for (uint64_t k = s.tail; k < n_elems; k += (uint64_t)gridDim.x * kWave) {
+#pragma unroll
+    for (int b = 0; b < E; ++b) {
+      if constexpr (kDelta) out[k * E + b] = src.p[b][k] ^ base[k * E + b];
+      else out[k * E + b] = src.p[b][k];
+    }
+  }
+}
+
+// the skewed merge of section 17: src.p[b] is the 16-byte-aligned address at or below plane b's byte of the run's first
+// element, which stands `skew` = 1 .. 15 bytes behind it in EVERY plane.  As in k_planes_merge_range nothing outside
+// [0, (skew + n_elems + 15) & ~15) of a source is read; `base` holds the run's own elements and carries no skew
+template <int E, bool kDelta>
+__global__ __launch_bounds__(kWave) void k_planes_merge_range_from(PlaneSrcs<E> src, uint32_t skew, const uint8_t* base, uint64_t n_elems,
+                                                                   uint8_t* out, const int* __restrict__ status) {
+  using G = PlanesGeom<E>;
+  __shared__ uint4 tile[G::kRows * G::kRowVec];
+  if (status && __builtin_amdgcn_readfirstlane(*status) != 0) return;
+  const uint32_t lane = threadIdx.x;
+  skew = __builtin_amdgcn_readfirstlane(skew);
+  const Slab s = slab_of(n_elems, G::kTile);
+  for (uint64_t t = s.lo; t < s.end; ++t) {
+    uint4 lo[G::kRowsPerLane][E], hi[G::kRowsPerLane][E], d[G::kVec];
+#pragma unroll
+    for (int r = 0; r < G::kRowsPerLane; ++r)
+#pragma unroll
+      for (int b = 0; b < E; ++b) {
+        const uint4* v = reinterpret_cast<const uint4*>(src.p[b] + (t * G::kRows + r * kWave) * 16) + lane;
+        lo[r][b] = ld16(v);
+        hi[r][b] = ld16(v + 1);
+      }
+    if constexpr (kDelta) {
+      const uint4* bsrc = reinterpret_cast<const uint4*>(base) + t * (kWave * G::kVec);
+#pragma unroll
+      for (int j = 0; j < G::kVec; ++j) d[j] = ld16(bsrc + j * kWave + lane);
+    }
+#pragma unroll
+    for (int r = 0; r < G::kRowsPerLane; ++r) {
+      const uint32_t row = r * kWave + lane;
+      uint4 p[E], y[E];
+#pragma unroll
+      for (int b = 0; b < E; ++b) p[b] = funnel16(lo[r][b], hi[r][b], skew);
+      planes_to_row<E>(p, y);
+#pragma unroll
+      for (int j = 0; j < E; ++j) tile[row * G::kRowVec + j] = y[j];
+    }
+    wave_sync();
+    uint4* dst = reinterpret_cast<uint4*>(out) + t * (kWave * G::kVec);
+#pragma unroll
+    for (int j = 0; j < G::kVec; ++j) {
+      const uint32_t v = j * kWave + lane;
+      if constexpr (kDelta) st16(dst + j * kWave + lane, xor16(tile[(v / E) * G::kRowVec + v % E], d[j]));
+      else st16(dst + j * kWave + lane, tile[(v / E) * G::kRowVec + v % E]);
+    }
+    wave_sync();
+  }
+  for (uint64_t k = s.tail; k < n_elems; k += (uint64_t)gridDim.x * kWave) {
+#pragma unroll
+    for (int b = 0; b < E; ++b) {
+      if constexpr (kDelta) out[k * E + b] = src.p[b][skew + k] ^ base[k * E + b];
+      else out[k * E + b] = src.p[b][skew + k];
+    }
+  }
+}
+
+template <int E>
+static void split_to(const uint8_t* d_in, const uint8_t* d_base, uint64_t n_elems, uint8_t* const* h_dst, hipStream_t s) {
+  const dim3 grid(planes_grid(n_elems, E)), block(kWave);
+  PlaneDsts<E> dst;
+  for (int b = 0; b < E; ++b) dst.p[b] = h_dst[b];
+  if (d_base) hipLaunchKernelGGL((k_planes_split_to<E, true>), grid, block, 0, s, d_in, d_base, n_elems, dst);
+  else hipLaunchKernelGGL((k_planes_split_to<E, false>), grid, block, 0, s, d_in, d_base, n_elems, dst);
+}
+
+// h_src[b] is plane b's byte of the first element; all have the same address mod 16 (the caller has seen to it)
+template <int E>
+static void merge_from(const uint8_t* const* h_src, const uint8_t* d_base, uint64_t n_elems, uint8_t* d_out, const int* d_status,
+                       hipStream_t s) {
+  const dim3 grid(planes_grid(n_elems, E)), block(kWave);
+  const uint32_t skew = (uint32_t)(reinterpret_cast<uintptr_t>(h_src[0]) & 15u);
+  PlaneSrcs<E> src;
+  for (int b = 0; b < E; ++b) src.p[b] = h_src[b] - skew;
+  if (skew == 0) {
+    if (d_base) hipLaunchKernelGGL((k_planes_merge_from<E, true>), grid, block, 0, s, src, d_base, n_elems, d_out, d_status);
+    else hipLaunchKernelGGL((k_planes_merge_from<E, false>), grid, block, 0, s, src, d_base, n_elems, d_out, d_status);
+  } else {
+    if (d_base) hipLaunchKernelGGL((k_planes_merge_range_from<E, true>), grid, block, 0, s, src, skew, d_base, n_elems, d_out, d_status);
+    else hipLaunchKernelGGL((k_planes_merge_range_from<E, false>), grid, block, 0, s, src, skew, d_base, n_elems, d_out, d_status);
+  }
+}
+
+void launch_planes_split_to(const uint8_t* d_in, const uint8_t* d_base, uint64_t n_elems, uint32_t elem_bytes, uint8_t* const* h_dst,
+                            hipStream_t s) {
+  if (elem_bytes == 2) split_to<2>(d_in, d_base, n_elems, h_dst, s);
+  else if (elem_bytes == 4) split_to<4>(d_in, d_base, n_elems, h_dst, s);
+  else split_to<8>(d_in, d_base, n_elems, h_dst, s);
+}
+
+void launch_planes_merge_from(const uint8_t* const* h_src, const uint8_t* d_base, uint64_t n_elems, uint32_t elem_bytes, uint8_t* d_out,
+                              const int* d_status, hipStream_t s) {
+  if (elem_bytes == 2) merge_from<2>(h_src, d_base, n_elems, d_out, d_status, s);
+  else if (elem_bytes == 4) merge_from<4>(h_src, d_base, n_elems, d_out, d_status, s);
+  else merge_from<8>(h_src, d_base, n_elems, d_out, d_status, s);
+}
+
 }  // namespace ghf

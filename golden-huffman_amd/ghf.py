@@ -35,6 +35,7 @@ SPARSE_TILE = 4096
 SPARSE_GROUPS = 256 * 16
 SPARSE_SCAN = SPARSE_GROUPS
 SPARSE_RANK_ELEMS = 32768  # GHF_SPARSE_RANK_ELEMS: the elements of a rank block: 4096 mask bytes, one seek block
+RAW_AUTO = 0x80000000  # GHF_RAW_AUTO (ghf_compress_planes_forms): a plane whose image would be at least n_elems bytes is stored raw
 SPARSE_AUTO = 0x80000000  # GHF_SPARSE_AUTO (ghf_compress_planes_sparse): planes with at least 3/4 zero bytes are stored sparse
 EMPTY_OK = 2  # opt-in: n == 0 -> header of the one-symbol code + 0x7F (builder's definition, parity unpinned)
 
@@ -177,6 +178,8 @@ EXPORTS = [
     "ghf_sparse_rank_bytes", "ghf_sparse_rank_pack", "ghf_sparse_rank_parse", "ghf_sparse_merge_at",
     "ghf_compress_planes_sparse_ranked", "ghf_compress_planes_sparse_ranked_delta", "ghf_decode_planes_sparse_range",
     "ghf_decode_planes_sparse_range_delta",
+    "ghf_planes_split_to", "ghf_planes_merge_from", "ghf_planes_merge_range_from", "ghf_compress_planes_forms",
+    "ghf_decode_planes_forms", "ghf_decode_planes_forms_range",
 ]
 COMM_ID_BYTES = 128
 
@@ -343,6 +346,14 @@ def lib():
                           C.POINTER(SparseRankInfo), C.POINTER(vp)]
     L.ghf_decode_planes_sparse_range.argtypes = sparse_range_front + [C.c_uint, sz, u32, u64, u64, vp, sz]
     L.ghf_decode_planes_sparse_range_delta.argtypes = sparse_range_front + [vp, C.c_uint, sz, u32, u64, u64, vp, sz]
+    L.ghf_planes_split_to.argtypes = [vp, vp, vp, sz, u32, C.POINTER(vp)]
+    L.ghf_planes_merge_from.argtypes = [vp, C.POINTER(vp), vp, sz, u32, vp]
+    L.ghf_planes_merge_range_from.argtypes = [vp, C.POINTER(vp), vp, sz, u32, vp]
+    L.ghf_compress_planes_forms.argtypes = [vp, vp, vp, sz, u32, C.c_uint, C.c_uint, vp, sz, vp, vp, C.POINTER(Index), vp, sz,
+                                            C.POINTER(C.c_uint), C.POINTER(C.c_uint), C.POINTER(sz)]
+    L.ghf_decode_planes_forms.argtypes = [vp, C.POINTER(vp), C.POINTER(sz), vp, C.POINTER(Index), vp, C.c_uint, C.c_uint, C.POINTER(sz),
+                                          sz, u32, vp, sz, vp]
+    L.ghf_decode_planes_forms_range.argtypes = sparse_range_front + [vp, C.c_uint, C.c_uint, sz, u32, u64, u64, vp, sz]
     _lib = L
     return L
 
@@ -1564,6 +1575,125 @@ class Context:
         d_out, and may be d_out.  -> d_out"""
         return self._decode_planes_sparse_range(streams, stream_bytes, d_codes, d_base, True, sparse_planes, ranks, n_elems, elem_bytes,
                                                 first, count, indexes, infos, d_tables, table_bytes, d_out, cap)
+
+    # ---- byte planes in three forms (DESIGN.md section 23): raw planes beside dense and sparse ones; d_base is optional ------
+    @staticmethod
+    def _plane_ptrs(planes, elem_bytes):
+        """planes: elem_bytes CUDA uint8 tensors or raw device addresses -> a host array of addresses"""
+        return (C.c_void_p * elem_bytes)(*[x if isinstance(x, int) else x.data_ptr() for x in planes])
+
+    def planes_split_to(self, d_in, planes, elem_bytes, n_elems=None, d_base=None):
+        """plane p of d_in (of d_in ^ d_base) -> planes[p][0 : n_elems]; planes: elem_bytes CUDA uint8 tensors (or device
+        addresses), each 16-byte aligned, anywhere and in any order.  No host synchronisation.  -> planes"""
+        n_elems = d_in.numel() * d_in.element_size() // elem_bytes if n_elems is None else n_elems
+        self._chk(self.L.ghf_planes_split_to(self.h, d_in.data_ptr(), self._base_ptr(d_base), n_elems, elem_bytes,
+                                             self._plane_ptrs(planes, elem_bytes)), "ghf_planes_split_to")
+        return planes
+
+    def planes_merge_from(self, planes, n_elems, elem_bytes, d_out=None, d_base=None):
+        """the inverse of planes_split_to; d_out may be d_base.  -> d_out uint8[n_elems * elem_bytes]"""
+        if d_out is None:
+            d_out = self.empty_u8(n_elems * elem_bytes)
+        self._chk(self.L.ghf_planes_merge_from(self.h, self._plane_ptrs(planes, elem_bytes), self._base_ptr(d_base), n_elems, elem_bytes,
+                                               d_out.data_ptr()), "ghf_planes_merge_from")
+        return d_out
+
+    def planes_merge_range_from(self, planes, count, elem_bytes, d_out=None, d_base=None):
+        """planes[p]: the address (or a tensor view that starts there) of plane p's byte of the run's first element; all equal
+        modulo 16.  d_base: the base elements of the run, indexed like d_out.  -> d_out uint8[count * elem_bytes]"""
+        if d_out is None:
+            d_out = self.empty_u8(count * elem_bytes)
+        self._chk(self.L.ghf_planes_merge_range_from(self.h, self._plane_ptrs(planes, elem_bytes), self._base_ptr(d_base), count,
+                                                     elem_bytes, d_out.data_ptr()), "ghf_planes_merge_range_from")
+        return d_out
+
+    def compress_planes_forms(self, d_in, elem_bytes, raw_planes=RAW_AUTO, sparse_planes=0, d_base=None, n_elems=None, d_out=None,
+                              slot_bytes=None, d_codes=None, indexes=False, ranks=False, d_ranks=None, rank_slot_bytes=None,
+                              out_bytes=None):
+        """the byte planes of d_in (of d_in ^ d_base), each stored raw, sparse or dense: raw_planes / sparse_planes are a bit
+        per plane, or RAW_AUTO (raw exactly when the plane's image would be at least n_elems bytes) / SPARSE_AUTO.  A raw plane
+        is its n_elems bytes at the start of slot p, written by the split itself.  SYNCHRONISES at most once; never with both
+        masks explicit and sparse_planes == 0.  ranks=True (or d_ranks): the rank table of every sparse plane.
+        -> the dict of compress_planes_sparse_ranked plus raw_planes (the planes stored raw)"""
+        t = self.torch
+        n_elems = d_in.numel() * d_in.element_size() // elem_bytes if n_elems is None else n_elems
+        if slot_bytes is None:
+            slot_bytes = planes_slot_bytes(n_elems)
+        if d_out is None:
+            d_out = self.empty_u8(slot_bytes * 2 * elem_bytes)
+        if rank_slot_bytes is None:
+            rank_slot_bytes = (sparse_rank_bytes(n_elems) + 15) & ~15
+        if d_ranks is None and ranks:
+            d_ranks = self.empty_u8(rank_slot_bytes * elem_bytes)
+        if d_codes is None:
+            d_codes = t.zeros((2 * elem_bytes, C.sizeof(Code)), dtype=t.uint8, device=self.device)
+        if out_bytes is None:
+            out_bytes = t.zeros(2 * elem_bytes, dtype=t.int64, device=self.device)
+        idx = (Index * (2 * elem_bytes))() if indexes else None
+        raw, chosen, n_vals = C.c_uint(0), C.c_uint(0), (C.c_size_t * elem_bytes)()
+        self._chk(self.L.ghf_compress_planes_forms(self.h, d_in.data_ptr(), self._base_ptr(d_base), n_elems, elem_bytes, raw_planes,
+                                                   sparse_planes, d_out.data_ptr(), slot_bytes, out_bytes.data_ptr(), d_codes.data_ptr(),
+                                                   idx, None if d_ranks is None else d_ranks.data_ptr(), rank_slot_bytes, C.byref(raw),
+                                                   C.byref(chosen), n_vals), "ghf_compress_planes_forms")
+        return {"out": d_out, "slot_bytes": slot_bytes, "out_bytes": out_bytes, "codes": d_codes, "n_elems": n_elems,
+                "elem_bytes": elem_bytes, "raw_planes": int(raw.value), "sparse_planes": int(chosen.value),
+                "n_vals": [int(v) for v in n_vals], "indexes": idx, "ranks": d_ranks, "rank_slot_bytes": rank_slot_bytes}
+
+    def decode_planes_forms(self, streams, stream_bytes, d_codes, raw_planes, sparse_planes, n_vals, n_elems, elem_bytes, indexes=None,
+                            d_base=None, d_out=None, cap=None, nbytes=None):
+        """streams: 2 * elem_bytes CUDA uint8 tensors (None for an empty slot; a raw plane's holds the plane itself and its
+        stream_bytes entry is n_elems); raw_planes, sparse_planes and n_vals as compress_planes_forms returned them.  A raw
+        plane is read where it lies.  d_out may be d_base.  indexes=None synchronises per stream that has a code.
+        -> (d_out uint8, nbytes int64[1] device)"""
+        ptrs = (C.c_void_p * (2 * elem_bytes))(*[None if x is None else x if isinstance(x, int) else x.data_ptr() for x in streams])
+        sizes = (C.c_size_t * (2 * elem_bytes))(*[int(v) for v in stream_bytes])
+        h_n_vals = (C.c_size_t * elem_bytes)(*[int(v) for v in n_vals])
+        if d_out is None:
+            d_out = self.empty_u8(n_elems * elem_bytes)
+        if nbytes is None:
+            nbytes = self.torch.zeros(1, dtype=self.torch.int64, device=self.device)
+        cap = d_out.numel() if cap is None else cap
+        self._chk(self.L.ghf_decode_planes_forms(self.h, ptrs, sizes, None if d_codes is None else d_codes.data_ptr(), indexes,
+                                                 self._base_ptr(d_base), raw_planes, sparse_planes, h_n_vals, n_elems, elem_bytes,
+                                                 d_out.data_ptr(), cap, nbytes.data_ptr()), "ghf_decode_planes_forms")
+        return d_out, nbytes
+
+    def decode_planes_forms_range(self, streams, stream_bytes, d_codes, raw_planes, sparse_planes, ranks, n_elems, elem_bytes, first,
+                                  count, indexes=None, infos=None, d_tables=None, table_bytes=None, d_base=None, d_out=None, cap=None):
+        """d_out[0 : count * elem_bytes] = elements [first, first + count) of a tensor stored by compress_planes_forms; the
+        arguments of decode_planes_sparse_range plus raw_planes and the optional d_base (the base elements of the range, indexed
+        like d_out).  The index, info and table entries of a raw plane may be None.  Never synchronises.  -> d_out"""
+        import numpy as np
+
+        slots = 2 * elem_bytes
+        ptrs = (C.c_void_p * slots)(*[None if x is None else x if isinstance(x, int) else x.data_ptr() for x in streams])
+        sizes = (C.c_size_t * slots)(*[int(v) for v in stream_bytes])
+        h_infos = t_ptrs = t_bytes = None
+        if infos is not None:
+            h_infos = (SeekInfo * slots)(*[SeekInfo() if i is None else i for i in infos])
+            t_ptrs = (C.c_void_p * slots)(*[None if x is None else x.data_ptr() for x in d_tables])
+            if table_bytes is None:
+                table_bytes = [0 if i is None else seek_bytes(i.n_symbols) for i in infos]
+            t_bytes = (C.c_size_t * slots)(*[int(v) for v in table_bytes])
+        r_infos = r_ptrs = None
+        keep = []
+        if ranks is not None:  # per plane: None, or (SparseRankInfo, the table as host bytes)
+            r_infos, r_ptrs = (SparseRankInfo * elem_bytes)(), (C.c_void_p * elem_bytes)()
+            for p, r in enumerate(ranks):
+                if r is None:
+                    continue
+                r_infos[p] = r[0]
+                if r[1] is not None:
+                    keep.append(np.ascontiguousarray(r[1], dtype=np.uint8))
+                    r_ptrs[p] = keep[-1].ctypes.data
+        if d_out is None:
+            d_out = self.empty_u8(count * elem_bytes)
+        cap = d_out.numel() if cap is None else cap
+        self._chk(self.L.ghf_decode_planes_forms_range(self.h, ptrs, sizes, None if d_codes is None else d_codes.data_ptr(), indexes,
+                                                       h_infos, t_ptrs, t_bytes, r_infos, r_ptrs, self._base_ptr(d_base), raw_planes,
+                                                       sparse_planes, n_elems, elem_bytes, first, count, d_out.data_ptr(), cap),
+                  "ghf_decode_planes_forms_range")
+        return d_out
 
     # ---- seekable streams: the seek table (the persistent form of the side-car) ----------------
     def seek_pack(self, index, d_stream=None, stream_bytes=0, d_table=None, n=None):

@@ -869,6 +869,105 @@ int ghf_decode_planes_range_delta(ghf_ctx* ctx, const uint8_t* const* h_stream_p
 int ghf_sync_piece(ghf_ctx* ctx, const uint8_t* d_piece, size_t piece_bytes, uint32_t first_bit, uint64_t end_bit,
                    const ghf_code* d_code, uint64_t* landing, uint64_t* n_symbols, int* has_end_mark);
 
+/* ---- byte planes in three forms: raw planes beside dense and sparse ones -------------
+ * The mantissa planes of a float tensor gain nothing from a Huffman code: their images are LARGER than the planes, and
+ * every one of them costs a whole compress pass and a whole decode pass on 8-bit codes.  THE RAW FORM of a plane is the
+ * plane's n_elems bytes at the start of its slot and nothing else (no container, no magic, no header): d_out_bytes[p] =
+ * n_elems, the slot's code is unwritten and its side-car entry zeroed.  It is the third form beside the dense one (a
+ * standalone .crs2 image) and the sparse one; the calls of this section take any mix of the three.
+ * No .crs2, seek-table, run-record or rank-table byte changes, and a decode is told which planes are raw as it is told
+ * which are sparse.
+ *
+ * A raw plane is never copied: the split writes it straight into the caller's slot and the merge reads it there, through
+ * kernels that take ONE ADDRESS PER PLANE (k_planes_split_to, k_planes_merge_from, k_planes_merge_range_from).
+ * IN THIS FAMILY d_base IS OPTIONAL: NULL is the plain call, non-NULL XORs the interleaved side against it as the calls
+ * of DESIGN.md section 19 do; a misaligned d_base is still GHF_E_INVAL.  Every device pointer is 16-byte aligned.
+ * Call-level refusals come before anything touches HIP, with nothing queued, in the order of the sparse calls; in
+ * addition a raw_planes with a bit at or above elem_bytes, GHF_RAW_AUTO together with an explicit bit, GHF_RAW_AUTO in a
+ * decode, a plane named in both explicit masks, a raw stream whose size is not n_elems: GHF_E_INVAL. */
+#define GHF_RAW_AUTO 0x80000000u
+struct ghf_sparse_rank_info; /* the parsed rank table of a sparse plane: defined with the rank tables below */
+
+/* No reference counterpart (generalises the flat input of include/compressor.h:62-73).  ghf_planes_split with a
+ * destination per plane: byte p of element k of d_in -- of d_in ^ d_base when d_base is not NULL -- goes to
+ * h_plane_ptrs[p][k].  h_plane_ptrs is a HOST array of elem_bytes DEVICE pointers, each 16-byte aligned and good for
+ * n_elems bytes, read before the call returns; the planes may lie anywhere and in any order but must not overlap.
+ * Asynchronous, never synchronises. */
+int ghf_planes_split_to(ghf_ctx* ctx, const uint8_t* d_in, const uint8_t* d_base /* optional */, size_t n_elems,
+                        uint32_t elem_bytes, uint8_t* const* h_plane_ptrs /* HOST [elem_bytes] */);
+
+/* No reference counterpart (generalises the flat output of include/compressor.h:87-92).  The inverse: d_out[0 .. n_elems
+ * * elem_bytes) <- the planes at h_plane_ptrs (HOST [elem_bytes], each 16-byte aligned), XOR d_base when it is not NULL.
+ * d_base == d_out is allowed.  Does not look at the context's status word. */
+int ghf_planes_merge_from(ghf_ctx* ctx, const uint8_t* const* h_plane_ptrs /* HOST [elem_bytes] */,
+                          const uint8_t* d_base /* optional */, size_t n_elems, uint32_t elem_bytes, uint8_t* d_out);
+
+/* No reference counterpart (generalises the flat output of include/compressor.h:87-92).  ghf_planes_merge_range with a
+ * source per plane: h_plane_ptrs[p] is the address of plane p's byte of the run's FIRST element, d_out[0 .. count *
+ * elem_bytes) receives the run.  The addresses need not be aligned but all have the same remainder modulo 16 (GHF_E_INVAL
+ * otherwise) -- what holds when every plane begins 16-byte aligned at element 0 or at a block of 4096 elements.  Nothing
+ * is read outside the aligned 16-byte vectors that hold the run's bytes.  d_base (optional) holds the base elements of
+ * the run itself at d_base[0 .. count * elem_bytes), unskewed and indexed like d_out; d_base == d_out is allowed. */
+int ghf_planes_merge_range_from(ghf_ctx* ctx, const uint8_t* const* h_plane_ptrs /* HOST [elem_bytes] */,
+                                const uint8_t* d_base /* optional */, size_t count, uint32_t elem_bytes, uint8_t* d_out);
+
+/* No reference counterpart: Compressor::compress(), include/compressor.h:62-73, once per stored stream that has a code,
+ * and not at all for a raw plane.  The slots, sizes, codes, side-cars and rank tables are laid out as by
+ * ghf_compress_planes_sparse_ranked: 2 * elem_bytes slots of slot_bytes >= ghf_planes_slot_bytes of n_elems.  A dense
+ * plane's image, size, code and side-car are byte for byte what ghf_compress_planes writes, a sparse plane's what the
+ * sparse call writes; a raw plane is written by the split itself, straight into slot p: no workspace copy, no histogram
+ * pass of its own, no code build, no packing, and no byte of the slot behind n_elems is written.  d_ranks == NULL: no
+ * rank tables.
+ * raw_planes / sparse_planes: explicit bits below elem_bytes (a plane named in both: GHF_E_INVAL), or GHF_RAW_AUTO /
+ * GHF_SPARSE_AUTO.  With GHF_RAW_AUTO a plane that is not sparse is raw EXACTLY when the image it would get is at least
+ * n_elems bytes -- the size ghf_planes_image_bytes gives under the code ghf_build_codes builds from its counts -- so no
+ * such plane stores more than n_elems bytes.  With GHF_SPARSE_AUTO the rule of the sparse call (at least n_elems -
+ * n_elems / 4 zero bytes) picks the sparse planes first; with BOTH masks automatic only when n_elems > 2 *
+ * ghf_header_bytes(1): a sparse plane stores two headers, and at or below that size raw is always the smaller.
+ * *h_raw_planes, *h_sparse_planes and h_n_vals (HOST) report what was chosen and are what the decode must be told.
+ * The call SYNCHRONISES with the host AT MOST ONCE: ghf_histogram_planes, and with GHF_RAW_AUTO ghf_build_codes for all
+ * planes and ghf_planes_image_bytes, are queued, and one copy brings back the counts and the sizes; the dense planes are
+ * packed with those codes, there is no second build.  With both masks explicit and sparse_planes == 0 the call NEVER
+ * synchronises, and h_n_vals is zeroed.  With every plane raw the call is one split launch and the size stores.
+ * Device failures latch as for ghf_compress_planes_coded. */
+int ghf_compress_planes_forms(ghf_ctx* ctx, const uint8_t* d_in, const uint8_t* d_base /* optional */, size_t n_elems,
+                              uint32_t elem_bytes, unsigned raw_planes, unsigned sparse_planes, uint8_t* d_out, size_t slot_bytes,
+                              uint64_t* d_out_bytes /* [2 * elem_bytes] */, ghf_code* d_codes /* [2 * elem_bytes] optional OUT */,
+                              ghf_index* h_indexes /* [2 * elem_bytes] optional OUT */, uint8_t* d_ranks /* optional */,
+                              size_t rank_slot_bytes, unsigned* h_raw_planes /* OUT */, unsigned* h_sparse_planes /* OUT */,
+                              size_t* h_n_vals /* [elem_bytes] OUT */);
+
+/* No reference counterpart: Decompressor::decompress(), include/compressor.h:87-92, once per stored stream that has a
+ * code.  ghf_decode_planes_sparse with raw planes: raw_planes, sparse_planes and h_n_vals are what the compress call
+ * reported.  For a raw plane h_stream_ptrs[p] (16-byte aligned) holds the plane itself and h_stream_bytes[p] is n_elems,
+ * GHF_E_INVAL otherwise with nothing queued; its code and index entries are ignored.  The plane is never copied: the
+ * merge, which comes last and stores nothing behind a latched status, reads it where it lies.  d_base == d_out is
+ * allowed, and behind a latched status d_out then still holds the base.  With every plane raw the call is one merge
+ * launch and d_codes may be NULL.  indexes == NULL SYNCHRONISES per stream that has a code, as ghf_decode_planes does. */
+int ghf_decode_planes_forms(ghf_ctx* ctx, const uint8_t* const* h_stream_ptrs /* [2 * elem_bytes] */,
+                            const size_t* h_stream_bytes /* [2 * elem_bytes] */, const ghf_code* d_codes /* [2 * elem_bytes] */,
+                            const ghf_index* indexes /* [2 * elem_bytes] or NULL */, const uint8_t* d_base /* optional */,
+                            unsigned raw_planes, unsigned sparse_planes, const size_t* h_n_vals /* [elem_bytes] */, size_t n_elems,
+                            uint32_t elem_bytes, uint8_t* d_out, size_t cap, uint64_t* d_out_bytes);
+
+/* No reference counterpart: Decompressor::decompress(), include/compressor.h:87-92, for a part of a typed tensor stored
+ * in any mix of the three forms.  ghf_decode_planes_sparse_range with raw planes, from side-cars or from seek tables;
+ * never synchronises.  Nothing is decoded or expanded for a raw plane: its index, seek info, table and code entries are
+ * not read (they may be NULL or zero), its size is n_elems (GHF_E_INVAL otherwise) and its source is h_stream_ptrs[p] +
+ * first.  With raw planes and no sparse one the other planes are decoded from the seek block that holds `first`, as
+ * ghf_decode_planes_range does it; with a sparse plane from the rank block, by the plan of the sparse range call.  The
+ * refusals and their order are that call's; count == 0: GHF_OK, nothing queued. */
+int ghf_decode_planes_forms_range(ghf_ctx* ctx, const uint8_t* const* h_stream_ptrs /* [2 * elem_bytes] */,
+                                  const size_t* h_stream_bytes /* [2 * elem_bytes] */, const ghf_code* d_codes /* [2 * elem_bytes] */,
+                                  const ghf_index* indexes /* [2 * elem_bytes] or NULL */,
+                                  const ghf_seek_info* h_infos /* [2 * elem_bytes] or NULL */,
+                                  const uint8_t* const* h_table_ptrs /* [2 * elem_bytes] or NULL */,
+                                  const size_t* h_table_bytes /* [2 * elem_bytes] or NULL */,
+                                  const struct ghf_sparse_rank_info* h_rank_infos /* [elem_bytes] */,
+                                  const uint8_t* const* h_rank_ptrs /* [elem_bytes] */, const uint8_t* d_base /* optional */,
+                                  unsigned raw_planes, unsigned sparse_planes, size_t n_elems, uint32_t elem_bytes, uint64_t first,
+                                  uint64_t count, uint8_t* d_out, size_t cap);
+
 /* ------------------------------------------------------------------------------------------------
  * one stream sharded over the GPUs of a node, one process (or thread) and one ghf_ctx per GPU,
  * RCCL over xGMI underneath.  The reference has no counterpart (it is single-threaded, single-stream:
