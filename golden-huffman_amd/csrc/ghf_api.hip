@@ -25,32 +25,56 @@ int ensure_ws(ghf_ctx* c, size_t nchunks) {
   return rc;
 }
 
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+}  // namespace
 
-// the part of "this side-car is one of ours" that packing and decoding both ask for
-inline bool index_has_arrays(const ghf_index* ix) {
-  return ix->d_chunk_bit && ix->d_seg_bit && ix->chunk_symbols == (uint32_t)kBlockSymbols && ix->seg_symbols == (uint32_t)kSegSymbols;
-}
-// ... and its counts are the ones its n_symbols implies
-inline bool index_matches_n(const ghf_index* ix) {
-  return index_has_arrays(ix) && ix->n_segs == segs_for(ix->n_symbols) && ix->n_chunks == blocks_for(ix->n_symbols);
-}
-inline bool index_is_whole(const ghf_index* ix) { return index_matches_n(ix) && ix->n_chunks < kDecMaxGroups; }
+// ---- a range of a seekable stream: what ghf_ctx.h declares for this unit and ghf_api_planes.hip -------------------------
+namespace ghf {
 
-// ghf_index and ghf_batch_index: waits for the stream, then frees the two arrays
-template <class Index>
-int free_index_arrays(ghf_ctx* c, Index* idx) {
-  if (!c || !idx) return GHF_E_INVAL;
-  GHF_HIP(c, hipSetDevice(c->device));
-  GHF_HIP(c, hipStreamSynchronize(c->stream));
-  if (idx->d_chunk_bit) (void)hipFree(idx->d_chunk_bit);
-  if (idx->d_seg_bit) (void)hipFree(idx->d_seg_bit);
-  idx->d_chunk_bit = nullptr;
-  idx->d_seg_bit = nullptr;
+int seek_table_ok(ghf_ctx* c, const char* who, const ghf_seek_info* info, const uint8_t* d_table, size_t table_bytes) {
+  const std::string f = std::string(who) + ": ";
+  if (!aligned16(d_table)) return fail(c, GHF_E_INVAL, (f + "d_table must be 16-byte aligned").c_str());
+  if (info->version != kSeekVersion || (info->flags & ~(uint32_t)GHF_INDEX_NO_END_MARK) || info->n_blocks != blocks_for(info->n_symbols) ||
+      info->n_blocks >= kDecMaxGroups || table_bytes != ghf_seek_bytes(info->n_symbols))
+    return fail(c, GHF_E_FORMAT, (f + "the seek table does not have the size its header implies").c_str());
   return GHF_OK;
 }
 
-}  // namespace
+SeekExpandParams seek_expand_params(ghf_ctx* c, const ghf_seek_info* info, const uint8_t* d_table, const uint8_t* d_stream,
+                                    size_t stream_bytes, const DecTables* dt, uint64_t g0, uint64_t g1, uint64_t* chunk_bit,
+                                    uint32_t* seg_bit) {
+  SeekExpandParams p = {};
+  p.records = d_table + kSeekHeaderBytes;
+  p.stream = d_stream;
+  p.stream_bytes = stream_bytes;
+  p.dt = dt;
+  p.n_symbols = info->n_symbols;
+  p.n_blocks = info->n_blocks;
+  p.g0 = g0;
+  p.g1 = g1;
+  p.chunk_bit = chunk_bit;
+  p.seg_bit = seg_bit;
+  p.status = c->d_status;
+  return p;
+}
+
+DecParams range_decode_params(ghf_ctx* c, const uint8_t* d_stream, size_t stream_bytes, DecTables* dt, const uint64_t* chunk_bit,
+                              const uint32_t* seg_bit, uint64_t g, uint64_t end, uint64_t n, uint32_t index_flags, uint8_t* out) {
+  DecParams p = {};
+  p.stream = d_stream;
+  p.stream_bytes = stream_bytes;
+  p.dt = dt;
+  p.chunk_bit = chunk_bit;
+  p.seg_bit = seg_bit;
+  p.n_symbols = end - g * kBlockSymbols;
+  p.n_segs = segs_for(p.n_symbols);
+  p.no_end_mark = (end == n && !(index_flags & GHF_INDEX_NO_END_MARK)) ? 0u : 1u;
+  p.out = out;
+  p.out_bytes = nullptr;
+  p.status = c->d_status;
+  return p;
+}
+
+}  // namespace ghf
 
 extern "C" {
 
@@ -1276,255 +1300,9 @@ int ghf_decode(ghf_ctx* c, const uint8_t* d_stream, size_t stream_bytes, const g
   return decode_with_index(c, "ghf_decode", index, cap, p);
 }
 
-// ---------------------------------------------------------------------------------------------- byte planes
-// (no reference counterpart)
-size_t ghf_planes_slot_bytes(size_t n_elems) { return (ghf_compress_bound(n_elems) + 15) & ~(size_t)15; }
-
-static inline bool elem_bytes_ok(uint32_t e) { return e == 2 || e == 4 || e == 8; }
-static inline bool elems_overflow(size_t n_elems, uint32_t e) { return n_elems > (size_t)-1 / e; }
-// ... and for the calls that go through the workspace, whose planes sit at n_elems rounded up to 256
-static inline bool workspace_overflow(size_t n_elems, uint32_t e) { return elems_overflow(n_elems, e) || elems_overflow(n_elems + 255, e); }
-
-// The calls against a base share the implementation of their plain calls: a Base says whether the
-// call has one, and d_base is null exactly where it has none -- which is what selects the plain kernels in the launchers.
-// A delta call with a null or misaligned d_base is refused where the other pointers are.
-struct Base {
-  bool delta;
-  const uint8_t* p;
-  bool null() const { return delta && !p; }
-  bool misaligned() const { return delta && !aligned16(p); }
-};
-static inline Base no_base() { return {false, nullptr}; }
-static inline Base base_of(const uint8_t* d_base) { return {true, d_base}; }
-
-// what ghf_planes_split and ghf_planes_merge check alike: `d_inter` is the interleaved side
-static int planes_args(ghf_ctx* c, const char* who, const uint8_t* d_inter, const uint8_t* d_planes, size_t plane_stride, size_t n_elems,
-                       uint32_t elem_bytes, Base base) {
-  if (!c || !d_inter || !d_planes || base.null()) return GHF_E_INVAL;
-  const std::string f = std::string(who) + ": ";
-  if (!elem_bytes_ok(elem_bytes)) return fail(c, GHF_E_INVAL, (f + "elem_bytes must be 2, 4 or 8").c_str());
-  if (!aligned16(d_inter) || !aligned16(d_planes) || (plane_stride & 15u) || base.misaligned())
-    return fail(c, GHF_E_INVAL, (f + "pointers and plane_stride must be multiples of 16").c_str());
-  if (elems_overflow(n_elems, elem_bytes)) return fail(c, GHF_E_INVAL, (f + "n_elems * elem_bytes overflows").c_str());
-  if (n_elems == 0) return fail(c, GHF_E_EMPTY, (f + "no elements").c_str());
-  if (plane_stride < n_elems) return fail(c, GHF_E_CAP, (f + "plane_stride below n_elems").c_str());
-  return GHF_OK;
-}
-
-static int planes_split(ghf_ctx* c, const char* who, const uint8_t* d_in, Base base, size_t n_elems, uint32_t elem_bytes,
-                        uint8_t* d_planes, size_t plane_stride) {
-  const int rc = planes_args(c, who, d_in, d_planes, plane_stride, n_elems, elem_bytes, base);
-  if (rc) return rc;
-  GHF_HIP(c, hipSetDevice(c->device));
-  launch_planes_split(d_in, base.p, n_elems, elem_bytes, d_planes, plane_stride, c->stream);
-  GHF_HIP(c, hipGetLastError());
-  return GHF_OK;
-}
-int ghf_planes_split(ghf_ctx* c, const uint8_t* d_in, size_t n_elems, uint32_t elem_bytes, uint8_t* d_planes, size_t plane_stride) {
-  return planes_split(c, "ghf_planes_split", d_in, no_base(), n_elems, elem_bytes, d_planes, plane_stride);
-}
-
-static int planes_merge(ghf_ctx* c, const char* who, const uint8_t* d_planes, size_t plane_stride, Base base, size_t n_elems,
-                        uint32_t elem_bytes, uint8_t* d_out) {
-  const int rc = planes_args(c, who, d_out, d_planes, plane_stride, n_elems, elem_bytes, base);
-  if (rc) return rc;
-  GHF_HIP(c, hipSetDevice(c->device));
-  launch_planes_merge(d_planes, plane_stride, base.p, n_elems, elem_bytes, d_out, nullptr, c->stream);
-  GHF_HIP(c, hipGetLastError());
-  return GHF_OK;
-}
-int ghf_planes_merge(ghf_ctx* c, const uint8_t* d_planes, size_t plane_stride, size_t n_elems, uint32_t elem_bytes, uint8_t* d_out) {
-  return planes_merge(c, "ghf_planes_merge", d_planes, plane_stride, no_base(), n_elems, elem_bytes, d_out);
-}
-
-static int planes_merge_range(ghf_ctx* c, const char* who, const uint8_t* d_planes, size_t plane_stride, Base base, size_t first,
-                              size_t count, uint32_t elem_bytes, uint8_t* d_out) {
-  const std::string f = std::string(who) + ": ";
-  if (c && first + count < first) return fail(c, GHF_E_INVAL, (f + "first + count overflows").c_str());
-  int rc = planes_args(c, who, d_out, d_planes, plane_stride, count, elem_bytes, base);
-  if (!rc && plane_stride < first + count) rc = fail(c, GHF_E_CAP, (f + "plane_stride below first + count").c_str());
-  if (rc) return rc;
-  GHF_HIP(c, hipSetDevice(c->device));
-  launch_planes_merge_range(d_planes, plane_stride, base.p, first, count, elem_bytes, d_out, nullptr, c->stream);
-  GHF_HIP(c, hipGetLastError());
-  return GHF_OK;
-}
-int ghf_planes_merge_range(ghf_ctx* c, const uint8_t* d_planes, size_t plane_stride, size_t first, size_t count, uint32_t elem_bytes,
-                           uint8_t* d_out) {
-  return planes_merge_range(c, "ghf_planes_merge_range", d_planes, plane_stride, no_base(), first, count, elem_bytes, d_out);
-}
-
-// the context's plane workspace for n_elems elements (workspace_overflow has cleared them): *stride <- the distance
-// between two planes
-static int planes_workspace(ghf_ctx* c, size_t n_elems, uint32_t elem_bytes, size_t* stride) {
-  *stride = (n_elems + 255) & ~(size_t)255;
-  return grow(c, c->planes, *stride * elem_bytes);
-}
-
-int ghf_compress_planes(ghf_ctx* c, const uint8_t* d_in, size_t n_elems, uint32_t elem_bytes, uint8_t* d_out, size_t slot_bytes,
-                        uint64_t* d_out_bytes, ghf_code* d_codes, const ghf_index* indexes) {
-  if (!c || !d_in || !d_out || !d_out_bytes) return GHF_E_INVAL;
-  if (!elem_bytes_ok(elem_bytes)) return fail(c, GHF_E_INVAL, "ghf_compress_planes: elem_bytes must be 2, 4 or 8");
-  if (!aligned16(d_in) || !aligned16(d_out) || (slot_bytes & 15u))
-    return fail(c, GHF_E_INVAL, "ghf_compress_planes: d_in, d_out and slot_bytes must be multiples of 16");
-  if (workspace_overflow(n_elems, elem_bytes)) return fail(c, GHF_E_INVAL, "ghf_compress_planes: n_elems * elem_bytes overflows");
-  for (uint32_t p = 0; indexes && p < elem_bytes; ++p)
-    if (indexes[p].n_symbols != n_elems || !index_has_arrays(&indexes[p]))
-      return fail(c, GHF_E_INVAL, "ghf_compress_planes: an index does not match n_elems (use ghf_index_alloc)");
-  if (n_elems == 0) return fail(c, GHF_E_EMPTY, "ghf_compress_planes: no elements");
-  if (slot_bytes < ghf_planes_slot_bytes(n_elems)) return fail(c, GHF_E_CAP, "ghf_compress_planes: slot_bytes below ghf_planes_slot_bytes(n_elems)");
-  GHF_HIP(c, hipSetDevice(c->device));
-  size_t stride = 0;
-  int rc = planes_workspace(c, n_elems, elem_bytes, &stride);
-  if (rc) return rc;
-  launch_planes_split(d_in, nullptr, n_elems, elem_bytes, c->planes.p, stride, c->stream);
-  GHF_HIP(c, hipGetLastError());
-  for (uint32_t p = 0; p < elem_bytes && !rc; ++p)  // compressor.h:62-73, once per plane
-    rc = ghf_compress(c, c->planes.p + p * stride, n_elems, d_out + p * slot_bytes, slot_bytes, d_out_bytes + p,
-                      d_codes ? d_codes + p : nullptr, indexes ? indexes + p : nullptr);
-  // the workspace is private and the next call refills the same addresses with other bytes
-  c->hist.forget();
-  c->plan.forget();
-  return rc;
-}
-
-// ---------------------------------------------------------------------------------------------- byte planes in stages
-// (no reference counterpart)
-// k_histogram_planes and its finish on the stream.  The finish is what leaves the replicas zero for the next call: if it
-// cannot be queued behind a counting launch that was, a memset takes its place before the error is returned
-static int histogram_planes_into(ghf_ctx* c, const char* who, const uint8_t* d_in, const uint8_t* d_base, size_t n_elems,
-                                 uint32_t elem_bytes, unsigned flags, uint64_t* d_hists) {
-  const hipError_t e = launch_histogram_planes(d_in, d_base, n_elems, elem_bytes, flags, c->d_planes_hist_acc, d_hists, c->stream);
-  if (e == hipSuccess) return GHF_OK;
-  (void)hipMemsetAsync(c->d_planes_hist_acc, 0, kPlanesHistAccWords * sizeof(uint64_t), c->stream);
-  return fail(c, GHF_E_HIP, who, e);
-}
-
-static int histogram_planes(ghf_ctx* c, const char* who, const uint8_t* d_in, Base base, size_t n_elems, uint32_t elem_bytes,
-                            unsigned flags, uint64_t* d_hists) {
-  if (!c || !d_in || !d_hists || base.null()) return GHF_E_INVAL;
-  const std::string f = std::string(who) + ": ";
-  if (!elem_bytes_ok(elem_bytes)) return fail(c, GHF_E_INVAL, (f + "elem_bytes must be 2, 4 or 8").c_str());
-  if (!aligned16(d_in) || base.misaligned()) return fail(c, GHF_E_INVAL, (f + "d_in and d_base must be 16-byte aligned").c_str());
-  if (flags & ~GHF_HIST_COVER_ALL) return fail(c, GHF_E_INVAL, (f + "unknown flags").c_str());
-  if (elems_overflow(n_elems, elem_bytes)) return fail(c, GHF_E_INVAL, (f + "n_elems * elem_bytes overflows").c_str());
-  if (n_elems == 0) return fail(c, GHF_E_EMPTY, (f + "no elements").c_str());
-  GHF_HIP(c, hipSetDevice(c->device));
-  return histogram_planes_into(c, (f + "launch").c_str(), d_in, base.p, n_elems, elem_bytes, flags, d_hists);
-}
-int ghf_histogram_planes(ghf_ctx* c, const uint8_t* d_in, size_t n_elems, uint32_t elem_bytes, unsigned flags, uint64_t* d_hists) {
-  return histogram_planes(c, "ghf_histogram_planes", d_in, no_base(), n_elems, elem_bytes, flags, d_hists);
-}
-
-int ghf_planes_image_bytes(ghf_ctx* c, const uint64_t* d_hists, const ghf_code* d_codes, uint32_t elem_bytes, uint64_t* d_bytes) {
-  if (!c || !d_hists || !d_codes || !d_bytes) return GHF_E_INVAL;
-  if (!elem_bytes_ok(elem_bytes)) return fail(c, GHF_E_INVAL, "ghf_planes_image_bytes: elem_bytes must be 2, 4 or 8");
-  GHF_HIP(c, hipSetDevice(c->device));
-  launch_planes_image_bytes(d_hists, d_codes, elem_bytes, d_bytes, c->stream);
-  GHF_HIP(c, hipGetLastError());
-  return GHF_OK;
-}
-
-static int compress_planes_coded(ghf_ctx* c, const char* who, const uint8_t* d_in, Base base, size_t n_elems, uint32_t elem_bytes,
-                                 ghf_code* d_codes, unsigned flags, uint8_t* d_out, size_t slot_bytes, uint64_t* d_out_bytes,
-                                 const ghf_index* indexes) {
-  if (!c || !d_in || !d_out || !d_out_bytes || !d_codes || base.null()) return GHF_E_INVAL;
-  const std::string f = std::string(who) + ": ";
-  if (!elem_bytes_ok(elem_bytes)) return fail(c, GHF_E_INVAL, (f + "elem_bytes must be 2, 4 or 8").c_str());
-  if (!aligned16(d_in) || !aligned16(d_out) || (slot_bytes & 15u) || !aligned16(d_codes) || base.misaligned())
-    return fail(c, GHF_E_INVAL, (f + "d_in, d_base, d_out, d_codes and slot_bytes must be multiples of 16").c_str());
-  if (flags & ~GHF_PLANES_BUILD_CODES) return fail(c, GHF_E_INVAL, (f + "unknown flags").c_str());
-  if (workspace_overflow(n_elems, elem_bytes)) return fail(c, GHF_E_INVAL, (f + "n_elems * elem_bytes overflows").c_str());
-  for (uint32_t p = 0; indexes && p < elem_bytes; ++p)
-    if (indexes[p].n_symbols != n_elems || !index_has_arrays(&indexes[p]))
-      return fail(c, GHF_E_INVAL, (f + "an index does not match n_elems (use ghf_index_alloc)").c_str());
-  if (n_elems == 0) return fail(c, GHF_E_EMPTY, (f + "no elements").c_str());
-  if (slot_bytes < ghf_planes_slot_bytes(n_elems)) return fail(c, GHF_E_CAP, (f + "slot_bytes below ghf_planes_slot_bytes(n_elems)").c_str());
-  GHF_HIP(c, hipSetDevice(c->device));
-  size_t stride = 0;
-  int rc = planes_workspace(c, n_elems, elem_bytes, &stride);
-  if (rc) return rc;
-  // compressor.h:63 for all planes in one pass over the interleaved buffer, then compressor.h:64 for all planes in one launch --
-  // or the caller's codes, held against the counts
-  if ((rc = histogram_planes_into(c, (f + "histogram launch").c_str(), d_in, base.p, n_elems, elem_bytes, 0, c->d_planes_hists))) return rc;
-  if (flags & GHF_PLANES_BUILD_CODES) {
-    if ((rc = ghf_build_codes(c, c->d_planes_hists, elem_bytes, d_codes, 0))) return rc;
-  } else {
-    launch_planes_vet_codes(c->d_planes_hists, d_codes, elem_bytes, c->d_status, c->stream);
-    GHF_HIP(c, hipGetLastError());
-  }
-  launch_planes_split(d_in, base.p, n_elems, elem_bytes, c->planes.p, stride, c->stream);
-  GHF_HIP(c, hipGetLastError());
-  // K1 has not seen these planes: whatever it remembers about an address inside the workspace is of another call, and the
-  // planner counts each plane itself (k_chunk_bits_direct)
-  c->hist.forget();
-  for (uint32_t p = 0; p < elem_bytes && !rc; ++p) {  // compressor.h:70-72, once per plane: what ghf_compress_ex does behind its code build
-    const uint8_t* plane = c->planes.p + p * stride;
-    if ((rc = ghf_encode_plan(c, plane, n_elems, d_codes + p, &c->d->total_bits))) break;
-    if ((rc = ghf_encode_emit(c, plane, n_elems, d_codes + p, nullptr, GHF_EMIT_LAST | GHF_EMIT_HEADER, d_out + p * slot_bytes, slot_bytes,
-                              indexes ? indexes + p : nullptr, c->d->end)))
-      break;
-    launch_store_u64(d_out_bytes + p, &c->d->end[1], 0, c->stream);
-    GHF_HIP(c, hipGetLastError());
-  }
-  c->hist.forget();
-  c->plan.forget();
-  return rc;
-}
-int ghf_compress_planes_coded(ghf_ctx* c, const uint8_t* d_in, size_t n_elems, uint32_t elem_bytes, ghf_code* d_codes, unsigned flags,
-                              uint8_t* d_out, size_t slot_bytes, uint64_t* d_out_bytes, const ghf_index* indexes) {
-  return compress_planes_coded(c, "ghf_compress_planes_coded", d_in, no_base(), n_elems, elem_bytes, d_codes, flags, d_out, slot_bytes,
-                               d_out_bytes, indexes);
-}
-
-static int decode_planes(ghf_ctx* c, const char* who, const uint8_t* const* h_stream_ptrs, const size_t* h_stream_bytes,
-                         const ghf_code* d_codes, const ghf_index* indexes, Base base, size_t n_elems, uint32_t elem_bytes, uint8_t* d_out,
-                         size_t cap, uint64_t* d_out_bytes) {
-  if (!c || !h_stream_ptrs || !h_stream_bytes || !d_codes || !d_out || base.null()) return GHF_E_INVAL;
-  const std::string f = std::string(who) + ": ";
-  if (!elem_bytes_ok(elem_bytes)) return fail(c, GHF_E_INVAL, (f + "elem_bytes must be 2, 4 or 8").c_str());
-  for (uint32_t p = 0; p < elem_bytes; ++p)
-    if (!h_stream_ptrs[p] || !aligned16(h_stream_ptrs[p])) return fail(c, GHF_E_INVAL, (f + "a stream pointer is null or not 16-byte aligned").c_str());
-  if (!aligned16(d_out) || base.misaligned()) return fail(c, GHF_E_INVAL, (f + "d_out and d_base must be 16-byte aligned").c_str());
-  if (workspace_overflow(n_elems, elem_bytes)) return fail(c, GHF_E_INVAL, (f + "n_elems * elem_bytes overflows").c_str());
-  for (uint32_t p = 0; indexes && p < elem_bytes; ++p)
-    if (indexes[p].n_symbols != n_elems || !index_is_whole(&indexes[p]))
-      return fail(c, GHF_E_INVAL, (f + "an index does not cover exactly n_elems symbols").c_str());
-  if (n_elems == 0) return fail(c, GHF_E_EMPTY, (f + "no elements").c_str());
-  if (cap < n_elems * elem_bytes) return fail(c, GHF_E_CAP, (f + "output capacity below n_elems * elem_bytes").c_str());
-  GHF_HIP(c, hipSetDevice(c->device));
-  size_t stride = 0;
-  int rc = planes_workspace(c, n_elems, elem_bytes, &stride);
-  if (rc) return rc;
-  for (uint32_t p = 0; p < elem_bytes; ++p) {
-    if (!indexes) {  // the side-car-less path: synchronises, and keeps the side-car for the decode that follows
-      uint64_t n_p = 0;
-      if ((rc = ghf_decoded_size(c, h_stream_ptrs[p], h_stream_bytes[p], d_codes + p, &n_p))) return rc;
-      if (n_p != n_elems) return fail(c, GHF_E_CORRUPT, (f + "a plane does not decode to n_elems bytes").c_str());
-    }
-    if ((rc = ghf_decode(c, h_stream_ptrs[p], h_stream_bytes[p], d_codes + p, indexes ? indexes + p : nullptr, c->planes.p + p * stride,
-                         stride, nullptr)))
-      return rc;
-  }
-  launch_planes_merge(c->planes.p, stride, base.p, n_elems, elem_bytes, d_out, c->d_status, c->stream);  // nothing is stored behind a failed decode
-  if (d_out_bytes) launch_store_u64(d_out_bytes, nullptr, (uint64_t)n_elems * elem_bytes, c->stream);
-  GHF_HIP(c, hipGetLastError());
-  return GHF_OK;
-}
-int ghf_decode_planes(ghf_ctx* c, const uint8_t* const* h_stream_ptrs, const size_t* h_stream_bytes, const ghf_code* d_codes,
-                      const ghf_index* indexes, size_t n_elems, uint32_t elem_bytes, uint8_t* d_out, size_t cap, uint64_t* d_out_bytes) {
-  return decode_planes(c, "ghf_decode_planes", h_stream_ptrs, h_stream_bytes, d_codes, indexes, no_base(), n_elems, elem_bytes, d_out, cap,
-                       d_out_bytes);
-}
-
 // ---------------------------------------------------------------------------------------------- seek table
 // (no reference counterpart; the format: DESIGN.md "Seekable .crs2")
 size_t ghf_seek_bytes(size_t n_symbols) { return kSeekHeaderBytes + kSeekRecordBytes * (size_t)blocks_for(n_symbols); }
-
-static inline uint32_t le32(const uint8_t* p) {
-  return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
-}
-static inline uint64_t le64(const uint8_t* p) { return (uint64_t)le32(p) | ((uint64_t)le32(p + 4) << 32); }
 
 int ghf_seek_parse(const uint8_t* h, size_t bytes, ghf_seek_info* info) {
   if (!h || !info) return GHF_E_INVAL;
@@ -1543,16 +1321,6 @@ int ghf_seek_parse(const uint8_t* h, size_t bytes, ghf_seek_info* info) {
   info->n_blocks = n_blocks;
   info->flags = flags;
   info->version = kSeekVersion;
-  return GHF_OK;
-}
-
-// the part of "this info describes a table of table_bytes" that every consumer of (info, d_table) asks for
-static int seek_table_ok(ghf_ctx* c, const char* who, const ghf_seek_info* info, const uint8_t* d_table, size_t table_bytes) {
-  const std::string f = std::string(who) + ": ";
-  if (!aligned16(d_table)) return fail(c, GHF_E_INVAL, (f + "d_table must be 16-byte aligned").c_str());
-  if (info->version != kSeekVersion || (info->flags & ~(uint32_t)GHF_INDEX_NO_END_MARK) || info->n_blocks != blocks_for(info->n_symbols) ||
-      info->n_blocks >= kDecMaxGroups || table_bytes != ghf_seek_bytes(info->n_symbols))
-    return fail(c, GHF_E_FORMAT, (f + "the seek table does not have the size its header implies").c_str());
   return GHF_OK;
 }
 
@@ -1584,19 +1352,7 @@ int ghf_seek_pack(ghf_ctx* c, const ghf_index* index, const uint8_t* d_stream, s
 // queues k_seek_expand for blocks [g0, g1) of the table; d_dt must already be queued
 static void expand_blocks(ghf_ctx* c, const ghf_seek_info* info, const uint8_t* d_table, const uint8_t* d_stream, size_t stream_bytes,
                           uint64_t g0, uint64_t g1, uint64_t* d_chunk_bit, uint32_t* d_seg_bit) {
-  SeekExpandParams p = {};
-  p.records = d_table + kSeekHeaderBytes;
-  p.stream = d_stream;
-  p.stream_bytes = stream_bytes;
-  p.dt = c->d_dt;
-  p.n_symbols = info->n_symbols;
-  p.n_blocks = info->n_blocks;
-  p.g0 = g0;
-  p.g1 = g1;
-  p.chunk_bit = d_chunk_bit;
-  p.seg_bit = d_seg_bit;
-  p.status = c->d_status;
-  launch_seek_expand(p, c->stream);
+  launch_seek_expand(seek_expand_params(c, info, d_table, d_stream, stream_bytes, c->d_dt, g0, g1, d_chunk_bit, d_seg_bit), c->stream);
 }
 
 int ghf_seek_expand(ghf_ctx* c, const ghf_seek_info* info, const uint8_t* d_table, size_t table_bytes, const uint8_t* d_stream,
@@ -1676,169 +1432,13 @@ int ghf_decode_range(ghf_ctx* c, const uint8_t* d_stream, size_t stream_bytes, c
     launch_decode_head(h, c->stream);
     gI = gA + 1;
   }
-  if (end > gI * kBlockSymbols) {
-    // K7 on a view of the side-car that begins at block gI and ends with the range: a segment's start depends on its own
-    // block only.  The view's last segment may be cut short by the range; only the stream's own end is followed by the end mark.
-    DecParams p = {};
-    p.stream = d_stream;
-    p.stream_bytes = stream_bytes;
-    p.dt = c->d_dt;
-    p.chunk_bit = chunk_bit + (gI - gA);
-    p.seg_bit = seg_bit + (gI - gA) * (kBlockSymbols / kSegSymbols);
-    p.n_symbols = end - gI * kBlockSymbols;
-    p.n_segs = segs_for(p.n_symbols);
-    p.no_end_mark = (end == n && !(flags & GHF_INDEX_NO_END_MARK)) ? 0u : 1u;
-    p.out = d_out + (gI * kBlockSymbols - first);
-    p.out_bytes = nullptr;
-    p.status = c->d_status;
-    launch_decode(p, c->stream);
-  }
+  if (end > gI * kBlockSymbols)  // K7 on the view of the side-car that begins at block gI and ends with the range
+    launch_decode(range_decode_params(c, d_stream, stream_bytes, c->d_dt, chunk_bit + (gI - gA),
+                                      seg_bit + (gI - gA) * (kBlockSymbols / kSegSymbols), gI, end, n, flags,
+                                      d_out + (gI * kBlockSymbols - first)),
+                  c->stream);
   GHF_HIP(c, hipGetLastError());
   return GHF_OK;
-}
-
-// ---------------------------------------------------------------------------------------------- element range of byte planes
-// (no reference counterpart)
-static int decode_planes_range(ghf_ctx* c, const char* who, const uint8_t* const* h_stream_ptrs, const size_t* h_stream_bytes,
-                               const ghf_code* d_codes, const ghf_index* indexes, const ghf_seek_info* h_infos,
-                               const uint8_t* const* h_table_ptrs, const size_t* h_table_bytes, Base base, uint32_t elem_bytes,
-                               uint64_t first, uint64_t count, uint8_t* d_out, size_t cap) {
-  if (!c || !h_stream_ptrs || !h_stream_bytes || !d_codes || !d_out || base.null()) return GHF_E_INVAL;
-  const std::string f = std::string(who) + ": ";
-  if (!elem_bytes_ok(elem_bytes)) return fail(c, GHF_E_INVAL, (f + "elem_bytes must be 2, 4 or 8").c_str());
-  const bool by_table = h_infos || h_table_ptrs || h_table_bytes;
-  if ((indexes != nullptr) == by_table || (by_table && !(h_infos && h_table_ptrs && h_table_bytes)))
-    return fail(c, GHF_E_INVAL, (f + "exactly one of indexes / (h_infos, h_table_ptrs, h_table_bytes) must be given").c_str());
-  for (uint32_t p = 0; p < elem_bytes; ++p) {
-    if (!h_stream_ptrs[p] || !aligned16(h_stream_ptrs[p]))
-      return fail(c, GHF_E_INVAL, (f + "a stream pointer is null or not 16-byte aligned").c_str());
-    if (by_table && (!h_table_ptrs[p] || !aligned16(h_table_ptrs[p])))
-      return fail(c, GHF_E_INVAL, (f + "a table pointer is null or not 16-byte aligned").c_str());
-  }
-  if (!aligned16(d_out) || base.misaligned()) return fail(c, GHF_E_INVAL, (f + "d_out and d_base must be 16-byte aligned").c_str());
-  const uint64_t n_elems = by_table ? h_infos[0].n_symbols : indexes[0].n_symbols;
-  for (uint32_t p = 0; p < elem_bytes; ++p) {
-    if (!by_table && indexes[p].n_symbols != 0 && !index_is_whole(&indexes[p]))
-      return fail(c, GHF_E_INVAL, (f + "malformed index").c_str());
-    if ((by_table ? h_infos[p].n_symbols : indexes[p].n_symbols) != n_elems)
-      return fail(c, GHF_E_INVAL, (f + "the planes disagree on n_symbols").c_str());
-  }
-  if (first > n_elems || count > n_elems - first) return fail(c, GHF_E_INVAL, (f + "first + count exceeds n_elems").c_str());
-  // the workspace holds the range from the start of its first block (below), and a vector more for the merge's second load
-  const size_t lead = (size_t)(first % kBlockSymbols);
-  if (count > (size_t)-1 - lead - 16 || workspace_overflow((size_t)count + lead + 16, elem_bytes))
-    return fail(c, GHF_E_INVAL, (f + "count * elem_bytes overflows").c_str());
-  for (uint32_t p = 0; by_table && p < elem_bytes; ++p) {  // every plane before anything is queued for the first
-    const int rc = seek_table_ok(c, who, h_infos + p, h_table_ptrs[p], h_table_bytes[p]);
-    if (rc) return rc;
-  }
-  if (cap < count * elem_bytes) return fail(c, GHF_E_CAP, (f + "output capacity below count * elem_bytes").c_str());
-  if (count == 0) return GHF_OK;
-  GHF_HIP(c, hipSetDevice(c->device));
-  // Every plane is decoded from the start of the block that holds `first`: plane p's byte `first - lead` lands on the
-  // 16-byte aligned start of its workspace plane, so every later byte sits at an address congruent to its index modulo 16 --
-  // what K7's 16-byte store path asks for -- and no block is entered in its middle: ghf_decode_range queues no k_decode_head,
-  // whose one wave walks up to a block serially (DESIGN.md section 17 has the measurement).  The up to 4095 symbols in front
-  // of the range are one K7 block of work; the merge skips them and takes the skew out.
-  size_t stride = 0;
-  int rc = planes_workspace(c, (size_t)count + lead + 16, elem_bytes, &stride);
-  if (rc) return rc;
-  const uint64_t from = first - lead, end = first + count;
-  if (!by_table) {
-    for (uint32_t p = 0; p < elem_bytes; ++p)
-      if ((rc = ghf_decode_range(c, h_stream_ptrs[p], h_stream_bytes[p], d_codes + p, indexes + p, nullptr, nullptr, 0, from, end - from,
-                                 c->planes.p + p * stride, stride)))
-        return rc;
-  } else {
-    // From tables ghf_decode_range would expand every plane by itself, and k_seek_expand has a latency floor -- a lane walks
-    // its 512 symbols serially -- that a range does not shrink: E floors one after the other cost more than decoding the
-    // whole tensor from side-cars.  So: all E table sets first, ONE launch that expands the covered blocks of all planes
-    // (k_seek_expand_planes), then K7 per plane on that view, set up as ghf_decode_range sets it up (the range begins on a
-    // block, so there is no head).
-    const uint64_t gA = from / kBlockSymbols, gB = blocks_for(end), nb = gB - gA;
-    const size_t segs_per_block = kBlockSymbols / kSegSymbols;
-    if (!(rc = grow(c, c->range_dt, elem_bytes))) rc = grow(c, c->range_chunk, nb * elem_bytes, 1024);
-    if (!rc) rc = grow(c, c->range_seg, nb * elem_bytes * segs_per_block, 1024 * 64);
-    if (rc) return rc;
-    SeekExpandPlanesParams a = {};
-    for (uint32_t p = 0; p < elem_bytes; ++p) {
-      launch_build_decode_tables(d_codes + p, c->range_dt.p + p, c->d_status, c->stream);
-      SeekExpandParams& x = a.plane[p];
-      x.records = h_table_ptrs[p] + kSeekHeaderBytes;
-      x.stream = h_stream_ptrs[p];
-      x.stream_bytes = h_stream_bytes[p];
-      x.dt = c->range_dt.p + p;
-      x.n_symbols = n_elems;
-      x.n_blocks = h_infos[p].n_blocks;
-      x.g0 = gA;
-      x.g1 = gB;
-      x.chunk_bit = c->range_chunk.p + p * nb;
-      x.seg_bit = c->range_seg.p + p * nb * segs_per_block;
-      x.status = c->d_status;
-    }
-    launch_seek_expand_planes(a, elem_bytes, c->stream);
-    for (uint32_t p = 0; p < elem_bytes; ++p) {
-      DecParams d = {};
-      d.stream = h_stream_ptrs[p];
-      d.stream_bytes = h_stream_bytes[p];
-      d.dt = c->range_dt.p + p;
-      d.chunk_bit = a.plane[p].chunk_bit;
-      d.seg_bit = a.plane[p].seg_bit;
-      d.n_symbols = end - from;
-      d.n_segs = segs_for(d.n_symbols);
-      d.no_end_mark = (end == n_elems && !(h_infos[p].flags & GHF_INDEX_NO_END_MARK)) ? 0u : 1u;
-      d.out = c->planes.p + p * stride;
-      d.out_bytes = nullptr;
-      d.status = c->d_status;
-      launch_decode(d, c->stream);
-    }
-  }
-  launch_planes_merge_range(c->planes.p, stride, base.p, lead, count, elem_bytes, d_out, c->d_status, c->stream);  // nothing behind a failed decode
-  GHF_HIP(c, hipGetLastError());
-  return GHF_OK;
-}
-int ghf_decode_planes_range(ghf_ctx* c, const uint8_t* const* h_stream_ptrs, const size_t* h_stream_bytes, const ghf_code* d_codes,
-                            const ghf_index* indexes, const ghf_seek_info* h_infos, const uint8_t* const* h_table_ptrs,
-                            const size_t* h_table_bytes, uint32_t elem_bytes, uint64_t first, uint64_t count, uint8_t* d_out, size_t cap) {
-  return decode_planes_range(c, "ghf_decode_planes_range", h_stream_ptrs, h_stream_bytes, d_codes, indexes, h_infos, h_table_ptrs,
-                             h_table_bytes, no_base(), elem_bytes, first, count, d_out, cap);
-}
-
-// ---------------------------------------------------------------------------------------------- byte planes against a base
-// (no reference counterpart): the calls above with the XOR against d_base in their streaming kernels
-int ghf_histogram_planes_delta(ghf_ctx* c, const uint8_t* d_in, const uint8_t* d_base, size_t n_elems, uint32_t elem_bytes, unsigned flags,
-                               uint64_t* d_hists) {
-  return histogram_planes(c, "ghf_histogram_planes_delta", d_in, base_of(d_base), n_elems, elem_bytes, flags, d_hists);
-}
-int ghf_planes_split_delta(ghf_ctx* c, const uint8_t* d_in, const uint8_t* d_base, size_t n_elems, uint32_t elem_bytes, uint8_t* d_planes,
-                           size_t plane_stride) {
-  return planes_split(c, "ghf_planes_split_delta", d_in, base_of(d_base), n_elems, elem_bytes, d_planes, plane_stride);
-}
-int ghf_planes_merge_delta(ghf_ctx* c, const uint8_t* d_planes, size_t plane_stride, const uint8_t* d_base, size_t n_elems,
-                           uint32_t elem_bytes, uint8_t* d_out) {
-  return planes_merge(c, "ghf_planes_merge_delta", d_planes, plane_stride, base_of(d_base), n_elems, elem_bytes, d_out);
-}
-int ghf_planes_merge_range_delta(ghf_ctx* c, const uint8_t* d_planes, size_t plane_stride, const uint8_t* d_base, size_t first, size_t count,
-                                 uint32_t elem_bytes, uint8_t* d_out) {
-  return planes_merge_range(c, "ghf_planes_merge_range_delta", d_planes, plane_stride, base_of(d_base), first, count, elem_bytes, d_out);
-}
-int ghf_compress_planes_delta(ghf_ctx* c, const uint8_t* d_in, const uint8_t* d_base, size_t n_elems, uint32_t elem_bytes, ghf_code* d_codes,
-                              unsigned flags, uint8_t* d_out, size_t slot_bytes, uint64_t* d_out_bytes, const ghf_index* indexes) {
-  return compress_planes_coded(c, "ghf_compress_planes_delta", d_in, base_of(d_base), n_elems, elem_bytes, d_codes, flags, d_out, slot_bytes,
-                               d_out_bytes, indexes);
-}
-int ghf_decode_planes_delta(ghf_ctx* c, const uint8_t* const* h_stream_ptrs, const size_t* h_stream_bytes, const ghf_code* d_codes,
-                            const ghf_index* indexes, const uint8_t* d_base, size_t n_elems, uint32_t elem_bytes, uint8_t* d_out, size_t cap,
-                            uint64_t* d_out_bytes) {
-  return decode_planes(c, "ghf_decode_planes_delta", h_stream_ptrs, h_stream_bytes, d_codes, indexes, base_of(d_base), n_elems, elem_bytes,
-                       d_out, cap, d_out_bytes);
-}
-int ghf_decode_planes_range_delta(ghf_ctx* c, const uint8_t* const* h_stream_ptrs, const size_t* h_stream_bytes, const ghf_code* d_codes,
-                                  const ghf_index* indexes, const ghf_seek_info* h_infos, const uint8_t* const* h_table_ptrs,
-                                  const size_t* h_table_bytes, const uint8_t* d_base, uint32_t elem_bytes, uint64_t first, uint64_t count,
-                                  uint8_t* d_out, size_t cap) {
-  return decode_planes_range(c, "ghf_decode_planes_range_delta", h_stream_ptrs, h_stream_bytes, d_codes, indexes, h_infos, h_table_ptrs,
-                             h_table_bytes, base_of(d_base), elem_bytes, first, count, d_out, cap);
 }
 
 // ---------------------------------------------------------------------------------------------- .crs
@@ -2003,775 +1603,6 @@ int ghf_crs_decode(ghf_ctx* c, const uint8_t* d_stream, size_t stream_bytes, int
   p.out = d_out;
   p.out_bytes = d_out_bytes;
   return decode_with_index(c, "ghf_crs_decode", index, cap, p);
-}
-
-// ---------------------------------------------------------------------------------------------- zero-suppressed byte planes
-// (no reference counterpart)
-size_t ghf_sparse_mask_bytes(size_t n) { return n / 8 + (n % 8 != 0); }
-
-int ghf_sparse_split(ghf_ctx* c, const uint8_t* d_in, size_t n, uint8_t* d_mask, uint8_t* d_vals, size_t vals_cap, uint64_t* d_n_vals) {
-  if (!c || !d_in || !d_mask || !d_n_vals || (vals_cap && !d_vals)) return GHF_E_INVAL;
-  if (!aligned16(d_in) || !aligned16(d_mask) || !aligned16(d_vals) || (reinterpret_cast<uintptr_t>(d_n_vals) & 7u))
-    return fail(c, GHF_E_INVAL, "ghf_sparse_split: d_in, d_mask and d_vals must be 16-byte aligned, d_n_vals 8-byte aligned");
-  if (n > (size_t)-1 - kSparseTile) return fail(c, GHF_E_INVAL, "ghf_sparse_split: n overflows");
-  if (n == 0) return fail(c, GHF_E_EMPTY, "ghf_sparse_split: no bytes");
-  GHF_HIP(c, hipSetDevice(c->device));
-  launch_sparse_split(d_in, n, d_mask, d_vals, vals_cap, d_n_vals, c->d_sparse_counts, c->d_sparse_offs, c->d_status, c->stream);
-  GHF_HIP(c, hipGetLastError());
-  return GHF_OK;
-}
-
-int ghf_sparse_merge(ghf_ctx* c, const uint8_t* d_mask, const uint8_t* d_vals, size_t n_vals, size_t n, uint8_t* d_out) {
-  if (!c || !d_mask || !d_out || (n_vals && !d_vals)) return GHF_E_INVAL;
-  if (!aligned16(d_mask) || !aligned16(d_vals) || !aligned16(d_out))
-    return fail(c, GHF_E_INVAL, "ghf_sparse_merge: d_mask, d_vals and d_out must be 16-byte aligned");
-  if (n > (size_t)-1 - kSparseTile) return fail(c, GHF_E_INVAL, "ghf_sparse_merge: n overflows");
-  if (n == 0) return fail(c, GHF_E_EMPTY, "ghf_sparse_merge: no bytes");
-  GHF_HIP(c, hipSetDevice(c->device));
-  launch_sparse_merge(d_mask, d_vals, n_vals, n, d_out, c->d_sparse_counts, c->d_sparse_offs, c->d_status, c->stream);
-  GHF_HIP(c, hipGetLastError());
-  return GHF_OK;
-}
-
-// sparse_planes as the compress call (GHF_SPARSE_AUTO alone, or bits below elem_bytes) or the decode (bits only) takes it
-static inline bool sparse_planes_ok(unsigned sparse_planes, uint32_t elem_bytes, bool may_be_auto) {
-  if (sparse_planes == GHF_SPARSE_AUTO) return may_be_auto;
-  return (sparse_planes >> elem_bytes) == 0;
-}
-
-// raw_planes beside sparse_planes: GHF_RAW_AUTO alone where the call may choose, or bits below
-// elem_bytes; a plane has one form, so where both masks are explicit they share no bit
-static inline bool forms_ok(unsigned raw_planes, unsigned sparse_planes, uint32_t elem_bytes, bool may_be_auto) {
-  if (raw_planes == GHF_RAW_AUTO) return may_be_auto;
-  if ((raw_planes >> elem_bytes) != 0) return false;
-  return sparse_planes == GHF_SPARSE_AUTO || (raw_planes & sparse_planes) == 0;
-}
-
-// the context's second workspace for one sparse plane of n_elems bytes: the mask at [0, *mask_stride), the values behind it
-static int sparse_workspace(ghf_ctx* c, size_t n_elems, size_t* mask_stride) {
-  *mask_stride = (ghf_sparse_mask_bytes(n_elems) + 255) & ~(size_t)255;
-  return grow(c, c->sparse, *mask_stride + ((n_elems + 255) & ~(size_t)255));
-}
-
-static void free_indexes(ghf_ctx* c, ghf_index* ix, uint32_t count) {
-  for (uint32_t j = 0; j < count; ++j)
-    if (ix[j].d_chunk_bit || ix[j].d_seg_bit) (void)free_index_arrays(c, &ix[j]);
-  std::memset(ix, 0, count * sizeof *ix);
-}
-
-// where the ranked compress calls want the rank tables of their sparse planes; the plain calls want none
-struct RankOut {
-  bool wanted;
-  uint8_t* p;
-  size_t slot_bytes;
-  bool null() const { return wanted && !p; }
-  bool misaligned() const { return wanted && (!aligned16(p) || (slot_bytes & 15u)); }
-};
-static inline RankOut no_ranks() { return {false, nullptr, 0}; }
-
-static int compress_planes_sparse(ghf_ctx* c, const char* who, const uint8_t* d_in, Base base, size_t n_elems, uint32_t elem_bytes,
-                                  unsigned sparse_planes, uint8_t* d_out, size_t slot_bytes, uint64_t* d_out_bytes, ghf_code* d_codes,
-                                  ghf_index* h_indexes, unsigned* h_sparse_planes, size_t* h_n_vals, RankOut ranks) {
-  if (!c || !d_in || !d_out || !d_out_bytes || !h_sparse_planes || !h_n_vals || base.null() || ranks.null()) return GHF_E_INVAL;
-  const std::string f = std::string(who) + ": ";
-  if (!elem_bytes_ok(elem_bytes)) return fail(c, GHF_E_INVAL, (f + "elem_bytes must be 2, 4 or 8").c_str());
-  if (!aligned16(d_in) || !aligned16(d_out) || (slot_bytes & 15u) || !aligned16(d_codes) || base.misaligned())
-    return fail(c, GHF_E_INVAL, (f + "d_in, d_base, d_out, d_codes and slot_bytes must be multiples of 16").c_str());
-  if (ranks.misaligned()) return fail(c, GHF_E_INVAL, (f + "d_ranks and rank_slot_bytes must be multiples of 16").c_str());
-  if (!sparse_planes_ok(sparse_planes, elem_bytes, true))
-    return fail(c, GHF_E_INVAL, (f + "sparse_planes is GHF_SPARSE_AUTO alone or has bits below elem_bytes only").c_str());
-  if (workspace_overflow(n_elems, elem_bytes)) return fail(c, GHF_E_INVAL, (f + "n_elems * elem_bytes overflows").c_str());
-  if (n_elems == 0) return fail(c, GHF_E_EMPTY, (f + "no elements").c_str());
-  if (slot_bytes < ghf_planes_slot_bytes(n_elems)) return fail(c, GHF_E_CAP, (f + "slot_bytes below ghf_planes_slot_bytes(n_elems)").c_str());
-  if (ranks.wanted && ranks.slot_bytes < ghf_sparse_rank_bytes(n_elems))
-    return fail(c, GHF_E_CAP, (f + "rank_slot_bytes below ghf_sparse_rank_bytes(n_elems)").c_str());
-  GHF_HIP(c, hipSetDevice(c->device));
-  const uint32_t E = elem_bytes;
-  size_t stride = 0, mask_stride = 0;
-  int rc = planes_workspace(c, n_elems, E, &stride);
-  if (!rc) rc = sparse_workspace(c, n_elems, &mask_stride);
-  if (!rc && !d_codes) rc = grow(c, c->batch_codes, 2 * GHF_PLANES_MAX);
-  if (rc) return rc;
-  ghf_code* codes = d_codes ? d_codes : c->batch_codes.p;
-  // compressor.h:63 for all planes in one pass, and THE ONE WAIT of the call: count_p[0] says how many values plane p has
-  if ((rc = histogram_planes_into(c, (f + "histogram launch").c_str(), d_in, base.p, n_elems, E, 0, c->d_planes_hists))) return rc;
-  uint64_t counts[GHF_PLANES_MAX * GHF_NSYM];
-  GHF_HIP(c, hipMemcpyAsync(counts, c->d_planes_hists, (size_t)E * GHF_NSYM * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
-  GHF_HIP(c, hipStreamSynchronize(c->stream));
-  unsigned chosen = 0;
-  for (uint32_t p = 0; p < E; ++p) {
-    const uint64_t zeros = counts[(size_t)p * GHF_NSYM];
-    if (zeros > n_elems) return fail(c, GHF_E_HIP, (f + "the plane counts did not arrive").c_str());
-    h_n_vals[p] = n_elems - (size_t)zeros;
-    if (sparse_planes == GHF_SPARSE_AUTO ? zeros >= n_elems - n_elems / 4 : (sparse_planes >> p) & 1u) chosen |= 1u << p;
-  }
-  *h_sparse_planes = chosen;
-  const size_t mask_bytes = ghf_sparse_mask_bytes(n_elems);
-  if (h_indexes) {  // one side-car per stored stream, of that stream's own symbol count
-    std::memset(h_indexes, 0, 2 * E * sizeof *h_indexes);
-    for (uint32_t p = 0; p < E && !rc; ++p) {
-      const bool sparse = (chosen >> p) & 1u;
-      rc = ghf_index_alloc(c, sparse ? mask_bytes : n_elems, &h_indexes[p]);
-      if (!rc && sparse && h_n_vals[p]) rc = ghf_index_alloc(c, h_n_vals[p], &h_indexes[E + p]);
-    }
-    if (rc) {
-      free_indexes(c, h_indexes, 2 * E);
-      return rc;
-    }
-  }
-  GHF_HIP(c, hipMemsetAsync(d_out_bytes, 0, 2 * E * sizeof(uint64_t), c->stream));  // the empty slots
-  launch_planes_split(d_in, base.p, n_elems, E, c->planes.p, stride, c->stream);
-  GHF_HIP(c, hipGetLastError());
-  uint8_t *d_mask = c->sparse.p, *d_vals = c->sparse.p + mask_stride;
-  for (uint32_t p = 0; p < E && !rc; ++p) {
-    const uint8_t* plane = c->planes.p + p * stride;
-    // K1 has not seen what stands at these addresses now: the workspaces are refilled for every plane
-    c->hist.forget();
-    c->plan.forget();
-    if (!((chosen >> p) & 1u)) {  // what ghf_compress_planes_coded(GHF_PLANES_BUILD_CODES) queues for the plane
-      if ((rc = ghf_build_codes(c, c->d_planes_hists + (size_t)p * GHF_NSYM, 1, codes + p, 0))) break;
-      if ((rc = ghf_encode_plan(c, plane, n_elems, codes + p, &c->d->total_bits))) break;
-      if ((rc = ghf_encode_emit(c, plane, n_elems, codes + p, nullptr, GHF_EMIT_LAST | GHF_EMIT_HEADER, d_out + p * slot_bytes, slot_bytes,
-                                h_indexes ? h_indexes + p : nullptr, c->d->end)))
-        break;
-      launch_store_u64(d_out_bytes + p, &c->d->end[1], 0, c->stream);
-      GHF_HIP(c, hipGetLastError());
-      continue;
-    }
-    launch_sparse_split(plane, n_elems, d_mask, d_vals, n_elems, c->d_sparse_offs + kSparseOffWords - 1, c->d_sparse_counts, c->d_sparse_offs,
-                        c->d_status, c->stream);
-    // the plane's rank table, while its mask stands in the workspace; the split is done with the counts and offsets
-    if (ranks.wanted)
-      launch_sparse_rank_pack(d_mask, n_elems, ranks.p + p * ranks.slot_bytes, c->d_sparse_counts, c->d_sparse_offs, c->d_status, c->stream);
-    GHF_HIP(c, hipGetLastError());
-    // compressor.h:62-73 for the mask and for the values, each a byte string of its own
-    if ((rc = ghf_compress(c, d_mask, mask_bytes, d_out + p * slot_bytes, slot_bytes, d_out_bytes + p, codes + p,
-                           h_indexes ? h_indexes + p : nullptr)))
-      break;
-    if (h_n_vals[p])
-      rc = ghf_compress(c, d_vals, h_n_vals[p], d_out + (E + p) * slot_bytes, slot_bytes, d_out_bytes + E + p, codes + E + p,
-                        h_indexes ? h_indexes + E + p : nullptr);
-  }
-  c->hist.forget();
-  c->plan.forget();
-  return rc;
-}
-
-int ghf_compress_planes_sparse(ghf_ctx* c, const uint8_t* d_in, size_t n_elems, uint32_t elem_bytes, unsigned sparse_planes, uint8_t* d_out,
-                               size_t slot_bytes, uint64_t* d_out_bytes, ghf_code* d_codes, ghf_index* h_indexes, unsigned* h_sparse_planes,
-                               size_t* h_n_vals) {
-  return compress_planes_sparse(c, "ghf_compress_planes_sparse", d_in, no_base(), n_elems, elem_bytes, sparse_planes, d_out, slot_bytes,
-                                d_out_bytes, d_codes, h_indexes, h_sparse_planes, h_n_vals, no_ranks());
-}
-int ghf_compress_planes_sparse_delta(ghf_ctx* c, const uint8_t* d_in, const uint8_t* d_base, size_t n_elems, uint32_t elem_bytes,
-                                     unsigned sparse_planes, uint8_t* d_out, size_t slot_bytes, uint64_t* d_out_bytes, ghf_code* d_codes,
-                                     ghf_index* h_indexes, unsigned* h_sparse_planes, size_t* h_n_vals) {
-  return compress_planes_sparse(c, "ghf_compress_planes_sparse_delta", d_in, base_of(d_base), n_elems, elem_bytes, sparse_planes, d_out,
-                                slot_bytes, d_out_bytes, d_codes, h_indexes, h_sparse_planes, h_n_vals, no_ranks());
-}
-
-// ghf_decode of one stored stream of `symbols` bytes into the workspace at d_to[0 .. cap)
-static int decode_stored(ghf_ctx* c, const std::string& f, const uint8_t* d_stream, size_t stream_bytes, const ghf_code* d_code,
-                         const ghf_index* index, size_t symbols, uint8_t* d_to, size_t cap) {
-  int rc;
-  if (!index) {  // the side-car-less path: synchronises, and keeps the side-car for the decode that follows
-    uint64_t got = 0;
-    if ((rc = ghf_decoded_size(c, d_stream, stream_bytes, d_code, &got))) return rc;
-    if (got != symbols) return fail(c, GHF_E_CORRUPT, (f + "a stream does not decode to the size its plane gives it").c_str());
-  }
-  return ghf_decode(c, d_stream, stream_bytes, d_code, index, d_to, cap, nullptr);
-}
-
-static int decode_planes_sparse(ghf_ctx* c, const char* who, const uint8_t* const* h_stream_ptrs, const size_t* h_stream_bytes,
-                                const ghf_code* d_codes, const ghf_index* indexes, Base base, unsigned raw_planes, unsigned sparse_planes,
-                                const size_t* h_n_vals, size_t n_elems, uint32_t elem_bytes, uint8_t* d_out, size_t cap,
-                                uint64_t* d_out_bytes) {
-  // the codes of raw planes are not looked at: a tensor of nothing but raw planes needs none
-  const bool all_raw = elem_bytes_ok(elem_bytes) && raw_planes == (1u << elem_bytes) - 1u;
-  if (!c || !h_stream_ptrs || !h_stream_bytes || (!d_codes && !all_raw) || !d_out || !h_n_vals || base.null()) return GHF_E_INVAL;
-  const std::string f = std::string(who) + ": ";
-  if (!elem_bytes_ok(elem_bytes)) return fail(c, GHF_E_INVAL, (f + "elem_bytes must be 2, 4 or 8").c_str());
-  const uint32_t E = elem_bytes;
-  if (!sparse_planes_ok(sparse_planes, E, false))
-    return fail(c, GHF_E_INVAL, (f + "sparse_planes has bits below elem_bytes only (the mask the compress call reported)").c_str());
-  if (!forms_ok(raw_planes, sparse_planes, E, false))
-    return fail(c, GHF_E_INVAL, (f + "raw_planes has bits below elem_bytes only, none of them a sparse plane's").c_str());
-  const size_t mask_bytes = ghf_sparse_mask_bytes(n_elems);
-  auto raw = [&](uint32_t p) { return ((raw_planes >> p) & 1u) != 0; };
-  // slot j is stored when it is a plane's own slot, or the values slot of a sparse plane that has values
-  auto symbols_of = [&](uint32_t j) -> size_t {
-    const uint32_t p = j % E;
-    const bool sparse = (sparse_planes >> p) & 1u;
-    if (j < E) return sparse ? mask_bytes : n_elems;
-    return sparse ? h_n_vals[p] : 0;
-  };
-  for (uint32_t p = 0; p < E; ++p)
-    if (((sparse_planes >> p) & 1u) && h_n_vals[p] > n_elems) return fail(c, GHF_E_INVAL, (f + "a plane has more values than elements").c_str());
-  for (uint32_t j = 0; j < 2 * E; ++j)
-    if ((j < E || symbols_of(j)) && (!h_stream_ptrs[j] || !aligned16(h_stream_ptrs[j])))
-      return fail(c, GHF_E_INVAL, (f + "a stream pointer is null or not 16-byte aligned").c_str());
-  if (!aligned16(d_out) || base.misaligned()) return fail(c, GHF_E_INVAL, (f + "d_out and d_base must be 16-byte aligned").c_str());
-  if (workspace_overflow(n_elems, E)) return fail(c, GHF_E_INVAL, (f + "n_elems * elem_bytes overflows").c_str());
-  for (uint32_t j = 0; indexes && j < 2 * E; ++j)
-    if ((j < E || symbols_of(j)) && !raw(j % E) && (indexes[j].n_symbols != symbols_of(j) || !index_is_whole(&indexes[j])))
-      return fail(c, GHF_E_INVAL, (f + "an index does not cover exactly the symbols of its stream").c_str());
-  for (uint32_t p = 0; p < E; ++p)  // a raw plane is its n_elems bytes and nothing else
-    if (raw(p) && h_stream_bytes[p] != n_elems) return fail(c, GHF_E_INVAL, (f + "a raw plane does not have n_elems bytes").c_str());
-  if (n_elems == 0) return fail(c, GHF_E_EMPTY, (f + "no elements").c_str());
-  if (cap < n_elems * E) return fail(c, GHF_E_CAP, (f + "output capacity below n_elems * elem_bytes").c_str());
-  GHF_HIP(c, hipSetDevice(c->device));
-  size_t stride = 0, mask_stride = 0;
-  int rc = all_raw ? GHF_OK : planes_workspace(c, n_elems, E, &stride);
-  if (!rc && sparse_planes) rc = sparse_workspace(c, n_elems, &mask_stride);
-  if (rc) return rc;
-  for (uint32_t p = 0; p < E; ++p) {
-    if (raw(p)) continue;  // never copied: the merge reads it where it lies
-    uint8_t* plane = c->planes.p + p * stride;
-    if (!((sparse_planes >> p) & 1u)) {
-      if ((rc = decode_stored(c, f, h_stream_ptrs[p], h_stream_bytes[p], d_codes + p, indexes ? indexes + p : nullptr, n_elems, plane, stride)))
-        return rc;
-      continue;
-    }
-    uint8_t *d_mask = c->sparse.p, *d_vals = c->sparse.p + mask_stride;
-    if ((rc = decode_stored(c, f, h_stream_ptrs[p], h_stream_bytes[p], d_codes + p, indexes ? indexes + p : nullptr, mask_bytes, d_mask,
-                            mask_stride)))
-      return rc;
-    if (h_n_vals[p] &&
-        (rc = decode_stored(c, f, h_stream_ptrs[E + p], h_stream_bytes[E + p], d_codes + E + p, indexes ? indexes + E + p : nullptr,
-                            h_n_vals[p], d_vals, c->sparse.cap - mask_stride)))
-      return rc;
-    launch_sparse_merge(d_mask, d_vals, h_n_vals[p], n_elems, plane, c->d_sparse_counts, c->d_sparse_offs, c->d_status, c->stream);
-    GHF_HIP(c, hipGetLastError());
-  }
-  // nothing is stored behind a latched status
-  if (!raw_planes) {
-    launch_planes_merge(c->planes.p, stride, base.p, n_elems, E, d_out, c->d_status, c->stream);
-  } else {
-    const uint8_t* from[GHF_PLANES_MAX];
-    for (uint32_t p = 0; p < E; ++p) from[p] = raw(p) ? h_stream_ptrs[p] : c->planes.p + p * stride;
-    launch_planes_merge_from(from, base.p, n_elems, E, d_out, c->d_status, c->stream);
-  }
-  if (d_out_bytes) launch_store_u64(d_out_bytes, nullptr, (uint64_t)n_elems * E, c->stream);
-  GHF_HIP(c, hipGetLastError());
-  return GHF_OK;
-}
-
-int ghf_decode_planes_sparse(ghf_ctx* c, const uint8_t* const* h_stream_ptrs, const size_t* h_stream_bytes, const ghf_code* d_codes,
-                             const ghf_index* indexes, unsigned sparse_planes, const size_t* h_n_vals, size_t n_elems, uint32_t elem_bytes,
-                             uint8_t* d_out, size_t cap, uint64_t* d_out_bytes) {
-  return decode_planes_sparse(c, "ghf_decode_planes_sparse", h_stream_ptrs, h_stream_bytes, d_codes, indexes, no_base(), 0, sparse_planes,
-                              h_n_vals, n_elems, elem_bytes, d_out, cap, d_out_bytes);
-}
-int ghf_decode_planes_sparse_delta(ghf_ctx* c, const uint8_t* const* h_stream_ptrs, const size_t* h_stream_bytes, const ghf_code* d_codes,
-                                   const ghf_index* indexes, const uint8_t* d_base, unsigned sparse_planes, const size_t* h_n_vals,
-                                   size_t n_elems, uint32_t elem_bytes, uint8_t* d_out, size_t cap, uint64_t* d_out_bytes) {
-  return decode_planes_sparse(c, "ghf_decode_planes_sparse_delta", h_stream_ptrs, h_stream_bytes, d_codes, indexes, base_of(d_base), 0,
-                              sparse_planes, h_n_vals, n_elems, elem_bytes, d_out, cap, d_out_bytes);
-}
-
-// ---------------------------------------------------------------------------------------------- element range of sparse planes
-// (no reference counterpart)
-static inline uint64_t rank_blocks_for(uint64_t n) { return n / kSparseRankElems + (n % kSparseRankElems != 0); }
-
-size_t ghf_sparse_rank_bytes(size_t n) { return kSparseRankHeaderBytes + 8 * ((size_t)rank_blocks_for(n) + 1); }
-
-int ghf_sparse_rank_pack(ghf_ctx* c, const uint8_t* d_mask, size_t n, uint8_t* d_table, size_t cap) {
-  if (!c || !d_mask || !d_table) return GHF_E_INVAL;
-  if (!aligned16(d_mask) || !aligned16(d_table)) return fail(c, GHF_E_INVAL, "ghf_sparse_rank_pack: d_mask and d_table must be 16-byte aligned");
-  if (n > (size_t)-1 - kSparseRankElems) return fail(c, GHF_E_INVAL, "ghf_sparse_rank_pack: n overflows");
-  if (n == 0) return fail(c, GHF_E_EMPTY, "ghf_sparse_rank_pack: no bytes");
-  if (cap < ghf_sparse_rank_bytes(n)) return fail(c, GHF_E_CAP, "ghf_sparse_rank_pack: table capacity below ghf_sparse_rank_bytes(n)");
-  GHF_HIP(c, hipSetDevice(c->device));
-  launch_sparse_rank_pack(d_mask, n, d_table, c->d_sparse_counts, c->d_sparse_offs, c->d_status, c->stream);
-  GHF_HIP(c, hipGetLastError());
-  return GHF_OK;
-}
-
-// The table is not trusted: everything one entry can be held against without the mask is checked here.  Whether the entries
-// are the mask's own ranks is not: a range call holds the DIFFERENCE of the two entries it reads against the mask's set bits
-// (the sparse merge's count) and nothing more, so two entries wrong by the same amount pass.
-int ghf_sparse_rank_parse(const uint8_t* h, size_t bytes, ghf_sparse_rank_info* info) {
-  if (!h || !info) return GHF_E_INVAL;
-  std::memset(info, 0, sizeof *info);
-  if (bytes < kSparseRankHeaderBytes + 8) return GHF_E_FORMAT;
-  if (le64(h) != kSparseRankMagic || le32(h + 8) != kSparseRankVersion || le32(h + 12) != kSparseRankElems) return GHF_E_FORMAT;
-  const uint64_t n = le64(h + 16), n_vals = le64(h + 24), nb = le64(h + 32);
-  if (nb != rank_blocks_for(n) || n_vals > n) return GHF_E_FORMAT;
-  for (size_t i = 40; i < kSparseRankHeaderBytes; ++i)
-    if (h[i]) return GHF_E_FORMAT;
-  if ((bytes - kSparseRankHeaderBytes) / 8 != nb + 1 || (bytes & 7u)) return GHF_E_FORMAT;  // truncated, or something behind it
-  const uint8_t* cum = h + kSparseRankHeaderBytes;
-  uint64_t prev = le64(cum);
-  if (prev != 0) return GHF_E_FORMAT;
-  for (uint64_t j = 1; j <= nb; ++j) {
-    const uint64_t v = le64(cum + 8 * j), elems = j < nb ? kSparseRankElems : n - (nb - 1) * kSparseRankElems;
-    if (v < prev || v - prev > elems) return GHF_E_FORMAT;  // a rank block has no more non-zero bytes than bytes
-    prev = v;
-  }
-  if (prev != n_vals) return GHF_E_FORMAT;
-  info->n = n;
-  info->n_vals = n_vals;
-  info->n_blocks = nb;
-  info->version = kSparseRankVersion;
-  return GHF_OK;
-}
-
-int ghf_sparse_merge_at(ghf_ctx* c, const uint8_t* d_mask, const uint8_t* d_vals, size_t vals_skip, size_t n_vals, size_t n, uint8_t* d_out) {
-  if (!c || !d_mask || !d_out || (n_vals && !d_vals)) return GHF_E_INVAL;
-  if (!aligned16(d_mask) || !aligned16(d_vals) || !aligned16(d_out))
-    return fail(c, GHF_E_INVAL, "ghf_sparse_merge_at: d_mask, d_vals and d_out must be 16-byte aligned");
-  if (n > (size_t)-1 - kSparseTile || vals_skip + n_vals < vals_skip) return fail(c, GHF_E_INVAL, "ghf_sparse_merge_at: n or vals_skip + n_vals overflows");
-  if (n == 0) return fail(c, GHF_E_EMPTY, "ghf_sparse_merge_at: no bytes");
-  GHF_HIP(c, hipSetDevice(c->device));
-  launch_sparse_merge_at(d_mask, d_vals, vals_skip, n_vals, n, d_out, c->d_sparse_counts, c->d_sparse_offs, c->d_status, c->stream);
-  GHF_HIP(c, hipGetLastError());
-  return GHF_OK;
-}
-
-int ghf_compress_planes_sparse_ranked(ghf_ctx* c, const uint8_t* d_in, size_t n_elems, uint32_t elem_bytes, unsigned sparse_planes,
-                                      uint8_t* d_out, size_t slot_bytes, uint64_t* d_out_bytes, ghf_code* d_codes, ghf_index* h_indexes,
-                                      unsigned* h_sparse_planes, size_t* h_n_vals, uint8_t* d_ranks, size_t rank_slot_bytes) {
-  return compress_planes_sparse(c, "ghf_compress_planes_sparse_ranked", d_in, no_base(), n_elems, elem_bytes, sparse_planes, d_out, slot_bytes,
-                                d_out_bytes, d_codes, h_indexes, h_sparse_planes, h_n_vals, {true, d_ranks, rank_slot_bytes});
-}
-int ghf_compress_planes_sparse_ranked_delta(ghf_ctx* c, const uint8_t* d_in, const uint8_t* d_base, size_t n_elems, uint32_t elem_bytes,
-                                            unsigned sparse_planes, uint8_t* d_out, size_t slot_bytes, uint64_t* d_out_bytes,
-                                            ghf_code* d_codes, ghf_index* h_indexes, unsigned* h_sparse_planes, size_t* h_n_vals,
-                                            uint8_t* d_ranks, size_t rank_slot_bytes) {
-  return compress_planes_sparse(c, "ghf_compress_planes_sparse_ranked_delta", d_in, base_of(d_base), n_elems, elem_bytes, sparse_planes, d_out,
-                                slot_bytes, d_out_bytes, d_codes, h_indexes, h_sparse_planes, h_n_vals, {true, d_ranks, rank_slot_bytes});
-}
-
-// one stored stream of a range call: which symbols of it the call decodes, and where to
-struct RangePart {
-  uint32_t slot;      // in the caller's arrays of 2 * elem_bytes
-  uint64_t lo, hi;    // symbols [lo, hi) of the stream; lo is a multiple of kBlockSymbols
-  uint64_t symbols;   // of the whole stream
-  uint8_t* to;        // symbol lo lands here (16-byte aligned)
-  size_t cap;
-};
-
-static int decode_planes_sparse_range(ghf_ctx* c, const char* who, const uint8_t* const* h_stream_ptrs, const size_t* h_stream_bytes,
-                                      const ghf_code* d_codes, const ghf_index* indexes, const ghf_seek_info* h_infos,
-                                      const uint8_t* const* h_table_ptrs, const size_t* h_table_bytes,
-                                      const ghf_sparse_rank_info* h_rank_infos, const uint8_t* const* h_rank_ptrs, Base base,
-                                      unsigned raw_planes, unsigned sparse_planes, size_t n_elems, uint32_t elem_bytes, uint64_t first,
-                                      uint64_t count, uint8_t* d_out, size_t cap) {
-  // the codes of raw planes are not looked at: a tensor of nothing but raw planes needs none
-  const bool all_raw = elem_bytes_ok(elem_bytes) && raw_planes == (1u << elem_bytes) - 1u;
-  if (!c || !h_stream_ptrs || !h_stream_bytes || (!d_codes && !all_raw) || !d_out || base.null()) return GHF_E_INVAL;
-  const std::string f = std::string(who) + ": ";
-  if (!elem_bytes_ok(elem_bytes)) return fail(c, GHF_E_INVAL, (f + "elem_bytes must be 2, 4 or 8").c_str());
-  const uint32_t E = elem_bytes;
-  const bool by_table = h_infos || h_table_ptrs || h_table_bytes;
-  if ((indexes != nullptr) == by_table || (by_table && !(h_infos && h_table_ptrs && h_table_bytes)))
-    return fail(c, GHF_E_INVAL, (f + "exactly one of indexes / (h_infos, h_table_ptrs, h_table_bytes) must be given").c_str());
-  // a raw plane has a stream pointer and a size and nothing else: its index, info and table are not read
-  auto raw = [&](uint32_t p) { return ((raw_planes >> p) & 1u) != 0; };
-  // what ghf_decode_planes_range asks of a plane, of one stored stream
-  auto pointers_ok = [&](uint32_t j) {
-    return h_stream_ptrs[j] && aligned16(h_stream_ptrs[j]) && (!by_table || raw(j) || (h_table_ptrs[j] && aligned16(h_table_ptrs[j])));
-  };
-  auto symbols_of = [&](uint32_t j) -> uint64_t { return by_table ? h_infos[j].n_symbols : indexes[j].n_symbols; };
-  auto index_ok = [&](uint32_t j) { return by_table || indexes[j].n_symbols == 0 || index_is_whole(&indexes[j]); };
-  for (uint32_t p = 0; p < E; ++p)
-    if (!pointers_ok(p)) return fail(c, GHF_E_INVAL, (f + "a stream or table pointer is null or not 16-byte aligned").c_str());
-  if (!aligned16(d_out) || base.misaligned()) return fail(c, GHF_E_INVAL, (f + "d_out and d_base must be 16-byte aligned").c_str());
-  for (uint32_t p = 0; p < E; ++p)
-    if (!raw(p) && !index_ok(p)) return fail(c, GHF_E_INVAL, (f + "malformed index").c_str());
-  if (first > n_elems || count > n_elems - first) return fail(c, GHF_E_INVAL, (f + "first + count exceeds n_elems").c_str());
-  // the workspace holds the range from the start of its first rank block to the end of its last, and a vector more
-  const size_t slack = 2 * (size_t)kSparseRankElems + 16;
-  if (count > (size_t)-1 - slack || workspace_overflow((size_t)count + slack, E))
-    return fail(c, GHF_E_INVAL, (f + "count * elem_bytes overflows").c_str());
-  for (uint32_t p = 0; by_table && p < E; ++p) {
-    if (raw(p)) continue;
-    const int rc = seek_table_ok(c, who, h_infos + p, h_table_ptrs[p], h_table_bytes[p]);
-    if (rc) return rc;
-  }
-  if (cap < count * E) return fail(c, GHF_E_CAP, (f + "output capacity below count * elem_bytes").c_str());
-  // ... and what the sparse form adds
-  if (!sparse_planes_ok(sparse_planes, E, false))
-    return fail(c, GHF_E_INVAL, (f + "sparse_planes has bits below elem_bytes only (the mask the compress call reported)").c_str());
-  // ... and the raw form
-  if (!forms_ok(raw_planes, sparse_planes, E, false))
-    return fail(c, GHF_E_INVAL, (f + "raw_planes has bits below elem_bytes only, none of them a sparse plane's").c_str());
-  for (uint32_t p = 0; p < E; ++p)
-    if (raw(p) && h_stream_bytes[p] != n_elems) return fail(c, GHF_E_INVAL, (f + "a raw plane does not have n_elems bytes").c_str());
-  if (sparse_planes && (!h_rank_infos || !h_rank_ptrs)) return fail(c, GHF_E_INVAL, (f + "sparse planes need their rank tables").c_str());
-  const uint64_t mask_bytes = ghf_sparse_mask_bytes(n_elems);
-  for (uint32_t p = 0; p < E; ++p) {
-    if (!((sparse_planes >> p) & 1u)) continue;
-    if (!h_rank_ptrs[p]) return fail(c, GHF_E_INVAL, (f + "a sparse plane has no rank table").c_str());
-    if (h_rank_infos[p].n != n_elems) return fail(c, GHF_E_INVAL, (f + "a rank table is not one of n_elems elements").c_str());
-    if (h_rank_infos[p].version != kSparseRankVersion || h_rank_infos[p].n_blocks != rank_blocks_for(n_elems) || h_rank_infos[p].n_vals > n_elems)
-      return fail(c, GHF_E_FORMAT, (f + "a rank info is not what ghf_sparse_rank_parse fills in").c_str());
-  }
-  for (uint32_t p = 0; p < E; ++p) {
-    if (raw(p)) continue;
-    const bool sparse = (sparse_planes >> p) & 1u;
-    if (symbols_of(p) != (sparse ? mask_bytes : (uint64_t)n_elems))
-      return fail(c, GHF_E_INVAL, sparse ? (f + "a mask stream does not have ghf_sparse_mask_bytes(n_elems) symbols").c_str()
-                                         : (f + "a dense stream does not have n_elems symbols").c_str());
-    if (!sparse || h_rank_infos[p].n_vals == 0) continue;  // the values slot of any other plane is ignored
-    if (!pointers_ok(E + p)) return fail(c, GHF_E_INVAL, (f + "a stream or table pointer is null or not 16-byte aligned").c_str());
-    if (!index_ok(E + p)) return fail(c, GHF_E_INVAL, (f + "malformed index").c_str());
-    if (symbols_of(E + p) != h_rank_infos[p].n_vals)
-      return fail(c, GHF_E_INVAL, (f + "a values stream does not have the symbols its rank table counts").c_str());
-    if (by_table) {
-      const int rc = seek_table_ok(c, who, h_infos + E + p, h_table_ptrs[E + p], h_table_bytes[E + p]);
-      if (rc) return rc;
-    }
-  }
-  if (count == 0) return GHF_OK;
-  if (!sparse_planes && !raw_planes)  // nothing sparse: the origin of section 17, and its call
-    return decode_planes_range(c, who, h_stream_ptrs, h_stream_bytes, d_codes, indexes, h_infos, h_table_ptrs, h_table_bytes, base, E, first,
-                               count, d_out, cap);
-  // THE PLAN.  The common origin of all planes is the start of the rank block that holds `first`: a multiple of 4096 for a
-  // dense plane, of 4096 mask bytes for a mask, and the values in front of it number cum[b0].  A sparse plane is rebuilt for the
-  // whole rank blocks [b0, b1) (cut at n_elems): the sub-string's mask bytes are whole, so its last mask byte obeys the pad rule.
-  // With raw planes and no sparse one the origin is section 17's, the start of the seek block that holds `first`.  A raw plane has
-  // no part in the plan: nothing of it is decoded or copied, the merge reads it at stream + first.
-  const uint64_t origin = sparse_planes ? kSparseRankElems : kBlockSymbols;
-  const uint64_t from = first - first % origin, end = first + count;
-  const uint64_t b0 = from / kSparseRankElems, b1 = rank_blocks_for(end);
-  const uint64_t sub_n = (sparse_planes ? std::min<uint64_t>(b1 * kSparseRankElems, n_elems) : end) - from;
-  const uint64_t m_lo = b0 * (kSparseRankElems / 8), m_hi = std::min<uint64_t>(b1 * (kSparseRankElems / 8), mask_bytes);
-  uint64_t v_lo[GHF_PLANES_MAX] = {}, v_hi[GHF_PLANES_MAX] = {};
-  for (uint32_t p = 0; p < E; ++p) {
-    if (!((sparse_planes >> p) & 1u)) continue;
-    const uint8_t* cum = h_rank_ptrs[p] + kSparseRankHeaderBytes;
-    v_lo[p] = le64(cum + 8 * b0);
-    v_hi[p] = le64(cum + 8 * b1);
-    if (v_lo[p] > v_hi[p] || v_hi[p] > h_rank_infos[p].n_vals || v_hi[p] - v_lo[p] > sub_n)
-      return fail(c, GHF_E_FORMAT, (f + "the rank table's entries for the range are not ordered ranks").c_str());
-  }
-  GHF_HIP(c, hipSetDevice(c->device));
-  size_t stride = 0;
-  int rc = all_raw ? GHF_OK : planes_workspace(c, (size_t)sub_n + 16, E, &stride);
-  // the second workspace: the sub-string's mask, and behind it its values from the start of their first seek block
-  const size_t mask_stride = ((size_t)(m_hi - m_lo) + 255) & ~(size_t)255;
-  const size_t vals_room = ((size_t)sub_n + kBlockSymbols + 255) & ~(size_t)255;
-  if (!rc && sparse_planes) rc = grow(c, c->sparse, mask_stride + vals_room);
-  if (rc) return rc;
-  uint8_t *d_mask = c->sparse.p, *d_vals = c->sparse.p + mask_stride;
-  RangePart parts[2 * GHF_PLANES_MAX];
-  uint32_t n_parts = 0;
-  for (uint32_t p = 0; p < E; ++p) {
-    if (raw(p)) continue;
-    if (!((sparse_planes >> p) & 1u)) {
-      parts[n_parts++] = {p, from, end, n_elems, c->planes.p + p * stride, stride};
-      continue;
-    }
-    parts[n_parts++] = {p, m_lo, m_hi, mask_bytes, d_mask, mask_stride};
-    if (v_hi[p] > v_lo[p]) parts[n_parts++] = {E + p, v_lo[p] - v_lo[p] % kBlockSymbols, v_hi[p], h_rank_infos[p].n_vals, d_vals, vals_room};
-  }
-  // behind the last stored stream of a sparse plane (its values, or its mask when the sub-string has none): the plane's merge
-  auto merge_behind = [&](uint32_t j) {
-    const uint32_t p = j % E;
-    if (((sparse_planes >> p) & 1u) && (j >= E || v_hi[p] == v_lo[p]))
-      launch_sparse_merge_at(d_mask, d_vals, v_lo[p] % kBlockSymbols, v_hi[p] - v_lo[p], sub_n, c->planes.p + p * stride, c->d_sparse_counts,
-                             c->d_sparse_offs, c->d_status, c->stream);
-  };
-  if (!n_parts) {
-    // every plane is raw: the merge below is the whole call
-  } else if (by_table) {
-    // One launch expands the covered blocks of every stored stream (k_seek_expand_streams): expanding each by itself would
-    // pay k_seek_expand's latency floor up to 2 E times (DESIGN.md section 17 has the measurement).  Every stream gets tables of
-    // its own, alive until its K7 has run.
-    const size_t segs_per_block = kBlockSymbols / kSegSymbols;
-    size_t blocks = 0;
-    for (uint32_t i = 0; i < n_parts; ++i) blocks += (size_t)(blocks_for(parts[i].hi) - parts[i].lo / kBlockSymbols);
-    if (!(rc = grow(c, c->range_dt, 2 * GHF_PLANES_MAX))) rc = grow(c, c->range_chunk, blocks, 1024);
-    if (!rc) rc = grow(c, c->range_seg, blocks * segs_per_block, 1024 * 64);
-    if (rc) return rc;
-    SeekExpandStreamsParams a = {};
-    size_t at = 0;
-    uint32_t stored = 0;
-    for (uint32_t i = 0; i < n_parts; ++i) stored |= 1u << parts[i].slot;
-    launch_build_decode_tables_slots(d_codes, c->range_dt.p, 2 * E, stored, c->d_status, c->stream);  // range_dt[j]: the tables of slot j
-    for (uint32_t i = 0; i < n_parts; ++i) {
-      const uint32_t j = parts[i].slot;
-      SeekExpandParams& x = a.stream[i];
-      x.records = h_table_ptrs[j] + kSeekHeaderBytes;
-      x.stream = h_stream_ptrs[j];
-      x.stream_bytes = h_stream_bytes[j];
-      x.dt = c->range_dt.p + j;
-      x.n_symbols = parts[i].symbols;
-      x.n_blocks = h_infos[j].n_blocks;
-      x.g0 = parts[i].lo / kBlockSymbols;
-      x.g1 = blocks_for(parts[i].hi);
-      x.chunk_bit = c->range_chunk.p + at;
-      x.seg_bit = c->range_seg.p + at * segs_per_block;
-      x.status = c->d_status;
-      at += (size_t)(x.g1 - x.g0);
-    }
-    launch_seek_expand_streams(a, n_parts, c->stream);
-    GHF_HIP(c, hipGetLastError());
-    for (uint32_t i = 0; i < n_parts; ++i) {  // K7 on the expanded view, set up as ghf_decode_planes_range sets it up
-      const uint32_t j = parts[i].slot;
-      DecParams d = {};
-      d.stream = h_stream_ptrs[j];
-      d.stream_bytes = h_stream_bytes[j];
-      d.dt = c->range_dt.p + j;
-      d.chunk_bit = a.stream[i].chunk_bit;
-      d.seg_bit = a.stream[i].seg_bit;
-      d.n_symbols = parts[i].hi - parts[i].lo;
-      d.n_segs = segs_for(d.n_symbols);
-      d.no_end_mark = (parts[i].hi == parts[i].symbols && !(h_infos[j].flags & GHF_INDEX_NO_END_MARK)) ? 0u : 1u;
-      d.out = parts[i].to;
-      d.out_bytes = nullptr;
-      d.status = c->d_status;
-      launch_decode(d, c->stream);
-      merge_behind(j);
-    }
-  } else {
-    for (uint32_t i = 0; i < n_parts; ++i) {
-      const uint32_t j = parts[i].slot;
-      if ((rc = ghf_decode_range(c, h_stream_ptrs[j], h_stream_bytes[j], d_codes + j, indexes + j, nullptr, nullptr, 0, parts[i].lo,
-                                 parts[i].hi - parts[i].lo, parts[i].to, parts[i].cap)))
-        return rc;
-      merge_behind(j);
-    }
-  }
-  // nothing reaches d_out behind a failed decode or a count that does not match the rank table
-  if (!raw_planes) {
-    launch_planes_merge_range(c->planes.p, stride, base.p, first - from, count, E, d_out, c->d_status, c->stream);
-  } else {
-    // the workspace planes start 256-byte aligned at element `from`, a multiple of 4096, and a raw plane 16-byte aligned at
-    // element 0: the run's first byte stands first % 16 behind a vector in every one of them
-    const uint8_t* src[GHF_PLANES_MAX];
-    for (uint32_t p = 0; p < E; ++p) src[p] = raw(p) ? h_stream_ptrs[p] + first : c->planes.p + p * stride + (first - from);
-    launch_planes_merge_from(src, base.p, count, E, d_out, c->d_status, c->stream);
-  }
-  GHF_HIP(c, hipGetLastError());
-  return GHF_OK;
-}
-
-int ghf_decode_planes_sparse_range(ghf_ctx* c, const uint8_t* const* h_stream_ptrs, const size_t* h_stream_bytes, const ghf_code* d_codes,
-                                   const ghf_index* indexes, const ghf_seek_info* h_infos, const uint8_t* const* h_table_ptrs,
-                                   const size_t* h_table_bytes, const ghf_sparse_rank_info* h_rank_infos, const uint8_t* const* h_rank_ptrs,
-                                   unsigned sparse_planes, size_t n_elems, uint32_t elem_bytes, uint64_t first, uint64_t count, uint8_t* d_out,
-                                   size_t cap) {
-  return decode_planes_sparse_range(c, "ghf_decode_planes_sparse_range", h_stream_ptrs, h_stream_bytes, d_codes, indexes, h_infos, h_table_ptrs,
-                                    h_table_bytes, h_rank_infos, h_rank_ptrs, no_base(), 0, sparse_planes, n_elems, elem_bytes, first, count,
-                                    d_out, cap);
-}
-int ghf_decode_planes_sparse_range_delta(ghf_ctx* c, const uint8_t* const* h_stream_ptrs, const size_t* h_stream_bytes, const ghf_code* d_codes,
-                                         const ghf_index* indexes, const ghf_seek_info* h_infos, const uint8_t* const* h_table_ptrs,
-                                         const size_t* h_table_bytes, const ghf_sparse_rank_info* h_rank_infos,
-                                         const uint8_t* const* h_rank_ptrs, const uint8_t* d_base, unsigned sparse_planes, size_t n_elems,
-                                         uint32_t elem_bytes, uint64_t first, uint64_t count, uint8_t* d_out, size_t cap) {
-  return decode_planes_sparse_range(c, "ghf_decode_planes_sparse_range_delta", h_stream_ptrs, h_stream_bytes, d_codes, indexes, h_infos,
-                                    h_table_ptrs, h_table_bytes, h_rank_infos, h_rank_ptrs, base_of(d_base), 0, sparse_planes, n_elems,
-                                    elem_bytes, first, count, d_out, cap);
-}
-
-// ---------------------------------------------------------------------------------------------- byte planes in three forms
-// (no reference counterpart).  In this family d_base is optional: null is the plain call
-static inline Base base_opt(const uint8_t* d_base) { return d_base ? base_of(d_base) : no_base(); }
-
-// what the three pointer calls check alike: `d_inter` is the interleaved side, `h_ptrs` the host array of plane addresses;
-// *skew <- their common address mod 16 (the split wants 0)
-static int plane_ptrs_args(ghf_ctx* c, const char* who, const uint8_t* d_inter, const uint8_t* const* h_ptrs, const uint8_t* d_base,
-                           size_t n_elems, uint32_t elem_bytes, uint32_t* skew) {
-  if (!c || !d_inter || !h_ptrs) return GHF_E_INVAL;
-  const std::string f = std::string(who) + ": ";
-  if (!elem_bytes_ok(elem_bytes)) return fail(c, GHF_E_INVAL, (f + "elem_bytes must be 2, 4 or 8").c_str());
-  for (uint32_t p = 0; p < elem_bytes; ++p)
-    if (!h_ptrs[p]) return fail(c, GHF_E_INVAL, (f + "a plane pointer is null").c_str());
-  *skew = (uint32_t)(reinterpret_cast<uintptr_t>(h_ptrs[0]) & 15u);
-  for (uint32_t p = 1; p < elem_bytes; ++p)
-    if ((reinterpret_cast<uintptr_t>(h_ptrs[p]) & 15u) != *skew)
-      return fail(c, GHF_E_INVAL, (f + "the plane pointers do not have the same address modulo 16").c_str());
-  if (!aligned16(d_inter) || !aligned16(d_base)) return fail(c, GHF_E_INVAL, (f + "d_in / d_out and d_base must be 16-byte aligned").c_str());
-  if (elems_overflow(n_elems, elem_bytes)) return fail(c, GHF_E_INVAL, (f + "n_elems * elem_bytes overflows").c_str());
-  if (n_elems == 0) return fail(c, GHF_E_EMPTY, (f + "no elements").c_str());
-  return GHF_OK;
-}
-
-int ghf_planes_split_to(ghf_ctx* c, const uint8_t* d_in, const uint8_t* d_base, size_t n_elems, uint32_t elem_bytes,
-                        uint8_t* const* h_plane_ptrs) {
-  uint32_t skew = 0;
-  const int rc = plane_ptrs_args(c, "ghf_planes_split_to", d_in, h_plane_ptrs, d_base, n_elems, elem_bytes, &skew);
-  if (rc) return rc;
-  if (skew) return fail(c, GHF_E_INVAL, "ghf_planes_split_to: the plane pointers must be 16-byte aligned");
-  GHF_HIP(c, hipSetDevice(c->device));
-  launch_planes_split_to(d_in, d_base, n_elems, elem_bytes, h_plane_ptrs, c->stream);
-  GHF_HIP(c, hipGetLastError());
-  return GHF_OK;
-}
-
-int ghf_planes_merge_from(ghf_ctx* c, const uint8_t* const* h_plane_ptrs, const uint8_t* d_base, size_t n_elems, uint32_t elem_bytes,
-                          uint8_t* d_out) {
-  uint32_t skew = 0;
-  const int rc = plane_ptrs_args(c, "ghf_planes_merge_from", d_out, h_plane_ptrs, d_base, n_elems, elem_bytes, &skew);
-  if (rc) return rc;
-  if (skew) return fail(c, GHF_E_INVAL, "ghf_planes_merge_from: the plane pointers must be 16-byte aligned");
-  GHF_HIP(c, hipSetDevice(c->device));
-  launch_planes_merge_from(h_plane_ptrs, d_base, n_elems, elem_bytes, d_out, nullptr, c->stream);
-  GHF_HIP(c, hipGetLastError());
-  return GHF_OK;
-}
-
-int ghf_planes_merge_range_from(ghf_ctx* c, const uint8_t* const* h_plane_ptrs, const uint8_t* d_base, size_t count, uint32_t elem_bytes,
-                                uint8_t* d_out) {
-  uint32_t skew = 0;
-  const int rc = plane_ptrs_args(c, "ghf_planes_merge_range_from", d_out, h_plane_ptrs, d_base, count, elem_bytes, &skew);
-  if (rc) return rc;
-  GHF_HIP(c, hipSetDevice(c->device));
-  launch_planes_merge_from(h_plane_ptrs, d_base, count, elem_bytes, d_out, nullptr, c->stream);  // the common skew picks the kernel
-  GHF_HIP(c, hipGetLastError());
-  return GHF_OK;
-}
-
-int ghf_compress_planes_forms(ghf_ctx* c, const uint8_t* d_in, const uint8_t* d_base, size_t n_elems, uint32_t elem_bytes,
-                              unsigned raw_planes, unsigned sparse_planes, uint8_t* d_out, size_t slot_bytes, uint64_t* d_out_bytes,
-                              ghf_code* d_codes, ghf_index* h_indexes, uint8_t* d_ranks, size_t rank_slot_bytes, unsigned* h_raw_planes,
-                              unsigned* h_sparse_planes, size_t* h_n_vals) {
-  if (!c || !d_in || !d_out || !d_out_bytes || !h_raw_planes || !h_sparse_planes || !h_n_vals) return GHF_E_INVAL;
-  const char* f = "ghf_compress_planes_forms: ";
-  auto say = [&](const char* what) { return std::string(f) + what; };
-  if (!elem_bytes_ok(elem_bytes)) return fail(c, GHF_E_INVAL, say("elem_bytes must be 2, 4 or 8").c_str());
-  const uint32_t E = elem_bytes;
-  if (!aligned16(d_in) || !aligned16(d_out) || (slot_bytes & 15u) || !aligned16(d_codes) || !aligned16(d_base))
-    return fail(c, GHF_E_INVAL, say("d_in, d_base, d_out, d_codes and slot_bytes must be multiples of 16").c_str());
-  if (d_ranks && (!aligned16(d_ranks) || (rank_slot_bytes & 15u)))
-    return fail(c, GHF_E_INVAL, say("d_ranks and rank_slot_bytes must be multiples of 16").c_str());
-  if (!sparse_planes_ok(sparse_planes, E, true))
-    return fail(c, GHF_E_INVAL, say("sparse_planes is GHF_SPARSE_AUTO alone or has bits below elem_bytes only").c_str());
-  if (!forms_ok(raw_planes, sparse_planes, E, true))
-    return fail(c, GHF_E_INVAL, say("raw_planes is GHF_RAW_AUTO alone or has bits below elem_bytes only, none of them a sparse plane's").c_str());
-  if (workspace_overflow(n_elems, E)) return fail(c, GHF_E_INVAL, say("n_elems * elem_bytes overflows").c_str());
-  if (n_elems == 0) return fail(c, GHF_E_EMPTY, say("no elements").c_str());
-  if (slot_bytes < ghf_planes_slot_bytes(n_elems)) return fail(c, GHF_E_CAP, say("slot_bytes below ghf_planes_slot_bytes(n_elems)").c_str());
-  if (d_ranks && rank_slot_bytes < ghf_sparse_rank_bytes(n_elems))
-    return fail(c, GHF_E_CAP, say("rank_slot_bytes below ghf_sparse_rank_bytes(n_elems)").c_str());
-  GHF_HIP(c, hipSetDevice(c->device));
-  const bool raw_auto = raw_planes == GHF_RAW_AUTO, sparse_auto = sparse_planes == GHF_SPARSE_AUTO;
-  const unsigned all = (1u << E) - 1u;
-  // the counts are needed on the HOST for a choice and for the value counts of sparse planes, on the device for every code
-  const bool wait = raw_auto || sparse_auto || sparse_planes != 0;
-  int rc = GHF_OK;
-  // [0, 2 MAX): the codes of the stored streams when the caller wants none; [2 MAX, 3 MAX): the codes the choice is priced with
-  if ((rc = grow(c, c->batch_codes, 3 * GHF_PLANES_MAX))) return rc;
-  ghf_code* codes = d_codes ? d_codes : c->batch_codes.p;
-  ghf_code* priced = c->batch_codes.p + 2 * GHF_PLANES_MAX;
-  uint64_t* d_prices = c->d_planes_hists + (size_t)GHF_PLANES_MAX * GHF_NSYM;
-  if (wait || raw_planes != all)
-    if ((rc = histogram_planes_into(c, say("histogram launch").c_str(), d_in, d_base, n_elems, E, 0, c->d_planes_hists))) return rc;
-  unsigned raw_chosen = raw_auto ? 0u : raw_planes, sparse_chosen = sparse_auto ? 0u : sparse_planes;
-  std::memset(h_n_vals, 0, E * sizeof *h_n_vals);
-  if (wait) {
-    // THE ONE WAIT of the call.  With GHF_RAW_AUTO the codes of all planes and the sizes of their images are queued in front of
-    // it, and one copy brings the counts and the sizes back; the dense planes are then packed with those codes
-    if (raw_auto) {
-      if ((rc = ghf_build_codes(c, c->d_planes_hists, E, priced, 0))) return rc;
-      launch_planes_image_bytes(c->d_planes_hists, priced, E, d_prices, c->stream);
-      GHF_HIP(c, hipGetLastError());
-    }
-    uint64_t got[GHF_PLANES_MAX * GHF_NSYM + GHF_PLANES_MAX];
-    GHF_HIP(c, hipMemcpyAsync(got, c->d_planes_hists, sizeof got, hipMemcpyDeviceToHost, c->stream));
-    GHF_HIP(c, hipStreamSynchronize(c->stream));
-    const uint64_t* prices = got + (size_t)GHF_PLANES_MAX * GHF_NSYM;
-    // a sparse plane stores two headers: at or below that size the raw form is the smaller one whatever the plane holds
-    const bool sparse_pays = !raw_auto || n_elems > 2 * ghf_header_bytes(1);
-    for (uint32_t p = 0; p < E; ++p) {
-      const uint64_t zeros = got[(size_t)p * GHF_NSYM];
-      if (zeros > n_elems) return fail(c, GHF_E_HIP, say("the plane counts did not arrive").c_str());
-      h_n_vals[p] = n_elems - (size_t)zeros;
-      if (sparse_auto && !((raw_chosen >> p) & 1u) && sparse_pays && zeros >= n_elems - n_elems / 4) sparse_chosen |= 1u << p;
-      // prices[p] == 0: the plane has no code (a count at or above 2^55); it stays dense, and the dense path latches why
-      if (raw_auto && !((sparse_chosen >> p) & 1u) && prices[p] >= n_elems) raw_chosen |= 1u << p;
-    }
-  }
-  *h_raw_planes = raw_chosen;
-  *h_sparse_planes = sparse_chosen;
-  auto raw = [&](uint32_t p) { return ((raw_chosen >> p) & 1u) != 0; };
-  auto sparse = [&](uint32_t p) { return ((sparse_chosen >> p) & 1u) != 0; };
-  size_t stride = 0, mask_stride = 0;
-  if (raw_chosen != all) rc = planes_workspace(c, n_elems, E, &stride);
-  if (!rc && sparse_chosen) rc = sparse_workspace(c, n_elems, &mask_stride);
-  if (rc) return rc;
-  const size_t mask_bytes = ghf_sparse_mask_bytes(n_elems);
-  if (h_indexes) {  // one side-car per stream that has a code, of that stream's own symbol count; a raw plane has none
-    std::memset(h_indexes, 0, 2 * E * sizeof *h_indexes);
-    for (uint32_t p = 0; p < E && !rc; ++p) {
-      if (raw(p)) continue;
-      rc = ghf_index_alloc(c, sparse(p) ? mask_bytes : n_elems, &h_indexes[p]);
-      if (!rc && sparse(p) && h_n_vals[p]) rc = ghf_index_alloc(c, h_n_vals[p], &h_indexes[E + p]);
-    }
-    if (rc) {
-      free_indexes(c, h_indexes, 2 * E);
-      return rc;
-    }
-  }
-  GHF_HIP(c, hipMemsetAsync(d_out_bytes, 0, 2 * E * sizeof(uint64_t), c->stream));  // the empty slots
-  // the split writes a raw plane straight into its slot and every other plane into the workspace
-  if (!raw_chosen) {
-    launch_planes_split(d_in, d_base, n_elems, E, c->planes.p, stride, c->stream);
-  } else {
-    uint8_t* to[GHF_PLANES_MAX];
-    for (uint32_t p = 0; p < E; ++p) to[p] = raw(p) ? d_out + p * slot_bytes : c->planes.p + p * stride;
-    launch_planes_split_to(d_in, d_base, n_elems, E, to, c->stream);
-  }
-  GHF_HIP(c, hipGetLastError());
-  uint8_t *d_mask = c->sparse.p, *d_vals = c->sparse.p + mask_stride;
-  for (uint32_t p = 0; p < E && !rc; ++p) {
-    if (raw(p)) {
-      launch_store_u64(d_out_bytes + p, nullptr, (uint64_t)n_elems, c->stream);
-      GHF_HIP(c, hipGetLastError());
-      continue;
-    }
-    const uint8_t* plane = c->planes.p + p * stride;
-    // K1 has not seen what stands at these addresses now: the workspaces are refilled for every plane
-    c->hist.forget();
-    c->plan.forget();
-    if (!sparse(p)) {  // what ghf_compress_planes_coded(GHF_PLANES_BUILD_CODES) queues for the plane
-      const ghf_code* code = raw_auto ? priced + p : codes + p;
-      if (!raw_auto && (rc = ghf_build_codes(c, c->d_planes_hists + (size_t)p * GHF_NSYM, 1, codes + p, 0))) break;
-      if ((rc = ghf_encode_plan(c, plane, n_elems, code, &c->d->total_bits))) break;
-      if ((rc = ghf_encode_emit(c, plane, n_elems, code, nullptr, GHF_EMIT_LAST | GHF_EMIT_HEADER, d_out + p * slot_bytes, slot_bytes,
-                                h_indexes ? h_indexes + p : nullptr, c->d->end)))
-        break;
-      launch_store_u64(d_out_bytes + p, &c->d->end[1], 0, c->stream);
-      GHF_HIP(c, hipGetLastError());
-      if (raw_auto && d_codes) GHF_HIP(c, hipMemcpyAsync(d_codes + p, code, sizeof(ghf_code), hipMemcpyDeviceToDevice, c->stream));
-      continue;
-    }
-    launch_sparse_split(plane, n_elems, d_mask, d_vals, n_elems, c->d_sparse_offs + kSparseOffWords - 1, c->d_sparse_counts, c->d_sparse_offs,
-                        c->d_status, c->stream);
-    // the plane's rank table, while its mask stands in the workspace; the split is done with the counts and offsets
-    if (d_ranks) launch_sparse_rank_pack(d_mask, n_elems, d_ranks + p * rank_slot_bytes, c->d_sparse_counts, c->d_sparse_offs, c->d_status, c->stream);
-    GHF_HIP(c, hipGetLastError());
-    // compressor.h:62-73 for the mask and for the values, each a byte string of its own
-    if ((rc = ghf_compress(c, d_mask, mask_bytes, d_out + p * slot_bytes, slot_bytes, d_out_bytes + p, codes + p,
-                           h_indexes ? h_indexes + p : nullptr)))
-      break;
-    if (h_n_vals[p])
-      rc = ghf_compress(c, d_vals, h_n_vals[p], d_out + (E + p) * slot_bytes, slot_bytes, d_out_bytes + E + p, codes + E + p,
-                        h_indexes ? h_indexes + E + p : nullptr);
-  }
-  c->hist.forget();
-  c->plan.forget();
-  return rc;
-}
-
-int ghf_decode_planes_forms(ghf_ctx* c, const uint8_t* const* h_stream_ptrs, const size_t* h_stream_bytes, const ghf_code* d_codes,
-                            const ghf_index* indexes, const uint8_t* d_base, unsigned raw_planes, unsigned sparse_planes,
-                            const size_t* h_n_vals, size_t n_elems, uint32_t elem_bytes, uint8_t* d_out, size_t cap, uint64_t* d_out_bytes) {
-  return decode_planes_sparse(c, "ghf_decode_planes_forms", h_stream_ptrs, h_stream_bytes, d_codes, indexes, base_opt(d_base), raw_planes,
-                              sparse_planes, h_n_vals, n_elems, elem_bytes, d_out, cap, d_out_bytes);
-}
-
-int ghf_decode_planes_forms_range(ghf_ctx* c, const uint8_t* const* h_stream_ptrs, const size_t* h_stream_bytes, const ghf_code* d_codes,
-                                  const ghf_index* indexes, const ghf_seek_info* h_infos, const uint8_t* const* h_table_ptrs,
-                                  const size_t* h_table_bytes, const ghf_sparse_rank_info* h_rank_infos, const uint8_t* const* h_rank_ptrs,
-                                  const uint8_t* d_base, unsigned raw_planes, unsigned sparse_planes, size_t n_elems, uint32_t elem_bytes,
-                                  uint64_t first, uint64_t count, uint8_t* d_out, size_t cap) {
-  return decode_planes_sparse_range(c, "ghf_decode_planes_forms_range", h_stream_ptrs, h_stream_bytes, d_codes, indexes, h_infos,
-                                    h_table_ptrs, h_table_bytes, h_rank_infos, h_rank_ptrs, base_opt(d_base), raw_planes, sparse_planes,
-                                    n_elems, elem_bytes, first, count, d_out, cap);
 }
 
 }  // extern "C"

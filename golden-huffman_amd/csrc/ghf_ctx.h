@@ -1,9 +1,11 @@
-// golden-huffman_amd/csrc/ghf_ctx.h -- the context behind the C ABI of include/ghf.h.  Host-only and private to
-// ghf_api.hip and ghf_comm.hip: what a ghf_ctx owns on the device, and what its workspace currently describes.
+// golden-huffman_amd/csrc/ghf_ctx.h -- the context behind the C ABI of include/ghf.h.  Host-only and private to the ABI
+// units (ghf_api.hip, ghf_api_planes.hip, ghf_comm.hip): what a ghf_ctx owns on the device, what its workspace currently
+// describes, and the few host helpers more than one of those units asks for.
 #ifndef GHF_CTX_H_
 #define GHF_CTX_H_
 #include <algorithm>
 #include <cstddef>
+#include <cstdint>
 #include <string>
 
 #include "ghf_internal.h"
@@ -145,7 +147,7 @@ struct ghf_ctx {
   // launches), and the E x 257 counts of the tensor a ghf_compress_planes_coded is working on (describe nothing between calls).
   // The replicas are zeroed by k_histogram_planes_finish, the launch behind every counting launch: the invariant holds as
   // long as that pair is queued whole.  Where the second launch fails, the host queues a memset of the replicas instead
-  // (histogram_planes_into, ghf_api.hip), so that a later histogram on this context does not start from stale sums.
+  // (histogram_planes_into, ghf_api_planes.hip), so that a later histogram on this context does not start from stale sums.
   uint64_t* d_planes_hist_acc = nullptr;
   uint64_t* d_planes_hists = nullptr;  // [GHF_PLANES_MAX][257], and behind them [GHF_PLANES_MAX] image sizes (ghf_compress_planes_forms)
   // ghf_sparse_split / ghf_sparse_merge: the counts of the workgroups' slabs and their exclusive
@@ -191,6 +193,52 @@ int grow(ghf_ctx* c, DevBuf<T>& b, size_t need, size_t floor = 0, bool* replaced
   if (replaced) *replaced = true;
   return GHF_OK;
 }
+
+// ---- what ghf_api.hip and ghf_api_planes.hip both ask ------------------------------------------------------------------
+inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+
+// the part of "this side-car is one of ours" that packing and decoding both ask for
+inline bool index_has_arrays(const ghf_index* ix) {
+  return ix->d_chunk_bit && ix->d_seg_bit && ix->chunk_symbols == (uint32_t)kBlockSymbols && ix->seg_symbols == (uint32_t)kSegSymbols;
+}
+// ... and its counts are the ones its n_symbols implies
+inline bool index_matches_n(const ghf_index* ix) {
+  return index_has_arrays(ix) && ix->n_segs == segs_for(ix->n_symbols) && ix->n_chunks == blocks_for(ix->n_symbols);
+}
+inline bool index_is_whole(const ghf_index* ix) { return index_matches_n(ix) && ix->n_chunks < kDecMaxGroups; }
+
+// ghf_index and ghf_batch_index: waits for the stream, then frees the two arrays
+template <class Index>
+int free_index_arrays(ghf_ctx* c, Index* idx) {
+  if (!c || !idx) return GHF_E_INVAL;
+  GHF_HIP(c, hipSetDevice(c->device));
+  GHF_HIP(c, hipStreamSynchronize(c->stream));
+  if (idx->d_chunk_bit) (void)hipFree(idx->d_chunk_bit);
+  if (idx->d_seg_bit) (void)hipFree(idx->d_seg_bit);
+  idx->d_chunk_bit = nullptr;
+  idx->d_seg_bit = nullptr;
+  return GHF_OK;
+}
+
+inline uint32_t le32(const uint8_t* p) {
+  return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
+}
+inline uint64_t le64(const uint8_t* p) { return (uint64_t)le32(p) | ((uint64_t)le32(p + 4) << 32); }
+
+// ---- a range of a seekable stream (defined in ghf_api.hip) -----------------------------------------------------------------
+// the part of "this info describes a table of table_bytes" that every consumer of (info, d_table) asks for
+int seek_table_ok(ghf_ctx* c, const char* who, const ghf_seek_info* info, const uint8_t* d_table, size_t table_bytes);
+// k_seek_expand* for blocks [g0, g1) of one stream's table, under the decode tables at dt (which must be queued first): block g's
+// entries land at chunk_bit[g - g0] and seg_bit[(g - g0) * 64]
+SeekExpandParams seek_expand_params(ghf_ctx* c, const ghf_seek_info* info, const uint8_t* d_table, const uint8_t* d_stream,
+                                    size_t stream_bytes, const DecTables* dt, uint64_t g0, uint64_t g1, uint64_t* chunk_bit,
+                                    uint32_t* seg_bit);
+// K7 on a view of a side-car that begins at block g -- chunk_bit / seg_bit point at that block's entries -- and ends with
+// symbol `end` of a stream of n symbols whose index or seek table carries `index_flags`: a segment's start depends on its own
+// block only.  The view's last segment may be cut short by the range; only the stream's own end is followed by the end mark.
+// Symbol g * kBlockSymbols lands at out[0]
+DecParams range_decode_params(ghf_ctx* c, const uint8_t* d_stream, size_t stream_bytes, DecTables* dt, const uint64_t* chunk_bit,
+                              const uint32_t* seg_bit, uint64_t g, uint64_t end, uint64_t n, uint32_t index_flags, uint8_t* out);
 
 }  // namespace ghf
 #endif
