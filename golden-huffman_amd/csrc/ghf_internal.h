@@ -3,6 +3,7 @@
 #define GHF_INTERNAL_H_
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 #include "ghf.h"
 
 namespace ghf {
@@ -48,6 +49,13 @@ constexpr uint32_t kPlanesGroups = 256 * 16;      // one resident round: 16 one-
 constexpr uint32_t kPlanesLdsBytes = 9 * 1024;    // per workgroup: 64 rows of (8 + 1) vectors at E = 8; 6 KiB (E = 2), 5 KiB (E = 4)
 __host__ __device__ constexpr inline uint32_t planes_tile_elems(uint32_t elem_bytes) {
   return (uint32_t)kWave * (elem_bytes < 4 ? 4 : elem_bytes) * 16 / elem_bytes;
+}
+// the launchers' ladder over elem_bytes = 2, 4 or 8 (the callers have checked it): f(std::integral_constant<int, E>())
+template <class F>
+inline void with_elem_bytes(uint32_t elem_bytes, F&& f) {
+  if (elem_bytes == 2) f(std::integral_constant<int, 2>());
+  else if (elem_bytes == 4) f(std::integral_constant<int, 4>());
+  else f(std::integral_constant<int, 8>());
 }
 // the one-pass plane histograms (ghf_planes_hist.hip): K1's 32 KiB of u32 counters, bins[256][32], whose
 // 32 columns are E planes x 32 / E replicas

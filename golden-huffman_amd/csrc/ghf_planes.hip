@@ -13,6 +13,10 @@
 // E consecutive vectors of row l.  A row is padded by one vector, (E + 1) * 16 bytes: the ds_read_b128 / ds_write_b128 of
 // the row side, 16 lanes (8 lanes) at that stride, then fall on distinct banks for every E (12, 20, 36 dwords: 4 * odd).
 // The LDS carries 2 N bytes at 16 bytes per lane and instruction; no barrier is needed, the tile is private to its wave.
+//
+// The tile is written twice, split_body and merge_body; the nine kernels -- split, merge and the skewed merge of a range
+// (section 17), each plain, against a base tensor (_delta, section 19) and with one address per plane (_to / _from, section
+// 23) -- are one call of a body each, which takes base, skew and the shape of the plane addresses as compile-time switches.
 #include "ghf_device.h"
 
 namespace ghf {
@@ -103,84 +107,6 @@ __device__ __forceinline__ Slab slab_of(uint64_t n_elems, uint32_t tile) {
   return {lo, lo + per < nt ? lo + per : nt, nt * tile + (uint64_t)blockIdx.x * kWave + threadIdx.x};
 }
 
-}  // namespace
-
-template <int E>
-__global__ __launch_bounds__(kWave) void k_planes_split(const uint8_t* __restrict__ in, uint64_t n_elems, uint8_t* __restrict__ planes,
-                                                        uint64_t plane_stride) {
-  using G = PlanesGeom<E>;
-  __shared__ uint4 tile[G::kRows * G::kRowVec];
-  const uint32_t lane = threadIdx.x;
-  const Slab s = slab_of(n_elems, G::kTile);
-  for (uint64_t t = s.lo; t < s.end; ++t) {
-    const uint4* src = reinterpret_cast<const uint4*>(in) + t * (kWave * G::kVec);
-    uint4 x[G::kVec];
-#pragma unroll
-    for (int j = 0; j < G::kVec; ++j) x[j] = ld16(src + j * kWave + lane);
-#pragma unroll
-    for (int j = 0; j < G::kVec; ++j) {
-      const uint32_t v = j * kWave + lane;
-      tile[(v / E) * G::kRowVec + v % E] = x[j];
-    }
-    wave_sync();
-#pragma unroll
-    for (int r = 0; r < G::kRowsPerLane; ++r) {
-      const uint32_t row = r * kWave + lane;
-      uint4 y[E], p[E];
-#pragma unroll
-      for (int j = 0; j < E; ++j) y[j] = tile[row * G::kRowVec + j];
-      row_to_planes<E>(y, p);
-#pragma unroll
-      for (int b = 0; b < E; ++b) st16(reinterpret_cast<uint4*>(planes + b * plane_stride) + t * G::kRows + row, p[b]);
-    }
-    wave_sync();
-  }
-  for (uint64_t k = s.tail; k < n_elems; k += (uint64_t)gridDim.x * kWave) {  // the ragged end: byte by byte
-#pragma unroll
-    for (int b = 0; b < E; ++b) planes[b * plane_stride + k] = in[k * E + b];
-  }
-}
-
-// status (may be null): the context's latched status word; a launch that finds it non-zero stores nothing (one read per
-// workgroup, the convention of k_decode) -- the planes of a failed decode are not merged
-template <int E>
-__global__ __launch_bounds__(kWave) void k_planes_merge(const uint8_t* __restrict__ planes, uint64_t plane_stride, uint64_t n_elems,
-                                                        uint8_t* __restrict__ out, const int* __restrict__ status) {
-  using G = PlanesGeom<E>;
-  __shared__ uint4 tile[G::kRows * G::kRowVec];
-  if (status && __builtin_amdgcn_readfirstlane(*status) != 0) return;
-  const uint32_t lane = threadIdx.x;
-  const Slab s = slab_of(n_elems, G::kTile);
-  for (uint64_t t = s.lo; t < s.end; ++t) {
-    uint4 p[G::kRowsPerLane][E];
-#pragma unroll
-    for (int r = 0; r < G::kRowsPerLane; ++r)
-#pragma unroll
-      for (int b = 0; b < E; ++b)
-        p[r][b] = ld16(reinterpret_cast<const uint4*>(planes + b * plane_stride) + t * G::kRows + r * kWave + lane);
-#pragma unroll
-    for (int r = 0; r < G::kRowsPerLane; ++r) {
-      const uint32_t row = r * kWave + lane;
-      uint4 y[E];
-      planes_to_row<E>(p[r], y);
-#pragma unroll
-      for (int j = 0; j < E; ++j) tile[row * G::kRowVec + j] = y[j];
-    }
-    wave_sync();
-    uint4* dst = reinterpret_cast<uint4*>(out) + t * (kWave * G::kVec);
-#pragma unroll
-    for (int j = 0; j < G::kVec; ++j) {
-      const uint32_t v = j * kWave + lane;
-      st16(dst + j * kWave + lane, tile[(v / E) * G::kRowVec + v % E]);
-    }
-    wave_sync();
-  }
-  for (uint64_t k = s.tail; k < n_elems; k += (uint64_t)gridDim.x * kWave) {
-#pragma unroll
-    for (int b = 0; b < E; ++b) out[k * E + b] = planes[b * plane_stride + k];
-  }
-}
-
 // bytes [skew, skew + 16) of the 32 bytes lo || hi, skew = 1 .. 15 and wave-uniform: the dword part of the skew picks five of
 // the eight dwords (two rounds of uniform v_cndmask_b32), the byte part funnels neighbours with v_alignbyte_b32
 __device__ __forceinline__ uint4 funnel16(const uint4& lo, const uint4& hi, uint32_t skew) {
@@ -193,285 +119,64 @@ __device__ __forceinline__ uint4 funnel16(const uint4& lo, const uint4& hi, uint
                     __builtin_amdgcn_alignbyte(x3, x2, b), __builtin_amdgcn_alignbyte(x4, x3, b));
 }
 
-// k_planes_merge for a run of elements that starts `skew` = 1 .. 15 bytes into a 16-byte vector of every plane (DESIGN.md
-// section 17): out[0 .. n_elems * E) <- elements [skew, skew + n_elems) of the planes.  `planes` itself is 16-byte aligned
-// (the caller has taken first & ~15 into it; skew == 0 is k_planes_merge's).  The same tiles, slabs, LDS rows and stores; on
-// the plane side a lane loads the two ALIGNED vectors that hold its 16 bytes and funnels them.  The second vector of the
-// last row of the last whole tile ends at or before the vector that holds element skew + n_elems - 1 (skew > 0), so
-// nothing outside [0, (skew + n_elems + 15) & ~15) of a plane is read.
-template <int E>
-__global__ __launch_bounds__(kWave) void k_planes_merge_range(const uint8_t* __restrict__ planes, uint64_t plane_stride, uint32_t skew,
-                                                              uint64_t n_elems, uint8_t* __restrict__ out,
-                                                              const int* __restrict__ status) {
-  using G = PlanesGeom<E>;
-  __shared__ uint4 tile[G::kRows * G::kRowVec];
-  if (status && __builtin_amdgcn_readfirstlane(*status) != 0) return;
-  const uint32_t lane = threadIdx.x;
-  skew = __builtin_amdgcn_readfirstlane(skew);
-  const Slab s = slab_of(n_elems, G::kTile);
-  for (uint64_t t = s.lo; t < s.end; ++t) {
-    uint4 lo[G::kRowsPerLane][E], hi[G::kRowsPerLane][E];
-#pragma unroll
-    for (int r = 0; r < G::kRowsPerLane; ++r)
-#pragma unroll
-      for (int b = 0; b < E; ++b) {
-        const uint4* v = reinterpret_cast<const uint4*>(planes + b * plane_stride) + t * G::kRows + r * kWave + lane;
-        lo[r][b] = ld16(v);
-        hi[r][b] = ld16(v + 1);
-      }
-#pragma unroll
-    for (int r = 0; r < G::kRowsPerLane; ++r) {
-      const uint32_t row = r * kWave + lane;
-      uint4 p[E], y[E];
-#pragma unroll
-      for (int b = 0; b < E; ++b) p[b] = funnel16(lo[r][b], hi[r][b], skew);
-      planes_to_row<E>(p, y);
-#pragma unroll
-      for (int j = 0; j < E; ++j) tile[row * G::kRowVec + j] = y[j];
-    }
-    wave_sync();
-    uint4* dst = reinterpret_cast<uint4*>(out) + t * (kWave * G::kVec);
-#pragma unroll
-    for (int j = 0; j < G::kVec; ++j) {
-      const uint32_t v = j * kWave + lane;
-      st16(dst + j * kWave + lane, tile[(v / E) * G::kRowVec + v % E]);
-    }
-    wave_sync();
-  }
-  for (uint64_t k = s.tail; k < n_elems; k += (uint64_t)gridDim.x * kWave) {
-#pragma unroll
-    for (int b = 0; b < E; ++b) out[k * E + b] = planes[b * plane_stride + skew + k];
-  }
-}
-
-// ----------------------------------------------------------------------------------------------------------------------
-// The same three kernels against a BASE tensor: the planes are those of in ^ base, the merge gives
-// back planes ^ base.  `base` holds the bytes of the interleaved side and is read with the interleaved side's access
-// shape: lane l on vector 64 j + l of the tile, 16 bytes per lane, the non-temporal hint.  Its max(E, 4) loads are issued
-// together with the tile's other loads, before the first LDS instruction, and the XOR is applied to registers: on the way
-// into the LDS tile in the split, on the way out of it in the merges (whose base load so never waits behind the
-// transposition).  Tiles, slabs, LDS rows, grid and the bytewise ragged end are the parents'; nothing outside
-// base[0 .. n_elems * E) is read.  The bodies stand beside the parents' and do not share code with them, so that the
-// parents' instruction streams stay what they were.
-// ----------------------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ uint4 xor16(const uint4& a, const uint4& b) { return make_uint4(a.x ^ b.x, a.y ^ b.y, a.z ^ b.z, a.w ^ b.w); }
 
-template <int E>
-__global__ __launch_bounds__(kWave) void k_planes_split_delta(const uint8_t* __restrict__ in, const uint8_t* __restrict__ base,
-                                                              uint64_t n_elems, uint8_t* __restrict__ planes, uint64_t plane_stride) {
-  using G = PlanesGeom<E>;
-  __shared__ uint4 tile[G::kRows * G::kRowVec];
-  const uint32_t lane = threadIdx.x;
-  const Slab s = slab_of(n_elems, G::kTile);
-  for (uint64_t t = s.lo; t < s.end; ++t) {
-    const uint4* src = reinterpret_cast<const uint4*>(in) + t * (kWave * G::kVec);
-    const uint4* bsrc = reinterpret_cast<const uint4*>(base) + t * (kWave * G::kVec);
-    uint4 x[G::kVec], d[G::kVec];
-#pragma unroll
-    for (int j = 0; j < G::kVec; ++j) x[j] = ld16(src + j * kWave + lane);
-#pragma unroll
-    for (int j = 0; j < G::kVec; ++j) d[j] = ld16(bsrc + j * kWave + lane);
-#pragma unroll
-    for (int j = 0; j < G::kVec; ++j) {
-      const uint32_t v = j * kWave + lane;
-      tile[(v / E) * G::kRowVec + v % E] = xor16(x[j], d[j]);
-    }
-    wave_sync();
-#pragma unroll
-    for (int r = 0; r < G::kRowsPerLane; ++r) {
-      const uint32_t row = r * kWave + lane;
-      uint4 y[E], p[E];
-#pragma unroll
-      for (int j = 0; j < E; ++j) y[j] = tile[row * G::kRowVec + j];
-      row_to_planes<E>(y, p);
-#pragma unroll
-      for (int b = 0; b < E; ++b) st16(reinterpret_cast<uint4*>(planes + b * plane_stride) + t * G::kRows + row, p[b]);
-    }
-    wave_sync();
-  }
-  for (uint64_t k = s.tail; k < n_elems; k += (uint64_t)gridDim.x * kWave) {  // the ragged end: byte by byte
-#pragma unroll
-    for (int b = 0; b < E; ++b) planes[b * plane_stride + k] = in[k * E + b] ^ base[k * E + b];
-  }
-}
-
-// `out` and `base` may be the SAME pointer ("XOR the delta into the base") and carry no __restrict__: a lane reads the base
-// vector (the base bytes of the ragged end) that it overwrites itself, and every load of a tile's base is issued before
-// the tile's first store.  status: as in k_planes_merge
-template <int E>
-__global__ __launch_bounds__(kWave) void k_planes_merge_delta(const uint8_t* __restrict__ planes, uint64_t plane_stride,
-                                                              const uint8_t* base, uint64_t n_elems, uint8_t* out,
-                                                              const int* __restrict__ status) {
-  using G = PlanesGeom<E>;
-  __shared__ uint4 tile[G::kRows * G::kRowVec];
-  if (status && __builtin_amdgcn_readfirstlane(*status) != 0) return;
-  const uint32_t lane = threadIdx.x;
-  const Slab s = slab_of(n_elems, G::kTile);
-  for (uint64_t t = s.lo; t < s.end; ++t) {
-    const uint4* bsrc = reinterpret_cast<const uint4*>(base) + t * (kWave * G::kVec);
-    uint4 p[G::kRowsPerLane][E], d[G::kVec];
-#pragma unroll
-    for (int r = 0; r < G::kRowsPerLane; ++r)
-#pragma unroll
-      for (int b = 0; b < E; ++b)
-        p[r][b] = ld16(reinterpret_cast<const uint4*>(planes + b * plane_stride) + t * G::kRows + r * kWave + lane);
-#pragma unroll
-    for (int j = 0; j < G::kVec; ++j) d[j] = ld16(bsrc + j * kWave + lane);
-#pragma unroll
-    for (int r = 0; r < G::kRowsPerLane; ++r) {
-      const uint32_t row = r * kWave + lane;
-      uint4 y[E];
-      planes_to_row<E>(p[r], y);
-#pragma unroll
-      for (int j = 0; j < E; ++j) tile[row * G::kRowVec + j] = y[j];
-    }
-    wave_sync();
-    uint4* dst = reinterpret_cast<uint4*>(out) + t * (kWave * G::kVec);
-#pragma unroll
-    for (int j = 0; j < G::kVec; ++j) {
-      const uint32_t v = j * kWave + lane;
-      st16(dst + j * kWave + lane, xor16(tile[(v / E) * G::kRowVec + v % E], d[j]));
-    }
-    wave_sync();
-  }
-  for (uint64_t k = s.tail; k < n_elems; k += (uint64_t)gridDim.x * kWave) {
-#pragma unroll
-    for (int b = 0; b < E; ++b) out[k * E + b] = planes[b * plane_stride + k] ^ base[k * E + b];
-  }
-}
-
-// k_planes_merge_range against a base: the planes start `skew` = 1 .. 15 bytes into a vector, `base` does not -- it holds
-// the range's own elements, base[0 .. n_elems * E), aligned and indexed exactly like `out` (and may be `out`)
-template <int E>
-__global__ __launch_bounds__(kWave) void k_planes_merge_range_delta(const uint8_t* __restrict__ planes, uint64_t plane_stride,
-                                                                    uint32_t skew, const uint8_t* base, uint64_t n_elems, uint8_t* out,
-                                                                    const int* __restrict__ status) {
-  using G = PlanesGeom<E>;
-  __shared__ uint4 tile[G::kRows * G::kRowVec];
-  if (status && __builtin_amdgcn_readfirstlane(*status) != 0) return;
-  const uint32_t lane = threadIdx.x;
-  skew = __builtin_amdgcn_readfirstlane(skew);
-  const Slab s = slab_of(n_elems, G::kTile);
-  for (uint64_t t = s.lo; t < s.end; ++t) {
-    const uint4* bsrc = reinterpret_cast<const uint4*>(base) + t * (kWave * G::kVec);
-    uint4 lo[G::kRowsPerLane][E], hi[G::kRowsPerLane][E], d[G::kVec];
-#pragma unroll
-    for (int r = 0; r < G::kRowsPerLane; ++r)
-#pragma unroll
-      for (int b = 0; b < E; ++b) {
-        const uint4* v = reinterpret_cast<const uint4*>(planes + b * plane_stride) + t * G::kRows + r * kWave + lane;
-        lo[r][b] = ld16(v);
-        hi[r][b] = ld16(v + 1);
-      }
-#pragma unroll
-    for (int j = 0; j < G::kVec; ++j) d[j] = ld16(bsrc + j * kWave + lane);
-#pragma unroll
-    for (int r = 0; r < G::kRowsPerLane; ++r) {
-      const uint32_t row = r * kWave + lane;
-      uint4 p[E], y[E];
-#pragma unroll
-      for (int b = 0; b < E; ++b) p[b] = funnel16(lo[r][b], hi[r][b], skew);
-      planes_to_row<E>(p, y);
-#pragma unroll
-      for (int j = 0; j < E; ++j) tile[row * G::kRowVec + j] = y[j];
-    }
-    wave_sync();
-    uint4* dst = reinterpret_cast<uint4*>(out) + t * (kWave * G::kVec);
-#pragma unroll
-    for (int j = 0; j < G::kVec; ++j) {
-      const uint32_t v = j * kWave + lane;
-      st16(dst + j * kWave + lane, xor16(tile[(v / E) * G::kRowVec + v % E], d[j]));
-    }
-    wave_sync();
-  }
-  for (uint64_t k = s.tail; k < n_elems; k += (uint64_t)gridDim.x * kWave) {
-#pragma unroll
-    for (int b = 0; b < E; ++b) out[k * E + b] = planes[b * plane_stride + skew + k] ^ base[k * E + b];
-  }
-}
-
-// one resident round: kPlanesGroups one-wave workgroups, each with a slab of whole tiles; at least one lane per element of
-// the ragged end
-static uint32_t planes_grid(uint64_t n_elems, uint32_t elem_bytes) {
-  const uint32_t tile = planes_tile_elems(elem_bytes);
-  const uint64_t nt = n_elems / tile, tail_waves = (n_elems % tile + kWave - 1) / kWave;
-  const uint64_t g = nt > tail_waves ? nt : tail_waves;
-  return (uint32_t)(g > kPlanesGroups ? kPlanesGroups : g);
-}
-
-// d_base == nullptr: the plain kernel; else the planes of d_in ^ d_base (DESIGN.md section 19), on the same grid
-void launch_planes_split(const uint8_t* d_in, const uint8_t* d_base, uint64_t n_elems, uint32_t elem_bytes, uint8_t* d_planes,
-                         uint64_t plane_stride, hipStream_t s) {
-  const dim3 grid(planes_grid(n_elems, elem_bytes)), block(kWave);
-  if (!d_base) {
-    if (elem_bytes == 2) hipLaunchKernelGGL(k_planes_split<2>, grid, block, 0, s, d_in, n_elems, d_planes, plane_stride);
-    else if (elem_bytes == 4) hipLaunchKernelGGL(k_planes_split<4>, grid, block, 0, s, d_in, n_elems, d_planes, plane_stride);
-    else hipLaunchKernelGGL(k_planes_split<8>, grid, block, 0, s, d_in, n_elems, d_planes, plane_stride);
-  } else {
-    if (elem_bytes == 2) hipLaunchKernelGGL(k_planes_split_delta<2>, grid, block, 0, s, d_in, d_base, n_elems, d_planes, plane_stride);
-    else if (elem_bytes == 4) hipLaunchKernelGGL(k_planes_split_delta<4>, grid, block, 0, s, d_in, d_base, n_elems, d_planes, plane_stride);
-    else hipLaunchKernelGGL(k_planes_split_delta<8>, grid, block, 0, s, d_in, d_base, n_elems, d_planes, plane_stride);
-  }
-}
-
-// d_base == nullptr: the plain kernel; else d_out = merge(planes) ^ d_base, d_base == d_out allowed
-void launch_planes_merge(const uint8_t* d_planes, uint64_t plane_stride, const uint8_t* d_base, uint64_t n_elems, uint32_t elem_bytes,
-                         uint8_t* d_out, const int* d_status, hipStream_t s) {
-  const dim3 grid(planes_grid(n_elems, elem_bytes)), block(kWave);
-  if (!d_base) {
-    if (elem_bytes == 2) hipLaunchKernelGGL(k_planes_merge<2>, grid, block, 0, s, d_planes, plane_stride, n_elems, d_out, d_status);
-    else if (elem_bytes == 4) hipLaunchKernelGGL(k_planes_merge<4>, grid, block, 0, s, d_planes, plane_stride, n_elems, d_out, d_status);
-    else hipLaunchKernelGGL(k_planes_merge<8>, grid, block, 0, s, d_planes, plane_stride, n_elems, d_out, d_status);
-  } else {
-    if (elem_bytes == 2) hipLaunchKernelGGL(k_planes_merge_delta<2>, grid, block, 0, s, d_planes, plane_stride, d_base, n_elems, d_out, d_status);
-    else if (elem_bytes == 4) hipLaunchKernelGGL(k_planes_merge_delta<4>, grid, block, 0, s, d_planes, plane_stride, d_base, n_elems, d_out, d_status);
-    else hipLaunchKernelGGL(k_planes_merge_delta<8>, grid, block, 0, s, d_planes, plane_stride, d_base, n_elems, d_out, d_status);
-  }
-}
-
-// elements [first, first + count) of the planes; a range that starts on a vector is k_planes_merge on the shifted planes.
-// d_base (may be null) holds base elements [first, first + count) at d_base[0 .. count * elem_bytes): it carries no skew,
-// only the planes do
-void launch_planes_merge_range(const uint8_t* d_planes, uint64_t plane_stride, const uint8_t* d_base, uint64_t first, uint64_t count,
-                               uint32_t elem_bytes, uint8_t* d_out, const int* d_status, hipStream_t s) {
-  const uint32_t skew = (uint32_t)(first & 15u);
-  const uint8_t* from = d_planes + (first - skew);
-  if (skew == 0) return launch_planes_merge(from, plane_stride, d_base, count, elem_bytes, d_out, d_status, s);
-  const dim3 grid(planes_grid(count, elem_bytes)), block(kWave);
-  if (!d_base) {
-    if (elem_bytes == 2) hipLaunchKernelGGL(k_planes_merge_range<2>, grid, block, 0, s, from, plane_stride, skew, count, d_out, d_status);
-    else if (elem_bytes == 4) hipLaunchKernelGGL(k_planes_merge_range<4>, grid, block, 0, s, from, plane_stride, skew, count, d_out, d_status);
-    else hipLaunchKernelGGL(k_planes_merge_range<8>, grid, block, 0, s, from, plane_stride, skew, count, d_out, d_status);
-  } else {
-    if (elem_bytes == 2)
-      hipLaunchKernelGGL(k_planes_merge_range_delta<2>, grid, block, 0, s, from, plane_stride, skew, d_base, count, d_out, d_status);
-    else if (elem_bytes == 4)
-      hipLaunchKernelGGL(k_planes_merge_range_delta<4>, grid, block, 0, s, from, plane_stride, skew, d_base, count, d_out, d_status);
-    else
-      hipLaunchKernelGGL(k_planes_merge_range_delta<8>, grid, block, 0, s, from, plane_stride, skew, d_base, count, d_out, d_status);
-  }
-}
-
 // ----------------------------------------------------------------------------------------------------------------------
-// The same three kernels with ONE ADDRESS PER PLANE: a plane stored raw lives in the caller's image,
-// the others in the context's workspace, and one base pointer and one stride cannot name both.  The E addresses travel by
-// value in the kernel arguments: they are wave-uniform, every index into them is a constant once the loops are unrolled,
-// and they stay in SGPRs.  kDelta: the interleaved side is taken against `base`, loaded and applied exactly as in the
-// _delta kernels above; without it `base` is not looked at.  Tiles, slabs, LDS rows, grid, load depth and the bytewise
-// ragged end are the parents'.  The bodies stand beside the parents' and share no code with them.
+// WHERE THE PLANES ARE, in two shapes.  Both give vec(b, t, r, lane), the 16-byte vector of plane b for row r * kWave + lane
+// of tile t, and byte(b, k), byte k of plane b.  B is uint8_t on the split's side, const uint8_t on the merge's.
 // ----------------------------------------------------------------------------------------------------------------------
-template <int E>
-struct PlaneDsts {
-  uint8_t* p[E];
-};
-template <int E>
-struct PlaneSrcs {
-  const uint8_t* p[E];
+template <class B>
+using vec_of = std::conditional_t<std::is_const<B>::value, const uint4, uint4>;
+
+// one pointer and one stride: plane b starts at p + b * stride
+template <int E, class B>
+struct StridedPlanes {
+  static constexpr bool kPerPlane = false;
+  B* p;
+  uint64_t stride;
+  __device__ __forceinline__ vec_of<B>* vec(int b, uint64_t t, int r, uint32_t lane) const {
+    return reinterpret_cast<vec_of<B>*>(p + b * stride) + t * PlanesGeom<E>::kRows + r * kWave + lane;
+  }
+  __device__ __forceinline__ B& byte(int b, uint64_t k) const { return p[b * stride + k]; }
 };
 
-template <int E, bool kDelta>
-__global__ __launch_bounds__(kWave) void k_planes_split_to(const uint8_t* __restrict__ in, const uint8_t* __restrict__ base,
-                                                           uint64_t n_elems, PlaneDsts<E> dst) {
+// ONE ADDRESS PER PLANE: a plane stored raw lives in the caller's image, the others in the context's
+// workspace, and one pointer and one stride cannot name both.  The E addresses travel by value in the kernel arguments: they
+// are wave-uniform, every index into them is a constant once the loops are unrolled, and they stay in SGPRs.
+template <int E, class B>
+struct PlaneAddrs {
+  static constexpr bool kPerPlane = true;
+  B* p[E];
+  __device__ __forceinline__ vec_of<B>* vec(int b, uint64_t t, int r, uint32_t lane) const {
+    return reinterpret_cast<vec_of<B>*>(p[b] + (t * PlanesGeom<E>::kRows + r * kWave) * 16) + lane;
+  }
+  __device__ __forceinline__ B& byte(int b, uint64_t k) const { return p[b][k]; }
+};
+
+}  // namespace
+
+// the parameter types of the pointer kernels (their names are part of the kernels' symbols)
+template <int E>
+struct PlaneDsts : PlaneAddrs<E, uint8_t> {};
+template <int E>
+struct PlaneSrcs : PlaneAddrs<E, const uint8_t> {};
+
+namespace {
+
+// ----------------------------------------------------------------------------------------------------------------------
+// THE TWO BODIES.  Every kernel of this unit is one call of one of them; the `if constexpr` switches leave each kernel the
+// instruction stream it would have written out by hand (DESIGN.md section 19 has the rule the listings are held to).
+//
+// kDelta: the planes are those of in ^ base, the merge gives back planes ^ base.  `base` holds the
+// bytes of the interleaved side -- of a range: the range's own elements, base[0 .. n_elems * E), with no skew -- and is read
+// with the interleaved side's access shape: lane l on vector 64 j + l of the tile, 16 bytes per lane, the non-temporal
+// hint.  Its max(E, 4) loads are issued together with the tile's other loads, before the first LDS instruction, and the XOR
+// is applied to registers: on the way into the LDS tile in the split, on the way out of it in the merge (whose base load so
+// never waits behind the transposition).  Nothing outside base[0 .. n_elems * E) is read; without kDelta `base` is not
+// looked at.
+// ----------------------------------------------------------------------------------------------------------------------
+template <int E, bool kDelta, class P>
+__device__ __forceinline__ void split_body(const uint8_t* in, const uint8_t* base, uint64_t n_elems, const P& dst) {
   using G = PlanesGeom<E>;
   __shared__ uint4 tile[G::kRows * G::kRowVec];
   const uint32_t lane = threadIdx.x;
@@ -501,44 +206,68 @@ __global__ __launch_bounds__(kWave) void k_planes_split_to(const uint8_t* __rest
       for (int j = 0; j < E; ++j) y[j] = tile[row * G::kRowVec + j];
       row_to_planes<E>(y, p);
 #pragma unroll
-      for (int b = 0; b < E; ++b) st16(reinterpret_cast<uint4*>(dst.p[b] + (t * G::kRows + r * kWave) * 16) + lane, p[b]);
+      for (int b = 0; b < E; ++b) st16(dst.vec(b, t, r, lane), p[b]);
     }
     wave_sync();
   }
   for (uint64_t k = s.tail; k < n_elems; k += (uint64_t)gridDim.x * kWave) {  // the ragged end: byte by byte
 #pragma unroll
     for (int b = 0; b < E; ++b) {
-      if constexpr (kDelta) dst.p[b][k] = in[k * E + b] ^ base[k * E + b];
-      else dst.p[b][k] = in[k * E + b];
+      if constexpr (kDelta) dst.byte(b, k) = in[k * E + b] ^ base[k * E + b];
+      else dst.byte(b, k) = in[k * E + b];
     }
   }
 }
 
-// `out` and `base` may be the same pointer, as in k_planes_merge_delta; status: as in k_planes_merge
-template <int E, bool kDelta>
-__global__ __launch_bounds__(kWave) void k_planes_merge_from(PlaneSrcs<E> src, const uint8_t* base, uint64_t n_elems, uint8_t* out,
-                                                             const int* __restrict__ status) {
+// status (may be null): the context's latched status word; a launch that finds it non-zero stores nothing (one read per
+// workgroup, the convention of k_decode) -- the planes of a failed decode are not merged.
+//
+// kSkew: the run of n_elems elements starts `skew` = 1 .. 15 bytes into a 16-byte vector of EVERY
+// plane; the addresses in `src` are 16-byte aligned (the caller has taken the skew off them; skew == 0 is the kernel
+// without kSkew, which does not look at `skew`).  The same tiles, slabs, LDS rows and stores; on the plane side a lane loads
+// the two ALIGNED vectors that hold its 16 bytes and funnels them.  The second vector of the last row of the last whole
+// tile ends at or before the vector that holds element skew + n_elems - 1 (skew > 0), so nothing outside
+// [0, (skew + n_elems + 15) & ~15) of a plane is read.
+//
+// kDelta: `out` and `base` may be the SAME pointer ("XOR the delta into the base"), which is why the shells give neither a
+// __restrict__: a lane reads the base vector (the base bytes of the ragged end) that it overwrites itself, and every load
+// of a tile's base is issued before the tile's first store.
+template <int E, bool kDelta, bool kSkew, class P>
+__device__ __forceinline__ void merge_body(const P& src, uint32_t skew, const uint8_t* base, uint64_t n_elems, uint8_t* out,
+                                           const int* status) {
   using G = PlanesGeom<E>;
   __shared__ uint4 tile[G::kRows * G::kRowVec];
   if (status && __builtin_amdgcn_readfirstlane(*status) != 0) return;
   const uint32_t lane = threadIdx.x;
+  if constexpr (kSkew) skew = __builtin_amdgcn_readfirstlane(skew);
   const Slab s = slab_of(n_elems, G::kTile);
   for (uint64_t t = s.lo; t < s.end; ++t) {
-    uint4 p[G::kRowsPerLane][E], d[G::kVec];
+    uint4 p[G::kRowsPerLane][E], hi[G::kRowsPerLane][E], d[G::kVec];
 #pragma unroll
     for (int r = 0; r < G::kRowsPerLane; ++r)
 #pragma unroll
-      for (int b = 0; b < E; ++b) p[r][b] = ld16(reinterpret_cast<const uint4*>(src.p[b] + (t * G::kRows + r * kWave) * 16) + lane);
+      for (int b = 0; b < E; ++b) {
+        const uint4* v = src.vec(b, t, r, lane);
+        p[r][b] = ld16(v);
+        if constexpr (kSkew) hi[r][b] = ld16(v + 1);
+      }
     if constexpr (kDelta) {
       const uint4* bsrc = reinterpret_cast<const uint4*>(base) + t * (kWave * G::kVec);
 #pragma unroll
       for (int j = 0; j < G::kVec; ++j) d[j] = ld16(bsrc + j * kWave + lane);
-      __builtin_amdgcn_sched_barrier(0);  // every load of the tile is issued before the first use: none sinks below the transposition
+      // k_planes_merge_from<E, true> alone: every load of the tile is issued before the first use.  Left
+      // to itself the scheduler sinks two of the sixteen loads of E = 8 below the transposition, and orders those of E = 2, 4
+      // otherwise; every other kernel has all its loads in front unaided, or pays for the barrier with a wave (section 23)
+      if constexpr (P::kPerPlane && !kSkew) __builtin_amdgcn_sched_barrier(0);
     }
 #pragma unroll
     for (int r = 0; r < G::kRowsPerLane; ++r) {
       const uint32_t row = r * kWave + lane;
       uint4 y[E];
+      if constexpr (kSkew) {
+#pragma unroll
+        for (int b = 0; b < E; ++b) p[r][b] = funnel16(p[r][b], hi[r][b], skew);
+      }
       planes_to_row<E>(p[r], y);
 #pragma unroll
       for (int j = 0; j < E; ++j) tile[row * G::kRowVec + j] = y[j];
@@ -556,106 +285,144 @@ __global__ __launch_bounds__(kWave) void k_planes_merge_from(PlaneSrcs<E> src, c
   for (uint64_t k = s.tail; k < n_elems; k += (uint64_t)gridDim.x * kWave) {
 #pragma unroll
     for (int b = 0; b < E; ++b) {
-      if constexpr (kDelta) out[k * E + b] = src.p[b][k] ^ base[k * E + b];
-      else out[k * E + b] = src.p[b][k];
+      if constexpr (kDelta) out[k * E + b] = src.byte(b, kSkew ? skew + k : k) ^ base[k * E + b];
+      else out[k * E + b] = src.byte(b, kSkew ? skew + k : k);
     }
   }
 }
 
-// the skewed merge of section 17: src.p[b] is the 16-byte-aligned address at or below plane b's byte of the run's first
-// element, which stands `skew` = 1 .. 15 bytes behind it in EVERY plane.  As in k_planes_merge_range nothing outside
-// [0, (skew + n_elems + 15) & ~15) of a source is read; `base` holds the run's own elements and carries no skew
+}  // namespace
+
+// ---- the nine kernels: k_planes_split / _merge / _merge_range, plain, _delta (against a base) and _to / _from (one address
+// per plane).  n_elems > 0; every pointer, every plane address and plane_stride 16-byte aligned -------------------------------
+template <int E>
+__global__ __launch_bounds__(kWave) void k_planes_split(const uint8_t* __restrict__ in, uint64_t n_elems, uint8_t* __restrict__ planes,
+                                                        uint64_t plane_stride) {
+  split_body<E, false>(in, nullptr, n_elems, StridedPlanes<E, uint8_t>{planes, plane_stride});
+}
+template <int E>
+__global__ __launch_bounds__(kWave) void k_planes_split_delta(const uint8_t* __restrict__ in, const uint8_t* __restrict__ base,
+                                                              uint64_t n_elems, uint8_t* __restrict__ planes, uint64_t plane_stride) {
+  split_body<E, true>(in, base, n_elems, StridedPlanes<E, uint8_t>{planes, plane_stride});
+}
+template <int E, bool kDelta>
+__global__ __launch_bounds__(kWave) void k_planes_split_to(const uint8_t* __restrict__ in, const uint8_t* __restrict__ base,
+                                                           uint64_t n_elems, PlaneDsts<E> dst) {
+  split_body<E, kDelta>(in, base, n_elems, dst);
+}
+
+template <int E>
+__global__ __launch_bounds__(kWave) void k_planes_merge(const uint8_t* __restrict__ planes, uint64_t plane_stride, uint64_t n_elems,
+                                                        uint8_t* __restrict__ out, const int* __restrict__ status) {
+  merge_body<E, false, false>(StridedPlanes<E, const uint8_t>{planes, plane_stride}, 0, nullptr, n_elems, out, status);
+}
+template <int E>
+__global__ __launch_bounds__(kWave) void k_planes_merge_range(const uint8_t* __restrict__ planes, uint64_t plane_stride, uint32_t skew,
+                                                              uint64_t n_elems, uint8_t* __restrict__ out,
+                                                              const int* __restrict__ status) {
+  merge_body<E, false, true>(StridedPlanes<E, const uint8_t>{planes, plane_stride}, skew, nullptr, n_elems, out, status);
+}
+template <int E>
+__global__ __launch_bounds__(kWave) void k_planes_merge_delta(const uint8_t* __restrict__ planes, uint64_t plane_stride,
+                                                              const uint8_t* base, uint64_t n_elems, uint8_t* out,
+                                                              const int* __restrict__ status) {
+  merge_body<E, true, false>(StridedPlanes<E, const uint8_t>{planes, plane_stride}, 0, base, n_elems, out, status);
+}
+template <int E>
+__global__ __launch_bounds__(kWave) void k_planes_merge_range_delta(const uint8_t* __restrict__ planes, uint64_t plane_stride,
+                                                                    uint32_t skew, const uint8_t* base, uint64_t n_elems, uint8_t* out,
+                                                                    const int* __restrict__ status) {
+  merge_body<E, true, true>(StridedPlanes<E, const uint8_t>{planes, plane_stride}, skew, base, n_elems, out, status);
+}
+template <int E, bool kDelta>
+__global__ __launch_bounds__(kWave) void k_planes_merge_from(PlaneSrcs<E> src, const uint8_t* base, uint64_t n_elems, uint8_t* out,
+                                                             const int* __restrict__ status) {
+  merge_body<E, kDelta, false>(src, 0, base, n_elems, out, status);
+}
 template <int E, bool kDelta>
 __global__ __launch_bounds__(kWave) void k_planes_merge_range_from(PlaneSrcs<E> src, uint32_t skew, const uint8_t* base, uint64_t n_elems,
                                                                    uint8_t* out, const int* __restrict__ status) {
-  using G = PlanesGeom<E>;
-  __shared__ uint4 tile[G::kRows * G::kRowVec];
-  if (status && __builtin_amdgcn_readfirstlane(*status) != 0) return;
-  const uint32_t lane = threadIdx.x;
-  skew = __builtin_amdgcn_readfirstlane(skew);
-  const Slab s = slab_of(n_elems, G::kTile);
-  for (uint64_t t = s.lo; t < s.end; ++t) {
-    uint4 lo[G::kRowsPerLane][E], hi[G::kRowsPerLane][E], d[G::kVec];
-#pragma unroll
-    for (int r = 0; r < G::kRowsPerLane; ++r)
-#pragma unroll
-      for (int b = 0; b < E; ++b) {
-        const uint4* v = reinterpret_cast<const uint4*>(src.p[b] + (t * G::kRows + r * kWave) * 16) + lane;
-        lo[r][b] = ld16(v);
-        hi[r][b] = ld16(v + 1);
-      }
-    if constexpr (kDelta) {
-      const uint4* bsrc = reinterpret_cast<const uint4*>(base) + t * (kWave * G::kVec);
-#pragma unroll
-      for (int j = 0; j < G::kVec; ++j) d[j] = ld16(bsrc + j * kWave + lane);
-    }
-#pragma unroll
-    for (int r = 0; r < G::kRowsPerLane; ++r) {
-      const uint32_t row = r * kWave + lane;
-      uint4 p[E], y[E];
-#pragma unroll
-      for (int b = 0; b < E; ++b) p[b] = funnel16(lo[r][b], hi[r][b], skew);
-      planes_to_row<E>(p, y);
-#pragma unroll
-      for (int j = 0; j < E; ++j) tile[row * G::kRowVec + j] = y[j];
-    }
-    wave_sync();
-    uint4* dst = reinterpret_cast<uint4*>(out) + t * (kWave * G::kVec);
-#pragma unroll
-    for (int j = 0; j < G::kVec; ++j) {
-      const uint32_t v = j * kWave + lane;
-      if constexpr (kDelta) st16(dst + j * kWave + lane, xor16(tile[(v / E) * G::kRowVec + v % E], d[j]));
-      else st16(dst + j * kWave + lane, tile[(v / E) * G::kRowVec + v % E]);
-    }
-    wave_sync();
-  }
-  for (uint64_t k = s.tail; k < n_elems; k += (uint64_t)gridDim.x * kWave) {
-#pragma unroll
-    for (int b = 0; b < E; ++b) {
-      if constexpr (kDelta) out[k * E + b] = src.p[b][skew + k] ^ base[k * E + b];
-      else out[k * E + b] = src.p[b][skew + k];
-    }
-  }
+  merge_body<E, kDelta, true>(src, skew, base, n_elems, out, status);
 }
 
-template <int E>
-static void split_to(const uint8_t* d_in, const uint8_t* d_base, uint64_t n_elems, uint8_t* const* h_dst, hipStream_t s) {
-  const dim3 grid(planes_grid(n_elems, E)), block(kWave);
-  PlaneDsts<E> dst;
-  for (int b = 0; b < E; ++b) dst.p[b] = h_dst[b];
-  if (d_base) hipLaunchKernelGGL((k_planes_split_to<E, true>), grid, block, 0, s, d_in, d_base, n_elems, dst);
-  else hipLaunchKernelGGL((k_planes_split_to<E, false>), grid, block, 0, s, d_in, d_base, n_elems, dst);
+// ---- launchers -----------------------------------------------------------------------------------------------------------
+// one resident round: kPlanesGroups one-wave workgroups, each with a slab of whole tiles; at least one lane per element of
+// the ragged end
+static uint32_t planes_grid(uint64_t n_elems, uint32_t elem_bytes) {
+  const uint32_t tile = planes_tile_elems(elem_bytes);
+  const uint64_t nt = n_elems / tile, tail_waves = (n_elems % tile + kWave - 1) / kWave;
+  const uint64_t g = nt > tail_waves ? nt : tail_waves;
+  return (uint32_t)(g > kPlanesGroups ? kPlanesGroups : g);
 }
 
-// h_src[b] is plane b's byte of the first element; all have the same address mod 16 (the caller has seen to it)
-template <int E>
-static void merge_from(const uint8_t* const* h_src, const uint8_t* d_base, uint64_t n_elems, uint8_t* d_out, const int* d_status,
-                       hipStream_t s) {
-  const dim3 grid(planes_grid(n_elems, E)), block(kWave);
-  const uint32_t skew = (uint32_t)(reinterpret_cast<uintptr_t>(h_src[0]) & 15u);
-  PlaneSrcs<E> src;
-  for (int b = 0; b < E; ++b) src.p[b] = h_src[b] - skew;
-  if (skew == 0) {
-    if (d_base) hipLaunchKernelGGL((k_planes_merge_from<E, true>), grid, block, 0, s, src, d_base, n_elems, d_out, d_status);
-    else hipLaunchKernelGGL((k_planes_merge_from<E, false>), grid, block, 0, s, src, d_base, n_elems, d_out, d_status);
-  } else {
-    if (d_base) hipLaunchKernelGGL((k_planes_merge_range_from<E, true>), grid, block, 0, s, src, skew, d_base, n_elems, d_out, d_status);
-    else hipLaunchKernelGGL((k_planes_merge_range_from<E, false>), grid, block, 0, s, src, skew, d_base, n_elems, d_out, d_status);
-  }
+// d_base == nullptr: the plain kernel; else the planes of d_in ^ d_base (DESIGN.md section 19), on the same grid
+void launch_planes_split(const uint8_t* d_in, const uint8_t* d_base, uint64_t n_elems, uint32_t elem_bytes, uint8_t* d_planes,
+                         uint64_t plane_stride, hipStream_t s) {
+  const dim3 grid(planes_grid(n_elems, elem_bytes)), block(kWave);
+  with_elem_bytes(elem_bytes, [&](auto e) {
+    constexpr int E = decltype(e)::value;
+    if (d_base) hipLaunchKernelGGL(k_planes_split_delta<E>, grid, block, 0, s, d_in, d_base, n_elems, d_planes, plane_stride);
+    else hipLaunchKernelGGL(k_planes_split<E>, grid, block, 0, s, d_in, n_elems, d_planes, plane_stride);
+  });
+}
+
+// d_base == nullptr: the plain kernel; else d_out = merge(planes) ^ d_base, d_base == d_out allowed
+void launch_planes_merge(const uint8_t* d_planes, uint64_t plane_stride, const uint8_t* d_base, uint64_t n_elems, uint32_t elem_bytes,
+                         uint8_t* d_out, const int* d_status, hipStream_t s) {
+  const dim3 grid(planes_grid(n_elems, elem_bytes)), block(kWave);
+  with_elem_bytes(elem_bytes, [&](auto e) {
+    constexpr int E = decltype(e)::value;
+    if (d_base) hipLaunchKernelGGL(k_planes_merge_delta<E>, grid, block, 0, s, d_planes, plane_stride, d_base, n_elems, d_out, d_status);
+    else hipLaunchKernelGGL(k_planes_merge<E>, grid, block, 0, s, d_planes, plane_stride, n_elems, d_out, d_status);
+  });
+}
+
+// elements [first, first + count) of the planes; a range that starts on a vector is k_planes_merge on the shifted planes.
+// d_base (may be null) holds base elements [first, first + count) at d_base[0 .. count * elem_bytes): it carries no skew,
+// only the planes do
+void launch_planes_merge_range(const uint8_t* d_planes, uint64_t plane_stride, const uint8_t* d_base, uint64_t first, uint64_t count,
+                               uint32_t elem_bytes, uint8_t* d_out, const int* d_status, hipStream_t s) {
+  const uint32_t skew = (uint32_t)(first & 15u);
+  const uint8_t* from = d_planes + (first - skew);
+  if (skew == 0) return launch_planes_merge(from, plane_stride, d_base, count, elem_bytes, d_out, d_status, s);
+  const dim3 grid(planes_grid(count, elem_bytes)), block(kWave);
+  with_elem_bytes(elem_bytes, [&](auto e) {
+    constexpr int E = decltype(e)::value;
+    if (d_base)
+      hipLaunchKernelGGL(k_planes_merge_range_delta<E>, grid, block, 0, s, from, plane_stride, skew, d_base, count, d_out, d_status);
+    else hipLaunchKernelGGL(k_planes_merge_range<E>, grid, block, 0, s, from, plane_stride, skew, count, d_out, d_status);
+  });
 }
 
 void launch_planes_split_to(const uint8_t* d_in, const uint8_t* d_base, uint64_t n_elems, uint32_t elem_bytes, uint8_t* const* h_dst,
                             hipStream_t s) {
-  if (elem_bytes == 2) split_to<2>(d_in, d_base, n_elems, h_dst, s);
-  else if (elem_bytes == 4) split_to<4>(d_in, d_base, n_elems, h_dst, s);
-  else split_to<8>(d_in, d_base, n_elems, h_dst, s);
+  const dim3 grid(planes_grid(n_elems, elem_bytes)), block(kWave);
+  with_elem_bytes(elem_bytes, [&](auto e) {
+    constexpr int E = decltype(e)::value;
+    PlaneDsts<E> dst;
+    for (int b = 0; b < E; ++b) dst.p[b] = h_dst[b];
+    if (d_base) hipLaunchKernelGGL((k_planes_split_to<E, true>), grid, block, 0, s, d_in, d_base, n_elems, dst);
+    else hipLaunchKernelGGL((k_planes_split_to<E, false>), grid, block, 0, s, d_in, d_base, n_elems, dst);
+  });
 }
 
+// h_src[b] is plane b's byte of the first element; all have the same address mod 16 (the caller has seen to it)
 void launch_planes_merge_from(const uint8_t* const* h_src, const uint8_t* d_base, uint64_t n_elems, uint32_t elem_bytes, uint8_t* d_out,
                               const int* d_status, hipStream_t s) {
-  if (elem_bytes == 2) merge_from<2>(h_src, d_base, n_elems, d_out, d_status, s);
-  else if (elem_bytes == 4) merge_from<4>(h_src, d_base, n_elems, d_out, d_status, s);
-  else merge_from<8>(h_src, d_base, n_elems, d_out, d_status, s);
+  const dim3 grid(planes_grid(n_elems, elem_bytes)), block(kWave);
+  const uint32_t skew = (uint32_t)(reinterpret_cast<uintptr_t>(h_src[0]) & 15u);
+  with_elem_bytes(elem_bytes, [&](auto e) {
+    constexpr int E = decltype(e)::value;
+    PlaneSrcs<E> src;
+    for (int b = 0; b < E; ++b) src.p[b] = h_src[b] - skew;
+    if (skew == 0) {
+      if (d_base) hipLaunchKernelGGL((k_planes_merge_from<E, true>), grid, block, 0, s, src, d_base, n_elems, d_out, d_status);
+      else hipLaunchKernelGGL((k_planes_merge_from<E, false>), grid, block, 0, s, src, d_base, n_elems, d_out, d_status);
+    } else {
+      if (d_base) hipLaunchKernelGGL((k_planes_merge_range_from<E, true>), grid, block, 0, s, src, skew, d_base, n_elems, d_out, d_status);
+      else hipLaunchKernelGGL((k_planes_merge_range_from<E, false>), grid, block, 0, s, src, skew, d_base, n_elems, d_out, d_status);
+    }
+  });
 }
 
 }  // namespace ghf

@@ -332,15 +332,11 @@ hipError_t launch_histogram_planes(const uint8_t* d_in, const uint8_t* d_base, u
   const uint64_t n_bytes = n_elems * elem_bytes;
   const dim3 grid(planes_hist_grid(n_bytes)), block(kPlanesHistThreads);
   unsigned long long* const acc = reinterpret_cast<unsigned long long*>(d_acc);
-  if (!d_base) {
-    if (elem_bytes == 2) hipLaunchKernelGGL(k_histogram_planes<2>, grid, block, 0, s, d_in, n_bytes, acc);
-    else if (elem_bytes == 4) hipLaunchKernelGGL(k_histogram_planes<4>, grid, block, 0, s, d_in, n_bytes, acc);
-    else hipLaunchKernelGGL(k_histogram_planes<8>, grid, block, 0, s, d_in, n_bytes, acc);
-  } else {
-    if (elem_bytes == 2) hipLaunchKernelGGL(k_histogram_planes_delta<2>, grid, block, 0, s, d_in, d_base, n_bytes, acc);
-    else if (elem_bytes == 4) hipLaunchKernelGGL(k_histogram_planes_delta<4>, grid, block, 0, s, d_in, d_base, n_bytes, acc);
-    else hipLaunchKernelGGL(k_histogram_planes_delta<8>, grid, block, 0, s, d_in, d_base, n_bytes, acc);
-  }
+  with_elem_bytes(elem_bytes, [&](auto e) {
+    constexpr int E = decltype(e)::value;
+    if (d_base) hipLaunchKernelGGL(k_histogram_planes_delta<E>, grid, block, 0, s, d_in, d_base, n_bytes, acc);
+    else hipLaunchKernelGGL(k_histogram_planes<E>, grid, block, 0, s, d_in, n_bytes, acc);
+  });
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(k_histogram_planes_finish, dim3(elem_bytes), dim3(256), 0, s, acc, elem_bytes, d_hists,
