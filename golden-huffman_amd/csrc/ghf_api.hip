@@ -753,18 +753,23 @@ static bool planes_index_covers(const ghf_batch_index* ix, uint32_t count, uint3
   return (uint64_t)count * elem_bytes <= 0xFFFFFFFFull && batch_index_covers(ix, count * elem_bytes, plane_symbols);
 }
 
-int ghf_compress_batch_planes_shared(ghf_ctx* c, const uint8_t* const* d_in_ptrs, const uint64_t* d_in_bytes, size_t max_item_bytes,
-                                     uint32_t count, uint32_t elem_bytes, const ghf_code* d_codes, uint8_t* const* d_out_ptrs,
-                                     const uint64_t* d_out_caps, uint64_t* d_out_bytes, const ghf_batch_index* index,
-                                     int* d_item_status) {
+// a mask of raw planes names planes below elem_bytes only
+static inline bool planes_mask_ok(uint32_t raw_planes, uint32_t elem_bytes) { return (raw_planes >> elem_bytes) == 0; }
+
+// ghf_compress_batch_planes_shared (forms = false: its own kernel, no mask) and ghf_compress_batch_planes_forms
+static int compress_batch_planes(ghf_ctx* c, const std::string& who, bool forms, const uint8_t* const* d_in_ptrs, const uint64_t* d_in_bytes,
+                                 size_t max_item_bytes, uint32_t count, uint32_t elem_bytes, const ghf_code* d_codes, uint32_t raw_planes,
+                                 uint8_t* const* d_out_ptrs, const uint64_t* d_out_caps, uint64_t* d_out_bytes, const ghf_batch_index* index,
+                                 int* d_item_status) {
   if (!c) return GHF_E_INVAL;
-  if (!planes_elem_ok(elem_bytes)) return fail(c, GHF_E_INVAL, "ghf_compress_batch_planes_shared: elem_bytes must be 2, 4 or 8");
+  if (!planes_elem_ok(elem_bytes)) return fail(c, GHF_E_INVAL, (who + ": elem_bytes must be 2, 4 or 8").c_str());
   if (!planes_item_ok(max_item_bytes, elem_bytes))
-    return fail(c, GHF_E_INVAL, "ghf_compress_batch_planes_shared: max_item_bytes must be 1 .. GHF_BATCH_MAX_ITEM and a multiple of elem_bytes");
-  if ((uint64_t)count * elem_bytes > 0xFFFFFFFFull) return fail(c, GHF_E_INVAL, "ghf_compress_batch_planes_shared: count * elem_bytes beyond 32 bits");
+    return fail(c, GHF_E_INVAL, (who + ": max_item_bytes must be 1 .. GHF_BATCH_MAX_ITEM and a multiple of elem_bytes").c_str());
+  if ((uint64_t)count * elem_bytes > 0xFFFFFFFFull) return fail(c, GHF_E_INVAL, (who + ": count * elem_bytes beyond 32 bits").c_str());
   if (index && !planes_index_covers(index, count, elem_bytes, max_item_bytes / elem_bytes))
-    return fail(c, GHF_E_INVAL, "ghf_compress_batch_planes_shared: index does not cover (count * elem_bytes, max_item_bytes / elem_bytes)");
-  if (!d_codes || !aligned16(d_codes)) return fail(c, GHF_E_INVAL, "ghf_compress_batch_planes_shared: d_codes is null or not 16-byte aligned");
+    return fail(c, GHF_E_INVAL, (who + ": index does not cover (count * elem_bytes, max_item_bytes / elem_bytes)").c_str());
+  if (!d_codes || !aligned16(d_codes)) return fail(c, GHF_E_INVAL, (who + ": d_codes is null or not 16-byte aligned").c_str());
+  if (!planes_mask_ok(raw_planes, elem_bytes)) return fail(c, GHF_E_INVAL, (who + ": raw_planes names a plane at or above elem_bytes").c_str());
   if (!d_in_ptrs || !d_in_bytes || !d_out_ptrs || !d_out_caps || !d_out_bytes || !d_item_status) return GHF_E_INVAL;
   if (count == 0) return GHF_OK;
   GHF_HIP(c, hipSetDevice(c->device));
@@ -781,20 +786,50 @@ int ghf_compress_batch_planes_shared(ghf_ctx* c, const uint8_t* const* d_in_ptrs
   p.blocks_per_item = index ? index->blocks_per_item : 0;
   p.segs_per_item = index ? index->segs_per_item : 0;
   p.item_status = d_item_status;
-  launch_compress_batch_planes_shared(p, count, elem_bytes, c->stream);
+  if (forms) launch_compress_batch_planes_forms(p, count, elem_bytes, raw_planes, c->stream);
+  else launch_compress_batch_planes_shared(p, count, elem_bytes, c->stream);
   GHF_HIP(c, hipGetLastError());
   return GHF_OK;
 }
 
-int ghf_decode_batch_planes_shared(ghf_ctx* c, const uint8_t* const* d_stream_ptrs, const uint64_t* d_stream_bytes,
-                                   const ghf_code* d_codes, const ghf_batch_index* index, const uint64_t* d_n_elems, uint32_t count,
-                                   uint32_t elem_bytes, uint8_t* const* d_out_ptrs, const uint64_t* d_out_caps, uint64_t* d_out_bytes,
-                                   int* d_item_status) {
+int ghf_compress_batch_planes_shared(ghf_ctx* c, const uint8_t* const* d_in_ptrs, const uint64_t* d_in_bytes, size_t max_item_bytes,
+                                     uint32_t count, uint32_t elem_bytes, const ghf_code* d_codes, uint8_t* const* d_out_ptrs,
+                                     const uint64_t* d_out_caps, uint64_t* d_out_bytes, const ghf_batch_index* index,
+                                     int* d_item_status) {
+  return compress_batch_planes(c, "ghf_compress_batch_planes_shared", false, d_in_ptrs, d_in_bytes, max_item_bytes, count, elem_bytes, d_codes,
+                               0, d_out_ptrs, d_out_caps, d_out_bytes, index, d_item_status);
+}
+
+int ghf_compress_batch_planes_forms(ghf_ctx* c, const uint8_t* const* d_in_ptrs, const uint64_t* d_in_bytes, size_t max_item_bytes,
+                                    uint32_t count, uint32_t elem_bytes, const ghf_code* d_codes, uint32_t raw_planes,
+                                    uint8_t* const* d_out_ptrs, const uint64_t* d_out_caps, uint64_t* d_out_bytes,
+                                    const ghf_batch_index* index, int* d_item_status) {
+  return compress_batch_planes(c, "ghf_compress_batch_planes_forms", true, d_in_ptrs, d_in_bytes, max_item_bytes, count, elem_bytes, d_codes,
+                               raw_planes, d_out_ptrs, d_out_caps, d_out_bytes, index, d_item_status);
+}
+
+int ghf_batch_planes_raw_auto(ghf_ctx* c, const uint64_t* d_hists, const ghf_code* d_codes, uint32_t elem_bytes, uint32_t* d_raw_planes) {
+  if (!c) return GHF_E_INVAL;
+  if (!planes_elem_ok(elem_bytes)) return fail(c, GHF_E_INVAL, "ghf_batch_planes_raw_auto: elem_bytes must be 2, 4 or 8");
+  if (!d_codes || !aligned16(d_codes)) return fail(c, GHF_E_INVAL, "ghf_batch_planes_raw_auto: d_codes is null or not 16-byte aligned");
+  if (!d_hists || !d_raw_planes) return GHF_E_INVAL;
+  GHF_HIP(c, hipSetDevice(c->device));
+  launch_batch_planes_raw_auto(d_hists, d_codes, elem_bytes, d_raw_planes, c->stream);
+  GHF_HIP(c, hipGetLastError());
+  return GHF_OK;
+}
+
+// ghf_decode_batch_planes_shared (forms = false) and ghf_decode_batch_planes_forms
+static int decode_batch_planes(ghf_ctx* c, const std::string& who, bool forms, const uint8_t* const* d_stream_ptrs,
+                               const uint64_t* d_stream_bytes, const ghf_code* d_codes, const ghf_batch_index* index, const uint64_t* d_n_elems,
+                               uint32_t count, uint32_t elem_bytes, uint32_t raw_planes, uint8_t* const* d_out_ptrs, const uint64_t* d_out_caps,
+                               uint64_t* d_out_bytes, int* d_item_status) {
   if (!c || !index) return GHF_E_INVAL;
-  if (!planes_elem_ok(elem_bytes)) return fail(c, GHF_E_INVAL, "ghf_decode_batch_planes_shared: elem_bytes must be 2, 4 or 8");
+  if (!planes_elem_ok(elem_bytes)) return fail(c, GHF_E_INVAL, (who + ": elem_bytes must be 2, 4 or 8").c_str());
   if (!planes_index_covers(index, count, elem_bytes, 1))
-    return fail(c, GHF_E_INVAL, "ghf_decode_batch_planes_shared: index does not cover count * elem_bytes slots");
-  if (!d_codes || !aligned16(d_codes)) return fail(c, GHF_E_INVAL, "ghf_decode_batch_planes_shared: d_codes is null or not 16-byte aligned");
+    return fail(c, GHF_E_INVAL, (who + ": index does not cover count * elem_bytes slots").c_str());
+  if (!d_codes || !aligned16(d_codes)) return fail(c, GHF_E_INVAL, (who + ": d_codes is null or not 16-byte aligned").c_str());
+  if (!planes_mask_ok(raw_planes, elem_bytes)) return fail(c, GHF_E_INVAL, (who + ": raw_planes names a plane at or above elem_bytes").c_str());
   if (!d_stream_ptrs || !d_stream_bytes || !d_n_elems || !d_out_ptrs || !d_out_caps || !d_out_bytes || !d_item_status)
     return GHF_E_INVAL;
   if (count == 0) return GHF_OK;
@@ -813,19 +848,39 @@ int ghf_decode_batch_planes_shared(ghf_ctx* c, const uint8_t* const* d_stream_pt
   p.out_caps = d_out_caps;
   p.out_bytes = d_out_bytes;
   p.item_status = d_item_status;
-  launch_decode_batch_planes_shared(p, count, elem_bytes, c->stream);
+  if (forms) launch_decode_batch_planes_forms(p, count, elem_bytes, raw_planes, c->stream);
+  else launch_decode_batch_planes_shared(p, count, elem_bytes, c->stream);
   GHF_HIP(c, hipGetLastError());
   return GHF_OK;
 }
 
-int ghf_decode_bodies_batch_planes_shared(ghf_ctx* c, const uint8_t* const* d_stream_ptrs, const uint64_t* d_stream_bytes,
-                                          const ghf_code* d_codes, uint32_t count, uint32_t elem_bytes, uint8_t* const* d_out_ptrs,
-                                          const uint64_t* d_out_caps, uint64_t* d_out_bytes, int* d_item_status) {
+int ghf_decode_batch_planes_shared(ghf_ctx* c, const uint8_t* const* d_stream_ptrs, const uint64_t* d_stream_bytes,
+                                   const ghf_code* d_codes, const ghf_batch_index* index, const uint64_t* d_n_elems, uint32_t count,
+                                   uint32_t elem_bytes, uint8_t* const* d_out_ptrs, const uint64_t* d_out_caps, uint64_t* d_out_bytes,
+                                   int* d_item_status) {
+  return decode_batch_planes(c, "ghf_decode_batch_planes_shared", false, d_stream_ptrs, d_stream_bytes, d_codes, index, d_n_elems, count,
+                             elem_bytes, 0, d_out_ptrs, d_out_caps, d_out_bytes, d_item_status);
+}
+
+int ghf_decode_batch_planes_forms(ghf_ctx* c, const uint8_t* const* d_stream_ptrs, const uint64_t* d_stream_bytes, const ghf_code* d_codes,
+                                  const ghf_batch_index* index, const uint64_t* d_n_elems, uint32_t count, uint32_t elem_bytes,
+                                  uint32_t raw_planes, uint8_t* const* d_out_ptrs, const uint64_t* d_out_caps, uint64_t* d_out_bytes,
+                                  int* d_item_status) {
+  return decode_batch_planes(c, "ghf_decode_batch_planes_forms", true, d_stream_ptrs, d_stream_bytes, d_codes, index, d_n_elems, count,
+                             elem_bytes, raw_planes, d_out_ptrs, d_out_caps, d_out_bytes, d_item_status);
+}
+
+// ghf_decode_bodies_batch_planes_shared (forms = false) and ghf_decode_bodies_batch_planes_forms
+static int decode_bodies_batch_planes(ghf_ctx* c, const std::string& who, bool forms, const uint8_t* const* d_stream_ptrs,
+                                      const uint64_t* d_stream_bytes, const ghf_code* d_codes, uint32_t count, uint32_t elem_bytes,
+                                      uint32_t raw_planes, uint8_t* const* d_out_ptrs, const uint64_t* d_out_caps, uint64_t* d_out_bytes,
+                                      int* d_item_status) {
   if (!c || !d_stream_ptrs || !d_stream_bytes || !d_out_bytes || !d_item_status) return GHF_E_INVAL;
-  if (!planes_elem_ok(elem_bytes)) return fail(c, GHF_E_INVAL, "ghf_decode_bodies_batch_planes_shared: elem_bytes must be 2, 4 or 8");
-  if (d_out_ptrs && !d_out_caps) return fail(c, GHF_E_INVAL, "ghf_decode_bodies_batch_planes_shared: d_out_ptrs without d_out_caps");
+  if (!planes_elem_ok(elem_bytes)) return fail(c, GHF_E_INVAL, (who + ": elem_bytes must be 2, 4 or 8").c_str());
+  if (d_out_ptrs && !d_out_caps) return fail(c, GHF_E_INVAL, (who + ": d_out_ptrs without d_out_caps").c_str());
   if (!d_codes || !aligned16(d_codes))
-    return fail(c, GHF_E_INVAL, "ghf_decode_bodies_batch_planes_shared: d_codes is null or not 16-byte aligned");
+    return fail(c, GHF_E_INVAL, (who + ": d_codes is null or not 16-byte aligned").c_str());
+  if (!planes_mask_ok(raw_planes, elem_bytes)) return fail(c, GHF_E_INVAL, (who + ": raw_planes names a plane at or above elem_bytes").c_str());
   if (count == 0) return GHF_OK;
   GHF_HIP(c, hipSetDevice(c->device));
   BatchPlanesBodiesParams p;
@@ -838,9 +893,24 @@ int ghf_decode_bodies_batch_planes_shared(ghf_ctx* c, const uint8_t* const* d_st
   p.out_bytes = d_out_bytes;
   p.item_status = d_item_status;
   p.stats = c->images_stats;
-  launch_decode_bodies_batch_planes_shared(p, count, elem_bytes, c->stream);
+  if (forms) launch_decode_bodies_batch_planes_forms(p, count, elem_bytes, raw_planes, c->stream);
+  else launch_decode_bodies_batch_planes_shared(p, count, elem_bytes, c->stream);
   GHF_HIP(c, hipGetLastError());
   return GHF_OK;
+}
+
+int ghf_decode_bodies_batch_planes_shared(ghf_ctx* c, const uint8_t* const* d_stream_ptrs, const uint64_t* d_stream_bytes,
+                                          const ghf_code* d_codes, uint32_t count, uint32_t elem_bytes, uint8_t* const* d_out_ptrs,
+                                          const uint64_t* d_out_caps, uint64_t* d_out_bytes, int* d_item_status) {
+  return decode_bodies_batch_planes(c, "ghf_decode_bodies_batch_planes_shared", false, d_stream_ptrs, d_stream_bytes, d_codes, count, elem_bytes,
+                                    0, d_out_ptrs, d_out_caps, d_out_bytes, d_item_status);
+}
+
+int ghf_decode_bodies_batch_planes_forms(ghf_ctx* c, const uint8_t* const* d_stream_ptrs, const uint64_t* d_stream_bytes,
+                                         const ghf_code* d_codes, uint32_t count, uint32_t elem_bytes, uint32_t raw_planes,
+                                         uint8_t* const* d_out_ptrs, const uint64_t* d_out_caps, uint64_t* d_out_bytes, int* d_item_status) {
+  return decode_bodies_batch_planes(c, "ghf_decode_bodies_batch_planes_forms", true, d_stream_ptrs, d_stream_bytes, d_codes, count, elem_bytes,
+                                    raw_planes, d_out_ptrs, d_out_caps, d_out_bytes, d_item_status);
 }
 
 // ---------------------------------------------------------------------------------------------- stored shared-code bodies
@@ -877,11 +947,13 @@ int ghf_batch_seek_pack(ghf_ctx* c, const ghf_batch_index* index, const uint64_t
 static int decode_bodies_batch_seek(ghf_ctx* c, const char* who, const uint8_t* const* d_stream_ptrs, const uint64_t* d_stream_bytes,
                                     const uint8_t* const* d_rec_ptrs, const uint64_t* d_rec_bytes, const ghf_code* d_codes, uint32_t count,
                                     uint32_t elem_bytes, uint8_t* const* d_out_ptrs, const uint64_t* d_out_caps, uint64_t* d_out_bytes,
-                                    int* d_item_status) {
+                                    int* d_item_status, bool forms = false, uint32_t raw_planes = 0) {
   if (!c || !d_stream_ptrs || !d_stream_bytes || !d_rec_ptrs || !d_rec_bytes || !d_out_bytes || !d_item_status) return GHF_E_INVAL;
   if (elem_bytes != 1 && !planes_elem_ok(elem_bytes)) return fail(c, GHF_E_INVAL, (std::string(who) + ": elem_bytes must be 2, 4 or 8").c_str());
   if (d_out_ptrs && !d_out_caps) return fail(c, GHF_E_INVAL, (std::string(who) + ": d_out_ptrs without d_out_caps").c_str());
   if (!d_codes || !aligned16(d_codes)) return fail(c, GHF_E_INVAL, (std::string(who) + ": the code array is null or not 16-byte aligned").c_str());
+  if (forms && !planes_mask_ok(raw_planes, elem_bytes))
+    return fail(c, GHF_E_INVAL, (std::string(who) + ": raw_planes names a plane at or above elem_bytes").c_str());
   if (count == 0) return GHF_OK;
   GHF_HIP(c, hipSetDevice(c->device));
   BatchSeekDecodeParams p;
@@ -895,7 +967,8 @@ static int decode_bodies_batch_seek(ghf_ctx* c, const char* who, const uint8_t* 
   p.out_caps = d_out_caps;
   p.out_bytes = d_out_bytes;
   p.item_status = d_item_status;
-  launch_decode_bodies_batch_seek(p, count, elem_bytes, c->stream);
+  if (forms) launch_decode_bodies_batch_planes_forms_seek(p, count, elem_bytes, raw_planes, c->stream);
+  else launch_decode_bodies_batch_seek(p, count, elem_bytes, c->stream);
   GHF_HIP(c, hipGetLastError());
   return GHF_OK;
 }
@@ -916,6 +989,16 @@ int ghf_decode_bodies_batch_planes_shared_seek(ghf_ctx* c, const uint8_t* const*
     return fail(c, GHF_E_INVAL, "ghf_decode_bodies_batch_planes_shared_seek: elem_bytes must be 2, 4 or 8");
   return decode_bodies_batch_seek(c, "ghf_decode_bodies_batch_planes_shared_seek", d_stream_ptrs, d_stream_bytes, d_rec_ptrs, d_rec_bytes,
                                   d_codes, count, elem_bytes, d_out_ptrs, d_out_caps, d_out_bytes, d_item_status);
+}
+
+int ghf_decode_bodies_batch_planes_forms_seek(ghf_ctx* c, const uint8_t* const* d_stream_ptrs, const uint64_t* d_stream_bytes,
+                                              const uint8_t* const* d_rec_ptrs, const uint64_t* d_rec_bytes, const ghf_code* d_codes,
+                                              uint32_t count, uint32_t elem_bytes, uint32_t raw_planes, uint8_t* const* d_out_ptrs,
+                                              const uint64_t* d_out_caps, uint64_t* d_out_bytes, int* d_item_status) {
+  if (c && !planes_elem_ok(elem_bytes))
+    return fail(c, GHF_E_INVAL, "ghf_decode_bodies_batch_planes_forms_seek: elem_bytes must be 2, 4 or 8");
+  return decode_bodies_batch_seek(c, "ghf_decode_bodies_batch_planes_forms_seek", d_stream_ptrs, d_stream_bytes, d_rec_ptrs, d_rec_bytes,
+                                  d_codes, count, elem_bytes, d_out_ptrs, d_out_caps, d_out_bytes, d_item_status, true, raw_planes);
 }
 
 // ---------------------------------------------------------------------------------------------- decode

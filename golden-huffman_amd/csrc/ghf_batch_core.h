@@ -6,7 +6,8 @@
 // decoder is made of: the table fill of one vetted code (batch_code_tables) with the code check in front of it
 // (batch_code_ok), and the three round loops -- the one that follows a side-car (batch_decode_segments), the one that
 // finds the code boundaries itself (batch_decode_rounds) and the one that follows a run record (batch_decode_runs) --
-// each over the way its stage leaves (StoreFlat, StorePlane).  Which kernels call them and which still carry a
+// each over the way its stage leaves (StoreFlat, StorePlane) -- and the raw form of a byte plane, packed and copied
+// back without a code (batch_raw_compress_body, batch_raw_plane_copy).  Which kernels call them and which still carry a
 // written-out copy, and why: profiles/batch_core/README.md.
 #ifndef GHF_BATCH_CORE_H_
 #define GHF_BATCH_CORE_H_
@@ -795,6 +796,82 @@ __device__ __forceinline__ void batch_decode_runs(Lds& S, const uint8_t* stream,
     __syncthreads();
     carry += round_bits;
   }
+}
+
+// ----------------------------------------------------------------------------------------------------------------------
+// the raw form of a byte plane of the batch: slot j = i * E + p holds the n bytes in[p], in[p + E],
+// .. of item i and nothing else -- no code, no header, no end mark.  batch_raw_compress_body is what a workgroup of the
+// forms packer runs for a raw slot in place of batch_shared_compress_body; batch_raw_plane_copy is what the forms
+// decoders run for a raw plane in place of the table fill and the round loop.
+// ----------------------------------------------------------------------------------------------------------------------
+// the verdicts and their order are batch_shared_compress_body's without the code's: the item, the slot's pointer, the cap
+// -- all before the first store.  Each lane takes rows of 16 symbols through PlaneItem::load16 (E vectors narrowed with
+// v_perm_b32, at any alignment of the item) and stores one vector to the aligned slot; the ragged end goes byte by
+// byte, nothing at or beyond n is written.  No pricing pass, no table, no LDS.
+template <int E>
+__device__ __forceinline__ void batch_raw_compress_body(const BatchSharedSlot& W, PlaneItem<E> it) {
+  const int tid = threadIdx.x;
+  const uint32_t slot = W.slot;
+  auto finish = [&](int status, uint64_t bytes) {  // every lane of the workgroup takes the same exit
+    if (tid == 0) {
+      W.item_status[slot] = status;
+      W.out_bytes[slot] = bytes;
+    }
+  };
+  const int refused = it.open();
+  if (refused) return finish(refused, 0);
+  uint8_t* __restrict__ const out = W.out_ptrs[slot];
+  if (!out || (reinterpret_cast<uintptr_t>(out) & 15u)) return finish(GHF_E_INVAL, 0);
+  const uint32_t n = it.n;
+  if (n > W.out_caps[slot]) return finish(GHF_E_CAP, 0);
+  for (uint32_t off = (uint32_t)tid * 16u; off < n; off += kBatchRoundSymbols) {
+    const uint4 v = it.load16(off);
+    if (off + 16u <= n) {
+      *reinterpret_cast<uint4*>(out + off) = v;
+    } else {
+#pragma unroll
+      for (uint32_t j = 0; j < 16; ++j)
+        if (off + j < n) out[off + j] = (uint8_t)batch_byte(v, (int)j);
+    }
+  }
+  finish(GHF_OK, n);
+}
+
+// stream[0 .. n) -> out[k * E + p]: rounds of stage_bytes (a multiple of 16; the stage keeps four spare words behind them)
+// -- 16-byte loads of the aligned slot into the stage, then the strided byte stores of StorePlane<E>, so that a wave's
+// stores fall on consecutive elements as the dense planes' do.  The stream's ragged end is read byte by byte: no byte
+// outside stream[0 .. n) is read.  Every lane of the workgroup calls it with the same arguments; nobody reads the stage
+// when it starts (a barrier lies behind the plane before), and a barrier closes the last round.
+template <int E>
+__device__ __forceinline__ void batch_raw_plane_copy(uint32_t* stage, uint32_t stage_bytes, const uint8_t* stream, uint32_t n,
+                                                     uint8_t* out, uint32_t p, int tid) {
+#pragma unroll 1
+  for (uint32_t rb = 0; rb < n; rb += stage_bytes) {
+    const uint32_t rbytes = n - rb < stage_bytes ? n - rb : stage_bytes;
+    for (uint32_t q = (uint32_t)tid * 16u; q < rbytes; q += kBatchThreads * 16u) {
+      const uint32_t off = rb + q;
+      uint4 v;
+      if (off + 16u <= n) {
+        v = *reinterpret_cast<const uint4*>(stream + off);
+      } else {
+        uint32_t w[4] = {0, 0, 0, 0};
+#pragma unroll
+        for (uint32_t j = 0; j < 16; ++j)
+          if (off + j < n) w[j >> 2] |= (uint32_t)stream[off + j] << (8 * (j & 3));
+        v = make_uint4(w[0], w[1], w[2], w[3]);
+      }
+      *reinterpret_cast<uint4*>(&stage[q >> 2]) = v;
+    }
+    __syncthreads();
+    StorePlane<E>{p}(out, rb, stage, rbytes, tid);
+    __syncthreads();
+  }
+}
+
+// a raw slot's size as a symbol count: 1 .. GHF_BATCH_MAX_ITEM / E (the decoders that have nothing else to go by)
+template <int E>
+__device__ __forceinline__ bool batch_raw_count_ok(uint64_t stream_bytes) {
+  return stream_bytes != 0 && stream_bytes <= GHF_BATCH_MAX_ITEM / E;
 }
 
 }  // namespace ghf

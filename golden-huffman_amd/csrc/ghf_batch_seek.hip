@@ -1,6 +1,7 @@
 // golden-huffman_amd/csrc/ghf_batch_seek.hip -- stored shared-code bodies: the run record of a body and the decoders that
 // follow it (ghf_batch_seek_pack, ghf_decode_bodies_batch_shared_seek, ghf_decode_bodies_batch_planes_shared_seek,
-// include/ghf.h).
+// include/ghf.h; ghf_decode_bodies_batch_planes_forms_seek, where some planes are stored raw:
+// section 24).
 //
 // ghf_decode_batch_shared / ghf_decode_batch_planes_shared follow a live ghf_batch_index: 6.25 % of the input in device
 // memory, gone with the process that compressed.  ghf_decode_bodies_batch_shared / .._planes_shared need nothing but the
@@ -189,6 +190,73 @@ __global__ __launch_bounds__(kBatchThreads) void k_decode_bodies_batch_planes_sh
   }
 }
 
+// ----------------------------------------------------------------------------------------------------------------------
+// decode, byte planes in two forms: bit p of `raw` (a kernel argument, the same in every wave) says
+// that plane p is stored as it is.  A raw slot has no record -- its pointer and size are not looked at -- and no code:
+// its count is its size, held against its bounds and against the records of the dense planes before the first store.
+// ----------------------------------------------------------------------------------------------------------------------
+template <int E, bool kWrite>
+__global__ __launch_bounds__(kBatchThreads) void k_decode_bodies_batch_planes_forms_seek(BatchSeekDecodeParams P, uint32_t raw) {
+  __shared__ BatchSeekLds S;
+  const int tid = threadIdx.x;
+  const uint32_t item = blockIdx.x;
+  const size_t slot0 = (size_t)item * E;
+  if (tid == 0) S.err = 0;
+  int status = GHF_OK;  // the same in every lane, as is all below
+#pragma unroll 1
+  for (int p = 0; p < E; ++p)
+    if (!(raw >> p & 1u) && !batch_code_ok(S.vet, P.codes + p, tid)) status = GHF_E_FORMAT;  // (raw is uniform: so are the barriers)
+  __syncthreads();  // (S.err, when every plane is raw)
+  uint8_t* const out = kWrite && status == GHF_OK ? P.out_ptrs[item] : nullptr;
+  uint32_t n = 0;
+  if (status == GHF_OK) {
+    bool inval = kWrite && !out;
+#pragma unroll
+    for (int p = 0; p < E; ++p) {
+      const uint8_t* const sp = P.stream_ptrs[slot0 + p];
+      inval |= !sp || (reinterpret_cast<uintptr_t>(sp) & 15u);
+      if (raw >> p & 1u) {
+        inval |= !batch_raw_count_ok<E>(P.stream_bytes[slot0 + p]);
+      } else {
+        const uint8_t* const rp = P.rec_ptrs[slot0 + p];
+        inval |= !rp || (reinterpret_cast<uintptr_t>(rp) & 15u) || P.stream_bytes[slot0 + p] > P.max_stream_bytes;
+      }
+    }
+    if (inval) status = GHF_E_INVAL;
+  }
+  if (status == GHF_OK) {
+    bool differ = false;
+#pragma unroll 1
+    for (int p = 0; p < E && status == GHF_OK; ++p) {
+      uint32_t np = 0;
+      if (raw >> p & 1u) np = (uint32_t)P.stream_bytes[slot0 + p];
+      else status = batch_seek_open(P.rec_ptrs[slot0 + p], P.rec_bytes[slot0 + p], &np);
+      differ |= p != 0 && np != n;
+      n = np;
+    }
+    if (status == GHF_OK && differ) status = GHF_E_CORRUPT;  // the planes of one item hold the same number of symbols
+  }
+  if (kWrite) {
+    if (status == GHF_OK && (uint64_t)n * E > P.out_caps[item]) status = GHF_E_CAP;  // before any store
+#pragma unroll 1
+    for (uint32_t p = 0; p < E && status == GHF_OK; ++p) {
+      if (raw >> p & 1u) {
+        batch_raw_plane_copy<E>(S.stage, kBatchSeekRoundBytes, P.stream_ptrs[slot0 + p], n, out, p, tid);
+        continue;
+      }
+      int lb, long_from, max_len;
+      batch_code_tables(S.t, P.codes + p, tid, lb, long_from, max_len);
+      batch_decode_runs(S, P.stream_ptrs[slot0 + p], P.stream_bytes[slot0 + p], P.rec_ptrs[slot0 + p], n, out, lb, long_from, max_len,
+                        StorePlane<E>{p});
+      if (S.err) status = GHF_E_CORRUPT;  // (a barrier lies behind the last write of S.err)
+    }
+  }
+  if (tid == 0) {
+    P.item_status[item] = status;
+    P.out_bytes[item] = status == GHF_OK ? (uint64_t)n * E : 0;
+  }
+}
+
 // ---- launchers ---------------------------------------------------------------------------------------------------------
 void launch_batch_seek_pack(const BatchSeekPackParams& p, uint32_t slots, hipStream_t s) {
   if (slots == 0) return;
@@ -205,6 +273,23 @@ void launch_decode_bodies_batch_seek(const BatchSeekDecodeParams& p, uint32_t co
     if (p.out_ptrs) hipLaunchKernelGGL(k_decode_bodies_batch_shared_seek<true>, grid, block, 0, s, p);
     else hipLaunchKernelGGL(k_decode_bodies_batch_shared_seek<false>, grid, block, 0, s, p);
   } else if (elem_bytes == 2) {
+    GHF_CALL(2);
+  } else if (elem_bytes == 4) {
+    GHF_CALL(4);
+  } else {
+    GHF_CALL(8);
+  }
+#undef GHF_CALL
+}
+
+void launch_decode_bodies_batch_planes_forms_seek(const BatchSeekDecodeParams& p, uint32_t count, uint32_t elem_bytes, uint32_t raw_planes,
+                                                  hipStream_t s) {
+  if (count == 0) return;
+  const dim3 grid(count), block(kBatchThreads);
+#define GHF_CALL(E)                                                                                                          \
+  if (p.out_ptrs) hipLaunchKernelGGL((k_decode_bodies_batch_planes_forms_seek<E, true>), grid, block, 0, s, p, raw_planes); \
+  else hipLaunchKernelGGL((k_decode_bodies_batch_planes_forms_seek<E, false>), grid, block, 0, s, p, raw_planes)
+  if (elem_bytes == 2) {
     GHF_CALL(2);
   } else if (elem_bytes == 4) {
     GHF_CALL(4);

@@ -180,6 +180,8 @@ EXPORTS = [
     "ghf_decode_planes_sparse_range_delta",
     "ghf_planes_split_to", "ghf_planes_merge_from", "ghf_planes_merge_range_from", "ghf_compress_planes_forms",
     "ghf_decode_planes_forms", "ghf_decode_planes_forms_range",
+    "ghf_batch_planes_raw_auto", "ghf_compress_batch_planes_forms", "ghf_decode_batch_planes_forms",
+    "ghf_decode_bodies_batch_planes_forms", "ghf_decode_bodies_batch_planes_forms_seek",
 ]
 COMM_ID_BYTES = 128
 
@@ -309,6 +311,11 @@ def lib():
     L.ghf_batch_seek_pack.argtypes = [vp, C.POINTER(BatchIndex), vp, u32, u32, vp, vp, vp, vp]
     L.ghf_decode_bodies_batch_shared_seek.argtypes = [vp, vp, vp, vp, vp, vp, u32, vp, vp, vp, vp]
     L.ghf_decode_bodies_batch_planes_shared_seek.argtypes = [vp, vp, vp, vp, vp, vp, u32, u32, vp, vp, vp, vp]
+    L.ghf_batch_planes_raw_auto.argtypes = [vp, vp, vp, u32, vp]
+    L.ghf_compress_batch_planes_forms.argtypes = [vp, vp, vp, sz, u32, u32, vp, u32, vp, vp, vp, C.POINTER(BatchIndex), vp]
+    L.ghf_decode_batch_planes_forms.argtypes = [vp, vp, vp, vp, C.POINTER(BatchIndex), vp, u32, u32, u32, vp, vp, vp, vp]
+    L.ghf_decode_bodies_batch_planes_forms.argtypes = [vp, vp, vp, vp, u32, u32, u32, vp, vp, vp, vp]
+    L.ghf_decode_bodies_batch_planes_forms_seek.argtypes = [vp, vp, vp, vp, vp, vp, u32, u32, u32, vp, vp, vp, vp]
     L.ghf_histogram_planes.argtypes = [vp, vp, sz, u32, C.c_uint, vp]
     L.ghf_planes_image_bytes.argtypes = [vp, vp, vp, u32, vp]
     L.ghf_compress_planes_coded.argtypes = [vp, vp, sz, u32, vp, C.c_uint, vp, sz, vp, C.POINTER(Index)]
@@ -949,11 +956,12 @@ class Context:
         return d_codes
 
     def compress_batch_planes_shared(self, items, d_codes, elem_bytes, sizes=None, max_item_bytes=None, d_out=None, out_stride=None,
-                                     index=None):
+                                     index=None, raw_planes=None):
         """compress_batch_shared per byte plane: slot i * elem_bytes + p holds the BODY of plane p of item i under d_codes[p],
         at d_out[slot * out_stride ..).  index: None or batch_index_alloc(count * elem_bytes, max_item_bytes // elem_bytes).
         -> dict(out, out_stride, out_bytes int64[slots], status int32[slots], codes, in_ptrs, in_bytes, out_ptrs, out_caps,
-                count, elem_bytes, max_item_bytes, n_elems int64[count])"""
+                count, elem_bytes, max_item_bytes, n_elems int64[count])
+        raw_planes (None: this call; an int: ghf_compress_batch_planes_forms, see compress_batch_planes_forms)"""
         t = self.torch
         ptrs, sizes = self._item_arrays(items, sizes)
         count = len(sizes)
@@ -969,11 +977,19 @@ class Context:
         out_caps = t.full((max(slots, 1),), out_stride, dtype=t.int64, device=self.device)
         out_bytes = t.zeros(max(slots, 1), dtype=t.int64, device=self.device)
         status = t.full((max(slots, 1),), -1, dtype=t.int32, device=self.device)
-        self._chk(
-            self.L.ghf_compress_batch_planes_shared(self.h, in_ptrs.data_ptr(), in_bytes.data_ptr(), max_item_bytes, count, elem_bytes,
-                                                    d_codes.data_ptr(), out_ptrs.data_ptr(), out_caps.data_ptr(), out_bytes.data_ptr(),
-                                                    None if index is None else C.byref(index), status.data_ptr()),
-            "ghf_compress_batch_planes_shared")
+        ix = None if index is None else C.byref(index)
+        if raw_planes is None:
+            self._chk(
+                self.L.ghf_compress_batch_planes_shared(self.h, in_ptrs.data_ptr(), in_bytes.data_ptr(), max_item_bytes, count, elem_bytes,
+                                                        d_codes.data_ptr(), out_ptrs.data_ptr(), out_caps.data_ptr(), out_bytes.data_ptr(),
+                                                        ix, status.data_ptr()),
+                "ghf_compress_batch_planes_shared")
+        else:
+            self._chk(
+                self.L.ghf_compress_batch_planes_forms(self.h, in_ptrs.data_ptr(), in_bytes.data_ptr(), max_item_bytes, count, elem_bytes,
+                                                       d_codes.data_ptr(), raw_planes, out_ptrs.data_ptr(), out_caps.data_ptr(),
+                                                       out_bytes.data_ptr(), ix, status.data_ptr()),
+                "ghf_compress_batch_planes_forms")
         return {"out": d_out, "out_stride": out_stride, "out_bytes": out_bytes[:slots], "status": status[:slots], "codes": d_codes,
                 "in_ptrs": in_ptrs, "in_bytes": in_bytes, "out_ptrs": out_ptrs, "out_caps": out_caps, "count": count,
                 "elem_bytes": elem_bytes, "max_item_bytes": max_item_bytes, "n_elems": in_bytes // elem_bytes, "keep": items}
@@ -986,7 +1002,7 @@ class Context:
         return d_out, out_ptrs, t.full((max(count, 1),), out_stride, dtype=t.int64, device=self.device)
 
     def decode_batch_planes_shared(self, stream_ptrs, stream_bytes, d_codes, index, n_elems, elem_bytes, d_out=None, out_stride=None,
-                                   out_ptrs=None, out_caps=None):
+                                   out_ptrs=None, out_caps=None, raw_planes=None):
         """the way back with the live side-car: stream_ptrs / stream_bytes int64[count * elem_bytes] (out_ptrs and out_bytes
         of compress_batch_planes_shared), n_elems int64[count].  Item i is decoded to d_out[i * out_stride ..) unless
         out_ptrs / out_caps (bytes) say otherwise.  -> dict(out, out_stride, out_bytes int64[count], status int32[count])"""
@@ -998,15 +1014,22 @@ class Context:
             d_out, out_ptrs, out_caps = self._planes_out(count, out_stride, d_out)
         out_bytes = t.zeros(max(count, 1), dtype=t.int64, device=self.device)
         status = t.full((max(count, 1),), -1, dtype=t.int32, device=self.device)
-        self._chk(
-            self.L.ghf_decode_batch_planes_shared(self.h, stream_ptrs.data_ptr(), stream_bytes.data_ptr(), d_codes.data_ptr(),
-                                                  C.byref(index), n_elems.data_ptr(), count, elem_bytes, out_ptrs.data_ptr(),
-                                                  out_caps.data_ptr(), out_bytes.data_ptr(), status.data_ptr()),
-            "ghf_decode_batch_planes_shared")
+        if raw_planes is None:
+            self._chk(
+                self.L.ghf_decode_batch_planes_shared(self.h, stream_ptrs.data_ptr(), stream_bytes.data_ptr(), d_codes.data_ptr(),
+                                                      C.byref(index), n_elems.data_ptr(), count, elem_bytes, out_ptrs.data_ptr(),
+                                                      out_caps.data_ptr(), out_bytes.data_ptr(), status.data_ptr()),
+                "ghf_decode_batch_planes_shared")
+        else:
+            self._chk(
+                self.L.ghf_decode_batch_planes_forms(self.h, stream_ptrs.data_ptr(), stream_bytes.data_ptr(), d_codes.data_ptr(),
+                                                     C.byref(index), n_elems.data_ptr(), count, elem_bytes, raw_planes, out_ptrs.data_ptr(),
+                                                     out_caps.data_ptr(), out_bytes.data_ptr(), status.data_ptr()),
+                "ghf_decode_batch_planes_forms")
         return {"out": d_out, "out_stride": out_stride, "out_bytes": out_bytes[:count], "status": status[:count],
                 "out_ptrs": out_ptrs, "out_caps": out_caps}
 
-    def decode_bodies_batch_planes_shared(self, stream_ptrs, stream_bytes, d_codes, elem_bytes, out=None, caps=None):
+    def decode_bodies_batch_planes_shared(self, stream_ptrs, stream_bytes, d_codes, elem_bytes, out=None, caps=None, raw_planes=None):
         """the way back from nothing but the bytes: stream_ptrs / stream_bytes int64[count * elem_bytes].
         out=None: the sizes pass -> dict(out_bytes int64[count] (bytes), status int32[count]).
         Otherwise the decode pass, with out / caps (bytes per item) as in decode_images_batch."""
@@ -1027,12 +1050,17 @@ class Context:
             out_ptrs = out.data_ptr() + t.arange(count, dtype=t.int64, device=self.device) * out_stride
             out_caps = t.clamp(caps.to(t.int64), max=out_stride).contiguous()
             res.update(out=out, out_stride=out_stride, out_ptrs=out_ptrs, out_caps=out_caps)
-        self._chk(
-            self.L.ghf_decode_bodies_batch_planes_shared(self.h, stream_ptrs.data_ptr(), stream_bytes.data_ptr(), d_codes.data_ptr(),
-                                                         count, elem_bytes, None if out_ptrs is None else out_ptrs.data_ptr(),
-                                                         None if out_caps is None else out_caps.data_ptr(), out_bytes.data_ptr(),
-                                                         status.data_ptr()),
-            "ghf_decode_bodies_batch_planes_shared")
+        op, oc = None if out_ptrs is None else out_ptrs.data_ptr(), None if out_caps is None else out_caps.data_ptr()
+        if raw_planes is None:
+            self._chk(
+                self.L.ghf_decode_bodies_batch_planes_shared(self.h, stream_ptrs.data_ptr(), stream_bytes.data_ptr(), d_codes.data_ptr(),
+                                                             count, elem_bytes, op, oc, out_bytes.data_ptr(), status.data_ptr()),
+                "ghf_decode_bodies_batch_planes_shared")
+        else:
+            self._chk(
+                self.L.ghf_decode_bodies_batch_planes_forms(self.h, stream_ptrs.data_ptr(), stream_bytes.data_ptr(), d_codes.data_ptr(),
+                                                            count, elem_bytes, raw_planes, op, oc, out_bytes.data_ptr(), status.data_ptr()),
+                "ghf_decode_bodies_batch_planes_forms")
         return res
 
     # ---- stored shared-code bodies: one run record per body, the persistent form of a slice of a BatchIndex ----
@@ -1095,7 +1123,7 @@ class Context:
         return res
 
     def decode_bodies_batch_planes_shared_seek(self, stream_ptrs, stream_bytes, rec_ptrs, rec_bytes, d_codes, elem_bytes, out=None,
-                                               caps=None):
+                                               caps=None, raw_planes=None):
         """the same for the slots of compress_batch_planes_shared: stream_* / rec_* int64[count * elem_bytes]; out / caps
         (bytes per item) as in decode_bodies_batch_planes_shared."""
         t = self.torch
@@ -1105,14 +1133,55 @@ class Context:
         res = {"out_bytes": out_bytes[:count], "status": status[:count]}
         out_ptrs, out_caps, more = self._seek_out(count, out, caps, "decode_bodies_batch_planes_shared_seek")
         res.update(more)
-        self._chk(
-            self.L.ghf_decode_bodies_batch_planes_shared_seek(self.h, stream_ptrs.data_ptr(), stream_bytes.data_ptr(),
-                                                              rec_ptrs.data_ptr(), rec_bytes.data_ptr(), d_codes.data_ptr(), count,
-                                                              elem_bytes, None if out_ptrs is None else out_ptrs.data_ptr(),
-                                                              None if out_caps is None else out_caps.data_ptr(),
-                                                              out_bytes.data_ptr(), status.data_ptr()),
-            "ghf_decode_bodies_batch_planes_shared_seek")
+        op, oc = None if out_ptrs is None else out_ptrs.data_ptr(), None if out_caps is None else out_caps.data_ptr()
+        if raw_planes is None:
+            self._chk(
+                self.L.ghf_decode_bodies_batch_planes_shared_seek(self.h, stream_ptrs.data_ptr(), stream_bytes.data_ptr(),
+                                                                  rec_ptrs.data_ptr(), rec_bytes.data_ptr(), d_codes.data_ptr(), count,
+                                                                  elem_bytes, op, oc, out_bytes.data_ptr(), status.data_ptr()),
+                "ghf_decode_bodies_batch_planes_shared_seek")
+        else:
+            self._chk(
+                self.L.ghf_decode_bodies_batch_planes_forms_seek(self.h, stream_ptrs.data_ptr(), stream_bytes.data_ptr(),
+                                                                 rec_ptrs.data_ptr(), rec_bytes.data_ptr(), d_codes.data_ptr(), count,
+                                                                 elem_bytes, raw_planes, op, oc, out_bytes.data_ptr(), status.data_ptr()),
+                "ghf_decode_bodies_batch_planes_forms_seek")
         return res
+
+    # ---- the plane batch calls with raw planes: raw_planes is one int for the batch, bit p = plane p stored as it is ----
+    def batch_planes_raw_auto(self, d_hists, d_codes, out=None):
+        """d_hists int64[E, 257], d_codes uint8[E, sizeof(Code)] -> an int32[1] CUDA tensor holding the mask of the planes
+        that store no more raw than coded (sum hist * length >= 8 * sum hist).  No host synchronisation: int(mask.item())
+        when the caller wants it."""
+        elem_bytes = int(d_hists.numel()) // NSYM
+        mask = self.torch.zeros(1, dtype=self.torch.int32, device=self.device) if out is None else out
+        self._chk(self.L.ghf_batch_planes_raw_auto(self.h, d_hists.data_ptr(), d_codes.data_ptr(), elem_bytes, mask.data_ptr()),
+                  "ghf_batch_planes_raw_auto")
+        return mask
+
+    def compress_batch_planes_forms(self, items, d_codes, elem_bytes, raw_planes, **kw):
+        """compress_batch_planes_shared with the planes of raw_planes stored raw: a raw slot holds the plane's n bytes and
+        out_bytes[slot] = n.  The dict carries raw_planes too."""
+        r = self.compress_batch_planes_shared(items, d_codes, elem_bytes, raw_planes=int(raw_planes), **kw)
+        r["raw_planes"] = int(raw_planes)
+        return r
+
+    def decode_batch_planes_forms(self, stream_ptrs, stream_bytes, d_codes, index, n_elems, elem_bytes, raw_planes, **kw):
+        """decode_batch_planes_shared for the slots of compress_batch_planes_forms"""
+        return self.decode_batch_planes_shared(stream_ptrs, stream_bytes, d_codes, index, n_elems, elem_bytes, raw_planes=int(raw_planes),
+                                               **kw)
+
+    def decode_bodies_batch_planes_forms(self, stream_ptrs, stream_bytes, d_codes, elem_bytes, raw_planes, out=None, caps=None):
+        """decode_bodies_batch_planes_shared for the slots of compress_batch_planes_forms: a raw slot's count is its size"""
+        return self.decode_bodies_batch_planes_shared(stream_ptrs, stream_bytes, d_codes, elem_bytes, out=out, caps=caps,
+                                                      raw_planes=int(raw_planes))
+
+    def decode_bodies_batch_planes_forms_seek(self, stream_ptrs, stream_bytes, rec_ptrs, rec_bytes, d_codes, elem_bytes, raw_planes,
+                                              out=None, caps=None):
+        """decode_bodies_batch_planes_shared_seek for the slots of compress_batch_planes_forms: the record pointer and size of
+        a raw slot are ignored"""
+        return self.decode_bodies_batch_planes_shared_seek(stream_ptrs, stream_bytes, rec_ptrs, rec_bytes, d_codes, elem_bytes, out=out,
+                                                           caps=caps, raw_planes=int(raw_planes))
 
     # ---- byte planes: elements of 2, 4 or 8 bytes, one ordinary .crs2 image per byte position ---------
     planes_slot_bytes = staticmethod(planes_slot_bytes)

@@ -664,6 +664,82 @@ int ghf_decode_bodies_batch_planes_shared(ghf_ctx* ctx, const uint8_t* const* d_
                                           uint8_t* const* d_out_ptrs, const uint64_t* d_out_caps, uint64_t* d_out_bytes,
                                           int* d_item_status /* [count] */);
 
+/* ---- the plane batch calls with raw planes ------------------------------------
+ * No reference counterpart (include/compressor.h:62-73 always codes what it is given; 87-92 always decodes).  A mantissa
+ * plane of normal floats holds nearly uniform bytes: its code has 7 to 10 bits, its bodies store MORE than the plane's
+ * bytes (each rounds up behind an end mark) and the bodies-only decoder spends most of its passes on it.  The _forms calls
+ * store such a plane RAW: slot j = i * E + p of a raw plane p holds the n_i bytes in[p], in[p + E], ... of item i and
+ * nothing else -- no magic, no header, no end mark, as the raw form of ghf_compress_planes_forms.  A dense plane's slot stays
+ * byte for byte what ghf_compress_batch_planes_shared writes, so ghf_write_header(d_codes + p) || body is still a
+ * standalone .crs2.  Which planes are raw is ONE host value for the batch, uint32_t raw_planes (bit p = plane p), passed to
+ * every call; no container records it.  A bit at or above elem_bytes: GHF_E_INVAL at call level.  raw_planes == 0 gives
+ * exactly what the _shared call of the same name gives, in every output array.
+ * Conventions, call-level errors and per-slot / per-item statuses are those of the calls above, with these rules:
+ *   - d_codes[p] of a raw plane is never read: it may be garbage.  Only the codes of the dense planes are vetted; a bad one
+ *     is GHF_E_FORMAT as in the _shared call (compress: on that plane's slots; decode: on every item, nothing written).
+ *   - the order of the verdicts is the _shared call's: FORMAT, EMPTY / INVAL, CAP, CORRUPT.
+ *   - nothing at or beyond d_out_caps is written; no byte outside stream[0 .. d_stream_bytes[j]) is read.
+ *   - ghf_batch_seek_pack does not change: on the index of ghf_compress_batch_planes_forms it gives the records of the dense
+ *     slots as ever; a raw slot's slice of the index was not written, so what the call reports for a raw slot (status,
+ *     size, record bytes) is NOT SPECIFIED and the caller ignores it -- a raw slot has no record. */
+
+/* No reference counterpart (include/compressor.h:62-73 never asks whether coding pays; 87-92).  One tiny launch, asynchronous,
+ * never synchronises: *d_raw_planes (a device word) <- the mask of the planes that are better stored raw under d_codes
+ * (device ghf_code[elem_bytes], 16-byte aligned) given the counts d_hists (device u64[elem_bytes][257], as
+ * ghf_histogram_batch_planes leaves them).  Plane p is raw exactly when
+ *     sum over s < 256 of d_hists[p][s] * d_codes[p].length[s]  >=  8 * sum over s < 256 of d_hists[p][s]
+ * and the right-hand sum is not 0 -- 64-bit integer arithmetic on the arrays as given, slot 256 (the end mark) not
+ * counted.  With exact counts a raw plane then never stores more than its bodies would.  A code whose min_len / max_len
+ * fail the length bounds (1 <= min_len <= max_len <= 32) leaves its plane dense: ghf_compress_batch_planes_forms reports that
+ * code.  A null context or pointer, an elem_bytes other than 2, 4 or 8, misaligned d_codes: GHF_E_INVAL. */
+int ghf_batch_planes_raw_auto(ghf_ctx* ctx, const uint64_t* d_hists /* [elem_bytes][257] */, const ghf_code* d_codes /* [elem_bytes] */,
+                              uint32_t elem_bytes, uint32_t* d_raw_planes);
+
+/* No reference counterpart (generalises include/compressor.h:62-73; 87-92 is the way back).  ghf_compress_batch_planes_shared
+ * with the planes of raw_planes stored raw.  Arguments and per-slot statuses are that call's.  For a raw slot j of item i
+ * with n_i elements: d_out_ptrs[j][0 .. n_i) <- the plane's bytes, d_out_bytes[j] <- n_i; GHF_E_CAP when n_i >
+ * d_out_caps[j], and then nothing is written; GHF_E_EMPTY, and GHF_E_INVAL for a null item, an oversized item, a size that
+ * is not a multiple of elem_bytes or a null / misaligned slot pointer, as for a dense slot; never GHF_E_FORMAT or
+ * GHF_E_NOCODE.  A raw slot's slice of `index` is not written.  ghf_compress_batch_planes_shared_bound (>= n_i) stays the
+ * capacity that always suffices. */
+int ghf_compress_batch_planes_forms(ghf_ctx* ctx, const uint8_t* const* d_in_ptrs, const uint64_t* d_in_bytes,
+                                    size_t max_item_bytes, uint32_t count, uint32_t elem_bytes, const ghf_code* d_codes,
+                                    uint32_t raw_planes, uint8_t* const* d_out_ptrs, const uint64_t* d_out_caps,
+                                    uint64_t* d_out_bytes, const ghf_batch_index* index /* optional */,
+                                    int* d_item_status /* [count * elem_bytes] */);
+
+/* No reference counterpart (include/compressor.h:62-73 is the way there; generalises 87-92).  ghf_decode_batch_planes_shared
+ * (the live side-car) with the planes of raw_planes stored raw.  A raw slot needs a non-null, 16-byte aligned pointer
+ * (GHF_E_INVAL otherwise) and d_stream_bytes[j] == d_n_elems[i] (GHF_E_CORRUPT otherwise, seen before the item's first
+ * store); its slice of `index` is not read. */
+int ghf_decode_batch_planes_forms(ghf_ctx* ctx, const uint8_t* const* d_stream_ptrs, const uint64_t* d_stream_bytes,
+                                  const ghf_code* d_codes, const ghf_batch_index* index, const uint64_t* d_n_elems,
+                                  uint32_t count, uint32_t elem_bytes, uint32_t raw_planes, uint8_t* const* d_out_ptrs,
+                                  const uint64_t* d_out_caps, uint64_t* d_out_bytes, int* d_item_status /* [count] */);
+
+/* No reference counterpart (include/compressor.h:62-73 is the way there; generalises 87-92).
+ * ghf_decode_bodies_batch_planes_shared (nothing but the bytes; d_out_ptrs == NULL: sizes only) with the planes of raw_planes
+ * stored raw.  A raw slot's symbol count IS d_stream_bytes[j]: 0 or more than GHF_BATCH_MAX_ITEM / elem_bytes is
+ * GHF_E_INVAL (as is a null or misaligned pointer).  A raw slot takes part in "the planes of one item hold the same number
+ * of symbols" (GHF_E_CORRUPT), and an item whose planes are all raw decodes from the sizes alone.  The raw planes of an item
+ * are held against their bounds, the cap (GHF_E_CAP) and each other before the item's first store. */
+int ghf_decode_bodies_batch_planes_forms(ghf_ctx* ctx, const uint8_t* const* d_stream_ptrs, const uint64_t* d_stream_bytes,
+                                         const ghf_code* d_codes, uint32_t count, uint32_t elem_bytes, uint32_t raw_planes,
+                                         uint8_t* const* d_out_ptrs, const uint64_t* d_out_caps, uint64_t* d_out_bytes,
+                                         int* d_item_status /* [count] */);
+
+/* No reference counterpart (include/compressor.h:62-73 is the way there; generalises 87-92).
+ * ghf_decode_bodies_batch_planes_shared_seek (bodies with their run records, below) with the planes of raw_planes stored raw.
+ * A raw slot has no record: d_rec_ptrs[j] and d_rec_bytes[j] are ignored and may be null / 0 (the two arrays themselves are
+ * required).  Its count is d_stream_bytes[j], under the bounds of ghf_decode_bodies_batch_planes_forms, and must agree with
+ * the records of the dense planes (GHF_E_CORRUPT).  As there, all pointers, record headers and counts of an item are
+ * vetted before its first store. */
+int ghf_decode_bodies_batch_planes_forms_seek(ghf_ctx* ctx, const uint8_t* const* d_stream_ptrs /* [count * elem_bytes] */,
+                                              const uint64_t* d_stream_bytes, const uint8_t* const* d_rec_ptrs /* [count * elem_bytes] */,
+                                              const uint64_t* d_rec_bytes, const ghf_code* d_codes /* [elem_bytes] */, uint32_t count,
+                                              uint32_t elem_bytes, uint32_t raw_planes, uint8_t* const* d_out_ptrs /* [count] */,
+                                              const uint64_t* d_out_caps, uint64_t* d_out_bytes, int* d_item_status /* [count] */);
+
 /* ---- stored shared-code bodies: the run record, the persistent form of a batch's side-car -------------
  * No reference counterpart (the reference compresses one file per process, include/compressor.h:62-73, and reads one back,
  * include/compressor.h:87-92).  ghf_decode_batch_shared and ghf_decode_batch_planes_shared need the live ghf_batch_index:
