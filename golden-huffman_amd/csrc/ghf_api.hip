@@ -786,8 +786,7 @@ static int compress_batch_planes(ghf_ctx* c, const std::string& who, bool forms,
   p.blocks_per_item = index ? index->blocks_per_item : 0;
   p.segs_per_item = index ? index->segs_per_item : 0;
   p.item_status = d_item_status;
-  if (forms) launch_compress_batch_planes_forms(p, count, elem_bytes, raw_planes, c->stream);
-  else launch_compress_batch_planes_shared(p, count, elem_bytes, c->stream);
+  launch_compress_batch_planes(p, count, elem_bytes, forms, raw_planes, c->stream);
   GHF_HIP(c, hipGetLastError());
   return GHF_OK;
 }
@@ -848,8 +847,7 @@ static int decode_batch_planes(ghf_ctx* c, const std::string& who, bool forms, c
   p.out_caps = d_out_caps;
   p.out_bytes = d_out_bytes;
   p.item_status = d_item_status;
-  if (forms) launch_decode_batch_planes_forms(p, count, elem_bytes, raw_planes, c->stream);
-  else launch_decode_batch_planes_shared(p, count, elem_bytes, c->stream);
+  launch_decode_batch_planes(p, count, elem_bytes, forms, raw_planes, c->stream);
   GHF_HIP(c, hipGetLastError());
   return GHF_OK;
 }
@@ -893,8 +891,7 @@ static int decode_bodies_batch_planes(ghf_ctx* c, const std::string& who, bool f
   p.out_bytes = d_out_bytes;
   p.item_status = d_item_status;
   p.stats = c->images_stats;
-  if (forms) launch_decode_bodies_batch_planes_forms(p, count, elem_bytes, raw_planes, c->stream);
-  else launch_decode_bodies_batch_planes_shared(p, count, elem_bytes, c->stream);
+  launch_decode_bodies_batch_planes(p, count, elem_bytes, forms, raw_planes, c->stream);
   GHF_HIP(c, hipGetLastError());
   return GHF_OK;
 }
@@ -967,8 +964,7 @@ static int decode_bodies_batch_seek(ghf_ctx* c, const char* who, const uint8_t* 
   p.out_caps = d_out_caps;
   p.out_bytes = d_out_bytes;
   p.item_status = d_item_status;
-  if (forms) launch_decode_bodies_batch_planes_forms_seek(p, count, elem_bytes, raw_planes, c->stream);
-  else launch_decode_bodies_batch_seek(p, count, elem_bytes, c->stream);
+  launch_decode_bodies_batch_seek(p, count, elem_bytes, forms, raw_planes, c->stream);
   GHF_HIP(c, hipGetLastError());
   return GHF_OK;
 }

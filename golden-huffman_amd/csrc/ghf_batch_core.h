@@ -8,7 +8,8 @@
 // finds the code boundaries itself (batch_decode_rounds) and the one that follows a run record (batch_decode_runs) --
 // each over the way its stage leaves (StoreFlat, StorePlane) -- and the raw form of a byte plane, packed and copied
 // back without a code (batch_raw_compress_body, batch_raw_plane_copy).  Which kernels call them and which still carry a
-// written-out copy, and why: profiles/batch_core/README.md.
+// written-out copy, and why: profiles/batch_core/README.md; why the plane decoders and their raw-plane twins are still
+// written out beside each other: profiles/batch_planes_bodies/README.md.
 #ifndef GHF_BATCH_CORE_H_
 #define GHF_BATCH_CORE_H_
 #include "ghf_code_rules.h"

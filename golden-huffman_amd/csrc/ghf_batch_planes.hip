@@ -245,7 +245,9 @@ __global__ __launch_bounds__(kBatchThreads) void k_decode_bodies_batch_planes_sh
 // Planes in two forms: bit p of `raw` (a kernel argument: the same in every wave, an SGPR) says
 // that plane p of the batch is stored as it is -- slot j = i * E + p holds the n bytes of the plane, nothing else.  A
 // dense slot is what the kernels above write and read, byte for byte; codes[p] of a raw plane is never read.  The
-// kernels above stay as they are: these are their plane loops with the raw branch in front of the table fill.
+// kernels above stay as they are: these are their plane loops with the raw branch in front of the table fill.  (One body
+// per pair over <E, kForms> was built and lost timing rows to these written-out forms: profiles/batch_planes_bodies/README.md;
+// tests/test_gpu_batch_planes_twins.py holds each pair to the same verdicts.)
 // ----------------------------------------------------------------------------------------------------------------------
 // which planes are raw: plane p is when sum hist[p][s] * length[p][s] >= 8 * sum hist[p][s] over s < 256 and the right
 // side is not 0 (64-bit integers; the end mark is not counted): then its bodies, each rounded up behind an end mark, never
@@ -456,20 +458,11 @@ __global__ __launch_bounds__(kBatchThreads) void k_decode_bodies_batch_planes_fo
 }
 
 // ---- launchers ---------------------------------------------------------------------------------------------------------
-#define GHF_PLANES_DISPATCH(E_, CALL) \
-  do {                                \
-    if ((E_) == 2) { CALL(2); }       \
-    else if ((E_) == 4) { CALL(4); }  \
-    else { CALL(8); }                 \
-  } while (0)
-
 void launch_histogram_batch_planes(const BatchPlanesHistParams& p, uint32_t elem_bytes, uint32_t flags, hipStream_t s) {
   if (p.count == 0) return;
   (void)hipMemsetAsync(p.hists, 0, (size_t)elem_bytes * GHF_NSYM * sizeof(uint64_t), s);
-  const uint32_t grid = p.count < hist_planes_grid(elem_bytes) ? p.count : hist_planes_grid(elem_bytes);
-#define GHF_CALL(E) hipLaunchKernelGGL(k_histogram_batch_planes<E>, dim3(grid), dim3(kBatchThreads), 0, s, p)
-  GHF_PLANES_DISPATCH(elem_bytes, GHF_CALL);
-#undef GHF_CALL
+  const dim3 grid(p.count < hist_planes_grid(elem_bytes) ? p.count : hist_planes_grid(elem_bytes)), block(kBatchThreads);
+  with_elem_bytes(elem_bytes, [&](auto e) { hipLaunchKernelGGL(k_histogram_batch_planes<decltype(e)::value>, grid, block, 0, s, p); });
   launch_histogram_batch_finish(p.hists, elem_bytes, flags, s);
 }
 
@@ -479,62 +472,49 @@ void launch_build_codes(const uint64_t* d_hists, uint32_t n_codes, ghf_code* d_c
   else hipLaunchKernelGGL(k_build_codes<false>, dim3(n_codes), dim3(64), 0, s, h, d_codes, d_status, flags & GHF_EMPTY_OK);
 }
 
-void launch_compress_batch_planes_shared(const BatchPlanesCompressParams& p, uint32_t count, uint32_t elem_bytes, hipStream_t s) {
-  if (count == 0) return;
-  const dim3 grid(count * elem_bytes);
-#define GHF_CALL(E) hipLaunchKernelGGL(k_compress_batch_planes_shared<E>, grid, dim3(kBatchThreads), 0, s, p)
-  GHF_PLANES_DISPATCH(elem_bytes, GHF_CALL);
-#undef GHF_CALL
-}
-
-void launch_decode_batch_planes_shared(const BatchPlanesDecodeParams& p, uint32_t count, uint32_t elem_bytes, hipStream_t s) {
-  if (count == 0) return;
-#define GHF_CALL(E) hipLaunchKernelGGL(k_decode_batch_planes_shared<E>, dim3(count), dim3(kBatchThreads), 0, s, p)
-  GHF_PLANES_DISPATCH(elem_bytes, GHF_CALL);
-#undef GHF_CALL
-}
-
-void launch_decode_bodies_batch_planes_shared(const BatchPlanesBodiesParams& p, uint32_t count, uint32_t elem_bytes, hipStream_t s) {
-  if (count == 0) return;
-#define GHF_CALL(E)                                                                                                                \
-  if (p.out_ptrs) hipLaunchKernelGGL((k_decode_bodies_batch_planes_shared<E, true>), dim3(count), dim3(kBatchThreads), 0, s, p); \
-  else hipLaunchKernelGGL((k_decode_bodies_batch_planes_shared<E, false>), dim3(count), dim3(kBatchThreads), 0, s, p)
-  GHF_PLANES_DISPATCH(elem_bytes, GHF_CALL);
-#undef GHF_CALL
-}
-
 void launch_batch_planes_raw_auto(const uint64_t* d_hists, const ghf_code* d_codes, uint32_t elem_bytes, uint32_t* d_raw_planes,
                                   hipStream_t s) {
   hipLaunchKernelGGL(k_batch_planes_raw_auto, dim3(1), dim3(kBatchThreads), 0, s, reinterpret_cast<const unsigned long long*>(d_hists),
                      d_codes, elem_bytes, d_raw_planes);
 }
 
-void launch_compress_batch_planes_forms(const BatchPlanesCompressParams& p, uint32_t count, uint32_t elem_bytes, uint32_t raw_planes,
-                                        hipStream_t s) {
+// forms: the _forms kernel with raw_planes behind the struct; else the _shared kernel, which takes no mask
+void launch_compress_batch_planes(const BatchPlanesCompressParams& p, uint32_t count, uint32_t elem_bytes, bool forms, uint32_t raw_planes,
+                                  hipStream_t s) {
   if (count == 0) return;
-  const dim3 grid(count * elem_bytes);
-#define GHF_CALL(E) hipLaunchKernelGGL(k_compress_batch_planes_forms<E>, grid, dim3(kBatchThreads), 0, s, p, raw_planes)
-  GHF_PLANES_DISPATCH(elem_bytes, GHF_CALL);
-#undef GHF_CALL
+  const dim3 grid(count * elem_bytes), block(kBatchThreads);
+  with_elem_bytes(elem_bytes, [&](auto e) {
+    constexpr int E = decltype(e)::value;
+    if (forms) hipLaunchKernelGGL(k_compress_batch_planes_forms<E>, grid, block, 0, s, p, raw_planes);
+    else hipLaunchKernelGGL(k_compress_batch_planes_shared<E>, grid, block, 0, s, p);
+  });
 }
 
-void launch_decode_batch_planes_forms(const BatchPlanesDecodeParams& p, uint32_t count, uint32_t elem_bytes, uint32_t raw_planes,
-                                      hipStream_t s) {
+void launch_decode_batch_planes(const BatchPlanesDecodeParams& p, uint32_t count, uint32_t elem_bytes, bool forms, uint32_t raw_planes,
+                                hipStream_t s) {
   if (count == 0) return;
-#define GHF_CALL(E) hipLaunchKernelGGL(k_decode_batch_planes_forms<E>, dim3(count), dim3(kBatchThreads), 0, s, p, raw_planes)
-  GHF_PLANES_DISPATCH(elem_bytes, GHF_CALL);
-#undef GHF_CALL
+  const dim3 grid(count), block(kBatchThreads);
+  with_elem_bytes(elem_bytes, [&](auto e) {
+    constexpr int E = decltype(e)::value;
+    if (forms) hipLaunchKernelGGL(k_decode_batch_planes_forms<E>, grid, block, 0, s, p, raw_planes);
+    else hipLaunchKernelGGL(k_decode_batch_planes_shared<E>, grid, block, 0, s, p);
+  });
 }
 
-void launch_decode_bodies_batch_planes_forms(const BatchPlanesBodiesParams& p, uint32_t count, uint32_t elem_bytes, uint32_t raw_planes,
-                                             hipStream_t s) {
+void launch_decode_bodies_batch_planes(const BatchPlanesBodiesParams& p, uint32_t count, uint32_t elem_bytes, bool forms,
+                                       uint32_t raw_planes, hipStream_t s) {
   if (count == 0) return;
-#define GHF_CALL(E)                                                                                                                           \
-  if (p.out_ptrs) hipLaunchKernelGGL((k_decode_bodies_batch_planes_forms<E, true>), dim3(count), dim3(kBatchThreads), 0, s, p, raw_planes); \
-  else hipLaunchKernelGGL((k_decode_bodies_batch_planes_forms<E, false>), dim3(count), dim3(kBatchThreads), 0, s, p, raw_planes)
-  GHF_PLANES_DISPATCH(elem_bytes, GHF_CALL);
-#undef GHF_CALL
+  const dim3 grid(count), block(kBatchThreads);
+  with_elem_bytes(elem_bytes, [&](auto e) {
+    constexpr int E = decltype(e)::value;
+    auto write = [&](auto w) {  // p.out_ptrs null: sizes only
+      constexpr bool kWrite = decltype(w)::value;
+      if (forms) hipLaunchKernelGGL((k_decode_bodies_batch_planes_forms<E, kWrite>), grid, block, 0, s, p, raw_planes);
+      else hipLaunchKernelGGL((k_decode_bodies_batch_planes_shared<E, kWrite>), grid, block, 0, s, p);
+    };
+    if (p.out_ptrs) write(std::true_type());
+    else write(std::false_type());
+  });
 }
-#undef GHF_PLANES_DISPATCH
 
 }  // namespace ghf

@@ -194,6 +194,7 @@ __global__ __launch_bounds__(kBatchThreads) void k_decode_bodies_batch_planes_sh
 // decode, byte planes in two forms: bit p of `raw` (a kernel argument, the same in every wave) says
 // that plane p is stored as it is.  A raw slot has no record -- its pointer and size are not looked at -- and no code:
 // its count is its size, held against its bounds and against the records of the dense planes before the first store.
+// (Written out beside its parent: one body for the pair lost timing rows, profiles/batch_planes_bodies/README.md.)
 // ----------------------------------------------------------------------------------------------------------------------
 template <int E, bool kWrite>
 __global__ __launch_bounds__(kBatchThreads) void k_decode_bodies_batch_planes_forms_seek(BatchSeekDecodeParams P, uint32_t raw) {
@@ -263,40 +264,27 @@ void launch_batch_seek_pack(const BatchSeekPackParams& p, uint32_t slots, hipStr
   hipLaunchKernelGGL(k_batch_seek_pack, dim3(slots), dim3(kBatchThreads), 0, s, p);
 }
 
-void launch_decode_bodies_batch_seek(const BatchSeekDecodeParams& p, uint32_t count, uint32_t elem_bytes, hipStream_t s) {
+// elem_bytes == 1: the flat kernel (no planes, no mask).  Else forms: the _forms_seek kernel with raw_planes behind the
+// struct, or the _shared_seek kernel, which takes no mask.  p.out_ptrs null: sizes only
+void launch_decode_bodies_batch_seek(const BatchSeekDecodeParams& p, uint32_t count, uint32_t elem_bytes, bool forms, uint32_t raw_planes,
+                                     hipStream_t s) {
   if (count == 0) return;
   const dim3 grid(count), block(kBatchThreads);
-#define GHF_CALL(E)                                                                                               \
-  if (p.out_ptrs) hipLaunchKernelGGL((k_decode_bodies_batch_planes_shared_seek<E, true>), grid, block, 0, s, p); \
-  else hipLaunchKernelGGL((k_decode_bodies_batch_planes_shared_seek<E, false>), grid, block, 0, s, p)
   if (elem_bytes == 1) {
     if (p.out_ptrs) hipLaunchKernelGGL(k_decode_bodies_batch_shared_seek<true>, grid, block, 0, s, p);
     else hipLaunchKernelGGL(k_decode_bodies_batch_shared_seek<false>, grid, block, 0, s, p);
-  } else if (elem_bytes == 2) {
-    GHF_CALL(2);
-  } else if (elem_bytes == 4) {
-    GHF_CALL(4);
-  } else {
-    GHF_CALL(8);
+    return;
   }
-#undef GHF_CALL
-}
-
-void launch_decode_bodies_batch_planes_forms_seek(const BatchSeekDecodeParams& p, uint32_t count, uint32_t elem_bytes, uint32_t raw_planes,
-                                                  hipStream_t s) {
-  if (count == 0) return;
-  const dim3 grid(count), block(kBatchThreads);
-#define GHF_CALL(E)                                                                                                          \
-  if (p.out_ptrs) hipLaunchKernelGGL((k_decode_bodies_batch_planes_forms_seek<E, true>), grid, block, 0, s, p, raw_planes); \
-  else hipLaunchKernelGGL((k_decode_bodies_batch_planes_forms_seek<E, false>), grid, block, 0, s, p, raw_planes)
-  if (elem_bytes == 2) {
-    GHF_CALL(2);
-  } else if (elem_bytes == 4) {
-    GHF_CALL(4);
-  } else {
-    GHF_CALL(8);
-  }
-#undef GHF_CALL
+  with_elem_bytes(elem_bytes, [&](auto e) {
+    constexpr int E = decltype(e)::value;
+    auto write = [&](auto w) {
+      constexpr bool kWrite = decltype(w)::value;
+      if (forms) hipLaunchKernelGGL((k_decode_bodies_batch_planes_forms_seek<E, kWrite>), grid, block, 0, s, p, raw_planes);
+      else hipLaunchKernelGGL((k_decode_bodies_batch_planes_shared_seek<E, kWrite>), grid, block, 0, s, p);
+    };
+    if (p.out_ptrs) write(std::true_type());
+    else write(std::false_type());
+  });
 }
 
 }  // namespace ghf

@@ -489,24 +489,21 @@ void launch_histogram_batch_finish(uint64_t* d_hists, uint32_t n_hists, uint32_t
 // ghf_batch_planes.hip: elem_bytes is 2, 4 or 8
 void launch_histogram_batch_planes(const BatchPlanesHistParams& p, uint32_t elem_bytes, uint32_t flags, hipStream_t s);  // zeroes, counts, finishes
 void launch_build_codes(const uint64_t* d_hists, uint32_t n_codes, ghf_code* d_codes, int* d_status, uint32_t flags, hipStream_t s);
-void launch_compress_batch_planes_shared(const BatchPlanesCompressParams& p, uint32_t count, uint32_t elem_bytes, hipStream_t s);  // grid = count * E
-void launch_decode_batch_planes_shared(const BatchPlanesDecodeParams& p, uint32_t count, uint32_t elem_bytes, hipStream_t s);      // grid = count
-void launch_decode_bodies_batch_planes_shared(const BatchPlanesBodiesParams& p, uint32_t count, uint32_t elem_bytes, hipStream_t s);
-// the same with the planes of `raw_planes` (bit p = plane p, below elem_bytes) stored raw; d_raw_planes <- the mask the rule picks
+// d_raw_planes <- the mask the rule picks (bit p = plane p, below elem_bytes)
 void launch_batch_planes_raw_auto(const uint64_t* d_hists, const ghf_code* d_codes, uint32_t elem_bytes, uint32_t* d_raw_planes,
                                   hipStream_t s);
-void launch_compress_batch_planes_forms(const BatchPlanesCompressParams& p, uint32_t count, uint32_t elem_bytes, uint32_t raw_planes,
-                                        hipStream_t s);
-void launch_decode_batch_planes_forms(const BatchPlanesDecodeParams& p, uint32_t count, uint32_t elem_bytes, uint32_t raw_planes,
-                                      hipStream_t s);
-void launch_decode_bodies_batch_planes_forms(const BatchPlanesBodiesParams& p, uint32_t count, uint32_t elem_bytes, uint32_t raw_planes,
-                                             hipStream_t s);
-// ghf_batch_seek.hip: elem_bytes is 1 (flat items), 2, 4 or 8
+// forms: the _forms kernel, with the planes of `raw_planes` stored raw; else the _shared kernel, which takes no mask
+void launch_compress_batch_planes(const BatchPlanesCompressParams& p, uint32_t count, uint32_t elem_bytes, bool forms, uint32_t raw_planes,
+                                  hipStream_t s);  // grid = count * E
+void launch_decode_batch_planes(const BatchPlanesDecodeParams& p, uint32_t count, uint32_t elem_bytes, bool forms, uint32_t raw_planes,
+                                hipStream_t s);  // grid = count
+void launch_decode_bodies_batch_planes(const BatchPlanesBodiesParams& p, uint32_t count, uint32_t elem_bytes, bool forms,
+                                       uint32_t raw_planes, hipStream_t s);
+// ghf_batch_seek.hip: elem_bytes is 1 (flat items; no forms), 2, 4 or 8
 void launch_batch_seek_pack(const BatchSeekPackParams& p, uint32_t slots, hipStream_t s);  // one launch, grid = slots
-void launch_decode_bodies_batch_seek(const BatchSeekDecodeParams& p, uint32_t count, uint32_t elem_bytes, hipStream_t s);  // grid = count
-// elem_bytes 2, 4 or 8, the planes of `raw_planes` stored raw (no record)
-void launch_decode_bodies_batch_planes_forms_seek(const BatchSeekDecodeParams& p, uint32_t count, uint32_t elem_bytes, uint32_t raw_planes,
-                                                  hipStream_t s);
+// forms: as above; a raw plane has no record
+void launch_decode_bodies_batch_seek(const BatchSeekDecodeParams& p, uint32_t count, uint32_t elem_bytes, bool forms, uint32_t raw_planes,
+                                     hipStream_t s);  // grid = count
 // ghf_planes.hip: byte planes of elements of 2, 4 or 8 bytes (n_elems > 0; every pointer and plane_stride 16-byte aligned).
 // d_base (may be null) in every launch: the interleaved side is taken against it -- the planes of
 // d_in ^ d_base, d_out = merge ^ d_base -- by the _delta kernels; null launches exactly the plain kernel
