@@ -1,6 +1,6 @@
 // golden-huffman_amd/csrc/ghf_api_planes.hip -- the byte-plane family of the C ABI of include/ghf.h (DESIGN.md sections 14,
-// 17 - 21, 23): split / merge / compress, the staged calls, the element range, the calls against a base, sparse planes with
-// their rank tables, and planes in three forms.  Host-side only, like ghf_api.hip: argument checks, workspace, launches.
+// 17 - 21, 23, 25): split / merge / compress, the staged calls, the element range, the calls against a base, sparse planes with
+// their rank tables, planes in three forms, and many rows in one call.  Host-side only, like ghf_api.hip: argument checks, workspace, launches.
 // Every step the drivers share -- the slot rule, the compress-side checks, the side-cars, packing a dense or a sparse plane,
 // decoding a stored stream, the parts of a range -- is written once, in front of the drivers that call it.
 #include <algorithm>
@@ -1139,6 +1139,61 @@ int ghf_decode_planes_forms_range(ghf_ctx* c, const uint8_t* const* h_stream_ptr
   return decode_planes_sparse_range(c, "ghf_decode_planes_forms_range", h_stream_ptrs, h_stream_bytes, d_codes, indexes, h_infos,
                                     h_table_ptrs, h_table_bytes, h_rank_infos, h_rank_ptrs, base_opt(d_base), raw_planes, sparse_planes,
                                     n_elems, elem_bytes, first, count, d_out, cap);
+}
+
+// ------------------------------------------------------------------------------------------ many rows in one call
+// (no reference counterpart).  One launch whatever n_rows is; the rows' failures are their own
+// (d_row_status) and nothing here or on the device touches the context's status word.
+int ghf_decode_planes_gather(ghf_ctx* c, const uint8_t* const* h_stream_ptrs, const size_t* h_stream_bytes, const ghf_code* d_codes,
+                             const ghf_seek_info* h_infos, const uint8_t* const* h_table_ptrs, const size_t* h_table_bytes,
+                             unsigned raw_planes, size_t n_elems, uint32_t elem_bytes, const uint64_t* d_index, uint64_t index_stride,
+                             uint32_t row_elems, uint32_t n_rows, uint8_t* d_out, size_t out_stride, int32_t* d_row_status) {
+  if (!c) return GHF_E_INVAL;
+  const char* const who = "ghf_decode_planes_gather";
+  const std::string f = std::string(who) + ": ";
+  const uint32_t E = elem_bytes;
+  if (!elem_bytes_ok(E)) return fail(c, GHF_E_INVAL, (f + "elem_bytes must be 2, 4 or 8").c_str());
+  const PlaneForms forms = {E, raw_planes, 0, n_elems, nullptr};
+  if ((raw_planes >> E) != 0) return fail(c, GHF_E_INVAL, (f + "raw_planes has bits below elem_bytes only").c_str());
+  if (row_elems == 0 || row_elems > GHF_GATHER_MAX_ROW_ELEMS)
+    return fail(c, GHF_E_INVAL, (f + "row_elems must be 1 .. GHF_GATHER_MAX_ROW_ELEMS").c_str());
+  if (out_stride < (size_t)row_elems * E) return fail(c, GHF_E_INVAL, (f + "out_stride below row_elems * elem_bytes").c_str());
+  // the codes and tables of raw planes are not looked at: a tensor of nothing but raw planes needs none
+  const bool all_raw = forms.all_raw();
+  if (!h_stream_ptrs || !h_stream_bytes || !d_index || !d_out || !d_row_status ||
+      (!all_raw && (!d_codes || !h_infos || !h_table_ptrs || !h_table_bytes)))
+    return fail(c, GHF_E_INVAL, (f + "a required pointer is null").c_str());
+  for (uint32_t p = 0; p < E; ++p)
+    if (!h_stream_ptrs[p] || !aligned16(h_stream_ptrs[p]) || (!forms.is_raw(p) && (!h_table_ptrs[p] || !aligned16(h_table_ptrs[p]))))
+      return fail(c, GHF_E_INVAL, (f + "a stream or table pointer is null or not 16-byte aligned").c_str());
+  if (!aligned16(d_out) || !aligned16(d_codes) || (reinterpret_cast<uintptr_t>(d_index) & 7u) || (reinterpret_cast<uintptr_t>(d_row_status) & 3u))
+    return fail(c, GHF_E_INVAL, (f + "d_out and d_codes must be 16-byte, d_index 8-byte and d_row_status 4-byte aligned").c_str());
+  for (uint32_t p = 0; p < E; ++p)
+    if (forms.is_raw(p) && h_stream_bytes[p] != n_elems) return fail(c, GHF_E_INVAL, (f + "a raw plane does not have n_elems bytes").c_str());
+  for (uint32_t p = 0; p < E; ++p) {
+    if (forms.is_raw(p)) continue;
+    if (h_infos[p].n_symbols != n_elems) return fail(c, GHF_E_INVAL, (f + "a dense stream does not have n_elems symbols").c_str());
+    const int rc = seek_table_ok(c, who, h_infos + p, h_table_ptrs[p], h_table_bytes[p]);
+    if (rc) return rc;
+  }
+  if (n_rows == 0) return GHF_OK;
+  PlanesGatherParams g = {};
+  for (uint32_t p = 0; p < E; ++p) {
+    g.streams[p] = h_stream_ptrs[p];
+    g.stream_bytes[p] = h_stream_bytes[p];
+    g.records[p] = forms.is_raw(p) ? nullptr : h_table_ptrs[p] + kSeekHeaderBytes;
+  }
+  g.codes = d_codes;
+  g.n_elems = n_elems;
+  g.n_blocks = blocks_for(n_elems);  // what seek_table_ok held every table's size against
+  g.index = d_index;
+  g.index_stride = index_stride;
+  g.row_elems = row_elems;
+  g.n_rows = n_rows;
+  g.out = d_out;
+  g.out_stride = out_stride;
+  g.row_status = d_row_status;
+  return queued(c, [&] { launch_decode_planes_gather(g, E, raw_planes, c->stream); });
 }
 
 }  // extern "C"

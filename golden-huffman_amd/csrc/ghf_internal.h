@@ -550,5 +550,25 @@ void launch_planes_image_bytes(const uint64_t* d_hists, const ghf_code* d_codes,
 // latches GHF_E_FORMAT (a code is not a complete prefix code) or GHF_E_NOCODE (a counted byte has no code) at *d_status
 void launch_planes_vet_codes(const uint64_t* d_hists, const ghf_code* d_codes, uint32_t elem_bytes, int* d_status, hipStream_t s);
 
+// ghf_planes_gather.hip: rows [index[r] * index_stride, + row_elems) of a tensor of n_elems elements
+// stored as elem_bytes planes, each a .crs2 image with a seek table or raw -> out + r * out_stride; row_status[r] <- the row's
+// verdict.  Entry p of the arrays is plane p's; a raw plane's stream is the plane and its records and code are not read.
+struct PlanesGatherParams {
+  const uint8_t* streams[GHF_PLANES_MAX];  // 16-byte aligned
+  uint64_t stream_bytes[GHF_PLANES_MAX];
+  const uint8_t* records[GHF_PLANES_MAX];  // the seek table behind its header: n_blocks records
+  const ghf_code* codes;                   // [elem_bytes]
+  uint64_t n_elems, n_blocks;              // n_blocks = blocks_for(n_elems), what every table was held against
+  const uint64_t* index;                   // [n_rows]
+  uint64_t index_stride;
+  uint32_t row_elems, n_rows;              // 1 <= row_elems <= GHF_GATHER_MAX_ROW_ELEMS
+  uint32_t stage_bytes;                    // the launch's dynamic LDS: filled in by the launcher from row_elems
+  uint8_t* out;
+  uint64_t out_stride;                     // >= row_elems * elem_bytes
+  int32_t* row_status;                     // [n_rows]
+};
+// one launch whatever n_rows is (none when it is 0); raw_planes has bits below elem_bytes only
+void launch_decode_planes_gather(const PlanesGatherParams& p, uint32_t elem_bytes, uint32_t raw_planes, hipStream_t s);
+
 }  // namespace ghf
 #endif

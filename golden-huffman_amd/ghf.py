@@ -36,6 +36,7 @@ SPARSE_GROUPS = 256 * 16
 SPARSE_SCAN = SPARSE_GROUPS
 SPARSE_RANK_ELEMS = 32768  # GHF_SPARSE_RANK_ELEMS: the elements of a rank block: 4096 mask bytes, one seek block
 RAW_AUTO = 0x80000000  # GHF_RAW_AUTO (ghf_compress_planes_forms): a plane whose image would be at least n_elems bytes is stored raw
+GATHER_MAX_ROW_ELEMS = 32768  # GHF_GATHER_MAX_ROW_ELEMS: the longest row of ghf_decode_planes_gather
 SPARSE_AUTO = 0x80000000  # GHF_SPARSE_AUTO (ghf_compress_planes_sparse): planes with at least 3/4 zero bytes are stored sparse
 EMPTY_OK = 2  # opt-in: n == 0 -> header of the one-symbol code + 0x7F (builder's definition, parity unpinned)
 
@@ -179,7 +180,7 @@ EXPORTS = [
     "ghf_compress_planes_sparse_ranked", "ghf_compress_planes_sparse_ranked_delta", "ghf_decode_planes_sparse_range",
     "ghf_decode_planes_sparse_range_delta",
     "ghf_planes_split_to", "ghf_planes_merge_from", "ghf_planes_merge_range_from", "ghf_compress_planes_forms",
-    "ghf_decode_planes_forms", "ghf_decode_planes_forms_range",
+    "ghf_decode_planes_forms", "ghf_decode_planes_forms_range", "ghf_decode_planes_gather",
     "ghf_batch_planes_raw_auto", "ghf_compress_batch_planes_forms", "ghf_decode_batch_planes_forms",
     "ghf_decode_bodies_batch_planes_forms", "ghf_decode_bodies_batch_planes_forms_seek",
 ]
@@ -361,6 +362,8 @@ def lib():
     L.ghf_decode_planes_forms.argtypes = [vp, C.POINTER(vp), C.POINTER(sz), vp, C.POINTER(Index), vp, C.c_uint, C.c_uint, C.POINTER(sz),
                                           sz, u32, vp, sz, vp]
     L.ghf_decode_planes_forms_range.argtypes = sparse_range_front + [vp, C.c_uint, C.c_uint, sz, u32, u64, u64, vp, sz]
+    L.ghf_decode_planes_gather.argtypes = [vp, C.POINTER(vp), C.POINTER(sz), vp, C.POINTER(SeekInfo), C.POINTER(vp), C.POINTER(sz), C.c_uint,
+                                           sz, u32, vp, u64, u32, u32, vp, sz, vp]
     _lib = L
     return L
 
@@ -1763,6 +1766,38 @@ class Context:
                                                        sparse_planes, n_elems, elem_bytes, first, count, d_out.data_ptr(), cap),
                   "ghf_decode_planes_forms_range")
         return d_out
+
+    def decode_planes_gather(self, streams, stream_bytes, d_codes, raw_planes, n_elems, elem_bytes, d_index, row_elems, index_stride=None,
+                             infos=None, d_tables=None, table_bytes=None, n_rows=None, d_out=None, out_stride=None, d_row_status=None):
+        """rows [d_index[r] * index_stride, + row_elems) of a tensor stored by compress_planes_forms without sparse planes, ONE
+        launch whatever the number of rows: streams / stream_bytes / infos / d_tables are the first elem_bytes entries of
+        decode_planes_forms_range's (seek tables are the only source of run starts; a raw plane's info and table may be None).
+        d_index: int64 / uint64 CUDA tensor of row indices; index_stride defaults to row_elems (a lookup by row id).  d_out
+        (uint8, out_stride bytes from row to row, default row_elems * elem_bytes) and d_row_status (int32[n_rows]) are
+        allocated when not given.  A failed row stores nothing and never latches the context.  Never synchronises.
+        -> (d_out, d_row_status)"""
+        t = self.torch
+        E = elem_bytes
+        n_rows = d_index.numel() if n_rows is None else n_rows
+        index_stride = row_elems if index_stride is None else index_stride
+        out_stride = row_elems * E if out_stride is None else out_stride
+        ptrs = (C.c_void_p * E)(*[None if x is None else x if isinstance(x, int) else x.data_ptr() for x in streams[:E]])
+        sizes = (C.c_size_t * E)(*[int(v) for v in stream_bytes[:E]])
+        h_infos = t_ptrs = t_bytes = None
+        if infos is not None:
+            h_infos = (SeekInfo * E)(*[SeekInfo() if i is None else i for i in infos[:E]])
+            t_ptrs = (C.c_void_p * E)(*[None if x is None else x if isinstance(x, int) else x.data_ptr() for x in d_tables[:E]])
+            if table_bytes is None:
+                table_bytes = [0 if i is None else seek_bytes(i.n_symbols) for i in infos[:E]]
+            t_bytes = (C.c_size_t * E)(*[int(v) for v in table_bytes[:E]])
+        if d_out is None:
+            d_out = self.empty_u8(max(n_rows, 1) * out_stride)
+        if d_row_status is None:
+            d_row_status = t.zeros(max(n_rows, 1), dtype=t.int32, device=self.device)
+        self._chk(self.L.ghf_decode_planes_gather(self.h, ptrs, sizes, None if d_codes is None else d_codes.data_ptr(), h_infos, t_ptrs,
+                                                  t_bytes, raw_planes, n_elems, E, d_index.data_ptr(), index_stride, row_elems, n_rows,
+                                                  d_out.data_ptr(), out_stride, d_row_status.data_ptr()), "ghf_decode_planes_gather")
+        return d_out, d_row_status
 
     # ---- seekable streams: the seek table (the persistent form of the side-car) ----------------
     def seek_pack(self, index, d_stream=None, stream_bytes=0, d_table=None, n=None):

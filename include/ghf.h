@@ -1044,6 +1044,52 @@ int ghf_decode_planes_forms_range(ghf_ctx* ctx, const uint8_t* const* h_stream_p
                                   unsigned raw_planes, unsigned sparse_planes, size_t n_elems, uint32_t elem_bytes, uint64_t first,
                                   uint64_t count, uint8_t* d_out, size_t cap);
 
+/* ---- byte planes: many rows in one call ------------------------------------------
+ * The range calls above serve one range per call and every range is a host argument; a lookup of rows of an embedding
+ * table that stays compressed in device memory has its row indices on the device and wants them all in one launch. */
+#define GHF_GATHER_MAX_ROW_ELEMS 32768u /* the longest row of ghf_decode_planes_gather */
+
+/* No reference counterpart: Decompressor::decompress(), include/compressor.h:87-92, for MANY parts of a typed tensor at
+ * once.  ROW r is elements [d_index[r] *
+ * index_stride, + row_elems) of the tensor, and its row_elems * elem_bytes interleaved bytes go to d_out + r * out_stride:
+ * index_stride = row_elems is a lookup by row id, index_stride = 1 takes arbitrary element offsets; rows may repeat,
+ * overlap in the source and come in any order.  The row indices are DEVICE memory, and the call queues ONE launch whatever
+ * n_rows is (one workgroup per row); it never waits for the device.
+ * The tensor is stored as ghf_compress_planes_forms stores it with sparse_planes == 0: plane p is a standalone .crs2 image
+ * with a seek table from ghf_seek_pack, or raw (bit p of raw_planes).  The arrays are the first elem_bytes entries of the
+ * forms calls' arrays; seek tables are the only source of run starts (a caller with live side-cars packs them once).
+ * READ: the row indices; of a raw plane the rows' bytes where they lie; of a dense plane its code, the records of the
+ * blocks a row covers and the stream bytes of the runs of 512 symbols it touches -- at most 511 symbols are decoded in
+ * front of a row and 511 behind it.  WRITTEN: d_row_status[0 .. n_rows), and bytes [r * out_stride, r * out_stride +
+ * row_elems * elem_bytes) of d_out for every row whose status is GHF_OK.  Nothing else: out_stride need not be a multiple
+ * of 16, and padding between rows keeps what it held.
+ * CALL-LEVEL REFUSALS come before anything touches HIP, queue nothing and leave the context's status alone, in this
+ * order: a null context; elem_bytes not 2, 4 or 8; a raw_planes bit at or above elem_bytes; row_elems == 0 or above
+ * GHF_GATHER_MAX_ROW_ELEMS; out_stride < row_elems * elem_bytes; a null pointer, a stream, table, d_codes or d_out that is
+ * not 16-byte aligned, a d_index that is not 8-byte or a d_row_status that is not 4-byte aligned (d_codes, h_infos,
+ * h_table_ptrs and h_table_bytes may be NULL when every plane is raw); a raw stream whose size is not n_elems; a dense
+ * plane whose table says n_symbols != n_elems: GHF_E_INVAL; a dense plane's table whose table_bytes is not what its header
+ * implies: GHF_E_FORMAT.  Then n_rows == 0: GHF_OK, nothing queued.
+ * FAILURES ARE PER ROW: they land in d_row_status[r] and never latch the context.  A failed row stores NOTHING -- every
+ * verdict of a row is reached before its first store -- and the other rows are unaffected.
+ *   GHF_OK
+ *   GHF_E_FORMAT  on every row: the code of a dense plane is not a complete prefix code of lengths <= 32
+ *   GHF_E_INVAL   d_index[r] * index_stride overflows 64 bits, or the row passes n_elems
+ *   GHF_E_CORRUPT for any dense plane: a covered block's start_bit + the sum of its run_bits lies beyond bit 8 *
+ *                 stream_bytes, or is not the next block's start_bit; a covered run does not land exactly on its recorded
+ *                 end, meets an end mark, or meets bits that start no code
+ * The tables and streams come from disk and nothing in them is trusted: no byte outside stream[0 .. stream_bytes) or
+ * outside a table is read, whatever they hold.  Start bits are 64-bit: planes of more than 2^32 stream bits are served. */
+int ghf_decode_planes_gather(ghf_ctx* ctx, const uint8_t* const* h_stream_ptrs /* HOST [elem_bytes] device pointers 16-byte aligned */,
+                             const size_t* h_stream_bytes /* [elem_bytes] */,
+                             const ghf_code* d_codes /* DEVICE [elem_bytes] -- a raw plane's entry is never read */,
+                             const ghf_seek_info* h_infos /* [elem_bytes] -- a raw plane's entry is not read */,
+                             const uint8_t* const* h_table_ptrs /* [elem_bytes] seek-table images in device memory */,
+                             const size_t* h_table_bytes /* [elem_bytes] */, unsigned raw_planes, size_t n_elems, uint32_t elem_bytes,
+                             const uint64_t* d_index /* DEVICE [n_rows] */, uint64_t index_stride, uint32_t row_elems, uint32_t n_rows,
+                             uint8_t* d_out, size_t out_stride /* bytes from one output row to the next */,
+                             int32_t* d_row_status /* DEVICE [n_rows] */);
+
 /* ------------------------------------------------------------------------------------------------
  * one stream sharded over the GPUs of a node, one process (or thread) and one ghf_ctx per GPU,
  * RCCL over xGMI underneath.  The reference has no counterpart (it is single-threaded, single-stream:
