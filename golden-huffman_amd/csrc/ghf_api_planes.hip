@@ -1,5 +1,5 @@
 // golden-huffman_amd/csrc/ghf_api_planes.hip -- the byte-plane family of the C ABI of include/ghf.h (DESIGN.md sections 14,
-// 17 - 21, 23, 25): split / merge / compress, the staged calls, the element range, the calls against a base, sparse planes with
+// 17 - 21, 23, 25, 26): split / merge / compress, the staged calls, the element range, the calls against a base, sparse planes with
 // their rank tables, planes in three forms, and many rows in one call.  Host-side only, like ghf_api.hip: argument checks, workspace, launches.
 // Every step the drivers share -- the slot rule, the compress-side checks, the side-cars, packing a dense or a sparse plane,
 // decoding a stored stream, the parts of a range -- is written once, in front of the drivers that call it.
@@ -1144,19 +1144,21 @@ int ghf_decode_planes_forms_range(ghf_ctx* c, const uint8_t* const* h_stream_ptr
 // ------------------------------------------------------------------------------------------ many rows in one call
 // (no reference counterpart).  One launch whatever n_rows is; the rows' failures are their own
 // (d_row_status) and nothing here or on the device touches the context's status word.
-int ghf_decode_planes_gather(ghf_ctx* c, const uint8_t* const* h_stream_ptrs, const size_t* h_stream_bytes, const ghf_code* d_codes,
-                             const ghf_seek_info* h_infos, const uint8_t* const* h_table_ptrs, const size_t* h_table_bytes,
-                             unsigned raw_planes, size_t n_elems, uint32_t elem_bytes, const uint64_t* d_index, uint64_t index_stride,
-                             uint32_t row_elems, uint32_t n_rows, uint8_t* d_out, size_t out_stride, int32_t* d_row_status) {
-  if (!c) return GHF_E_INVAL;
-  const char* const who = "ghf_decode_planes_gather";
+// what the two gather calls refuse alike, in this order (include/ghf.h), over the planes' own slots j < elem_bytes: `sparse` names
+// the planes whose slot holds a mask -- a stream with a code and a table like a dense plane's, but of another symbol count,
+// which the forms call holds against the mask's size behind its own masks -- and sets the row cap
+static int gather_args(ghf_ctx* c, const char* who, const uint8_t* const* h_stream_ptrs, const size_t* h_stream_bytes, const ghf_code* d_codes,
+                       const ghf_seek_info* h_infos, const uint8_t* const* h_table_ptrs, const size_t* h_table_bytes, unsigned raw_planes,
+                       unsigned sparse, size_t n_elems, uint32_t elem_bytes, const uint64_t* d_index, uint32_t row_elems, const uint8_t* d_out,
+                       size_t out_stride, const int32_t* d_row_status) {
   const std::string f = std::string(who) + ": ";
   const uint32_t E = elem_bytes;
   if (!elem_bytes_ok(E)) return fail(c, GHF_E_INVAL, (f + "elem_bytes must be 2, 4 or 8").c_str());
   const PlaneForms forms = {E, raw_planes, 0, n_elems, nullptr};
   if ((raw_planes >> E) != 0) return fail(c, GHF_E_INVAL, (f + "raw_planes has bits below elem_bytes only").c_str());
-  if (row_elems == 0 || row_elems > GHF_GATHER_MAX_ROW_ELEMS)
-    return fail(c, GHF_E_INVAL, (f + "row_elems must be 1 .. GHF_GATHER_MAX_ROW_ELEMS").c_str());
+  if (row_elems == 0 || row_elems > (sparse ? GHF_GATHER_SPARSE_MAX_ROW_ELEMS : GHF_GATHER_MAX_ROW_ELEMS))
+    return fail(c, GHF_E_INVAL, sparse ? (f + "row_elems must be 1 .. GHF_GATHER_SPARSE_MAX_ROW_ELEMS with a sparse plane").c_str()
+                                       : (f + "row_elems must be 1 .. GHF_GATHER_MAX_ROW_ELEMS").c_str());
   if (out_stride < (size_t)row_elems * E) return fail(c, GHF_E_INVAL, (f + "out_stride below row_elems * elem_bytes").c_str());
   // the codes and tables of raw planes are not looked at: a tensor of nothing but raw planes needs none
   const bool all_raw = forms.all_raw();
@@ -1172,11 +1174,25 @@ int ghf_decode_planes_gather(ghf_ctx* c, const uint8_t* const* h_stream_ptrs, co
     if (forms.is_raw(p) && h_stream_bytes[p] != n_elems) return fail(c, GHF_E_INVAL, (f + "a raw plane does not have n_elems bytes").c_str());
   for (uint32_t p = 0; p < E; ++p) {
     if (forms.is_raw(p)) continue;
-    if (h_infos[p].n_symbols != n_elems) return fail(c, GHF_E_INVAL, (f + "a dense stream does not have n_elems symbols").c_str());
+    if (!(sparse >> p & 1u) && h_infos[p].n_symbols != n_elems)
+      return fail(c, GHF_E_INVAL, (f + "a dense stream does not have n_elems symbols").c_str());
     const int rc = seek_table_ok(c, who, h_infos + p, h_table_ptrs[p], h_table_bytes[p]);
     if (rc) return rc;
   }
+  return GHF_OK;
+}
+
+int ghf_decode_planes_gather(ghf_ctx* c, const uint8_t* const* h_stream_ptrs, const size_t* h_stream_bytes, const ghf_code* d_codes,
+                             const ghf_seek_info* h_infos, const uint8_t* const* h_table_ptrs, const size_t* h_table_bytes,
+                             unsigned raw_planes, size_t n_elems, uint32_t elem_bytes, const uint64_t* d_index, uint64_t index_stride,
+                             uint32_t row_elems, uint32_t n_rows, uint8_t* d_out, size_t out_stride, int32_t* d_row_status) {
+  if (!c) return GHF_E_INVAL;
+  const uint32_t E = elem_bytes;
+  const int rc = gather_args(c, "ghf_decode_planes_gather", h_stream_ptrs, h_stream_bytes, d_codes, h_infos, h_table_ptrs, h_table_bytes,
+                             raw_planes, 0, n_elems, E, d_index, row_elems, d_out, out_stride, d_row_status);
+  if (rc) return rc;
   if (n_rows == 0) return GHF_OK;
+  const PlaneForms forms = {E, raw_planes, 0, n_elems, nullptr};
   PlanesGatherParams g = {};
   for (uint32_t p = 0; p < E; ++p) {
     g.streams[p] = h_stream_ptrs[p];
@@ -1194,6 +1210,75 @@ int ghf_decode_planes_gather(ghf_ctx* c, const uint8_t* const* h_stream_ptrs, co
   g.out_stride = out_stride;
   g.row_status = d_row_status;
   return queued(c, [&] { launch_decode_planes_gather(g, E, raw_planes, c->stream); });
+}
+
+// (no reference counterpart)  The same rows of a tensor in any mix of the three forms, against a base
+// where there is one: the slots of the slot rule, the rank tables as images in device memory.
+int ghf_decode_planes_gather_forms(ghf_ctx* c, const uint8_t* const* h_stream_ptrs, const size_t* h_stream_bytes, const ghf_code* d_codes,
+                                   const ghf_seek_info* h_infos, const uint8_t* const* h_table_ptrs, const size_t* h_table_bytes,
+                                   const ghf_sparse_rank_info* h_rank_infos, const uint8_t* const* h_rank_ptrs, const size_t* h_rank_bytes,
+                                   const uint8_t* d_base, unsigned raw_planes, unsigned sparse_planes, size_t n_elems, uint32_t elem_bytes,
+                                   const uint64_t* d_index, uint64_t index_stride, uint32_t row_elems, uint32_t n_rows, uint8_t* d_out,
+                                   size_t out_stride, int32_t* d_row_status) {
+  if (!c) return GHF_E_INVAL;
+  const char* const who = "ghf_decode_planes_gather_forms";
+  const std::string f = std::string(who) + ": ";
+  const uint32_t E = elem_bytes;
+  int rc = gather_args(c, who, h_stream_ptrs, h_stream_bytes, d_codes, h_infos, h_table_ptrs, h_table_bytes, raw_planes,
+                       elem_bytes_ok(E) ? sparse_planes & ~raw_planes & ((1u << E) - 1u) : sparse_planes, n_elems, E, d_index, row_elems, d_out,
+                       out_stride, d_row_status);
+  if (rc) return rc;
+  size_t n_vals[GHF_PLANES_MAX] = {};  // of the sparse planes: what their rank infos count, once those are checked
+  const PlaneForms forms = {E, raw_planes, sparse_planes, n_elems, n_vals};
+  if (!forms.sparse_planes_ok(false) || !forms.forms_ok(false))
+    return fail(c, GHF_E_INVAL, (f + "the masks have bits below elem_bytes only and name no plane twice").c_str());
+  if (sparse_planes && (!h_rank_infos || !h_rank_ptrs || !h_rank_bytes)) return fail(c, GHF_E_INVAL, (f + "sparse planes need their rank tables").c_str());
+  for (uint32_t p = 0; p < E; ++p)
+    if (forms.is_sparse(p) && (!h_rank_ptrs[p] || (reinterpret_cast<uintptr_t>(h_rank_ptrs[p]) & 7u) || h_rank_bytes[p] != ghf_sparse_rank_bytes(n_elems)))
+      return fail(c, GHF_E_INVAL, (f + "a rank table is null, not 8-byte aligned or not ghf_sparse_rank_bytes(n_elems) long").c_str());
+  for (uint32_t p = 0; p < E; ++p) {
+    if (!forms.is_sparse(p)) continue;
+    if (h_rank_infos[p].n != n_elems) return fail(c, GHF_E_INVAL, (f + "a rank table is not one of n_elems elements").c_str());
+    if (h_rank_infos[p].version != kSparseRankVersion || h_rank_infos[p].n_blocks != rank_blocks_for(n_elems) || h_rank_infos[p].n_vals > n_elems)
+      return fail(c, GHF_E_FORMAT, (f + "a rank info is not what ghf_sparse_rank_parse fills in").c_str());
+    n_vals[p] = (size_t)h_rank_infos[p].n_vals;
+  }
+  for (uint32_t p = 0; p < E; ++p)
+    if (forms.is_sparse(p) && h_infos[p].n_symbols != forms.symbols(p))
+      return fail(c, GHF_E_INVAL, (f + "a mask stream does not have ghf_sparse_mask_bytes(n_elems) symbols").c_str());
+  for (uint32_t p = 0; p < E; ++p) {
+    const uint32_t j = E + p;
+    if (!forms.is_sparse(p) || !forms.stored(j)) continue;  // the values slot of any other plane is ignored
+    if (!h_stream_ptrs[j] || !aligned16(h_stream_ptrs[j]) || !h_table_ptrs[j] || !aligned16(h_table_ptrs[j]))
+      return fail(c, GHF_E_INVAL, (f + "a stream or table pointer is null or not 16-byte aligned").c_str());
+    if (h_infos[j].n_symbols != forms.symbols(j))
+      return fail(c, GHF_E_INVAL, (f + "a values stream does not have the symbols its rank table counts").c_str());
+    if ((rc = seek_table_ok(c, who, h_infos + j, h_table_ptrs[j], h_table_bytes[j]))) return rc;
+  }
+  if (n_rows == 0) return GHF_OK;
+  PlanesGatherFormsParams g = {};
+  for (uint32_t j = 0; j < 2 * E; ++j) {
+    if (!forms.stored(j)) continue;
+    g.streams[j] = h_stream_ptrs[j];
+    g.stream_bytes[j] = h_stream_bytes[j];
+    g.records[j] = forms.coded(j) ? h_table_ptrs[j] + kSeekHeaderBytes : nullptr;
+  }
+  for (uint32_t p = 0; p < E; ++p) {
+    if (!forms.is_sparse(p)) continue;
+    g.cum[p] = reinterpret_cast<const uint64_t*>(h_rank_ptrs[p] + kSparseRankHeaderBytes);
+    g.n_vals[p] = n_vals[p];
+  }
+  g.codes = d_codes;
+  g.base = d_base;
+  g.n_elems = n_elems;
+  g.index = d_index;
+  g.index_stride = index_stride;
+  g.row_elems = row_elems;
+  g.n_rows = n_rows;
+  g.out = d_out;
+  g.out_stride = out_stride;
+  g.row_status = d_row_status;
+  return queued(c, [&] { launch_decode_planes_gather_forms(g, E, raw_planes, sparse_planes, c->stream); });
 }
 
 }  // extern "C"

@@ -570,5 +570,31 @@ struct PlanesGatherParams {
 // one launch whatever n_rows is (none when it is 0); raw_planes has bits below elem_bytes only
 void launch_decode_planes_gather(const PlanesGatherParams& p, uint32_t elem_bytes, uint32_t raw_planes, hipStream_t s);
 
+// ghf_planes_gather_forms.hip: the same rows of a tensor stored in any mix of the three forms, against a
+// base tensor where there is one.  The arrays have an entry per SLOT (the slot rule of section 20): j < elem_bytes is plane j's
+// stream -- the plane itself, its .crs2 image, or the image of its mask -- and elem_bytes + p the image of sparse plane p's
+// values, which is not read when n_vals[p] == 0.  A stored stream that has a code has its records; a raw plane's are not read.
+struct PlanesGatherFormsParams {
+  const uint8_t* streams[2 * GHF_PLANES_MAX];  // 16-byte aligned
+  uint64_t stream_bytes[2 * GHF_PLANES_MAX];
+  const uint8_t* records[2 * GHF_PLANES_MAX];  // the seek table behind its header: blocks_for(the slot's symbols) records
+  const uint64_t* cum[GHF_PLANES_MAX];         // sparse plane p: cum[0 .. rank blocks] of its rank table image; untrusted
+  uint64_t n_vals[GHF_PLANES_MAX];             // sparse plane p: what its rank info counts (<= n_elems), the symbols of slot E + p
+  const ghf_code* codes;                       // [2 * elem_bytes]
+  const uint8_t* base;                         // the whole base tensor, or null
+  uint64_t n_elems;
+  const uint64_t* index;                       // [n_rows]
+  uint64_t index_stride;
+  uint32_t row_elems, n_rows;                  // 1 <= row_elems <= the cap of the launch's forms
+  uint32_t stage_bytes;                        // the launch's dynamic LDS ...
+  uint32_t once;                               // ... which holds every plane of a row at once, or one plane: by the launcher
+  uint8_t* out;
+  uint64_t out_stride;                         // >= row_elems * elem_bytes
+  int32_t* row_status;                         // [n_rows]
+};
+// one launch whatever n_rows is (none when it is 0); the masks have bits below elem_bytes only and share none
+void launch_decode_planes_gather_forms(const PlanesGatherFormsParams& p, uint32_t elem_bytes, uint32_t raw_planes, uint32_t sparse_planes,
+                                       hipStream_t s);
+
 }  // namespace ghf
 #endif

@@ -37,6 +37,7 @@ SPARSE_SCAN = SPARSE_GROUPS
 SPARSE_RANK_ELEMS = 32768  # GHF_SPARSE_RANK_ELEMS: the elements of a rank block: 4096 mask bytes, one seek block
 RAW_AUTO = 0x80000000  # GHF_RAW_AUTO (ghf_compress_planes_forms): a plane whose image would be at least n_elems bytes is stored raw
 GATHER_MAX_ROW_ELEMS = 32768  # GHF_GATHER_MAX_ROW_ELEMS: the longest row of ghf_decode_planes_gather
+GATHER_SPARSE_MAX_ROW_ELEMS = 8192  # GHF_GATHER_SPARSE_MAX_ROW_ELEMS: ... of ghf_decode_planes_gather_forms with a sparse plane
 SPARSE_AUTO = 0x80000000  # GHF_SPARSE_AUTO (ghf_compress_planes_sparse): planes with at least 3/4 zero bytes are stored sparse
 EMPTY_OK = 2  # opt-in: n == 0 -> header of the one-symbol code + 0x7F (builder's definition, parity unpinned)
 
@@ -180,7 +181,7 @@ EXPORTS = [
     "ghf_compress_planes_sparse_ranked", "ghf_compress_planes_sparse_ranked_delta", "ghf_decode_planes_sparse_range",
     "ghf_decode_planes_sparse_range_delta",
     "ghf_planes_split_to", "ghf_planes_merge_from", "ghf_planes_merge_range_from", "ghf_compress_planes_forms",
-    "ghf_decode_planes_forms", "ghf_decode_planes_forms_range", "ghf_decode_planes_gather",
+    "ghf_decode_planes_forms", "ghf_decode_planes_forms_range", "ghf_decode_planes_gather", "ghf_decode_planes_gather_forms",
     "ghf_batch_planes_raw_auto", "ghf_compress_batch_planes_forms", "ghf_decode_batch_planes_forms",
     "ghf_decode_bodies_batch_planes_forms", "ghf_decode_bodies_batch_planes_forms_seek",
 ]
@@ -364,6 +365,9 @@ def lib():
     L.ghf_decode_planes_forms_range.argtypes = sparse_range_front + [vp, C.c_uint, C.c_uint, sz, u32, u64, u64, vp, sz]
     L.ghf_decode_planes_gather.argtypes = [vp, C.POINTER(vp), C.POINTER(sz), vp, C.POINTER(SeekInfo), C.POINTER(vp), C.POINTER(sz), C.c_uint,
                                            sz, u32, vp, u64, u32, u32, vp, sz, vp]
+    L.ghf_decode_planes_gather_forms.argtypes = [vp, C.POINTER(vp), C.POINTER(sz), vp, C.POINTER(SeekInfo), C.POINTER(vp), C.POINTER(sz),
+                                                 C.POINTER(SparseRankInfo), C.POINTER(vp), C.POINTER(sz), vp, C.c_uint, C.c_uint, sz, u32,
+                                                 vp, u64, u32, u32, vp, sz, vp]
     _lib = L
     return L
 
@@ -1797,6 +1801,48 @@ class Context:
         self._chk(self.L.ghf_decode_planes_gather(self.h, ptrs, sizes, None if d_codes is None else d_codes.data_ptr(), h_infos, t_ptrs,
                                                   t_bytes, raw_planes, n_elems, E, d_index.data_ptr(), index_stride, row_elems, n_rows,
                                                   d_out.data_ptr(), out_stride, d_row_status.data_ptr()), "ghf_decode_planes_gather")
+        return d_out, d_row_status
+
+    def decode_planes_gather_forms(self, streams, stream_bytes, d_codes, raw_planes, sparse_planes, ranks, n_elems, elem_bytes, d_index,
+                                   row_elems, index_stride=None, infos=None, d_tables=None, table_bytes=None, d_base=None, n_rows=None,
+                                   d_out=None, out_stride=None, d_row_status=None):
+        """decode_planes_gather for a tensor stored by compress_planes_forms in any mix of the three forms, against the WHOLE base
+        tensor d_base where there is one: ONE launch whatever the number of rows.  streams / stream_bytes / infos / d_tables
+        have 2 * elem_bytes entries, indexed like decode_planes_forms_range's (None for a slot that is not stored).  ranks: per
+        plane None, or (SparseRankInfo, the rank table as a CUDA uint8 tensor of sparse_rank_bytes(n_elems)) for a sparse
+        plane -- the image lies in DEVICE memory here.  The row cap is GATHER_SPARSE_MAX_ROW_ELEMS with a sparse plane.
+        Never synchronises.  -> (d_out, d_row_status)"""
+        t = self.torch
+        E = elem_bytes
+        slots = 2 * E
+        n_rows = d_index.numel() if n_rows is None else n_rows
+        index_stride = row_elems if index_stride is None else index_stride
+        out_stride = row_elems * E if out_stride is None else out_stride
+        ptr = lambda x: None if x is None else x if isinstance(x, int) else x.data_ptr()
+        ptrs = (C.c_void_p * slots)(*[ptr(x) for x in streams])
+        sizes = (C.c_size_t * slots)(*[int(v) for v in stream_bytes])
+        h_infos = t_ptrs = t_bytes = None
+        if infos is not None:
+            h_infos = (SeekInfo * slots)(*[SeekInfo() if i is None else i for i in infos])
+            t_ptrs = (C.c_void_p * slots)(*[ptr(x) for x in d_tables])
+            if table_bytes is None:
+                table_bytes = [0 if i is None else seek_bytes(i.n_symbols) for i in infos]
+            t_bytes = (C.c_size_t * slots)(*[int(v) for v in table_bytes])
+        r_infos = r_ptrs = r_bytes = None
+        if ranks is not None:
+            r_infos, r_ptrs, r_bytes = (SparseRankInfo * E)(), (C.c_void_p * E)(), (C.c_size_t * E)()
+            for p, r in enumerate(ranks):
+                if r is not None:
+                    r_infos[p], r_ptrs[p] = r[0], ptr(r[1])
+                    r_bytes[p] = 0 if r[1] is None else r[2] if len(r) > 2 else r[1].numel()
+        if d_out is None:
+            d_out = self.empty_u8(max(n_rows, 1) * out_stride)
+        if d_row_status is None:
+            d_row_status = t.zeros(max(n_rows, 1), dtype=t.int32, device=self.device)
+        self._chk(self.L.ghf_decode_planes_gather_forms(self.h, ptrs, sizes, None if d_codes is None else d_codes.data_ptr(), h_infos, t_ptrs,
+                                                        t_bytes, r_infos, r_ptrs, r_bytes, self._base_ptr(d_base), raw_planes, sparse_planes,
+                                                        n_elems, E, d_index.data_ptr(), index_stride, row_elems, n_rows, d_out.data_ptr(),
+                                                        out_stride, d_row_status.data_ptr()), "ghf_decode_planes_gather_forms")
         return d_out, d_row_status
 
     # ---- seekable streams: the seek table (the persistent form of the side-car) ----------------

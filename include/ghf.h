@@ -1090,6 +1090,73 @@ int ghf_decode_planes_gather(ghf_ctx* ctx, const uint8_t* const* h_stream_ptrs /
                              uint8_t* d_out, size_t out_stride /* bytes from one output row to the next */,
                              int32_t* d_row_status /* DEVICE [n_rows] */);
 
+/* ---- byte planes: many rows of a tensor stored sparse or against a base -----------
+ * ghf_decode_planes_gather serves a tensor of dense and raw planes that was compressed by itself; the forms that compress
+ * best -- against a base tensor, and sparse planes on top of that -- are served here, with the same row rule. */
+#define GHF_GATHER_SPARSE_MAX_ROW_ELEMS 8192u /* the longest row of ghf_decode_planes_gather_forms when a plane is sparse */
+
+/* No reference counterpart: Decompressor::decompress(), include/compressor.h:87-92, for MANY parts of a typed tensor
+ * stored in any mix of the three forms, against a base tensor where there is one.  The ROW RULE, the output rule and the
+ * per-row statuses are those of ghf_decode_planes_gather: row r is elements [d_index[r] * index_stride, + row_elems), its
+ * bytes go to d_out + r * out_stride at any alignment, rows may repeat, overlap and come in any order; ONE launch whatever
+ * n_rows is, never a wait for the device, and nothing latches the context.
+ * SLOTS are indexed as ghf_compress_planes_forms lays them out: slot j < elem_bytes holds plane j when it is dense or raw,
+ * or its mask when it is sparse; slot elem_bytes + p the values of sparse plane p, ignored (pointers, sizes, code, info
+ * and table) when h_rank_infos[p].n_vals == 0, as are the upper slots of every other plane.  Every stored stream that has
+ * a code comes with its seek table from ghf_seek_pack (device memory, 16-byte aligned).  Every sparse plane comes with
+ * its rank table (ghf_sparse_rank_pack, or d_ranks of the compress call) AS AN IMAGE IN DEVICE MEMORY: h_rank_ptrs is a
+ * HOST array of DEVICE pointers, 8-byte aligned, h_rank_bytes[p] == ghf_sparse_rank_bytes of n_elems, and h_rank_infos[p]
+ * is what ghf_sparse_rank_parse gave for it -- the range calls take the table on the host; this call reads cum[] per row
+ * on the device.  With sparse_planes == 0 the three rank arrays may be NULL.
+ * BASE: with d_base != NULL row r is the planes' bytes XOR d_base[first * elem_bytes .. + row_elems * elem_bytes), first
+ * = d_index[r] * index_stride: d_base is the WHOLE base tensor, n_elems * elem_bytes bytes.  It is read byte by byte: no
+ * alignment is required of it and none is refused.  d_base and d_out must not overlap: a gather is not in place.
+ * ROW CAP: GHF_GATHER_MAX_ROW_ELEMS when sparse_planes == 0, GHF_GATHER_SPARSE_MAX_ROW_ELEMS otherwise: a row then
+ * touches at most two rank blocks, 11 runs of a mask stream and 17 of a values stream.
+ * READ: what ghf_decode_planes_gather reads of raw and dense planes; of a sparse plane two or three entries of cum[], the
+ * records and stream bytes of the mask's runs of 512 bytes from the start of the row's rank block to the row's end, and of
+ * the values' runs that hold the row's values; of the base the rows' bytes.  WRITTEN: d_row_status[0 .. n_rows), and
+ * bytes [r * out_stride, r * out_stride + row_elems * elem_bytes) of d_out for every row whose status is GHF_OK.
+ * CALL-LEVEL REFUSALS come before anything touches HIP, queue nothing and leave the context's status alone, in this
+ * order: those of ghf_decode_planes_gather in its order (the row cap as above; the slots looked at are those of dense,
+ * raw and sparse planes' own streams, a "dense stream" check applying to dense planes only); then a plane named in both
+ * masks, GHF_RAW_AUTO or GHF_SPARSE_AUTO, or a sparse_planes bit at or above elem_bytes; then, with a sparse plane, a
+ * null rank array, a null or misaligned rank pointer or an h_rank_bytes that is not ghf_sparse_rank_bytes of n_elems; then
+ * a rank info whose n is not n_elems; then a mask table whose n_symbols is not ghf_sparse_mask_bytes of n_elems; then, for
+ * a sparse plane with values, a null or misaligned values stream or table, or a values table whose n_symbols is not the
+ * rank info's n_vals: all GHF_E_INVAL; a rank info whose other fields are not what ghf_sparse_rank_parse fills in, or a
+ * seek table whose size contradicts its header: GHF_E_FORMAT.  Then n_rows == 0: GHF_OK, nothing queued.
+ * FAILURES ARE PER ROW, as in ghf_decode_planes_gather; a failed row stores NOTHING: every verdict of a row, of all its
+ * planes, is reached before its first store.
+ *   GHF_OK
+ *   GHF_E_FORMAT  on every row: the code of a stored stream is not a complete prefix code of lengths <= 32
+ *   GHF_E_INVAL   d_index[r] * index_stride overflows 64 bits, or the row passes n_elems
+ *   GHF_E_CORRUPT a dense plane, a mask stream or a values stream fails a block or run check of ghf_decode_planes_gather;
+ *                 or for a sparse plane, with b0 = first / 32768: cum[b0], cum[b0 + 1] (and cum[b0 + 2] where the row
+ *                 crosses into the next rank block) are not ordered, exceed n_vals, or step by more than the elements
+ *                 of their block; the decoded mask holds a rank block to its end (or the tensor's) and the block's set
+ *                 bits do not number the difference of its two entries; the row touches the last mask byte and a pad
+ *                 bit is set; cum[b0] + the set bits in front of the row + the row's own exceed n_vals
+ * As in DESIGN.md section 21 the mask is held against DIFFERENCES of rank entries, and only where a whole block is
+ * decoded: a table whose entries were all shifted, or a wrong entry in front of a row that ends more than 4096 elements
+ * before its block does, is not noticed and moves the row's values.  The rank table is as trusted as the streams' order
+ * of bytes; what IS guaranteed whatever the tables and streams hold: no byte outside a stream, a seek table or a rank
+ * table is read, and no byte outside the rows is written.
+ * IDENTITY: with sparse_planes == 0 and d_base == NULL the output and the statuses are byte for byte those of
+ * ghf_decode_planes_gather on the first elem_bytes entries of the arrays. */
+int ghf_decode_planes_gather_forms(ghf_ctx* ctx, const uint8_t* const* h_stream_ptrs /* HOST [2 * elem_bytes] device pointers */,
+                                   const size_t* h_stream_bytes /* [2 * elem_bytes] */, const ghf_code* d_codes /* DEVICE [2 * elem_bytes] */,
+                                   const ghf_seek_info* h_infos /* [2 * elem_bytes] */,
+                                   const uint8_t* const* h_table_ptrs /* [2 * elem_bytes] seek tables, device */,
+                                   const size_t* h_table_bytes /* [2 * elem_bytes] */,
+                                   const struct ghf_sparse_rank_info* h_rank_infos /* [elem_bytes] */,
+                                   const uint8_t* const* h_rank_ptrs /* HOST [elem_bytes] DEVICE images */,
+                                   const size_t* h_rank_bytes /* [elem_bytes] */,
+                                   const uint8_t* d_base /* optional: the whole base tensor, n_elems * elem_bytes bytes */,
+                                   unsigned raw_planes, unsigned sparse_planes, size_t n_elems, uint32_t elem_bytes,
+                                   const uint64_t* d_index /* DEVICE [n_rows] */, uint64_t index_stride, uint32_t row_elems, uint32_t n_rows,
+                                   uint8_t* d_out, size_t out_stride, int32_t* d_row_status /* DEVICE [n_rows] */);
+
 /* ------------------------------------------------------------------------------------------------
  * one stream sharded over the GPUs of a node, one process (or thread) and one ghf_ctx per GPU,
  * RCCL over xGMI underneath.  The reference has no counterpart (it is single-threaded, single-stream:
