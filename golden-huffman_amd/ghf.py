@@ -149,42 +149,155 @@ class Tree(C.Structure):
         return out
 
 
-EXPORTS = [
-    "ghf_ctx_create", "ghf_ctx_destroy", "ghf_ctx_set_stream", "ghf_sync", "ghf_status", "ghf_clear_status",
-    "ghf_last_error", "ghf_status_string", "ghf_version", "ghf_device_alloc", "ghf_device_free", "ghf_host_alloc",
-    "ghf_host_free", "ghf_copy_h2d", "ghf_copy_d2h", "ghf_memset_d", "ghf_histogram", "ghf_build_code",
-    "ghf_write_header", "ghf_header_bytes", "ghf_encode_plan", "ghf_encode_emit", "ghf_compress", "ghf_compress_bound",
-    "ghf_chunk_symbols", "ghf_index_alloc", "ghf_index_free", "ghf_parse_header", "ghf_decode", "ghf_decoded_size",
-    "ghf_shard_start_bit", "ghf_crs_build_code", "ghf_crs_compress", "ghf_crs_compress_bound", "ghf_crs_parse_header",
-    "ghf_crs_decode", "ghf_crs_decoded_size", "ghf_build_code_ex", "ghf_compress_ex", "ghf_sync_piece", "ghf_decode_prepare",
-    "ghf_comm_unique_id", "ghf_comm_init_rank", "ghf_comm_destroy", "ghf_comm_world", "ghf_rccl_version",
-    "ghf_comm_allreduce_hist", "ghf_comm_allgather_total", "ghf_encode_sharded", "ghf_shard_bound",
-    "ghf_event_create", "ghf_event_destroy", "ghf_event_record", "ghf_event_wait", "ghf_event_sync", "ghf_histogram_add",
-    "ghf_crs_sync_piece", "ghf_copy_d2d", "ghf_shard_bytes",
-    "ghf_seek_bytes", "ghf_seek_parse", "ghf_seek_pack", "ghf_seek_expand", "ghf_decode_range",
-    "ghf_compress_batch_bound", "ghf_batch_index_alloc", "ghf_batch_index_free", "ghf_batch_index_item",
-    "ghf_compress_batch", "ghf_decode_batch", "ghf_decode_images_batch", "ghf_decode_images_batch_stats",
-    "ghf_histogram_batch", "ghf_compress_batch_shared_bound", "ghf_compress_batch_shared", "ghf_decode_batch_shared",
-    "ghf_decode_bodies_batch_shared",
-    "ghf_planes_slot_bytes", "ghf_planes_split", "ghf_planes_merge", "ghf_compress_planes", "ghf_decode_planes",
-    "ghf_histogram_batch_planes", "ghf_build_codes", "ghf_compress_batch_planes_shared_bound",
-    "ghf_compress_batch_planes_shared", "ghf_decode_batch_planes_shared", "ghf_decode_bodies_batch_planes_shared",
-    "ghf_batch_seek_bytes", "ghf_batch_seek_bound", "ghf_batch_seek_pack", "ghf_decode_bodies_batch_shared_seek",
-    "ghf_decode_bodies_batch_planes_shared_seek",
-    "ghf_planes_merge_range", "ghf_decode_planes_range",
-    "ghf_histogram_planes", "ghf_planes_image_bytes", "ghf_compress_planes_coded",
-    "ghf_histogram_planes_delta", "ghf_planes_split_delta", "ghf_planes_merge_delta", "ghf_planes_merge_range_delta",
-    "ghf_compress_planes_delta", "ghf_decode_planes_delta", "ghf_decode_planes_range_delta",
-    "ghf_sparse_mask_bytes", "ghf_sparse_split", "ghf_sparse_merge", "ghf_compress_planes_sparse",
-    "ghf_compress_planes_sparse_delta", "ghf_decode_planes_sparse", "ghf_decode_planes_sparse_delta",
-    "ghf_sparse_rank_bytes", "ghf_sparse_rank_pack", "ghf_sparse_rank_parse", "ghf_sparse_merge_at",
-    "ghf_compress_planes_sparse_ranked", "ghf_compress_planes_sparse_ranked_delta", "ghf_decode_planes_sparse_range",
-    "ghf_decode_planes_sparse_range_delta",
-    "ghf_planes_split_to", "ghf_planes_merge_from", "ghf_planes_merge_range_from", "ghf_compress_planes_forms",
-    "ghf_decode_planes_forms", "ghf_decode_planes_forms_range", "ghf_decode_planes_gather", "ghf_decode_planes_gather_forms",
-    "ghf_batch_planes_raw_auto", "ghf_compress_batch_planes_forms", "ghf_decode_batch_planes_forms",
-    "ghf_decode_bodies_batch_planes_forms", "ghf_decode_bodies_batch_planes_forms_seek",
-]
+# ---- the prototypes of the C ABI: every exported function once, name -> (restype or None for the default int, argtypes).
+# lib() applies the table and EXPORTS is its keys, so a name cannot be exported without a prototype.
+_vp, _sz, _u64, _i32, _u32, _ui, _str = C.c_void_p, C.c_size_t, C.c_uint64, C.c_int, C.c_uint32, C.c_uint, C.c_char_p
+_pvp, _psz, _pu64, _pi32, _pui = C.POINTER(_vp), C.POINTER(_sz), C.POINTER(_u64), C.POINTER(_i32), C.POINTER(_ui)
+_pidx, _pbidx, _pseek, _prank = C.POINTER(Index), C.POINTER(BatchIndex), C.POINTER(SeekInfo), C.POINTER(SparseRankInfo)
+# ctx, stream pointers, stream sizes, codes, side-cars: the front of every plane decode; a range decode adds the seek tables
+# (infos, table pointers, table sizes), one from sparse planes the rank tables (infos, host pointers)
+_PLANES_FRONT = [_vp, _pvp, _psz, _vp, _pidx]
+_RANGE_FRONT = _PLANES_FRONT + [_pseek, _pvp, _psz]
+_SPARSE_RANGE_FRONT = _RANGE_FRONT + [_prank, _pvp]
+_COMPRESS_SPARSE = [_vp, _vp, _sz, _u32, _ui, _vp, _sz, _vp, _vp, _pidx, _pui, _psz]
+_COMPRESS_SPARSE_DELTA = [_vp, _vp, _vp, _sz, _u32, _ui, _vp, _sz, _vp, _vp, _pidx, _pui, _psz]
+_PROTOS = {
+    "ghf_ctx_create": (None, [_i32, _pvp]),
+    "ghf_ctx_destroy": (None, [_vp]),
+    "ghf_ctx_set_stream": (None, [_vp, _vp]),
+    "ghf_sync": (None, [_vp]),
+    "ghf_status": (None, [_vp]),
+    "ghf_clear_status": (None, [_vp]),
+    "ghf_last_error": (_str, [_vp]),
+    "ghf_status_string": (_str, [_i32]),
+    "ghf_version": (None, []),
+    "ghf_device_alloc": (None, [_vp, _sz, _pvp]),
+    "ghf_device_free": (None, [_vp, _vp]),
+    "ghf_host_alloc": (None, [_vp, _sz, _pvp]),
+    "ghf_host_free": (None, [_vp, _vp]),
+    "ghf_copy_h2d": (None, [_vp, _vp, _vp, _sz]),
+    "ghf_copy_d2h": (None, [_vp, _vp, _vp, _sz]),
+    "ghf_memset_d": (None, [_vp, _vp, _i32, _sz]),
+    "ghf_histogram": (None, [_vp, _vp, _sz, _vp]),
+    "ghf_build_code": (None, [_vp, _vp, _vp]),
+    "ghf_write_header": (None, [_vp, _vp, _vp, _sz]),
+    "ghf_header_bytes": (_sz, [_i32]),
+    "ghf_encode_plan": (None, [_vp, _vp, _sz, _vp, _vp]),
+    "ghf_encode_emit": (None, [_vp, _vp, _sz, _vp, _vp, _i32, _vp, _sz, _pidx, _vp]),
+    "ghf_compress": (None, [_vp, _vp, _sz, _vp, _sz, _vp, _vp, _pidx]),
+    "ghf_compress_bound": (_sz, [_sz]),
+    "ghf_chunk_symbols": (_u32, [_sz]),
+    "ghf_index_alloc": (None, [_vp, _sz, _pidx]),
+    "ghf_index_free": (None, [_vp, _pidx]),
+    "ghf_parse_header": (None, [_vp, _sz, C.POINTER(Code), _psz]),
+    "ghf_decode": (None, [_vp, _vp, _sz, _vp, _pidx, _vp, _sz, _vp]),
+    "ghf_decoded_size": (None, [_vp, _vp, _sz, _vp, _pu64]),
+    "ghf_shard_start_bit": (None, [_vp, _vp, _vp, _i32, _i32, _vp]),
+    "ghf_crs_build_code": (None, [_vp, _vp, _vp, _vp]),
+    "ghf_crs_compress": (None, [_vp, _vp, _sz, _vp, _sz, _vp, _vp, _pidx]),
+    "ghf_crs_compress_bound": (_sz, [_sz]),
+    "ghf_crs_parse_header": (None, [_vp, _sz, C.POINTER(Tree), _psz]),
+    "ghf_crs_decode": (None, [_vp, _vp, _sz, _i32, _vp, _pidx, _vp, _sz, _vp]),
+    "ghf_crs_decoded_size": (None, [_vp, _vp, _sz, _i32, _vp, _pu64]),
+    "ghf_build_code_ex": (None, [_vp, _vp, _vp, _ui]),
+    "ghf_compress_ex": (None, [_vp, _vp, _sz, _vp, _sz, _vp, _vp, _pidx, _ui]),
+    "ghf_sync_piece": (None, [_vp, _vp, _sz, _u32, _u64, _vp, _pu64, _pu64, _pi32]),
+    "ghf_decode_prepare": (None, [_vp, _vp]),
+    "ghf_comm_unique_id": (None, [_str]),
+    "ghf_comm_init_rank": (None, [_vp, _str, _i32, _i32, _pvp]),
+    "ghf_comm_destroy": (None, [_vp]),
+    "ghf_comm_world": (None, [_vp, _pi32, _pi32]),
+    "ghf_rccl_version": (None, [_pi32]),
+    "ghf_comm_allreduce_hist": (None, [_vp, _vp, _vp]),
+    "ghf_comm_allgather_total": (None, [_vp, _vp, _vp, _vp]),
+    "ghf_encode_sharded": (None, [_vp, _vp, _vp, _sz, _vp, _sz, _vp, _pidx, _vp, _vp]),
+    "ghf_shard_bound": (_sz, [_sz]),
+    "ghf_event_create": (None, [_vp, _pvp]),
+    "ghf_event_destroy": (None, [_vp]),
+    "ghf_event_record": (None, [_vp, _vp]),
+    "ghf_event_wait": (None, [_vp, _vp]),
+    "ghf_event_sync": (None, [_vp]),
+    "ghf_histogram_add": (None, [_vp, _vp, _sz, _vp]),
+    "ghf_crs_sync_piece": (None, [_vp, _vp, _sz, _u32, _u64, _vp, _pu64, _pu64]),
+    "ghf_copy_d2d": (None, [_vp, _vp, _vp, _sz, _i32]),
+    "ghf_shard_bytes": (None, [_vp, _vp, _vp, _i32, _i32, _psz]),
+    "ghf_seek_bytes": (_sz, [_sz]),
+    "ghf_seek_parse": (None, [_vp, _sz, _pseek]),
+    "ghf_seek_pack": (None, [_vp, _pidx, _vp, _sz, _vp, _sz]),
+    "ghf_seek_expand": (None, [_vp, _pseek, _vp, _sz, _vp, _sz, _vp, _pidx]),
+    "ghf_decode_range": (None, [_vp, _vp, _sz, _vp, _pidx, _pseek, _vp, _sz, _u64, _u64, _vp, _sz]),
+    "ghf_compress_batch_bound": (_sz, [_sz]),
+    "ghf_batch_index_alloc": (None, [_vp, _u32, _sz, _pbidx]),
+    "ghf_batch_index_free": (None, [_vp, _pbidx]),
+    "ghf_batch_index_item": (None, [_pbidx, _u32, _sz, _pidx]),
+    "ghf_compress_batch": (None, [_vp, _vp, _vp, _sz, _u32, _vp, _vp, _vp, _vp, _pbidx, _vp]),
+    "ghf_decode_batch": (None, [_vp, _vp, _vp, _vp, _pbidx, _vp, _u32, _vp, _vp, _vp, _vp]),
+    "ghf_decode_images_batch": (None, [_vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp]),
+    "ghf_decode_images_batch_stats": (None, [_vp, _vp]),
+    "ghf_histogram_batch": (None, [_vp, _vp, _vp, _sz, _u32, _ui, _vp]),
+    "ghf_compress_batch_shared_bound": (_sz, [_sz]),
+    "ghf_compress_batch_shared": (None, [_vp, _vp, _vp, _sz, _u32, _vp, _vp, _vp, _vp, _pbidx, _vp]),
+    "ghf_decode_batch_shared": (None, [_vp, _vp, _vp, _vp, _pbidx, _vp, _u32, _vp, _vp, _vp, _vp]),
+    "ghf_decode_bodies_batch_shared": (None, [_vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp]),
+    "ghf_planes_slot_bytes": (_sz, [_sz]),
+    "ghf_planes_split": (None, [_vp, _vp, _sz, _u32, _vp, _sz]),
+    "ghf_planes_merge": (None, [_vp, _vp, _sz, _sz, _u32, _vp]),
+    "ghf_compress_planes": (None, [_vp, _vp, _sz, _u32, _vp, _sz, _vp, _vp, _pidx]),
+    "ghf_decode_planes": (None, _PLANES_FRONT + [_sz, _u32, _vp, _sz, _vp]),
+    "ghf_histogram_batch_planes": (None, [_vp, _vp, _vp, _sz, _u32, _u32, _ui, _vp]),
+    "ghf_build_codes": (None, [_vp, _vp, _u32, _vp, _ui]),
+    "ghf_compress_batch_planes_shared_bound": (_sz, [_sz, _u32]),
+    "ghf_compress_batch_planes_shared": (None, [_vp, _vp, _vp, _sz, _u32, _u32, _vp, _vp, _vp, _vp, _pbidx, _vp]),
+    "ghf_decode_batch_planes_shared": (None, [_vp, _vp, _vp, _vp, _pbidx, _vp, _u32, _u32, _vp, _vp, _vp, _vp]),
+    "ghf_decode_bodies_batch_planes_shared": (None, [_vp, _vp, _vp, _vp, _u32, _u32, _vp, _vp, _vp, _vp]),
+    "ghf_batch_seek_bytes": (_sz, [_sz]),
+    "ghf_batch_seek_bound": (_sz, [_sz]),
+    "ghf_batch_seek_pack": (None, [_vp, _pbidx, _vp, _u32, _u32, _vp, _vp, _vp, _vp]),
+    "ghf_decode_bodies_batch_shared_seek": (None, [_vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp]),
+    "ghf_decode_bodies_batch_planes_shared_seek": (None, [_vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32, _vp, _vp, _vp, _vp]),
+    "ghf_planes_merge_range": (None, [_vp, _vp, _sz, _sz, _sz, _u32, _vp]),
+    "ghf_decode_planes_range": (None, _RANGE_FRONT + [_u32, _u64, _u64, _vp, _sz]),
+    "ghf_histogram_planes": (None, [_vp, _vp, _sz, _u32, _ui, _vp]),
+    "ghf_planes_image_bytes": (None, [_vp, _vp, _vp, _u32, _vp]),
+    "ghf_compress_planes_coded": (None, [_vp, _vp, _sz, _u32, _vp, _ui, _vp, _sz, _vp, _pidx]),
+    "ghf_histogram_planes_delta": (None, [_vp, _vp, _vp, _sz, _u32, _ui, _vp]),
+    "ghf_planes_split_delta": (None, [_vp, _vp, _vp, _sz, _u32, _vp, _sz]),
+    "ghf_planes_merge_delta": (None, [_vp, _vp, _sz, _vp, _sz, _u32, _vp]),
+    "ghf_planes_merge_range_delta": (None, [_vp, _vp, _sz, _vp, _sz, _sz, _u32, _vp]),
+    "ghf_compress_planes_delta": (None, [_vp, _vp, _vp, _sz, _u32, _vp, _ui, _vp, _sz, _vp, _pidx]),
+    "ghf_decode_planes_delta": (None, _PLANES_FRONT + [_vp, _sz, _u32, _vp, _sz, _vp]),
+    "ghf_decode_planes_range_delta": (None, _RANGE_FRONT + [_vp, _u32, _u64, _u64, _vp, _sz]),
+    "ghf_sparse_mask_bytes": (_sz, [_sz]),
+    "ghf_sparse_split": (None, [_vp, _vp, _sz, _vp, _vp, _sz, _vp]),
+    "ghf_sparse_merge": (None, [_vp, _vp, _vp, _sz, _sz, _vp]),
+    "ghf_compress_planes_sparse": (None, _COMPRESS_SPARSE),
+    "ghf_compress_planes_sparse_delta": (None, _COMPRESS_SPARSE_DELTA),
+    "ghf_decode_planes_sparse": (None, _PLANES_FRONT + [_ui, _psz, _sz, _u32, _vp, _sz, _vp]),
+    "ghf_decode_planes_sparse_delta": (None, _PLANES_FRONT + [_vp, _ui, _psz, _sz, _u32, _vp, _sz, _vp]),
+    "ghf_sparse_rank_bytes": (_sz, [_sz]),
+    "ghf_sparse_rank_pack": (None, [_vp, _vp, _sz, _vp, _sz]),
+    "ghf_sparse_rank_parse": (None, [_vp, _sz, _prank]),
+    "ghf_sparse_merge_at": (None, [_vp, _vp, _vp, _sz, _sz, _sz, _vp]),
+    "ghf_compress_planes_sparse_ranked": (None, _COMPRESS_SPARSE + [_vp, _sz]),
+    "ghf_compress_planes_sparse_ranked_delta": (None, _COMPRESS_SPARSE_DELTA + [_vp, _sz]),
+    "ghf_decode_planes_sparse_range": (None, _SPARSE_RANGE_FRONT + [_ui, _sz, _u32, _u64, _u64, _vp, _sz]),
+    "ghf_decode_planes_sparse_range_delta": (None, _SPARSE_RANGE_FRONT + [_vp, _ui, _sz, _u32, _u64, _u64, _vp, _sz]),
+    "ghf_planes_split_to": (None, [_vp, _vp, _vp, _sz, _u32, _pvp]),
+    "ghf_planes_merge_from": (None, [_vp, _pvp, _vp, _sz, _u32, _vp]),
+    "ghf_planes_merge_range_from": (None, [_vp, _pvp, _vp, _sz, _u32, _vp]),
+    "ghf_compress_planes_forms": (None, [_vp, _vp, _vp, _sz, _u32, _ui, _ui, _vp, _sz, _vp, _vp, _pidx, _vp, _sz, _pui, _pui, _psz]),
+    "ghf_decode_planes_forms": (None, _PLANES_FRONT + [_vp, _ui, _ui, _psz, _sz, _u32, _vp, _sz, _vp]),
+    "ghf_decode_planes_forms_range": (None, _SPARSE_RANGE_FRONT + [_vp, _ui, _ui, _sz, _u32, _u64, _u64, _vp, _sz]),
+    "ghf_decode_planes_gather": (None, [_vp, _pvp, _psz, _vp, _pseek, _pvp, _psz, _ui, _sz, _u32, _vp, _u64, _u32, _u32, _vp, _sz, _vp]),
+    "ghf_decode_planes_gather_forms": (None, [_vp, _pvp, _psz, _vp, _pseek, _pvp, _psz, _prank, _pvp, _psz, _vp, _ui, _ui, _sz, _u32,
+                                              _vp, _u64, _u32, _u32, _vp, _sz, _vp]),
+    "ghf_batch_planes_raw_auto": (None, [_vp, _vp, _vp, _u32, _vp]),
+    "ghf_compress_batch_planes_forms": (None, [_vp, _vp, _vp, _sz, _u32, _u32, _vp, _u32, _vp, _vp, _vp, _pbidx, _vp]),
+    "ghf_decode_batch_planes_forms": (None, [_vp, _vp, _vp, _vp, _pbidx, _vp, _u32, _u32, _u32, _vp, _vp, _vp, _vp]),
+    "ghf_decode_bodies_batch_planes_forms": (None, [_vp, _vp, _vp, _vp, _u32, _u32, _u32, _vp, _vp, _vp, _vp]),
+    "ghf_decode_bodies_batch_planes_forms_seek": (None, [_vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _vp, _vp, _vp, _vp]),
+}
+EXPORTS = list(_PROTOS)
 COMM_ID_BYTES = 128
 
 _lib = None
@@ -205,169 +318,11 @@ def lib():
     except ImportError:
         pass
     L = C.CDLL(LIB_PATH)
-    vp, sz, u64, i32 = C.c_void_p, C.c_size_t, C.c_uint64, C.c_int
-    L.ghf_ctx_create.argtypes = [i32, C.POINTER(vp)]
-    L.ghf_ctx_destroy.argtypes = [vp]
-    L.ghf_ctx_set_stream.argtypes = [vp, vp]
-    L.ghf_sync.argtypes = [vp]
-    L.ghf_status.argtypes = [vp]
-    L.ghf_clear_status.argtypes = [vp]
-    L.ghf_last_error.argtypes = [vp]
-    L.ghf_last_error.restype = C.c_char_p
-    L.ghf_status_string.argtypes = [i32]
-    L.ghf_status_string.restype = C.c_char_p
-    L.ghf_device_alloc.argtypes = [vp, sz, C.POINTER(vp)]
-    L.ghf_device_free.argtypes = [vp, vp]
-    L.ghf_host_alloc.argtypes = [vp, sz, C.POINTER(vp)]
-    L.ghf_host_free.argtypes = [vp, vp]
-    L.ghf_copy_h2d.argtypes = [vp, vp, vp, sz]
-    L.ghf_copy_d2h.argtypes = [vp, vp, vp, sz]
-    L.ghf_memset_d.argtypes = [vp, vp, i32, sz]
-    L.ghf_copy_d2d.argtypes = [vp, vp, vp, sz, i32]
-    L.ghf_histogram.argtypes = [vp, vp, sz, vp]
-    L.ghf_histogram_add.argtypes = [vp, vp, sz, vp]
-    L.ghf_event_create.argtypes = [vp, C.POINTER(vp)]
-    for f in (L.ghf_event_destroy, L.ghf_event_sync):
-        f.argtypes = [vp]
-    for f in (L.ghf_event_record, L.ghf_event_wait):
-        f.argtypes = [vp, vp]
-    L.ghf_build_code.argtypes = [vp, vp, vp]
-    L.ghf_write_header.argtypes = [vp, vp, vp, sz]
-    L.ghf_header_bytes.argtypes = [i32]
-    L.ghf_header_bytes.restype = sz
-    L.ghf_encode_plan.argtypes = [vp, vp, sz, vp, vp]
-    L.ghf_encode_emit.argtypes = [vp, vp, sz, vp, vp, i32, vp, sz, C.POINTER(Index), vp]
-    L.ghf_compress.argtypes = [vp, vp, sz, vp, sz, vp, vp, C.POINTER(Index)]
-    L.ghf_compress_bound.argtypes = [sz]
-    L.ghf_compress_bound.restype = sz
-    L.ghf_chunk_symbols.argtypes = [sz]
-    L.ghf_chunk_symbols.restype = C.c_uint32
-    L.ghf_index_alloc.argtypes = [vp, sz, C.POINTER(Index)]
-    L.ghf_index_free.argtypes = [vp, C.POINTER(Index)]
-    L.ghf_parse_header.argtypes = [vp, sz, C.POINTER(Code), C.POINTER(sz)]
-    L.ghf_decode.argtypes = [vp, vp, sz, vp, C.POINTER(Index), vp, sz, vp]
-    L.ghf_decoded_size.argtypes = [vp, vp, sz, vp, C.POINTER(u64)]
-    L.ghf_shard_start_bit.argtypes = [vp, vp, vp, i32, i32, vp]
-    L.ghf_decode_prepare.argtypes = [vp, vp]
-    L.ghf_sync_piece.argtypes = [vp, vp, sz, C.c_uint32, u64, vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(i32)]
-    L.ghf_build_code_ex.argtypes = [vp, vp, vp, C.c_uint]
-    L.ghf_compress_ex.argtypes = [vp, vp, sz, vp, sz, vp, vp, C.POINTER(Index), C.c_uint]
-    L.ghf_crs_build_code.argtypes = [vp, vp, vp, vp]
-    L.ghf_crs_compress.argtypes = [vp, vp, sz, vp, sz, vp, vp, C.POINTER(Index)]
-    L.ghf_crs_compress_bound.argtypes = [sz]
-    L.ghf_crs_compress_bound.restype = sz
-    L.ghf_crs_parse_header.argtypes = [vp, sz, C.POINTER(Tree), C.POINTER(sz)]
-    L.ghf_crs_decode.argtypes = [vp, vp, sz, i32, vp, C.POINTER(Index), vp, sz, vp]
-    L.ghf_crs_decoded_size.argtypes = [vp, vp, sz, i32, vp, C.POINTER(u64)]
-    L.ghf_crs_sync_piece.argtypes = [vp, vp, sz, C.c_uint32, u64, vp, C.POINTER(u64), C.POINTER(u64)]
-    L.ghf_comm_unique_id.argtypes = [C.c_char_p]
-    L.ghf_comm_init_rank.argtypes = [vp, C.c_char_p, i32, i32, C.POINTER(vp)]
-    L.ghf_comm_destroy.argtypes = [vp]
-    L.ghf_comm_world.argtypes = [vp, C.POINTER(i32), C.POINTER(i32)]
-    L.ghf_rccl_version.argtypes = [C.POINTER(i32)]
-    L.ghf_comm_allreduce_hist.argtypes = [vp, vp, vp]
-    L.ghf_comm_allgather_total.argtypes = [vp, vp, vp, vp]
-    L.ghf_encode_sharded.argtypes = [vp, vp, vp, sz, vp, sz, vp, C.POINTER(Index), vp, vp]
-    L.ghf_shard_bound.argtypes = [sz]
-    L.ghf_shard_bound.restype = sz
-    L.ghf_shard_bytes.argtypes = [vp, vp, vp, i32, i32, C.POINTER(sz)]
-    L.ghf_seek_bytes.argtypes = [sz]
-    L.ghf_seek_bytes.restype = sz
-    L.ghf_seek_parse.argtypes = [vp, sz, C.POINTER(SeekInfo)]
-    L.ghf_seek_pack.argtypes = [vp, C.POINTER(Index), vp, sz, vp, sz]
-    L.ghf_seek_expand.argtypes = [vp, C.POINTER(SeekInfo), vp, sz, vp, sz, vp, C.POINTER(Index)]
-    L.ghf_decode_range.argtypes = [vp, vp, sz, vp, C.POINTER(Index), C.POINTER(SeekInfo), vp, sz, u64, u64, vp, sz]
-    L.ghf_compress_batch_bound.argtypes = [sz]
-    L.ghf_compress_batch_bound.restype = sz
-    L.ghf_batch_index_alloc.argtypes = [vp, C.c_uint32, sz, C.POINTER(BatchIndex)]
-    L.ghf_batch_index_free.argtypes = [vp, C.POINTER(BatchIndex)]
-    L.ghf_batch_index_item.argtypes = [C.POINTER(BatchIndex), C.c_uint32, sz, C.POINTER(Index)]
-    L.ghf_compress_batch.argtypes = [vp, vp, vp, sz, C.c_uint32, vp, vp, vp, vp, C.POINTER(BatchIndex), vp]
-    L.ghf_decode_batch.argtypes = [vp, vp, vp, vp, C.POINTER(BatchIndex), vp, C.c_uint32, vp, vp, vp, vp]
-    L.ghf_decode_images_batch.argtypes = [vp, vp, vp, C.c_uint32, vp, vp, vp, vp, vp]
-    L.ghf_decode_images_batch_stats.argtypes = [vp, vp]
-    L.ghf_histogram_batch.argtypes = [vp, vp, vp, sz, C.c_uint32, C.c_uint, vp]
-    L.ghf_compress_batch_shared_bound.argtypes = [sz]
-    L.ghf_compress_batch_shared_bound.restype = sz
-    L.ghf_compress_batch_shared.argtypes = [vp, vp, vp, sz, C.c_uint32, vp, vp, vp, vp, C.POINTER(BatchIndex), vp]
-    L.ghf_decode_batch_shared.argtypes = [vp, vp, vp, vp, C.POINTER(BatchIndex), vp, C.c_uint32, vp, vp, vp, vp]
-    L.ghf_decode_bodies_batch_shared.argtypes = [vp, vp, vp, vp, C.c_uint32, vp, vp, vp, vp]
-    L.ghf_planes_slot_bytes.argtypes = [sz]
-    L.ghf_planes_slot_bytes.restype = sz
-    L.ghf_planes_split.argtypes = [vp, vp, sz, C.c_uint32, vp, sz]
-    L.ghf_planes_merge.argtypes = [vp, vp, sz, sz, C.c_uint32, vp]
-    L.ghf_compress_planes.argtypes = [vp, vp, sz, C.c_uint32, vp, sz, vp, vp, C.POINTER(Index)]
-    L.ghf_decode_planes.argtypes = [vp, C.POINTER(vp), C.POINTER(sz), vp, C.POINTER(Index), sz, C.c_uint32, vp, sz, vp]
-    u32 = C.c_uint32
-    L.ghf_histogram_batch_planes.argtypes = [vp, vp, vp, sz, u32, u32, C.c_uint, vp]
-    L.ghf_build_codes.argtypes = [vp, vp, u32, vp, C.c_uint]
-    L.ghf_compress_batch_planes_shared_bound.argtypes = [sz, u32]
-    L.ghf_compress_batch_planes_shared_bound.restype = sz
-    L.ghf_compress_batch_planes_shared.argtypes = [vp, vp, vp, sz, u32, u32, vp, vp, vp, vp, C.POINTER(BatchIndex), vp]
-    L.ghf_decode_batch_planes_shared.argtypes = [vp, vp, vp, vp, C.POINTER(BatchIndex), vp, u32, u32, vp, vp, vp, vp]
-    L.ghf_decode_bodies_batch_planes_shared.argtypes = [vp, vp, vp, vp, u32, u32, vp, vp, vp, vp]
-    L.ghf_batch_seek_bytes.argtypes = [sz]
-    L.ghf_batch_seek_bytes.restype = sz
-    L.ghf_batch_seek_bound.argtypes = [sz]
-    L.ghf_batch_seek_bound.restype = sz
-    L.ghf_batch_seek_pack.argtypes = [vp, C.POINTER(BatchIndex), vp, u32, u32, vp, vp, vp, vp]
-    L.ghf_decode_bodies_batch_shared_seek.argtypes = [vp, vp, vp, vp, vp, vp, u32, vp, vp, vp, vp]
-    L.ghf_decode_bodies_batch_planes_shared_seek.argtypes = [vp, vp, vp, vp, vp, vp, u32, u32, vp, vp, vp, vp]
-    L.ghf_batch_planes_raw_auto.argtypes = [vp, vp, vp, u32, vp]
-    L.ghf_compress_batch_planes_forms.argtypes = [vp, vp, vp, sz, u32, u32, vp, u32, vp, vp, vp, C.POINTER(BatchIndex), vp]
-    L.ghf_decode_batch_planes_forms.argtypes = [vp, vp, vp, vp, C.POINTER(BatchIndex), vp, u32, u32, u32, vp, vp, vp, vp]
-    L.ghf_decode_bodies_batch_planes_forms.argtypes = [vp, vp, vp, vp, u32, u32, u32, vp, vp, vp, vp]
-    L.ghf_decode_bodies_batch_planes_forms_seek.argtypes = [vp, vp, vp, vp, vp, vp, u32, u32, u32, vp, vp, vp, vp]
-    L.ghf_histogram_planes.argtypes = [vp, vp, sz, u32, C.c_uint, vp]
-    L.ghf_planes_image_bytes.argtypes = [vp, vp, vp, u32, vp]
-    L.ghf_compress_planes_coded.argtypes = [vp, vp, sz, u32, vp, C.c_uint, vp, sz, vp, C.POINTER(Index)]
-    L.ghf_planes_merge_range.argtypes = [vp, vp, sz, sz, sz, u32, vp]
-    L.ghf_histogram_planes_delta.argtypes = [vp, vp, vp, sz, u32, C.c_uint, vp]
-    L.ghf_planes_split_delta.argtypes = [vp, vp, vp, sz, u32, vp, sz]
-    L.ghf_planes_merge_delta.argtypes = [vp, vp, sz, vp, sz, u32, vp]
-    L.ghf_planes_merge_range_delta.argtypes = [vp, vp, sz, vp, sz, sz, u32, vp]
-    L.ghf_compress_planes_delta.argtypes = [vp, vp, vp, sz, u32, vp, C.c_uint, vp, sz, vp, C.POINTER(Index)]
-    L.ghf_decode_planes_delta.argtypes = [vp, C.POINTER(vp), C.POINTER(sz), vp, C.POINTER(Index), vp, sz, u32, vp, sz, vp]
-    L.ghf_decode_planes_range_delta.argtypes = [vp, C.POINTER(vp), C.POINTER(sz), vp, C.POINTER(Index), C.POINTER(SeekInfo),
-                                                C.POINTER(vp), C.POINTER(sz), vp, u32, C.c_uint64, C.c_uint64, vp, sz]
-    L.ghf_decode_planes_range.argtypes = [vp, C.POINTER(vp), C.POINTER(sz), vp, C.POINTER(Index), C.POINTER(SeekInfo),
-                                          C.POINTER(vp), C.POINTER(sz), u32, u64, u64, vp, sz]
-    L.ghf_sparse_mask_bytes.argtypes = [sz]
-    L.ghf_sparse_mask_bytes.restype = sz
-    L.ghf_sparse_split.argtypes = [vp, vp, sz, vp, vp, sz, vp]
-    L.ghf_sparse_merge.argtypes = [vp, vp, vp, sz, sz, vp]
-    L.ghf_compress_planes_sparse.argtypes = [vp, vp, sz, u32, C.c_uint, vp, sz, vp, vp, C.POINTER(Index), C.POINTER(C.c_uint),
-                                             C.POINTER(sz)]
-    L.ghf_compress_planes_sparse_delta.argtypes = [vp, vp, vp, sz, u32, C.c_uint, vp, sz, vp, vp, C.POINTER(Index),
-                                                   C.POINTER(C.c_uint), C.POINTER(sz)]
-    L.ghf_decode_planes_sparse.argtypes = [vp, C.POINTER(vp), C.POINTER(sz), vp, C.POINTER(Index), C.c_uint, C.POINTER(sz), sz, u32,
-                                           vp, sz, vp]
-    L.ghf_decode_planes_sparse_delta.argtypes = [vp, C.POINTER(vp), C.POINTER(sz), vp, C.POINTER(Index), vp, C.c_uint, C.POINTER(sz),
-                                                 sz, u32, vp, sz, vp]
-    L.ghf_sparse_rank_bytes.argtypes = [sz]
-    L.ghf_sparse_rank_bytes.restype = sz
-    L.ghf_sparse_rank_pack.argtypes = [vp, vp, sz, vp, sz]
-    L.ghf_sparse_rank_parse.argtypes = [vp, sz, C.POINTER(SparseRankInfo)]
-    L.ghf_sparse_merge_at.argtypes = [vp, vp, vp, sz, sz, sz, vp]
-    L.ghf_compress_planes_sparse_ranked.argtypes = L.ghf_compress_planes_sparse.argtypes + [vp, sz]
-    L.ghf_compress_planes_sparse_ranked_delta.argtypes = L.ghf_compress_planes_sparse_delta.argtypes + [vp, sz]
-    sparse_range_front = [vp, C.POINTER(vp), C.POINTER(sz), vp, C.POINTER(Index), C.POINTER(SeekInfo), C.POINTER(vp), C.POINTER(sz),
-                          C.POINTER(SparseRankInfo), C.POINTER(vp)]
-    L.ghf_decode_planes_sparse_range.argtypes = sparse_range_front + [C.c_uint, sz, u32, u64, u64, vp, sz]
-    L.ghf_decode_planes_sparse_range_delta.argtypes = sparse_range_front + [vp, C.c_uint, sz, u32, u64, u64, vp, sz]
-    L.ghf_planes_split_to.argtypes = [vp, vp, vp, sz, u32, C.POINTER(vp)]
-    L.ghf_planes_merge_from.argtypes = [vp, C.POINTER(vp), vp, sz, u32, vp]
-    L.ghf_planes_merge_range_from.argtypes = [vp, C.POINTER(vp), vp, sz, u32, vp]
-    L.ghf_compress_planes_forms.argtypes = [vp, vp, vp, sz, u32, C.c_uint, C.c_uint, vp, sz, vp, vp, C.POINTER(Index), vp, sz,
-                                            C.POINTER(C.c_uint), C.POINTER(C.c_uint), C.POINTER(sz)]
-    L.ghf_decode_planes_forms.argtypes = [vp, C.POINTER(vp), C.POINTER(sz), vp, C.POINTER(Index), vp, C.c_uint, C.c_uint, C.POINTER(sz),
-                                          sz, u32, vp, sz, vp]
-    L.ghf_decode_planes_forms_range.argtypes = sparse_range_front + [vp, C.c_uint, C.c_uint, sz, u32, u64, u64, vp, sz]
-    L.ghf_decode_planes_gather.argtypes = [vp, C.POINTER(vp), C.POINTER(sz), vp, C.POINTER(SeekInfo), C.POINTER(vp), C.POINTER(sz), C.c_uint,
-                                           sz, u32, vp, u64, u32, u32, vp, sz, vp]
-    L.ghf_decode_planes_gather_forms.argtypes = [vp, C.POINTER(vp), C.POINTER(sz), vp, C.POINTER(SeekInfo), C.POINTER(vp), C.POINTER(sz),
-                                                 C.POINTER(SparseRankInfo), C.POINTER(vp), C.POINTER(sz), vp, C.c_uint, C.c_uint, sz, u32,
-                                                 vp, u64, u32, u32, vp, sz, vp]
+    for name, (restype, argtypes) in _PROTOS.items():
+        f = getattr(L, name)
+        f.argtypes = argtypes
+        if restype is not None:
+            f.restype = restype
     _lib = L
     return L
 
@@ -527,6 +482,72 @@ def crs_parse_header(host_bytes):
     return tree, tb.value
 
 
+# ---- marshalling, each step once.  The host arrays made here hold addresses C reads during the call: whoever makes one keeps
+# it referenced (an argument of the call, or a local of the method that calls) until the call has returned.
+def _addr(x):
+    """what C gets for a device buffer: None -> NULL, an int address as it is, a tensor's data_ptr()"""
+    return None if x is None else x if isinstance(x, int) else x.data_ptr()
+
+
+def _ref(struct):
+    """byref of a ctypes structure, None -> NULL"""
+    return None if struct is None else C.byref(struct)
+
+
+def _ptr_array(xs, n):
+    """a host array of n addresses from the first n of xs: tensors, int addresses or None (-> NULL)"""
+    return (C.c_void_p * n)(*[_addr(x) for x in list(xs)[:n]])
+
+
+def _size_array(values, n):
+    """a host size_t array of n entries from the first n of values"""
+    return (C.c_size_t * n)(*[int(v) for v in list(values)[:n]])
+
+
+def _n_elems(d_in, elem_bytes, n_elems):
+    """n_elems, by default all of the tensor d_in taken as elements of elem_bytes bytes"""
+    return d_in.numel() * d_in.element_size() // elem_bytes if n_elems is None else n_elems
+
+
+def _seek_tables(infos, d_tables, table_bytes, n):
+    """(SeekInfo array, table pointers, table sizes) of n slots, or three NULLs without infos.  A None info is SeekInfo() with
+    a table of 0 bytes; table_bytes defaults to seek_bytes(info.n_symbols)."""
+    if infos is None:
+        return None, None, None
+    infos = list(infos)[:n]
+    if table_bytes is None:
+        table_bytes = [0 if i is None else seek_bytes(i.n_symbols) for i in infos]
+    return (SeekInfo * n)(*[SeekInfo() if i is None else i for i in infos]), _ptr_array(d_tables, n), _size_array(table_bytes, n)
+
+
+def _rank_arrays(ranks, n, device):
+    """ranks: None, or per plane None or (SparseRankInfo, table[, table bytes]) -> (infos, pointers, sizes, keep) of n planes
+    (NULLs without ranks).  device False: the tables are HOST bytes, and `keep` holds the contiguous arrays the pointers
+    point into: the caller keeps it until the call has returned.  device True: tensors or addresses, with their sizes."""
+    if ranks is None:
+        return None, None, None, []
+    infos, ptrs, sizes, keep = (SparseRankInfo * n)(), (C.c_void_p * n)(), (C.c_size_t * n)(), []
+    for p, r in enumerate(ranks):
+        if r is None:
+            continue
+        infos[p] = r[0]
+        if device:
+            ptrs[p] = _addr(r[1])
+            sizes[p] = 0 if r[1] is None else r[2] if len(r) > 2 else r[1].numel()
+        elif r[1] is not None:
+            import numpy as np
+
+            keep.append(np.ascontiguousarray(r[1], dtype=np.uint8))
+            ptrs[p] = keep[-1].ctypes.data
+    return infos, ptrs, sizes, keep
+
+
+def _entry(shared, forms, raw):
+    """(entry point, what it takes more): without a mask of raw planes (None) the all-dense call `shared`, with one (an int,
+    0 included) its twin `forms` and the mask"""
+    return (shared, ()) if raw is None else (forms, (raw,))
+
+
 class Context:
     """one ghf_ctx; work is queued on torch's current stream of `device`."""
 
@@ -572,6 +593,10 @@ class Context:
     def _chk(self, rc, where):
         if rc:
             raise GhfError(rc, where, self.L.ghf_last_error(self.h).decode(errors="replace"))
+
+    def _call(self, name, *args):
+        """the C function `name` on this context; a status raises GhfError with that name as its `where`"""
+        self._chk(getattr(self.L, name)(self.h, *args), name)
 
     def sync(self):
         """wait for the stream; raises when a device-side stage latched an error."""
@@ -731,106 +756,6 @@ class Context:
     def _i64(self, values):
         return self.torch.tensor([int(v) for v in values], dtype=self.torch.int64).to(self.device)
 
-    def compress_batch(self, items, sizes=None, max_item_bytes=None, d_out=None, out_stride=None, d_codes=None, index=None):
-        """items: a list of CUDA uint8 tensors, or ONE packed CUDA uint8 tensor with `sizes` (item i at the sum of the
-        sizes before it).  The pointer and size arrays are built on the device; no host synchronisation.  d_out: one
-        uint8 tensor holding item i's image at i * out_stride (allocated here unless given).
-        -> dict(out, out_stride, out_bytes int64[count], status int32[count], codes uint8[count, sizeof(Code)], in_ptrs,
-                in_bytes, out_ptrs, count, max_item_bytes)"""
-        t = self.torch
-        if sizes is None:
-            sizes = [int(x.numel()) for x in items]
-            ptrs = [x.data_ptr() if x.numel() else 0 for x in items]
-        else:
-            sizes = [int(v) for v in sizes]
-            base, ptrs, at = items.data_ptr(), [], 0
-            for v in sizes:
-                ptrs.append(base + at)
-                at += v
-        count = len(sizes)
-        if max_item_bytes is None:
-            max_item_bytes = max(max(sizes, default=1), 1)
-        if out_stride is None:
-            out_stride = compress_batch_bound(max_item_bytes)
-        if d_out is None:
-            d_out = t.empty(max(count * out_stride, 16), dtype=t.uint8, device=self.device)
-        if d_codes is None:
-            d_codes = t.zeros((max(count, 1), C.sizeof(Code)), dtype=t.uint8, device=self.device)
-        in_ptrs, in_bytes = self._i64(ptrs), self._i64(sizes)
-        out_ptrs = d_out.data_ptr() + t.arange(count, dtype=t.int64, device=self.device) * out_stride
-        out_caps = t.full((max(count, 1),), out_stride, dtype=t.int64, device=self.device)
-        out_bytes = t.zeros(max(count, 1), dtype=t.int64, device=self.device)
-        status = t.full((max(count, 1),), -1, dtype=t.int32, device=self.device)
-        self._chk(
-            self.L.ghf_compress_batch(self.h, in_ptrs.data_ptr(), in_bytes.data_ptr(), max_item_bytes, count, out_ptrs.data_ptr(),
-                                      out_caps.data_ptr(), out_bytes.data_ptr(), d_codes.data_ptr(),
-                                      None if index is None else C.byref(index), status.data_ptr()),
-            "ghf_compress_batch")
-        return {"out": d_out, "out_stride": out_stride, "out_bytes": out_bytes[:count], "status": status[:count], "codes": d_codes,
-                "in_ptrs": in_ptrs, "in_bytes": in_bytes, "out_ptrs": out_ptrs, "out_caps": out_caps, "count": count,
-                "max_item_bytes": max_item_bytes, "keep": items}
-
-    def decode_batch(self, stream_ptrs, stream_bytes, d_codes, index, n_symbols, d_out=None, out_stride=None, out_ptrs=None,
-                     out_caps=None):
-        """stream_ptrs / stream_bytes / n_symbols: int64 CUDA tensors [count] (e.g. out_ptrs, out_bytes and in_bytes of
-        compress_batch).  Item i is decoded to d_out[i * out_stride ..) unless out_ptrs / out_caps (int64 CUDA tensors) say
-        otherwise.  -> dict(out, out_stride, out_bytes int64[count], status int32[count])"""
-        t = self.torch
-        count = int(n_symbols.numel())
-        if out_ptrs is None:
-            if out_stride is None:
-                out_stride = (int(index.max_item_bytes) + 15) & ~15
-            if d_out is None:
-                d_out = t.empty(max(count * out_stride, 16), dtype=t.uint8, device=self.device)
-            out_ptrs = d_out.data_ptr() + t.arange(count, dtype=t.int64, device=self.device) * out_stride
-            out_caps = t.full((max(count, 1),), out_stride, dtype=t.int64, device=self.device)
-        out_bytes = t.zeros(max(count, 1), dtype=t.int64, device=self.device)
-        status = t.full((max(count, 1),), -1, dtype=t.int32, device=self.device)
-        self._chk(
-            self.L.ghf_decode_batch(self.h, stream_ptrs.data_ptr(), stream_bytes.data_ptr(), d_codes.data_ptr(), C.byref(index),
-                                    n_symbols.data_ptr(), count, out_ptrs.data_ptr(), out_caps.data_ptr(), out_bytes.data_ptr(),
-                                    status.data_ptr()),
-            "ghf_decode_batch")
-        return {"out": d_out, "out_stride": out_stride, "out_bytes": out_bytes[:count], "status": status[:count],
-                "out_ptrs": out_ptrs, "out_caps": out_caps}
-
-    def decode_images_batch(self, stream_ptrs, stream_bytes, out=None, caps=None, codes=False):
-        """Standalone .crs2 images and nothing else.  stream_ptrs / stream_bytes: int64 CUDA tensors [count].
-        out=None: the sizes pass -> dict(out_bytes int64[count], status int32[count]).
-        Otherwise the decode pass: `caps` (int64 CUDA tensor [count], e.g. the out_bytes of the sizes pass) says how much
-        room every item gets; out=True allocates one uint8 tensor with item i at i * out_stride, out_stride = the largest
-        cap rounded up to 16 (this reads `caps` back: one host synchronisation); a uint8 CUDA tensor is used as it is, cut
-        into count equal slots.  codes=True: also the items' tables, uint8[count, sizeof(Code)].
-        -> dict(out, out_stride, out_bytes, status[, codes])"""
-        t = self.torch
-        count = int(stream_bytes.numel())
-        out_bytes = t.zeros(max(count, 1), dtype=t.int64, device=self.device)
-        status = t.full((max(count, 1),), -1, dtype=t.int32, device=self.device)
-        d_codes = t.zeros((max(count, 1), C.sizeof(Code)), dtype=t.uint8, device=self.device) if codes else None
-        res = {"out_bytes": out_bytes[:count], "status": status[:count]}
-        out_ptrs = out_caps = None
-        if out is not None:
-            if caps is None:
-                raise ValueError("decode_images_batch: the decode pass needs caps (e.g. the out_bytes of the sizes pass)")
-            if out is True:
-                out_stride = (int(caps.max().item()) + 15) & ~15 if count else 16
-                out = t.empty(max(count * out_stride, 16), dtype=t.uint8, device=self.device)
-            else:
-                out_stride = int(out.numel()) // max(count, 1)
-            out_ptrs = out.data_ptr() + t.arange(count, dtype=t.int64, device=self.device) * out_stride
-            out_caps = t.clamp(caps.to(t.int64), max=out_stride).contiguous()
-            res.update(out=out, out_stride=out_stride, out_ptrs=out_ptrs, out_caps=out_caps)
-        if codes:
-            res["codes"] = d_codes
-        self._chk(
-            self.L.ghf_decode_images_batch(self.h, stream_ptrs.data_ptr(), stream_bytes.data_ptr(), count,
-                                           None if out_ptrs is None else out_ptrs.data_ptr(),
-                                           None if out_caps is None else out_caps.data_ptr(), out_bytes.data_ptr(),
-                                           None if d_codes is None else d_codes.data_ptr(), status.data_ptr()),
-            "ghf_decode_images_batch")
-        return res
-
-    # ---- shared-code batches: one code for the whole batch, an item's output is its body alone ----
     def _item_arrays(self, items, sizes):
         """(ptrs, sizes) of a list of CUDA uint8 tensors, or of ONE packed tensor cut by `sizes`"""
         if sizes is None:
@@ -842,83 +767,68 @@ class Context:
             at += v
         return ptrs, sizes
 
-    def histogram_batch(self, items, sizes=None, max_item_bytes=None, flags=0, out=None):
-        """the byte counts of all items in one int64[257] CUDA tensor (slot 256 = 1), ready for build_code.  items / sizes
-        as in compress_batch; flags: HIST_COVER_ALL.  No host synchronisation."""
+    def _batch_in(self, items, sizes, max_item_bytes, elem_bytes=1):
+        """the items of a batch call -> (in_ptrs, in_bytes as int64 CUDA tensors, count, max_item_bytes: by default the largest
+        item, at least 1, rounded up to whole elements)"""
         ptrs, sizes = self._item_arrays(items, sizes)
         if max_item_bytes is None:
-            max_item_bytes = max(max(sizes, default=1), 1)
-        hist = self.torch.empty(NSYM, dtype=self.torch.int64, device=self.device) if out is None else out
-        in_ptrs, in_bytes = self._i64(ptrs), self._i64(sizes)
-        self._chk(self.L.ghf_histogram_batch(self.h, in_ptrs.data_ptr(), in_bytes.data_ptr(), max_item_bytes, len(sizes), flags,
-                                             hist.data_ptr()), "ghf_histogram_batch")
-        return hist
+            max_item_bytes = -(-max(max(sizes, default=1), 1) // elem_bytes) * elem_bytes
+        return self._i64(ptrs), self._i64(sizes), len(sizes), max_item_bytes
 
-    def compress_batch_shared(self, items, d_code, sizes=None, max_item_bytes=None, d_out=None, out_stride=None, index=None):
-        """compress_batch under the one code `d_code` (e.g. build_code(histogram_batch(items))): item i's BODY goes to
-        d_out[i * out_stride ..).  -> dict(out, out_stride, out_bytes int64[count], status int32[count], code, in_ptrs,
-        in_bytes, out_ptrs, out_caps, count, max_item_bytes)"""
+    def _planes_out(self, count, out_stride, d_out):
+        """count output slots of out_stride bytes in one uint8 tensor (allocated unless given) -> (d_out, out_ptrs, out_caps)"""
         t = self.torch
-        ptrs, sizes = self._item_arrays(items, sizes)
-        count = len(sizes)
-        if max_item_bytes is None:
-            max_item_bytes = max(max(sizes, default=1), 1)
-        if out_stride is None:
-            out_stride = compress_batch_shared_bound(max_item_bytes)
         if d_out is None:
             d_out = t.empty(max(count * out_stride, 16), dtype=t.uint8, device=self.device)
-        in_ptrs, in_bytes = self._i64(ptrs), self._i64(sizes)
         out_ptrs = d_out.data_ptr() + t.arange(count, dtype=t.int64, device=self.device) * out_stride
-        out_caps = t.full((max(count, 1),), out_stride, dtype=t.int64, device=self.device)
-        out_bytes = t.zeros(max(count, 1), dtype=t.int64, device=self.device)
-        status = t.full((max(count, 1),), -1, dtype=t.int32, device=self.device)
-        self._chk(
-            self.L.ghf_compress_batch_shared(self.h, in_ptrs.data_ptr(), in_bytes.data_ptr(), max_item_bytes, count,
-                                             d_code.data_ptr(), out_ptrs.data_ptr(), out_caps.data_ptr(), out_bytes.data_ptr(),
-                                             None if index is None else C.byref(index), status.data_ptr()),
-            "ghf_compress_batch_shared")
-        return {"out": d_out, "out_stride": out_stride, "out_bytes": out_bytes[:count], "status": status[:count], "code": d_code,
-                "in_ptrs": in_ptrs, "in_bytes": in_bytes, "out_ptrs": out_ptrs, "out_caps": out_caps, "count": count,
-                "max_item_bytes": max_item_bytes, "keep": items}
+        return d_out, out_ptrs, t.full((max(count, 1),), out_stride, dtype=t.int64, device=self.device)
 
-    def decode_batch_shared(self, stream_ptrs, stream_bytes, d_code, index, n_symbols, d_out=None, out_stride=None, out_ptrs=None,
-                            out_caps=None):
-        """decode_batch with one code for all items: stream_ptrs / stream_bytes are the bodies (e.g. out_ptrs and
-        out_bytes of compress_batch_shared).  -> dict(out, out_stride, out_bytes int64[count], status int32[count])"""
+    def _item_status(self, count):
+        """(out_bytes int64 of zeros, status int32 of -1) for count slots, never empty; callers hand out [:count]"""
         t = self.torch
-        count = int(n_symbols.numel())
+        return t.zeros(max(count, 1), dtype=t.int64, device=self.device), t.full((max(count, 1),), -1, dtype=t.int32, device=self.device)
+
+    def _compress_batch_io(self, items, sizes, max_item_bytes, elem_bytes, bound, d_out, out_stride, **codes):
+        """inputs and outputs of a batch compress call with elem_bytes output slots per item; `codes` is the call's codes under
+        the key its dict shows them.  -> (the result dict, the addresses (in_ptrs, in_bytes, out_ptrs, out_caps, out_bytes,
+        status) of the tensors the dict keeps)"""
+        in_ptrs, in_bytes, count, max_item_bytes = self._batch_in(items, sizes, max_item_bytes, elem_bytes)
+        slots = count * elem_bytes
+        if out_stride is None:
+            out_stride = bound(max_item_bytes)
+        d_out, out_ptrs, out_caps = self._planes_out(slots, out_stride, d_out)
+        out_bytes, status = self._item_status(slots)
+        res = {"out": d_out, "out_stride": out_stride, "out_bytes": out_bytes[:slots], "status": status[:slots], **codes,
+               "in_ptrs": in_ptrs, "in_bytes": in_bytes, "out_ptrs": out_ptrs, "out_caps": out_caps, "count": count,
+               "max_item_bytes": max_item_bytes, "keep": items}
+        return res, tuple(x.data_ptr() for x in (in_ptrs, in_bytes, out_ptrs, out_caps, out_bytes, status))
+
+    def _decode_batch(self, name, stream_ptrs, stream_bytes, d_codes, index, n_items, more, elem_bytes, d_out, out_stride, out_ptrs,
+                      out_caps):
+        """the batch decodes with the live side-car; `more`: what the entry point takes between the count and the outputs"""
+        count = int(n_items.numel())
         if out_ptrs is None:
             if out_stride is None:
-                out_stride = (int(index.max_item_bytes) + 15) & ~15
-            if d_out is None:
-                d_out = t.empty(max(count * out_stride, 16), dtype=t.uint8, device=self.device)
-            out_ptrs = d_out.data_ptr() + t.arange(count, dtype=t.int64, device=self.device) * out_stride
-            out_caps = t.full((max(count, 1),), out_stride, dtype=t.int64, device=self.device)
-        out_bytes = t.zeros(max(count, 1), dtype=t.int64, device=self.device)
-        status = t.full((max(count, 1),), -1, dtype=t.int32, device=self.device)
-        self._chk(
-            self.L.ghf_decode_batch_shared(self.h, stream_ptrs.data_ptr(), stream_bytes.data_ptr(), d_code.data_ptr(),
-                                           C.byref(index), n_symbols.data_ptr(), count, out_ptrs.data_ptr(), out_caps.data_ptr(),
-                                           out_bytes.data_ptr(), status.data_ptr()),
-            "ghf_decode_batch_shared")
+                out_stride = (int(index.max_item_bytes) * elem_bytes + 15) & ~15
+            d_out, out_ptrs, out_caps = self._planes_out(count, out_stride, d_out)
+        out_bytes, status = self._item_status(count)
+        self._call(name, stream_ptrs.data_ptr(), stream_bytes.data_ptr(), d_codes.data_ptr(), C.byref(index), n_items.data_ptr(), count,
+                   *more, out_ptrs.data_ptr(), out_caps.data_ptr(), out_bytes.data_ptr(), status.data_ptr())
         return {"out": d_out, "out_stride": out_stride, "out_bytes": out_bytes[:count], "status": status[:count],
                 "out_ptrs": out_ptrs, "out_caps": out_caps}
 
-    def decode_bodies_batch_shared(self, stream_ptrs, stream_bytes, d_code, out=None, caps=None):
-        """Bodies under the one code `d_code` and nothing else: no side-car, no sizes.  stream_ptrs / stream_bytes: int64
-        CUDA tensors [count] (e.g. out_ptrs and out_bytes of compress_batch_shared, or stored bodies copied up).
-        out=None: the sizes pass -> dict(out_bytes int64[count], status int32[count]).
-        Otherwise the decode pass, with out / caps as in decode_images_batch -> dict(out, out_stride, out_bytes, status,
-        out_ptrs, out_caps)"""
+    def _two_pass(self, who, count, out, caps):
+        """the outputs of a two-pass batch decode, called by the public method `who`.  out None: the sizes pass, no output
+        pointers.  Otherwise the decode pass with `caps`: out True allocates slots of the largest cap rounded up to 16 (reads
+        caps back: the one host synchronisation), a tensor is cut into count equal slots.
+        -> (the result dict, the call's last arguments: out_ptrs, out_caps, out_bytes, status as addresses or NULL)"""
         t = self.torch
-        count = int(stream_bytes.numel())
-        out_bytes = t.zeros(max(count, 1), dtype=t.int64, device=self.device)
-        status = t.full((max(count, 1),), -1, dtype=t.int32, device=self.device)
+        out_bytes, status = self._item_status(count)
         res = {"out_bytes": out_bytes[:count], "status": status[:count]}
         out_ptrs = out_caps = None
         if out is not None:
             if caps is None:
-                raise ValueError("decode_bodies_batch_shared: the decode pass needs caps (e.g. the out_bytes of the sizes pass)")
+                raise ValueError(who + ": the decode pass needs caps (e.g. the out_bytes of the sizes pass)")
             if out is True:
                 out_stride = (int(caps.max().item()) + 15) & ~15 if count else 16
                 out = t.empty(max(count * out_stride, 16), dtype=t.uint8, device=self.device)
@@ -927,13 +837,88 @@ class Context:
             out_ptrs = out.data_ptr() + t.arange(count, dtype=t.int64, device=self.device) * out_stride
             out_caps = t.clamp(caps.to(t.int64), max=out_stride).contiguous()
             res.update(out=out, out_stride=out_stride, out_ptrs=out_ptrs, out_caps=out_caps)
-        self._chk(
-            self.L.ghf_decode_bodies_batch_shared(self.h, stream_ptrs.data_ptr(), stream_bytes.data_ptr(), d_code.data_ptr(), count,
-                                                  None if out_ptrs is None else out_ptrs.data_ptr(),
-                                                  None if out_caps is None else out_caps.data_ptr(), out_bytes.data_ptr(),
-                                                  status.data_ptr()),
-            "ghf_decode_bodies_batch_shared")
+        return res, (_addr(out_ptrs), _addr(out_caps), out_bytes.data_ptr(), status.data_ptr())
+
+    def _decode_bodies(self, name, who, front, count, more, out, caps):
+        """the two-pass decodes of shared-code bodies: `front` are the CUDA tensors the entry point takes before the count
+        (streams, sizes[, records, sizes], codes), `more` what it takes between the count and the outputs"""
+        res, outs = self._two_pass(who, count, out, caps)
+        self._call(name, *[x.data_ptr() for x in front], count, *more, *outs)
         return res
+
+    def compress_batch(self, items, sizes=None, max_item_bytes=None, d_out=None, out_stride=None, d_codes=None, index=None):
+        """items: a list of CUDA uint8 tensors, or ONE packed CUDA uint8 tensor with `sizes` (item i at the sum of the
+        sizes before it).  The pointer and size arrays are built on the device; no host synchronisation.  d_out: one
+        uint8 tensor holding item i's image at i * out_stride (allocated here unless given).
+        -> dict(out, out_stride, out_bytes int64[count], status int32[count], codes uint8[count, sizeof(Code)], in_ptrs,
+                in_bytes, out_ptrs, count, max_item_bytes)"""
+        t = self.torch
+        if d_codes is None:
+            count = len(items) if sizes is None else len(sizes)
+            d_codes = t.zeros((max(count, 1), C.sizeof(Code)), dtype=t.uint8, device=self.device)
+        r, (ip, ib, op, oc, ob, st) = self._compress_batch_io(items, sizes, max_item_bytes, 1, compress_batch_bound, d_out, out_stride,
+                                                              codes=d_codes)
+        self._call("ghf_compress_batch", ip, ib, r["max_item_bytes"], r["count"], op, oc, ob, d_codes.data_ptr(), _ref(index), st)
+        return r
+
+    def decode_batch(self, stream_ptrs, stream_bytes, d_codes, index, n_symbols, d_out=None, out_stride=None, out_ptrs=None,
+                     out_caps=None):
+        """stream_ptrs / stream_bytes / n_symbols: int64 CUDA tensors [count] (e.g. out_ptrs, out_bytes and in_bytes of
+        compress_batch).  Item i is decoded to d_out[i * out_stride ..) unless out_ptrs / out_caps (int64 CUDA tensors) say
+        otherwise.  -> dict(out, out_stride, out_bytes int64[count], status int32[count])"""
+        return self._decode_batch("ghf_decode_batch", stream_ptrs, stream_bytes, d_codes, index, n_symbols, (), 1, d_out, out_stride,
+                                  out_ptrs, out_caps)
+
+    def decode_images_batch(self, stream_ptrs, stream_bytes, out=None, caps=None, codes=False):
+        """Standalone .crs2 images and nothing else.  stream_ptrs / stream_bytes: int64 CUDA tensors [count].
+        out=None: the sizes pass -> dict(out_bytes int64[count], status int32[count]).
+        Otherwise the decode pass: `caps` (int64 CUDA tensor [count], e.g. the out_bytes of the sizes pass) says how much
+        room every item gets; out=True allocates one uint8 tensor with item i at i * out_stride, out_stride = the largest
+        cap rounded up to 16 (this reads `caps` back: one host synchronisation); a uint8 CUDA tensor is used as it is, cut
+        into count equal slots.  codes=True: also the items' tables, uint8[count, sizeof(Code)].
+        -> dict(out, out_stride, out_bytes, status[, codes])"""
+        t = self.torch
+        count = int(stream_bytes.numel())
+        res, (op, oc, ob, st) = self._two_pass("decode_images_batch", count, out, caps)
+        d_codes = None
+        if codes:
+            res["codes"] = d_codes = t.zeros((max(count, 1), C.sizeof(Code)), dtype=t.uint8, device=self.device)
+        self._call("ghf_decode_images_batch", stream_ptrs.data_ptr(), stream_bytes.data_ptr(), count, op, oc, ob, _addr(d_codes), st)
+        return res
+
+    # ---- shared-code batches: one code for the whole batch, an item's output is its body alone ----
+    def histogram_batch(self, items, sizes=None, max_item_bytes=None, flags=0, out=None):
+        """the byte counts of all items in one int64[257] CUDA tensor (slot 256 = 1), ready for build_code.  items / sizes
+        as in compress_batch; flags: HIST_COVER_ALL.  No host synchronisation."""
+        in_ptrs, in_bytes, count, max_item_bytes = self._batch_in(items, sizes, max_item_bytes)
+        hist = self.torch.empty(NSYM, dtype=self.torch.int64, device=self.device) if out is None else out
+        self._call("ghf_histogram_batch", in_ptrs.data_ptr(), in_bytes.data_ptr(), max_item_bytes, count, flags, hist.data_ptr())
+        return hist
+
+    def compress_batch_shared(self, items, d_code, sizes=None, max_item_bytes=None, d_out=None, out_stride=None, index=None):
+        """compress_batch under the one code `d_code` (e.g. build_code(histogram_batch(items))): item i's BODY goes to
+        d_out[i * out_stride ..).  -> dict(out, out_stride, out_bytes int64[count], status int32[count], code, in_ptrs,
+        in_bytes, out_ptrs, out_caps, count, max_item_bytes)"""
+        r, (ip, ib, op, oc, ob, st) = self._compress_batch_io(items, sizes, max_item_bytes, 1, compress_batch_shared_bound, d_out,
+                                                              out_stride, code=d_code)
+        self._call("ghf_compress_batch_shared", ip, ib, r["max_item_bytes"], r["count"], d_code.data_ptr(), op, oc, ob, _ref(index), st)
+        return r
+
+    def decode_batch_shared(self, stream_ptrs, stream_bytes, d_code, index, n_symbols, d_out=None, out_stride=None, out_ptrs=None,
+                            out_caps=None):
+        """decode_batch with one code for all items: stream_ptrs / stream_bytes are the bodies (e.g. out_ptrs and
+        out_bytes of compress_batch_shared).  -> dict(out, out_stride, out_bytes int64[count], status int32[count])"""
+        return self._decode_batch("ghf_decode_batch_shared", stream_ptrs, stream_bytes, d_code, index, n_symbols, (), 1, d_out,
+                                  out_stride, out_ptrs, out_caps)
+
+    def decode_bodies_batch_shared(self, stream_ptrs, stream_bytes, d_code, out=None, caps=None):
+        """Bodies under the one code `d_code` and nothing else: no side-car, no sizes.  stream_ptrs / stream_bytes: int64
+        CUDA tensors [count] (e.g. out_ptrs and out_bytes of compress_batch_shared, or stored bodies copied up).
+        out=None: the sizes pass -> dict(out_bytes int64[count], status int32[count]).
+        Otherwise the decode pass, with out / caps as in decode_images_batch -> dict(out, out_stride, out_bytes, status,
+        out_ptrs, out_caps)"""
+        return self._decode_bodies("ghf_decode_bodies_batch_shared", "decode_bodies_batch_shared", (stream_ptrs, stream_bytes, d_code),
+                                   int(stream_bytes.numel()), (), out, caps)
 
     def decode_images_batch_stats(self, d_stats):
         """d_stats: an int64 CUDA tensor [2] that later decode_images_batch and decode_bodies_batch_shared calls add
@@ -945,13 +930,10 @@ class Context:
     def histogram_batch_planes(self, items, elem_bytes, sizes=None, max_item_bytes=None, flags=0, out=None):
         """the byte counts of every byte plane of all items: an int64[elem_bytes, 257] CUDA tensor, ready for build_codes.
         items / sizes (in bytes) as in compress_batch; flags: HIST_COVER_ALL.  No host synchronisation."""
-        ptrs, sizes = self._item_arrays(items, sizes)
-        if max_item_bytes is None:
-            max_item_bytes = -(-max(max(sizes, default=1), 1) // elem_bytes) * elem_bytes
+        in_ptrs, in_bytes, count, max_item_bytes = self._batch_in(items, sizes, max_item_bytes, elem_bytes)
         hists = self.torch.empty((elem_bytes, NSYM), dtype=self.torch.int64, device=self.device) if out is None else out
-        in_ptrs, in_bytes = self._i64(ptrs), self._i64(sizes)
-        self._chk(self.L.ghf_histogram_batch_planes(self.h, in_ptrs.data_ptr(), in_bytes.data_ptr(), max_item_bytes, len(sizes),
-                                                    elem_bytes, flags, hists.data_ptr()), "ghf_histogram_batch_planes")
+        self._call("ghf_histogram_batch_planes", in_ptrs.data_ptr(), in_bytes.data_ptr(), max_item_bytes, count, elem_bytes, flags,
+                   hists.data_ptr())
         return hists
 
     def build_codes(self, d_hists, d_codes=None, flags=0):
@@ -969,106 +951,30 @@ class Context:
         -> dict(out, out_stride, out_bytes int64[slots], status int32[slots], codes, in_ptrs, in_bytes, out_ptrs, out_caps,
                 count, elem_bytes, max_item_bytes, n_elems int64[count])
         raw_planes (None: this call; an int: ghf_compress_batch_planes_forms, see compress_batch_planes_forms)"""
-        t = self.torch
-        ptrs, sizes = self._item_arrays(items, sizes)
-        count = len(sizes)
-        slots = count * elem_bytes
-        if max_item_bytes is None:
-            max_item_bytes = -(-max(max(sizes, default=1), 1) // elem_bytes) * elem_bytes
-        if out_stride is None:
-            out_stride = compress_batch_planes_shared_bound(max_item_bytes, elem_bytes)
-        if d_out is None:
-            d_out = t.empty(max(slots * out_stride, 16), dtype=t.uint8, device=self.device)
-        in_ptrs, in_bytes = self._i64(ptrs), self._i64(sizes)
-        out_ptrs = d_out.data_ptr() + t.arange(slots, dtype=t.int64, device=self.device) * out_stride
-        out_caps = t.full((max(slots, 1),), out_stride, dtype=t.int64, device=self.device)
-        out_bytes = t.zeros(max(slots, 1), dtype=t.int64, device=self.device)
-        status = t.full((max(slots, 1),), -1, dtype=t.int32, device=self.device)
-        ix = None if index is None else C.byref(index)
-        if raw_planes is None:
-            self._chk(
-                self.L.ghf_compress_batch_planes_shared(self.h, in_ptrs.data_ptr(), in_bytes.data_ptr(), max_item_bytes, count, elem_bytes,
-                                                        d_codes.data_ptr(), out_ptrs.data_ptr(), out_caps.data_ptr(), out_bytes.data_ptr(),
-                                                        ix, status.data_ptr()),
-                "ghf_compress_batch_planes_shared")
-        else:
-            self._chk(
-                self.L.ghf_compress_batch_planes_forms(self.h, in_ptrs.data_ptr(), in_bytes.data_ptr(), max_item_bytes, count, elem_bytes,
-                                                       d_codes.data_ptr(), raw_planes, out_ptrs.data_ptr(), out_caps.data_ptr(),
-                                                       out_bytes.data_ptr(), ix, status.data_ptr()),
-                "ghf_compress_batch_planes_forms")
-        return {"out": d_out, "out_stride": out_stride, "out_bytes": out_bytes[:slots], "status": status[:slots], "codes": d_codes,
-                "in_ptrs": in_ptrs, "in_bytes": in_bytes, "out_ptrs": out_ptrs, "out_caps": out_caps, "count": count,
-                "elem_bytes": elem_bytes, "max_item_bytes": max_item_bytes, "n_elems": in_bytes // elem_bytes, "keep": items}
-
-    def _planes_out(self, count, out_stride, d_out):
-        t = self.torch
-        if d_out is None:
-            d_out = t.empty(max(count * out_stride, 16), dtype=t.uint8, device=self.device)
-        out_ptrs = d_out.data_ptr() + t.arange(count, dtype=t.int64, device=self.device) * out_stride
-        return d_out, out_ptrs, t.full((max(count, 1),), out_stride, dtype=t.int64, device=self.device)
+        r, (ip, ib, op, oc, ob, st) = self._compress_batch_io(items, sizes, max_item_bytes, elem_bytes,
+                                                              lambda m: compress_batch_planes_shared_bound(m, elem_bytes), d_out,
+                                                              out_stride, codes=d_codes)
+        name, raw = _entry("ghf_compress_batch_planes_shared", "ghf_compress_batch_planes_forms", raw_planes)
+        self._call(name, ip, ib, r["max_item_bytes"], r["count"], elem_bytes, d_codes.data_ptr(), *raw, op, oc, ob, _ref(index), st)
+        r.update(elem_bytes=elem_bytes, n_elems=r["in_bytes"] // elem_bytes)
+        return r
 
     def decode_batch_planes_shared(self, stream_ptrs, stream_bytes, d_codes, index, n_elems, elem_bytes, d_out=None, out_stride=None,
                                    out_ptrs=None, out_caps=None, raw_planes=None):
         """the way back with the live side-car: stream_ptrs / stream_bytes int64[count * elem_bytes] (out_ptrs and out_bytes
         of compress_batch_planes_shared), n_elems int64[count].  Item i is decoded to d_out[i * out_stride ..) unless
         out_ptrs / out_caps (bytes) say otherwise.  -> dict(out, out_stride, out_bytes int64[count], status int32[count])"""
-        t = self.torch
-        count = int(n_elems.numel())
-        if out_ptrs is None:
-            if out_stride is None:
-                out_stride = (int(index.max_item_bytes) * elem_bytes + 15) & ~15
-            d_out, out_ptrs, out_caps = self._planes_out(count, out_stride, d_out)
-        out_bytes = t.zeros(max(count, 1), dtype=t.int64, device=self.device)
-        status = t.full((max(count, 1),), -1, dtype=t.int32, device=self.device)
-        if raw_planes is None:
-            self._chk(
-                self.L.ghf_decode_batch_planes_shared(self.h, stream_ptrs.data_ptr(), stream_bytes.data_ptr(), d_codes.data_ptr(),
-                                                      C.byref(index), n_elems.data_ptr(), count, elem_bytes, out_ptrs.data_ptr(),
-                                                      out_caps.data_ptr(), out_bytes.data_ptr(), status.data_ptr()),
-                "ghf_decode_batch_planes_shared")
-        else:
-            self._chk(
-                self.L.ghf_decode_batch_planes_forms(self.h, stream_ptrs.data_ptr(), stream_bytes.data_ptr(), d_codes.data_ptr(),
-                                                     C.byref(index), n_elems.data_ptr(), count, elem_bytes, raw_planes, out_ptrs.data_ptr(),
-                                                     out_caps.data_ptr(), out_bytes.data_ptr(), status.data_ptr()),
-                "ghf_decode_batch_planes_forms")
-        return {"out": d_out, "out_stride": out_stride, "out_bytes": out_bytes[:count], "status": status[:count],
-                "out_ptrs": out_ptrs, "out_caps": out_caps}
+        name, raw = _entry("ghf_decode_batch_planes_shared", "ghf_decode_batch_planes_forms", raw_planes)
+        return self._decode_batch(name, stream_ptrs, stream_bytes, d_codes, index, n_elems, (elem_bytes,) + raw, elem_bytes, d_out,
+                                  out_stride, out_ptrs, out_caps)
 
     def decode_bodies_batch_planes_shared(self, stream_ptrs, stream_bytes, d_codes, elem_bytes, out=None, caps=None, raw_planes=None):
         """the way back from nothing but the bytes: stream_ptrs / stream_bytes int64[count * elem_bytes].
         out=None: the sizes pass -> dict(out_bytes int64[count] (bytes), status int32[count]).
         Otherwise the decode pass, with out / caps (bytes per item) as in decode_images_batch."""
-        t = self.torch
-        count = int(stream_bytes.numel()) // elem_bytes
-        out_bytes = t.zeros(max(count, 1), dtype=t.int64, device=self.device)
-        status = t.full((max(count, 1),), -1, dtype=t.int32, device=self.device)
-        res = {"out_bytes": out_bytes[:count], "status": status[:count]}
-        out_ptrs = out_caps = None
-        if out is not None:
-            if caps is None:
-                raise ValueError("decode_bodies_batch_planes_shared: the decode pass needs caps (e.g. the out_bytes of the sizes pass)")
-            if out is True:
-                out_stride = (int(caps.max().item()) + 15) & ~15 if count else 16
-                out = t.empty(max(count * out_stride, 16), dtype=t.uint8, device=self.device)
-            else:
-                out_stride = int(out.numel()) // max(count, 1)
-            out_ptrs = out.data_ptr() + t.arange(count, dtype=t.int64, device=self.device) * out_stride
-            out_caps = t.clamp(caps.to(t.int64), max=out_stride).contiguous()
-            res.update(out=out, out_stride=out_stride, out_ptrs=out_ptrs, out_caps=out_caps)
-        op, oc = None if out_ptrs is None else out_ptrs.data_ptr(), None if out_caps is None else out_caps.data_ptr()
-        if raw_planes is None:
-            self._chk(
-                self.L.ghf_decode_bodies_batch_planes_shared(self.h, stream_ptrs.data_ptr(), stream_bytes.data_ptr(), d_codes.data_ptr(),
-                                                             count, elem_bytes, op, oc, out_bytes.data_ptr(), status.data_ptr()),
-                "ghf_decode_bodies_batch_planes_shared")
-        else:
-            self._chk(
-                self.L.ghf_decode_bodies_batch_planes_forms(self.h, stream_ptrs.data_ptr(), stream_bytes.data_ptr(), d_codes.data_ptr(),
-                                                            count, elem_bytes, raw_planes, op, oc, out_bytes.data_ptr(), status.data_ptr()),
-                "ghf_decode_bodies_batch_planes_forms")
-        return res
+        name, raw = _entry("ghf_decode_bodies_batch_planes_shared", "ghf_decode_bodies_batch_planes_forms", raw_planes)
+        return self._decode_bodies(name, "decode_bodies_batch_planes_shared", (stream_ptrs, stream_bytes, d_codes),
+                                   int(stream_bytes.numel()) // elem_bytes, (elem_bytes,) + raw, out, caps)
 
     # ---- stored shared-code bodies: one run record per body, the persistent form of a slice of a BatchIndex ----
     def batch_seek_pack(self, index, in_bytes, elem_bytes=1, d_rec=None, rec_stride=None):
@@ -1076,84 +982,31 @@ class Context:
         record per body, slot j at d_rec[j * rec_stride ..).  in_bytes: int64[count], the items' sizes in bytes (the
         in_bytes of the compress call).  -> dict(rec, rec_stride, rec_ptrs, rec_caps, rec_bytes int64[slots], status
         int32[slots])"""
-        t = self.torch
         count = int(in_bytes.numel())
         slots = count * elem_bytes
         if rec_stride is None:
             rec_stride = batch_seek_bound(int(index.max_item_bytes))
-        if d_rec is None:
-            d_rec = t.empty(max(slots * rec_stride, 16), dtype=t.uint8, device=self.device)
-        rec_ptrs = d_rec.data_ptr() + t.arange(slots, dtype=t.int64, device=self.device) * rec_stride
-        rec_caps = t.full((max(slots, 1),), rec_stride, dtype=t.int64, device=self.device)
-        rec_bytes = t.zeros(max(slots, 1), dtype=t.int64, device=self.device)
-        status = t.full((max(slots, 1),), -1, dtype=t.int32, device=self.device)
-        self._chk(
-            self.L.ghf_batch_seek_pack(self.h, C.byref(index), in_bytes.data_ptr(), count, elem_bytes, rec_ptrs.data_ptr(),
-                                       rec_caps.data_ptr(), rec_bytes.data_ptr(), status.data_ptr()),
-            "ghf_batch_seek_pack")
+        d_rec, rec_ptrs, rec_caps = self._planes_out(slots, rec_stride, d_rec)
+        rec_bytes, status = self._item_status(slots)
+        self._call("ghf_batch_seek_pack", C.byref(index), in_bytes.data_ptr(), count, elem_bytes, rec_ptrs.data_ptr(),
+                   rec_caps.data_ptr(), rec_bytes.data_ptr(), status.data_ptr())
         return {"rec": d_rec, "rec_stride": rec_stride, "rec_ptrs": rec_ptrs, "rec_caps": rec_caps, "rec_bytes": rec_bytes[:slots],
                 "status": status[:slots]}
-
-    def _seek_out(self, count, out, caps, who):
-        t = self.torch
-        if out is None:
-            return None, None, {}
-        if caps is None:
-            raise ValueError(who + ": the decode pass needs caps (e.g. the out_bytes of the sizes pass)")
-        if out is True:
-            out_stride = (int(caps.max().item()) + 15) & ~15 if count else 16
-            out = t.empty(max(count * out_stride, 16), dtype=t.uint8, device=self.device)
-        else:
-            out_stride = int(out.numel()) // max(count, 1)
-        out_ptrs = out.data_ptr() + t.arange(count, dtype=t.int64, device=self.device) * out_stride
-        out_caps = t.clamp(caps.to(t.int64), max=out_stride).contiguous()
-        return out_ptrs, out_caps, dict(out=out, out_stride=out_stride, out_ptrs=out_ptrs, out_caps=out_caps)
 
     def decode_bodies_batch_shared_seek(self, stream_ptrs, stream_bytes, rec_ptrs, rec_bytes, d_code, out=None, caps=None):
         """Stored bodies under the one code `d_code`, each with its run record: int64 CUDA tensors [count] of pointers and
         sizes.  out=None: the sizes pass (the records' shapes are checked, the streams are not read) -> dict(out_bytes,
         status).  Otherwise the decode pass, with out / caps as in decode_bodies_batch_shared."""
-        t = self.torch
-        count = int(stream_bytes.numel())
-        out_bytes = t.zeros(max(count, 1), dtype=t.int64, device=self.device)
-        status = t.full((max(count, 1),), -1, dtype=t.int32, device=self.device)
-        res = {"out_bytes": out_bytes[:count], "status": status[:count]}
-        out_ptrs, out_caps, more = self._seek_out(count, out, caps, "decode_bodies_batch_shared_seek")
-        res.update(more)
-        self._chk(
-            self.L.ghf_decode_bodies_batch_shared_seek(self.h, stream_ptrs.data_ptr(), stream_bytes.data_ptr(), rec_ptrs.data_ptr(),
-                                                       rec_bytes.data_ptr(), d_code.data_ptr(), count,
-                                                       None if out_ptrs is None else out_ptrs.data_ptr(),
-                                                       None if out_caps is None else out_caps.data_ptr(), out_bytes.data_ptr(),
-                                                       status.data_ptr()),
-            "ghf_decode_bodies_batch_shared_seek")
-        return res
+        return self._decode_bodies("ghf_decode_bodies_batch_shared_seek", "decode_bodies_batch_shared_seek",
+                                   (stream_ptrs, stream_bytes, rec_ptrs, rec_bytes, d_code), int(stream_bytes.numel()), (), out, caps)
 
     def decode_bodies_batch_planes_shared_seek(self, stream_ptrs, stream_bytes, rec_ptrs, rec_bytes, d_codes, elem_bytes, out=None,
                                                caps=None, raw_planes=None):
         """the same for the slots of compress_batch_planes_shared: stream_* / rec_* int64[count * elem_bytes]; out / caps
         (bytes per item) as in decode_bodies_batch_planes_shared."""
-        t = self.torch
-        count = int(stream_bytes.numel()) // elem_bytes
-        out_bytes = t.zeros(max(count, 1), dtype=t.int64, device=self.device)
-        status = t.full((max(count, 1),), -1, dtype=t.int32, device=self.device)
-        res = {"out_bytes": out_bytes[:count], "status": status[:count]}
-        out_ptrs, out_caps, more = self._seek_out(count, out, caps, "decode_bodies_batch_planes_shared_seek")
-        res.update(more)
-        op, oc = None if out_ptrs is None else out_ptrs.data_ptr(), None if out_caps is None else out_caps.data_ptr()
-        if raw_planes is None:
-            self._chk(
-                self.L.ghf_decode_bodies_batch_planes_shared_seek(self.h, stream_ptrs.data_ptr(), stream_bytes.data_ptr(),
-                                                                  rec_ptrs.data_ptr(), rec_bytes.data_ptr(), d_codes.data_ptr(), count,
-                                                                  elem_bytes, op, oc, out_bytes.data_ptr(), status.data_ptr()),
-                "ghf_decode_bodies_batch_planes_shared_seek")
-        else:
-            self._chk(
-                self.L.ghf_decode_bodies_batch_planes_forms_seek(self.h, stream_ptrs.data_ptr(), stream_bytes.data_ptr(),
-                                                                 rec_ptrs.data_ptr(), rec_bytes.data_ptr(), d_codes.data_ptr(), count,
-                                                                 elem_bytes, raw_planes, op, oc, out_bytes.data_ptr(), status.data_ptr()),
-                "ghf_decode_bodies_batch_planes_forms_seek")
-        return res
+        name, raw = _entry("ghf_decode_bodies_batch_planes_shared_seek", "ghf_decode_bodies_batch_planes_forms_seek", raw_planes)
+        return self._decode_bodies(name, "decode_bodies_batch_planes_shared_seek", (stream_ptrs, stream_bytes, rec_ptrs, rec_bytes, d_codes),
+                                   int(stream_bytes.numel()) // elem_bytes, (elem_bytes,) + raw, out, caps)
 
     # ---- the plane batch calls with raw planes: raw_planes is one int for the batch, bit p = plane p stored as it is ----
     def batch_planes_raw_auto(self, d_hists, d_codes, out=None):
@@ -1191,26 +1044,114 @@ class Context:
                                                            caps=caps, raw_planes=int(raw_planes))
 
     # ---- byte planes: elements of 2, 4 or 8 bytes, one ordinary .crs2 image per byte position ---------
+    # Every call here has a twin against a base tensor (further down).  Both go through one private method that takes the C
+    # entry point's name and `base`: () for the plain call, (address or NULL,) for the twin, spliced where the twin takes it --
+    # a twin called without a base still reaches ITS entry point, which refuses it.
     planes_slot_bytes = staticmethod(planes_slot_bytes)
 
-    def planes_split(self, d_in, elem_bytes, n_elems=None, d_planes=None, plane_stride=None):
-        """byte b of element k of d_in -> d_planes[b * plane_stride + k].  -> (d_planes uint8, plane_stride)"""
-        n_elems = d_in.numel() * d_in.element_size() // elem_bytes if n_elems is None else n_elems
+    def _planes_split(self, name, d_in, base, elem_bytes, n_elems, d_planes, plane_stride):
+        n_elems = _n_elems(d_in, elem_bytes, n_elems)
         if plane_stride is None:
             plane_stride = (n_elems + 255) & ~255
         if d_planes is None:
             d_planes = self.empty_u8(plane_stride * elem_bytes)
-        self._chk(self.L.ghf_planes_split(self.h, d_in.data_ptr(), n_elems, elem_bytes, d_planes.data_ptr(), plane_stride),
-                  "ghf_planes_split")
+        self._call(name, d_in.data_ptr(), *base, n_elems, elem_bytes, d_planes.data_ptr(), plane_stride)
         return d_planes, plane_stride
+
+    def _planes_merge(self, name, d_planes, plane_stride, base, which, n, elem_bytes, d_out):
+        """which: (n_elems,) of a whole merge or (first, count) of a range; n: the elements d_out gets"""
+        if d_out is None:
+            d_out = self.empty_u8(n * elem_bytes)
+        self._call(name, d_planes.data_ptr(), plane_stride, *base, *which, elem_bytes, d_out.data_ptr())
+        return d_out
+
+    def _histogram_planes(self, name, d_in, base, elem_bytes, n_elems, flags, out):
+        hists = self.torch.empty((elem_bytes, NSYM), dtype=self.torch.int64, device=self.device) if out is None else out
+        self._call(name, d_in.data_ptr(), *base, _n_elems(d_in, elem_bytes, n_elems), elem_bytes, flags, hists.data_ptr())
+        return hists
+
+    def _compress_planes_out(self, d_in, elem_bytes, slots, n_elems, d_out, slot_bytes, d_codes, out_bytes=None):
+        """the outputs of a planes compress call over `slots` slots, each allocated unless given -> its result dict"""
+        t = self.torch
+        n_elems = _n_elems(d_in, elem_bytes, n_elems)
+        if slot_bytes is None:
+            slot_bytes = planes_slot_bytes(n_elems)
+        if d_out is None:
+            d_out = self.empty_u8(slot_bytes * slots)
+        if d_codes is None:
+            d_codes = t.zeros((slots, C.sizeof(Code)), dtype=t.uint8, device=self.device)
+        if out_bytes is None:
+            out_bytes = t.zeros(slots, dtype=t.int64, device=self.device)
+        return {"out": d_out, "slot_bytes": slot_bytes, "out_bytes": out_bytes, "codes": d_codes, "n_elems": n_elems,
+                "elem_bytes": elem_bytes}
+
+    def _compress_planes_coded(self, name, d_in, base, elem_bytes, d_codes, flags, n_elems, d_out, slot_bytes, indexes):
+        if flags is None:
+            flags = PLANES_BUILD_CODES if d_codes is None else 0
+        r = self._compress_planes_out(d_in, elem_bytes, elem_bytes, n_elems, d_out, slot_bytes, d_codes)
+        self._call(name, d_in.data_ptr(), *base, r["n_elems"], elem_bytes, r["codes"].data_ptr(), flags, r["out"].data_ptr(),
+                   r["slot_bytes"], r["out_bytes"].data_ptr(), indexes)
+        return r
+
+    def _range_out(self, d_out, n_bytes, cap):
+        """(d_out, cap) of a decode: d_out of n_bytes unless given, cap all of d_out unless given"""
+        if d_out is None:
+            d_out = self.empty_u8(n_bytes)
+        return d_out, d_out.numel() if cap is None else cap
+
+    def _decode_planes(self, name, streams, stream_bytes, slots, d_codes, indexes, more, n_elems, elem_bytes, d_out, cap, nbytes):
+        """the whole-tensor plane decodes over `slots` streams; `more`: what the entry point takes between the side-cars and
+        n_elems.  -> (d_out uint8, nbytes int64[1] device)"""
+        d_out, cap = self._range_out(d_out, n_elems * elem_bytes, cap)
+        if nbytes is None:
+            nbytes = self.torch.zeros(1, dtype=self.torch.int64, device=self.device)
+        self._call(name, _ptr_array(streams, slots), _size_array(stream_bytes, slots), _addr(d_codes), indexes, *more, n_elems,
+                   elem_bytes, d_out.data_ptr(), cap, nbytes.data_ptr())
+        return d_out, nbytes
+
+    def _decode_planes_range(self, name, streams, stream_bytes, slots, d_codes, indexes, infos, d_tables, table_bytes, more, elem_bytes,
+                             first, count, d_out, cap):
+        """the range plane decodes over `slots` streams; `more`: what the entry point takes between the seek tables and
+        elem_bytes.  -> d_out"""
+        d_out, cap = self._range_out(d_out, count * elem_bytes, cap)
+        self._call(name, _ptr_array(streams, slots), _size_array(stream_bytes, slots), _addr(d_codes), indexes,
+                   *_seek_tables(infos, d_tables, table_bytes, slots), *more, elem_bytes, first, count, d_out.data_ptr(), cap)
+        return d_out
+
+    def _decode_planes_ranked_range(self, name, streams, stream_bytes, d_codes, ranks, more, n_elems, elem_bytes, first, count, indexes,
+                                    infos, d_tables, table_bytes, d_out, cap):
+        """the range decodes of 2 * elem_bytes slots with rank tables in HOST memory; `more`: what the entry point takes between
+        the rank tables and n_elems"""
+        r_infos, r_ptrs, _, keep = _rank_arrays(ranks, elem_bytes, device=False)
+        d_out = self._decode_planes_range(name, streams, stream_bytes, 2 * elem_bytes, d_codes, indexes, infos, d_tables, table_bytes,
+                                          (r_infos, r_ptrs) + more + (n_elems,), elem_bytes, first, count, d_out, cap)
+        del keep  # the tables r_ptrs points into had to live until here
+        return d_out
+
+    def _decode_planes_gather(self, name, streams, stream_bytes, slots, d_codes, infos, d_tables, table_bytes, more, n_elems, elem_bytes,
+                              d_index, row_elems, index_stride, n_rows, d_out, out_stride, d_row_status):
+        """the row gathers over `slots` streams; `more`: what the entry point takes between the seek tables and n_elems.
+        -> (d_out, d_row_status)"""
+        t = self.torch
+        n_rows = d_index.numel() if n_rows is None else n_rows
+        index_stride = row_elems if index_stride is None else index_stride
+        out_stride = row_elems * elem_bytes if out_stride is None else out_stride
+        if d_out is None:
+            d_out = self.empty_u8(max(n_rows, 1) * out_stride)
+        if d_row_status is None:
+            d_row_status = t.zeros(max(n_rows, 1), dtype=t.int32, device=self.device)
+        self._call(name, _ptr_array(streams, slots), _size_array(stream_bytes, slots), _addr(d_codes),
+                   *_seek_tables(infos, d_tables, table_bytes, slots), *more, n_elems, elem_bytes, d_index.data_ptr(), index_stride,
+                   row_elems, n_rows, d_out.data_ptr(), out_stride, d_row_status.data_ptr())
+        return d_out, d_row_status
+
+    def planes_split(self, d_in, elem_bytes, n_elems=None, d_planes=None, plane_stride=None):
+        """byte b of element k of d_in -> d_planes[b * plane_stride + k].  -> (d_planes uint8, plane_stride)"""
+        return self._planes_split("ghf_planes_split", d_in, (), elem_bytes, n_elems, d_planes, plane_stride)
 
     def planes_merge(self, d_planes, plane_stride, n_elems, elem_bytes, d_out=None):
         """the inverse of planes_split.  -> d_out uint8[n_elems * elem_bytes]"""
-        if d_out is None:
-            d_out = self.empty_u8(n_elems * elem_bytes)
-        self._chk(self.L.ghf_planes_merge(self.h, d_planes.data_ptr(), plane_stride, n_elems, elem_bytes, d_out.data_ptr()),
-                  "ghf_planes_merge")
-        return d_out
+        return self._planes_merge("ghf_planes_merge", d_planes, plane_stride, (), (n_elems,), n_elems, elem_bytes, d_out)
 
     def planes_index_alloc(self, n_elems, elem_bytes):
         """elem_bytes side-cars of n_elems symbols as the ctypes array compress_planes / decode_planes take"""
@@ -1227,30 +1168,15 @@ class Context:
         """d_in: a CUDA tensor of elements (any dtype; elem_bytes says how wide an element is).  Plane p's .crs2 image goes to
         d_out[p * slot_bytes ..); no host synchronisation.  indexes: None or planes_index_alloc(n_elems, elem_bytes).
         -> dict(out, slot_bytes, out_bytes int64[elem_bytes], codes uint8[elem_bytes, sizeof(Code)], n_elems, elem_bytes)"""
-        t = self.torch
-        n_elems = d_in.numel() * d_in.element_size() // elem_bytes if n_elems is None else n_elems
-        if slot_bytes is None:
-            slot_bytes = planes_slot_bytes(n_elems)
-        if d_out is None:
-            d_out = self.empty_u8(slot_bytes * elem_bytes)
-        if d_codes is None:
-            d_codes = t.zeros((elem_bytes, C.sizeof(Code)), dtype=t.uint8, device=self.device)
-        out_bytes = t.zeros(elem_bytes, dtype=t.int64, device=self.device)
-        self._chk(
-            self.L.ghf_compress_planes(self.h, d_in.data_ptr(), n_elems, elem_bytes, d_out.data_ptr(), slot_bytes,
-                                       out_bytes.data_ptr(), d_codes.data_ptr(), indexes),
-            "ghf_compress_planes")
-        return {"out": d_out, "slot_bytes": slot_bytes, "out_bytes": out_bytes, "codes": d_codes, "n_elems": n_elems,
-                "elem_bytes": elem_bytes}
+        r = self._compress_planes_out(d_in, elem_bytes, elem_bytes, n_elems, d_out, slot_bytes, d_codes)
+        self._call("ghf_compress_planes", d_in.data_ptr(), r["n_elems"], elem_bytes, r["out"].data_ptr(), r["slot_bytes"],
+                   r["out_bytes"].data_ptr(), r["codes"].data_ptr(), indexes)
+        return r
 
     def histogram_planes(self, d_in, elem_bytes, n_elems=None, flags=0, out=None):
         """the byte counts of every byte plane of one tensor, in one pass: an int64[elem_bytes, 257] CUDA tensor, ready for
         build_codes.  flags: HIST_COVER_ALL.  No host synchronisation."""
-        n_elems = d_in.numel() * d_in.element_size() // elem_bytes if n_elems is None else n_elems
-        hists = self.torch.empty((elem_bytes, NSYM), dtype=self.torch.int64, device=self.device) if out is None else out
-        self._chk(self.L.ghf_histogram_planes(self.h, d_in.data_ptr(), n_elems, elem_bytes, flags, hists.data_ptr()),
-                  "ghf_histogram_planes")
-        return hists
+        return self._histogram_planes("ghf_histogram_planes", d_in, (), elem_bytes, n_elems, flags, out)
 
     def planes_image_bytes(self, d_hists, d_codes, elem_bytes, out=None):
         """what planes with the counts d_hists (int64[elem_bytes, 257]) compress to under d_codes: int64[elem_bytes], 0 for
@@ -1265,171 +1191,69 @@ class Context:
         """compress_planes with one histogram pass and the codes either built in one launch (d_codes None or flags
         PLANES_BUILD_CODES: they are returned) or brought by the caller (d_codes uint8[elem_bytes, sizeof(Code)], flags 0).
         No host synchronisation.  -> the dict of compress_planes"""
-        t = self.torch
-        n_elems = d_in.numel() * d_in.element_size() // elem_bytes if n_elems is None else n_elems
-        if flags is None:
-            flags = PLANES_BUILD_CODES if d_codes is None else 0
-        if slot_bytes is None:
-            slot_bytes = planes_slot_bytes(n_elems)
-        if d_out is None:
-            d_out = self.empty_u8(slot_bytes * elem_bytes)
-        if d_codes is None:
-            d_codes = t.zeros((elem_bytes, C.sizeof(Code)), dtype=t.uint8, device=self.device)
-        out_bytes = t.zeros(elem_bytes, dtype=t.int64, device=self.device)
-        self._chk(
-            self.L.ghf_compress_planes_coded(self.h, d_in.data_ptr(), n_elems, elem_bytes, d_codes.data_ptr(), flags,
-                                             d_out.data_ptr(), slot_bytes, out_bytes.data_ptr(), indexes),
-            "ghf_compress_planes_coded")
-        return {"out": d_out, "slot_bytes": slot_bytes, "out_bytes": out_bytes, "codes": d_codes, "n_elems": n_elems,
-                "elem_bytes": elem_bytes}
+        return self._compress_planes_coded("ghf_compress_planes_coded", d_in, (), elem_bytes, d_codes, flags, n_elems, d_out, slot_bytes,
+                                           indexes)
 
     def decode_planes(self, streams, stream_bytes, d_codes, n_elems, elem_bytes, indexes=None, d_out=None, cap=None, nbytes=None):
         """streams: elem_bytes CUDA uint8 tensors (e.g. the slots of compress_planes), stream_bytes: their sizes as host
         ints.  indexes=None: the side-car-less path (synchronises).  -> (d_out uint8, nbytes int64[1] device)"""
-        ptrs = (C.c_void_p * elem_bytes)(*[x.data_ptr() for x in streams])
-        sizes = (C.c_size_t * elem_bytes)(*[int(v) for v in stream_bytes])
-        if d_out is None:
-            d_out = self.empty_u8(n_elems * elem_bytes)
-        if nbytes is None:
-            nbytes = self.torch.zeros(1, dtype=self.torch.int64, device=self.device)
-        self._chk(
-            self.L.ghf_decode_planes(self.h, ptrs, sizes, d_codes.data_ptr(), indexes, n_elems, elem_bytes, d_out.data_ptr(),
-                                     d_out.numel() if cap is None else cap, nbytes.data_ptr()),
-            "ghf_decode_planes")
-        return d_out, nbytes
+        return self._decode_planes("ghf_decode_planes", streams, stream_bytes, elem_bytes, d_codes, indexes, (), n_elems, elem_bytes,
+                                   d_out, cap, nbytes)
 
     def planes_merge_range(self, d_planes, plane_stride, first, count, elem_bytes, d_out=None):
         """elements [first, first + count) of the planes, interleaved.  -> d_out uint8[count * elem_bytes]"""
-        if d_out is None:
-            d_out = self.empty_u8(count * elem_bytes)
-        self._chk(self.L.ghf_planes_merge_range(self.h, d_planes.data_ptr(), plane_stride, first, count, elem_bytes,
-                                                d_out.data_ptr()), "ghf_planes_merge_range")
-        return d_out
+        return self._planes_merge("ghf_planes_merge_range", d_planes, plane_stride, (), (first, count), count, elem_bytes, d_out)
 
     def decode_planes_range(self, streams, stream_bytes, d_codes, elem_bytes, first, count, indexes=None, infos=None,
                             d_tables=None, table_bytes=None, d_out=None, cap=None):
         """d_out[0 .. count * elem_bytes) = elements [first, first + count) of the planes' decoded elements.  streams,
         stream_bytes, d_codes as for decode_planes; give either indexes (planes_index_alloc) or infos (elem_bytes SeekInfo)
         with d_tables (elem_bytes CUDA uint8 tensors).  Never synchronises.  -> d_out uint8"""
-        ptrs = (C.c_void_p * elem_bytes)(*[x.data_ptr() for x in streams])
-        sizes = (C.c_size_t * elem_bytes)(*[int(v) for v in stream_bytes])
-        h_infos = t_ptrs = t_bytes = None
-        if infos is not None:
-            h_infos = (SeekInfo * elem_bytes)(*infos)
-            t_ptrs = (C.c_void_p * elem_bytes)(*[x.data_ptr() for x in d_tables])
-            if table_bytes is None:
-                table_bytes = [seek_bytes(i.n_symbols) for i in infos]
-            t_bytes = (C.c_size_t * elem_bytes)(*[int(v) for v in table_bytes])
-        if d_out is None:
-            d_out = self.empty_u8(count * elem_bytes)
-        self._chk(
-            self.L.ghf_decode_planes_range(self.h, ptrs, sizes, d_codes.data_ptr(), indexes, h_infos, t_ptrs, t_bytes, elem_bytes,
-                                           first, count, d_out.data_ptr(), d_out.numel() if cap is None else cap),
-            "ghf_decode_planes_range")
-        return d_out
+        return self._decode_planes_range("ghf_decode_planes_range", streams, stream_bytes, elem_bytes, d_codes, indexes, infos, d_tables,
+                                         table_bytes, (), elem_bytes, first, count, d_out, cap)
 
     # ---- byte planes against a base tensor (DESIGN.md section 19): the calls above on d_in ^ d_base, the XOR inside their
     # streaming kernels.  d_base: a CUDA tensor of the same bytes as d_in / d_out (the range calls: of the range's own
     # elements); it may be d_out itself in the merging calls ----------------------------------------------------------
-    @staticmethod
-    def _base_ptr(d_base):
-        return None if d_base is None else d_base.data_ptr()
-
     def histogram_planes_delta(self, d_in, d_base, elem_bytes, n_elems=None, flags=0, out=None):
         """histogram_planes of d_in ^ d_base in one pass over both; nothing is materialised.  -> int64[elem_bytes, 257]"""
-        n_elems = d_in.numel() * d_in.element_size() // elem_bytes if n_elems is None else n_elems
-        hists = self.torch.empty((elem_bytes, NSYM), dtype=self.torch.int64, device=self.device) if out is None else out
-        self._chk(self.L.ghf_histogram_planes_delta(self.h, d_in.data_ptr(), self._base_ptr(d_base), n_elems, elem_bytes, flags,
-                                                    hists.data_ptr()), "ghf_histogram_planes_delta")
-        return hists
+        return self._histogram_planes("ghf_histogram_planes_delta", d_in, (_addr(d_base),), elem_bytes, n_elems, flags, out)
 
     def planes_split_delta(self, d_in, d_base, elem_bytes, n_elems=None, d_planes=None, plane_stride=None):
         """planes_split of d_in ^ d_base.  -> (d_planes uint8, plane_stride)"""
-        n_elems = d_in.numel() * d_in.element_size() // elem_bytes if n_elems is None else n_elems
-        if plane_stride is None:
-            plane_stride = (n_elems + 255) & ~255
-        if d_planes is None:
-            d_planes = self.empty_u8(plane_stride * elem_bytes)
-        self._chk(self.L.ghf_planes_split_delta(self.h, d_in.data_ptr(), self._base_ptr(d_base), n_elems, elem_bytes,
-                                                d_planes.data_ptr(), plane_stride), "ghf_planes_split_delta")
-        return d_planes, plane_stride
+        return self._planes_split("ghf_planes_split_delta", d_in, (_addr(d_base),), elem_bytes, n_elems, d_planes, plane_stride)
 
     def planes_merge_delta(self, d_planes, plane_stride, d_base, n_elems, elem_bytes, d_out=None):
         """d_out = planes_merge(d_planes) ^ d_base; d_out may be d_base.  -> d_out uint8[n_elems * elem_bytes]"""
-        if d_out is None:
-            d_out = self.empty_u8(n_elems * elem_bytes)
-        self._chk(self.L.ghf_planes_merge_delta(self.h, d_planes.data_ptr(), plane_stride, self._base_ptr(d_base), n_elems, elem_bytes,
-                                                d_out.data_ptr()), "ghf_planes_merge_delta")
-        return d_out
+        return self._planes_merge("ghf_planes_merge_delta", d_planes, plane_stride, (_addr(d_base),), (n_elems,), n_elems, elem_bytes,
+                                  d_out)
 
     def planes_merge_range_delta(self, d_planes, plane_stride, d_base, first, count, elem_bytes, d_out=None):
         """planes_merge_range ^ d_base, where d_base holds base elements [first, first + count) and is indexed like d_out
         (and may be d_out).  -> d_out uint8[count * elem_bytes]"""
-        if d_out is None:
-            d_out = self.empty_u8(count * elem_bytes)
-        self._chk(self.L.ghf_planes_merge_range_delta(self.h, d_planes.data_ptr(), plane_stride, self._base_ptr(d_base), first, count,
-                                                      elem_bytes, d_out.data_ptr()), "ghf_planes_merge_range_delta")
-        return d_out
+        return self._planes_merge("ghf_planes_merge_range_delta", d_planes, plane_stride, (_addr(d_base),), (first, count), count,
+                                  elem_bytes, d_out)
 
     def compress_planes_delta(self, d_in, d_base, elem_bytes, d_codes=None, flags=None, n_elems=None, d_out=None, slot_bytes=None,
                               indexes=None):
         """compress_planes_coded of d_in ^ d_base: every image is an ordinary .crs2 of a plane of the XOR.  No host
         synchronisation.  -> the dict of compress_planes"""
-        t = self.torch
-        n_elems = d_in.numel() * d_in.element_size() // elem_bytes if n_elems is None else n_elems
-        if flags is None:
-            flags = PLANES_BUILD_CODES if d_codes is None else 0
-        if slot_bytes is None:
-            slot_bytes = planes_slot_bytes(n_elems)
-        if d_out is None:
-            d_out = self.empty_u8(slot_bytes * elem_bytes)
-        if d_codes is None:
-            d_codes = t.zeros((elem_bytes, C.sizeof(Code)), dtype=t.uint8, device=self.device)
-        out_bytes = t.zeros(elem_bytes, dtype=t.int64, device=self.device)
-        self._chk(
-            self.L.ghf_compress_planes_delta(self.h, d_in.data_ptr(), self._base_ptr(d_base), n_elems, elem_bytes, d_codes.data_ptr(),
-                                             flags, d_out.data_ptr(), slot_bytes, out_bytes.data_ptr(), indexes),
-            "ghf_compress_planes_delta")
-        return {"out": d_out, "slot_bytes": slot_bytes, "out_bytes": out_bytes, "codes": d_codes, "n_elems": n_elems,
-                "elem_bytes": elem_bytes}
+        return self._compress_planes_coded("ghf_compress_planes_delta", d_in, (_addr(d_base),), elem_bytes, d_codes, flags, n_elems,
+                                           d_out, slot_bytes, indexes)
 
     def decode_planes_delta(self, streams, stream_bytes, d_codes, d_base, n_elems, elem_bytes, indexes=None, d_out=None, cap=None,
                             nbytes=None):
         """decode_planes, then ^ d_base in the merge; d_out may be d_base (behind a latched status it then still holds the
         base).  indexes=None synchronises.  -> (d_out uint8, nbytes int64[1] device)"""
-        ptrs = (C.c_void_p * elem_bytes)(*[x.data_ptr() for x in streams])
-        sizes = (C.c_size_t * elem_bytes)(*[int(v) for v in stream_bytes])
-        if d_out is None:
-            d_out = self.empty_u8(n_elems * elem_bytes)
-        if nbytes is None:
-            nbytes = self.torch.zeros(1, dtype=self.torch.int64, device=self.device)
-        self._chk(
-            self.L.ghf_decode_planes_delta(self.h, ptrs, sizes, d_codes.data_ptr(), indexes, self._base_ptr(d_base), n_elems, elem_bytes,
-                                           d_out.data_ptr(), d_out.numel() if cap is None else cap, nbytes.data_ptr()),
-            "ghf_decode_planes_delta")
-        return d_out, nbytes
+        return self._decode_planes("ghf_decode_planes_delta", streams, stream_bytes, elem_bytes, d_codes, indexes, (_addr(d_base),),
+                                   n_elems, elem_bytes, d_out, cap, nbytes)
 
     def decode_planes_range_delta(self, streams, stream_bytes, d_codes, d_base, elem_bytes, first, count, indexes=None, infos=None,
                                   d_tables=None, table_bytes=None, d_out=None, cap=None):
         """decode_planes_range, then ^ d_base in the merge: d_base holds base elements [first, first + count), indexed like
         d_out, and may be d_out.  Never synchronises.  -> d_out uint8"""
-        ptrs = (C.c_void_p * elem_bytes)(*[x.data_ptr() for x in streams])
-        sizes = (C.c_size_t * elem_bytes)(*[int(v) for v in stream_bytes])
-        h_infos = t_ptrs = t_bytes = None
-        if infos is not None:
-            h_infos = (SeekInfo * elem_bytes)(*infos)
-            t_ptrs = (C.c_void_p * elem_bytes)(*[x.data_ptr() for x in d_tables])
-            if table_bytes is None:
-                table_bytes = [seek_bytes(i.n_symbols) for i in infos]
-            t_bytes = (C.c_size_t * elem_bytes)(*[int(v) for v in table_bytes])
-        if d_out is None:
-            d_out = self.empty_u8(count * elem_bytes)
-        self._chk(
-            self.L.ghf_decode_planes_range_delta(self.h, ptrs, sizes, d_codes.data_ptr(), indexes, h_infos, t_ptrs, t_bytes,
-                                                 self._base_ptr(d_base), elem_bytes, first, count, d_out.data_ptr(),
-                                                 d_out.numel() if cap is None else cap),
-            "ghf_decode_planes_range_delta")
-        return d_out
+        return self._decode_planes_range("ghf_decode_planes_range_delta", streams, stream_bytes, elem_bytes, d_codes, indexes, infos,
+                                         d_tables, table_bytes, (_addr(d_base),), elem_bytes, first, count, d_out, cap)
 
     # ---- zero-suppressed byte planes (DESIGN.md section 20): a byte string as a bit mask of its non-zero bytes plus those
     # bytes; planes that are almost all zeros stored as two ordinary .crs2 images, mask and values -------------------------
@@ -1462,28 +1286,31 @@ class Context:
                                           d_out.data_ptr()), "ghf_sparse_merge")
         return d_out
 
-    def _compress_planes_sparse(self, d_in, d_base, delta, elem_bytes, sparse_planes, n_elems, d_out, slot_bytes, d_codes, indexes):
-        t = self.torch
-        n_elems = d_in.numel() * d_in.element_size() // elem_bytes if n_elems is None else n_elems
-        if slot_bytes is None:
-            slot_bytes = planes_slot_bytes(n_elems)
-        if d_out is None:
-            d_out = self.empty_u8(slot_bytes * 2 * elem_bytes)
-        if d_codes is None:
-            d_codes = t.zeros((2 * elem_bytes, C.sizeof(Code)), dtype=t.uint8, device=self.device)
-        out_bytes = t.zeros(2 * elem_bytes, dtype=t.int64, device=self.device)
+    def _rank_slots(self, n_elems, elem_bytes, d_ranks, rank_slot_bytes, alloc):
+        """(d_ranks, rank_slot_bytes): a slot is by default the rank table of n_elems bytes rounded up to 16; elem_bytes of
+        them are allocated when `alloc` says so and none are given"""
+        if rank_slot_bytes is None:
+            rank_slot_bytes = (sparse_rank_bytes(n_elems) + 15) & ~15
+        if d_ranks is None and alloc:
+            d_ranks = self.empty_u8(rank_slot_bytes * elem_bytes)
+        return d_ranks, rank_slot_bytes
+
+    def _compress_planes_sparse(self, name, d_in, base, elem_bytes, sparse_planes, n_elems, d_out, slot_bytes, d_codes, indexes,
+                                ranks=None):
+        """the four sparse compress calls; ranks: None, or (d_ranks, rank_slot_bytes) of the two that write rank tables"""
+        r = self._compress_planes_out(d_in, elem_bytes, 2 * elem_bytes, n_elems, d_out, slot_bytes, d_codes)
         idx = (Index * (2 * elem_bytes))() if indexes else None
         chosen, n_vals = C.c_uint(0), (C.c_size_t * elem_bytes)()
-        if delta:
-            rc = self.L.ghf_compress_planes_sparse_delta(self.h, d_in.data_ptr(), self._base_ptr(d_base), n_elems, elem_bytes,
-                                                         sparse_planes, d_out.data_ptr(), slot_bytes, out_bytes.data_ptr(),
-                                                         d_codes.data_ptr(), idx, C.byref(chosen), n_vals)
-        else:
-            rc = self.L.ghf_compress_planes_sparse(self.h, d_in.data_ptr(), n_elems, elem_bytes, sparse_planes, d_out.data_ptr(),
-                                                   slot_bytes, out_bytes.data_ptr(), d_codes.data_ptr(), idx, C.byref(chosen), n_vals)
-        self._chk(rc, "ghf_compress_planes_sparse_delta" if delta else "ghf_compress_planes_sparse")
-        return {"out": d_out, "slot_bytes": slot_bytes, "out_bytes": out_bytes, "codes": d_codes, "n_elems": n_elems,
-                "elem_bytes": elem_bytes, "sparse_planes": int(chosen.value), "n_vals": [int(v) for v in n_vals], "indexes": idx}
+        tail = ()
+        if ranks is not None:
+            d_ranks, rank_slot_bytes = self._rank_slots(r["n_elems"], elem_bytes, *ranks, alloc=True)
+            tail = (d_ranks.data_ptr(), rank_slot_bytes)
+        self._call(name, d_in.data_ptr(), *base, r["n_elems"], elem_bytes, sparse_planes, r["out"].data_ptr(), r["slot_bytes"],
+                   r["out_bytes"].data_ptr(), r["codes"].data_ptr(), idx, C.byref(chosen), n_vals, *tail)
+        r.update(sparse_planes=int(chosen.value), n_vals=[int(v) for v in n_vals], indexes=idx)
+        if ranks is not None:
+            r.update(ranks=d_ranks, rank_slot_bytes=rank_slot_bytes)
+        return r
 
     def compress_planes_sparse(self, d_in, elem_bytes, sparse_planes=SPARSE_AUTO, n_elems=None, d_out=None, slot_bytes=None,
                                d_codes=None, indexes=False):
@@ -1492,47 +1319,29 @@ class Context:
         SYNCHRONISES once (the plane counts).  indexes=True: the call allocates a side-car per stored stream (free them with
         planes_index_free).  -> the dict of compress_planes over 2 * elem_bytes slots, plus sparse_planes (the planes stored
         sparse), n_vals (host ints, per plane) and indexes (a ctypes Index array or None)"""
-        return self._compress_planes_sparse(d_in, None, False, elem_bytes, sparse_planes, n_elems, d_out, slot_bytes, d_codes, indexes)
+        return self._compress_planes_sparse("ghf_compress_planes_sparse", d_in, (), elem_bytes, sparse_planes, n_elems, d_out, slot_bytes,
+                                            d_codes, indexes)
 
     def compress_planes_sparse_delta(self, d_in, d_base, elem_bytes, sparse_planes=SPARSE_AUTO, n_elems=None, d_out=None,
                                      slot_bytes=None, d_codes=None, indexes=False):
         """compress_planes_sparse of d_in ^ d_base (the XOR inside the histogram and split kernels).  -> the same dict"""
-        return self._compress_planes_sparse(d_in, d_base, True, elem_bytes, sparse_planes, n_elems, d_out, slot_bytes, d_codes, indexes)
-
-    def _decode_planes_sparse(self, streams, stream_bytes, d_codes, d_base, delta, sparse_planes, n_vals, n_elems, elem_bytes, indexes,
-                              d_out, cap, nbytes):
-        ptrs = (C.c_void_p * (2 * elem_bytes))(*[None if x is None else x.data_ptr() for x in streams])
-        sizes = (C.c_size_t * (2 * elem_bytes))(*[int(v) for v in stream_bytes])
-        h_n_vals = (C.c_size_t * elem_bytes)(*[int(v) for v in n_vals])
-        if d_out is None:
-            d_out = self.empty_u8(n_elems * elem_bytes)
-        if nbytes is None:
-            nbytes = self.torch.zeros(1, dtype=self.torch.int64, device=self.device)
-        cap = d_out.numel() if cap is None else cap
-        if delta:
-            rc = self.L.ghf_decode_planes_sparse_delta(self.h, ptrs, sizes, d_codes.data_ptr(), indexes, self._base_ptr(d_base),
-                                                       sparse_planes, h_n_vals, n_elems, elem_bytes, d_out.data_ptr(), cap,
-                                                       nbytes.data_ptr())
-        else:
-            rc = self.L.ghf_decode_planes_sparse(self.h, ptrs, sizes, d_codes.data_ptr(), indexes, sparse_planes, h_n_vals, n_elems,
-                                                 elem_bytes, d_out.data_ptr(), cap, nbytes.data_ptr())
-        self._chk(rc, "ghf_decode_planes_sparse_delta" if delta else "ghf_decode_planes_sparse")
-        return d_out, nbytes
+        return self._compress_planes_sparse("ghf_compress_planes_sparse_delta", d_in, (_addr(d_base),), elem_bytes, sparse_planes, n_elems,
+                                            d_out, slot_bytes, d_codes, indexes)
 
     def decode_planes_sparse(self, streams, stream_bytes, d_codes, sparse_planes, n_vals, n_elems, elem_bytes, indexes=None,
                              d_out=None, cap=None, nbytes=None):
         """streams: 2 * elem_bytes CUDA uint8 tensors (None for an empty slot), stream_bytes: their sizes as host ints;
         sparse_planes and n_vals as compress_planes_sparse returned them.  indexes=None synchronises per stream.
         -> (d_out uint8, nbytes int64[1] device)"""
-        return self._decode_planes_sparse(streams, stream_bytes, d_codes, None, False, sparse_planes, n_vals, n_elems, elem_bytes,
-                                          indexes, d_out, cap, nbytes)
+        return self._decode_planes("ghf_decode_planes_sparse", streams, stream_bytes, 2 * elem_bytes, d_codes, indexes,
+                                   (sparse_planes, _size_array(n_vals, elem_bytes)), n_elems, elem_bytes, d_out, cap, nbytes)
 
     def decode_planes_sparse_delta(self, streams, stream_bytes, d_codes, d_base, sparse_planes, n_vals, n_elems, elem_bytes,
                                    indexes=None, d_out=None, cap=None, nbytes=None):
         """decode_planes_sparse, then ^ d_base in the merge; d_out may be d_base (behind a latched status it then still holds
         the base).  -> (d_out uint8, nbytes int64[1] device)"""
-        return self._decode_planes_sparse(streams, stream_bytes, d_codes, d_base, True, sparse_planes, n_vals, n_elems, elem_bytes,
-                                          indexes, d_out, cap, nbytes)
+        return self._decode_planes("ghf_decode_planes_sparse_delta", streams, stream_bytes, 2 * elem_bytes, d_codes, indexes,
+                                   (_addr(d_base), sparse_planes, _size_array(n_vals, elem_bytes)), n_elems, elem_bytes, d_out, cap, nbytes)
 
     # ---- an element range of zero-suppressed byte planes (DESIGN.md section 21): rank tables, the merge with values that start
     # anywhere, the compress calls that write rank tables, the range decode -------------------------------------------------
@@ -1555,123 +1364,50 @@ class Context:
                                              d_out.data_ptr()), "ghf_sparse_merge_at")
         return d_out
 
-    def _compress_planes_sparse_ranked(self, d_in, d_base, delta, elem_bytes, sparse_planes, n_elems, d_out, slot_bytes, d_codes, indexes,
-                                       d_ranks, rank_slot_bytes):
-        t = self.torch
-        n_elems = d_in.numel() * d_in.element_size() // elem_bytes if n_elems is None else n_elems
-        if slot_bytes is None:
-            slot_bytes = planes_slot_bytes(n_elems)
-        if rank_slot_bytes is None:
-            rank_slot_bytes = (sparse_rank_bytes(n_elems) + 15) & ~15
-        if d_out is None:
-            d_out = self.empty_u8(slot_bytes * 2 * elem_bytes)
-        if d_ranks is None:
-            d_ranks = self.empty_u8(rank_slot_bytes * elem_bytes)
-        if d_codes is None:
-            d_codes = t.zeros((2 * elem_bytes, C.sizeof(Code)), dtype=t.uint8, device=self.device)
-        out_bytes = t.zeros(2 * elem_bytes, dtype=t.int64, device=self.device)
-        idx = (Index * (2 * elem_bytes))() if indexes else None
-        chosen, n_vals = C.c_uint(0), (C.c_size_t * elem_bytes)()
-        if delta:
-            rc = self.L.ghf_compress_planes_sparse_ranked_delta(self.h, d_in.data_ptr(), self._base_ptr(d_base), n_elems, elem_bytes,
-                                                                sparse_planes, d_out.data_ptr(), slot_bytes, out_bytes.data_ptr(),
-                                                                d_codes.data_ptr(), idx, C.byref(chosen), n_vals, d_ranks.data_ptr(),
-                                                                rank_slot_bytes)
-        else:
-            rc = self.L.ghf_compress_planes_sparse_ranked(self.h, d_in.data_ptr(), n_elems, elem_bytes, sparse_planes, d_out.data_ptr(),
-                                                          slot_bytes, out_bytes.data_ptr(), d_codes.data_ptr(), idx, C.byref(chosen), n_vals,
-                                                          d_ranks.data_ptr(), rank_slot_bytes)
-        self._chk(rc, "ghf_compress_planes_sparse_ranked_delta" if delta else "ghf_compress_planes_sparse_ranked")
-        return {"out": d_out, "slot_bytes": slot_bytes, "out_bytes": out_bytes, "codes": d_codes, "n_elems": n_elems,
-                "elem_bytes": elem_bytes, "sparse_planes": int(chosen.value), "n_vals": [int(v) for v in n_vals], "indexes": idx,
-                "ranks": d_ranks, "rank_slot_bytes": rank_slot_bytes}
-
     def compress_planes_sparse_ranked(self, d_in, elem_bytes, sparse_planes=SPARSE_AUTO, n_elems=None, d_out=None, slot_bytes=None,
                                       d_codes=None, indexes=False, d_ranks=None, rank_slot_bytes=None):
         """compress_planes_sparse, and the rank table of every sparse plane in slot p of `ranks` (device uint8, elem_bytes slots
         of rank_slot_bytes; slots of dense planes stay unwritten).  -> the same dict plus ranks and rank_slot_bytes"""
-        return self._compress_planes_sparse_ranked(d_in, None, False, elem_bytes, sparse_planes, n_elems, d_out, slot_bytes, d_codes,
-                                                   indexes, d_ranks, rank_slot_bytes)
+        return self._compress_planes_sparse("ghf_compress_planes_sparse_ranked", d_in, (), elem_bytes, sparse_planes, n_elems, d_out,
+                                            slot_bytes, d_codes, indexes, ranks=(d_ranks, rank_slot_bytes))
 
     def compress_planes_sparse_ranked_delta(self, d_in, d_base, elem_bytes, sparse_planes=SPARSE_AUTO, n_elems=None, d_out=None,
                                             slot_bytes=None, d_codes=None, indexes=False, d_ranks=None, rank_slot_bytes=None):
         """compress_planes_sparse_ranked of d_in ^ d_base.  -> the same dict"""
-        return self._compress_planes_sparse_ranked(d_in, d_base, True, elem_bytes, sparse_planes, n_elems, d_out, slot_bytes, d_codes,
-                                                   indexes, d_ranks, rank_slot_bytes)
-
-    def _decode_planes_sparse_range(self, streams, stream_bytes, d_codes, d_base, delta, sparse_planes, ranks, n_elems, elem_bytes, first,
-                                    count, indexes, infos, d_tables, table_bytes, d_out, cap):
-        import numpy as np
-
-        slots = 2 * elem_bytes
-        ptrs = (C.c_void_p * slots)(*[None if x is None else x.data_ptr() for x in streams])
-        sizes = (C.c_size_t * slots)(*[int(v) for v in stream_bytes])
-        h_infos = t_ptrs = t_bytes = None
-        if infos is not None:
-            h_infos = (SeekInfo * slots)(*[SeekInfo() if i is None else i for i in infos])
-            t_ptrs = (C.c_void_p * slots)(*[None if x is None else x.data_ptr() for x in d_tables])
-            if table_bytes is None:
-                table_bytes = [0 if i is None else seek_bytes(i.n_symbols) for i in infos]
-            t_bytes = (C.c_size_t * slots)(*[int(v) for v in table_bytes])
-        r_infos = r_ptrs = None
-        keep = []
-        if ranks is not None:  # per plane: None, or (SparseRankInfo, the table as host bytes)
-            r_infos, r_ptrs = (SparseRankInfo * elem_bytes)(), (C.c_void_p * elem_bytes)()
-            for p, r in enumerate(ranks):
-                if r is None:
-                    continue
-                r_infos[p] = r[0]
-                if r[1] is not None:
-                    keep.append(np.ascontiguousarray(r[1], dtype=np.uint8))
-                    r_ptrs[p] = keep[-1].ctypes.data
-        if d_out is None:
-            d_out = self.empty_u8(count * elem_bytes)
-        cap = d_out.numel() if cap is None else cap
-        if delta:
-            rc = self.L.ghf_decode_planes_sparse_range_delta(self.h, ptrs, sizes, d_codes.data_ptr(), indexes, h_infos, t_ptrs, t_bytes,
-                                                             r_infos, r_ptrs, self._base_ptr(d_base), sparse_planes, n_elems, elem_bytes,
-                                                             first, count, d_out.data_ptr(), cap)
-        else:
-            rc = self.L.ghf_decode_planes_sparse_range(self.h, ptrs, sizes, d_codes.data_ptr(), indexes, h_infos, t_ptrs, t_bytes, r_infos,
-                                                       r_ptrs, sparse_planes, n_elems, elem_bytes, first, count, d_out.data_ptr(), cap)
-        self._chk(rc, "ghf_decode_planes_sparse_range_delta" if delta else "ghf_decode_planes_sparse_range")
-        return d_out
+        return self._compress_planes_sparse("ghf_compress_planes_sparse_ranked_delta", d_in, (_addr(d_base),), elem_bytes, sparse_planes,
+                                            n_elems, d_out, slot_bytes, d_codes, indexes, ranks=(d_ranks, rank_slot_bytes))
 
     def decode_planes_sparse_range(self, streams, stream_bytes, d_codes, sparse_planes, ranks, n_elems, elem_bytes, first, count,
                                    indexes=None, infos=None, d_tables=None, table_bytes=None, d_out=None, cap=None):
         """d_out[0 : count * elem_bytes] = elements [first, first + count) of a tensor stored by compress_planes_sparse[_ranked].
         streams / stream_bytes / infos / d_tables: 2 * elem_bytes entries (None for an empty slot); ranks: per plane None or
         (SparseRankInfo, the table as HOST bytes); give either indexes or (infos, d_tables).  Never synchronises.  -> d_out"""
-        return self._decode_planes_sparse_range(streams, stream_bytes, d_codes, None, False, sparse_planes, ranks, n_elems, elem_bytes,
-                                                first, count, indexes, infos, d_tables, table_bytes, d_out, cap)
+        return self._decode_planes_ranked_range("ghf_decode_planes_sparse_range", streams, stream_bytes, d_codes, ranks, (sparse_planes,),
+                                                n_elems, elem_bytes, first, count, indexes, infos, d_tables, table_bytes, d_out, cap)
 
     def decode_planes_sparse_range_delta(self, streams, stream_bytes, d_codes, d_base, sparse_planes, ranks, n_elems, elem_bytes, first,
                                          count, indexes=None, infos=None, d_tables=None, table_bytes=None, d_out=None, cap=None):
         """decode_planes_sparse_range, then ^ d_base in the merge: d_base holds base elements [first, first + count), indexed like
         d_out, and may be d_out.  -> d_out"""
-        return self._decode_planes_sparse_range(streams, stream_bytes, d_codes, d_base, True, sparse_planes, ranks, n_elems, elem_bytes,
-                                                first, count, indexes, infos, d_tables, table_bytes, d_out, cap)
+        return self._decode_planes_ranked_range("ghf_decode_planes_sparse_range_delta", streams, stream_bytes, d_codes, ranks,
+                                                (_addr(d_base), sparse_planes), n_elems, elem_bytes, first, count, indexes, infos,
+                                                d_tables, table_bytes, d_out, cap)
 
     # ---- byte planes in three forms (DESIGN.md section 23): raw planes beside dense and sparse ones; d_base is optional ------
-    @staticmethod
-    def _plane_ptrs(planes, elem_bytes):
-        """planes: elem_bytes CUDA uint8 tensors or raw device addresses -> a host array of addresses"""
-        return (C.c_void_p * elem_bytes)(*[x if isinstance(x, int) else x.data_ptr() for x in planes])
+    _plane_ptrs = staticmethod(_ptr_array)  # (planes, elem_bytes): CUDA uint8 tensors or raw device addresses -> a host array
 
     def planes_split_to(self, d_in, planes, elem_bytes, n_elems=None, d_base=None):
         """plane p of d_in (of d_in ^ d_base) -> planes[p][0 : n_elems]; planes: elem_bytes CUDA uint8 tensors (or device
         addresses), each 16-byte aligned, anywhere and in any order.  No host synchronisation.  -> planes"""
-        n_elems = d_in.numel() * d_in.element_size() // elem_bytes if n_elems is None else n_elems
-        self._chk(self.L.ghf_planes_split_to(self.h, d_in.data_ptr(), self._base_ptr(d_base), n_elems, elem_bytes,
-                                             self._plane_ptrs(planes, elem_bytes)), "ghf_planes_split_to")
+        self._call("ghf_planes_split_to", d_in.data_ptr(), _addr(d_base), _n_elems(d_in, elem_bytes, n_elems), elem_bytes,
+                   _ptr_array(planes, elem_bytes))
         return planes
 
     def planes_merge_from(self, planes, n_elems, elem_bytes, d_out=None, d_base=None):
         """the inverse of planes_split_to; d_out may be d_base.  -> d_out uint8[n_elems * elem_bytes]"""
         if d_out is None:
             d_out = self.empty_u8(n_elems * elem_bytes)
-        self._chk(self.L.ghf_planes_merge_from(self.h, self._plane_ptrs(planes, elem_bytes), self._base_ptr(d_base), n_elems, elem_bytes,
-                                               d_out.data_ptr()), "ghf_planes_merge_from")
+        self._call("ghf_planes_merge_from", _ptr_array(planes, elem_bytes), _addr(d_base), n_elems, elem_bytes, d_out.data_ptr())
         return d_out
 
     def planes_merge_range_from(self, planes, count, elem_bytes, d_out=None, d_base=None):
@@ -1679,8 +1415,7 @@ class Context:
         modulo 16.  d_base: the base elements of the run, indexed like d_out.  -> d_out uint8[count * elem_bytes]"""
         if d_out is None:
             d_out = self.empty_u8(count * elem_bytes)
-        self._chk(self.L.ghf_planes_merge_range_from(self.h, self._plane_ptrs(planes, elem_bytes), self._base_ptr(d_base), count,
-                                                     elem_bytes, d_out.data_ptr()), "ghf_planes_merge_range_from")
+        self._call("ghf_planes_merge_range_from", _ptr_array(planes, elem_bytes), _addr(d_base), count, elem_bytes, d_out.data_ptr())
         return d_out
 
     def compress_planes_forms(self, d_in, elem_bytes, raw_planes=RAW_AUTO, sparse_planes=0, d_base=None, n_elems=None, d_out=None,
@@ -1691,29 +1426,16 @@ class Context:
         is its n_elems bytes at the start of slot p, written by the split itself.  SYNCHRONISES at most once; never with both
         masks explicit and sparse_planes == 0.  ranks=True (or d_ranks): the rank table of every sparse plane.
         -> the dict of compress_planes_sparse_ranked plus raw_planes (the planes stored raw)"""
-        t = self.torch
-        n_elems = d_in.numel() * d_in.element_size() // elem_bytes if n_elems is None else n_elems
-        if slot_bytes is None:
-            slot_bytes = planes_slot_bytes(n_elems)
-        if d_out is None:
-            d_out = self.empty_u8(slot_bytes * 2 * elem_bytes)
-        if rank_slot_bytes is None:
-            rank_slot_bytes = (sparse_rank_bytes(n_elems) + 15) & ~15
-        if d_ranks is None and ranks:
-            d_ranks = self.empty_u8(rank_slot_bytes * elem_bytes)
-        if d_codes is None:
-            d_codes = t.zeros((2 * elem_bytes, C.sizeof(Code)), dtype=t.uint8, device=self.device)
-        if out_bytes is None:
-            out_bytes = t.zeros(2 * elem_bytes, dtype=t.int64, device=self.device)
+        r = self._compress_planes_out(d_in, elem_bytes, 2 * elem_bytes, n_elems, d_out, slot_bytes, d_codes, out_bytes)
+        d_ranks, rank_slot_bytes = self._rank_slots(r["n_elems"], elem_bytes, d_ranks, rank_slot_bytes, alloc=ranks)
         idx = (Index * (2 * elem_bytes))() if indexes else None
         raw, chosen, n_vals = C.c_uint(0), C.c_uint(0), (C.c_size_t * elem_bytes)()
-        self._chk(self.L.ghf_compress_planes_forms(self.h, d_in.data_ptr(), self._base_ptr(d_base), n_elems, elem_bytes, raw_planes,
-                                                   sparse_planes, d_out.data_ptr(), slot_bytes, out_bytes.data_ptr(), d_codes.data_ptr(),
-                                                   idx, None if d_ranks is None else d_ranks.data_ptr(), rank_slot_bytes, C.byref(raw),
-                                                   C.byref(chosen), n_vals), "ghf_compress_planes_forms")
-        return {"out": d_out, "slot_bytes": slot_bytes, "out_bytes": out_bytes, "codes": d_codes, "n_elems": n_elems,
-                "elem_bytes": elem_bytes, "raw_planes": int(raw.value), "sparse_planes": int(chosen.value),
-                "n_vals": [int(v) for v in n_vals], "indexes": idx, "ranks": d_ranks, "rank_slot_bytes": rank_slot_bytes}
+        self._call("ghf_compress_planes_forms", d_in.data_ptr(), _addr(d_base), r["n_elems"], elem_bytes, raw_planes, sparse_planes,
+                   r["out"].data_ptr(), r["slot_bytes"], r["out_bytes"].data_ptr(), r["codes"].data_ptr(), idx, _addr(d_ranks),
+                   rank_slot_bytes, C.byref(raw), C.byref(chosen), n_vals)
+        r.update(raw_planes=int(raw.value), sparse_planes=int(chosen.value), n_vals=[int(v) for v in n_vals], indexes=idx, ranks=d_ranks,
+                 rank_slot_bytes=rank_slot_bytes)
+        return r
 
     def decode_planes_forms(self, streams, stream_bytes, d_codes, raw_planes, sparse_planes, n_vals, n_elems, elem_bytes, indexes=None,
                             d_base=None, d_out=None, cap=None, nbytes=None):
@@ -1721,55 +1443,18 @@ class Context:
         stream_bytes entry is n_elems); raw_planes, sparse_planes and n_vals as compress_planes_forms returned them.  A raw
         plane is read where it lies.  d_out may be d_base.  indexes=None synchronises per stream that has a code.
         -> (d_out uint8, nbytes int64[1] device)"""
-        ptrs = (C.c_void_p * (2 * elem_bytes))(*[None if x is None else x if isinstance(x, int) else x.data_ptr() for x in streams])
-        sizes = (C.c_size_t * (2 * elem_bytes))(*[int(v) for v in stream_bytes])
-        h_n_vals = (C.c_size_t * elem_bytes)(*[int(v) for v in n_vals])
-        if d_out is None:
-            d_out = self.empty_u8(n_elems * elem_bytes)
-        if nbytes is None:
-            nbytes = self.torch.zeros(1, dtype=self.torch.int64, device=self.device)
-        cap = d_out.numel() if cap is None else cap
-        self._chk(self.L.ghf_decode_planes_forms(self.h, ptrs, sizes, None if d_codes is None else d_codes.data_ptr(), indexes,
-                                                 self._base_ptr(d_base), raw_planes, sparse_planes, h_n_vals, n_elems, elem_bytes,
-                                                 d_out.data_ptr(), cap, nbytes.data_ptr()), "ghf_decode_planes_forms")
-        return d_out, nbytes
+        return self._decode_planes("ghf_decode_planes_forms", streams, stream_bytes, 2 * elem_bytes, d_codes, indexes,
+                                   (_addr(d_base), raw_planes, sparse_planes, _size_array(n_vals, elem_bytes)), n_elems, elem_bytes, d_out,
+                                   cap, nbytes)
 
     def decode_planes_forms_range(self, streams, stream_bytes, d_codes, raw_planes, sparse_planes, ranks, n_elems, elem_bytes, first,
                                   count, indexes=None, infos=None, d_tables=None, table_bytes=None, d_base=None, d_out=None, cap=None):
         """d_out[0 : count * elem_bytes] = elements [first, first + count) of a tensor stored by compress_planes_forms; the
         arguments of decode_planes_sparse_range plus raw_planes and the optional d_base (the base elements of the range, indexed
         like d_out).  The index, info and table entries of a raw plane may be None.  Never synchronises.  -> d_out"""
-        import numpy as np
-
-        slots = 2 * elem_bytes
-        ptrs = (C.c_void_p * slots)(*[None if x is None else x if isinstance(x, int) else x.data_ptr() for x in streams])
-        sizes = (C.c_size_t * slots)(*[int(v) for v in stream_bytes])
-        h_infos = t_ptrs = t_bytes = None
-        if infos is not None:
-            h_infos = (SeekInfo * slots)(*[SeekInfo() if i is None else i for i in infos])
-            t_ptrs = (C.c_void_p * slots)(*[None if x is None else x.data_ptr() for x in d_tables])
-            if table_bytes is None:
-                table_bytes = [0 if i is None else seek_bytes(i.n_symbols) for i in infos]
-            t_bytes = (C.c_size_t * slots)(*[int(v) for v in table_bytes])
-        r_infos = r_ptrs = None
-        keep = []
-        if ranks is not None:  # per plane: None, or (SparseRankInfo, the table as host bytes)
-            r_infos, r_ptrs = (SparseRankInfo * elem_bytes)(), (C.c_void_p * elem_bytes)()
-            for p, r in enumerate(ranks):
-                if r is None:
-                    continue
-                r_infos[p] = r[0]
-                if r[1] is not None:
-                    keep.append(np.ascontiguousarray(r[1], dtype=np.uint8))
-                    r_ptrs[p] = keep[-1].ctypes.data
-        if d_out is None:
-            d_out = self.empty_u8(count * elem_bytes)
-        cap = d_out.numel() if cap is None else cap
-        self._chk(self.L.ghf_decode_planes_forms_range(self.h, ptrs, sizes, None if d_codes is None else d_codes.data_ptr(), indexes,
-                                                       h_infos, t_ptrs, t_bytes, r_infos, r_ptrs, self._base_ptr(d_base), raw_planes,
-                                                       sparse_planes, n_elems, elem_bytes, first, count, d_out.data_ptr(), cap),
-                  "ghf_decode_planes_forms_range")
-        return d_out
+        return self._decode_planes_ranked_range("ghf_decode_planes_forms_range", streams, stream_bytes, d_codes, ranks,
+                                                (_addr(d_base), raw_planes, sparse_planes), n_elems, elem_bytes, first, count, indexes,
+                                                infos, d_tables, table_bytes, d_out, cap)
 
     def decode_planes_gather(self, streams, stream_bytes, d_codes, raw_planes, n_elems, elem_bytes, d_index, row_elems, index_stride=None,
                              infos=None, d_tables=None, table_bytes=None, n_rows=None, d_out=None, out_stride=None, d_row_status=None):
@@ -1780,28 +1465,9 @@ class Context:
         (uint8, out_stride bytes from row to row, default row_elems * elem_bytes) and d_row_status (int32[n_rows]) are
         allocated when not given.  A failed row stores nothing and never latches the context.  Never synchronises.
         -> (d_out, d_row_status)"""
-        t = self.torch
-        E = elem_bytes
-        n_rows = d_index.numel() if n_rows is None else n_rows
-        index_stride = row_elems if index_stride is None else index_stride
-        out_stride = row_elems * E if out_stride is None else out_stride
-        ptrs = (C.c_void_p * E)(*[None if x is None else x if isinstance(x, int) else x.data_ptr() for x in streams[:E]])
-        sizes = (C.c_size_t * E)(*[int(v) for v in stream_bytes[:E]])
-        h_infos = t_ptrs = t_bytes = None
-        if infos is not None:
-            h_infos = (SeekInfo * E)(*[SeekInfo() if i is None else i for i in infos[:E]])
-            t_ptrs = (C.c_void_p * E)(*[None if x is None else x if isinstance(x, int) else x.data_ptr() for x in d_tables[:E]])
-            if table_bytes is None:
-                table_bytes = [0 if i is None else seek_bytes(i.n_symbols) for i in infos[:E]]
-            t_bytes = (C.c_size_t * E)(*[int(v) for v in table_bytes[:E]])
-        if d_out is None:
-            d_out = self.empty_u8(max(n_rows, 1) * out_stride)
-        if d_row_status is None:
-            d_row_status = t.zeros(max(n_rows, 1), dtype=t.int32, device=self.device)
-        self._chk(self.L.ghf_decode_planes_gather(self.h, ptrs, sizes, None if d_codes is None else d_codes.data_ptr(), h_infos, t_ptrs,
-                                                  t_bytes, raw_planes, n_elems, E, d_index.data_ptr(), index_stride, row_elems, n_rows,
-                                                  d_out.data_ptr(), out_stride, d_row_status.data_ptr()), "ghf_decode_planes_gather")
-        return d_out, d_row_status
+        return self._decode_planes_gather("ghf_decode_planes_gather", streams, stream_bytes, elem_bytes, d_codes, infos, d_tables,
+                                          table_bytes, (raw_planes,), n_elems, elem_bytes, d_index, row_elems, index_stride, n_rows, d_out,
+                                          out_stride, d_row_status)
 
     def decode_planes_gather_forms(self, streams, stream_bytes, d_codes, raw_planes, sparse_planes, ranks, n_elems, elem_bytes, d_index,
                                    row_elems, index_stride=None, infos=None, d_tables=None, table_bytes=None, d_base=None, n_rows=None,
@@ -1812,38 +1478,10 @@ class Context:
         plane None, or (SparseRankInfo, the rank table as a CUDA uint8 tensor of sparse_rank_bytes(n_elems)) for a sparse
         plane -- the image lies in DEVICE memory here.  The row cap is GATHER_SPARSE_MAX_ROW_ELEMS with a sparse plane.
         Never synchronises.  -> (d_out, d_row_status)"""
-        t = self.torch
-        E = elem_bytes
-        slots = 2 * E
-        n_rows = d_index.numel() if n_rows is None else n_rows
-        index_stride = row_elems if index_stride is None else index_stride
-        out_stride = row_elems * E if out_stride is None else out_stride
-        ptr = lambda x: None if x is None else x if isinstance(x, int) else x.data_ptr()
-        ptrs = (C.c_void_p * slots)(*[ptr(x) for x in streams])
-        sizes = (C.c_size_t * slots)(*[int(v) for v in stream_bytes])
-        h_infos = t_ptrs = t_bytes = None
-        if infos is not None:
-            h_infos = (SeekInfo * slots)(*[SeekInfo() if i is None else i for i in infos])
-            t_ptrs = (C.c_void_p * slots)(*[ptr(x) for x in d_tables])
-            if table_bytes is None:
-                table_bytes = [0 if i is None else seek_bytes(i.n_symbols) for i in infos]
-            t_bytes = (C.c_size_t * slots)(*[int(v) for v in table_bytes])
-        r_infos = r_ptrs = r_bytes = None
-        if ranks is not None:
-            r_infos, r_ptrs, r_bytes = (SparseRankInfo * E)(), (C.c_void_p * E)(), (C.c_size_t * E)()
-            for p, r in enumerate(ranks):
-                if r is not None:
-                    r_infos[p], r_ptrs[p] = r[0], ptr(r[1])
-                    r_bytes[p] = 0 if r[1] is None else r[2] if len(r) > 2 else r[1].numel()
-        if d_out is None:
-            d_out = self.empty_u8(max(n_rows, 1) * out_stride)
-        if d_row_status is None:
-            d_row_status = t.zeros(max(n_rows, 1), dtype=t.int32, device=self.device)
-        self._chk(self.L.ghf_decode_planes_gather_forms(self.h, ptrs, sizes, None if d_codes is None else d_codes.data_ptr(), h_infos, t_ptrs,
-                                                        t_bytes, r_infos, r_ptrs, r_bytes, self._base_ptr(d_base), raw_planes, sparse_planes,
-                                                        n_elems, E, d_index.data_ptr(), index_stride, row_elems, n_rows, d_out.data_ptr(),
-                                                        out_stride, d_row_status.data_ptr()), "ghf_decode_planes_gather_forms")
-        return d_out, d_row_status
+        r_infos, r_ptrs, r_bytes, _ = _rank_arrays(ranks, elem_bytes, device=True)
+        return self._decode_planes_gather("ghf_decode_planes_gather_forms", streams, stream_bytes, 2 * elem_bytes, d_codes, infos, d_tables,
+                                          table_bytes, (r_infos, r_ptrs, r_bytes, _addr(d_base), raw_planes, sparse_planes), n_elems,
+                                          elem_bytes, d_index, row_elems, index_stride, n_rows, d_out, out_stride, d_row_status)
 
     # ---- seekable streams: the seek table (the persistent form of the side-car) ----------------
     def seek_pack(self, index, d_stream=None, stream_bytes=0, d_table=None, n=None):
