@@ -346,6 +346,20 @@ int ghf_build_code_ex(ghf_ctx* c, const uint64_t* d_hist, ghf_code* d_code, unsi
 
 int ghf_build_code(ghf_ctx* c, const uint64_t* d_hist, ghf_code* d_code) { return ghf_build_code_ex(c, d_hist, d_code, 0); }
 
+// n_codes exact builds in one launch: for the plane batches (ghf_api_batch.hip) and the staged plane calls (ghf_api_planes.hip)
+int ghf_build_codes(ghf_ctx* c, const uint64_t* d_hists, uint32_t n_codes, ghf_code* d_codes, unsigned flags) {
+  if (!c || !d_hists || !d_codes || n_codes == 0 || n_codes > GHF_PLANES_MAX || (flags & ~(unsigned)(GHF_CODE_LIMIT | GHF_EMPTY_OK)))
+    return GHF_E_INVAL;
+  GHF_HIP(c, hipSetDevice(c->device));
+  launch_build_codes(d_hists, n_codes, d_codes, c->d_status, flags, c->stream);
+  GHF_HIP(c, hipGetLastError());
+  for (uint32_t k = 0; k < n_codes; ++k) {  // as ghf_build_code_ex: the tables changed, what was derived from them is stale
+    if (c->plan.code == d_codes + k) c->plan.forget();
+    if (c->prepared.describes(d_codes + k)) c->prepared.forget();
+  }
+  return GHF_OK;
+}
+
 int ghf_write_header(ghf_ctx* c, const ghf_code* d_code, uint8_t* d_out, size_t cap) {
   if (!c || !d_code || !d_out || (reinterpret_cast<uintptr_t>(d_out) & 3u)) return GHF_E_INVAL;
   GHF_HIP(c, hipSetDevice(c->device));
@@ -466,536 +480,6 @@ int ghf_index_alloc(ghf_ctx* c, size_t n_symbols, ghf_index* out) {
 }
 
 int ghf_index_free(ghf_ctx* c, ghf_index* idx) { return free_index_arrays(c, idx); }
-
-// ---------------------------------------------------------------------------------------------- batches
-size_t ghf_compress_batch_bound(size_t max_item_bytes) { return ghf_compress_bound(max_item_bytes); }
-
-int ghf_batch_index_alloc(ghf_ctx* c, uint32_t count, size_t max_item_bytes, ghf_batch_index* out) {
-  if (!c || !out || max_item_bytes == 0 || max_item_bytes > GHF_BATCH_MAX_ITEM) return GHF_E_INVAL;
-  GHF_HIP(c, hipSetDevice(c->device));
-  std::memset(out, 0, sizeof *out);
-  out->count = count;
-  out->max_item_bytes = max_item_bytes;
-  out->blocks_per_item = blocks_for(max_item_bytes);
-  out->segs_per_item = segs_for(max_item_bytes);
-  GHF_HIP(c, hipMalloc(&out->d_chunk_bit, std::max<size_t>((size_t)count * out->blocks_per_item, 1) * sizeof(uint64_t)));
-  hipError_t e = hipMalloc(&out->d_seg_bit, std::max<size_t>((size_t)count * out->segs_per_item, 1) * sizeof(uint32_t));
-  if (e != hipSuccess) {
-    (void)hipFree(out->d_chunk_bit);
-    out->d_chunk_bit = nullptr;
-    return fail(c, GHF_E_HIP, "hipMalloc(batch seg_bit)", e);
-  }
-  return GHF_OK;
-}
-
-int ghf_batch_index_free(ghf_ctx* c, ghf_batch_index* idx) { return free_index_arrays(c, idx); }
-
-int ghf_batch_index_item(const ghf_batch_index* idx, uint32_t i, size_t n_i, ghf_index* view) {
-  if (!idx || !view || i >= idx->count || n_i > idx->max_item_bytes) return GHF_E_INVAL;
-  std::memset(view, 0, sizeof *view);
-  index_shape(n_i, view);
-  view->d_chunk_bit = idx->d_chunk_bit ? idx->d_chunk_bit + (size_t)i * idx->blocks_per_item : nullptr;
-  view->d_seg_bit = idx->d_seg_bit ? idx->d_seg_bit + (size_t)i * idx->segs_per_item : nullptr;
-  return GHF_OK;
-}
-
-// the index covers `count` items of up to max_item_bytes, at the strides the kernels assume
-static bool batch_index_covers(const ghf_batch_index* ix, uint32_t count, size_t max_item_bytes) {
-  return ix->d_chunk_bit && ix->d_seg_bit && ix->count >= count && ix->max_item_bytes >= max_item_bytes &&
-         ix->max_item_bytes <= GHF_BATCH_MAX_ITEM &&
-         ix->blocks_per_item == blocks_for(ix->max_item_bytes) && ix->segs_per_item == segs_for(ix->max_item_bytes);
-}
-
-int ghf_compress_batch(ghf_ctx* c, const uint8_t* const* d_in_ptrs, const uint64_t* d_in_bytes, size_t max_item_bytes,
-                       uint32_t count, uint8_t* const* d_out_ptrs, const uint64_t* d_out_caps, uint64_t* d_out_bytes,
-                       ghf_code* d_codes, const ghf_batch_index* index, int* d_item_status) {
-  if (!c) return GHF_E_INVAL;
-  if (max_item_bytes == 0 || max_item_bytes > GHF_BATCH_MAX_ITEM)
-    return fail(c, GHF_E_INVAL, "ghf_compress_batch: max_item_bytes must be 1 .. GHF_BATCH_MAX_ITEM");
-  if (index && !batch_index_covers(index, count, max_item_bytes))
-    return fail(c, GHF_E_INVAL, "ghf_compress_batch: index does not cover (count, max_item_bytes) (use ghf_batch_index_alloc)");
-  if (count == 0) return GHF_OK;
-  if (!d_in_ptrs || !d_in_bytes || !d_out_ptrs || !d_out_caps || !d_out_bytes || !d_item_status) return GHF_E_INVAL;
-  GHF_HIP(c, hipSetDevice(c->device));
-  if (!d_codes) {
-    const int rc = grow(c, c->batch_codes, count);
-    if (rc) return rc;
-    d_codes = c->batch_codes.p;
-  }
-  BatchCompressParams p;
-  p.in_ptrs = d_in_ptrs;
-  p.in_bytes = d_in_bytes;
-  p.max_item_bytes = max_item_bytes;
-  p.out_ptrs = d_out_ptrs;
-  p.out_caps = d_out_caps;
-  p.out_bytes = d_out_bytes;
-  p.codes = d_codes;
-  p.chunk_bit = index ? index->d_chunk_bit : nullptr;
-  p.seg_bit = index ? index->d_seg_bit : nullptr;
-  p.blocks_per_item = index ? index->blocks_per_item : 0;
-  p.segs_per_item = index ? index->segs_per_item : 0;
-  p.item_status = d_item_status;
-  launch_compress_batch(p, count, c->stream);
-  GHF_HIP(c, hipGetLastError());
-  return GHF_OK;
-}
-
-int ghf_decode_batch(ghf_ctx* c, const uint8_t* const* d_stream_ptrs, const uint64_t* d_stream_bytes, const ghf_code* d_codes,
-                     const ghf_batch_index* index, const uint64_t* d_n_symbols, uint32_t count, uint8_t* const* d_out_ptrs,
-                     const uint64_t* d_out_caps, uint64_t* d_out_bytes, int* d_item_status) {
-  if (!c || !index) return GHF_E_INVAL;
-  if (!batch_index_covers(index, count, 1))
-    return fail(c, GHF_E_INVAL, "ghf_decode_batch: index does not cover count items (use ghf_batch_index_alloc)");
-  if (count == 0) return GHF_OK;
-  if (!d_stream_ptrs || !d_stream_bytes || !d_codes || !d_n_symbols || !d_out_ptrs || !d_out_caps || !d_out_bytes || !d_item_status)
-    return GHF_E_INVAL;
-  GHF_HIP(c, hipSetDevice(c->device));
-  BatchDecodeParams p;
-  p.stream_ptrs = d_stream_ptrs;
-  p.stream_bytes = d_stream_bytes;
-  p.codes = d_codes;
-  p.chunk_bit = index->d_chunk_bit;
-  p.seg_bit = index->d_seg_bit;
-  p.blocks_per_item = index->blocks_per_item;
-  p.segs_per_item = index->segs_per_item;
-  p.max_item_bytes = index->max_item_bytes;
-  p.n_symbols = d_n_symbols;
-  p.out_ptrs = d_out_ptrs;
-  p.out_caps = d_out_caps;
-  p.out_bytes = d_out_bytes;
-  p.item_status = d_item_status;
-  launch_decode_batch(p, count, c->stream);
-  GHF_HIP(c, hipGetLastError());
-  return GHF_OK;
-}
-
-int ghf_decode_images_batch(ghf_ctx* c, const uint8_t* const* d_stream_ptrs, const uint64_t* d_stream_bytes, uint32_t count,
-                            uint8_t* const* d_out_ptrs, const uint64_t* d_out_caps, uint64_t* d_out_bytes, ghf_code* d_codes,
-                            int* d_item_status) {
-  if (!c || !d_stream_ptrs || !d_stream_bytes || !d_out_bytes || !d_item_status) return GHF_E_INVAL;
-  if (d_out_ptrs && !d_out_caps) return fail(c, GHF_E_INVAL, "ghf_decode_images_batch: d_out_ptrs without d_out_caps");
-  if (count == 0) return GHF_OK;
-  GHF_HIP(c, hipSetDevice(c->device));
-  BatchImagesParams p;
-  p.stream_ptrs = d_stream_ptrs;
-  p.stream_bytes = d_stream_bytes;
-  p.max_stream_bytes = ghf_compress_bound(GHF_BATCH_MAX_ITEM);
-  p.out_ptrs = d_out_ptrs;
-  p.out_caps = d_out_caps;
-  p.out_bytes = d_out_bytes;
-  p.codes = d_codes;
-  p.item_status = d_item_status;
-  p.stats = c->images_stats;
-  launch_decode_images_batch(p, count, c->stream);
-  GHF_HIP(c, hipGetLastError());
-  return GHF_OK;
-}
-
-int ghf_decode_images_batch_stats(ghf_ctx* c, uint64_t* d_stats) {
-  if (!c || (reinterpret_cast<uintptr_t>(d_stats) & 7u)) return GHF_E_INVAL;
-  c->images_stats = d_stats;
-  return GHF_OK;
-}
-
-// ---------------------------------------------------------------------------------------------- shared-code batches
-int ghf_histogram_batch(ghf_ctx* c, const uint8_t* const* d_in_ptrs, const uint64_t* d_in_bytes, size_t max_item_bytes,
-                        uint32_t count, unsigned flags, uint64_t* d_hist) {
-  if (!c) return GHF_E_INVAL;
-  if (max_item_bytes == 0 || max_item_bytes > GHF_BATCH_MAX_ITEM)
-    return fail(c, GHF_E_INVAL, "ghf_histogram_batch: max_item_bytes must be 1 .. GHF_BATCH_MAX_ITEM");
-  if (flags & ~GHF_HIST_COVER_ALL) return fail(c, GHF_E_INVAL, "ghf_histogram_batch: unknown flags");
-  if (!d_in_ptrs || !d_in_bytes || !d_hist) return GHF_E_INVAL;
-  if (count == 0) return GHF_OK;
-  GHF_HIP(c, hipSetDevice(c->device));
-  BatchHistParams p;
-  p.in_ptrs = d_in_ptrs;
-  p.in_bytes = d_in_bytes;
-  p.max_item_bytes = max_item_bytes;
-  p.count = count;
-  p.hist = d_hist;
-  launch_histogram_batch(p, flags, c->stream);
-  GHF_HIP(c, hipGetLastError());
-  return GHF_OK;
-}
-
-size_t ghf_compress_batch_shared_bound(size_t max_item_bytes) { return (4 * max_item_bytes + 4 + 15) & ~(size_t)15; }
-
-int ghf_compress_batch_shared(ghf_ctx* c, const uint8_t* const* d_in_ptrs, const uint64_t* d_in_bytes, size_t max_item_bytes,
-                              uint32_t count, const ghf_code* d_code, uint8_t* const* d_out_ptrs, const uint64_t* d_out_caps,
-                              uint64_t* d_out_bytes, const ghf_batch_index* index, int* d_item_status) {
-  if (!c) return GHF_E_INVAL;
-  if (max_item_bytes == 0 || max_item_bytes > GHF_BATCH_MAX_ITEM)
-    return fail(c, GHF_E_INVAL, "ghf_compress_batch_shared: max_item_bytes must be 1 .. GHF_BATCH_MAX_ITEM");
-  if (index && !batch_index_covers(index, count, max_item_bytes))
-    return fail(c, GHF_E_INVAL, "ghf_compress_batch_shared: index does not cover (count, max_item_bytes) (use ghf_batch_index_alloc)");
-  if (!d_code || !aligned16(d_code)) return fail(c, GHF_E_INVAL, "ghf_compress_batch_shared: d_code is null or not 16-byte aligned");
-  if (!d_in_ptrs || !d_in_bytes || !d_out_ptrs || !d_out_caps || !d_out_bytes || !d_item_status) return GHF_E_INVAL;
-  if (count == 0) return GHF_OK;
-  GHF_HIP(c, hipSetDevice(c->device));
-  BatchSharedCompressParams p;
-  p.in_ptrs = d_in_ptrs;
-  p.in_bytes = d_in_bytes;
-  p.max_item_bytes = max_item_bytes;
-  p.code = d_code;
-  p.out_ptrs = d_out_ptrs;
-  p.out_caps = d_out_caps;
-  p.out_bytes = d_out_bytes;
-  p.chunk_bit = index ? index->d_chunk_bit : nullptr;
-  p.seg_bit = index ? index->d_seg_bit : nullptr;
-  p.blocks_per_item = index ? index->blocks_per_item : 0;
-  p.segs_per_item = index ? index->segs_per_item : 0;
-  p.item_status = d_item_status;
-  launch_compress_batch_shared(p, count, c->stream);
-  GHF_HIP(c, hipGetLastError());
-  return GHF_OK;
-}
-
-int ghf_decode_batch_shared(ghf_ctx* c, const uint8_t* const* d_stream_ptrs, const uint64_t* d_stream_bytes, const ghf_code* d_code,
-                            const ghf_batch_index* index, const uint64_t* d_n_symbols, uint32_t count, uint8_t* const* d_out_ptrs,
-                            const uint64_t* d_out_caps, uint64_t* d_out_bytes, int* d_item_status) {
-  if (!c || !index) return GHF_E_INVAL;
-  if (!batch_index_covers(index, count, 1))
-    return fail(c, GHF_E_INVAL, "ghf_decode_batch_shared: index does not cover count items (use ghf_batch_index_alloc)");
-  if (!d_code || !aligned16(d_code)) return fail(c, GHF_E_INVAL, "ghf_decode_batch_shared: d_code is null or not 16-byte aligned");
-  if (!d_stream_ptrs || !d_stream_bytes || !d_n_symbols || !d_out_ptrs || !d_out_caps || !d_out_bytes || !d_item_status)
-    return GHF_E_INVAL;
-  if (count == 0) return GHF_OK;
-  GHF_HIP(c, hipSetDevice(c->device));
-  BatchSharedDecodeParams p;
-  p.stream_ptrs = d_stream_ptrs;
-  p.stream_bytes = d_stream_bytes;
-  p.code = d_code;
-  p.chunk_bit = index->d_chunk_bit;
-  p.seg_bit = index->d_seg_bit;
-  p.blocks_per_item = index->blocks_per_item;
-  p.segs_per_item = index->segs_per_item;
-  p.max_item_bytes = index->max_item_bytes;
-  p.n_symbols = d_n_symbols;
-  p.out_ptrs = d_out_ptrs;
-  p.out_caps = d_out_caps;
-  p.out_bytes = d_out_bytes;
-  p.item_status = d_item_status;
-  launch_decode_batch_shared(p, count, c->stream);
-  GHF_HIP(c, hipGetLastError());
-  return GHF_OK;
-}
-
-int ghf_decode_bodies_batch_shared(ghf_ctx* c, const uint8_t* const* d_stream_ptrs, const uint64_t* d_stream_bytes,
-                                   const ghf_code* d_code, uint32_t count, uint8_t* const* d_out_ptrs, const uint64_t* d_out_caps,
-                                   uint64_t* d_out_bytes, int* d_item_status) {
-  if (!c || !d_stream_ptrs || !d_stream_bytes || !d_out_bytes || !d_item_status) return GHF_E_INVAL;
-  if (d_out_ptrs && !d_out_caps) return fail(c, GHF_E_INVAL, "ghf_decode_bodies_batch_shared: d_out_ptrs without d_out_caps");
-  if (!d_code || !aligned16(d_code)) return fail(c, GHF_E_INVAL, "ghf_decode_bodies_batch_shared: d_code is null or not 16-byte aligned");
-  if (count == 0) return GHF_OK;
-  GHF_HIP(c, hipSetDevice(c->device));
-  BatchSharedBodiesParams p;
-  p.stream_ptrs = d_stream_ptrs;
-  p.stream_bytes = d_stream_bytes;
-  p.max_stream_bytes = ghf_compress_batch_shared_bound(GHF_BATCH_MAX_ITEM);
-  p.code = d_code;
-  p.out_ptrs = d_out_ptrs;
-  p.out_caps = d_out_caps;
-  p.out_bytes = d_out_bytes;
-  p.item_status = d_item_status;
-  p.stats = c->images_stats;
-  launch_decode_bodies_batch_shared(p, count, c->stream);
-  GHF_HIP(c, hipGetLastError());
-  return GHF_OK;
-}
-
-// ---------------------------------------------------------------------------------------------- shared-code batches of byte planes
-static inline bool planes_elem_ok(uint32_t elem_bytes) { return elem_bytes == 2 || elem_bytes == 4 || elem_bytes == 8; }
-// max_item_bytes of a batch of elements: 1 .. GHF_BATCH_MAX_ITEM and a whole number of elements
-static inline bool planes_item_ok(size_t max_item_bytes, uint32_t elem_bytes) {
-  return max_item_bytes != 0 && max_item_bytes <= GHF_BATCH_MAX_ITEM && max_item_bytes % elem_bytes == 0;
-}
-
-int ghf_histogram_batch_planes(ghf_ctx* c, const uint8_t* const* d_in_ptrs, const uint64_t* d_in_bytes, size_t max_item_bytes,
-                               uint32_t count, uint32_t elem_bytes, unsigned flags, uint64_t* d_hists) {
-  if (!c) return GHF_E_INVAL;
-  if (!planes_elem_ok(elem_bytes)) return fail(c, GHF_E_INVAL, "ghf_histogram_batch_planes: elem_bytes must be 2, 4 or 8");
-  if (!planes_item_ok(max_item_bytes, elem_bytes))
-    return fail(c, GHF_E_INVAL, "ghf_histogram_batch_planes: max_item_bytes must be 1 .. GHF_BATCH_MAX_ITEM and a multiple of elem_bytes");
-  if (flags & ~GHF_HIST_COVER_ALL) return fail(c, GHF_E_INVAL, "ghf_histogram_batch_planes: unknown flags");
-  if (!d_in_ptrs || !d_in_bytes || !d_hists) return GHF_E_INVAL;
-  if (count == 0) return GHF_OK;
-  GHF_HIP(c, hipSetDevice(c->device));
-  BatchPlanesHistParams p;
-  p.in_ptrs = d_in_ptrs;
-  p.in_bytes = d_in_bytes;
-  p.max_item_bytes = max_item_bytes;
-  p.count = count;
-  p.hists = d_hists;
-  launch_histogram_batch_planes(p, elem_bytes, flags, c->stream);
-  GHF_HIP(c, hipGetLastError());
-  return GHF_OK;
-}
-
-int ghf_build_codes(ghf_ctx* c, const uint64_t* d_hists, uint32_t n_codes, ghf_code* d_codes, unsigned flags) {
-  if (!c || !d_hists || !d_codes || n_codes == 0 || n_codes > GHF_PLANES_MAX || (flags & ~(unsigned)(GHF_CODE_LIMIT | GHF_EMPTY_OK)))
-    return GHF_E_INVAL;
-  GHF_HIP(c, hipSetDevice(c->device));
-  launch_build_codes(d_hists, n_codes, d_codes, c->d_status, flags, c->stream);
-  GHF_HIP(c, hipGetLastError());
-  for (uint32_t k = 0; k < n_codes; ++k) {  // as ghf_build_code_ex: the tables changed, what was derived from them is stale
-    if (c->plan.code == d_codes + k) c->plan.forget();
-    if (c->prepared.describes(d_codes + k)) c->prepared.forget();
-  }
-  return GHF_OK;
-}
-
-size_t ghf_compress_batch_planes_shared_bound(size_t max_item_bytes, uint32_t elem_bytes) {
-  return planes_elem_ok(elem_bytes) ? ghf_compress_batch_shared_bound(max_item_bytes / elem_bytes) : 0;
-}
-
-// the index covers count * elem_bytes slots of max_item_bytes / elem_bytes symbols (the product fits: count is 32 bits wide)
-static bool planes_index_covers(const ghf_batch_index* ix, uint32_t count, uint32_t elem_bytes, size_t plane_symbols) {
-  return (uint64_t)count * elem_bytes <= 0xFFFFFFFFull && batch_index_covers(ix, count * elem_bytes, plane_symbols);
-}
-
-// a mask of raw planes names planes below elem_bytes only
-static inline bool planes_mask_ok(uint32_t raw_planes, uint32_t elem_bytes) { return (raw_planes >> elem_bytes) == 0; }
-
-// ghf_compress_batch_planes_shared (forms = false: its own kernel, no mask) and ghf_compress_batch_planes_forms
-static int compress_batch_planes(ghf_ctx* c, const std::string& who, bool forms, const uint8_t* const* d_in_ptrs, const uint64_t* d_in_bytes,
-                                 size_t max_item_bytes, uint32_t count, uint32_t elem_bytes, const ghf_code* d_codes, uint32_t raw_planes,
-                                 uint8_t* const* d_out_ptrs, const uint64_t* d_out_caps, uint64_t* d_out_bytes, const ghf_batch_index* index,
-                                 int* d_item_status) {
-  if (!c) return GHF_E_INVAL;
-  if (!planes_elem_ok(elem_bytes)) return fail(c, GHF_E_INVAL, (who + ": elem_bytes must be 2, 4 or 8").c_str());
-  if (!planes_item_ok(max_item_bytes, elem_bytes))
-    return fail(c, GHF_E_INVAL, (who + ": max_item_bytes must be 1 .. GHF_BATCH_MAX_ITEM and a multiple of elem_bytes").c_str());
-  if ((uint64_t)count * elem_bytes > 0xFFFFFFFFull) return fail(c, GHF_E_INVAL, (who + ": count * elem_bytes beyond 32 bits").c_str());
-  if (index && !planes_index_covers(index, count, elem_bytes, max_item_bytes / elem_bytes))
-    return fail(c, GHF_E_INVAL, (who + ": index does not cover (count * elem_bytes, max_item_bytes / elem_bytes)").c_str());
-  if (!d_codes || !aligned16(d_codes)) return fail(c, GHF_E_INVAL, (who + ": d_codes is null or not 16-byte aligned").c_str());
-  if (!planes_mask_ok(raw_planes, elem_bytes)) return fail(c, GHF_E_INVAL, (who + ": raw_planes names a plane at or above elem_bytes").c_str());
-  if (!d_in_ptrs || !d_in_bytes || !d_out_ptrs || !d_out_caps || !d_out_bytes || !d_item_status) return GHF_E_INVAL;
-  if (count == 0) return GHF_OK;
-  GHF_HIP(c, hipSetDevice(c->device));
-  BatchPlanesCompressParams p;
-  p.in_ptrs = d_in_ptrs;
-  p.in_bytes = d_in_bytes;
-  p.max_item_bytes = max_item_bytes;
-  p.codes = d_codes;
-  p.out_ptrs = d_out_ptrs;
-  p.out_caps = d_out_caps;
-  p.out_bytes = d_out_bytes;
-  p.chunk_bit = index ? index->d_chunk_bit : nullptr;
-  p.seg_bit = index ? index->d_seg_bit : nullptr;
-  p.blocks_per_item = index ? index->blocks_per_item : 0;
-  p.segs_per_item = index ? index->segs_per_item : 0;
-  p.item_status = d_item_status;
-  launch_compress_batch_planes(p, count, elem_bytes, forms, raw_planes, c->stream);
-  GHF_HIP(c, hipGetLastError());
-  return GHF_OK;
-}
-
-int ghf_compress_batch_planes_shared(ghf_ctx* c, const uint8_t* const* d_in_ptrs, const uint64_t* d_in_bytes, size_t max_item_bytes,
-                                     uint32_t count, uint32_t elem_bytes, const ghf_code* d_codes, uint8_t* const* d_out_ptrs,
-                                     const uint64_t* d_out_caps, uint64_t* d_out_bytes, const ghf_batch_index* index,
-                                     int* d_item_status) {
-  return compress_batch_planes(c, "ghf_compress_batch_planes_shared", false, d_in_ptrs, d_in_bytes, max_item_bytes, count, elem_bytes, d_codes,
-                               0, d_out_ptrs, d_out_caps, d_out_bytes, index, d_item_status);
-}
-
-int ghf_compress_batch_planes_forms(ghf_ctx* c, const uint8_t* const* d_in_ptrs, const uint64_t* d_in_bytes, size_t max_item_bytes,
-                                    uint32_t count, uint32_t elem_bytes, const ghf_code* d_codes, uint32_t raw_planes,
-                                    uint8_t* const* d_out_ptrs, const uint64_t* d_out_caps, uint64_t* d_out_bytes,
-                                    const ghf_batch_index* index, int* d_item_status) {
-  return compress_batch_planes(c, "ghf_compress_batch_planes_forms", true, d_in_ptrs, d_in_bytes, max_item_bytes, count, elem_bytes, d_codes,
-                               raw_planes, d_out_ptrs, d_out_caps, d_out_bytes, index, d_item_status);
-}
-
-int ghf_batch_planes_raw_auto(ghf_ctx* c, const uint64_t* d_hists, const ghf_code* d_codes, uint32_t elem_bytes, uint32_t* d_raw_planes) {
-  if (!c) return GHF_E_INVAL;
-  if (!planes_elem_ok(elem_bytes)) return fail(c, GHF_E_INVAL, "ghf_batch_planes_raw_auto: elem_bytes must be 2, 4 or 8");
-  if (!d_codes || !aligned16(d_codes)) return fail(c, GHF_E_INVAL, "ghf_batch_planes_raw_auto: d_codes is null or not 16-byte aligned");
-  if (!d_hists || !d_raw_planes) return GHF_E_INVAL;
-  GHF_HIP(c, hipSetDevice(c->device));
-  launch_batch_planes_raw_auto(d_hists, d_codes, elem_bytes, d_raw_planes, c->stream);
-  GHF_HIP(c, hipGetLastError());
-  return GHF_OK;
-}
-
-// ghf_decode_batch_planes_shared (forms = false) and ghf_decode_batch_planes_forms
-static int decode_batch_planes(ghf_ctx* c, const std::string& who, bool forms, const uint8_t* const* d_stream_ptrs,
-                               const uint64_t* d_stream_bytes, const ghf_code* d_codes, const ghf_batch_index* index, const uint64_t* d_n_elems,
-                               uint32_t count, uint32_t elem_bytes, uint32_t raw_planes, uint8_t* const* d_out_ptrs, const uint64_t* d_out_caps,
-                               uint64_t* d_out_bytes, int* d_item_status) {
-  if (!c || !index) return GHF_E_INVAL;
-  if (!planes_elem_ok(elem_bytes)) return fail(c, GHF_E_INVAL, (who + ": elem_bytes must be 2, 4 or 8").c_str());
-  if (!planes_index_covers(index, count, elem_bytes, 1))
-    return fail(c, GHF_E_INVAL, (who + ": index does not cover count * elem_bytes slots").c_str());
-  if (!d_codes || !aligned16(d_codes)) return fail(c, GHF_E_INVAL, (who + ": d_codes is null or not 16-byte aligned").c_str());
-  if (!planes_mask_ok(raw_planes, elem_bytes)) return fail(c, GHF_E_INVAL, (who + ": raw_planes names a plane at or above elem_bytes").c_str());
-  if (!d_stream_ptrs || !d_stream_bytes || !d_n_elems || !d_out_ptrs || !d_out_caps || !d_out_bytes || !d_item_status)
-    return GHF_E_INVAL;
-  if (count == 0) return GHF_OK;
-  GHF_HIP(c, hipSetDevice(c->device));
-  BatchPlanesDecodeParams p;
-  p.stream_ptrs = d_stream_ptrs;
-  p.stream_bytes = d_stream_bytes;
-  p.codes = d_codes;
-  p.chunk_bit = index->d_chunk_bit;
-  p.seg_bit = index->d_seg_bit;
-  p.blocks_per_item = index->blocks_per_item;
-  p.segs_per_item = index->segs_per_item;
-  p.max_plane_symbols = index->max_item_bytes;
-  p.n_elems = d_n_elems;
-  p.out_ptrs = d_out_ptrs;
-  p.out_caps = d_out_caps;
-  p.out_bytes = d_out_bytes;
-  p.item_status = d_item_status;
-  launch_decode_batch_planes(p, count, elem_bytes, forms, raw_planes, c->stream);
-  GHF_HIP(c, hipGetLastError());
-  return GHF_OK;
-}
-
-int ghf_decode_batch_planes_shared(ghf_ctx* c, const uint8_t* const* d_stream_ptrs, const uint64_t* d_stream_bytes,
-                                   const ghf_code* d_codes, const ghf_batch_index* index, const uint64_t* d_n_elems, uint32_t count,
-                                   uint32_t elem_bytes, uint8_t* const* d_out_ptrs, const uint64_t* d_out_caps, uint64_t* d_out_bytes,
-                                   int* d_item_status) {
-  return decode_batch_planes(c, "ghf_decode_batch_planes_shared", false, d_stream_ptrs, d_stream_bytes, d_codes, index, d_n_elems, count,
-                             elem_bytes, 0, d_out_ptrs, d_out_caps, d_out_bytes, d_item_status);
-}
-
-int ghf_decode_batch_planes_forms(ghf_ctx* c, const uint8_t* const* d_stream_ptrs, const uint64_t* d_stream_bytes, const ghf_code* d_codes,
-                                  const ghf_batch_index* index, const uint64_t* d_n_elems, uint32_t count, uint32_t elem_bytes,
-                                  uint32_t raw_planes, uint8_t* const* d_out_ptrs, const uint64_t* d_out_caps, uint64_t* d_out_bytes,
-                                  int* d_item_status) {
-  return decode_batch_planes(c, "ghf_decode_batch_planes_forms", true, d_stream_ptrs, d_stream_bytes, d_codes, index, d_n_elems, count,
-                             elem_bytes, raw_planes, d_out_ptrs, d_out_caps, d_out_bytes, d_item_status);
-}
-
-// ghf_decode_bodies_batch_planes_shared (forms = false) and ghf_decode_bodies_batch_planes_forms
-static int decode_bodies_batch_planes(ghf_ctx* c, const std::string& who, bool forms, const uint8_t* const* d_stream_ptrs,
-                                      const uint64_t* d_stream_bytes, const ghf_code* d_codes, uint32_t count, uint32_t elem_bytes,
-                                      uint32_t raw_planes, uint8_t* const* d_out_ptrs, const uint64_t* d_out_caps, uint64_t* d_out_bytes,
-                                      int* d_item_status) {
-  if (!c || !d_stream_ptrs || !d_stream_bytes || !d_out_bytes || !d_item_status) return GHF_E_INVAL;
-  if (!planes_elem_ok(elem_bytes)) return fail(c, GHF_E_INVAL, (who + ": elem_bytes must be 2, 4 or 8").c_str());
-  if (d_out_ptrs && !d_out_caps) return fail(c, GHF_E_INVAL, (who + ": d_out_ptrs without d_out_caps").c_str());
-  if (!d_codes || !aligned16(d_codes))
-    return fail(c, GHF_E_INVAL, (who + ": d_codes is null or not 16-byte aligned").c_str());
-  if (!planes_mask_ok(raw_planes, elem_bytes)) return fail(c, GHF_E_INVAL, (who + ": raw_planes names a plane at or above elem_bytes").c_str());
-  if (count == 0) return GHF_OK;
-  GHF_HIP(c, hipSetDevice(c->device));
-  BatchPlanesBodiesParams p;
-  p.stream_ptrs = d_stream_ptrs;
-  p.stream_bytes = d_stream_bytes;
-  p.max_stream_bytes = ghf_compress_batch_shared_bound(GHF_BATCH_MAX_ITEM);
-  p.codes = d_codes;
-  p.out_ptrs = d_out_ptrs;
-  p.out_caps = d_out_caps;
-  p.out_bytes = d_out_bytes;
-  p.item_status = d_item_status;
-  p.stats = c->images_stats;
-  launch_decode_bodies_batch_planes(p, count, elem_bytes, forms, raw_planes, c->stream);
-  GHF_HIP(c, hipGetLastError());
-  return GHF_OK;
-}
-
-int ghf_decode_bodies_batch_planes_shared(ghf_ctx* c, const uint8_t* const* d_stream_ptrs, const uint64_t* d_stream_bytes,
-                                          const ghf_code* d_codes, uint32_t count, uint32_t elem_bytes, uint8_t* const* d_out_ptrs,
-                                          const uint64_t* d_out_caps, uint64_t* d_out_bytes, int* d_item_status) {
-  return decode_bodies_batch_planes(c, "ghf_decode_bodies_batch_planes_shared", false, d_stream_ptrs, d_stream_bytes, d_codes, count, elem_bytes,
-                                    0, d_out_ptrs, d_out_caps, d_out_bytes, d_item_status);
-}
-
-int ghf_decode_bodies_batch_planes_forms(ghf_ctx* c, const uint8_t* const* d_stream_ptrs, const uint64_t* d_stream_bytes,
-                                         const ghf_code* d_codes, uint32_t count, uint32_t elem_bytes, uint32_t raw_planes,
-                                         uint8_t* const* d_out_ptrs, const uint64_t* d_out_caps, uint64_t* d_out_bytes, int* d_item_status) {
-  return decode_bodies_batch_planes(c, "ghf_decode_bodies_batch_planes_forms", true, d_stream_ptrs, d_stream_bytes, d_codes, count, elem_bytes,
-                                    raw_planes, d_out_ptrs, d_out_caps, d_out_bytes, d_item_status);
-}
-
-// ---------------------------------------------------------------------------------------------- stored shared-code bodies
-size_t ghf_batch_seek_bytes(size_t n_symbols) { return (size_t)batch_seek_bytes_for(n_symbols); }
-size_t ghf_batch_seek_bound(size_t max_item_bytes) { return (ghf_batch_seek_bytes(max_item_bytes) + 15) & ~(size_t)15; }
-
-int ghf_batch_seek_pack(ghf_ctx* c, const ghf_batch_index* index, const uint64_t* d_in_bytes, uint32_t count, uint32_t elem_bytes,
-                        uint8_t* const* d_rec_ptrs, const uint64_t* d_rec_caps, uint64_t* d_rec_bytes, int* d_slot_status) {
-  if (!c || !index) return GHF_E_INVAL;
-  if (elem_bytes != 1 && !planes_elem_ok(elem_bytes)) return fail(c, GHF_E_INVAL, "ghf_batch_seek_pack: elem_bytes must be 1, 2, 4 or 8");
-  if (!planes_index_covers(index, count, elem_bytes, 1))
-    return fail(c, GHF_E_INVAL, "ghf_batch_seek_pack: index does not cover count * elem_bytes slots (use ghf_batch_index_alloc)");
-  if (!d_in_bytes || !d_rec_ptrs || !d_rec_caps || !d_rec_bytes || !d_slot_status) return GHF_E_INVAL;
-  if (count == 0) return GHF_OK;
-  GHF_HIP(c, hipSetDevice(c->device));
-  BatchSeekPackParams p;
-  p.chunk_bit = index->d_chunk_bit;
-  p.seg_bit = index->d_seg_bit;
-  p.blocks_per_item = index->blocks_per_item;
-  p.segs_per_item = index->segs_per_item;
-  p.max_slice_symbols = index->max_item_bytes;
-  p.in_bytes = d_in_bytes;
-  p.elem_bytes = elem_bytes;
-  p.rec_ptrs = d_rec_ptrs;
-  p.rec_caps = d_rec_caps;
-  p.rec_bytes = d_rec_bytes;
-  p.slot_status = d_slot_status;
-  launch_batch_seek_pack(p, count * elem_bytes, c->stream);
-  GHF_HIP(c, hipGetLastError());
-  return GHF_OK;
-}
-
-// the two decoders of stored bodies: elem_bytes = 1 is the flat call
-static int decode_bodies_batch_seek(ghf_ctx* c, const char* who, const uint8_t* const* d_stream_ptrs, const uint64_t* d_stream_bytes,
-                                    const uint8_t* const* d_rec_ptrs, const uint64_t* d_rec_bytes, const ghf_code* d_codes, uint32_t count,
-                                    uint32_t elem_bytes, uint8_t* const* d_out_ptrs, const uint64_t* d_out_caps, uint64_t* d_out_bytes,
-                                    int* d_item_status, bool forms = false, uint32_t raw_planes = 0) {
-  if (!c || !d_stream_ptrs || !d_stream_bytes || !d_rec_ptrs || !d_rec_bytes || !d_out_bytes || !d_item_status) return GHF_E_INVAL;
-  if (elem_bytes != 1 && !planes_elem_ok(elem_bytes)) return fail(c, GHF_E_INVAL, (std::string(who) + ": elem_bytes must be 2, 4 or 8").c_str());
-  if (d_out_ptrs && !d_out_caps) return fail(c, GHF_E_INVAL, (std::string(who) + ": d_out_ptrs without d_out_caps").c_str());
-  if (!d_codes || !aligned16(d_codes)) return fail(c, GHF_E_INVAL, (std::string(who) + ": the code array is null or not 16-byte aligned").c_str());
-  if (forms && !planes_mask_ok(raw_planes, elem_bytes))
-    return fail(c, GHF_E_INVAL, (std::string(who) + ": raw_planes names a plane at or above elem_bytes").c_str());
-  if (count == 0) return GHF_OK;
-  GHF_HIP(c, hipSetDevice(c->device));
-  BatchSeekDecodeParams p;
-  p.stream_ptrs = d_stream_ptrs;
-  p.stream_bytes = d_stream_bytes;
-  p.rec_ptrs = d_rec_ptrs;
-  p.rec_bytes = d_rec_bytes;
-  p.max_stream_bytes = ghf_compress_batch_shared_bound(GHF_BATCH_MAX_ITEM);
-  p.codes = d_codes;
-  p.out_ptrs = d_out_ptrs;
-  p.out_caps = d_out_caps;
-  p.out_bytes = d_out_bytes;
-  p.item_status = d_item_status;
-  launch_decode_bodies_batch_seek(p, count, elem_bytes, forms, raw_planes, c->stream);
-  GHF_HIP(c, hipGetLastError());
-  return GHF_OK;
-}
-
-int ghf_decode_bodies_batch_shared_seek(ghf_ctx* c, const uint8_t* const* d_stream_ptrs, const uint64_t* d_stream_bytes,
-                                        const uint8_t* const* d_rec_ptrs, const uint64_t* d_rec_bytes, const ghf_code* d_code,
-                                        uint32_t count, uint8_t* const* d_out_ptrs, const uint64_t* d_out_caps, uint64_t* d_out_bytes,
-                                        int* d_item_status) {
-  return decode_bodies_batch_seek(c, "ghf_decode_bodies_batch_shared_seek", d_stream_ptrs, d_stream_bytes, d_rec_ptrs, d_rec_bytes, d_code,
-                                  count, 1, d_out_ptrs, d_out_caps, d_out_bytes, d_item_status);
-}
-
-int ghf_decode_bodies_batch_planes_shared_seek(ghf_ctx* c, const uint8_t* const* d_stream_ptrs, const uint64_t* d_stream_bytes,
-                                               const uint8_t* const* d_rec_ptrs, const uint64_t* d_rec_bytes, const ghf_code* d_codes,
-                                               uint32_t count, uint32_t elem_bytes, uint8_t* const* d_out_ptrs,
-                                               const uint64_t* d_out_caps, uint64_t* d_out_bytes, int* d_item_status) {
-  if (c && !planes_elem_ok(elem_bytes))
-    return fail(c, GHF_E_INVAL, "ghf_decode_bodies_batch_planes_shared_seek: elem_bytes must be 2, 4 or 8");
-  return decode_bodies_batch_seek(c, "ghf_decode_bodies_batch_planes_shared_seek", d_stream_ptrs, d_stream_bytes, d_rec_ptrs, d_rec_bytes,
-                                  d_codes, count, elem_bytes, d_out_ptrs, d_out_caps, d_out_bytes, d_item_status);
-}
-
-int ghf_decode_bodies_batch_planes_forms_seek(ghf_ctx* c, const uint8_t* const* d_stream_ptrs, const uint64_t* d_stream_bytes,
-                                              const uint8_t* const* d_rec_ptrs, const uint64_t* d_rec_bytes, const ghf_code* d_codes,
-                                              uint32_t count, uint32_t elem_bytes, uint32_t raw_planes, uint8_t* const* d_out_ptrs,
-                                              const uint64_t* d_out_caps, uint64_t* d_out_bytes, int* d_item_status) {
-  if (c && !planes_elem_ok(elem_bytes))
-    return fail(c, GHF_E_INVAL, "ghf_decode_bodies_batch_planes_forms_seek: elem_bytes must be 2, 4 or 8");
-  return decode_bodies_batch_seek(c, "ghf_decode_bodies_batch_planes_forms_seek", d_stream_ptrs, d_stream_bytes, d_rec_ptrs, d_rec_bytes,
-                                  d_codes, count, elem_bytes, d_out_ptrs, d_out_caps, d_out_bytes, d_item_status, true, raw_planes);
-}
 
 // ---------------------------------------------------------------------------------------------- decode
 static inline uint32_t be32(const uint8_t* p) {

@@ -13,7 +13,6 @@ using namespace ghf;
 
 namespace {
 
-inline bool elem_bytes_ok(uint32_t e) { return e == 2 || e == 4 || e == 8; }
 inline bool elems_overflow(size_t n_elems, uint32_t e) { return n_elems > (size_t)-1 / e; }
 // ... and for the calls that go through the workspace, whose planes sit at n_elems rounded up to 256
 inline bool workspace_overflow(size_t n_elems, uint32_t e) { return elems_overflow(n_elems, e) || elems_overflow(n_elems + 255, e); }
@@ -84,15 +83,6 @@ struct PlaneForms {
     return sparse_planes == GHF_SPARSE_AUTO || (raw_planes & sparse_planes) == 0;
   }
 };
-
-// what a call that queues one launch does around it
-template <class Launch>
-int queued(ghf_ctx* c, Launch launch) {
-  GHF_HIP(c, hipSetDevice(c->device));
-  launch();
-  GHF_HIP(c, hipGetLastError());
-  return GHF_OK;
-}
 
 // ---- the workspaces ------------------------------------------------------------------------------------------------------------
 // the context's plane workspace for n_elems elements (workspace_overflow has cleared them): *stride <- the distance

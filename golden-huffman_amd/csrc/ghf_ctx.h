@@ -1,6 +1,6 @@
 // golden-huffman_amd/csrc/ghf_ctx.h -- the context behind the C ABI of include/ghf.h.  Host-only and private to the ABI
-// units (ghf_api.hip, ghf_api_planes.hip, ghf_comm.hip): what a ghf_ctx owns on the device, what its workspace currently
-// describes, and the few host helpers more than one of those units asks for.
+// units (ghf_api.hip, ghf_api_batch.hip, ghf_api_planes.hip, ghf_comm.hip): what a ghf_ctx owns on the device, what its
+// workspace currently describes, and the few host helpers more than one of those units asks for.
 #ifndef GHF_CTX_H_
 #define GHF_CTX_H_
 #include <algorithm>
@@ -194,8 +194,19 @@ int grow(ghf_ctx* c, DevBuf<T>& b, size_t need, size_t floor = 0, bool* replaced
   return GHF_OK;
 }
 
-// ---- what ghf_api.hip and ghf_api_planes.hip both ask ------------------------------------------------------------------
+// ---- what more than one of ghf_api.hip, ghf_api_batch.hip and ghf_api_planes.hip ask ------------------------------------
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+// the element widths that have byte-plane kernels
+inline bool elem_bytes_ok(uint32_t e) { return e == 2 || e == 4 || e == 8; }
+
+// what a call that queues one launch does around it
+template <class Launch>
+int queued(ghf_ctx* c, Launch launch) {
+  GHF_HIP(c, hipSetDevice(c->device));
+  launch();
+  GHF_HIP(c, hipGetLastError());
+  return GHF_OK;
+}
 
 // the part of "this side-car is one of ours" that packing and decoding both ask for
 inline bool index_has_arrays(const ghf_index* ix) {
