@@ -586,6 +586,10 @@ static int settle_boundaries(ghf_ctx* c, SyncParams& p, uint8_t* scan_ws, const 
   // the stride of the scan's function rows (launch_sync_scan): a shallow code does not pay for 64-byte rows
   const uint32_t stride = (q.max_len >= 1 && q.max_len <= 16) ? 16u : (q.max_len > 32 ? 64u : 32u);
   bool scanned = q.first_start >= stride;  // (the scan follows entry offsets below its stride only: such a piece counts as seeded)
+  // (An entry offset in [max_len, stride) -- no true boundary lies there, only a caller's wrong guess -- indexes a row entry
+  //  that k_sync_table does not write: class rows hold counts there, other rows whatever the workspace held.  The scan then
+  //  seeds start[] with values that depend on stale memory; the passes repair them, one subsequence per pass, within the bound
+  //  below, so the result is right and only the number of passes varies.)
   const bool scan_first = q.scan_at_once && !scanned;
   p.first = scan_first ? 0u : 3u;
   p.first_start = q.first_start;
