@@ -175,6 +175,11 @@ int ghf_ctx_destroy(ghf_ctx* c) {
   release(c->batch_codes);
   release(c->planes);
   release(c->sparse);
+  release(c->tensor_slots);
+  release(c->tensor_ranks);
+  release(c->tensor_sizes);
+  release(c->tensor_chunk_bit);
+  release(c->tensor_seg_bit);
   if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
   delete c;
   return GHF_OK;

@@ -43,46 +43,7 @@ struct RankOut {
 };
 inline RankOut no_ranks() { return {false, nullptr, 0}; }
 
-// ---- THE SLOT RULE (DESIGN.md sections 20 and 23) ----------------------------------------------------------------------------
-// A tensor of E = elem_bytes planes is stored in 2 E slots.  Slot p < E is plane p's own: a raw plane lies there as its n_elems
-// bytes and has no code, index or table; a dense plane as its .crs2 image of n_elems symbols; a sparse plane as the image of its
-// mask, ghf_sparse_mask_bytes(n_elems) symbols.  Slot E + p holds the image of a sparse plane's values, h_n_vals[p] symbols,
-// where it has any, and is empty otherwise.  Every driver asks this type which slots hold what; none reads a mask itself.
-struct PlaneForms {
-  uint32_t elem_bytes;
-  unsigned raw_planes, sparse_planes;  // a bit per plane, as asked for (then GHF_*_AUTO may stand in their place) or as chosen
-  size_t n_elems;
-  const size_t* h_n_vals;  // per plane, where the call has them; read for sparse planes only
-
-  bool is_raw(uint32_t p) const { return ((raw_planes >> p) & 1u) != 0; }
-  bool is_sparse(uint32_t p) const { return ((sparse_planes >> p) & 1u) != 0; }
-  void store_raw(uint32_t p) { raw_planes |= 1u << p; }
-  void store_sparse(uint32_t p) { sparse_planes |= 1u << p; }
-  bool all_raw() const { return raw_planes == (1u << elem_bytes) - 1u; }
-  size_t mask_bytes() const { return ghf_sparse_mask_bytes(n_elems); }
-  // the symbols slot j holds (the bytes, where its plane is raw); 0 behind the planes' own slots: the slot is empty
-  size_t symbols(uint32_t j) const {
-    const uint32_t p = j % elem_bytes;
-    if (j < elem_bytes) return is_sparse(p) ? mask_bytes() : n_elems;
-    return is_sparse(p) ? h_n_vals[p] : 0;
-  }
-  bool stored(uint32_t j) const { return j < elem_bytes || symbols(j) != 0; }
-  // ... as a .crs2 image: with a code, and with a side-car or a seek table where the call has them
-  bool coded(uint32_t j) const { return stored(j) && !is_raw(j % elem_bytes); }
-
-  // sparse_planes as the compress call (GHF_SPARSE_AUTO alone, or bits below elem_bytes) or the decode (bits only) takes it
-  bool sparse_planes_ok(bool may_be_auto) const {
-    if (sparse_planes == GHF_SPARSE_AUTO) return may_be_auto;
-    return (sparse_planes >> elem_bytes) == 0;
-  }
-  // raw_planes beside sparse_planes: GHF_RAW_AUTO alone where the call may choose, or bits below elem_bytes; a plane has one
-  // form, so where both masks are explicit they share no bit
-  bool forms_ok(bool may_be_auto) const {
-    if (raw_planes == GHF_RAW_AUTO) return may_be_auto;
-    if ((raw_planes >> elem_bytes) != 0) return false;
-    return sparse_planes == GHF_SPARSE_AUTO || (raw_planes & sparse_planes) == 0;
-  }
-};
+// THE SLOT RULE (PlaneForms: which of the 2 E slots hold what) stands in ghf_ctx.h: the container calls of ghf_api_tensor.hip ask it too.
 
 // ---- the workspaces ------------------------------------------------------------------------------------------------------------
 // the context's plane workspace for n_elems elements (workspace_overflow has cleared them): *stride <- the distance
@@ -141,11 +102,32 @@ void free_indexes(ghf_ctx* c, ghf_index* ix, uint32_t count) {
 
 // the side-cars a compress call hands out (h_indexes may be null: none): one per stream that has a code, of that stream's own
 // symbol count; the other entries stay zero.  Nothing is left allocated behind a failure
-int alloc_sidecars(ghf_ctx* c, const PlaneForms& forms, ghf_index* h_indexes) {
+// pooled (ghf_compress_tensor): the side-cars are views into ONE pair of arrays of the context, which grows on demand
+int alloc_sidecars(ghf_ctx* c, const PlaneForms& forms, ghf_index* h_indexes, bool pooled = false) {
   if (!h_indexes) return GHF_OK;
   const uint32_t E = forms.elem_bytes;
   std::memset(h_indexes, 0, 2 * E * sizeof *h_indexes);
   int rc = GHF_OK;
+  if (pooled) {
+    // every view begins 16-byte aligned: a stream's blocks rounded up to 2 words of 8 bytes, its segments to 4 of 4
+    const auto blocks_of = [&](uint32_t j) { return ((size_t)blocks_for(forms.symbols(j)) + 1) & ~(size_t)1; };
+    const auto segs_of = [&](uint32_t j) { return ((size_t)segs_for(forms.symbols(j)) + 3) & ~(size_t)3; };
+    size_t blocks = 0, segs = 0;
+    for (uint32_t j = 0; j < 2 * E; ++j)
+      if (forms.coded(j)) blocks += blocks_of(j), segs += segs_of(j);
+    if ((rc = grow(c, c->tensor_chunk_bit, std::max<size_t>(blocks, 1)))) return rc;
+    if ((rc = grow(c, c->tensor_seg_bit, std::max<size_t>(segs, 1)))) return rc;
+    blocks = segs = 0;
+    for (uint32_t j = 0; j < 2 * E; ++j) {
+      if (!forms.coded(j)) continue;
+      index_shape(forms.symbols(j), &h_indexes[j]);
+      h_indexes[j].d_chunk_bit = c->tensor_chunk_bit.p + blocks;
+      h_indexes[j].d_seg_bit = c->tensor_seg_bit.p + segs;
+      blocks += blocks_of(j);
+      segs += segs_of(j);
+    }
+    return GHF_OK;
+  }
   for (uint32_t p = 0; p < E && !rc; ++p)
     for (uint32_t j = p; j < 2 * E && !rc; j += E)
       if (forms.coded(j)) rc = ghf_index_alloc(c, forms.symbols(j), &h_indexes[j]);
@@ -1022,8 +1004,20 @@ int ghf_compress_planes_forms(ghf_ctx* c, const uint8_t* d_in, const uint8_t* d_
                               unsigned raw_planes, unsigned sparse_planes, uint8_t* d_out, size_t slot_bytes, uint64_t* d_out_bytes,
                               ghf_code* d_codes, ghf_index* h_indexes, uint8_t* d_ranks, size_t rank_slot_bytes, unsigned* h_raw_planes,
                               unsigned* h_sparse_planes, size_t* h_n_vals) {
+  return compress_planes_forms(c, "ghf_compress_planes_forms", d_in, d_base, n_elems, elem_bytes, raw_planes, sparse_planes, d_out,
+                               slot_bytes, d_out_bytes, d_codes, h_indexes, false, d_ranks, rank_slot_bytes, h_raw_planes, h_sparse_planes,
+                               h_n_vals);
+}
+
+}  // extern "C"
+
+// the driver of the call above, under the caller's name: ghf_compress_tensor (ghf_api_tensor.hip) runs it with pooled side-cars
+int ghf::compress_planes_forms(ghf_ctx* c, const char* who, const uint8_t* d_in, const uint8_t* d_base, size_t n_elems, uint32_t elem_bytes,
+                               unsigned raw_planes, unsigned sparse_planes, uint8_t* d_out, size_t slot_bytes, uint64_t* d_out_bytes,
+                               ghf_code* d_codes, ghf_index* h_indexes, bool pooled, uint8_t* d_ranks, size_t rank_slot_bytes,
+                               unsigned* h_raw_planes, unsigned* h_sparse_planes, size_t* h_n_vals) {
   if (!c || !d_in || !d_out || !d_out_bytes || !h_raw_planes || !h_sparse_planes || !h_n_vals) return GHF_E_INVAL;
-  const std::string f = "ghf_compress_planes_forms: ";
+  const std::string f = std::string(who) + ": ";
   const uint32_t E = elem_bytes;
   const PlaneForms asked = {E, raw_planes, sparse_planes, n_elems, h_n_vals};
   const RankOut ranks = {d_ranks != nullptr, d_ranks, rank_slot_bytes};  // optional too
@@ -1077,7 +1071,7 @@ int ghf_compress_planes_forms(ghf_ctx* c, const uint8_t* d_in, const uint8_t* d_
   if (!forms.all_raw()) rc = planes_workspace(c, n_elems, E, &stride);
   if (!rc && forms.sparse_planes) rc = sparse_workspace(c, n_elems, &mask_stride);
   if (rc) return rc;
-  if ((rc = alloc_sidecars(c, forms, h_indexes))) return rc;
+  if ((rc = alloc_sidecars(c, forms, h_indexes, pooled))) return rc;
   GHF_HIP(c, hipMemsetAsync(d_out_bytes, 0, 2 * E * sizeof(uint64_t), c->stream));  // the empty slots
   const SlotsOut out = {d_out, slot_bytes, d_out_bytes, codes, h_indexes};
   // the split writes a raw plane straight into its slot and every other plane into the workspace
@@ -1113,6 +1107,8 @@ int ghf_compress_planes_forms(ghf_ctx* c, const uint8_t* d_in, const uint8_t* d_
   c->plan.forget();
   return rc;
 }
+
+extern "C" {
 
 int ghf_decode_planes_forms(ghf_ctx* c, const uint8_t* const* h_stream_ptrs, const size_t* h_stream_bytes, const ghf_code* d_codes,
                             const ghf_index* indexes, const uint8_t* d_base, unsigned raw_planes, unsigned sparse_planes,

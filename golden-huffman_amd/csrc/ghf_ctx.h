@@ -1,5 +1,5 @@
 // golden-huffman_amd/csrc/ghf_ctx.h -- the context behind the C ABI of include/ghf.h.  Host-only and private to the ABI
-// units (ghf_api.hip, ghf_api_batch.hip, ghf_api_planes.hip, ghf_comm.hip): what a ghf_ctx owns on the device, what its
+// units (ghf_api.hip, ghf_api_batch.hip, ghf_api_planes.hip, ghf_api_tensor.hip, ghf_comm.hip): what a ghf_ctx owns on the device, what its
 // workspace currently describes, and the few host helpers more than one of those units asks for.
 #ifndef GHF_CTX_H_
 #define GHF_CTX_H_
@@ -103,6 +103,47 @@ struct RebuiltIndex {
   void forget() { stream = nullptr; }
 };
 
+// ---- THE SLOT RULE (DESIGN.md sections 20 and 23) ----------------------------------------------------------------------------
+// A tensor of E = elem_bytes planes is stored in 2 E slots.  Slot p < E is plane p's own: a raw plane lies there as its n_elems
+// bytes and has no code, index or table; a dense plane as its .crs2 image of n_elems symbols; a sparse plane as the image of its
+// mask, ghf_sparse_mask_bytes(n_elems) symbols.  Slot E + p holds the image of a sparse plane's values, h_n_vals[p] symbols,
+// where it has any, and is empty otherwise.  Every driver asks this type which slots hold what; none reads a mask itself.
+struct PlaneForms {
+  uint32_t elem_bytes;
+  unsigned raw_planes, sparse_planes;  // a bit per plane, as asked for (then GHF_*_AUTO may stand in their place) or as chosen
+  size_t n_elems;
+  const size_t* h_n_vals;  // per plane, where the call has them; read for sparse planes only
+
+  bool is_raw(uint32_t p) const { return ((raw_planes >> p) & 1u) != 0; }
+  bool is_sparse(uint32_t p) const { return ((sparse_planes >> p) & 1u) != 0; }
+  void store_raw(uint32_t p) { raw_planes |= 1u << p; }
+  void store_sparse(uint32_t p) { sparse_planes |= 1u << p; }
+  bool all_raw() const { return raw_planes == (1u << elem_bytes) - 1u; }
+  size_t mask_bytes() const { return ghf_sparse_mask_bytes(n_elems); }
+  // the symbols slot j holds (the bytes, where its plane is raw); 0 behind the planes' own slots: the slot is empty
+  size_t symbols(uint32_t j) const {
+    const uint32_t p = j % elem_bytes;
+    if (j < elem_bytes) return is_sparse(p) ? mask_bytes() : n_elems;
+    return is_sparse(p) ? h_n_vals[p] : 0;
+  }
+  bool stored(uint32_t j) const { return j < elem_bytes || symbols(j) != 0; }
+  // ... as a .crs2 image: with a code, and with a side-car or a seek table where the call has them
+  bool coded(uint32_t j) const { return stored(j) && !is_raw(j % elem_bytes); }
+
+  // sparse_planes as the compress call (GHF_SPARSE_AUTO alone, or bits below elem_bytes) or the decode (bits only) takes it
+  bool sparse_planes_ok(bool may_be_auto) const {
+    if (sparse_planes == GHF_SPARSE_AUTO) return may_be_auto;
+    return (sparse_planes >> elem_bytes) == 0;
+  }
+  // raw_planes beside sparse_planes: GHF_RAW_AUTO alone where the call may choose, or bits below elem_bytes; a plane has one
+  // form, so where both masks are explicit they share no bit
+  bool forms_ok(bool may_be_auto) const {
+    if (raw_planes == GHF_RAW_AUTO) return may_be_auto;
+    if ((raw_planes >> elem_bytes) != 0) return false;
+    return sparse_planes == GHF_SPARSE_AUTO || (raw_planes & sparse_planes) == 0;
+  }
+};
+
 }  // namespace ghf
 
 struct ghf_ctx {
@@ -159,6 +200,14 @@ struct ghf_ctx {
   ghf::DevBuf<uint8_t> sparse;
   // ghf_decode_images_batch_stats: where the image decoder counts its rounds and passes (the caller's; null = nowhere)
   uint64_t* images_stats = nullptr;
+  // ghf_compress_tensor: what ghf_compress_planes_forms leaves for ghf_tensor_pack -- the 2 E slots, the
+  // E rank slots, the 2 E device sizes, and ONE pair of arrays that the side-cars of all stored streams are carved from.
+  // Private to the call; they describe nothing between calls and grow on demand
+  ghf::DevBuf<uint8_t> tensor_slots;
+  ghf::DevBuf<uint8_t> tensor_ranks;
+  ghf::DevBuf<uint64_t> tensor_sizes;
+  ghf::DevBuf<uint64_t> tensor_chunk_bit;
+  ghf::DevBuf<uint32_t> tensor_seg_bit;
   std::string err;
 };
 
@@ -250,6 +299,15 @@ SeekExpandParams seek_expand_params(ghf_ctx* c, const ghf_seek_info* info, const
 // Symbol g * kBlockSymbols lands at out[0]
 DecParams range_decode_params(ghf_ctx* c, const uint8_t* d_stream, size_t stream_bytes, DecTables* dt, const uint64_t* chunk_bit,
                               const uint32_t* seg_bit, uint64_t g, uint64_t end, uint64_t n, uint32_t index_flags, uint8_t* out);
+
+// ---- planes in three forms with the context's own side-cars (defined in ghf_api_planes.hip) ---------------------------------------
+// ghf_compress_planes_forms under the name `who`.  pooled: the side-cars handed out in h_indexes are views into the context's
+// tensor_chunk_bit / tensor_seg_bit, which grow on demand -- nothing is allocated per stream and nothing is the caller's to free;
+// they are good until the next pooled call on the context.  Not pooled: ghf_index_alloc per stream, as the public call says
+int compress_planes_forms(ghf_ctx* c, const char* who, const uint8_t* d_in, const uint8_t* d_base, size_t n_elems, uint32_t elem_bytes,
+                          unsigned raw_planes, unsigned sparse_planes, uint8_t* d_out, size_t slot_bytes, uint64_t* d_out_bytes,
+                          ghf_code* d_codes, ghf_index* h_indexes, bool pooled, uint8_t* d_ranks, size_t rank_slot_bytes,
+                          unsigned* h_raw_planes, unsigned* h_sparse_planes, size_t* h_n_vals);
 
 }  // namespace ghf
 #endif

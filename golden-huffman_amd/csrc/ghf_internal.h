@@ -596,5 +596,47 @@ struct PlanesGatherFormsParams {
 void launch_decode_planes_gather_forms(const PlanesGatherFormsParams& p, uint32_t elem_bytes, uint32_t raw_planes, uint32_t sparse_planes,
                                        hipStream_t s);
 
+// ghf_tensor.hip: the container GHFTENS1 of one typed tensor.  A 768-byte head -- 128 bytes of fields,
+// then a directory of 40 {u64 offset, u64 bytes}: entries 0 .. 15 the stored streams by slot, 16 .. 31 their seek tables, 32 .. 39
+// the rank tables by plane -- and behind it the seek tables, the rank tables and the streams, each section 16-byte aligned and
+// zero-padded to the next.  The tables' sizes are the host's, the streams' only the device's.
+constexpr uint32_t kTensorHeadBytes = GHF_TENSOR_HEAD_BYTES;
+constexpr uint32_t kTensorSlots = 2 * GHF_PLANES_MAX;
+constexpr uint32_t kTensorFixed = kTensorSlots + GHF_PLANES_MAX;  // the directory entries whose sizes the host knows
+constexpr uint64_t kTensorMagic = 0x31534E4554464847ull;          // "GHFTENS1"
+constexpr uint32_t kTensorVersion = 1;
+constexpr uint32_t kTensorPackGroups = 4096;  // the most slabs of the copy: 16 workgroups of 4 waves per CU, as k_stream_copy
+struct TensorPackParams {
+  const uint8_t* streams[kTensorSlots];  // slot j where it lies now (16-byte aligned, readable to its size rounded up to 16)
+  const uint64_t* stream_bytes;          // DEVICE [2 * elem_bytes]: the streams' sizes
+  uint32_t stored;                       // bit j: slot j holds a stream
+  uint32_t elem_bytes, raw_planes, sparse_planes, flags;
+  uint64_t n_elems;
+  uint64_t n_vals[GHF_PLANES_MAX];       // as the head states them: 0 for a plane that is not sparse
+  uint64_t fixed_off[kTensorFixed], fixed_bytes[kTensorFixed];  // directory entries 16 .. 39 ({0, 0}: absent); bytes % 8 == 0
+  uint64_t streams_off;                  // where the stream region begins: the end of the host-known part
+  uint8_t* out;                          // the container, 16-byte aligned
+  uint64_t cap;
+  uint64_t* out_bytes;                   // <- total_bytes, also when it exceeds cap
+  int* status;
+};
+// one launch of `groups` workgroups (1 .. kTensorPackGroups); no workgroup waits for another
+void launch_tensor_pack(const TensorPackParams& p, uint32_t groups, hipStream_t s);
+// one workgroup per stored stream that has a code: every offset + bytes lies inside the container (the host's parse)
+struct TensorOpenParams {
+  const uint8_t* container;
+  uint32_t n_streams;
+  uint32_t slot[kTensorSlots];  // workgroup b vets the stream of slot[b] and fills codes[slot[b]]
+  uint64_t stream_off[kTensorSlots], stream_bytes[kTensorSlots];
+  uint64_t table_off[kTensorSlots], symbols[kTensorSlots];  // its seek table and the symbols the head gives the stream
+  uint64_t rank_off[kTensorSlots], rank_n_vals[kTensorSlots];  // a mask's workgroup: its plane's rank table (0: none)
+  uint64_t n_elems;
+  ghf_code* codes;  // [2 * elem_bytes], all zero when the kernel starts
+  int* status;
+};
+void launch_tensor_open(const TensorOpenParams& p, hipStream_t s);  // nothing is queued when n_streams == 0
+// *d_dst <- value, unless *d_status is non-zero
+void launch_tensor_store_size(uint64_t* d_dst, uint64_t value, const int* d_status, hipStream_t s);
+
 }  // namespace ghf
 #endif

@@ -1502,4 +1502,13 @@ int ghf_decode_planes_sparse_delta(ghf_ctx* ctx, const uint8_t* const* h_stream_
 #ifdef __cplusplus
 }
 #endif
+
+/* ---- one stored object per typed tensor: the container GHFTENS1 ----------------------------
+ * Everything above stores a typed tensor as slots, device sizes, codes, side-cars, rank tables, two masks and value counts
+ * that the caller keeps.  The calls of this section keep all of it in ONE contiguous, self-describing, relocatable image:
+ * bound, pack, compress, workspace release, parse, open, close, describe, decode, range decode and gather of a tensor container.  No
+ * reference counterpart.  The declarations stand in include/ghf_tensor.h, which this header includes here, as their
+ * binding stands in a Python module of its own (golden-huffman_amd/ghf_tensor.py) beside the recorded one. */
+#include "ghf_tensor.h"
+
 #endif /* GHF_H_ */
