@@ -9,14 +9,15 @@
   d  ONE ghf_compress / ghf_decode of the concatenation: the ceiling
 
 Reported per item (a, b: call time / items; c: loop time / looped items) with the ratios c / a and the fraction of d's
-throughput that a and b reach.  Device events around every call, variants interleaved within each repeat, every variant
-warmed up first and checked once (batch images against the looped single-stream images, decodes against the input).
-Prints one JSON document; --out also writes it to a file."""
+throughput that a and b reach.  Every variant is checked once (batch images against the looped single-stream images,
+decodes against the input).  Recipe: tools/benchkit.py, without the cache sweep.  Prints one JSON document; --out also
+writes it to a file."""
 import argparse
-import json
+import functools
 import os
-import statistics
 import sys
+
+import benchkit
 
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 sys.path.insert(0, ROOT)
@@ -27,10 +28,8 @@ def main():
     ap.add_argument("--mib", type=int, default=256)
     ap.add_argument("--item-kib", default="4,64,1024")
     ap.add_argument("--loop-items", type=int, default=256)
-    ap.add_argument("--reps", type=int, default=10)
-    ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--kinds", default="uniform,zipf")
-    ap.add_argument("--out", default=None)
+    benchkit.add_args(ap, reps=10, warmup=2, out=None)
     args = ap.parse_args()
 
     import importlib
@@ -45,25 +44,9 @@ def main():
     assert torch.cuda.is_available(), "batch_bench needs the GPU: there is nothing to fall back to"
     ctx = ghf.Context(0)
     n = args.mib << 20
-    res = {"device": torch.cuda.get_device_name(0), "mib": args.mib, "reps": args.reps, "warmup": args.warmup,
-           "loop_items": args.loop_items, "lib": ghf.lib_identity(), "unit": "ms (device events)", "kinds": {}}
-
-    def timed(variants):
-        for _ in range(args.warmup):
-            for _, fn in variants:
-                fn()
-        ctx.sync()
-        times = {name: [] for name, _ in variants}
-        for _ in range(args.reps):
-            for name, fn in variants:
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-                fn()
-                e1.record()
-                e1.synchronize()
-                times[name].append(e0.elapsed_time(e1))
-        ctx.sync()
-        return {k: statistics.median(v) for k, v in times.items()}, times
+    res = benchkit.envelope(torch, ghf, args, "ms (device events)")
+    res.update({"mib": args.mib, "loop_items": args.loop_items, "kinds": {}})
+    timed = functools.partial(benchkit.timed, reps=args.reps, warmup=args.warmup, sync=ctx.sync)
 
     for kind in args.kinds.split(","):
         d_in = synth.make(torch, kind, n, offset=0, device="cuda")
@@ -83,8 +66,8 @@ def main():
         v_d_dec()
         ctx.sync()
         assert torch.equal(d_back_all[:n], d_in), kind
-        med_d, _ = timed([("d_compress", v_d_comp), ("d_decode", v_d_dec)])
-        kres = {"one_stream_ms": {k: round(v, 4) for k, v in med_d.items()}, "stream_bytes": nb_all, "items": {}}
+        med_d, times_d = timed([("d_compress", v_d_comp), ("d_decode", v_d_dec)])
+        kres = {"one_stream_ms": benchkit.stats(times_d)["median_ms"], "stream_bytes": nb_all, "items": {}}
 
         for kib in [int(x) for x in args.item_kib.split(",")]:
             item = kib << 10
@@ -155,9 +138,7 @@ def main():
             kres["items"]["%dKiB" % kib] = {
                 "count": count,
                 "looped_items": k,
-                "median_ms": {x: round(v, 4) for x, v in med.items()},
-                "min_ms": {x: round(min(v), 4) for x, v in times.items()},
-                "max_ms": {x: round(max(v), 4) for x, v in times.items()},
+                **benchkit.stats(times),
                 "per_item_us": {x: round(v, 3) for x, v in per_item_us.items()},
                 "gb_per_s": {"a": round(n / med["a"] / 1e6, 2), "b": round(n / med["b"] / 1e6, 2),
                              "c_compress": round(k * item / med["c_compress"] / 1e6, 3),
@@ -177,12 +158,7 @@ def main():
         ctx.index_free(idx_all)
         del d_in, d_stream_all, d_back_all
     ctx.close()
-    text = json.dumps(res, indent=1)
-    print(text)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            f.write(text + "\n")
+    benchkit.write(res, args.out)
 
 
 if __name__ == "__main__":

@@ -10,15 +10,16 @@ ghf_histogram_batch(COVER_ALL) + ghf_build_code + ghf_compress_batch_shared.  Th
   b1   ghf_decode_batch_shared with the live side-car              (b' of the issue: the floor, gone with the process)
 
 REQUIRED: g < h at every size and input.  g / e, g / b1 and g0 / g are reported without a requirement, and so are the
-passes per round of g (the words of ghf_decode_images_batch_stats).  Device events around every call, variants
-interleaved within each repeat, every variant warmed up first and checked once against the input.
-Prints one JSON document; --out also writes it to a file.  Exit status 1 when a required row fails."""
+passes per round of g (the words of ghf_decode_images_batch_stats).  Every variant is checked once against the input.
+Recipe: tools/benchkit.py, without the cache sweep.  Prints one JSON document; --out also writes it to a file.  Exit
+status 1 when a required row fails."""
 import argparse
 import ctypes as C
-import json
+import functools
 import os
-import statistics
 import sys
+
+import benchkit
 
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 sys.path.insert(0, ROOT)
@@ -31,10 +32,8 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--mib", type=int, default=256)
     ap.add_argument("--item-kib", default="4,64")
-    ap.add_argument("--reps", type=int, default=10)
-    ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--kinds", default="uniform,zipf")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "batch", "bodies_bench.json"))
+    benchkit.add_args(ap, reps=10, warmup=2, out=os.path.join(ROOT, "profiles", "batch", "bodies_bench.json"))
     args = ap.parse_args()
 
     import importlib
@@ -50,25 +49,9 @@ def main():
     ctx = ghf.Context(0)
     L = ghf.lib()
     n = args.mib << 20
-    res = {"device": torch.cuda.get_device_name(0), "mib": args.mib, "reps": args.reps, "warmup": args.warmup,
-           "lib": ghf.lib_identity(), "unit": "ms (device events)", "assembly": ASSEMBLY, "kinds": {}}
-
-    def timed(variants):
-        for _ in range(args.warmup):
-            for _, fn in variants:
-                fn()
-        ctx.sync()
-        times = {name: [] for name, _ in variants}
-        for _ in range(args.reps):
-            for name, fn in variants:
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-                fn()
-                e1.record()
-                e1.synchronize()
-                times[name].append(e0.elapsed_time(e1))
-        ctx.sync()
-        return {k: statistics.median(v) for k, v in times.items()}, times
+    res = benchkit.envelope(torch, ghf, args, "ms (device events)")
+    res.update({"mib": args.mib, "assembly": ASSEMBLY, "kinds": {}})
+    timed = functools.partial(benchkit.timed, reps=args.reps, warmup=args.warmup, sync=ctx.sync)
 
     ok = True
     for kind in args.kinds.split(","):
@@ -151,9 +134,7 @@ def main():
             per_item_us = {x: 1e3 * v / count for x, v in med.items()}
             row = {
                 "count": count,
-                "median_ms": {x: round(v, 4) for x, v in med.items()},
-                "min_ms": {x: round(min(v), 4) for x, v in times.items()},
-                "max_ms": {x: round(max(v), 4) for x, v in times.items()},
+                **benchkit.stats(times),
                 "per_item_us": {x: round(v, 4) for x, v in per_item_us.items()},
                 "gb_per_s": {x: round(n / v / 1e6, 2) for x, v in med.items()},
                 "body_bytes_per_item": round(float(s["out_bytes"].sum().item()) / count, 1),
@@ -173,12 +154,7 @@ def main():
         del d_in
     res["required_g_lt_h_everywhere"] = ok
     ctx.close()
-    text = json.dumps(res, indent=1)
-    print(text)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            f.write(text + "\n")
+    benchkit.write(res, args.out)
     return 0 if ok else 1
 
 

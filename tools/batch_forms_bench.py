@@ -12,42 +12,38 @@ ghf_batch_planes_raw_auto.  Each forms call is timed against its all-dense paren
 
 Required: on bf16 and fp32 at both item sizes sf takes less time than sp (no margin: the call drops the planes that
 dominate the parent's time).  Recorded, not required: the other three pairs and the raw_planes == 0 calls against their
-parents; the stored bytes of both forms.  Method as tools/batch_planes_bench.py: device events around every call,
-variants interleaved within each repeat, medians, every variant warmed up and checked against the input first, and a
-plain 256 MiB copy between two buffers of the tool's own in front of every timed call, so that no figure depends on which
-variant ran before it.  Prints one JSON document; --out also writes it.  Exit status 1 when a required row fails."""
+parents; the stored bytes of both forms.  Every variant is checked against the input first.  Recipe: tools/benchkit.py,
+with the cache sweep.  Prints one JSON document; --out also writes it.  Exit status 1 when a required row fails."""
 import argparse
 import ctypes as C
-import json
+import functools
 import os
-import statistics
 import sys
+
+import benchkit
 
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 sys.path.insert(0, ROOT)
 
 KINDS = {"bf16_normal": 2, "fp32_normal": 4, "uniform_bytes": 2}
 PAIRS = {"c": "compress", "d": "decode with the live side-car", "s": "decode from the bodies alone", "k": "decode with run records"}
+SEED = 7
 
 
 def make(torch, kind, n):
-    g = torch.Generator(device="cuda")
-    g.manual_seed(7)
     if kind == "bf16_normal":
-        return torch.randn(n // 2, generator=g, device="cuda", dtype=torch.float32).to(torch.bfloat16).view(torch.uint8)
+        return benchkit.normal_bf16_rounded(torch, n, SEED)
     if kind == "fp32_normal":
-        return torch.randn(n // 4, generator=g, device="cuda", dtype=torch.float32).view(torch.uint8)
-    return torch.randint(0, 256, (n,), generator=g, device="cuda", dtype=torch.uint8)
+        return benchkit.normal_fp(torch, n, 4, SEED)
+    return benchkit.uniform_bytes(torch, n, SEED)
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--mib", type=int, default=256)
     ap.add_argument("--item-kib", default="4,64")
-    ap.add_argument("--reps", type=int, default=10)
-    ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--kinds", default=",".join(KINDS))
-    ap.add_argument("--out", default=None)
+    benchkit.add_args(ap, reps=10, warmup=2, out=None)
     args = ap.parse_args()
 
     import torch
@@ -59,29 +55,9 @@ def main():
     ctx = ghf.Context(0)
     L = ghf.lib()
     n = args.mib << 20
-    res = {"device": torch.cuda.get_device_name(0), "mib": args.mib, "reps": args.reps, "warmup": args.warmup,
-           "lib": ghf.lib_identity(), "unit": "ms (device events), medians",
-           "cache_sweep": "plain 256 MiB copy in front of every timed call", "kinds": {}}
-    flush_src, flush_dst = ctx.empty_u8(256 << 20), ctx.empty_u8(256 << 20)
-    flush_src.zero_()
-
-    def timed(variants):
-        for _ in range(args.warmup):
-            for _, fn in variants:
-                fn()
-        ctx.sync()
-        times = {name: [] for name, _ in variants}
-        for _ in range(args.reps):
-            for name, fn in variants:
-                assert L.ghf_copy_d2d(ctx.h, flush_dst.data_ptr(), flush_src.data_ptr(), flush_src.numel(), 0) == 0
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-                fn()
-                e1.record()
-                e1.synchronize()
-                times[name].append(e0.elapsed_time(e1))
-        ctx.sync()
-        return {k: statistics.median(v) for k, v in times.items()}, times
+    res = benchkit.envelope(torch, ghf, args, "ms (device events), medians")
+    res.update({"mib": args.mib, "cache_sweep": benchkit.CACHE_SWEEP, "kinds": {}})
+    timed = functools.partial(benchkit.timed, reps=args.reps, warmup=args.warmup, sync=ctx.sync, sweep=benchkit.cache_sweep(ctx))
 
     def clean(*results):
         return all(int(r["status"].abs().sum().item()) == 0 for r in results)
@@ -118,9 +94,7 @@ def main():
 
             par, frm = whole(None), whole(mask)
 
-            def call(rc):
-                assert rc == 0, rc
-
+            call = benchkit.ok
             P = lambda t: t.data_ptr()
 
             def four(tag, w, raw):
@@ -153,9 +127,7 @@ def main():
             row = {
                 "count": count,
                 "raw_planes": mask,
-                "median_ms": {x: round(v, 4) for x, v in med.items()},
-                "min_ms": {x: round(min(v), 4) for x, v in times.items()},
-                "max_ms": {x: round(max(v), 4) for x, v in times.items()},
+                **benchkit.stats(times),
                 "stored_bytes": {"input": n, "all_dense": dense_bytes, "forms": forms_bytes, "forms_over_dense": round(forms_bytes / dense_bytes, 6)},
                 "forms_over_parent": {x: round(med[x + "f"] / med[x + "p"], 4) for x in PAIRS},
                 "mask0_over_parent": {x: round(med[x + "0"] / med[x + "p"], 4) for x in PAIRS},
@@ -164,7 +136,7 @@ def main():
                 row["bodies_decode_faster_than_parent"] = med["sf"] < med["sp"]
                 ok = ok and row["bodies_decode_faster_than_parent"]
             kres["items"]["%dKiB" % kib] = row
-            print(json.dumps({kind: {"%dKiB" % kib: row}}), file=sys.stderr, flush=True)
+            benchkit.progress({kind: {"%dKiB" % kib: row}})
             ctx.batch_index_free(par["idx"])
             ctx.batch_index_free(frm["idx"])
             del par, frm, variants
@@ -173,12 +145,7 @@ def main():
     res["pairs"] = PAIRS
     res["required_bodies_decode_faster_on_typed_inputs"] = ok
     ctx.close()
-    text = json.dumps(res, indent=1)
-    print(text)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            f.write(text + "\n")
+    benchkit.write(res, args.out)
     return 0 if ok else 1
 
 

@@ -9,18 +9,18 @@ and compressed once with ghf_compress_batch; then, per item:
   f   the existing route for images that come with nothing: a loop over `--loop-items` of the same items of host
       ghf_parse_header + table upload + ghf_decode(index = NULL)
 
-Device events around every call, medians of `--reps` repeats after `--warmup` warm-ups, variants interleaved within each
-repeat, every variant checked once against the input.  For e0 the kernel's own counters (ghf_decode_images_batch_stats)
-give the observed passes per round, to hold against the bound of 256.
+Every variant is checked once against the input.  Recipe: tools/benchkit.py, without the cache sweep.  For e0 the kernel's
+own counters (ghf_decode_images_batch_stats) give the observed passes per round, to hold against the bound of 256.
 
 Every (kind, item size) is one GPU step: a child process of its own under `timeout -k 10`, started only if the one
 before it ended well.  Prints one JSON document; --out (default profiles/batch/images_bench.json) also keeps it."""
 import argparse
 import json
 import os
-import statistics
 import subprocess
 import sys
+
+import benchkit
 
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 sys.path.insert(0, ROOT)
@@ -98,22 +98,7 @@ def step(args, kind, kib):
     ctx.sync()
     assert all(torch.equal(it["back"][:item], d_in[i * item : (i + 1) * item]) for i, it in enumerate(loop)), (kind, kib)
 
-    variants = [("e", v_e), ("e0", v_e0), ("b", v_b), ("f", v_f)]
-    for _ in range(args.warmup):
-        for _, fn in variants:
-            fn()
-    ctx.sync()
-    times = {name: [] for name, _ in variants}
-    for _ in range(args.reps):
-        for name, fn in variants:
-            t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            t0.record()
-            fn()
-            t1.record()
-            t1.synchronize()
-            times[name].append(t0.elapsed_time(t1))
-    ctx.sync()
-    med = {x: statistics.median(v) for x, v in times.items()}
+    med, times = benchkit.timed([("e", v_e), ("e0", v_e0), ("b", v_b), ("f", v_f)], args.reps, args.warmup, ctx.sync)
 
     # the kernel's own counters over one sizes-only call
     stats = torch.zeros(2, dtype=torch.int64, device="cuda")
@@ -130,9 +115,7 @@ def step(args, kind, kib):
         "count": count,
         "looped_items": k,
         "image_bytes_mean": round(float(r["out_bytes"].double().mean().item()), 1),
-        "median_ms": {x: round(v, 4) for x, v in med.items()},
-        "min_ms": {x: round(min(v), 4) for x, v in times.items()},
-        "max_ms": {x: round(max(v), 4) for x, v in times.items()},
+        **benchkit.stats(times),
         "per_item_us": {x: round(v, 3) for x, v in per_item_us.items()},
         "gb_per_s": {"e": round(n / med["e"] / 1e6, 2), "e0": round(n / med["e0"] / 1e6, 2), "b": round(n / med["b"] / 1e6, 2),
                      "f": round(k * item / med["f"] / 1e6, 3)},
@@ -153,11 +136,9 @@ def main():
     ap.add_argument("--mib", type=int, default=256)
     ap.add_argument("--item-kib", default="4,64,1024")
     ap.add_argument("--loop-items", type=int, default=256)
-    ap.add_argument("--reps", type=int, default=10)
-    ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--kinds", default="uniform,zipf")
     ap.add_argument("--step-seconds", type=int, default=240, help="time limit of one (kind, item size) step")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "batch", "images_bench.json"))
+    benchkit.add_args(ap, reps=10, warmup=2, out=os.path.join(ROOT, "profiles", "batch", "images_bench.json"))
     ap.add_argument("--step", nargs=2, metavar=("KIND", "KIB"), default=None, help="(internal) run one step in this process")
     args = ap.parse_args()
     if args.step:
@@ -180,12 +161,7 @@ def main():
             print("%s %d KiB done" % (kind, kib), file=sys.stderr, flush=True)
         if not ok:
             break
-    text = json.dumps(res, indent=1)
-    print(text)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            f.write(text + "\n")
+    benchkit.write(res, args.out)
     return 0 if ok else 1
 
 

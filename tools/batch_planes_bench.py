@@ -11,42 +11,38 @@ as 2-byte elements), cut into items of 4 KiB and 64 KiB:
 The flat calls run on the same interleaved bytes in the same run; their code paths are the parent commit's, so their times
 are also the check that templating their bodies cost nothing.  Reported per item (call time / items) with the stored
 bytes per item of both forms (bodies plus the headers' share).  No time ratio is required; the sizes are: the planes form
-must store strictly less than the flat form on the bf16 and fp32 inputs.  Method as tools/batch_shared_bench.py (device
-events around every call, variants interleaved within each repeat, medians, every variant warmed up and checked against
-the input first) with the cache sweep of tools/planes_bench.py: a plain 256 MiB copy between two buffers of the tool's
-own in front of every timed call, so that no figure depends on which variant ran before it.  Both codes come from
-GHF_HIST_COVER_ALL histograms.  Prints one JSON document; --out also writes it.  Exit status 1 when a required row fails."""
+must store strictly less than the flat form on the bf16 and fp32 inputs.  Every variant is checked against the input
+first.  Recipe: tools/benchkit.py, with the cache sweep.  Both codes come from GHF_HIST_COVER_ALL histograms.  Prints one
+JSON document; --out also writes it.  Exit status 1 when a required row fails."""
 import argparse
 import ctypes as C
-import json
+import functools
 import os
-import statistics
 import sys
+
+import benchkit
 
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 sys.path.insert(0, ROOT)
 
 KINDS = {"bf16_normal": 2, "fp32_normal": 4, "uniform_bytes": 2}
+SEED = 7
 
 
 def make(torch, kind, n):
-    g = torch.Generator(device="cuda")
-    g.manual_seed(7)
     if kind == "bf16_normal":
-        return torch.randn(n // 2, generator=g, device="cuda", dtype=torch.float32).to(torch.bfloat16).view(torch.uint8)
+        return benchkit.normal_bf16_rounded(torch, n, SEED)
     if kind == "fp32_normal":
-        return torch.randn(n // 4, generator=g, device="cuda", dtype=torch.float32).view(torch.uint8)
-    return torch.randint(0, 256, (n,), generator=g, device="cuda", dtype=torch.uint8)
+        return benchkit.normal_fp(torch, n, 4, SEED)
+    return benchkit.uniform_bytes(torch, n, SEED)
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--mib", type=int, default=256)
     ap.add_argument("--item-kib", default="4,64")
-    ap.add_argument("--reps", type=int, default=10)
-    ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--kinds", default=",".join(KINDS))
-    ap.add_argument("--out", default=None)
+    benchkit.add_args(ap, reps=10, warmup=2, out=None)
     args = ap.parse_args()
 
     import torch
@@ -58,29 +54,9 @@ def main():
     ctx = ghf.Context(0)
     L = ghf.lib()
     n = args.mib << 20
-    res = {"device": torch.cuda.get_device_name(0), "mib": args.mib, "reps": args.reps, "warmup": args.warmup,
-           "lib": ghf.lib_identity(), "unit": "ms (device events), medians",
-           "cache_sweep": "plain 256 MiB copy in front of every timed call", "kinds": {}}
-    flush_src, flush_dst = ctx.empty_u8(256 << 20), ctx.empty_u8(256 << 20)
-    flush_src.zero_()
-
-    def timed(variants):
-        for _ in range(args.warmup):
-            for _, fn in variants:
-                fn()
-        ctx.sync()
-        times = {name: [] for name, _ in variants}
-        for _ in range(args.reps):
-            for name, fn in variants:
-                assert L.ghf_copy_d2d(ctx.h, flush_dst.data_ptr(), flush_src.data_ptr(), flush_src.numel(), 0) == 0
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-                fn()
-                e1.record()
-                e1.synchronize()
-                times[name].append(e0.elapsed_time(e1))
-        ctx.sync()
-        return {k: statistics.median(v) for k, v in times.items()}, times
+    res = benchkit.envelope(torch, ghf, args, "ms (device events), medians")
+    res.update({"mib": args.mib, "cache_sweep": benchkit.CACHE_SWEEP, "kinds": {}})
+    timed = functools.partial(benchkit.timed, reps=args.reps, warmup=args.warmup, sync=ctx.sync, sweep=benchkit.cache_sweep(ctx))
 
     def clean(*results):
         return all(int(r["status"].abs().sum().item()) == 0 for r in results)
@@ -115,9 +91,7 @@ def main():
             f_hdr = int(L.ghf_header_bytes(ctx.code_to_host(f_code).max_len))
             p_hdr = sum(int(L.ghf_header_bytes(ctx.code_to_host(p_codes[k]).max_len)) for k in range(e))
 
-            def call(rc):
-                assert rc == 0, rc
-
+            call = benchkit.ok
             P = lambda t: t.data_ptr()
             variants = [
                 ("h", lambda: (call(L.ghf_histogram_batch(ctx.h, P(f["in_ptrs"]), P(f["in_bytes"]), item, count, 1, P(f_hist))),
@@ -146,9 +120,7 @@ def main():
             planes_bytes = float(p["out_bytes"].sum().item()) / count + p_hdr / count
             row = {
                 "count": count,
-                "median_ms": {x: round(v, 4) for x, v in med.items()},
-                "min_ms": {x: round(min(v), 4) for x, v in times.items()},
-                "max_ms": {x: round(max(v), 4) for x, v in times.items()},
+                **benchkit.stats(times),
                 "per_item_us": {x: round(1e3 * v / count, 4) for x, v in med.items()},
                 "gb_per_s": {x: round(n / v / 1e6, 2) for x, v in med.items()},
                 "stored_bytes_per_item": {"input": item, "flat": round(flat_bytes, 1), "planes": round(planes_bytes, 1),
@@ -160,7 +132,7 @@ def main():
                 row["planes_store_less"] = planes_bytes < flat_bytes
                 ok = ok and row["planes_store_less"]
             kres["items"]["%dKiB" % kib] = row
-            print(json.dumps({kind: {"%dKiB" % kib: row}}), file=sys.stderr, flush=True)
+            benchkit.progress({kind: {"%dKiB" % kib: row}})
             ctx.batch_index_free(fidx)
             ctx.batch_index_free(pidx)
             del f, fd, fs, p, pd, ps
@@ -168,12 +140,7 @@ def main():
         del d_in
     res["required_planes_store_less_on_typed_inputs"] = ok
     ctx.close()
-    text = json.dumps(res, indent=1)
-    print(text)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            f.write(text + "\n")
+    benchkit.write(res, args.out)
     return 0 if ok else 1
 
 

@@ -11,53 +11,41 @@ fp32 values (one code per byte plane), cut into items of 4 KiB and 64 KiB.  Time
 and the stored bytes per item with a record against the stored bytes with the raw side-car.  REQUIRED: s < g on uniform
 bytes and on both typed inputs, at both item sizes; the tool exits 1 otherwise.  g is existing code measured in the same
 run; no margin beyond "faster" is fixed.  s / b' and everything about the Zipf input (its skewed code settles in few
-passes, so g is already near b') are reported without a requirement.  Method as tools/batch_planes_bench.py: device
-events around every call, variants interleaved within each repeat, medians, every variant warmed up and checked against
-the input first, and a plain 256 MiB copy between two buffers of the tool's own in front of every timed call, so that no
-figure depends on which variant ran before it.  The codes come from GHF_HIST_COVER_ALL histograms.  Prints one JSON
+passes, so g is already near b') are reported without a requirement.  Every variant is checked against the input first.
+Recipe: tools/benchkit.py, with the cache sweep.  The codes come from GHF_HIST_COVER_ALL histograms.  Prints one JSON
 document; --out also writes it."""
 import argparse
 import ctypes as C
-import json
+import functools
 import os
-import statistics
 import sys
+
+import benchkit
 
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 sys.path.insert(0, ROOT)
 
 KINDS = {"uniform_bytes": 1, "zipf_bytes": 1, "bf16_normal": 2, "fp32_normal": 4}
 REQUIRED = ("uniform_bytes", "bf16_normal", "fp32_normal")
+SEED = 7
 
 
 def make(torch, kind, n):
-    g = torch.Generator(device="cuda")
-    g.manual_seed(7)
     if kind == "bf16_normal":
-        return torch.randn(n // 2, generator=g, device="cuda", dtype=torch.float32).to(torch.bfloat16).view(torch.uint8)
+        return benchkit.normal_bf16_rounded(torch, n, SEED)
     if kind == "fp32_normal":
-        return torch.randn(n // 4, generator=g, device="cuda", dtype=torch.float32).view(torch.uint8)
+        return benchkit.normal_fp(torch, n, 4, SEED)
     if kind == "uniform_bytes":
-        return torch.randint(0, 256, (n,), generator=g, device="cuda", dtype=torch.uint8)
-    # Zipf: P(value k) ~ 1 / (k + 1), by inversion of the cumulative distribution, a piece at a time
-    w = 1.0 / torch.arange(1, 257, device="cuda", dtype=torch.float64)
-    cdf = (torch.cumsum(w, 0) / w.sum()).to(torch.float32)
-    out = torch.empty(n, device="cuda", dtype=torch.uint8)
-    for at in range(0, n, 1 << 26):
-        m = min(1 << 26, n - at)
-        u = torch.rand(m, generator=g, device="cuda", dtype=torch.float32)
-        out[at : at + m] = torch.searchsorted(cdf, u).clamp_(max=255).to(torch.uint8)
-    return out
+        return benchkit.uniform_bytes(torch, n, SEED)
+    return benchkit.zipf_bytes(torch, n, SEED)
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--mib", type=int, default=256)
     ap.add_argument("--item-kib", default="4,64")
-    ap.add_argument("--reps", type=int, default=10)
-    ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--kinds", default=",".join(KINDS))
-    ap.add_argument("--out", default=None)
+    benchkit.add_args(ap, reps=10, warmup=2, out=None)
     args = ap.parse_args()
 
     import torch
@@ -69,36 +57,14 @@ def main():
     ctx = ghf.Context(0)
     L = ghf.lib()
     n = args.mib << 20
-    res = {"device": torch.cuda.get_device_name(0), "mib": args.mib, "reps": args.reps, "warmup": args.warmup,
-           "lib": ghf.lib_identity(), "unit": "ms (device events), medians",
-           "cache_sweep": "plain 256 MiB copy in front of every timed call", "kinds": {}}
-    flush_src, flush_dst = ctx.empty_u8(256 << 20), ctx.empty_u8(256 << 20)
-    flush_src.zero_()
-
-    def timed(variants):
-        for _ in range(args.warmup):
-            for _, fn in variants:
-                fn()
-        ctx.sync()
-        times = {name: [] for name, _ in variants}
-        for _ in range(args.reps):
-            for name, fn in variants:
-                assert L.ghf_copy_d2d(ctx.h, flush_dst.data_ptr(), flush_src.data_ptr(), flush_src.numel(), 0) == 0
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-                fn()
-                e1.record()
-                e1.synchronize()
-                times[name].append(e0.elapsed_time(e1))
-        ctx.sync()
-        return {k: statistics.median(v) for k, v in times.items()}, times
+    res = benchkit.envelope(torch, ghf, args, "ms (device events), medians")
+    res.update({"mib": args.mib, "cache_sweep": benchkit.CACHE_SWEEP, "kinds": {}})
+    timed = functools.partial(benchkit.timed, reps=args.reps, warmup=args.warmup, sync=ctx.sync, sweep=benchkit.cache_sweep(ctx))
 
     def clean(*results):
         return all(int(r["status"].abs().sum().item()) == 0 for r in results)
 
-    def call(rc):
-        assert rc == 0, rc
-
+    call = benchkit.ok
     P = lambda t: t.data_ptr()
     ok = True
     for kind in args.kinds.split(","):
@@ -159,9 +125,7 @@ def main():
             side_car = e * (8.0 * int(idx.blocks_per_item) + 4.0 * int(idx.segs_per_item))
             row = {
                 "count": count,
-                "median_ms": {x: round(v, 4) for x, v in med.items()},
-                "min_ms": {x: round(min(v), 4) for x, v in times.items()},
-                "max_ms": {x: round(max(v), 4) for x, v in times.items()},
+                **benchkit.stats(times),
                 "per_item_us": {x: round(1e3 * v / count, 4) for x, v in med.items()},
                 "gb_per_s": {x: round(n / v / 1e6, 2) for x, v in med.items()},
                 "stored_bytes_per_item": {"input": item, "bodies": round(bodies, 1), "records": round(records, 1),
@@ -174,7 +138,7 @@ def main():
             if kind in REQUIRED:
                 ok = ok and row["s_faster_than_g"]
             kres["items"]["%dKiB" % kib] = row
-            print(json.dumps({kind: {"%dKiB" % kib: row}}), file=sys.stderr, flush=True)
+            benchkit.progress({kind: {"%dKiB" % kib: row}})
             ctx.batch_index_free(idx)
             del c, r, live, bare, seek
         res["kinds"][kind] = kres
@@ -182,12 +146,7 @@ def main():
     res["required_s_faster_than_g_on"] = list(REQUIRED)
     res["required_met"] = ok
     ctx.close()
-    text = json.dumps(res, indent=1)
-    print(text)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            f.write(text + "\n")
+    benchkit.write(res, args.out)
     return 0 if ok else 1
 
 

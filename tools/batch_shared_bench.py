@@ -10,16 +10,17 @@ items.  `--mib` MiB of uniform and of zipf bytes, cut into items of 4 KiB and 64
 
 Reported per item (call time / items), with the stored bytes per item of both forms: the image of `a` against the body
 of `a2` plus the one header divided by the item count.  REQUIRED: a2 < a per item at every size and input (the shared
-kernel does a strict subset of a's work); a1 and b1 are reported against a and b without a requirement.  Device events
-around every call, variants interleaved within each repeat, every variant warmed up first and checked once (stored
-header || body through ghf_decode_images_batch on a sample, both decodes against the input).
-Prints one JSON document; --out also writes it to a file.  Exit status 1 when a required row fails."""
+kernel does a strict subset of a's work); a1 and b1 are reported against a and b without a requirement.  Every variant is
+checked once (stored header || body through ghf_decode_images_batch on a sample, both decodes against the input).
+Recipe: tools/benchkit.py, without the cache sweep.  Prints one JSON document; --out also writes it to a file.  Exit
+status 1 when a required row fails."""
 import argparse
 import ctypes as C
-import json
+import functools
 import os
-import statistics
 import sys
+
+import benchkit
 
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 sys.path.insert(0, ROOT)
@@ -29,10 +30,8 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--mib", type=int, default=256)
     ap.add_argument("--item-kib", default="4,64")
-    ap.add_argument("--reps", type=int, default=10)
-    ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--kinds", default="uniform,zipf")
-    ap.add_argument("--out", default=None)
+    benchkit.add_args(ap, reps=10, warmup=2, out=None)
     args = ap.parse_args()
 
     import importlib
@@ -48,25 +47,9 @@ def main():
     ctx = ghf.Context(0)
     L = ghf.lib()
     n = args.mib << 20
-    res = {"device": torch.cuda.get_device_name(0), "mib": args.mib, "reps": args.reps, "warmup": args.warmup,
-           "lib": ghf.lib_identity(), "unit": "ms (device events)", "kinds": {}}
-
-    def timed(variants):
-        for _ in range(args.warmup):
-            for _, fn in variants:
-                fn()
-        ctx.sync()
-        times = {name: [] for name, _ in variants}
-        for _ in range(args.reps):
-            for name, fn in variants:
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-                fn()
-                e1.record()
-                e1.synchronize()
-                times[name].append(e0.elapsed_time(e1))
-        ctx.sync()
-        return {k: statistics.median(v) for k, v in times.items()}, times
+    res = benchkit.envelope(torch, ghf, args, "ms (device events)")
+    res.update({"mib": args.mib, "kinds": {}})
+    timed = functools.partial(benchkit.timed, reps=args.reps, warmup=args.warmup, sync=ctx.sync)
 
     ok = True
     for kind in args.kinds.split(","):
@@ -152,9 +135,7 @@ def main():
             body_bytes = float(s["out_bytes"].sum().item()) / count
             row = {
                 "count": count,
-                "median_ms": {x: round(v, 4) for x, v in med.items()},
-                "min_ms": {x: round(min(v), 4) for x, v in times.items()},
-                "max_ms": {x: round(max(v), 4) for x, v in times.items()},
+                **benchkit.stats(times),
                 "per_item_us": {x: round(v, 4) for x, v in per_item_us.items()},
                 "gb_per_s": {x: round(n / v / 1e6, 2) for x, v in med.items()},
                 "stored_bytes_per_item": {"image": round(image_bytes, 1), "body_plus_header_share": round(body_bytes + hdr_bytes / count, 1),
@@ -172,12 +153,7 @@ def main():
         del d_in
     res["required_a2_lt_a_everywhere"] = ok
     ctx.close()
-    text = json.dumps(res, indent=1)
-    print(text)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            f.write(text + "\n")
+    benchkit.write(res, args.out)
     return 0 if ok else 1
 
 

@@ -9,16 +9,15 @@ values from a seeded generator (bf16 = the upper half of fp32, fp32, fp64) and u
      interleaved buffer
   c  the stored bytes of both forms
 
-Device events around every call, variants interleaved within each repeat, every variant warmed up first and checked once
-(merge(split(x)) == x, both decodes against the input).  In front of every timed call, outside its events, a plain copy of
-256 MiB between two buffers of the tool's own sweeps the 256 MiB Infinity Cache, so that no figure depends on which variant
-ran before it.  Prints one JSON document and writes it to --out."""
+Every variant is checked once (merge(split(x)) == x, both decodes against the input).  Recipe: tools/benchkit.py, with the
+cache sweep.  Prints one JSON document and writes it to --out."""
 import argparse
 import ctypes as C
-import json
+import functools
 import os
-import statistics
 import sys
+
+import benchkit
 
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 sys.path.insert(0, ROOT)
@@ -28,15 +27,7 @@ def make_elems(torch, synth, kind, n_bytes, e, seed):
     """n_bytes of `kind` as a CUDA uint8 tensor"""
     if kind == "uniform":
         return synth.make(torch, "uniform", n_bytes, offset=0, device="cuda")
-    g = torch.Generator(device="cuda")
-    g.manual_seed(seed)
-    n = n_bytes // e
-    if e == 8:
-        return torch.randn(n, generator=g, device="cuda", dtype=torch.float64).view(torch.uint8)
-    x = torch.randn(n, generator=g, device="cuda", dtype=torch.float32)
-    if e == 4:
-        return x.view(torch.uint8)
-    return (x.view(torch.int32) >> 16).to(torch.int16).view(torch.uint8)  # bf16 by truncation
+    return benchkit.normal_elems(torch, n_bytes, e, seed)
 
 
 def main():
@@ -44,10 +35,8 @@ def main():
     ap.add_argument("--mib", default="256,1024")
     ap.add_argument("--widths", default="2,4,8")
     ap.add_argument("--kinds", default="normal,uniform")
-    ap.add_argument("--reps", type=int, default=10)
-    ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--seed", type=int, default=7)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "planes", "planes_bench.json"))
+    benchkit.add_args(ap, reps=10, warmup=2, out=os.path.join(ROOT, "profiles", "planes", "planes_bench.json"))
     args = ap.parse_args()
 
     import importlib
@@ -62,29 +51,9 @@ def main():
     assert torch.cuda.is_available(), "planes_bench needs the GPU: there is nothing to fall back to"
     ctx = ghf.Context(0)
     L = ghf.lib()
-    res = {"device": torch.cuda.get_device_name(0), "reps": args.reps, "warmup": args.warmup, "seed": args.seed,
-           "lib": ghf.lib_identity(), "unit": "ms (device events), medians", "cache_sweep": "plain 256 MiB copy in front of every timed call", "required_fraction_of_copy": 0.5, "runs": []}
-
-    flush_src, flush_dst = ctx.empty_u8(256 << 20), ctx.empty_u8(256 << 20)
-    flush_src.zero_()
-
-    def timed(variants):
-        for _ in range(args.warmup):
-            for _, fn in variants:
-                fn()
-        ctx.sync()
-        times = {name: [] for name, _ in variants}
-        for _ in range(args.reps):
-            for name, fn in variants:
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                assert L.ghf_copy_d2d(ctx.h, flush_dst.data_ptr(), flush_src.data_ptr(), flush_src.numel(), 0) == 0
-                e0.record()
-                fn()
-                e1.record()
-                e1.synchronize()
-                times[name].append(e0.elapsed_time(e1))
-        ctx.sync()
-        return {k: statistics.median(v) for k, v in times.items()}, times
+    res = benchkit.envelope(torch, ghf, args, "ms (device events), medians")
+    res.update({"seed": args.seed, "cache_sweep": benchkit.CACHE_SWEEP, "required_fraction_of_copy": 0.5, "runs": []})
+    timed = functools.partial(benchkit.timed, reps=args.reps, warmup=args.warmup, sync=ctx.sync, sweep=benchkit.cache_sweep(ctx))
 
     for mib in [int(x) for x in args.mib.split(",")]:
         nbytes = mib << 20
@@ -154,9 +123,7 @@ def main():
                 times = dict(times_a, **times_b)
                 run = {
                     "mib": mib, "elem_bytes": e, "kind": kind, "n_elems": n,
-                    "median_ms": {k: round(v, 4) for k, v in med.items()},
-                    "min_ms": {k: round(min(v), 4) for k, v in times.items()},
-                    "max_ms": {k: round(max(v), 4) for k, v in times.items()},
+                    **benchkit.stats(times),
                     # read + write, as bench.py counts the copy probe
                     "tb_per_s": {k: round(2 * nbytes / med[k] / 1e9, 3) for k in ("copy_nt", "split", "merge")},
                     "fraction_of_copy": {"split": round(med["copy_nt"] / med["split"], 4), "merge": round(med["copy_nt"] / med["merge"], 4)},
@@ -167,17 +134,13 @@ def main():
                 }
                 run["meets_required"] = min(run["fraction_of_copy"].values()) >= res["required_fraction_of_copy"]
                 res["runs"].append(run)
-                print(json.dumps(run), file=sys.stderr, flush=True)
+                benchkit.progress(run)
                 ctx.planes_index_free(idx_p)
                 ctx.index_free(idx_f)
                 del d_in, d_planes, d_back, d_flat, r
                 torch.cuda.empty_cache()
     ctx.close()
-    text = json.dumps(res, indent=1)
-    print(text)
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as f:
-        f.write(text + "\n")
+    benchkit.write(res, args.out)
 
 
 if __name__ == "__main__":

@@ -14,16 +14,15 @@ ghf_compress_planes at E = 4 and E = 8 at both sizes.
   c  with --parent-lib (a libghf.so built from the parent commit): ghf_compress_planes and ghf_compress of this tree and of
      the parent, alternating in one process, at the first size of --mib and E = 4: the existing calls keep their times.
 
-Device events around every call, variants interleaved within each repeat, every variant warmed up first and checked once
-(histograms against the split + E histograms, BUILD_CODES images against ghf_compress_planes').  In front of every timed
-call, outside its events, a plain copy of 256 MiB between two buffers of the tool's own sweeps the 256 MiB Infinity Cache.
-Prints one JSON document and writes it to --out."""
+Every variant is checked once (histograms against the split + E histograms, BUILD_CODES images against
+ghf_compress_planes').  Recipe: tools/benchkit.py, with the cache sweep.  Prints one JSON document and writes it to --out."""
 import argparse
 import ctypes as C
-import json
+import functools
 import os
-import statistics
 import sys
+
+import benchkit
 
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 sys.path.insert(0, ROOT)
@@ -33,15 +32,7 @@ def make_elems(torch, synth, kind, n_bytes, e, seed):
     """n_bytes of `kind` as a CUDA uint8 tensor"""
     if kind == "uniform":
         return synth.make(torch, "uniform", n_bytes, offset=0, device="cuda")
-    g = torch.Generator(device="cuda")
-    g.manual_seed(seed)
-    n = n_bytes // e
-    if e == 8:
-        return torch.randn(n, generator=g, device="cuda", dtype=torch.float64).view(torch.uint8)
-    x = torch.randn(n, generator=g, device="cuda", dtype=torch.float32)
-    if e == 4:
-        return x.view(torch.uint8)
-    return (x.view(torch.int32) >> 16).to(torch.int16).view(torch.uint8)  # bf16 by truncation
+    return benchkit.normal_elems(torch, n_bytes, e, seed)
 
 
 def main():
@@ -49,11 +40,9 @@ def main():
     ap.add_argument("--mib", default="256,1024")
     ap.add_argument("--widths", default="2,4,8")
     ap.add_argument("--kinds", default="normal,uniform")
-    ap.add_argument("--reps", type=int, default=10)
-    ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--seed", type=int, default=7)
     ap.add_argument("--parent-lib", default="", help="a libghf.so built from the parent commit, for part c")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "planes", "coded_bench.json"))
+    benchkit.add_args(ap, reps=10, warmup=2, out=os.path.join(ROOT, "profiles", "planes", "coded_bench.json"))
     args = ap.parse_args()
 
     import importlib
@@ -68,30 +57,10 @@ def main():
     assert torch.cuda.is_available(), "planes_coded_bench needs the GPU: there is nothing to fall back to"
     ctx = ghf.Context(0)
     L = ghf.lib()
-    res = {"device": torch.cuda.get_device_name(0), "reps": args.reps, "warmup": args.warmup, "seed": args.seed,
-           "lib": ghf.lib_identity(), "unit": "ms (device events), medians", "cache_sweep": "plain 256 MiB copy in front of every timed call",
-           "required": ["hist_planes < split_plus_hists in every row", "coded_build < compress_planes at E = 4 and 8"], "runs": []}
-
-    flush_src, flush_dst = ctx.empty_u8(256 << 20), ctx.empty_u8(256 << 20)
-    flush_src.zero_()
-
-    def timed(variants):
-        for _ in range(args.warmup):
-            for _, fn in variants:
-                fn()
-        ctx.sync()
-        times = {name: [] for name, _ in variants}
-        for _ in range(args.reps):
-            for name, fn in variants:
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                assert L.ghf_copy_d2d(ctx.h, flush_dst.data_ptr(), flush_src.data_ptr(), flush_src.numel(), 0) == 0
-                e0.record()
-                fn()
-                e1.record()
-                e1.synchronize()
-                times[name].append(e0.elapsed_time(e1))
-        ctx.sync()
-        return {k: statistics.median(v) for k, v in times.items()}, times
+    res = benchkit.envelope(torch, ghf, args, "ms (device events), medians")
+    res.update({"seed": args.seed, "cache_sweep": benchkit.CACHE_SWEEP,
+                "required": ["hist_planes < split_plus_hists in every row", "coded_build < compress_planes at E = 4 and 8"], "runs": []})
+    timed = functools.partial(benchkit.timed, reps=args.reps, warmup=args.warmup, sync=ctx.sync, sweep=benchkit.cache_sweep(ctx))
 
     sizes_mib = [int(x) for x in args.mib.split(",")]
     for mib in sizes_mib:
@@ -169,9 +138,7 @@ def main():
                 times = dict(times_a, **times_b)
                 run = {
                     "mib": mib, "elem_bytes": e, "kind": kind, "n_elems": n,
-                    "median_ms": {k: round(v, 4) for k, v in med.items()},
-                    "min_ms": {k: round(min(v), 4) for k, v in times.items()},
-                    "max_ms": {k: round(max(v), 4) for k, v in times.items()},
+                    **benchkit.stats(times),
                     "copy_tb_per_s_read_plus_write": round(2 * nbytes / med["copy_nt"] / 1e9, 3),
                     "hist_planes_read_tb_per_s": round(nbytes / med["hist_planes"] / 1e9, 3),
                     # the copy moves 2 N bytes, the histogram reads N: the fraction is of the copy's TIME
@@ -189,7 +156,7 @@ def main():
                 }
                 run["meets_required"] = bool(med["hist_planes"] < med["split_plus_hists"] and (e == 2 or med["coded_build"] < med["compress_planes"]))
                 res["runs"].append(run)
-                print(json.dumps(run), file=sys.stderr, flush=True)
+                benchkit.progress(run)
                 del d_in, d_flat, r_old, r_new, r_ready
                 torch.cuda.empty_cache()
     res["meets_required"] = all(r["meets_required"] for r in res["runs"])
@@ -218,25 +185,16 @@ def main():
         for name, lib, h in (("this", L, ctx.h), ("parent", LB, hb)):
             variants.append((name + "_compress_planes", lambda lib=lib, h=h: lib.ghf_compress_planes(h, d_in.data_ptr(), n, e, d_out.data_ptr(), slot, nb.data_ptr(), None, None)))
             variants.append((name + "_compress", lambda lib=lib, h=h: lib.ghf_compress(h, d_in.data_ptr(), nbytes, d_flat.data_ptr(), d_flat.numel(), nb.data_ptr(), None, None)))
-        checked = [(k, (lambda fn=fn: _ok(fn()))) for k, fn in variants]
+        checked = [(k, (lambda fn=fn: benchkit.ok(fn()))) for k, fn in variants]
         med, times = timed(checked)
-        res["parent_ab"] = {"mib": mib, "elem_bytes": e, "kind": "normal", "median_ms": {k: round(v, 4) for k, v in med.items()},
-                            "min_ms": {k: round(min(v), 4) for k, v in times.items()}, "max_ms": {k: round(max(v), 4) for k, v in times.items()},
+        res["parent_ab"] = {"mib": mib, "elem_bytes": e, "kind": "normal", **benchkit.stats(times),
                             "this_over_parent": {"compress_planes": round(med["this_compress_planes"] / med["parent_compress_planes"], 4),
                                                  "compress": round(med["this_compress"] / med["parent_compress"], 4)}}
-        print(json.dumps(res["parent_ab"]), file=sys.stderr, flush=True)
+        benchkit.progress(res["parent_ab"])
         torch.cuda.synchronize()
         LB.ghf_ctx_destroy(hb)
     ctx.close()
-    text = json.dumps(res, indent=1)
-    print(text)
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as f:
-        f.write(text + "\n")
-
-
-def _ok(rc):
-    assert rc == 0, rc
+    benchkit.write(res, args.out)
 
 
 if __name__ == "__main__":

@@ -16,15 +16,15 @@ step of relative size 1e-3, and uniform bytes against uniform bytes of another s
 REQUIRED: every fused call is faster than its unfused pair in every row (it moves 3 N bytes where the pair moves 5 N).
 Recorded, not required: the ratios to the plain parents and to the copy.
 
-Device events around every call, variants interleaved within each repeat, every variant warmed up first and every fused
-result checked once against its unfused pair.  In front of every timed call, outside its events, a plain copy of 256 MiB
-between two buffers of the tool's own sweeps the 256 MiB Infinity Cache.  Prints one JSON document and writes it to --out."""
+Every fused result is checked once against its unfused pair.  Recipe: tools/benchkit.py, with the cache sweep.  Prints one
+JSON document and writes it to --out."""
 import argparse
 import ctypes as C
-import json
+import functools
 import os
-import statistics
 import sys
+
+import benchkit
 
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 sys.path.insert(0, ROOT)
@@ -33,25 +33,12 @@ STEP = 1e-3
 CALLS = ("hist", "split", "merge", "merge_range", "compress", "decode")
 
 
-def as_elems(torch, x, e):
-    """float values as a CUDA uint8 tensor: bf16 by truncation of fp32 / fp32 / fp64"""
-    if e == 2:
-        return (x.view(torch.int32) >> 16).to(torch.int16).view(torch.uint8)
-    return x.view(torch.uint8)
-
-
 def make_pair(torch, synth, kind, n_bytes, e, seed):
     """(new, base): n_bytes each"""
     if kind == "uniform":
         return (synth.make(torch, "uniform", n_bytes, seed=seed, offset=0, device="cuda"),
                 synth.make(torch, "uniform", n_bytes, seed=seed + 1, offset=0, device="cuda"))
-    g = torch.Generator(device="cuda")
-    g.manual_seed(seed)
-    n = n_bytes // e
-    dt = torch.float64 if e == 8 else torch.float32
-    w = torch.randn(n, generator=g, device="cuda", dtype=dt)
-    new = w + STEP * torch.randn(n, generator=g, device="cuda", dtype=dt)
-    return as_elems(torch, new, e), as_elems(torch, w, e)
+    return benchkit.normal_pair(torch, n_bytes, e, STEP, seed)
 
 
 def main():
@@ -59,10 +46,8 @@ def main():
     ap.add_argument("--mib", default="256,1024")
     ap.add_argument("--widths", default="2,4,8")
     ap.add_argument("--kinds", default="normal,uniform")
-    ap.add_argument("--reps", type=int, default=10)
-    ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--seed", type=int, default=7)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "planes", "delta_bench.json"))
+    benchkit.add_args(ap, reps=10, warmup=2, out=os.path.join(ROOT, "profiles", "planes", "delta_bench.json"))
     args = ap.parse_args()
 
     import importlib
@@ -77,34 +62,12 @@ def main():
     assert torch.cuda.is_available(), "planes_delta_bench needs the GPU: there is nothing to fall back to"
     ctx = ghf.Context(0)
     L = ghf.lib()
-    res = {"device": torch.cuda.get_device_name(0), "reps": args.reps, "warmup": args.warmup, "seed": args.seed, "step": STEP,
-           "lib": ghf.lib_identity(), "unit": "ms (device events), medians", "cache_sweep": "plain 256 MiB copy in front of every timed call",
-           "unfused": "torch.bitwise_xor(out = preallocated) + the plain call", "merge_range_first": 5,
-           "required": ["fused < unfused for every call in every row"], "runs": []}
-
-    flush_src, flush_dst = ctx.empty_u8(256 << 20), ctx.empty_u8(256 << 20)
-    flush_src.zero_()
-
-    def ok(rc):
-        assert rc == 0, rc
-
-    def timed(variants):
-        for _ in range(args.warmup):
-            for _, fn in variants:
-                fn()
-        ctx.sync()
-        times = {name: [] for name, _ in variants}
-        for _ in range(args.reps):
-            for name, fn in variants:
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                ok(L.ghf_copy_d2d(ctx.h, flush_dst.data_ptr(), flush_src.data_ptr(), flush_src.numel(), 0))
-                e0.record()
-                fn()
-                e1.record()
-                e1.synchronize()
-                times[name].append(e0.elapsed_time(e1))
-        ctx.sync()
-        return times
+    res = benchkit.envelope(torch, ghf, args, "ms (device events), medians")
+    res.update({"seed": args.seed, "step": STEP, "cache_sweep": benchkit.CACHE_SWEEP,
+                "unfused": "torch.bitwise_xor(out = preallocated) + the plain call", "merge_range_first": 5,
+                "required": ["fused < unfused for every call in every row"], "runs": []})
+    ok = benchkit.ok
+    timed = functools.partial(benchkit.timed, reps=args.reps, warmup=args.warmup, sync=ctx.sync, sweep=benchkit.cache_sweep(ctx))
 
     for mib in [int(x) for x in args.mib.split(",")]:
         nbytes = mib << 20
@@ -214,10 +177,8 @@ def main():
 
                 med, lo, hi = {}, {}, {}
                 for call in CALLS:
-                    times = timed([(k, fn) for k, fn in V[call].items()])
-                    med[call] = {k: round(statistics.median(v), 4) for k, v in times.items()}
-                    lo[call] = {k: round(min(v), 4) for k, v in times.items()}
-                    hi[call] = {k: round(max(v), 4) for k, v in times.items()}
+                    _, times = timed(V[call].items())
+                    med[call], lo[call], hi[call] = benchkit.stats(times).values()
                 ctx.planes_index_free(idx)
                 ctx.planes_index_free(idx2)
                 run = {
@@ -233,16 +194,12 @@ def main():
                 }
                 run["meets_required"] = all(med[c]["fused"] < med[c]["unfused"] for c in CALLS)
                 res["runs"].append(run)
-                print(json.dumps(run), file=sys.stderr, flush=True)
+                benchkit.progress(run)
                 del V, d_new, d_base, d_xor, d_planes, d_planes2, d_out, d_out2, r_f, r_u, r_plain
                 torch.cuda.empty_cache()
     res["meets_required"] = all(r["meets_required"] for r in res["runs"])
     ctx.close()
-    text = json.dumps(res, indent=1)
-    print(text)
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as f:
-        f.write(text + "\n")
+    benchkit.write(res, args.out)
 
 
 if __name__ == "__main__":

@@ -16,15 +16,15 @@ REQUIRED: split_to and merge_from reach at least 0.5 of the copy's rate in every
 (compress, decode, range) takes less time than its dense counterpart.
 Recorded, not required: the ratio of the pointer kernels to their parents, the uniform rows end to end, the no-wait compress.
 
-Device events around every call, variants interleaved within each repeat, every variant warmed up first and every result
-checked once.  In front of every timed call, outside its events, a plain copy of 256 MiB between two buffers of the tool's
-own sweeps the 256 MiB Infinity Cache.  Prints one JSON document and writes it to --out."""
+Every result is checked once.  Recipe: tools/benchkit.py, with the cache sweep.  Prints one JSON document and writes it to
+--out."""
 import argparse
 import ctypes as C
-import json
+import functools
 import os
-import statistics
 import sys
+
+import benchkit
 
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 sys.path.insert(0, ROOT)
@@ -32,27 +32,11 @@ sys.path.insert(0, ROOT)
 INPUTS = (("bf16", 2, "normal"), ("fp32", 4, "normal"), ("fp64", 8, "normal"), ("uniform", 2, "uniform"))
 
 
-def make_elems(torch, kind, e, n_bytes, seed):
-    """a CUDA uint8 tensor of n_bytes: standard-normal values (bf16 by truncation of fp32 / fp32 / fp64) or uniform bytes"""
-    g = torch.Generator(device="cuda")
-    g.manual_seed(seed)
-    if kind == "uniform":
-        return torch.randint(0, 256, (n_bytes,), generator=g, device="cuda", dtype=torch.uint8)
-    if e == 8:
-        return torch.randn(n_bytes // 8, generator=g, device="cuda", dtype=torch.float64).view(torch.uint8)
-    x = torch.randn(n_bytes // e, generator=g, device="cuda", dtype=torch.float32)
-    if e == 2:
-        return (x.view(torch.int32) >> 16).to(torch.int16).view(torch.uint8)
-    return x.view(torch.uint8)
-
-
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--mib", default="256,1024")
-    ap.add_argument("--reps", type=int, default=10)
-    ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--seed", type=int, default=7)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "planes", "forms_bench.json"))
+    benchkit.add_args(ap, reps=10, warmup=2, out=os.path.join(ROOT, "profiles", "planes", "forms_bench.json"))
     args = ap.parse_args()
 
     import torch
@@ -64,45 +48,19 @@ def main():
     assert torch.cuda.is_available(), "planes_forms_bench needs the GPU: there is nothing to fall back to"
     ctx = ghf.Context(0)
     L = ghf.lib()
-    res = {"device": torch.cuda.get_device_name(0), "reps": args.reps, "warmup": args.warmup, "seed": args.seed,
-           "lib": ghf.lib_identity(), "unit": "ms (device events), medians", "cache_sweep": "plain 256 MiB copy in front of every timed call",
-           "required": ["split_to and merge_from: at least 0.5 of the rate of ghf_copy_d2d(non_temporal = 1)",
-                        "bf16 / fp32 / fp64: compress_forms < compress_coded, decode_forms < decode_planes, range_forms < range_planes"],
-           "rows": []}
-
-    flush_src, flush_dst = ctx.empty_u8(256 << 20), ctx.empty_u8(256 << 20)
-    flush_src.zero_()
-
-    def ok(rc):
-        assert rc == 0, rc
-
-    def timed(variants):
-        for _ in range(args.warmup):
-            for _, fn in variants:
-                fn()
-        ctx.sync()
-        times = {name: [] for name, _ in variants}
-        for _ in range(args.reps):
-            for name, fn in variants:
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                ok(L.ghf_copy_d2d(ctx.h, flush_dst.data_ptr(), flush_src.data_ptr(), flush_src.numel(), 0))
-                e0.record()
-                fn()
-                e1.record()
-                e1.synchronize()
-                times[name].append(e0.elapsed_time(e1))
-        ctx.sync()
-        return times
-
-    def stats(times):
-        return ({k: round(statistics.median(v), 4) for k, v in times.items()}, {k: round(min(v), 4) for k, v in times.items()},
-                {k: round(max(v), 4) for k, v in times.items()})
+    res = benchkit.envelope(torch, ghf, args, "ms (device events), medians")
+    res.update({"seed": args.seed, "cache_sweep": benchkit.CACHE_SWEEP,
+                "required": ["split_to and merge_from: at least 0.5 of the rate of ghf_copy_d2d(non_temporal = 1)",
+                             "bf16 / fp32 / fp64: compress_forms < compress_coded, decode_forms < decode_planes, range_forms < range_planes"],
+                "rows": []})
+    ok = benchkit.ok
+    timed = functools.partial(benchkit.timed, reps=args.reps, warmup=args.warmup, sync=ctx.sync, sweep=benchkit.cache_sweep(ctx))
 
     for mib in [int(x) for x in args.mib.split(",")]:
         nbytes = mib << 20
         for name, e, kind in INPUTS:
             n = nbytes // e
-            d_x = make_elems(torch, kind, e, nbytes, args.seed)
+            d_x = benchkit.uniform_bytes(torch, nbytes, args.seed) if kind == "uniform" else benchkit.normal_elems(torch, nbytes, e, args.seed)
             x = d_x.data_ptr()
 
             # ---- the kernels, on the parents' own addresses
@@ -125,7 +83,7 @@ def main():
             ctx.sync()  # checked once: split_to writes what the parent writes, merge_from gives the tensor back
             assert torch.equal(d_planes, want_planes) and torch.equal(d_back, d_x), (mib, name)
             del want_planes
-            k_med, k_lo, k_hi = stats(timed(K))
+            k_med, k_lo, k_hi = benchkit.stats(timed(K)[1]).values()
             del K, d_planes, d_back, d_copy
             torch.cuda.empty_cache()
 
@@ -173,7 +131,7 @@ def main():
             want_part = d_x[first * e : (first + count) * e]
             assert torch.equal(d_out, d_x) and torch.equal(d_out2, d_x), (mib, name)
             assert torch.equal(d_part, want_part) and torch.equal(d_part2, want_part), (mib, name)
-            med, lo, hi = stats(timed(V))
+            med, lo, hi = benchkit.stats(timed(V)[1]).values()
             assert h_raw.value == raw and h_sparse.value == 0
             med.update(k_med), lo.update(k_lo), hi.update(k_hi)
             row = {"mib": mib, "input": name, "elem_bytes": e, "n_elems": n, "raw_planes": raw, "median_ms": med, "min_ms": lo, "max_ms": hi,
@@ -189,18 +147,14 @@ def main():
             if kind == "normal":
                 row["meets_required_end_to_end"] = all(row["forms_over_dense"][k] < 1.0 for k in ("compress", "decode", "range"))
             res["rows"].append(row)
-            print(json.dumps(row), file=sys.stderr, flush=True)
+            benchkit.progress(row)
             ctx.planes_index_free(idx_f)
             ctx.planes_index_free(idx_d)
             del V, d_x, d_out, d_out2, d_part, d_part2, r_f, r_d
             torch.cuda.empty_cache()
     res["meets_required"] = all(r["meets_required_kernels"] and r.get("meets_required_end_to_end", True) for r in res["rows"])
     ctx.close()
-    text = json.dumps(res, indent=1)
-    print(text)
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as f:
-        f.write(text + "\n")
+    benchkit.write(res, args.out)
 
 
 if __name__ == "__main__":

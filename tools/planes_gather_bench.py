@@ -12,16 +12,15 @@ REQUIRED: at 1024 rows of 4096 elements the gather takes less time than the per-
 Recorded, not required: the gather against whole decode + index_select, the row count at which the two cross (between
 the measured row counts that bracket it), and the output rate in GB/s.
 
-The recipe of tools/planes_range_bench.py: device events around every variant, variants interleaved within each repeat,
-medians of ten after two warm-ups, every variant checked once against index_select of the input, and a plain copy of
-256 MiB in front of every timed call, outside its events, to sweep the 256 MiB Infinity Cache.  Prints one JSON document and
-writes it to --out."""
+Every variant is checked once against index_select of the input.  Recipe: tools/benchkit.py, with the cache sweep.  Prints
+one JSON document and writes it to --out."""
 import argparse
 import ctypes as C
-import json
+import functools
 import os
-import statistics
 import sys
+
+import benchkit
 
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 sys.path.insert(0, ROOT)
@@ -30,23 +29,12 @@ CASES = [(64, 4096), (1024, 4096), (16384, 4096), (1024, 128)]  # (rows, element
 REQUIRED = (1024, 4096)
 
 
-def make_normal(torch, n_bytes, e, seed):
-    g = torch.Generator(device="cuda")
-    g.manual_seed(seed)
-    x = torch.randn(n_bytes // e, generator=g, device="cuda", dtype=torch.float32)
-    if e == 4:
-        return x.view(torch.uint8)
-    return (x.view(torch.int32) >> 16).to(torch.int16).view(torch.uint8)  # bf16 by truncation
-
-
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--mib", type=int, default=256)
     ap.add_argument("--widths", default="2,4")
-    ap.add_argument("--reps", type=int, default=10)
-    ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--seed", type=int, default=7)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "planes", "gather_bench.json"))
+    benchkit.add_args(ap, reps=10, warmup=2, out=os.path.join(ROOT, "profiles", "planes", "gather_bench.json"))
     args = ap.parse_args()
 
     import torch
@@ -58,36 +46,15 @@ def main():
     assert torch.cuda.is_available(), "planes_gather_bench needs the GPU: there is nothing to fall back to"
     ctx = ghf.Context(0)
     L = ghf.lib()
-    res = {"device": torch.cuda.get_device_name(0), "reps": args.reps, "warmup": args.warmup, "seed": args.seed,
-           "lib": ghf.lib_identity(), "unit": "ms (device events), medians", "data": "standard-normal, GHF_RAW_AUTO",
-           "cache_sweep": "plain 256 MiB copy in front of every timed call", "required": "gather < range_loop at %d rows of %d" % REQUIRED,
-           "runs": []}
-
-    flush_src, flush_dst = ctx.empty_u8(256 << 20), ctx.empty_u8(256 << 20)
-    flush_src.zero_()
-
-    def timed(variants):
-        for _ in range(args.warmup):
-            for _, fn in variants:
-                fn()
-        ctx.sync()
-        times = {name: [] for name, _ in variants}
-        for _ in range(args.reps):
-            for name, fn in variants:
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                assert L.ghf_copy_d2d(ctx.h, flush_dst.data_ptr(), flush_src.data_ptr(), flush_src.numel(), 0) == 0
-                e0.record()
-                fn()
-                e1.record()
-                e1.synchronize()
-                times[name].append(e0.elapsed_time(e1))
-        ctx.sync()
-        return {k: statistics.median(v) for k, v in times.items()}, times
+    res = benchkit.envelope(torch, ghf, args, "ms (device events), medians")
+    res.update({"seed": args.seed, "data": "standard-normal, GHF_RAW_AUTO", "cache_sweep": benchkit.CACHE_SWEEP,
+                "required": "gather < range_loop at %d rows of %d" % REQUIRED, "runs": []})
+    timed = functools.partial(benchkit.timed, reps=args.reps, warmup=args.warmup, sync=ctx.sync, sweep=benchkit.cache_sweep(ctx))
 
     nbytes = args.mib << 20
     for e in [int(x) for x in args.widths.split(",")]:
         n = nbytes // e
-        d_in = make_normal(torch, nbytes, e, args.seed)
+        d_in = benchkit.normal_elems(torch, nbytes, e, args.seed)
         r = ctx.compress_planes_forms(d_in, e, raw_planes=ghf.RAW_AUTO, sparse_planes=0, indexes=True)
         ctx.sync()
         raw = r["raw_planes"]
@@ -148,16 +115,14 @@ def main():
             assert torch.equal(sel[0].view(-1), want), (e, n_rows, row_elems, "whole_select")
             med, times = timed([("gather", v_gather), ("range_loop", v_loop), ("whole_select", v_whole)])
             case = {"rows": n_rows, "row_elems": row_elems, "out_bytes": n_rows * row_bytes,
-                    "median_ms": {k: round(v, 4) for k, v in med.items()},
-                    "min_ms": {k: round(min(v), 4) for k, v in times.items()},
-                    "max_ms": {k: round(max(v), 4) for k, v in times.items()},
+                    **benchkit.stats(times),
                     "loop_over_gather": round(med["range_loop"] / med["gather"], 2),
                     "whole_select_over_gather": round(med["whole_select"] / med["gather"], 3),
                     "gather_gb_per_s": round(n_rows * row_bytes / med["gather"] / 1e6, 3)}
             if (n_rows, row_elems) == REQUIRED:
                 case["meets_required"] = med["gather"] < med["range_loop"]
             run["cases"].append(case)
-            print(json.dumps(case), file=sys.stderr, flush=True)
+            benchkit.progress(case)
             del d_out, want, d_index
         # where the gather stops being faster than whole decode + index_select: between the two measured row counts of 4096
         # elements that bracket it, both times taken as straight lines in the row count (null: no crossing in the measured span)
@@ -174,11 +139,7 @@ def main():
         torch.cuda.empty_cache()
     res["meets_required"] = all(c.get("meets_required", True) for run in res["runs"] for c in run["cases"])
     ctx.close()
-    text = json.dumps(res, indent=1)
-    print(text)
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as f:
-        f.write(text + "\n")
+    benchkit.write(res, args.out)
 
 
 if __name__ == "__main__":

@@ -17,15 +17,14 @@ tables on the host for the range calls and as device images for the gather; rand
 REQUIRED: in every row of the table, 1024 rows of 4096 elements through forms_gather take less time than range_loop in the
 same run.  Everything else is recorded.  Every variant is checked once against index_select of `new`.
 
-The recipe of tools/planes_gather_bench.py: device events around every variant, variants interleaved within each repeat,
-medians after warm-ups, and a plain copy of 256 MiB in front of every timed call, outside its events, to sweep the 256 MiB
-Infinity Cache.  Prints one JSON document and writes it to --out."""
+Recipe: tools/benchkit.py, with the cache sweep.  Prints one JSON document and writes it to --out."""
 import argparse
 import ctypes as C
-import json
+import functools
 import os
-import statistics
 import sys
+
+import benchkit
 
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 sys.path.insert(0, ROOT)
@@ -35,32 +34,13 @@ REQUIRED = (1024, 4096)
 LOOP_MAX_ROWS = 1024
 
 
-def as_elements(torch, x, e):
-    """fp32 values as the bytes of the element type: fp32, or bf16 by truncation"""
-    if e == 4:
-        return x.view(torch.uint8)
-    return (x.view(torch.int32) >> 16).to(torch.int16).view(torch.uint8)
-
-
-def make_pair(torch, n, e, step, seed):
-    g = torch.Generator(device="cuda")
-    g.manual_seed(seed)
-    w = torch.randn(n, generator=g, device="cuda", dtype=torch.float32)
-    g.manual_seed(seed + 1)
-    d = torch.randn(n, generator=g, device="cuda", dtype=torch.float32)
-    new = as_elements(torch, w + step * d, e).clone()
-    return new, as_elements(torch, w, e).clone()
-
-
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--mib", type=int, default=256)
     ap.add_argument("--widths", default="2,4")
     ap.add_argument("--steps", default="1e-3,1e-5")
-    ap.add_argument("--reps", type=int, default=10)
-    ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--seed", type=int, default=7)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "planes", "gather_forms_bench.json"))
+    benchkit.add_args(ap, reps=10, warmup=2, out=os.path.join(ROOT, "profiles", "planes", "gather_forms_bench.json"))
     args = ap.parse_args()
 
     import torch
@@ -72,32 +52,11 @@ def main():
     assert torch.cuda.is_available(), "planes_gather_forms_bench needs the GPU: there is nothing to fall back to"
     ctx = ghf.Context(0)
     L = ghf.lib()
-    res = {"device": torch.cuda.get_device_name(0), "reps": args.reps, "warmup": args.warmup, "seed": args.seed,
-           "lib": ghf.lib_identity(), "unit": "ms (device events), medians",
-           "data": "standard-normal against itself after a step; GHF_RAW_AUTO | GHF_SPARSE_AUTO against the base",
-           "cache_sweep": "plain 256 MiB copy in front of every timed call",
-           "required": "forms_gather < range_loop at %d rows of %d, in every run" % REQUIRED, "runs": []}
-
-    flush_src, flush_dst = ctx.empty_u8(256 << 20), ctx.empty_u8(256 << 20)
-    flush_src.zero_()
-
-    def timed(variants):
-        for _ in range(args.warmup):
-            for _, fn in variants:
-                fn()
-        ctx.sync()
-        times = {name: [] for name, _ in variants}
-        for _ in range(args.reps):
-            for name, fn in variants:
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                assert L.ghf_copy_d2d(ctx.h, flush_dst.data_ptr(), flush_src.data_ptr(), flush_src.numel(), 0) == 0
-                e0.record()
-                fn()
-                e1.record()
-                e1.synchronize()
-                times[name].append(e0.elapsed_time(e1))
-        ctx.sync()
-        return {k: statistics.median(v) for k, v in times.items()}, times
+    res = benchkit.envelope(torch, ghf, args, "ms (device events), medians")
+    res.update({"seed": args.seed, "data": "standard-normal against itself after a step; GHF_RAW_AUTO | GHF_SPARSE_AUTO against the base",
+                "cache_sweep": benchkit.CACHE_SWEEP, "required": "forms_gather < range_loop at %d rows of %d, in every run" % REQUIRED,
+                "runs": []})
+    timed = functools.partial(benchkit.timed, reps=args.reps, warmup=args.warmup, sync=ctx.sync, sweep=benchkit.cache_sweep(ctx))
 
     def stored(r, e):
         """the arrays of a compress_planes_forms result as the decode calls take them; seek tables through the host and back"""
@@ -121,7 +80,7 @@ def main():
     for e in [int(x) for x in args.widths.split(",")]:
         for step in [float(x) for x in args.steps.split(",")]:
             n = nbytes // e
-            d_new, d_base = make_pair(torch, n, e, step, args.seed)
+            d_new, d_base = benchkit.normal_pair_reseeded(torch, nbytes, e, step, args.seed)
             r = ctx.compress_planes_forms(d_new, e, raw_planes=ghf.RAW_AUTO, sparse_planes=ghf.SPARSE_AUTO, d_base=d_base, indexes=True,
                                           ranks=True)
             ctx.sync()
@@ -201,9 +160,7 @@ def main():
                 assert torch.equal(sel[0].view(-1), want), (e, step, n_rows, row_elems, "whole_select")
                 med, times = timed(variants + [("whole_select", v_whole)])
                 case = {"rows": n_rows, "row_elems": row_elems, "out_bytes": n_rows * row_bytes,
-                        "median_ms": {k: round(v, 4) for k, v in med.items()},
-                        "min_ms": {k: round(min(v), 4) for k, v in times.items()},
-                        "max_ms": {k: round(max(v), 4) for k, v in times.items()},
+                        **benchkit.stats(times),
                         "loop_over_forms_gather": round(med["range_loop"] / med["forms_gather"], 2) if with_loop else None,
                         "whole_select_over_forms_gather": round(med["whole_select"] / med["forms_gather"], 3),
                         "forms_gather_over_self_gather": round(med["forms_gather"] / med["self_gather"], 3),
@@ -212,7 +169,7 @@ def main():
                 if (n_rows, row_elems) == REQUIRED:
                     case["meets_required"] = med["forms_gather"] < med["range_loop"]
                 run["cases"].append(case)
-                print(json.dumps(case), file=sys.stderr, flush=True)
+                benchkit.progress(case)
                 del d_out, want, d_index
             res["runs"].append(run)
             ctx.planes_index_free(r["indexes"])
@@ -221,11 +178,7 @@ def main():
             torch.cuda.empty_cache()
     res["meets_required"] = all(c.get("meets_required", True) for run in res["runs"] for c in run["cases"])
     ctx.close()
-    text = json.dumps(res, indent=1)
-    print(text)
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as f:
-        f.write(text + "\n")
+    benchkit.write(res, args.out)
 
 
 if __name__ == "__main__":

@@ -10,40 +10,26 @@ standard-normal values (bf16 = the upper half of fp32, fp32, fp64):
   d  what the call replaces: ghf_decode_range per plane into 16-byte aligned planes (the byte path of the decoder at
      skew 5) followed by ghf_planes_merge, for the skew-5 eighth
 
-Built like tools/planes_bench.py: device events around every call, variants interleaved within each repeat, every variant
-warmed up first and checked once against the input's slice, and a plain copy of 256 MiB in front of every timed call,
-outside its events, to sweep the 256 MiB Infinity Cache.  Prints one JSON document and writes it to --out."""
+Every variant is checked once against the input's slice.  Recipe: tools/benchkit.py, with the cache sweep.  Prints one JSON
+document and writes it to --out."""
 import argparse
 import ctypes as C
-import json
+import functools
 import os
-import statistics
 import sys
+
+import benchkit
 
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 sys.path.insert(0, ROOT)
-
-
-def make_normal(torch, n_bytes, e, seed):
-    g = torch.Generator(device="cuda")
-    g.manual_seed(seed)
-    n = n_bytes // e
-    if e == 8:
-        return torch.randn(n, generator=g, device="cuda", dtype=torch.float64).view(torch.uint8)
-    x = torch.randn(n, generator=g, device="cuda", dtype=torch.float32)
-    if e == 4:
-        return x.view(torch.uint8)
-    return (x.view(torch.int32) >> 16).to(torch.int16).view(torch.uint8)  # bf16 by truncation
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--mib", default="256,1024")
     ap.add_argument("--widths", default="2,4,8")
-    ap.add_argument("--reps", type=int, default=10)
-    ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--seed", type=int, default=7)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "planes", "range_bench.json"))
+    benchkit.add_args(ap, reps=10, warmup=2, out=os.path.join(ROOT, "profiles", "planes", "range_bench.json"))
     args = ap.parse_args()
 
     import torch
@@ -55,36 +41,16 @@ def main():
     assert torch.cuda.is_available(), "planes_range_bench needs the GPU: there is nothing to fall back to"
     ctx = ghf.Context(0)
     L = ghf.lib()
-    res = {"device": torch.cuda.get_device_name(0), "reps": args.reps, "warmup": args.warmup, "seed": args.seed,
-           "lib": ghf.lib_identity(), "unit": "ms (device events), medians", "data": "standard-normal",
-           "cache_sweep": "plain 256 MiB copy in front of every timed call", "required_fraction_of_copy": 0.5, "runs": []}
-
-    flush_src, flush_dst = ctx.empty_u8(256 << 20), ctx.empty_u8(256 << 20)
-    flush_src.zero_()
-
-    def timed(variants):
-        for _ in range(args.warmup):
-            for _, fn in variants:
-                fn()
-        ctx.sync()
-        times = {name: [] for name, _ in variants}
-        for _ in range(args.reps):
-            for name, fn in variants:
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                assert L.ghf_copy_d2d(ctx.h, flush_dst.data_ptr(), flush_src.data_ptr(), flush_src.numel(), 0) == 0
-                e0.record()
-                fn()
-                e1.record()
-                e1.synchronize()
-                times[name].append(e0.elapsed_time(e1))
-        ctx.sync()
-        return {k: statistics.median(v) for k, v in times.items()}, times
+    res = benchkit.envelope(torch, ghf, args, "ms (device events), medians")
+    res.update({"seed": args.seed, "data": "standard-normal", "cache_sweep": benchkit.CACHE_SWEEP, "required_fraction_of_copy": 0.5,
+                "runs": []})
+    timed = functools.partial(benchkit.timed, reps=args.reps, warmup=args.warmup, sync=ctx.sync, sweep=benchkit.cache_sweep(ctx))
 
     for mib in [int(x) for x in args.mib.split(",")]:
         nbytes = mib << 20
         for e in [int(x) for x in args.widths.split(",")]:
             n = nbytes // e
-            d_in = make_normal(torch, nbytes, e, args.seed)
+            d_in = benchkit.normal_elems(torch, nbytes, e, args.seed)
             d_back = ctx.empty_u8(nbytes)
             d_copy = ctx.empty_u8(nbytes)
 
@@ -185,9 +151,7 @@ def main():
             parts = [k for k in med_b if k.startswith("range_") and k != "range_whole_idx"]
             run = {
                 "mib": mib, "elem_bytes": e, "n_elems": n, "merge_elems": m, "ranges": {k: list(v) for k, v in ranges.items()},
-                "median_ms": {k: round(v, 4) for k, v in med.items()},
-                "min_ms": {k: round(min(v), 4) for k, v in times.items()},
-                "max_ms": {k: round(max(v), 4) for k, v in times.items()},
+                **benchkit.stats(times),
                 "tb_per_s": {k: round(2 * m * e / med[k] / 1e9, 3) for k in med_a},  # read + write
                 "fraction_of_copy": {k: round(med["copy_nt"] / med[k], 4) for k in med_a if k != "copy_nt"},
                 "whole_range_over_decode_planes": round(med["range_whole_idx"] / whole, 4),
@@ -199,16 +163,12 @@ def main():
             run["meets_b"] = run["whole_range_over_decode_planes"] <= run["decode_planes_max_over_min"]
             run["meets_c"] = all(med[k] < whole for k in parts) and all(v < 1 for v in run["eighth_s5_over_alternative"].values())
             res["runs"].append(run)
-            print(json.dumps(run), file=sys.stderr, flush=True)
+            benchkit.progress(run)
             ctx.planes_index_free(idx)
             del d_in, d_planes, d_back, r, d_tables
             torch.cuda.empty_cache()
     ctx.close()
-    text = json.dumps(res, indent=1)
-    print(text)
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as f:
-        f.write(text + "\n")
+    benchkit.write(res, args.out)
 
 
 if __name__ == "__main__":

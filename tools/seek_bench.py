@@ -9,13 +9,13 @@ paths a persisted .crs2 can take.  On `--mib` MiB of uniform and of zipf bytes:
   plus  b_expand (ghf_seek_expand alone), d_live (the same range from a live side-car) and d_coaligned (output pointer
         congruent to `first` modulo 16, so that K7 stores 16 bytes at a time).
 
-Device events around every call, variants interleaved within each repeat, every variant warmed up first and checked
-against the input once.  Prints one JSON document; --out also writes it to a file."""
+Every variant is checked against the input once.  Recipe: tools/benchkit.py, without the cache sweep.  Prints one JSON
+document; --out also writes it to a file."""
 import argparse
-import json
 import os
-import statistics
 import sys
+
+import benchkit
 
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 sys.path.insert(0, ROOT)
@@ -24,10 +24,8 @@ sys.path.insert(0, ROOT)
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--mib", type=int, default=256)
-    ap.add_argument("--reps", type=int, default=30)
-    ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--kinds", default="uniform,zipf")
-    ap.add_argument("--out", default=None)
+    benchkit.add_args(ap, reps=30, warmup=3, out=None)
     args = ap.parse_args()
 
     import importlib
@@ -42,8 +40,8 @@ def main():
     assert torch.cuda.is_available(), "seek_bench needs the GPU: there is nothing to fall back to"
     ctx = ghf.Context(0)
     n = args.mib << 20
-    res = {"device": torch.cuda.get_device_name(0), "mib": args.mib, "reps": args.reps, "warmup": args.warmup,
-           "lib": ghf.lib_identity(), "unit": "ms (device events)", "kinds": {}}
+    res = benchkit.envelope(torch, ghf, args, "ms (device events)")
+    res.update({"mib": args.mib, "kinds": {}})
     for kind in args.kinds.split(","):
         d_in = synth.make(torch, kind, n, offset=0, device="cuda")
         idx = ctx.index_alloc(n)
@@ -96,28 +94,12 @@ def main():
                 assert torch.equal(r_co, d_in[first : first + count]), (kind, name)
             elif name != "b_expand":
                 assert torch.equal(r_out, d_in[first : first + count]), (kind, name)
-        for _ in range(args.warmup):
-            for _, fn in variants:
-                fn()
-        ctx.sync()
-        times = {name: [] for name, _ in variants}
-        for _ in range(args.reps):
-            for name, fn in variants:
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-                fn()
-                e1.record()
-                e1.synchronize()
-                times[name].append(e0.elapsed_time(e1))
-        ctx.sync()
-        med = {k: statistics.median(v) for k, v in times.items()}
+        med, times = benchkit.timed(variants, args.reps, args.warmup, ctx.sync)
         res["kinds"][kind] = {
             "stream_bytes": nb,
             "table_bytes": int(d_table.numel()),
             "range": {"first": first, "count": count},
-            "median_ms": {k: round(v, 4) for k, v in med.items()},
-            "min_ms": {k: round(min(v), 4) for k, v in times.items()},
-            "max_ms": {k: round(max(v), 4) for k, v in times.items()},
+            **benchkit.stats(times),
             "ratios": {"b_over_a": round(med["b"] / med["a"], 3), "c_over_b": round(med["c"] / med["b"], 3),
                        "d_over_a": round(med["d"] / med["a"], 3)},
             "b_lt_c": med["b"] < med["c"],
@@ -127,12 +109,7 @@ def main():
         ctx.index_free(idx2)
         del d_in, d_stream, d_out, r_buf
     ctx.close()
-    text = json.dumps(res, indent=1)
-    print(text)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            f.write(text + "\n")
+    benchkit.write(res, args.out)
 
 
 if __name__ == "__main__":

@@ -17,57 +17,26 @@ split / merge kernels and the plane calls built on them.  In one run:
 REQUIRED: split and merge at 1 % non-zero reach at least 0.5 of the copy's rate at every size.
 Recorded, not required: the uniform rows and everything end to end.
 
-Device events around every call, variants interleaved within each repeat, every variant warmed up first and every result
-checked once.  In front of every timed call, outside its events, a plain copy of 256 MiB between two buffers of the tool's
-own sweeps the 256 MiB Infinity Cache.  Prints one JSON document and writes it to --out."""
+Every result is checked once.  Recipe: tools/benchkit.py, with the cache sweep.  Prints one JSON document and writes it to
+--out."""
 import argparse
 import ctypes as C
-import json
+import functools
 import os
-import statistics
 import sys
+
+import benchkit
 
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 sys.path.insert(0, ROOT)
-
-
-def make_bytes(torch, kind, n, seed):
-    """uniform: every byte value alike (255/256 non-zero); 1pct: one byte in a hundred non-zero, its value 1 .. 255"""
-    g = torch.Generator(device="cuda")
-    g.manual_seed(seed)
-    x = torch.randint(0, 256, (n,), generator=g, device="cuda", dtype=torch.uint8)
-    if kind == "uniform":
-        return x
-    keep = torch.randint(0, 100, (n,), generator=g, device="cuda", dtype=torch.uint8) == 0
-    return x.clamp_(min=1) * keep
-
-
-def as_elems(torch, x, e):
-    """float values as a CUDA uint8 tensor: bf16 by truncation of fp32 / fp32"""
-    if e == 2:
-        return (x.view(torch.int32) >> 16).to(torch.int16).view(torch.uint8)
-    return x.view(torch.uint8)
-
-
-def make_pair(torch, step, n_bytes, e, seed):
-    """(new, base): standard-normal values and the same after a step of relative size `step`; step None: new is base"""
-    g = torch.Generator(device="cuda")
-    g.manual_seed(seed)
-    w = torch.randn(n_bytes // e, generator=g, device="cuda", dtype=torch.float32)
-    base = as_elems(torch, w, e)
-    if step is None:
-        return base.clone(), base
-    return as_elems(torch, w + step * torch.randn(n_bytes // e, generator=g, device="cuda", dtype=torch.float32), e), base
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--mib", default="256,1024")
     ap.add_argument("--e2e-mib", type=int, default=256)
-    ap.add_argument("--reps", type=int, default=10)
-    ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--seed", type=int, default=7)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "planes", "sparse_bench.json"))
+    benchkit.add_args(ap, reps=10, warmup=2, out=os.path.join(ROOT, "profiles", "planes", "sparse_bench.json"))
     args = ap.parse_args()
 
     import torch
@@ -79,46 +48,21 @@ def main():
     assert torch.cuda.is_available(), "sparse_bench needs the GPU: there is nothing to fall back to"
     ctx = ghf.Context(0)
     L = ghf.lib()
-    res = {"device": torch.cuda.get_device_name(0), "reps": args.reps, "warmup": args.warmup, "seed": args.seed,
-           "lib": ghf.lib_identity(), "unit": "ms (device events), medians", "cache_sweep": "plain 256 MiB copy in front of every timed call",
-           "traffic": {"split": "2 n + n / 8 + n_vals", "merge": "2 * n / 8 + n_vals + n", "copy_nt": "2 n"},
-           "required": ["split and merge at 1 % non-zero bytes: at least 0.5 of the rate of ghf_copy_d2d(non_temporal = 1)"],
-           "kernels": [], "end_to_end": []}
-
-    flush_src, flush_dst = ctx.empty_u8(256 << 20), ctx.empty_u8(256 << 20)
-    flush_src.zero_()
-
-    def ok(rc):
-        assert rc == 0, rc
-
-    def timed(variants):
-        for _ in range(args.warmup):
-            for _, fn in variants:
-                fn()
-        ctx.sync()
-        times = {name: [] for name, _ in variants}
-        for _ in range(args.reps):
-            for name, fn in variants:
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                ok(L.ghf_copy_d2d(ctx.h, flush_dst.data_ptr(), flush_src.data_ptr(), flush_src.numel(), 0))
-                e0.record()
-                fn()
-                e1.record()
-                e1.synchronize()
-                times[name].append(e0.elapsed_time(e1))
-        ctx.sync()
-        return times
-
-    def stats(times):
-        return ({k: round(statistics.median(v), 4) for k, v in times.items()}, {k: round(min(v), 4) for k, v in times.items()},
-                {k: round(max(v), 4) for k, v in times.items()})
+    res = benchkit.envelope(torch, ghf, args, "ms (device events), medians")
+    res.update({"seed": args.seed, "cache_sweep": benchkit.CACHE_SWEEP,
+                "traffic": {"split": "2 n + n / 8 + n_vals", "merge": "2 * n / 8 + n_vals + n", "copy_nt": "2 n"},
+                "required": ["split and merge at 1 % non-zero bytes: at least 0.5 of the rate of ghf_copy_d2d(non_temporal = 1)"],
+                "kernels": [], "end_to_end": []})
+    ok = benchkit.ok
+    timed = functools.partial(benchkit.timed, reps=args.reps, warmup=args.warmup, sync=ctx.sync, sweep=benchkit.cache_sweep(ctx))
 
     # ---- the kernels
     for mib in [int(x) for x in args.mib.split(",")]:
         n = mib << 20
         mb = ghf.sparse_mask_bytes(n)
-        for kind in ("1pct", "uniform"):
-            d_x = make_bytes(torch, kind, n, args.seed)
+        # uniform: 255/256 non-zero; 1pct: one byte in a hundred non-zero
+        for kind, make_bytes in (("1pct", benchkit.sparse_bytes_1pct), ("uniform", benchkit.uniform_bytes)):
+            d_x = make_bytes(torch, n, args.seed)
             nv = int(torch.count_nonzero(d_x).item())
             d_mask, d_vals, d_out, d_copy = ctx.empty_u8(mb), ctx.empty_u8(nv), ctx.empty_u8(n), ctx.empty_u8(n)
             d_count = torch.zeros(1, dtype=torch.int64, device="cuda")
@@ -131,7 +75,7 @@ def main():
             V[1][1]()
             ctx.sync()  # checked once: the count, the values and the round trip
             assert int(d_count.item()) == nv and torch.equal(d_vals[:nv], d_x[d_x != 0]) and torch.equal(d_out, d_x), (mib, kind)
-            med, lo, hi = stats(timed(V))
+            med, lo, hi = benchkit.stats(timed(V)[1]).values()
             traffic = {"split": 2 * n + mb + nv, "merge": 2 * mb + nv + n, "copy_nt": 2 * n}
             rate = {k: round(traffic[k] / med[k] / 1e9, 3) for k in med}  # bytes / ms / 1e9 = TB/s
             run = {"mib": mib, "kind": kind, "n": n, "n_vals": nv, "median_ms": med, "min_ms": lo, "max_ms": hi, "traffic_bytes": traffic,
@@ -139,7 +83,7 @@ def main():
             if kind == "1pct":
                 run["meets_required"] = all(r >= 0.5 for r in run["rate_over_copy_nt"].values())
             res["kernels"].append(run)
-            print(json.dumps(run), file=sys.stderr, flush=True)
+            benchkit.progress(run)
             del V, d_x, d_mask, d_vals, d_out, d_copy
             torch.cuda.empty_cache()
 
@@ -148,7 +92,7 @@ def main():
     for e in (2, 4):
         n = nbytes // e
         for step in (1e-3, 1e-5, None):
-            d_new, d_base = make_pair(torch, step, nbytes, e, args.seed)
+            d_new, d_base = benchkit.normal_pair(torch, nbytes, e, step, args.seed)
             p, b = d_new.data_ptr(), d_base.data_ptr()
             slot = ghf.planes_slot_bytes(n)
             d_out, d_out2 = ctx.empty_u8(nbytes), ctx.empty_u8(nbytes)
@@ -182,7 +126,7 @@ def main():
             V[3][1]()
             ctx.sync()  # checked once: both decodes give the new tensor back
             assert torch.equal(d_out, d_new) and torch.equal(d_out2, d_new), (e, step)
-            med, lo, hi = stats(timed(V))
+            med, lo, hi = benchkit.stats(timed(V)[1]).values()
             assert h_chosen.value == chosen and list(h_nv) == n_vals
             run = {"mib": args.e2e_mib, "elem_bytes": e, "step": "identical" if step is None else step, "n_elems": n,
                    "sparse_planes": chosen, "n_vals": n_vals, "median_ms": med, "min_ms": lo, "max_ms": hi,
@@ -190,18 +134,14 @@ def main():
                    "sparse_over_dense": {"compress": round(med["compress_sparse"] / med["compress_dense"], 4),
                                          "decode": round(med["decode_sparse"] / med["decode_dense"], 4)}}
             res["end_to_end"].append(run)
-            print(json.dumps(run), file=sys.stderr, flush=True)
+            benchkit.progress(run)
             ctx.planes_index_free(idx_s)
             ctx.planes_index_free(idx_d)
             del V, d_new, d_base, d_out, d_out2, r_s, r_d
             torch.cuda.empty_cache()
     res["meets_required"] = all(r["meets_required"] for r in res["kernels"] if "meets_required" in r)
     ctx.close()
-    text = json.dumps(res, indent=1)
-    print(text)
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as f:
-        f.write(text + "\n")
+    benchkit.write(res, args.out)
 
 
 if __name__ == "__main__":

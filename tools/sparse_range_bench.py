@@ -10,35 +10,18 @@ values after the step, compressed by ghf_compress_planes_sparse_ranked_delta(GHF
   c  recorded: the same ranges through ghf_decode_planes_range_delta on dense images of the same pair
   d  recorded: ghf_sparse_rank_pack of one plane's mask on its own, and the ranked compress against the plain sparse one
 
-Built like tools/planes_range_bench.py: device events around every call, medians, variants interleaved within each repeat,
-every variant warmed up first and checked once against the tensor's slice, and a plain copy of 256 MiB in front of every
-timed call, outside its events, to sweep the 256 MiB Infinity Cache.  Prints one JSON document and writes it to --out."""
+Every variant is checked once against the tensor's slice.  Recipe: tools/benchkit.py, with the cache sweep.  Prints one JSON
+document and writes it to --out."""
 import argparse
 import ctypes as C
-import json
+import functools
 import os
-import statistics
 import sys
+
+import benchkit
 
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 sys.path.insert(0, ROOT)
-
-
-def as_elements(torch, x, e):
-    """fp32 values as the bytes of the element type: fp32, or bf16 by truncation"""
-    if e == 4:
-        return x.view(torch.uint8)
-    return (x.view(torch.int32) >> 16).to(torch.int16).view(torch.uint8)
-
-
-def make_pair(torch, n, e, step, seed):
-    g = torch.Generator(device="cuda")
-    g.manual_seed(seed)
-    w = torch.randn(n, generator=g, device="cuda", dtype=torch.float32)
-    g.manual_seed(seed + 1)
-    d = torch.randn(n, generator=g, device="cuda", dtype=torch.float32)
-    new = as_elements(torch, w + step * d, e).clone()
-    return new, as_elements(torch, w, e).clone()
 
 
 def main():
@@ -46,10 +29,8 @@ def main():
     ap.add_argument("--mib", default="256,1024")
     ap.add_argument("--widths", default="2,4")
     ap.add_argument("--steps", default="1e-3,1e-5")
-    ap.add_argument("--reps", type=int, default=10)
-    ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--seed", type=int, default=7)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "planes", "sparse_range_bench.json"))
+    benchkit.add_args(ap, reps=10, warmup=2, out=os.path.join(ROOT, "profiles", "planes", "sparse_range_bench.json"))
     args = ap.parse_args()
 
     import torch
@@ -61,31 +42,10 @@ def main():
     assert torch.cuda.is_available(), "sparse_range_bench needs the GPU: there is nothing to fall back to"
     ctx = ghf.Context(0)
     L = ghf.lib()
-    res = {"device": torch.cuda.get_device_name(0), "reps": args.reps, "warmup": args.warmup, "seed": args.seed,
-           "lib": ghf.lib_identity(), "unit": "ms (device events), medians", "data": "standard-normal against itself after a step",
-           "cache_sweep": "plain 256 MiB copy in front of every timed call",
-           "required": "range_eighth_idx and range_eighth_tab below decode_sparse_delta in every row", "runs": []}
-
-    flush_src, flush_dst = ctx.empty_u8(256 << 20), ctx.empty_u8(256 << 20)
-    flush_src.zero_()
-
-    def timed(variants):
-        for _ in range(args.warmup):
-            for _, fn in variants:
-                fn()
-        ctx.sync()
-        times = {name: [] for name, _ in variants}
-        for _ in range(args.reps):
-            for name, fn in variants:
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                assert L.ghf_copy_d2d(ctx.h, flush_dst.data_ptr(), flush_src.data_ptr(), flush_src.numel(), 0) == 0
-                e0.record()
-                fn()
-                e1.record()
-                e1.synchronize()
-                times[name].append(e0.elapsed_time(e1))
-        ctx.sync()
-        return {k: statistics.median(v) for k, v in times.items()}, times
+    res = benchkit.envelope(torch, ghf, args, "ms (device events), medians")
+    res.update({"seed": args.seed, "data": "standard-normal against itself after a step", "cache_sweep": benchkit.CACHE_SWEEP,
+                "required": "range_eighth_idx and range_eighth_tab below decode_sparse_delta in every row", "runs": []})
+    timed = functools.partial(benchkit.timed, reps=args.reps, warmup=args.warmup, sync=ctx.sync, sweep=benchkit.cache_sweep(ctx))
 
     def tables_of(indexes, slots):
         """seek tables through the host and back, as a caller that stored them would have them"""
@@ -108,7 +68,7 @@ def main():
         for e in [int(x) for x in args.widths.split(",")]:
             for step in [float(x) for x in args.steps.split(",")]:
                 n = nbytes // e
-                d_new, d_base = make_pair(torch, n, e, step, args.seed)
+                d_new, d_base = benchkit.normal_pair_reseeded(torch, nbytes, e, step, args.seed)
                 d_back = ctx.empty_u8(nbytes)
 
                 # the stored tensor: images, side-cars, rank tables (brought to the host and parsed), seek tables
@@ -213,30 +173,22 @@ def main():
                     "stored_bytes": sum(sizes), "dense_stored_bytes": sum(d_sizes),
                     "rank_table_bytes": sum(ghf.sparse_rank_bytes(n) for p in range(e) if (chosen >> p) & 1),
                     "ranges": {k: list(v) for k, v in ranges.items()},
-                    "median_ms": {k: round(v, 4) for k, v in med.items()},
-                    "min_ms": {k: round(min(v), 4) for k, v in times.items()},
-                    "max_ms": {k: round(max(v), 4) for k, v in times.items()},
+                    **benchkit.stats(times),
                     "range_over_decode_sparse_delta": {k: round(v / whole, 4) for k, v in med.items() if k.startswith("range_")},
                     "sparse_range_over_dense_range": {k: round(med[k] / med["dense_" + k], 4) for k in med if k.startswith("range_")},
                     "ranked_over_plain_compress": round(med["compress_sparse_ranked_delta"] / med["compress_sparse_delta"], 4),
                 }
                 run["meets_required"] = med["range_eighth_idx"] < whole and med["range_eighth_tab"] < whole
                 res["runs"].append(run)
-                print(json.dumps(run), file=sys.stderr, flush=True)
+                benchkit.progress(run)
                 ctx.planes_index_free(idx)
                 ctx.planes_index_free(pidx)
                 del d_new, d_base, d_back, r, dr, d_tables, d_dtables, shards, d_planes, d_mask, d_out2, d_ranks2
                 torch.cuda.empty_cache()
-                text = json.dumps(res, indent=1)  # kept current row by row: a run that is cut short leaves its finished rows
-                os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-                with open(args.out, "w") as f:
-                    f.write(text + "\n")
+                benchkit.save(res, args.out)  # kept current row by row: a run that is cut short leaves its finished rows
     ctx.close()
     res["meets_required"] = all(run["meets_required"] for run in res["runs"])
-    text = json.dumps(res, indent=1)
-    print(text)
-    with open(args.out, "w") as f:
-        f.write(text + "\n")
+    benchkit.write(res, args.out)
     if not res["meets_required"]:  # the required comparison is the point of the tool: a miss is an error, not a field
         missed = [(r["mib"], r["elem_bytes"], r["step"]) for r in res["runs"] if not r["meets_required"]]
         print("REQUIRED ROW MISSED in %s: the middle eighth is not below decode_sparse_delta" % missed, file=sys.stderr)

@@ -18,16 +18,15 @@ pack call -- which also holds the table launches, so the kernel alone is no slow
 (2) compress_tensor takes less time than today_route.  Everything else is recorded.  The container is checked once: it
 parses, and a decode of it gives the tensor back.
 
-The recipe of tools/planes_gather_forms_bench.py: device events around every variant, variants interleaved within each
-repeat, medians after warm-ups, and a plain copy of 256 MiB in front of every timed call, outside its events, to sweep the
-256 MiB Infinity Cache.  Prints one JSON document and writes it to --out."""
+Recipe: tools/benchkit.py, with the cache sweep.  Prints one JSON document and writes it to --out."""
 import argparse
 import ctypes as C
+import functools
 import importlib
-import json
 import os
-import statistics
 import sys
+
+import benchkit
 
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 sys.path.insert(0, ROOT)
@@ -36,19 +35,11 @@ DATA = [("bf16", 2, None), ("fp32", 4, None), ("fp32_step_1e-5", 4, 1e-5)]
 ROWS, ROW_ELEMS = 1024, 4096
 
 
-def as_elements(torch, x, e):
-    if e == 4:
-        return x.view(torch.uint8)
-    return (x.view(torch.int32) >> 16).to(torch.int16).view(torch.uint8)
-
-
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--mib", default="256,1024")
-    ap.add_argument("--reps", type=int, default=9)
-    ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--seed", type=int, default=7)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "planes", "tensor_bench.json"))
+    benchkit.add_args(ap, reps=9, warmup=2, out=os.path.join(ROOT, "profiles", "planes", "tensor_bench.json"))
     args = ap.parse_args()
 
     import torch
@@ -60,52 +51,32 @@ def main():
     gt = importlib.import_module("golden_huffman_amd.ghf_tensor")
     assert torch.cuda.is_available(), "tensor_bench needs the GPU: there is nothing to fall back to"
     ctx = ghf.Context(0)
-    L = gt.lib()
-    res = {"device": torch.cuda.get_device_name(0), "reps": args.reps, "warmup": args.warmup, "seed": args.seed,
-           "lib": ghf.lib_identity(), "unit": "ms (device events), medians", "cache_sweep": "plain 256 MiB copy in front of every timed call",
-           "required": ["2 * stream region / pack >= 0.5 * the rate of copy_nt", "compress_tensor < today_route"], "runs": []}
-    flush_src, flush_dst = ctx.empty_u8(256 << 20), ctx.empty_u8(256 << 20)
-    flush_src.zero_()
+    res = benchkit.envelope(torch, ghf, args, "ms (device events), medians")
+    res.update({"seed": args.seed, "cache_sweep": benchkit.CACHE_SWEEP,
+                "required": ["2 * stream region / pack >= 0.5 * the rate of copy_nt", "compress_tensor < today_route"], "runs": []})
+    sweep = benchkit.cache_sweep(ctx)
+    opened = []  # what the `open` variant opened and nobody has closed yet
 
-    def timed(variants):
-        """variants: (name, fn, after or None); `after` runs behind the closing event"""
-        for _ in range(args.warmup):
-            for _, fn, after in variants:
-                fn()
-                if after:
-                    after()
-        ctx.sync()
-        times = {name: [] for name, _, _ in variants}
-        for _ in range(args.reps):
-            for name, fn, after in variants:
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                assert L.ghf_copy_d2d(ctx.h, flush_dst.data_ptr(), flush_src.data_ptr(), flush_src.numel(), 0) == 0
-                e0.record()
-                fn()
-                e1.record()
-                e1.synchronize()
-                times[name].append(e0.elapsed_time(e1))
-                if after:
-                    after()
-        ctx.sync()
-        return {k: statistics.median(v) for k, v in times.items()}, times
+    def close_opened():
+        while opened:
+            ctx.sync()
+            opened.pop().close()
+
+    def close_then_sweep():
+        """the close of an opened container stays outside every pair of events: it runs in front of the next sample's sweep"""
+        close_opened()
+        sweep()
+
+    timed = functools.partial(benchkit.timed, reps=args.reps, warmup=args.warmup, sync=ctx.sync, sweep=close_then_sweep)
 
     for mib in [int(x) for x in args.mib.split(",")]:
         for name, e, step in DATA:
             nbytes = mib << 20
             n = nbytes // e
-            g = torch.Generator(device="cuda")
-            g.manual_seed(args.seed)
-            w = torch.randn(n, generator=g, device="cuda", dtype=torch.float32)
-            d_base = None
             if step is None:
-                d_new = as_elements(torch, w, e).clone()
+                d_new, d_base = benchkit.normal_elems(torch, nbytes, e, args.seed), None
             else:
-                g.manual_seed(args.seed + 1)
-                d = torch.randn(n, generator=g, device="cuda", dtype=torch.float32)
-                d_new, d_base = as_elements(torch, w + step * d, e).clone(), as_elements(torch, w, e).clone()
-                del d
-            del w
+                d_new, d_base = benchkit.normal_pair_reseeded(torch, nbytes, e, step, args.seed)
             raw_ask, sparse_ask = ghf.RAW_AUTO, (ghf.SPARSE_AUTO if step is not None else 0)
             flags = gt.DELTA if d_base is not None else 0
             cap = gt.bound(n, e)
@@ -186,14 +157,9 @@ def main():
 
             # the decode side, on the container compress_tensor wrote
             head = d_cont2[: gt.HEAD_BYTES].cpu().numpy()
-            opened = []
 
             def v_open():
                 opened.append(gt.open(ctx, d_cont2, total, head=head))
-
-            def close_opened():
-                ctx.sync()
-                opened.pop().close()
 
             t = gt.open(ctx, d_cont2, total, head=head)
             ctx.sync()
@@ -238,17 +204,16 @@ def main():
                 ctx.sync()
                 assert torch.equal(d_rows, want) and int(d_status.abs().sum().item()) == 0, what
 
-            med, times = timed([("copy_nt", v_copy, None), ("pack", v_pack, None), ("compress_tensor", v_compress, None),
-                                ("today_route", v_today, None), ("forms_alone", v_forms, None), ("open", v_open, close_opened),
-                                ("tensor_decode", v_tdecode, None), ("forms_decode", v_fdecode, None), ("tensor_gather", v_tgather, None),
-                                ("forms_gather", v_fgather, None)])
+            med, times = timed([("copy_nt", v_copy), ("pack", v_pack), ("compress_tensor", v_compress), ("today_route", v_today),
+                                ("forms_alone", v_forms), ("open", v_open), ("tensor_decode", v_tdecode), ("forms_decode", v_fdecode),
+                                ("tensor_gather", v_tgather), ("forms_gather", v_fgather)])
+            close_opened()
             copy_rate = 2 * region / med["copy_nt"] / 1e6
             pack_rate = 2 * region / med["pack"] / 1e6
             run = {"data": name, "mib": mib, "elem_bytes": e, "n_elems": n, "raw_planes": raw, "sparse_planes": sparse,
                    "bytes": {"tensor": nbytes, "container": total, "stream_region": region, "slots_2E": 2 * e * slot},
                    "container_over_tensor": round(total / nbytes, 4), "container_over_slots": round(total / (2 * e * slot), 4),
-                   "median_ms": {k: round(v, 4) for k, v in med.items()}, "min_ms": {k: round(min(v), 4) for k, v in times.items()},
-                   "max_ms": {k: round(max(v), 4) for k, v in times.items()},
+                   **benchkit.stats(times),
                    "copy_nt_gb_per_s": round(copy_rate, 1), "pack_gb_per_s": round(pack_rate, 1), "pack_over_copy_rate": round(pack_rate / copy_rate, 3),
                    "compress_tensor_over_today_route": round(med["compress_tensor"] / med["today_route"], 3),
                    "compress_tensor_over_forms_alone": round(med["compress_tensor"] / med["forms_alone"], 3),
@@ -256,7 +221,7 @@ def main():
                    "tensor_gather_over_forms_gather": round(med["tensor_gather"] / med["forms_gather"], 3),
                    "meets_required": {"pack_rate": pack_rate >= 0.5 * copy_rate, "one_call": med["compress_tensor"] < med["today_route"]}}
             res["runs"].append(run)
-            print(json.dumps(run), file=sys.stderr, flush=True)
+            benchkit.progress(run)
             t.close()
             ctx.planes_index_free(r["indexes"])
             del d_new, d_base, d_cont, d_cont2, d_cont3, r, rt, d_tabs, d_out, d_rows, streams, ranks, c_streams, c_tables, c_ranks, t
@@ -264,11 +229,7 @@ def main():
             torch.cuda.empty_cache()
     res["meets_required"] = all(all(run["meets_required"].values()) for run in res["runs"])
     ctx.close()
-    text = json.dumps(res, indent=1)
-    print(text)
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as f:
-        f.write(text + "\n")
+    benchkit.write(res, args.out)
 
 
 if __name__ == "__main__":
